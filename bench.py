@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """Benchmark of Etude's two hot paths on MI355X: audio-seconds/s transcribed + decoder tokens/s.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run is the headline alone: set-up, W warm-up steps, the K timed steps, and the ONE JSON line (metric, value, ms_per_step, the per-stage
+rates, config, token digests).  --dump-outputs DIR also writes what the last timed step computed to DIR/<name>.npy (dump_outputs()).
+Everything else below -- the stamped roofline stage, the serial event pass, cpu_baseline and the extras -- runs with --full only.
 
 One STEP = ONE PASS OVER THE BATCH north_star NAMES: 64 x 3-minute 44.1 kHz stereo clips (BASELINE.json configs[4]), sharded 64 / N
 per rank -- at N = 8 exactly configs[4], at N = 1 the whole batch on one MI355X ("strong" scaling: the batch is fixed).  Per rank the
@@ -19,7 +23,8 @@ step is infer.py's stage sequence for its clips (etude_amd/pipeline.py):
 --bar-tokens (48) tokens are generated per bar and Bar_EOS does not end a bar: seeded synthetic weights carry no musical EOS statistics,
 so bar lengths would otherwise be an artefact of the seed (the reference's own chain ends in degenerate 400-token bars on these
 weights).  Everything else -- prompt assembly, 4-pair history, truncation to the last 512 prompt tokens, KV reset per bar -- is
-generate()'s.  value = audio seconds taken through the WHOLE chain per wall second, all ranks.  Next to it:
+generate()'s.  value = audio seconds taken through the WHOLE chain per wall second, all ranks.  Next to it (roofline apart from decode_stage,
+cpu_baseline and extras with --full):
   extract_audio_s_per_s / decoder_tokens_per_s   the per-stage rates the metric names
   roofline      the dominant kernel (k_dstep_attn_down) in the TIMED configuration: device-side span of every launch of one extra
                 decode stage with all engines running (etd_decoder_stamp), algorithmic bytes from the library's exact counters;
@@ -36,6 +41,7 @@ timed steps (~130 s: 24 stamped bars, serial event pass, extras incl. the exact-
 everything is allocated, captured and cached by then).  Behind the timed steps the optional parts are sized / shed by the time left: extras.parity_mode (clips 64 -> 32 -> 16 -> 8, then bars), bar_tokens_144 (clips), ragged_bars,
 n8_share, the configs[1..3] extras, the serial pass, the stamped stage 24 -> 8 bars; the CPU baseline goes last.  Only if K full steps + that minimum cannot fit does the batch per step shrink
 (32 / 16 / 8 clips per rank) -- all of it written into config.workload / config.warmup_step.  The K timed steps are always full steps of the stated batch.
+Without --full nothing but the line (and the --dump-outputs files) follows the timed steps, and the plan reserves only that.
 """
 from __future__ import annotations
 
@@ -536,6 +542,56 @@ def bar_tokens_sensitivity(args, dev, pipe, conds, n_clips, bar_tokens, headline
         pipe.force_bar_tokens = old
 
 
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: all files together
+DUMP_JOBS = 256                # jobs whose ids, bar lengths and notes are written: all of them, or a fixed seeded sample of a larger batch (tokens_sha256_all covers every id)
+
+
+def _padded(rows, dtype):
+    """ragged 1-D arrays -> one 2-D array, short rows padded with -1"""
+    out = np.full((len(rows), max((len(r) for r in rows), default=0)), -1, dtype)
+    for i, r in enumerate(rows):
+        out[i, : len(r)] = r
+    return out
+
+
+def _note_rows(key, notes):
+    """NOTE_DTYPE array -> float64 rows (key, onset, offset, pitch, velocity)"""
+    return np.stack([np.full(len(notes), key, np.float64), notes["onset"], notes["offset"], notes["pitch"], notes["velocity"]], 1).reshape(-1, 5)
+
+
+def _sample_rows(a, max_bytes):
+    """`a`, or a fixed seeded sample of its rows (in order) that fits max_bytes"""
+    if a.nbytes <= max_bytes:
+        return a
+    keep = max(1, max_bytes // max(1, a[0].nbytes))
+    a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+    return a if a.nbytes <= max_bytes else a.reshape(-1)[: max_bytes // a.itemsize]
+
+
+def dump_outputs(out_dir: Path, conds, results, notes, clip_ids, n_tuples: int, suffix: str = "") -> None:
+    """--dump-outputs: what one step hands its caller, as out_dir/<name><suffix>.npy -- per clip the extracted notes, the volume contour and the
+    condition bars; per job the generated ids, their bar lengths and the decoded cover notes.  Ids and counts are float32 (exact below 2^24),
+    note times float64; ragged rows are padded with -1.  A job is named by its global index, clip * n_tuples + tuple."""
+    jobs = [clip_ids[j // n_tuples] * n_tuples + j % n_tuples for j in range(len(results))]
+    pick = range(len(results)) if len(results) <= DUMP_JOBS else np.sort(np.random.default_rng(0).choice(len(results), DUMP_JOBS, replace=False))
+    arrays = {
+        "extract_notes": np.concatenate([_note_rows(c, cd.notes) for c, cd in zip(clip_ids, conds)]),
+        "volume": _padded([cd.volume for cd in conds], np.float32),
+        "condition_ids": _padded([cd.bars.ids for cd in conds], np.float32),
+        "condition_bar_offsets": _padded([cd.bars.offsets for cd in conds], np.float32),
+        "job_index": np.asarray([jobs[j] for j in pick], np.float32),
+        "token_ids": _padded([results[j][0] for j in pick], np.float32),
+        "bar_lengths": _padded([results[j][1] for j in pick], np.float32),
+        "cover_notes": np.concatenate([_note_rows(jobs[j], notes[j]) for j in pick]),
+    }
+    out_dir.mkdir(parents=True, exist_ok=True)
+    left = DUMP_MAX_BYTES
+    for i, (name, a) in enumerate(sorted(arrays.items(), key=lambda kv: kv[1].nbytes)):      # smallest first: what they leave goes to the larger ones
+        a = _sample_rows(a, left // (len(arrays) - i) - 1024)                                  # (1 KiB: room for the .npy header)
+        np.save(out_dir / f"{name}{suffix}.npy", a)
+        left -= a.nbytes + 1024
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -567,7 +623,13 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-serial-pass", action="store_true", help="skip the short HIP-event pass (PMC profiling runs: its eager launches would be counted with the step's)")
     ap.add_argument("--no-stamp", action="store_true", help="skip the stamped decode stage (roofline then comes from the serial event pass)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run the stamped roofline stage, the serial event pass, the extras and the CPU baseline "
+                                                         "(the --no-* switches above apply to these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the last timed step computed to DIR/<name>.npy (dump_outputs())")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run is the headline alone: the parts behind these switches (and the serial event pass) run with --full
+        args.no_stamp = args.no_extras = args.no_cpu_baseline = True
 
     # ---- N > 1 without a launcher: start the N ranks ourselves, before anything in this process touches the GPU
     if (args.gpus > 1 or os.environ.get("ETD_FORCE_SPAWN") == "1") and "WORLD_SIZE" not in os.environ:
@@ -690,7 +752,7 @@ def main():
     # What follows the timed steps, in the order it is SHED when the run is late (time_left() below): extras.parity_mode (bars, then clips, then all of it), the extras
     # (configs[1..3], ~12 s), the serial event pass (~4 s), the stamped stage 24 -> 8 bars; the CPU baseline (~25 s) and an 8-bar stamped stage (~2 s) are what the
     # line cannot do without.  The batch per step shrinks only if K full steps + that minimum do not fit.
-    OVERHEAD_S = 34.0            # the minimum: 8 stamped bars + the CPU baseline + JSON + teardown
+    OVERHEAD_S = 34.0 if args.full else 6.0      # the minimum: 8 stamped bars + the CPU baseline + JSON + teardown (plain run: outputs + JSON + teardown)
     if args.warmup > 0:
         tw = time.perf_counter()
         a, b, c_, ntok1 = step()
@@ -701,7 +763,7 @@ def main():
         # full warm-up steps only if they leave room for EVERYTHING that follows the timed steps (24 stamped bars, serial pass, extras incl. the exact-parity pass,
         # CPU baseline: ~90 s); otherwise the warm-up steps shrink first -- they are untimed and everything is allocated, captured and cached after the first one
         FULL_POST_S = 0.27 * t_first + 4.0 + 14.0 + parity_cost(max(1, min(args.parity_clips, 32, clips)), 0, 92.0) + 16.0 + 11.0 + 30.0
-        if since + (rest + args.steps) * t_first + max(OVERHEAD_S, FULL_POST_S if rest > 0 else 0.0) > args.budget_s:
+        if since + (rest + args.steps) * t_first + max(OVERHEAD_S, FULL_POST_S if rest > 0 and args.full else 0.0) > args.budget_s:
             if since + args.steps * t_first + rest * short(t_first) + OVERHEAD_S <= args.budget_s:
                 warm_mode = "first warm-up step full, the others 4 bars per job (W + K full steps exceed the harness budget)"
                 for _ in range(rest):
@@ -802,6 +864,8 @@ def main():
         "cover_notes_per_job": float(np.mean([n.size for n in state["notes"]])), "jobs_gathered": gathered_jobs, "tokens_sha256_rank0": tok_digest, "tokens_sha256_all": tok_digest_all,
         "build_id": _lib.lib().etd_build_id().decode(),
     }
+    if args.dump_outputs:
+        dump_outputs(Path(args.dump_outputs), conds, results, state["notes"], my_clip_ids(clips), len(grid), f"_rank{rank}" if world > 1 else "")
 
     time_left = lambda: args.budget_s - since_process_start()                       # noqa: E731  (the ONE JSON line matters more than its optional parts)
     CPU_RESERVE_S = 30.0 if (rank == 0 and world == 1 and not args.no_cpu_baseline) else 4.0
@@ -876,33 +940,34 @@ def main():
 
     # ---- per-kernel HIP-event breakdown: a SHORT serial pass (4 bars per job, stages and engines one at a time, launches eager with an
     # event pair each -- event records cannot sit inside hipGraph replays).  Indicative: serial durations, not the timed configuration's.
-    try:
-        if args.no_serial_pass:
-            raise RuntimeError("skipped (--no-serial-pass)")
-        if late(CPU_RESERVE_S + 8.0):
-            raise RuntimeError("skipped: the run is close to its harness budget")
-        _lib.prof_reset()
-        _lib.prof_enable(True)
-        torch.cuda.synchronize(dev)
-        with torch.cuda.stream(pipe.ex_streams[0]):
-            pipe.conditions_of(wavs[0], 0, 0)
-        pipe.ex_streams[0].synchronize()
-        pipe.decode_stage(conds, max_bars=4, one_at_a_time=True)
-        torch.cuda.synchronize(dev)
-        _lib.prof_enable(False)
-        prof = _lib.prof_report()
-        result["kernel_ms_serial_pass"] = {"what": "one clip's extract + 4 bars of every decode job, engines one after the other, HIP events around every launch",
-                                           "ms": {k: round(v["ms"], 3) for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["ms"])},
-                                           "launches": {k: v["launches"] for k, v in prof.items()}}
-        p = prof.get("k_dstep_attn_down")
-        if p and p["ms"] > 0:
-            roof["frac_serial"] = round(p["bytes"] / (p["ms"] * 1e-3) / 1e9 / PEAK_HBM_GBS, 4)
-            if "frac" not in roof:
-                roof.update(achieved=round(p["bytes"] / (p["ms"] * 1e-3) / 1e9, 1), frac=roof["frac_serial"], launches=p["launches"], avg_launch_ms=round(p["ms"] / p["launches"], 5),
-                            alg_bytes_per_launch=p["bytes"] / p["launches"], frac_source="serial event pass (no device stamps in this run)")
-    except Exception as e:      # a diagnostics failure must not take the headline down
-        _lib.prof_enable(False)
-        result["kernel_ms_serial_pass"] = {"error": repr(e)}
+    if args.full:
+        try:
+            if args.no_serial_pass:
+                raise RuntimeError("skipped (--no-serial-pass)")
+            if late(CPU_RESERVE_S + 8.0):
+                raise RuntimeError("skipped: the run is close to its harness budget")
+            _lib.prof_reset()
+            _lib.prof_enable(True)
+            torch.cuda.synchronize(dev)
+            with torch.cuda.stream(pipe.ex_streams[0]):
+                pipe.conditions_of(wavs[0], 0, 0)
+            pipe.ex_streams[0].synchronize()
+            pipe.decode_stage(conds, max_bars=4, one_at_a_time=True)
+            torch.cuda.synchronize(dev)
+            _lib.prof_enable(False)
+            prof = _lib.prof_report()
+            result["kernel_ms_serial_pass"] = {"what": "one clip's extract + 4 bars of every decode job, engines one after the other, HIP events around every launch",
+                                               "ms": {k: round(v["ms"], 3) for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["ms"])},
+                                               "launches": {k: v["launches"] for k, v in prof.items()}}
+            p = prof.get("k_dstep_attn_down")
+            if p and p["ms"] > 0:
+                roof["frac_serial"] = round(p["bytes"] / (p["ms"] * 1e-3) / 1e9 / PEAK_HBM_GBS, 4)
+                if "frac" not in roof:
+                    roof.update(achieved=round(p["bytes"] / (p["ms"] * 1e-3) / 1e9, 1), frac=roof["frac_serial"], launches=p["launches"], avg_launch_ms=round(p["ms"] / p["launches"], 5),
+                                alg_bytes_per_launch=p["bytes"] / p["launches"], frac_source="serial event pass (no device stamps in this run)")
+        except Exception as e:      # a diagnostics failure must not take the headline down
+            _lib.prof_enable(False)
+            result["kernel_ms_serial_pass"] = {"error": repr(e)}
     if batch64:
         result.setdefault("extras", {})["batch64"] = batch64
 

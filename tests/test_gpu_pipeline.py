@@ -108,7 +108,7 @@ def _no_errors(node, path="result"):
 def test_bench_line_small_configuration():
     """bench.py end to end on a small batch: contract keys, roofline / cpu_baseline objects, no silent {"error": ...} in any extra,
     strong-scaling label, device stamps present and consistent with the exact byte counters"""
-    d = _run_bench(["--batch-clips", "2", "--attr-grid", "3", "--seconds", "24", "--steps", "1", "--warmup", "1"])
+    d = _run_bench(["--batch-clips", "2", "--attr-grid", "3", "--seconds", "24", "--steps", "1", "--warmup", "1", "--full"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
               "roofline", "cpu_baseline", "extras", "tokens_sha256_rank0"):
         assert k in d, k
@@ -133,3 +133,23 @@ def test_bench_spawned_single_rank_uses_the_launcher_and_rccl():
     d = _run_bench(["--gpus", "1", "--batch-clips", "1", "--attr-grid", "2", "--seconds", "20", "--steps", "1", "--warmup", "0", "--no-extras", "--no-cpu-baseline"],
                    {"ETD_FORCE_SPAWN": "1"})
     assert d["n_gpus"] == 1 and d["jobs_gathered"] == 2 and d["value"] > 0
+
+
+def test_bench_plain_run_is_the_headline_and_dumps_its_outputs(tmp_path):
+    """bench.py without --full: the timed steps and the line only (no stamped stage, serial pass, extras or CPU baseline); --dump-outputs writes the
+    last timed step's outputs, float files that two runs with the same arguments write identically"""
+    args = ["--batch-clips", "2", "--attr-grid", "3", "--seconds", "24", "--steps", "2", "--warmup", "1"]
+    runs = [_run_bench(args + ["--dump-outputs", str(tmp_path / r)]) for r in ("a", "b")]
+    for d in runs:
+        assert d["steps"] == 2 and d["dtype"] == "f16" and d["higher_is_better"] is True and d["ms_per_step"] > 0
+        assert not {"extras", "cpu_baseline", "kernel_ms_serial_pass"} & set(d) and "frac" not in d["roofline"]
+        assert abs(d["value"] - 24.0 * 2 / (d["ms_per_step"] / 1e3)) / d["value"] < 1e-3
+    assert runs[0]["tokens_sha256_all"] == runs[1]["tokens_sha256_all"]
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert "token_ids.npy" in names and "extract_notes.npy" in names and "cover_notes.npy" in names
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+    assert np.load(tmp_path / "a" / "job_index.npy").tolist() == list(range(6))
+    bl = np.load(tmp_path / "a" / "bar_lengths.npy")
+    assert len(set(bl[bl >= 0].tolist())) == 1                                  # --bar-tokens: every bar of every job has the same length

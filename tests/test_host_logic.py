@@ -230,6 +230,44 @@ def test_union_of_launch_intervals():
     assert abs(bench.union_seconds(big) - 10e-8) < 1e-15
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 / float64 files only, the same bytes for the same step outputs, the ids of a job under its global index,
+    a fixed job sample of a large batch, and all files within the size bound"""
+    from types import SimpleNamespace as NS
+    import numpy as np
+    import bench
+    note_dt = np.dtype([("onset", "<f8"), ("offset", "<f8"), ("pitch", "<i4"), ("velocity", "<i4")])
+    rng = np.random.default_rng(5)
+
+    def notes(n):
+        a = np.zeros(n, note_dt)
+        a["onset"] = np.sort(rng.random(n) * 180.0); a["offset"] = a["onset"] + 0.25; a["pitch"] = rng.integers(21, 109, n); a["velocity"] = rng.integers(1, 128, n)
+        return a
+
+    clip_ids, tuples = [1, 3, 5], 100                     # rank 1 of 2: clips 1, 3, 5 -> 300 jobs, more than DUMP_JOBS
+    conds = [NS(notes=notes(40 + c), volume=rng.random(90 + c).astype(np.float32),
+                bars=NS(ids=rng.integers(4, 154, 30 + c).astype(np.int32), offsets=np.asarray([0, 10, 30 + c], np.int32))) for c in range(3)]
+    results = [(rng.integers(4, 154, 96 + j % 7).astype(np.int32), np.asarray([48, 48 + j % 7], np.int64)) for j in range(300)]
+    cover = [notes(j % 11) for j in range(300)]
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, conds, results, cover, clip_ids, tuples)
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == sorted(f"{n}.npy" for n in ("extract_notes", "volume", "condition_ids", "condition_bar_offsets", "job_index", "token_ids", "bar_lengths", "cover_notes"))
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+    ji, ti = np.load(tmp_path / "a" / "job_index.npy"), np.load(tmp_path / "a" / "token_ids.npy")
+    assert len(ji) == bench.DUMP_JOBS and (np.diff(ji) > 0).all()
+    for row, g in zip(ti, ji.astype(np.int64)):
+        j = clip_ids.index(int(g) // tuples) * tuples + int(g) % tuples
+        assert np.array_equal(row[: results[j][0].size], results[j][0]) and (row[results[j][0].size:] == -1).all()
+    ex = np.load(tmp_path / "a" / "extract_notes.npy")
+    assert ex.shape == (40 + 41 + 42, 5) and np.array_equal(ex[:40, 1], conds[0].notes["onset"]) and set(ex[:, 0]) == {1.0, 3.0, 5.0}
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 16 << 10)
+    bench.dump_outputs(tmp_path / "c", conds, results, cover, clip_ids, tuples)
+    assert sum(p.stat().st_size for p in (tmp_path / "c").iterdir()) <= 16 << 10 and np.load(tmp_path / "c" / "token_ids.npy").size > 0
+
+
 def test_default_engine_layout():
     import bench
     assert bench.default_engines(64 * 27, 1) == 3 and bench.default_engines(8 * 27, 8) == 4 and bench.default_engines(8 * 27, 1) == 4

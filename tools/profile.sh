@@ -9,7 +9,7 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 rm -rf $OUT/prof_trace $OUT/prof_fetch $OUT/prof_write
-ARGS="--steps 1 --warmup 1 --no-cpu-baseline --no-extras ${BENCH_ARGS:-}"
+ARGS="--steps 1 --warmup 1 --full --no-cpu-baseline --no-extras ${BENCH_ARGS:-}"
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_trace -- python3 $ROOT/bench.py $ARGS > $OUT/prof_trace.json 2> $OUT/prof_trace.err || { tail -20 $OUT/prof_trace.err; exit 1; }
 PARGS="--steps 1 --warmup 0 --no-cpu-baseline --no-extras --no-stamp --no-serial-pass --max-bars ${PMC_BARS:-8} ${BENCH_ARGS:-}"
