@@ -49,6 +49,11 @@ class Job(C.Structure):
     _fields_ = [("x_ids", C.c_void_p), ("x_offsets", C.c_void_p), ("n_bars", C.c_int), ("attrs4", C.c_void_p), ("ready", C.c_void_p)]
 
 
+class ScoreJob(C.Structure):
+    _fields_ = [("x_ids", C.c_void_p), ("x_offsets", C.c_void_p), ("n_bars", C.c_int), ("attrs4", C.c_void_p),
+                ("y_ids", C.c_void_p), ("y_offsets", C.c_void_p), ("n_y_bars", C.c_int)]
+
+
 class SchedCfg(_SizedCfg):
     _fields_ = [("struct_bytes", C.c_int)] + [(n, C.c_int) for n in ("bar_bos_id", "bar_eos_id", "n_ctx_pairs", "max_position_embeddings", "max_output_tokens",
                                        "max_bar_token_limit")] + [("context_overlap_ratio", C.c_float)] + \
@@ -149,6 +154,10 @@ SIGNATURES = {
                                            C.c_int, C.c_int, C.c_void_p, c_int_p, C.c_void_p]),
     "etd_decoder_prefill_logits": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                              C.c_void_p]),
+    "etd_decoder_score": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 11 + [C.c_void_p]),
+    "etd_decoder_score_jobs": (C.c_int, [C.c_void_p, C.POINTER(SchedCfg), C.POINTER(ScoreJob), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "etd_debug_assemble_scored": (C.c_int, [C.POINTER(SchedCfg), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, c_int_p]),
     "etd_decoder_step_bytes": (C.c_double, [C.c_void_p, C.c_int, C.c_int]),
     "etd_decoder_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int, C.c_void_p]),
     "etd_decoder_stats_reset": (C.c_int, [C.c_void_p, C.c_void_p]),

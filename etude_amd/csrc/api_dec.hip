@@ -17,6 +17,7 @@
 #include "dec_kernels.h"
 #include "gemm3.h"
 #include "ext_kernels.h"
+#include "dec_score.h"
 #include "prof.h"
 
 namespace {
@@ -97,6 +98,10 @@ struct etd_dec {
   unsigned long long* stamp_dev = nullptr;       // device-side span accumulator of k_dstep_attn_down (etd_decoder_stamp); its own allocation
   bool stamp_on = false, stamp_armed = false; long long stamp_skip = 0;      // armed: requested; on: this call's steps are stamped (after `stamp_skip` more steps)
   float* logits_dbg = nullptr; bool logits_dbg_on = false, last_step_fused = false;   // test hook: the fused step's logits [S][V] (etd_debug_decoder_step_logits)
+  // teacher-forced scoring (etd_decoder_score): own buffers, allocated by the first score call and freed with the handle (the generate path never touches them).
+  // sc_i = [labels Mcap][row list Mcap + score_hb][seq row0 S][seq len S] (uploaded per chunk) then [argmax Mcap][seq tokens S][seq hits S];
+  // sc_f = [lp Mcap][lse Mcap]; sc_d = [seq log-likelihood S]; sc_x = [score_hb][H] gathered hidden rows of one head block
+  int* sc_i = nullptr; float* sc_f = nullptr; double* sc_d = nullptr; float* sc_x = nullptr; int score_hb = 0;
   // weight sharing (etd_decoder_clone): a clone reads the owner's weight buffers and has its own KV cache, workspaces and
   // stream state.  `allocs` of an owner = weights first (n_weight_allocs of them), then its workspaces; a clone's = workspaces only.
   etd_dec* weights_owner = nullptr;              // null: this handle owns its weights
@@ -944,6 +949,10 @@ extern "C" void etd_decoder_destroy(etd_dec* d) {
   if (d->trace_dbg) { (void)hipFree(d->trace_dbg); d->trace_dbg = nullptr; }
   if (d->stamp_dev) { (void)hipFree(d->stamp_dev); d->stamp_dev = nullptr; }
   if (d->logits_dbg) { (void)hipFree(d->logits_dbg); d->logits_dbg = nullptr; }
+  if (d->sc_i) { (void)hipFree(d->sc_i); d->sc_i = nullptr; }
+  if (d->sc_f) { (void)hipFree(d->sc_f); d->sc_f = nullptr; }
+  if (d->sc_d) { (void)hipFree(d->sc_d); d->sc_d = nullptr; }
+  if (d->sc_x) { (void)hipFree(d->sc_x); d->sc_x = nullptr; }
   if (d->pin_stage) { (void)hipHostFree(d->pin_stage); d->pin_stage = nullptr; }
   if (d->pin_rb) { (void)hipHostFree(d->pin_rb); d->pin_rb = nullptr; }
   if (d->pin_stage_evt) { (void)hipEventDestroy(d->pin_stage_evt); d->pin_stage_evt = nullptr; }
@@ -1346,6 +1355,93 @@ extern "C" int etd_decoder_prefill_logits(etd_dec* d, int slot, const int32_t* i
   ETD_TRY(head_logits(d, hf, T, d->logits, st));
   HIP_TRY(hipMemcpyAsync(logits_host, d->logits, (size_t)T * d->V * 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
+  return ETD_OK;
+}
+
+// Teacher-forced scoring of n packed sequences (etude_hip.h).  Sequences go through the batched prefill in chunks of at most S sequences
+// (the handle's slots are the scratch KV caches) and at most Mcap rows -- in the fp32 mode at most 512 rows unless one sequence is longer:
+// a sequence then runs on the weight-streaming kernels (<= 512 rows) or alone on the 128-row tiles (longer) whatever its neighbours are,
+// so its scores do not depend on max_streams or on the other sequences of the call.  The LM head runs on the rows that are scored only,
+// gathered into blocks of a fixed score_hb rows (one head kernel for every block: again independent of the layout), into d->logits.
+extern "C" int etd_decoder_score(etd_dec* d, int n, const int32_t* T, const int32_t* ids, const int32_t* cls, const int32_t* attrs4,
+                                 const int32_t* labels, double* seq_logprob, int32_t* seq_tokens, int32_t* seq_hits,
+                                 float* row_lp, int32_t* row_argmax, float* logits_dev, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!d || n < 1 || !T || !ids || !cls || !attrs4 || !labels || !seq_logprob || !seq_tokens || !seq_hits) ETD_FAIL(ETD_EINVAL, "score: bad arguments");
+  long long M = 0;
+  for (int i = 0; i < n; ++i) {
+    if (T[i] < 1 || T[i] > d->ctx) ETD_FAIL(ETD_EINVAL, "score: sequence %d has %d rows (max_ctx=%d)", i, T[i], d->ctx);
+    M += T[i];
+  }
+  if (M > 0x7fffffffLL) ETD_FAIL(ETD_EINVAL, "score: %lld rows in one call", M);
+  for (long long r = 0; r < M; ++r) {
+    if (ids[r] < 0 || ids[r] >= d->V) ETD_FAIL(ETD_EINVAL, "score: token id %d out of range [0, %d) at row %lld", ids[r], d->V, r);
+    if (cls[r] < 0 || cls[r] >= d->cfg.num_classes) ETD_FAIL(ETD_EINVAL, "score: class id %d out of range [0, %d) at row %lld", cls[r], d->cfg.num_classes, r);
+    for (int k = 0; k < 4; ++k)
+      if (attrs4[k * M + r] < 0 || attrs4[k * M + r] >= d->cfg.num_attribute_bins) ETD_FAIL(ETD_EINVAL, "score: attribute bin %d out of range [0, %d) at row %lld", attrs4[k * M + r], d->cfg.num_attribute_bins, r);
+    if (labels[r] != ETD_IGNORE_LABEL && (labels[r] < 0 || labels[r] >= d->V)) ETD_FAIL(ETD_EINVAL, "score: label %d at row %lld is neither -100 nor in [0, %d)", labels[r], r, d->V);
+  }
+  const int S = d->S, Mcap = d->Mcap;
+  if (!d->sc_x) {                                          // (allocated last: a call that failed half way through allocating starts over)
+    for (void* p : {(void*)d->sc_i, (void*)d->sc_f, (void*)d->sc_d}) if (p) (void)hipFree(p);
+    d->sc_i = nullptr; d->sc_f = nullptr; d->sc_d = nullptr;
+    d->score_hb = d->Mmax < 256 ? d->Mmax : 256;
+    const int hb = d->score_hb;
+    HIP_TRY(hipMalloc((void**)&d->sc_i, ((size_t)3 * Mcap + hb + 4 * (size_t)S) * sizeof(int)));
+    HIP_TRY(hipMalloc((void**)&d->sc_f, (size_t)2 * Mcap * sizeof(float)));
+    HIP_TRY(hipMalloc((void**)&d->sc_d, (size_t)S * sizeof(double)));
+    HIP_TRY(hipMalloc((void**)&d->sc_x, (size_t)hb * d->H * sizeof(float)));
+  }
+  const int hb = d->score_hb;
+  int* lab_dev = d->sc_i; int* idx_dev = lab_dev + Mcap; int* r0_dev = idx_dev + Mcap + hb; int* len_dev = r0_dev + S;
+  int* am_dev = len_dev + S; int* tok_dev = am_dev + Mcap; int* hit_dev = tok_dev + S;
+  float* lp_dev = d->sc_f; float* lse_dev = lp_dev + Mcap;
+  const int rowcap = d->bf16w ? Mcap : std::min(Mcap, G3_MIN_ROWS - 1);
+  const bool full = logits_dev != nullptr;
+  std::vector<int32_t> slots(S), a4c, up;
+  for (int i = 0; i < S; ++i) slots[i] = i;
+  long long r0 = 0;
+  for (int i0 = 0; i0 < n;) {
+    int k = 0; long long Mc = 0;
+    while (i0 + k < n && k < S && (k == 0 || Mc + T[i0 + k] <= rowcap)) Mc += T[i0 + k++];
+    const int mc = (int)Mc;
+    // chunk rows [r0, r0 + mc): attributes re-laid out as [4][mc]; upload = [labels mc][row list, padded to whole head blocks][row0 k][len k]
+    a4c.resize((size_t)4 * mc);
+    for (int a = 0; a < 4; ++a) memcpy(a4c.data() + (size_t)a * mc, attrs4 + a * M + r0, (size_t)mc * 4);
+    up.assign(labels + r0, labels + r0 + mc);
+    for (int r = 0; r < mc; ++r) if (full || labels[r0 + r] != ETD_IGNORE_LABEL) up.push_back(r);
+    const int nl = (int)up.size() - mc;
+    const int nblk = (nl + hb - 1) / hb;
+    up.resize((size_t)mc + (size_t)nblk * hb, 0);          // padding rows gather row 0 of the chunk; their results are never stored
+    HIP_TRY(hipMemcpyAsync(lab_dev, up.data(), (size_t)mc * 4, hipMemcpyHostToDevice, st));
+    if (nblk) HIP_TRY(hipMemcpyAsync(idx_dev, up.data() + mc, (size_t)nblk * hb * 4, hipMemcpyHostToDevice, st));
+    up.clear();
+    for (int i = 0, row = 0; i < k; ++i) { up.push_back(row); row += T[i0 + i]; }
+    up.insert(up.end(), T + i0, T + i0 + k);
+    HIP_TRY(hipMemcpyAsync(r0_dev, up.data(), (size_t)k * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(len_dev, up.data() + k, (size_t)k * 4, hipMemcpyHostToDevice, st));
+    if (row_lp || row_argmax) {
+      HIP_TRY(hipMemsetAsync(lp_dev, 0, (size_t)mc * 4, st));
+      HIP_TRY(hipMemsetAsync(am_dev, 0xff, (size_t)mc * 4, st));      // -1: row not scored
+    }
+    Staged sg; float* hf = nullptr;
+    ETD_TRY(stage_and_forward(d, k, slots.data(), T + i0, ids + r0, cls + r0, a4c.data(), nullptr, &sg, &hf, st));
+    for (int b = 0; b < nblk; ++b) {
+      const int nb = std::min(hb, nl - b * hb);
+      ETD_TRY(launch_gather_rows(hf, idx_dev + (size_t)b * hb, hb, d->H, d->sc_x, st));
+      ETD_TRY(head_logits(d, d->sc_x, hb, d->logits, st));
+      ETD_TRY(launch_row_logprob(d->logits, d->V, d->V, nb, idx_dev + (size_t)b * hb, lab_dev, lp_dev, lse_dev, am_dev, st));
+      if (full) HIP_TRY(hipMemcpyAsync(logits_dev + (size_t)(r0 + (long long)b * hb) * d->V, d->logits, (size_t)nb * d->V * 4, hipMemcpyDeviceToDevice, st));
+    }
+    ETD_TRY(launch_seq_reduce(r0_dev, len_dev, k, lab_dev, lp_dev, am_dev, d->sc_d, tok_dev, hit_dev, st));
+    HIP_TRY(hipMemcpyAsync(seq_logprob + i0, d->sc_d, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(seq_tokens + i0, tok_dev, (size_t)k * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(seq_hits + i0, hit_dev, (size_t)k * 4, hipMemcpyDeviceToHost, st));
+    if (row_lp) HIP_TRY(hipMemcpyAsync(row_lp + r0, lp_dev, (size_t)mc * 4, hipMemcpyDeviceToHost, st));
+    if (row_argmax) HIP_TRY(hipMemcpyAsync(row_argmax + r0, am_dev, (size_t)mc * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));                     // the host staging vectors and the device scratch are reused by the next chunk
+    i0 += k; r0 += mc;
+  }
   return ETD_OK;
 }
 

@@ -15,6 +15,7 @@
 
 namespace {
 constexpr int SRC_CLASS_ID = 1, TGT_CLASS_ID = 2;   // etude/data/dataset.py:18-19
+constexpr int IGNORE_LABEL = -100;                  // F.cross_entropy's ignore index, the dataset's unscored rows (dataset.py:426)
 
 struct Pair { const int32_t* x; int xn; std::vector<int32_t> y; int a[4]; };
 
@@ -59,6 +60,29 @@ int assemble(const Job& jb, const etd_sched_cfg& c, std::vector<int32_t>& ids, s
   ids.push_back(c.bar_bos_id); cls.push_back(TGT_CLASS_ID);
   for (int k = 0; k < 4; ++k) at[k].push_back(ya[k]);
   return (int)len + 1;
+}
+
+// teacher-forced sequence of a cover bar y = [Bar_BOS] + tokens (etd_decoder_score_jobs): the bar's prompt as generate() builds it, then the tokens
+// generate() fed back (y[1 : yn-1], target class, the bar's attributes); labels: what each row predicted -- -100 on the prompt rows but the last,
+// then y[1:].  Appended to ids / cls / at / labels; returns the rows (0 for a [Bar_BOS]-only bar: nothing to score, nothing appended)
+int assemble_scored(const Job& jb, const etd_sched_cfg& c, const int32_t* y, int yn, std::vector<int32_t>& ids, std::vector<int32_t>& cls,
+                    std::vector<int32_t> (&at)[4], std::vector<int32_t>& labels) {
+  if (yn <= 1) return 0;
+  const size_t start = ids.size();
+  const int P = assemble(jb, c, ids, cls, at);
+  const int* ya = jb.j->attrs4 + 4 * jb.bar;
+  ids.insert(ids.end(), y + 1, y + yn - 1);
+  cls.insert(cls.end(), (size_t)(yn - 2), TGT_CLASS_ID);
+  for (int k = 0; k < 4; ++k) at[k].insert(at[k].end(), (size_t)(yn - 2), ya[k]);
+  labels.insert(labels.end(), (size_t)(P - 1), IGNORE_LABEL);
+  labels.insert(labels.end(), y + 1, y + yn);
+  return (int)(ids.size() - start);
+}
+
+int check_cover_bar(const etd_sched_cfg& c, const int32_t* y, int yn, const char* who, int job, int bar) {
+  if (yn < 1 || !y || y[0] != c.bar_bos_id) ETD_FAIL(ETD_EINVAL, "%s: job %d bar %d does not start with Bar_BOS (id %d)", who, job, bar, c.bar_bos_id);
+  if (yn - 1 > c.max_bar_token_limit) ETD_FAIL(ETD_EINVAL, "%s: job %d bar %d has %d tokens, more than max_bar_token_limit=%d", who, job, bar, yn - 1, c.max_bar_token_limit);
+  return ETD_OK;
 }
 }  // namespace
 
@@ -255,5 +279,73 @@ extern "C" int etd_decoder_run_jobs(etd_dec* d, const etd_sched_cfg* cfg, const 
   }
   job_offsets[n_jobs] = pos;
   if (n_steps_out) *n_steps_out = n_steps;
+  return ETD_OK;
+}
+
+// test hook (no GPU needed): the teacher-forced sequence etd_decoder_score_jobs builds for one cover bar
+extern "C" int etd_debug_assemble_scored(const etd_sched_cfg* cfg, int n_hist, const int32_t* const* hx, const int32_t* hxn, const int32_t* const* hy,
+                                         const int32_t* hyn, const int32_t* hattrs4, const int32_t* x, int xn, const int32_t* y, int yn,
+                                         const int32_t* y_attrs4, int32_t* ids_out, int32_t* cls_out, int32_t* attrs4_out, int32_t* labels_out,
+                                         int cap, int* T_out) {
+  if (!cfg || n_hist < 0 || !x || !y_attrs4 || !ids_out || !cls_out || !attrs4_out || !labels_out || !T_out) ETD_FAIL(ETD_EINVAL, "assemble_scored: bad arguments");
+  if (cfg->struct_bytes != (int)sizeof(etd_sched_cfg)) ETD_FAIL(ETD_EINVAL, "assemble_scored: etd_sched_cfg of %d bytes, expected %d", cfg->struct_bytes, (int)sizeof(etd_sched_cfg));
+  ETD_TRY(check_cover_bar(*cfg, y, yn, "assemble_scored", 0, n_hist));
+  const int32_t offs[2] = {0, xn};
+  etd_job j{x, offs, 1, y_attrs4, nullptr};
+  Job jb; jb.j = &j; jb.bar = 0;
+  const int first = n_hist > cfg->n_ctx_pairs ? n_hist - cfg->n_ctx_pairs : 0;
+  for (int i = first; i < n_hist; ++i) {
+    Pair p; p.x = hx[i]; p.xn = hxn[i]; p.y.assign(hy[i], hy[i] + hyn[i]); memcpy(p.a, hattrs4 + 4 * i, 16);
+    jb.hist.push_back(std::move(p));
+  }
+  std::vector<int32_t> ids, cls, at[4], lab;
+  const int T = assemble_scored(jb, *cfg, y, yn, ids, cls, at, lab);
+  *T_out = T;
+  if (T > cap) ETD_FAIL(ETD_ENOMEM, "assemble_scored: need room for %d rows", T);
+  if (T > 0) {
+    memcpy(ids_out, ids.data(), (size_t)T * 4); memcpy(cls_out, cls.data(), (size_t)T * 4); memcpy(labels_out, lab.data(), (size_t)T * 4);
+    for (int k = 0; k < 4; ++k) memcpy(attrs4_out + (size_t)k * cap, at[k].data(), (size_t)T * 4);
+  }
+  return ETD_OK;
+}
+
+// Teacher-forced per-bar scores of many covers (etude_hip.h): every bar of every job becomes one sequence of ONE etd_decoder_score call
+extern "C" int etd_decoder_score_jobs(etd_dec* d, const etd_sched_cfg* cfg, const etd_score_job* jobs, int n_jobs, double* bar_logprob, int32_t* bar_tokens,
+                                      int32_t* bar_hits, void* stream) {
+  if (!d || !cfg || !jobs || n_jobs < 1 || !bar_logprob || !bar_tokens || !bar_hits) ETD_FAIL(ETD_EINVAL, "score_jobs: bad arguments");
+  if (cfg->struct_bytes != (int)sizeof(etd_sched_cfg)) ETD_FAIL(ETD_EINVAL, "score_jobs: etd_sched_cfg of %d bytes, this library (ABI %d) expects %d -- caller built against another etude_hip.h", cfg->struct_bytes, ETD_ABI_VERSION, (int)sizeof(etd_sched_cfg));
+  const etd_sched_cfg& c = *cfg;
+  if (c.n_ctx_pairs < 0 || c.max_bar_token_limit < 1) ETD_FAIL(ETD_EINVAL, "score_jobs: bad scheduler config");
+  std::vector<int32_t> ids, cls, at[4], lab, T;
+  std::vector<long long> seq_bar;                  // output index of each sequence (bars with nothing to score have none)
+  long long nout = 0;
+  for (int ji = 0; ji < n_jobs; ++ji) {
+    const etd_score_job& s = jobs[ji];
+    if (s.n_bars < 0 || s.n_y_bars < 0 || s.n_y_bars > s.n_bars || (s.n_bars > 0 && (!s.x_ids || !s.x_offsets || !s.attrs4)) || (s.n_y_bars > 0 && (!s.y_ids || !s.y_offsets)))
+      ETD_FAIL(ETD_EINVAL, "score_jobs: job %d malformed (%d condition bars, %d cover bars)", ji, s.n_bars, s.n_y_bars);
+    const etd_job j{s.x_ids, s.x_offsets, s.n_bars, s.attrs4, nullptr};
+    Job jb; jb.j = &j;
+    for (int b = 0; b < s.n_y_bars; ++b, ++nout) {
+      const int32_t* y = s.y_ids + s.y_offsets[b];
+      const int yn = s.y_offsets[b + 1] - s.y_offsets[b];
+      ETD_TRY(check_cover_bar(c, y, yn, "score_jobs", ji, b));
+      bar_logprob[nout] = 0.0; bar_tokens[nout] = 0; bar_hits[nout] = 0;
+      jb.bar = b;
+      const int t = assemble_scored(jb, c, y, yn, ids, cls, at, lab);
+      if (t > 0) { T.push_back(t); seq_bar.push_back(nout); }
+      Pair p; p.x = s.x_ids + s.x_offsets[b]; p.xn = s.x_offsets[b + 1] - s.x_offsets[b]; p.y.assign(y, y + yn);
+      memcpy(p.a, s.attrs4 + 4 * b, 16);
+      jb.hist.push_back(std::move(p));
+      if ((int)jb.hist.size() > c.n_ctx_pairs) jb.hist.erase(jb.hist.begin());
+    }
+  }
+  const int n = (int)T.size();
+  if (n == 0) return ETD_OK;
+  const size_t M = ids.size();
+  std::vector<int32_t> a4((size_t)4 * M);
+  for (int k = 0; k < 4; ++k) memcpy(a4.data() + (size_t)k * M, at[k].data(), M * 4);
+  std::vector<double> lp(n); std::vector<int32_t> tok(n), hit(n);
+  ETD_TRY(etd_decoder_score(d, n, T.data(), ids.data(), cls.data(), a4.data(), lab.data(), lp.data(), tok.data(), hit.data(), nullptr, nullptr, nullptr, stream));
+  for (int i = 0; i < n; ++i) { bar_logprob[seq_bar[i]] = lp[i]; bar_tokens[seq_bar[i]] = tok[i]; bar_hits[seq_bar[i]] = hit[i]; }
   return ETD_OK;
 }

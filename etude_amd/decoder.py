@@ -17,7 +17,7 @@ import json
 import os
 from collections import OrderedDict
 from pathlib import Path
-from typing import Dict, List, Optional, Sequence, Tuple, Union
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -28,6 +28,70 @@ SRC_CLASS_ID = 1   # etude/data/dataset.py:18
 TGT_CLASS_ID = 2   # etude/data/dataset.py:19
 # C-ABI attribute order = concat order of etude_decoder.py:171-176, keyed by generate()'s user keys (:238-243)
 ABI_ATTR_KEYS = ("pitch_overlap_bin", "polyphony_bin", "sustain_bin", "rhythm_intensity_bin")
+
+
+IGNORE_INDEX = -100   # F.cross_entropy's default ignore_index: the label of every row that is not scored (etude/data/dataset.py:426, :452)
+
+
+def _int_array(x, what: str) -> np.ndarray:
+    """torch tensor (any device) / numpy array / nested list -> int64 numpy array"""
+    if torch.is_tensor(x):
+        x = x.detach().cpu().numpy()
+    a = np.asarray(x)
+    if a.dtype.kind not in "iub":
+        raise TypeError(f"{what} must hold integers, got {a.dtype}")
+    return a.astype(np.int64, copy=False)
+
+
+def right_padded_lengths(shape: Tuple[int, int], attention_mask=None, labels=None) -> np.ndarray:
+    """Rows of a right-padded [B, T] batch (EtudeDataset.collate_fn, etude/data/dataset.py:438-461): ones then zeros in every row of
+    ``attention_mask`` (None = no padding).  Returns the valid length of each row.  ValueError on any other mask (left padding, holes), and on a
+    label other than -100 on a padded position."""
+    B, T = shape
+    if attention_mask is None:
+        lens = np.full(B, T, np.int64)
+    else:
+        m = _int_array(attention_mask, "attention_mask")
+        if m.shape != (B, T):
+            raise ValueError(f"attention_mask of shape {m.shape}, input_ids {(B, T)}")
+        if ((m != 0) & (m != 1)).any():
+            raise ValueError("attention_mask must hold 0 / 1 only")
+        lens = m.sum(axis=1)
+        if (m != (np.arange(T)[None, :] < lens[:, None])).any():
+            raise ValueError("attention_mask must be right padding (ones, then zeros, in every row); left padding and holes are not supported")
+    if labels is not None:
+        lab = _int_array(labels, "labels")
+        if lab.shape != (B, T):
+            raise ValueError(f"labels of shape {lab.shape}, input_ids {(B, T)}")
+        pad = np.arange(T)[None, :] >= lens[:, None]
+        if (lab[pad] != IGNORE_INDEX).any():
+            raise ValueError("a padded position (attention_mask 0) carries a label other than -100")
+    return lens
+
+
+class DecoderOutput:
+    """What ``EtudeDecoder.forward`` returns: the fields of transformers' CausalLMOutputWithPast that the reference fills
+    (etude_decoder.py:200-206); ``past_key_values`` is always None (the engine keeps its own KV cache)."""
+
+    def __init__(self, loss: Optional[torch.Tensor], logits: torch.Tensor):
+        self.loss, self.logits, self.past_key_values = loss, logits, None
+        self.hidden_states = self.attentions = None
+
+    def __getitem__(self, key):
+        if isinstance(key, str):
+            return getattr(self, key)
+        return self.to_tuple()[key]
+
+    def to_tuple(self) -> tuple:
+        return (self.loss, self.logits) if self.loss is not None else (self.logits,)
+
+
+class BarScores(NamedTuple):
+    """Per-bar teacher-forced scores of one cover (``EtudeDecoder.score_many``): log-likelihood of the bar's tokens (float64), the number of
+    tokens scored (= len(bar) - 1: every token after Bar_BOS, Bar_EOS included) and how many of them are the greedy choice."""
+    bar_logprob: np.ndarray
+    bar_tokens: np.ndarray
+    bar_greedy_hits: np.ndarray
 
 
 class EtudeDecoderConfig:
@@ -312,6 +376,120 @@ class EtudeDecoder:
         mp = int(self.config.max_position_embeddings)
         prompt = max(mp - int(max_bar_token_limit), int(mp * float(context_overlap_ratio))) + 1
         return prompt + int(gen_limit if gen_limit is not None else max_bar_token_limit) - 1
+
+    # ------------------------------------------------------------------ teacher-forced scoring
+    def _score(self, T: np.ndarray, ids: np.ndarray, cls: np.ndarray, attrs4: np.ndarray, labels: np.ndarray,
+               logits_dev: Optional[torch.Tensor] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """etd_decoder_score over packed sequences (attrs4 [4][M] in ABI order); returns per-sequence (log-likelihood, tokens, greedy hits)."""
+        T = np.ascontiguousarray(T, np.int32)
+        ids, cls, labels = (np.ascontiguousarray(a, np.int32) for a in (ids, cls, labels))
+        attrs4 = np.ascontiguousarray(attrs4, np.int32)
+        n = T.size
+        lp, tok, hit = np.zeros(n, np.float64), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().etd_decoder_score(self._h, n, T.ctypes.data, ids.ctypes.data, cls.ctypes.data, attrs4.ctypes.data, labels.ctypes.data,
+                                                    lp.ctypes.data, tok.ctypes.data, hit.ctypes.data, None, None,
+                                                    logits_dev.data_ptr() if logits_dev is not None else None, self._stream()), "etd_decoder_score")
+        return lp, tok, hit
+
+    @torch.no_grad()
+    def forward(self, input_ids, class_ids, polyphony_bin_ids, rhythm_intensity_bin_ids, note_sustain_bin_ids, pitch_overlap_bin_ids,
+                attention_mask=None, inputs_embeds=None, past_key_values=None, labels=None, use_cache=None, return_dict=None):
+        """EtudeDecoder.forward (etude_decoder.py:148-206), inference only: logits [B, T, V] float32 on this decoder's device and, with
+        ``labels``, the cross-entropy mean over the labels that are not -100 (labels are NOT shifted, as in the reference; nan when there
+        are none).  Inputs are torch tensors (any device) or numpy arrays, [B, T].  The batch must be right-padded (``attention_mask``:
+        ones then zeros per row, as EtudeDataset.collate_fn builds it); logits of padded positions are 0 (the reference computes them from
+        the pad tokens; nothing scores them).  ``use_cache`` is ignored."""
+        if inputs_embeds is not None:
+            raise NotImplementedError("forward: inputs_embeds is not supported (the engine embeds ids itself)")
+        if past_key_values is not None:
+            raise NotImplementedError("forward: past_key_values is not supported (the KV cache is the engine's own; generate / generate_many use it)")
+        ids = _int_array(input_ids, "input_ids")
+        if ids.ndim != 2:
+            raise ValueError(f"input_ids must be [batch, seq_len], got shape {ids.shape}")
+        B, T = ids.shape
+        # C-ABI attribute order = the concat order of etude_decoder.py:171-176
+        named = (("class_ids", class_ids), ("pitch_overlap_bin_ids", pitch_overlap_bin_ids), ("polyphony_bin_ids", polyphony_bin_ids),
+                 ("note_sustain_bin_ids", note_sustain_bin_ids), ("rhythm_intensity_bin_ids", rhythm_intensity_bin_ids))
+        arrs = []
+        for name, a in named:
+            a = _int_array(a, name)
+            if a.shape != (B, T):
+                raise ValueError(f"{name} of shape {a.shape}, input_ids {(B, T)}")
+            arrs.append(a)
+        lens = right_padded_lengths((B, T), attention_mask, labels)
+        valid = np.arange(T)[None, :] < lens[:, None]
+        lab = _int_array(labels, "labels") if labels is not None else np.full((B, T), IGNORE_INDEX, np.int64)
+        V = int(self.config.vocab_size)
+        logits = torch.zeros((B, T, V), dtype=torch.float32, device=self.device)
+        tot, cnt = 0.0, 0
+        rows = lens[lens > 0]
+        if rows.size:
+            M = int(rows.sum())
+            packed = torch.empty((M, V), dtype=torch.float32, device=self.device)
+            torch.cuda.current_stream(self.device).synchronize()      # (the library writes `packed` on the decoder's own stream)
+            lp, tok, _ = self._score(rows, ids[valid], arrs[0][valid], np.stack([a[valid] for a in arrs[1:]]), lab[valid], packed)
+            logits[torch.from_numpy(valid).to(self.device)] = packed
+            tot, cnt = float(lp.sum()), int(tok.sum())
+        loss = None
+        if labels is not None:
+            loss = torch.tensor(-tot / cnt if cnt else float("nan"), dtype=torch.float32, device=self.device)
+        out = DecoderOutput(loss, logits)
+        return out.to_tuple() if return_dict is False else out
+
+    __call__ = forward
+
+    def score_many(self, jobs, vocab, max_bar_token_limit: int = 512, context_overlap_ratio: float = 0.5) -> List[BarScores]:
+        """Teacher-forced log-likelihood of given covers under ``generate()``'s own context rule.  A job is ``(all_x_bars, y_bars,
+        target_attributes_per_bar)``: the condition bars and attributes as ``generate_many`` takes them (``PackedBars`` / int32 ``[n, 4]`` fast
+        forms included) and the cover as ``generate_ids`` returns it (``[Bar_BOS] + tokens`` per bar; a list of lists or a ``PackedBars``).
+        Bar i is scored with the prompt generate() would build from the history of the given bars 0..i-1 (padding with empty bars,
+        truncation at max_position_embeddings - max_bar_token_limit) and its tokens forced one by one; a cover may have fewer bars than
+        the song (a budget-stopped cover).  Returns per job a ``BarScores`` of per-bar arrays.  Uses this engine's slots: do not overlap
+        it with a generate call on the same decoder (``clone()`` gives a second engine)."""
+        bos, eos = vocab.get_bar_bos_id(), vocab.get_bar_eos_id()
+        if bos == -1 or eos == -1:
+            raise ValueError("Bar tokens not in vocab.")
+        need = self.ctx_needed(max_bar_token_limit, context_overlap_ratio)
+        if need > self.max_ctx:
+            raise _lib.EtudeHipError(f"score_many: max_bar_token_limit={max_bar_token_limit} with context_overlap_ratio={context_overlap_ratio} needs {need} KV positions "
+                                     f"per sequence, this decoder was created with max_ctx={self.max_ctx}; pass max_ctx>={need} to EtudeDecoder / load_etude_decoder")
+        V = int(self.config.vocab_size)
+        keep = []
+        cjobs = (_lib.ScoreJob * max(len(jobs), 1))()
+        n_out = []
+        for k, (x_bars, y_bars, attrs) in enumerate(jobs):
+            x = x_bars if isinstance(x_bars, PackedBars) else PackedBars.from_lists(x_bars)
+            y = y_bars if isinstance(y_bars, PackedBars) else PackedBars.from_lists(y_bars)
+            if isinstance(attrs, np.ndarray):
+                a4 = np.ascontiguousarray(attrs, np.int32).reshape(-1, 4)
+            else:
+                a4 = np.ascontiguousarray(np.asarray([[a[key] for key in ABI_ATTR_KEYS] for a in attrs], np.int32).reshape(-1, 4))
+            if len(a4) != len(x):
+                raise ValueError(f"score_many: job {k} has {len(x)} condition bars and {len(a4)} attribute rows")
+            if len(y) > len(x):
+                raise ValueError(f"score_many: job {k} has {len(y)} cover bars for {len(x)} condition bars")
+            for what, b in (("condition", x), ("cover", y)):
+                if b.ids.size and (b.ids.min() < 0 or b.ids.max() >= V):
+                    raise IndexError(f"score_many: token id out of range in job {k}'s {what} bars")
+            keep += [x, y, a4]
+            cjobs[k] = _lib.ScoreJob(x.ids.ctypes.data, x.offsets.ctypes.data, len(x), a4.ctypes.data, y.ids.ctypes.data, y.offsets.ctypes.data, len(y))
+            n_out.append(len(y))
+        total = int(sum(n_out))
+        lp, tok, hit = np.zeros(total, np.float64), np.zeros(total, np.int32), np.zeros(total, np.int32)
+        if total:
+            cfg = self.config
+            sc = _lib.SchedCfg(bar_bos_id=bos, bar_eos_id=eos, n_ctx_pairs=cfg.context_num_past_xy_pairs, max_position_embeddings=cfg.max_position_embeddings,
+                               max_output_tokens=0, max_bar_token_limit=max_bar_token_limit, context_overlap_ratio=context_overlap_ratio,
+                               max_streams=self.max_streams, max_prefill_rows=self.max_prefill_rows, steps_per_poll=1)
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().etd_decoder_score_jobs(self._h, C.byref(sc), cjobs, len(jobs), lp.ctypes.data, tok.ctypes.data, hit.ctypes.data,
+                                                             self._stream()), "etd_decoder_score_jobs")
+        out, p = [], 0
+        for n in n_out:
+            out.append(BarScores(lp[p:p + n].copy(), tok[p:p + n].astype(np.int64), hit[p:p + n].astype(np.int64)))
+            p += n
+        return out
 
     # ------------------------------------------------------------------ test / bench hooks
     def prefill_logits(self, ids, cls, attrs4, slot: int = 0) -> np.ndarray:

@@ -18,6 +18,8 @@
  *                         GPT-NeoX + lm_head) + greedy argmax + KV cache  etude/models/etude_decoder.py:300-343,148-206
  *   etd_decoder_generate_bar  one bar of generate(): prefill + <=limit greedy steps, stop at Bar_EOS
  *                                                                      etude/models/etude_decoder.py:291-343
+ *   etd_decoder_score     EtudeDecoder.forward(..., labels=...) -> .loss / .logits    etude/models/etude_decoder.py:148-206
+ *   etd_decoder_score_jobs  teacher-forced per-bar log-likelihood of covers under generate()'s prompt rule  :246-354
  *
  * Conventions: every function returns 0 on success or a negative errno-style code (ETD_E*); the
  * message is available from etd_last_error() (thread-local).  "dev" pointers are device (HBM)
@@ -246,6 +248,28 @@ int etd_decoder_generate_bar(etd_dec*, int slot, const int32_t* ids, const int32
 /* test hook: full logits [T][vocab] fp32 of a prompt (EtudeDecoder.forward), copied to the host. */
 int etd_decoder_prefill_logits(etd_dec*, int slot, const int32_t* ids, const int32_t* cls, const int32_t* attrs4, int T,
                                float* logits_host, void* stream);
+/* Teacher-forced scoring (EtudeDecoder.forward with labels, etude_decoder.py:148-206: F.cross_entropy with ignore index -100, labels NOT shifted).
+ * n sequences packed as for etd_decoder_begin_bars: T[n] rows each, ids / cls / labels int32 host [M = sum(T)], attrs4 int32 host [4][M] (C-ABI attribute
+ * order).  A row's label is the token it should predict, or -100 (not scored).  Per sequence: seq_logprob = sum over its labelled rows of
+ * log_softmax(logits)[label] (double), seq_tokens = labelled rows, seq_hits = labelled rows whose argmax (lowest index on ties) is the label.
+ * Optional (NULL = not wanted): row_lp [M] (0 on rows not scored) and row_argmax [M] (-1 on rows not scored) host; logits_dev = DEVICE fp32 [M][vocab]:
+ * then EVERY row's logits are written there and every row has an argmax.  Sequences are chunked internally (<= max_streams sequences and
+ * <= max_prefill_rows rows per pass; a sequence may not exceed max_ctx rows).  Out-of-range ids / classes / attribute bins / labels are ETD_EINVAL
+ * before anything runs.  The handle's KV slots serve as scratch: a score call and a generate call (begin_bars / step / run_jobs) on one handle must
+ * not overlap, and a stream's state does not survive a score call (etd_decoder_run_jobs starts every bar afresh).  Synchronous. */
+int etd_decoder_score(etd_dec*, int n, const int32_t* T, const int32_t* ids, const int32_t* cls, const int32_t* attrs4, const int32_t* labels,
+                      double* seq_logprob, int32_t* seq_tokens, int32_t* seq_hits, float* row_lp, int32_t* row_argmax, float* logits_dev, void* stream);
+/* Teacher-forced log-likelihood of given covers under generate()'s own context rule.  A job = condition bars as in etd_job (x_ids, x_offsets
+ * [n_bars + 1], attrs4 [n_bars][4]) + cover bars y_ids / y_offsets [n_y_bars + 1] as generate returns them ([Bar_BOS] + tokens each; n_y_bars <=
+ * n_bars: a budget-stopped cover scores the bars it has).  Bar i is scored as the sequence prompt(history of the given bars 0..i-1, x_i) + y_i[1:-1]
+ * with labels -100 on the prompt rows but the last, then y_i[1:] -- the logits generate() saw while producing y_i (same prompt assembly,
+ * truncation and history window as etd_decoder_run_jobs, from cfg's bar ids / n_ctx_pairs / max_position_embeddings / max_bar_token_limit /
+ * context_overlap_ratio).  Outputs per bar, jobs back to back (sum of n_y_bars entries): bar_logprob, bar_tokens (= len(y_i) - 1), bar_hits.
+ * A bar of [Bar_BOS] only scores 0 tokens; a bar of more than max_bar_token_limit tokens, or not led by Bar_BOS, is ETD_EINVAL.
+ * All bars of all jobs go through etd_decoder_score in one call (same rules on the handle's slots). */
+typedef struct { const int32_t* x_ids; const int32_t* x_offsets; int n_bars; const int32_t* attrs4; const int32_t* y_ids; const int32_t* y_offsets; int n_y_bars; } etd_score_job;
+int etd_decoder_score_jobs(etd_dec*, const etd_sched_cfg* cfg, const etd_score_job* jobs, int n_jobs, double* bar_logprob, int32_t* bar_tokens,
+                           int32_t* bar_hits, void* stream);
 /* algorithmic HBM bytes of one decode step for n_streams at context `ctx` (SURVEY.md 8d formula) */
 double etd_decoder_step_bytes(const etd_dec*, int n_streams, int ctx);
 /* Exact host-side accounting of the decode steps issued on this handle since the last reset (graph replays included):

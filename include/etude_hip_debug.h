@@ -31,6 +31,12 @@ int etd_extractor_debug_tap(etd_ext*, int stage, void* dst_dev);
 int etd_debug_assemble_prompt(const etd_sched_cfg* cfg, int n_hist, const int32_t* const* hx, const int32_t* hxn, const int32_t* const* hy,
                               const int32_t* hyn, const int32_t* hattrs4, const int32_t* x, int xn, const int32_t* y_attrs4,
                               int32_t* ids_out, int32_t* cls_out, int32_t* attrs4_out, int cap, int* T_out);
+/* test hook (host only): the teacher-forced sequence etd_decoder_score_jobs builds for a cover bar y ([Bar_BOS] + tokens, yn >= 1) after the
+   same history: ids / cls / attrs4 = that prompt + y[1 : yn-1] (target class, y_attrs4), labels = -100 on every prompt row but the last, then y[1:].
+   *T_out = rows (also when cap is too small: ETD_ENOMEM).  A bar of more than max_bar_token_limit tokens, or one not led by Bar_BOS, is ETD_EINVAL. */
+int etd_debug_assemble_scored(const etd_sched_cfg* cfg, int n_hist, const int32_t* const* hx, const int32_t* hxn, const int32_t* const* hy,
+                              const int32_t* hyn, const int32_t* hattrs4, const int32_t* x, int xn, const int32_t* y, int yn, const int32_t* y_attrs4,
+                              int32_t* ids_out, int32_t* cls_out, int32_t* attrs4_out, int32_t* labels_out, int cap, int* T_out);
 
 /* Diagnostic (tools/probe_race.py): weighted 64-bit sums over the words of the handle's KV cache, workspaces and stream state:
    out[0] = everything, out[1 + i] = its i-th allocation (as many as `cap` allows). */
