@@ -7,6 +7,7 @@ Drop-in surfaces (same names/signatures as the reference):
     etude_amd.Vocab / Event         <- etude.data.vocab
     etude_amd.HFT_Transformer       <- etude.models.hft_transformer.HFT_Transformer (prepare.py's transcriber)
     etude_amd.TinyREMITokenizer     <- etude.data.tokenizer.TinyREMITokenizer (native encode / split / decode_to_notes)
+    etude_amd.BeatDetector          <- etude.data.beat_detector.BeatDetector (the Beat-Transformer model; madmom's DBN stays the caller's)
 All arithmetic runs in libetude_hip.so (hand-written HIP, see csrc/); importing the heavy
 modules is lazy so that `import etude_amd` works on a box without a GPU.
 """
@@ -19,7 +20,8 @@ import os as _os
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 __all__ = ["AMTAPC_Extractor", "EtudeDecoder", "EtudeDecoderConfig", "load_etude_decoder", "Vocab", "Event",
-           "ExtractorConfig", "DecoderConfig", "HFT_Transformer", "HFTConfig", "TinyREMITokenizer", "run_engines"]
+           "ExtractorConfig", "DecoderConfig", "HFT_Transformer", "HFTConfig", "TinyREMITokenizer", "run_engines",
+           "BeatDetector", "BeatDetectorConfig", "BeatDetectorModelConfig"]
 
 
 def __getattr__(name):
@@ -38,7 +40,10 @@ def __getattr__(name):
     if name == "HFT_Transformer":
         from .hft_transformer import HFT_Transformer
         return HFT_Transformer
-    if name in ("ExtractorConfig", "DecoderConfig", "HFTConfig"):
+    if name == "BeatDetector":
+        from .beat import BeatDetector
+        return BeatDetector
+    if name in ("ExtractorConfig", "DecoderConfig", "HFTConfig", "BeatDetectorConfig", "BeatDetectorModelConfig"):
         from . import config
         return getattr(config, name)
     raise AttributeError(name)

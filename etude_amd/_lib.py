@@ -45,6 +45,11 @@ class DecCfg(_SizedCfg):
                 ("max_streams", C.c_int), ("max_ctx", C.c_int), ("precision", C.c_int), ("max_prefill_rows", C.c_int)]
 
 
+class BeatCfg(_SizedCfg):
+    _fields_ = [("struct_bytes", C.c_int)] + [(n, C.c_int) for n in ("attn_len", "instr", "ntoken", "dmodel", "nhead", "d_hid", "nlayers", "norm_first",
+                                       "n_mels", "tempo_out", "max_rows")]
+
+
 class Job(C.Structure):
     _fields_ = [("x_ids", C.c_void_p), ("x_offsets", C.c_void_p), ("n_bars", C.c_int), ("attrs4", C.c_void_p), ("ready", C.c_void_p)]
 
@@ -172,6 +177,11 @@ SIGNATURES = {
     "etd_debug_decoder_trace_lanes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p]),
     "etd_debug_decoder_trace_q": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p]),
     "etd_debug_decoder_peek_kv": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "etd_beat_create": (C.c_int, [C.POINTER(BeatCfg), C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), c_i64_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "etd_beat_destroy": (None, [C.c_void_p]),
+    "etd_beat_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_i64_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "etd_beat_flops": (C.c_double, [C.c_void_p, C.c_longlong]),
+    "etd_beat_debug_taps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "etd_debug_decoder_trace_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.POINTER(C.c_int), C.c_void_p]),
 }
 

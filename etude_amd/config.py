@@ -125,3 +125,25 @@ class DecoderConfig:               # schema.py:204-226
     top_p: float = 0.9
     max_output_tokens: int = 25600
     max_bar_token_limit: int = 512
+
+
+@dataclass
+class BeatDetectorModelConfig:     # schema.py:134-144
+    attn_len: int = 5
+    instr: int = 5
+    ntoken: int = 2
+    dmodel: int = 256
+    nhead: int = 8
+    d_hid: int = 1024
+    nlayers: int = 9
+    norm_first: bool = True
+
+
+@dataclass
+class BeatDetectorConfig:          # schema.py:147-158
+    min_bpm: float = 70.0
+    max_bpm: float = 250.0
+    fps_divisor: int = 1024
+    threshold: float = 0.2
+    beats_per_bar: list = field(default_factory=lambda: [3, 4])
+    model: BeatDetectorModelConfig = field(default_factory=BeatDetectorModelConfig)

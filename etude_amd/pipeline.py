@@ -4,7 +4,8 @@ What ``InferencePipeline.run`` does for one song and one attribute tuple (/root/
 
     stage 1  extractor.extract(origin.wav -> extract.json)                      infer.py:82-97
              analyze_volume(origin.wav -> volume.json)                           infer.py:99-104
-    stage 2  beat detection -> tempo.json   (OUT OF SCOPE: Spleeter / Beat-Transformer / madmom; the caller supplies tempo.json)
+    stage 2  beat detection -> tempo.json   (not run here: the caller supplies tempo.json.  The Beat-Transformer model itself now exists as
+             etude_amd.BeatDetector; source separation and madmom's DBN stay outside the library)
     stage 3  TinyREMITokenizer(tempo.json).encode(extract.json) -> vocab.encode_sequence -> split_sequence_into_bars
              -> model.generate(bars, attributes) -> tokenizer.decode_to_notes(events, volume.json) -> note_to_midi   infer.py:180-207
 

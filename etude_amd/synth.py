@@ -331,3 +331,70 @@ def song_bars(seed: int = 0, n_bars: int = 92, notes_per_bar: int = 8, n_pos: in
 def attrs(polyphony: int = 1, rhythm: int = 1, sustain: int = 1, overlap: int = 2) -> Dict[str, int]:
     """Target-attribute dict as infer.py builds it (infer.py:187, CLI defaults :280-300)."""
     return {"polyphony_bin": polyphony, "rhythm_intensity_bin": rhythm, "sustain_bin": sustain, "pitch_overlap_bin": overlap}
+
+
+# ----------------------------------------------------------------------------- Beat-Transformer
+
+
+def beat_dims(**over) -> Dict[str, int]:
+    """Default architecture = etude/config/schema.py:134-144 (BeatDetectorModelConfig)."""
+    d = dict(attn_len=5, instr=5, ntoken=2, dmodel=256, nhead=8, d_hid=1024, nlayers=9)
+    d.update(over)
+    return d
+
+
+def beat_state_dict(seed: int = 0, dims: Dict[str, int] | None = None) -> Dict[str, np.ndarray]:
+    """Every key and shape of Demixed_DilatedTransformerModel.state_dict() (etude/models/beat_transformer.py:23-52; 181 tensors at the default architecture).
+    Uniform fan-in weights like nn.Linear / nn.Conv2d's defaults, with the conv biases shifted so that the ReLUs pass about half of their inputs, and Er ~ N(0, 1)
+    as the reference initialises it (large enough that the relative term moves the softmax)."""
+    d = beat_dims(**(dims or {}))
+    rng = np.random.default_rng(seed)
+    D, H, nh, hd, L = d["dmodel"], d["d_hid"], d["nhead"], d["dmodel"] // d["nhead"], d["attn_len"]
+    sd: Dict[str, np.ndarray] = {}
+
+    def conv(name, co, ci, kh, kw, gain, shift):
+        b = 1.0 / math.sqrt(ci * kh * kw)
+        sd[f"{name}.weight"] = (rng.uniform(-b, b, (co, ci, kh, kw)) * gain).astype(np.float32)
+        sd[f"{name}.bias"] = (rng.uniform(-b, b, (co,)) * gain + shift).astype(np.float32)
+
+    # features are dB in [-80, 0]: conv1's bias recentres them
+    conv("conv1", 32, 1, 5, 3, 0.1, 1.5)
+    conv("conv2", 64, 32, 1, 12, 1.0, 0.0)
+    conv("conv3", D, 64, 3, 6, 1.0, 0.0)
+    for l in range(d["nlayers"]):
+        p = f"Transformer_layers.time_attention_{l}."
+        for n in ("key", "value", "query"):
+            sd[p + f"self_attn.{n}.weight"], sd[p + f"self_attn.{n}.bias"] = _lin(rng, D, D, gain=2.0 if n in ("key", "query") else 1.0)
+        sd[p + "self_attn.Er"] = rng.standard_normal((nh, hd, L)).astype(np.float32)
+        sd[p + "linear1.weight"], sd[p + "linear1.bias"] = _lin(rng, H, D)
+        sd[p + "linear2.weight"], sd[p + "linear2.bias"] = _lin(rng, D, H)
+        sd[p + "norm1.weight"], sd[p + "norm1.bias"] = _ln(rng, D)
+        sd[p + "norm2.weight"], sd[p + "norm2.bias"] = _ln(rng, D)
+        if 3 <= l <= 5:
+            q = f"Transformer_layers.instr_attention_{l}."
+            w, b = _lin(rng, 3 * D, D, gain=2.0)
+            sd[q + "self_attn.in_proj_weight"], sd[q + "self_attn.in_proj_bias"] = w, b
+            sd[q + "self_attn.out_proj.weight"], sd[q + "self_attn.out_proj.bias"] = _lin(rng, D, D)
+            sd[q + "linear1.weight"], sd[q + "linear1.bias"] = _lin(rng, H, D)
+            sd[q + "linear2.weight"], sd[q + "linear2.bias"] = _lin(rng, D, H)
+            sd[q + "norm1.weight"], sd[q + "norm1.bias"] = _ln(rng, D)
+            sd[q + "norm2.weight"], sd[q + "norm2.bias"] = _ln(rng, D)
+    sd["out_linear.weight"], sd["out_linear.bias"] = _lin(rng, d["ntoken"], D, gain=4.0)
+    sd["out_linear_t.weight"], sd["out_linear_t.bias"] = _lin(rng, 300, D)
+    return sd
+
+
+def beat_features(seed: int, T: int, instr: int = 5, n_mels: int = 128) -> np.ndarray:
+    """[instr][T][n_mels] float32 dB features in [-80, 0] like scripts/run_separation.py's power_to_db(ref=max): a noise floor with periodic onsets (a different
+    period and spectral shape per stem), so that beat logits vary over time."""
+    rng = np.random.default_rng(seed)
+    t = np.arange(T)[None, :, None]
+    out = np.empty((instr, T, n_mels), np.float32)
+    for i in range(instr):
+        period = 20 + 3 * i
+        phase = int(rng.integers(0, period))
+        env = np.exp(-((t + phase) % period) / (2.0 + i))                         # decaying onsets
+        shape = np.exp(-((np.arange(n_mels) - rng.uniform(10, 110)) / rng.uniform(10, 40)) ** 2)[None, None, :]
+        x = -60.0 + 55.0 * env * (0.3 + 0.7 * shape) + 6.0 * rng.standard_normal((1, T, n_mels))
+        out[i] = np.clip(x, -80.0, 0.0)[0]
+    return out

@@ -20,6 +20,10 @@
  *                                                                      etude/models/etude_decoder.py:291-343
  *   etd_decoder_score     EtudeDecoder.forward(..., labels=...) -> .loss / .logits    etude/models/etude_decoder.py:148-206
  *   etd_decoder_score_jobs  teacher-forced per-bar log-likelihood of covers under generate()'s prompt rule  :246-354
+ *   etd_beat_create       BeatDetector._load_model                      etude/data/beat_detector.py:79-97
+ *   etd_beat_forward      Demixed_DilatedTransformerModel.forward      etude/models/beat_transformer.py:56-106,
+ *                         (conv front end + 9 dilated layers + 3       etude/models/layers/dilated_transformer_layer.py:37-180
+ *                         instrument layers + beat / tempo heads)      (BeatDetector.detect's model call: etude/data/beat_detector.py:121-127)
  *
  * Conventions: every function returns 0 on success or a negative errno-style code (ETD_E*); the
  * message is available from etd_last_error() (thread-local).  "dev" pointers are device (HBM)
@@ -313,6 +317,27 @@ int etd_tok_decode(const etd_tok*, const etd_event* events, long long n, const d
  * File exactly as `pretty_midi.PrettyMIDI()` + one `Instrument(program=0)` + `.write()` lays it out (220 ticks per beat,
  * 120 bpm, tick = round(time * 440)).  pitch / velocity outside 0..127 fail with ETD_EINVAL (mido raises there). */
 int etd_midi_write(const etd_note* notes, long long n, const char* path);
+
+/* ------------------------------------------------------------------ Beat-Transformer (beat / downbeat activations; exact-parity fp32-grade arithmetic)
+ * Demixed_DilatedTransformerModel (etude/models/beat_transformer.py:23-106) as BeatDetector builds it (etude/data/beat_detector.py:79-97, schema.py:134-158).
+ * madmom's DBN trackers that turn the activations into beat times stay with the caller. */
+typedef struct etd_beat etd_beat;
+typedef struct {
+  int struct_bytes;       /* sizeof(etd_beat_cfg) of the caller: a mismatch is ETD_EINVAL */
+  int attn_len, instr, ntoken, dmodel, nhead, d_hid, nlayers, norm_first, n_mels, tempo_out;
+  int max_rows;           /* rows (instr x frames) per internal chunk: the workspace size (a single longer song gets a workspace of its own size) */
+} etd_beat_cfg;
+/* Weights: n named fp32 host tensors with the checkpoint's own keys (181 for the default architecture); a missing key or a wrong element count is ETD_EINVAL.
+ * Architectures: nhead = 8 and attn_len = 5 (the reference's dilated head table is written for them), dmodel = 256, n_mels = 128, norm_first = 1, instr <= 8,
+ * d_hid % 256 == 0; anything else is refused with ETD_EINVAL before any HIP call. */
+int etd_beat_create(const etd_beat_cfg* cfg, const char* const* names, const float* const* host_ptrs, const int64_t* numels, int n, etd_beat** out);
+void etd_beat_destroy(etd_beat*);
+/* feat_dev: the n_seq songs' [instr][T_s][n_mels] fp32 blocks back to back (T_host[s] >= 1 frames each); logits_dev [sum T_s][ntoken]; tempo_dev [n_seq][tempo_out]
+ * (NULL: not computed).  A song's outputs do not depend on the other songs of the call or on the chunking.  Synchronises `stream` once at the start (song table upload).
+ * PRECONDITION: finite features with |x| <= 80 (power_to_db's top_db floor); the plane scales are bounds derived from it.  Not checked here; the Python mirror checks it. */
+int etd_beat_forward(etd_beat*, const float* feat_dev, int n_seq, const int64_t* T_host, float* logits_dev, float* tempo_dev, void* stream);
+/* algorithmic FLOPs of one song of T frames (the reference's full convolutions; formula in DESIGN.md) */
+double etd_beat_flops(etd_beat*, long long T);
 
 #ifdef __cplusplus
 }

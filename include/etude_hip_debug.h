@@ -78,6 +78,10 @@ int etd_debug_attn3(const float* q_dev, const float* k_dev, const float* v_dev, 
  * bound of W x + c for |x| <= elem_bound, largest |value| in the packed f16 planes of W }, log2_out4 = the scale logarithms chosen for the three bounds and for W */
 int etd_debug_g3_bounds(const float* W, const float* c, int N, int K, const float* g, const float* b, float elem_bound, float* out4, int32_t* log2_out4);
 
+/* test hook: during the following etd_beat_forward calls copy the token rows after the conv front end and after time layer 0 ([rows][256], rows in the call's
+ * global row order) to front_dev / layer0_dev (NULL = off). */
+int etd_beat_debug_taps(etd_beat*, float* front_dev, float* layer0_dev);
+
 #ifdef __cplusplus
 }
 #endif
