@@ -23,39 +23,30 @@
 namespace {
 
 // fp32 -> the decoder's 16-bit operand type (dec_kernels.h: IEEE half by default, bf16 under -DETD_DEC_BF16), round to nearest even
-#if ETD_DEC_IS_F16
-inline uint16_t f2bf_h(float f) { const _Float16 h = (_Float16)f; uint16_t u; memcpy(&u, &h, 2); return u; }
-#else
-inline uint16_t f2bf_h(float f) {
-  uint32_t u; memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-  return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-#endif
+inline uint16_t f2bf_h(float f) { return ETD_DEC_IS_F16 ? f32_to_f16_bits(f) : f32_to_bf16_bits(f); }
 
 struct Lin { void* W = nullptr; float* b = nullptr; int N = 0, Npad = 0, K = 0;
              void* Wf = nullptr;      // d16 weights: a second copy in MFMA-fragment order for k_linear (the batched prefill); W stays row-major for the step kernels
-             void* Wp = nullptr; int w_log2 = 0; };   // fp32 weights: again as hi / lo f16 planes for k_gemm3 (csrc/gemm3.h; W stays fp32 for the weight-streaming kernels below 513 rows)
+             G3Lin g3; };             // fp32 weights: again as hi / lo f16 planes for k_gemm3 (csrc/gemm3.h; W stays fp32 for the weight-streaming kernels below 513 rows); b = g3.b
 struct Layer { float *ln1g, *ln1b, *ln2g, *ln2b; Lin qkv, dense, up, down;
                void* dense_hw = nullptr;   // d16 [heads][H][64]: attention.dense regrouped per head for k_dstep_attn_down
                Lin cat;      // decode step: [dense_4h_to_h | attention.dense] along K, so mlp + attn come out of ONE GEMM
                void* mlp_frag = nullptr;   // batched prefill: up | (down | dense) as k_dmlp_fused's weight stream (H 512, I 2048)
-               // fp32 mode on the f16 matrix cores: log2 of the plane scales of every GEMM / attention operand, from provable bounds (etd_decoder_create)
-               int x1_log2 = 0, x2_log2 = 0, q_log2 = 0, k_log2 = 0, v_log2 = 0, m_log2 = 0; };
+               // fp32 mode on the f16 matrix cores: log2 of the plane scales of the attention operands, from provable bounds (etd_decoder_create; the GEMM inputs': g3.x_log2)
+               int q_log2 = 0, k_log2 = 0, v_log2 = 0; };
 
 }  // namespace
 
 #define ETD_STAMP_WORDS (ETD_STAMP_HDR + 2 * ETD_STAMP_LOGCAP)      // u64 words of the device-side span accumulator + launch log of the attention launches (layout: dec_kernels.h)
 struct etd_dec {
   etd_dec_cfg cfg;
-  std::vector<void*> allocs;
-  std::vector<size_t> alloc_bytes;               // parallel to allocs (etd_debug_decoder_checksum)
+  DevPool pool;                                  // (its byte counts: etd_debug_decoder_checksum)
   bool bf16w = false;
   int H, I, V, L, nh, S, ctx, Mmax, Mcap, out_cap;
   float *word = nullptr, *cls_emb = nullptr, *attr_tab = nullptr;
   std::vector<Layer> layers;
   float *lnfg = nullptr, *lnfb = nullptr;
-  Lin head; int xf_log2 = 0;                     // (fp32 mode: plane scale of final_layer_norm's output)
+  Lin head;
   float *X1f = nullptr, *X2f = nullptr;          // fp32 mode, >= G3_MIN_ROWS rows: the two LayerNorm branches as fp32 rows
   float *t_q = nullptr, *t_ao = nullptr, *t_do = nullptr, *t_m1 = nullptr;   // fp32 mode: the last layer's tail on the prompts' last rows only ([S][H], [S][I])
   void* head_frag = nullptr;                     // lm_head in MFMA-fragment order for k_dstep_head: [tile][k-step][lane][8] (d16 weights, H == 512)
@@ -103,85 +94,54 @@ struct etd_dec {
   // sc_f = [lp Mcap][lse Mcap]; sc_d = [seq log-likelihood S]; sc_x = [score_hb][H] gathered hidden rows of one head block
   int* sc_i = nullptr; float* sc_f = nullptr; double* sc_d = nullptr; float* sc_x = nullptr; int score_hb = 0;
   // weight sharing (etd_decoder_clone): a clone reads the owner's weight buffers and has its own KV cache, workspaces and
-  // stream state.  `allocs` of an owner = weights first (n_weight_allocs of them), then its workspaces; a clone's = workspaces only.
+  // stream state.  `pool` of an owner = weights first (n_weight_allocs of them), then its workspaces; a clone's = workspaces only.
   etd_dec* weights_owner = nullptr;              // null: this handle owns its weights
   size_t n_weight_allocs = 0;
   int n_clones = 0; bool zombie = false;         // owner destroyed while clones are alive: weights freed with the last clone
-
-  template <typename T> int alloc(T** p, size_t n, bool zero = false) {
-    void* q = nullptr;
-    HIP_TRY(hipMalloc(&q, n * sizeof(T) + 256));
-    if (zero) HIP_TRY(hipMemset(q, 0, n * sizeof(T) + 256));
-    allocs.push_back(q);
-    alloc_bytes.push_back(n * sizeof(T) + 256);
-    *p = (T*)q;
-    return ETD_OK;
-  }
 };
 
 namespace {
 
-struct Loader {
-  std::map<std::string, std::pair<const float*, int64_t>> t;
-  const float* get(const std::string& k, int64_t numel) {
-    auto it = t.find(k);
-    if (it == t.end()) { g_etd_err = "missing weight '" + k + "'"; return nullptr; }
-    if (it->second.second != numel) { g_etd_err = "weight '" + k + "' has " + std::to_string(it->second.second) + " elements, expected " + std::to_string(numel); return nullptr; }
-    return it->second.first;
-  }
-};
-
-int up_f32(etd_dec* d, float** dst, const float* src, size_t n) {
-  ETD_TRY(d->alloc(dst, n));
-  HIP_TRY(hipMemcpy(*dst, src, n * 4, hipMemcpyHostToDevice));
-  return ETD_OK;
-}
-
 // weight [N][K] (+ bias [N] or null) -> device, rows padded with zeros to a multiple of 128
-int load_lin(etd_dec* d, Loader& L, const std::string& pfx, int N, int K, bool has_bias, Lin* w) {
+int load_lin(etd_dec* d, const WeightTable& L, const std::string& pfx, int N, int K, bool has_bias, Lin* w) {
   const float* W = L.get(pfx + ".weight", (int64_t)N * K);
   if (!W) return ETD_EINVAL;
   const float* b = nullptr;
   if (has_bias) { b = L.get(pfx + ".bias", N); if (!b) return ETD_EINVAL; }
   const int Npad = ((N + 127) / 128) * 128;
   w->N = N; w->Npad = Npad; w->K = K;
+  DevPool& P = d->pool;
   if (d->bf16w) {
     std::vector<uint16_t> hb((size_t)Npad * K, 0);
     for (size_t i = 0; i < (size_t)N * K; ++i) hb[i] = f2bf_h(W[i]);
-    uint16_t* p; ETD_TRY(d->alloc(&p, hb.size()));
-    HIP_TRY(hipMemcpy(p, hb.data(), hb.size() * 2, hipMemcpyHostToDevice));
+    uint16_t* p; ETD_TRY(P.upload(&p, hb.data(), hb.size()));
     w->W = p;
     if (K % 16 == 0) {
       std::vector<uint16_t> hp(hb.size());
       pack_wfrag_host(hb.data(), Npad, K, hp.data());
-      uint16_t* pf; ETD_TRY(d->alloc(&pf, hp.size()));
-      HIP_TRY(hipMemcpy(pf, hp.data(), hp.size() * 2, hipMemcpyHostToDevice));
+      uint16_t* pf; ETD_TRY(P.upload(&pf, hp.data(), hp.size()));
       w->Wf = pf;
     }
   } else {
     std::vector<float> hf((size_t)Npad * K, 0.f);
     memcpy(hf.data(), W, (size_t)N * K * 4);
-    float* p; ETD_TRY(d->alloc(&p, hf.size()));
-    HIP_TRY(hipMemcpy(p, hf.data(), hf.size() * 4, hipMemcpyHostToDevice));
+    float* p; ETD_TRY(P.upload(&p, hf.data(), hf.size()));
     w->W = p;
     if (K % 32 == 0) {
-      std::vector<uint16_t> planes(g3_packed_elems(Npad, K));
-      w->w_log2 = g3_pack_weights_host(W, N, Npad, K, planes.data());
-      uint16_t* pp; ETD_TRY(d->alloc(&pp, planes.size()));
-      HIP_TRY(hipMemcpy(pp, planes.data(), planes.size() * 2, hipMemcpyHostToDevice));
-      w->Wp = pp;
+      ETD_TRY(g3_lin_upload(P, W, b, N, K, 0.f, &w->g3));      // planes, then the padded bias; g3.x_log2: set by etd_decoder_create once the layer's bounds are known
+      w->b = w->g3.b;
+      return ETD_OK;
     }
   }
   std::vector<float> hb2(Npad, 0.f);
   if (b) memcpy(hb2.data(), b, (size_t)N * 4);
-  ETD_TRY(up_f32(d, &w->b, hb2.data(), Npad));
-  return ETD_OK;
+  return P.upload(&w->b, hb2.data(), hb2.size());
 }
 
-int load_vec(etd_dec* d, Loader& L, const std::string& name, int n, float** dst) {
+int load_vec(etd_dec* d, const WeightTable& L, const std::string& name, int n, float** dst) {
   const float* p = L.get(name, n);
   if (!p) return ETD_EINVAL;
-  return up_f32(d, dst, p, n);
+  return d->pool.upload(dst, p, n);
 }
 
 // ---- one forward pass over M rows.  `rows` describes each row (slot, position, active); the embeddings are in
@@ -234,9 +194,9 @@ static int trace_rows(etd_dec* d, const void* buf, long long row_stride, int wor
 static inline bool fused_pmlp_on() { const char* e = getenv("ETD_FUSED_PMLP"); return !e || atoi(e) > 0; }
 struct LastOnly { int n; const int* idx; DecRows rows; };
 
-static DGemmArgs g3_args(const float* X, int ldx, const Lin& w, int x_log2, int M) {
-  DGemmArgs a = {};
-  a.X = X; a.ldx = ldx; a.W = w.W; a.Wp = w.Wp; a.w_log2 = w.w_log2; a.x_log2 = x_log2; a.bias = w.b; a.M = M; a.N = w.N; a.Npad = w.Npad; a.K = w.K;
+static DGemmArgs g3_args(const float* X, int ldx, const Lin& w, int M) {
+  DGemmArgs a = g3_lin_args(w.g3, X, ldx, M);
+  a.W = w.W;               // (the weight-streaming kernels of the last layer's tail read the fp32 rows)
   return a;
 }
 
@@ -252,7 +212,7 @@ int forward_body_x3(etd_dec* d, int M, const DecRows& rows, float** hfinal, hipS
     void* Kl = (char*)d->Kc + (size_t)l * d->layer_stride * 4;
     void* Vl = (char*)d->Vc + (size_t)l * d->layer_stride * 4;
     ETD_TRY(launch_ln_rows_f32(hin, M, H, w.ln1g, w.ln1b, w.ln2g, w.ln2b, d->cfg.layer_norm_eps, d->X1f, d->X2f, st));
-    DGemmArgs q = g3_args(d->X1f, H, w.qkv, w.x1_log2, M);
+    DGemmArgs q = g3_args(d->X1f, H, w.qkv, M);
     q.rows = rows; q.rope_cos = d->rope_cos; q.rope_sin = d->rope_sin; q.rot_half = 8; q.Q = d->Q;
     q.Kc = Kl; q.Vc = Vl; q.slot_stride = d->slot_stride; q.max_ctx = d->ctx; q.n_heads = d->nh;
     ETD_TRY(gemm3_auto(q, DEPI_QKV, st));
@@ -265,11 +225,11 @@ int forward_body_x3(etd_dec* d, int M, const DecRows& rows, float** hfinal, hipS
       at.Q = d->t_q; at.Kc = Kl; at.Vc = Vl; at.slot_stride = d->slot_stride; at.max_ctx = d->ctx; at.n_heads = d->nh;
       at.rows = lo->rows; at.M = n; at.O = d->t_ao; at.scale = 0.125f; at.bytes_hint = 0;
       ETD_TRY(launch_dattn(at, false, st));
-      DGemmArgs de = g3_args(d->t_ao, H, w.dense, w.v_log2, n); de.Y = d->t_do; de.ldy = H;
+      DGemmArgs de = g3_args(d->t_ao, H, w.dense, n); de.Y = d->t_do; de.ldy = H;
       ETD_TRY(launch_dgemm(de, DEPI_BIAS, false, st));
-      DGemmArgs up = g3_args(d->hlast, H, w.up, w.x2_log2, n); up.Y = d->t_m1; up.ldy = d->I; up.ln_g = w.ln2g; up.ln_b = w.ln2b; up.ln_eps = d->cfg.layer_norm_eps;
+      DGemmArgs up = g3_args(d->hlast, H, w.up, n); up.Y = d->t_m1; up.ldy = d->I; up.ln_g = w.ln2g; up.ln_b = w.ln2b; up.ln_eps = d->cfg.layer_norm_eps;
       ETD_TRY(launch_dgemm(up, DEPI_GELU, false, st));
-      DGemmArgs dn = g3_args(d->t_m1, d->I, w.down, w.m_log2, n); dn.add = d->t_do; dn.hin = d->hlast; dn.hout = hout;
+      DGemmArgs dn = g3_args(d->t_m1, d->I, w.down, n); dn.add = d->t_do; dn.hin = d->hlast; dn.hout = hout;
       ETD_TRY(launch_dgemm(dn, DEPI_RESID, false, st));
       *hfinal = hout;                          // rows 0 .. n-1 = the prompts' last positions, in prompt order
       if (compact) *compact = true;
@@ -289,11 +249,11 @@ int forward_body_x3(etd_dec* d, int M, const DecRows& rows, float** hfinal, hipS
       at.stamp = d->stamp_on ? d->stamp_dev : nullptr; at.stamp_par = l & 1;
       ETD_TRY(launch_dattn(at, false, st));
     }
-    DGemmArgs de = g3_args(d->AO, H, w.dense, w.v_log2, M); de.Y = d->DO; de.ldy = H;      // (attention output: a convex combination of V rows)
+    DGemmArgs de = g3_args(d->AO, H, w.dense, M); de.Y = d->DO; de.ldy = H;      // (attention output: a convex combination of V rows)
     ETD_TRY(gemm3_auto(de, DEPI_BIAS, st));
-    DGemmArgs up = g3_args(d->X2f, H, w.up, w.x2_log2, M); up.Y = d->M1; up.ldy = d->I;
+    DGemmArgs up = g3_args(d->X2f, H, w.up, M); up.Y = d->M1; up.ldy = d->I;
     ETD_TRY(gemm3_auto(up, DEPI_GELU, st));
-    DGemmArgs dn = g3_args(d->M1, d->I, w.down, w.m_log2, M); dn.add = d->DO; dn.hin = hin; dn.hout = hout;
+    DGemmArgs dn = g3_args(d->M1, d->I, w.down, M); dn.add = d->DO; dn.hin = hin; dn.hout = hout;
     ETD_TRY(gemm3_auto(dn, DEPI_RESID, st));
     float* t = hin; hin = hout; hout = t;
   }
@@ -304,7 +264,7 @@ int forward_body_x3(etd_dec* d, int M, const DecRows& rows, float** hfinal, hipS
 int forward_body(etd_dec* d, int M, const DecRows& rows, float** hfinal, hipStream_t st, const PrefillInfo* pf = nullptr, bool ln0_done = false,
                  const LastOnly* lo = nullptr, bool* compact = nullptr, bool is_step = false) {
   if (compact) *compact = false;
-  if (!d->bf16w && M >= G3_MIN_ROWS && d->X1f && d->layers[0].qkv.Wp && d->layers[0].down.Wp && g3_enabled()) return forward_body_x3(d, M, rows, hfinal, st, pf, lo, compact);
+  if (!d->bf16w && M >= G3_MIN_ROWS && d->X1f && d->layers[0].qkv.g3.Wp && d->layers[0].down.g3.Wp && g3_enabled()) return forward_body_x3(d, M, rows, hfinal, st, pf, lo, compact);
   float* hin = d->h; float* hout = d->h2;
   const size_t esz = d->bf16w ? 2 : 4;
   const bool bpipe = d->bf16w && (M > 1 || is_step);     // (is_step with M == 1: the fused step kernels for a single stream, ETD_FUSED_M1)
@@ -326,7 +286,7 @@ int forward_body(etd_dec* d, int M, const DecRows& rows, float** hfinal, hipStre
     // ---- fused QKV + RoPE + KV append
     DGemmArgs q = {};
     q.X = hin; q.ldx = d->H; q.W = w.qkv.W; q.Wf = w.qkv.Wf; q.bias = w.qkv.b; q.M = M; q.N = w.qkv.N; q.Npad = w.qkv.Npad; q.K = d->H;
-    q.Wp = w.qkv.Wp; q.w_log2 = w.qkv.w_log2; q.x_log2 = w.x1_log2;
+    q.Wp = w.qkv.g3.Wp; q.w_log2 = w.qkv.g3.w_log2; q.x_log2 = w.qkv.g3.x_log2;
     if (bpipe) q.Xb = d->X1b; else { q.ln_g = w.ln1g; q.ln_b = w.ln1b; q.ln_eps = d->cfg.layer_norm_eps; }
     q.Y = d->qkv_raw; q.ldy = 3 * d->H;
     q.rows = rows; q.rope_cos = d->rope_cos; q.rope_sin = d->rope_sin; q.rot_half = 8; q.Q = d->Q;
@@ -462,7 +422,7 @@ int forward_body(etd_dec* d, int M, const DecRows& rows, float** hfinal, hipStre
     // ---- attention.dense
     DGemmArgs de = {};
     de.X = d->AO; de.ldx = d->H; de.W = w.dense.W; de.bias = w.dense.b; de.M = M; de.N = d->H; de.Npad = w.dense.Npad; de.K = d->H;
-    de.Y = d->DO; de.ldy = d->H; de.Wp = w.dense.Wp; de.w_log2 = w.dense.w_log2; de.x_log2 = w.v_log2;
+    de.Y = d->DO; de.ldy = d->H; de.Wp = w.dense.g3.Wp; de.w_log2 = w.dense.g3.w_log2; de.x_log2 = w.dense.g3.x_log2;
     if (bpipe) de.Xb = d->AOb;
     if (!catk) {                // (otherwise attention.dense is folded into the (down | dense) GEMM below)
       ETD_TRY(launch_dgemm(de, DEPI_BIAS, d->bf16w, st));
@@ -470,7 +430,7 @@ int forward_body(etd_dec* d, int M, const DecRows& rows, float** hfinal, hipStre
     // ---- MLP up + GELU
     DGemmArgs up = {};
     up.X = hin; up.ldx = d->H; up.W = w.up.W; up.bias = w.up.b; up.M = M; up.N = d->I; up.Npad = w.up.Npad; up.K = d->H;
-    up.Y = d->M1; up.ldy = d->I; up.Wp = w.up.Wp; up.w_log2 = w.up.w_log2; up.x_log2 = w.x2_log2;
+    up.Y = d->M1; up.ldy = d->I; up.Wp = w.up.g3.Wp; up.w_log2 = w.up.g3.w_log2; up.x_log2 = w.up.g3.x_log2;
     if (bpipe) { up.Xb = d->X2b; up.Yb = d->M1b; if (catk) { up.Yb = d->Xcat; up.ldy = d->I + d->H; } } else { up.ln_g = w.ln2g; up.ln_b = w.ln2b; up.ln_eps = d->cfg.layer_norm_eps; }
     if (fmlp) {
       // up + GELU, (down | dense), residual and the next layer's LayerNorms: one launch, the hidden layer never leaves the CU
@@ -494,7 +454,7 @@ int forward_body(etd_dec* d, int M, const DecRows& rows, float** hfinal, hipStre
     // ---- MLP down + parallel residual: h = (mlp + attn) + h   (modeling_gpt_neox.py:272)
     DGemmArgs dn = {};
     dn.X = d->M1; dn.ldx = d->I; dn.W = w.down.W; dn.bias = w.down.b; dn.M = M; dn.N = d->H; dn.Npad = w.down.Npad; dn.K = d->I;
-    dn.add = d->DO; dn.hin = hin; dn.hout = hout; dn.Wp = w.down.Wp; dn.w_log2 = w.down.w_log2; dn.x_log2 = w.m_log2;
+    dn.add = d->DO; dn.hin = hin; dn.hout = hout; dn.Wp = w.down.g3.Wp; dn.w_log2 = w.down.g3.w_log2; dn.x_log2 = w.down.g3.x_log2;
     if (bpipe) dn.Xb = d->M1b;
     if (big) {
       dn.add = nullptr;
@@ -522,16 +482,16 @@ int forward_body(etd_dec* d, int M, const DecRows& rows, float** hfinal, hipStre
 
 // final LayerNorm + lm_head for `n` rows of X (fp32 [n][H]) -> logits [n][V]
 int head_logits(etd_dec* d, const float* X, int n, float* logits, hipStream_t st) {
-  if (!d->bf16w && n >= G3_MIN_ROWS && d->X1f && d->head.Wp && g3_enabled()) {
+  if (!d->bf16w && n >= G3_MIN_ROWS && d->X1f && d->head.g3.Wp && g3_enabled()) {
     ETD_TRY(launch_ln_rows_f32(X, n, d->H, d->lnfg, d->lnfb, nullptr, nullptr, d->cfg.layer_norm_eps, d->X1f, nullptr, st));
-    DGemmArgs lm = g3_args(d->X1f, d->H, d->head, d->xf_log2, n);
+    DGemmArgs lm = g3_args(d->X1f, d->H, d->head, n);
     lm.bias = nullptr; lm.Y = logits; lm.ldy = d->V;
     return launch_gemm3(lm, DEPI_LOGITS, st);
   }
   DGemmArgs lm = {};
   lm.X = X; lm.ldx = d->H; lm.W = d->head.W; lm.bias = nullptr; lm.M = n; lm.N = d->V; lm.Npad = d->head.Npad; lm.K = d->H;
   lm.ln_g = d->lnfg; lm.ln_b = d->lnfb; lm.ln_eps = d->cfg.layer_norm_eps; lm.Y = logits; lm.ldy = d->V;
-  lm.Wp = d->head.Wp; lm.w_log2 = d->head.w_log2; lm.x_log2 = d->xf_log2;
+  lm.Wp = d->head.g3.Wp; lm.w_log2 = d->head.g3.w_log2; lm.x_log2 = d->head.g3.x_log2;
   return launch_dgemm(lm, DEPI_LOGITS, d->bf16w, st);
 }
 
@@ -645,49 +605,74 @@ int stage_and_forward(etd_dec* d, int n, const int32_t* slots, const int32_t* T,
 // KV cache, activation workspaces and stream state of one handle (everything that is not a weight)
 int alloc_workspaces(etd_dec* d) {
   const int H = d->H;
-  int rc = 0;
+  DevPool& P = d->pool;
   d->slot_stride = (long long)d->nh * d->ctx * 64;
   d->layer_stride = d->slot_stride * d->S;
   const size_t kv_elems = (size_t)d->layer_stride * d->L;
-  if (d->bf16w) { uint16_t *k, *v; if ((rc = d->alloc(&k, kv_elems, true)) || (rc = d->alloc(&v, kv_elems, true))) return rc; d->Kc = k; d->Vc = v; }
-  else { float *k, *v; if ((rc = d->alloc(&k, kv_elems, true)) || (rc = d->alloc(&v, kv_elems, true))) return rc; d->Kc = k; d->Vc = v; }
+  if (d->bf16w) { uint16_t *k, *v; ETD_TRY(P.alloc(&k, kv_elems, true)); ETD_TRY(P.alloc(&v, kv_elems, true)); d->Kc = k; d->Vc = v; }
+  else { float *k, *v; ETD_TRY(P.alloc(&k, kv_elems, true)); ETD_TRY(P.alloc(&v, kv_elems, true)); d->Kc = k; d->Vc = v; }
   const size_t M = d->Mcap;
   const size_t Mf = d->bf16w ? (size_t)(d->S > 1 ? d->S : 1) : M;     // rows that can take the fp32-activation path
-  rc = 0;
-  rc = rc ? rc : d->alloc(&d->h, M * H); rc = rc ? rc : d->alloc(&d->h2, M * H);
-  rc = rc ? rc : d->alloc(&d->Q, M * H); rc = rc ? rc : d->alloc(&d->AO, M * H); rc = rc ? rc : d->alloc(&d->DO, M * H);
-  rc = rc ? rc : d->alloc(&d->M1, Mf * d->I); rc = rc ? rc : d->alloc(&d->logits, (size_t)d->Mmax * d->V);
-  rc = rc ? rc : d->alloc(&d->qkv_raw, (size_t)3 * H); rc = rc ? rc : d->alloc(&d->hlast, (size_t)d->S * H);
+  ETD_TRY(P.alloc(&d->h, M * H)); ETD_TRY(P.alloc(&d->h2, M * H));
+  ETD_TRY(P.alloc(&d->Q, M * H)); ETD_TRY(P.alloc(&d->AO, M * H)); ETD_TRY(P.alloc(&d->DO, M * H));
+  ETD_TRY(P.alloc(&d->M1, Mf * d->I)); ETD_TRY(P.alloc(&d->logits, (size_t)d->Mmax * d->V));
+  ETD_TRY(P.alloc(&d->qkv_raw, (size_t)3 * H)); ETD_TRY(P.alloc(&d->hlast, (size_t)d->S * H));
   if (d->bf16w) {
-    rc = rc ? rc : d->alloc(&d->X1b, M * H); rc = rc ? rc : d->alloc(&d->X2b, M * H); rc = rc ? rc : d->alloc(&d->AOb, M * H);
-    rc = rc ? rc : d->alloc(&d->M1b, M * d->I);
-    rc = rc ? rc : d->alloc(&d->Pk, (size_t)12 * DS_STEP_MAX_ROWS * H);     // split-K slabs of the decode step: 5 (down | dense) or 4 (down) + one per head (dense inside the attention workgroups)
-    rc = rc ? rc : d->alloc(&d->row_cnt, (size_t)d->L * DS_STEP_MAX_ROWS, true);
-    rc = rc ? rc : d->alloc(&d->Xcat, M * (d->I + H));
-    rc = rc ? rc : d->alloc(&d->Qb, M * H);      // RoPE'd queries of a batched prefill (K / V: the cache rows)
+    ETD_TRY(P.alloc(&d->X1b, M * H)); ETD_TRY(P.alloc(&d->X2b, M * H)); ETD_TRY(P.alloc(&d->AOb, M * H));
+    ETD_TRY(P.alloc(&d->M1b, M * d->I));
+    ETD_TRY(P.alloc(&d->Pk, (size_t)12 * DS_STEP_MAX_ROWS * H));     // split-K slabs of the decode step: 5 (down | dense) or 4 (down) + one per head (dense inside the attention workgroups)
+    ETD_TRY(P.alloc(&d->row_cnt, (size_t)d->L * DS_STEP_MAX_ROWS, true));
+    ETD_TRY(P.alloc(&d->Xcat, M * (d->I + H)));
+    ETD_TRY(P.alloc(&d->Qb, M * H));      // RoPE'd queries of a batched prefill (K / V: the cache rows)
   }
   if (!d->bf16w) {
-    rc = rc ? rc : d->alloc(&d->X1f, M * H); rc = rc ? rc : d->alloc(&d->X2f, M * H);
+    ETD_TRY(P.alloc(&d->X1f, M * H)); ETD_TRY(P.alloc(&d->X2f, M * H));
     const size_t Sr = d->S > 1 ? d->S : 1;
-    rc = rc ? rc : d->alloc(&d->t_q, Sr * H); rc = rc ? rc : d->alloc(&d->t_ao, Sr * H); rc = rc ? rc : d->alloc(&d->t_do, Sr * H); rc = rc ? rc : d->alloc(&d->t_m1, Sr * d->I);
+    ETD_TRY(P.alloc(&d->t_q, Sr * H)); ETD_TRY(P.alloc(&d->t_ao, Sr * H)); ETD_TRY(P.alloc(&d->t_do, Sr * H)); ETD_TRY(P.alloc(&d->t_m1, Sr * d->I));
   }
-  rc = rc ? rc : d->alloc(&d->samp_dev, (size_t)1, true); rc = rc ? rc : d->alloc(&d->rng_key, (size_t)d->S, true);
-  rc = rc ? rc : d->alloc(&d->row_sp, (size_t)2 * d->Mmax, true);
-  rc = rc ? rc : d->alloc(&d->row_slot, (size_t)d->Mmax); rc = rc ? rc : d->alloc(&d->row_pos, (size_t)d->Mmax); rc = rc ? rc : d->alloc(&d->row_active, (size_t)d->Mmax);
-  rc = rc ? rc : d->alloc(&d->ids, 10 * M + 13 * (size_t)d->S); rc = rc ? rc : d->alloc(&d->slots_dev, (size_t)d->S);
+  ETD_TRY(P.alloc(&d->samp_dev, (size_t)1, true)); ETD_TRY(P.alloc(&d->rng_key, (size_t)d->S, true));
+  ETD_TRY(P.alloc(&d->row_sp, (size_t)2 * d->Mmax, true));
+  ETD_TRY(P.alloc(&d->row_slot, (size_t)d->Mmax)); ETD_TRY(P.alloc(&d->row_pos, (size_t)d->Mmax)); ETD_TRY(P.alloc(&d->row_active, (size_t)d->Mmax));
+  ETD_TRY(P.alloc(&d->ids, 10 * M + 13 * (size_t)d->S)); ETD_TRY(P.alloc(&d->slots_dev, (size_t)d->S));
   const size_t S = d->S;
-  rc = rc ? rc : d->alloc(&d->cur_tok, S, true); rc = rc ? rc : d->alloc(&d->len, S, true); rc = rc ? rc : d->alloc(&d->done, S, true);
-  rc = rc ? rc : d->alloc(&d->n_out, S, true); rc = rc ? rc : d->alloc(&d->eos, S, true); rc = rc ? rc : d->alloc(&d->limit, S, true);
-  rc = rc ? rc : d->alloc(&d->tgt_proj, S * (size_t)d->H, true);
-  rc = rc ? rc : d->alloc(&d->tgt_attrs, 4 * S, true); rc = rc ? rc : d->alloc(&d->out_tok, S * d->out_cap, true);
-  if (!rc && !ETD_XENV("ETD_NO_PINNED")) {
+  ETD_TRY(P.alloc(&d->cur_tok, S, true)); ETD_TRY(P.alloc(&d->len, S, true)); ETD_TRY(P.alloc(&d->done, S, true));
+  ETD_TRY(P.alloc(&d->n_out, S, true)); ETD_TRY(P.alloc(&d->eos, S, true)); ETD_TRY(P.alloc(&d->limit, S, true));
+  ETD_TRY(P.alloc(&d->tgt_proj, S * (size_t)d->H, true));
+  ETD_TRY(P.alloc(&d->tgt_attrs, 4 * S, true)); ETD_TRY(P.alloc(&d->out_tok, S * d->out_cap, true));
+  if (!ETD_XENV("ETD_NO_PINNED")) {
     d->pin_stage_ints = 10 * M + 13 * S;
     if (hipHostMalloc((void**)&d->pin_stage, d->pin_stage_ints * 4, hipHostMallocDefault) != hipSuccess) { d->pin_stage = nullptr; (void)hipGetLastError(); }
     if (hipHostMalloc((void**)&d->pin_rb, (2 * S + S * (size_t)d->out_cap) * 4, hipHostMallocDefault) != hipSuccess) { d->pin_rb = nullptr; (void)hipGetLastError(); }
     if (d->pin_stage && hipEventCreateWithFlags(&d->pin_stage_evt, hipEventDisableTiming) != hipSuccess) { (void)hipHostFree(d->pin_stage); d->pin_stage = nullptr; d->pin_stage_evt = nullptr; }
   }
   d->host_n_out.assign(S, 0);
-  return rc;
+  return ETD_OK;
+}
+
+// a handle that never reached its caller (create / clone failed half way): everything it owns so far
+void free_unborn(etd_dec* d) {
+  d->pool.free_all();
+  if (d->pin_stage) (void)hipHostFree(d->pin_stage);
+  if (d->pin_rb) (void)hipHostFree(d->pin_rb);
+  if (d->pin_stage_evt) (void)hipEventDestroy(d->pin_stage_evt);
+  delete d;
+}
+
+// provable bounds of one layer's activations, whatever the input (csrc/gemm3.h): LayerNorm outputs by their parameters, projections of them by Cauchy-Schwarz on the
+// weight rows; the rotary embedding mixes two dims of a Q / K row (|x1 c - x2 s| <= |x1| + |x2|: q and k carry the factor 2); |gelu(u)| <= |u|
+struct LayerBounds { float ln1, ln2, q, k, v, up; };
+int layer_bounds(const WeightTable& L, const std::string& p, int H, int I, LayerBounds* B) {
+  const float* g1 = L.get(p + "input_layernorm.weight", H); const float* b1 = L.get(p + "input_layernorm.bias", H);
+  const float* g2 = L.get(p + "post_attention_layernorm.weight", H); const float* b2 = L.get(p + "post_attention_layernorm.bias", H);
+  const float* Wq = L.get(p + "attention.query_key_value.weight", (int64_t)3 * H * H); const float* bq = L.get(p + "attention.query_key_value.bias", 3 * H);
+  const float* Wu = L.get(p + "mlp.dense_h_to_4h.weight", (int64_t)I * H); const float* bu = L.get(p + "mlp.dense_h_to_4h.bias", I);
+  if (!g1 || !b1 || !g2 || !b2 || !Wq || !bq || !Wu || !bu) return ETD_EINVAL;
+  std::vector<float> rb((size_t)3 * H);
+  g3_row_bounds_of_ln(Wq, bq, 3 * H, H, g1, b1, rb.data());
+  float bnd[3] = {0.f, 0.f, 0.f};
+  for (int j = 0; j < 3 * H; ++j) { const int part = (j % 192) >> 6; bnd[part] = fmaxf(bnd[part], rb[j]); }      // GPT-NeoX's [head][q|k|v][64] rows
+  *B = LayerBounds{g3_bound_ln(g1, b1, H), g3_bound_ln(g2, b2, H), 2.f * bnd[0], 2.f * bnd[1], bnd[2], g3_bound_linear_of_ln(Wu, bu, I, H, g2, b2)};
+  return ETD_OK;
 }
 
 }  // namespace
@@ -722,19 +707,12 @@ extern "C" int etd_decoder_create(const etd_dec_cfg* cfg, const char* const* nam
   d->host_len.assign(d->S, 0);
   d->host_key.resize(d->S);
   for (int i = 0; i < d->S; ++i) d->host_key[i] = (unsigned long long)i;
-  Loader Ld;
-  for (int i = 0; i < n; ++i) Ld.t[names[i]] = {host_ptrs[i], numels[i]};
-  auto fail = [&](int rc) {
-    for (void* p : d->allocs) (void)hipFree(p);
-    if (d->pin_stage) (void)hipHostFree(d->pin_stage);
-    if (d->pin_rb) (void)hipHostFree(d->pin_rb);
-    if (d->pin_stage_evt) (void)hipEventDestroy(d->pin_stage_evt);
-    delete d; return rc;
-  };
+  const WeightTable Ld(names, host_ptrs, numels, n);
+  DevPool& P = d->pool;
+  auto fail = [&](int rc) { free_unborn(d); return rc; };
   const int H = d->H, E = c.attribute_emb_dim, NB = c.num_attribute_bins;
-  int rc;
-  if ((rc = load_vec(d, Ld, "word_embeddings.weight", d->V * H, &d->word))) return fail(rc);
-  if ((rc = load_vec(d, Ld, "class_embeddings.weight", c.num_classes * H, &d->cls_emb))) return fail(rc);
+  ETD_TRY_OR(fail, load_vec(d, Ld, "word_embeddings.weight", d->V * H, &d->word));
+  ETD_TRY_OR(fail, load_vec(d, Ld, "class_embeddings.weight", c.num_classes * H, &d->cls_emb));
   {
     // attribute_projection(cat(e0,e1,e2,e3)) = bias + sum_a W[:, aE:(a+1)E] e_a  -> per (attribute, bin) vectors
     const char* an[4] = {"pitch_overlap_embeddings.weight", "polyphony_embeddings.weight", "note_sustain_embeddings.weight", "rhythm_intensity_embeddings.weight"};
@@ -752,36 +730,27 @@ extern "C" int etd_decoder_create(const etd_dec_cfg* cfg, const char* const* nam
           tab[((size_t)a * NB + b) * H + o] = (float)s;
         }
     }
-    if ((rc = up_f32(d, &d->attr_tab, tab.data(), tab.size()))) return fail(rc);
+    ETD_TRY_OR(fail, P.upload(&d->attr_tab, tab.data(), tab.size()));
   }
   d->layers.resize(d->L);
   for (int l = 0; l < d->L; ++l) {
     const std::string p = "transformer.layers." + std::to_string(l) + ".";
     Layer& w = d->layers[l];
-    if ((rc = load_vec(d, Ld, p + "input_layernorm.weight", H, &w.ln1g))) return fail(rc);
-    if ((rc = load_vec(d, Ld, p + "input_layernorm.bias", H, &w.ln1b))) return fail(rc);
-    if ((rc = load_vec(d, Ld, p + "post_attention_layernorm.weight", H, &w.ln2g))) return fail(rc);
-    if ((rc = load_vec(d, Ld, p + "post_attention_layernorm.bias", H, &w.ln2b))) return fail(rc);
-    if ((rc = load_lin(d, Ld, p + "attention.query_key_value", 3 * H, H, true, &w.qkv))) return fail(rc);
-    if ((rc = load_lin(d, Ld, p + "attention.dense", H, H, true, &w.dense))) return fail(rc);
-    if ((rc = load_lin(d, Ld, p + "mlp.dense_h_to_4h", d->I, H, true, &w.up))) return fail(rc);
-    if ((rc = load_lin(d, Ld, p + "mlp.dense_4h_to_h", H, d->I, true, &w.down))) return fail(rc);
+    ETD_TRY_OR(fail, load_vec(d, Ld, p + "input_layernorm.weight", H, &w.ln1g));
+    ETD_TRY_OR(fail, load_vec(d, Ld, p + "input_layernorm.bias", H, &w.ln1b));
+    ETD_TRY_OR(fail, load_vec(d, Ld, p + "post_attention_layernorm.weight", H, &w.ln2g));
+    ETD_TRY_OR(fail, load_vec(d, Ld, p + "post_attention_layernorm.bias", H, &w.ln2b));
+    ETD_TRY_OR(fail, load_lin(d, Ld, p + "attention.query_key_value", 3 * H, H, true, &w.qkv));
+    ETD_TRY_OR(fail, load_lin(d, Ld, p + "attention.dense", H, H, true, &w.dense));
+    ETD_TRY_OR(fail, load_lin(d, Ld, p + "mlp.dense_h_to_4h", d->I, H, true, &w.up));
+    ETD_TRY_OR(fail, load_lin(d, Ld, p + "mlp.dense_4h_to_h", H, d->I, true, &w.down));
+    LayerBounds B = {};
+    if (!d->bf16w || ETD_DEC_IS_F16) ETD_TRY_OR(fail, layer_bounds(Ld, p, H, d->I, &B));
     if (!d->bf16w) {
-      // plane scales of the fp32-grade f16 path from provable bounds (csrc/gemm3.h): LayerNorm outputs by their parameters, projections of them by Cauchy-Schwarz on the
-      // weight rows; the rotary embedding mixes two dims of a row (|x1 c - x2 s| <= |x1| + |x2|); the attention output is a convex combination of V rows; |gelu(u)| <= |u|
-      const float* g1 = Ld.get(p + "input_layernorm.weight", H); const float* b1 = Ld.get(p + "input_layernorm.bias", H);
-      const float* g2 = Ld.get(p + "post_attention_layernorm.weight", H); const float* b2 = Ld.get(p + "post_attention_layernorm.bias", H);
-      const float* Wq = Ld.get(p + "attention.query_key_value.weight", (int64_t)3 * H * H); const float* bq = Ld.get(p + "attention.query_key_value.bias", 3 * H);
-      const float* Wu = Ld.get(p + "mlp.dense_h_to_4h.weight", (int64_t)d->I * H); const float* bu = Ld.get(p + "mlp.dense_h_to_4h.bias", d->I);
-      if (!g1 || !b1 || !g2 || !b2 || !Wq || !bq || !Wu || !bu) return fail(ETD_EINVAL);
-      w.x1_log2 = g3_scale_log2(g3_bound_ln(g1, b1, H));
-      w.x2_log2 = g3_scale_log2(g3_bound_ln(g2, b2, H));
-      std::vector<float> rb((size_t)3 * H);
-      g3_row_bounds_of_ln(Wq, bq, 3 * H, H, g1, b1, rb.data());
-      float bnd[3] = {0.f, 0.f, 0.f};
-      for (int j = 0; j < 3 * H; ++j) { const int part = (j % 192) >> 6; bnd[part] = fmaxf(bnd[part], rb[j]); }
-      w.q_log2 = g3_scale_log2(2.f * bnd[0]); w.k_log2 = g3_scale_log2(2.f * bnd[1]); w.v_log2 = g3_scale_log2(bnd[2]);
-      w.m_log2 = g3_scale_log2(g3_bound_linear_of_ln(Wu, bu, d->I, H, g2, b2));
+      // plane scales of the fp32-grade f16 path (csrc/gemm3.h); the attention output is a convex combination of V rows
+      w.qkv.g3.x_log2 = g3_scale_log2(B.ln1); w.up.g3.x_log2 = g3_scale_log2(B.ln2);
+      w.q_log2 = g3_scale_log2(B.q); w.k_log2 = g3_scale_log2(B.k); w.v_log2 = g3_scale_log2(B.v);
+      w.dense.g3.x_log2 = w.v_log2; w.down.g3.x_log2 = g3_scale_log2(B.up);
     }
 #if ETD_DEC_IS_F16
     if (d->bf16w) {
@@ -789,16 +758,7 @@ extern "C" int etd_decoder_create(const etd_dec_cfg* cfg, const char* const* nam
       // the softmax / the next LayerNorm.  Every 16-bit tensor of this path is a weight, a LayerNorm output, a projection of one (Q / K / V after the rotary mix, GELU(up): |gelu(u)| <= |u|)
       // or a convex combination of V rows: the same provable bounds the fp32-grade path takes its plane scales from (csrc/gemm3.h) say at load time whether THIS checkpoint
       // can leave the range, whatever the input.  A checkpoint that could is refused (a -DETD_DEC_BF16 build, or precision "fp32", takes it).
-      const float* g1 = Ld.get(p + "input_layernorm.weight", H); const float* b1 = Ld.get(p + "input_layernorm.bias", H);
-      const float* g2 = Ld.get(p + "post_attention_layernorm.weight", H); const float* b2l = Ld.get(p + "post_attention_layernorm.bias", H);
-      const float* Wq = Ld.get(p + "attention.query_key_value.weight", (int64_t)3 * H * H); const float* bq = Ld.get(p + "attention.query_key_value.bias", 3 * H);
-      const float* Wu = Ld.get(p + "mlp.dense_h_to_4h.weight", (int64_t)d->I * H); const float* bu = Ld.get(p + "mlp.dense_h_to_4h.bias", d->I);
-      if (!g1 || !b1 || !g2 || !b2l || !Wq || !bq || !Wu || !bu) return fail(ETD_EINVAL);
-      std::vector<float> rb((size_t)3 * H);
-      g3_row_bounds_of_ln(Wq, bq, 3 * H, H, g1, b1, rb.data());
-      float qkv_b = 0.f;
-      for (int j = 0; j < 3 * H; ++j) qkv_b = fmaxf(qkv_b, (((j % 192) >> 6) < 2 ? 2.f : 1.f) * rb[j]);      // (the rotary embedding mixes two dims of a Q / K row)
-      const float bounds[4] = {g3_bound_ln(g1, b1, H), g3_bound_ln(g2, b2l, H), qkv_b, g3_bound_linear_of_ln(Wu, bu, d->I, H, g2, b2l)};
+      const float bounds[4] = {B.ln1, B.ln2, fmaxf(B.q, fmaxf(B.k, B.v)), B.up};
       static const char* const what[4] = {"input_layernorm rows", "post_attention_layernorm rows", "Q / K / V rows", "gelu(dense_h_to_4h) rows"};
       for (int i = 0; i < 4; ++i)
         if (!(bounds[i] < 65504.f)) { g_etd_err = "decoder_create: layer " + std::to_string(l) + ": " + what[i] + " can reach " + std::to_string(bounds[i]) +
@@ -817,8 +777,7 @@ extern "C" int etd_decoder_create(const etd_dec_cfg* cfg, const char* const* nam
         for (int k = 0; k < d->I; ++k) wc[(size_t)o * Kc + k] = f2bf_h(W2[(size_t)o * d->I + k]);
         for (int k = 0; k < H; ++k) wc[(size_t)o * Kc + d->I + k] = f2bf_h(Wd[(size_t)o * H + k]);
       }
-      uint16_t* pw; if ((rc = d->alloc(&pw, wc.size()))) return fail(rc);
-      HIP_TRY(hipMemcpy(pw, wc.data(), wc.size() * 2, hipMemcpyHostToDevice));
+      uint16_t* pw; ETD_TRY_OR(fail, P.upload(&pw, wc.data(), wc.size()));
       std::vector<float> bc(H);
       for (int o = 0; o < H; ++o) bc[o] = b2[o] + bd[o];
       w.cat.W = pw; w.cat.N = H; w.cat.Npad = H; w.cat.K = Kc;
@@ -827,37 +786,34 @@ extern "C" int etd_decoder_create(const etd_dec_cfg* cfg, const char* const* nam
         for (int hd = 0; hd < d->nh; ++hd)
           for (int o = 0; o < H; ++o)
             for (int dd = 0; dd < 64; ++dd) dh[((size_t)hd * H + o) * 64 + dd] = f2bf_h(Wd[(size_t)o * H + hd * 64 + dd]);
-        uint16_t* pd; if ((rc = d->alloc(&pd, dh.size()))) return fail(rc);
-        HIP_TRY(hipMemcpy(pd, dh.data(), dh.size() * 2, hipMemcpyHostToDevice));
+        uint16_t* pd; ETD_TRY_OR(fail, P.upload(&pd, dh.data(), dh.size()));
         w.dense_hw = pd;
       }
       if (H % 32 == 0 && Kc % 16 == 0) {
         std::vector<uint16_t> wp(wc.size());
         pack_wfrag_host(wc.data(), H, Kc, wp.data());
-        uint16_t* pf; if ((rc = d->alloc(&pf, wp.size()))) return fail(rc);
-        HIP_TRY(hipMemcpy(pf, wp.data(), wp.size() * 2, hipMemcpyHostToDevice));
+        uint16_t* pf; ETD_TRY_OR(fail, P.upload(&pf, wp.data(), wp.size()));
         w.cat.Wf = pf;
       }
-      if ((rc = up_f32(d, &w.cat.b, bc.data(), H))) return fail(rc);
+      ETD_TRY_OR(fail, P.upload(&w.cat.b, bc.data(), H));
       if (H == 512 && d->I == 2048 && fused_pmlp_on()) {
         const float* W1 = Ld.get(p + "mlp.dense_h_to_4h.weight", (int64_t)d->I * H);
         if (!W1) return fail(ETD_EINVAL);
         std::vector<uint16_t> w1((size_t)d->I * H), ws((size_t)DMLP_STREAM_ELEMS);
         for (size_t i = 0; i < w1.size(); ++i) w1[i] = f2bf_h(W1[i]);
         pack_dmlp_weights(w1.data(), wc.data(), ws.data());
-        uint16_t* pm; if ((rc = d->alloc(&pm, ws.size()))) return fail(rc);
-        HIP_TRY(hipMemcpy(pm, ws.data(), ws.size() * 2, hipMemcpyHostToDevice));
+        uint16_t* pm; ETD_TRY_OR(fail, P.upload(&pm, ws.data(), ws.size()));
         w.mlp_frag = pm;
       }
     }
   }
-  if ((rc = load_vec(d, Ld, "transformer.final_layer_norm.weight", H, &d->lnfg))) return fail(rc);
-  if ((rc = load_vec(d, Ld, "transformer.final_layer_norm.bias", H, &d->lnfb))) return fail(rc);
-  if ((rc = load_lin(d, Ld, "lm_head", d->V, H, false, &d->head))) return fail(rc);
+  ETD_TRY_OR(fail, load_vec(d, Ld, "transformer.final_layer_norm.weight", H, &d->lnfg));
+  ETD_TRY_OR(fail, load_vec(d, Ld, "transformer.final_layer_norm.bias", H, &d->lnfb));
+  ETD_TRY_OR(fail, load_lin(d, Ld, "lm_head", d->V, H, false, &d->head));
   if (!d->bf16w) {
     const float* gf = Ld.get("transformer.final_layer_norm.weight", H); const float* bf_ = Ld.get("transformer.final_layer_norm.bias", H);
     if (!gf || !bf_) return fail(ETD_EINVAL);
-    d->xf_log2 = g3_scale_log2(g3_bound_ln(gf, bf_, H));
+    d->head.g3.x_log2 = g3_scale_log2(g3_bound_ln(gf, bf_, H));
   }
   if (d->bf16w && H % 16 == 0) {
     // the same d16 values in the order one wave's A-operand loads want them: (tile t, k-step s, lane l) holds row
@@ -874,8 +830,7 @@ extern "C" int etd_decoder_create(const etd_dec_cfg* cfg, const char* const* nam
           if (row >= d->V) continue;
           for (int e = 0; e < 8; ++e) hp[(((size_t)t * ks + sx) * 64 + l) * 8 + e] = f2bf_h(W[(size_t)row * H + sx * 16 + (l >> 5) * 8 + e]);
         }
-    uint16_t* pp; if ((rc = d->alloc(&pp, hp.size()))) return fail(rc);
-    if (hipMemcpy(pp, hp.data(), hp.size() * 2, hipMemcpyHostToDevice) != hipSuccess) return fail(ETD_EHIP);
+    uint16_t* pp; ETD_TRY_OR(fail, P.upload(&pp, hp.data(), hp.size()));
     d->head_frag = pp;
   }
   {
@@ -885,12 +840,11 @@ extern "C" int etd_decoder_create(const etd_dec_cfg* cfg, const char* const* nam
       const float inv = 1.0f / powf(c.rope_theta, (float)(2 * i) / 16.0f);
       for (int p = 0; p < d->ctx; ++p) { const float ang = (float)p * inv; cs[(size_t)p * 8 + i] = cosf(ang); sn[(size_t)p * 8 + i] = sinf(ang); }
     }
-    if ((rc = up_f32(d, &d->rope_cos, cs.data(), cs.size()))) return fail(rc);
-    if ((rc = up_f32(d, &d->rope_sin, sn.data(), sn.size()))) return fail(rc);
+    ETD_TRY_OR(fail, P.upload(&d->rope_cos, cs.data(), cs.size()));
+    ETD_TRY_OR(fail, P.upload(&d->rope_sin, sn.data(), sn.size()));
   }
-  d->n_weight_allocs = d->allocs.size();
-  rc = alloc_workspaces(d);
-  if (rc) return fail(rc);
+  d->n_weight_allocs = P.mark();
+  ETD_TRY_OR(fail, alloc_workspaces(d));
   if (hipDeviceSynchronize() != hipSuccess) { g_etd_err = "decoder_create: device synchronisation failed"; return fail(ETD_EHIP); }
   *out = d;
   return ETD_OK;
@@ -911,14 +865,14 @@ extern "C" int etd_decoder_clone(etd_dec* src, etd_dec** out) {
   auto unref = [own]() {
     bool last;
     { std::lock_guard<std::mutex> lk(g_family_mu); last = --own->n_clones == 0 && own->zombie; }
-    if (last) { for (void* p : own->allocs) (void)hipFree(p); delete own; }
+    if (last) { own->pool.free_all(); delete own; }
   };
   etd_dec* d = new etd_dec();
   d->cfg = own->cfg; d->bf16w = own->bf16w;
   d->H = own->H; d->I = own->I; d->V = own->V; d->L = own->L; d->nh = own->nh; d->S = own->S; d->ctx = own->ctx;
   d->Mmax = own->Mmax; d->Mcap = own->Mcap; d->out_cap = own->out_cap;
   d->word = own->word; d->cls_emb = own->cls_emb; d->attr_tab = own->attr_tab; d->layers = own->layers;
-  d->lnfg = own->lnfg; d->lnfb = own->lnfb; d->head = own->head; d->head_frag = own->head_frag; d->xf_log2 = own->xf_log2;
+  d->lnfg = own->lnfg; d->lnfb = own->lnfb; d->head = own->head; d->head_frag = own->head_frag;
   d->rope_cos = own->rope_cos; d->rope_sin = own->rope_sin;
   d->host_len.assign(d->S, 0);
   d->host_key.resize(d->S);
@@ -926,13 +880,7 @@ extern "C" int etd_decoder_clone(etd_dec* src, etd_dec** out) {
   d->weights_owner = own;
   int rc = alloc_workspaces(d);
   if (!rc && hipDeviceSynchronize() != hipSuccess) { g_etd_err = "decoder_clone: device synchronisation failed"; rc = ETD_EHIP; }
-  if (rc) {
-    for (void* p : d->allocs) (void)hipFree(p);
-    if (d->pin_stage) (void)hipHostFree(d->pin_stage);
-    if (d->pin_rb) (void)hipHostFree(d->pin_rb);
-    if (d->pin_stage_evt) (void)hipEventDestroy(d->pin_stage_evt);
-    delete d; unref(); return rc;
-  }
+  if (rc) { free_unborn(d); unref(); return rc; }
   *out = d;
   return ETD_OK;
 }
@@ -958,22 +906,21 @@ extern "C" void etd_decoder_destroy(etd_dec* d) {
   if (d->pin_stage_evt) { (void)hipEventDestroy(d->pin_stage_evt); d->pin_stage_evt = nullptr; }
   if (d->weights_owner) {
     etd_dec* own = d->weights_owner;
-    for (void* p : d->allocs) (void)hipFree(p);
+    d->pool.free_all();
     delete d;
     bool last;
     { std::lock_guard<std::mutex> lk(g_family_mu); last = --own->n_clones == 0 && own->zombie; }
-    if (last) { for (void* p : own->allocs) (void)hipFree(p); delete own; }
+    if (last) { own->pool.free_all(); delete own; }
     return;
   }
   bool keep;
   { std::lock_guard<std::mutex> lk(g_family_mu); keep = d->n_clones > 0; if (keep) d->zombie = true; }
   if (keep) {
     // clones still read the weights: release this handle's own workspaces now, the weights with the last clone
-    for (size_t i = d->n_weight_allocs; i < d->allocs.size(); ++i) (void)hipFree(d->allocs[i]);
-    d->allocs.resize(d->n_weight_allocs);
+    d->pool.free_from(d->n_weight_allocs);
     return;
   }
-  for (void* p : d->allocs) (void)hipFree(p);
+  d->pool.free_all();
   delete d;
 }
 
@@ -1459,12 +1406,12 @@ extern "C" int etd_debug_decoder_checksum(etd_dec* d, unsigned long long* out, i
   hipStream_t st = (hipStream_t)stream;
   if (!d || !out || cap < 1) ETD_FAIL(ETD_EINVAL, "decoder_checksum: bad arguments");
   const size_t first = d->weights_owner ? 0 : d->n_weight_allocs;
-  const size_t n = d->allocs.size() - first;
+  const size_t n = d->pool.ptrs.size() - first;
   unsigned long long* acc = nullptr;
   HIP_TRY(hipMalloc(&acc, 8 * (n + 1)));
   HIP_TRY(hipMemsetAsync(acc, 0, 8 * (n + 1), st));
   for (size_t i = 0; i < n; ++i)
-    hipLaunchKernelGGL(k_sum_words, dim3(1024), dim3(256), 0, st, (const unsigned*)d->allocs[first + i], (long long)(d->alloc_bytes[first + i] / 4), acc + 1 + i);
+    hipLaunchKernelGGL(k_sum_words, dim3(1024), dim3(256), 0, st, (const unsigned*)d->pool.ptrs[first + i], (long long)(d->pool.bytes[first + i] / 4), acc + 1 + i);
   std::vector<unsigned long long> h(n + 1);
   HIP_TRY(hipMemcpyAsync(h.data(), acc, 8 * (n + 1), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));

@@ -1,7 +1,6 @@
 // C-ABI glue for the Extract stage: weight preparation (fp32 checkpoint -> e16 device layout,
 // conv+linear folding, QKV concatenation, constant query precompute) and the launch sequence of
 // _Spec2MIDI.forward / AMTAPC_Extractor._transcript (etude/data/extractor.py:53-56,199-253).
-#include <map>
 #include <string>
 #include <vector>
 #include <cmath>
@@ -18,29 +17,12 @@ extern "C" int etd_version(void) { return ETD_ABI_VERSION; }
 
 namespace {
 
-struct DevPool {   // everything the extractor allocates; freed in destroy
-  std::vector<void*> ptrs;
-  template <typename T> int alloc(T** p, size_t n, bool zero = false) {
-    void* q = nullptr;
-    HIP_TRY(hipMalloc(&q, n * sizeof(T) + 256));
-    if (zero) HIP_TRY(hipMemset(q, 0, n * sizeof(T) + 256));
-    ptrs.push_back(q);
-    *p = (T*)q;
-    return ETD_OK;
-  }
-  void free_all() { for (void* p : ptrs) (void)hipFree(p); ptrs.clear(); }
-};
-
 // fp32 -> the extractor's 16-bit operand type (ext_kernels.h: IEEE half by default, bf16 under -DETD_EXT_BF16), round-to-nearest-even, NaN kept; and back
 #if ETD_EXT_IS_F16
-inline uint16_t f2bf(float f) { const _Float16 h = (_Float16)f; uint16_t u; memcpy(&u, &h, 2); return u; }
+inline uint16_t f2bf(float f) { return f32_to_f16_bits(f); }
 inline float e2f(uint16_t q) { _Float16 h; memcpy(&h, &q, 2); return (float)h; }
 #else
-inline uint16_t f2bf(float f) {
-  uint32_t u; memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-  return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
+inline uint16_t f2bf(float f) { return f32_to_bf16_bits(f); }
 inline float e2f(uint16_t q) { const uint32_t u = (uint32_t)q << 16; float w; memcpy(&w, &u, 4); return w; }
 #endif
 
@@ -55,7 +37,7 @@ struct DecLayerW { LinW qkv_s, o_s, q_c, kv_c, o_c, f1, f2; float *g = nullptr, 
 
 struct etd_ext {
   etd_ext_cfg cfg;
-  DevPool pool;
+  DevPool pool;                // everything the extractor allocates; freed in destroy
   int nf, nn, margin, wb, fc;
   // weights
   e16* Wf = nullptr; float* bfold = nullptr; e16* pos_freq_enc = nullptr;
@@ -82,38 +64,21 @@ struct etd_ext {
 
 namespace {
 
-struct Loader {
-  std::map<std::string, std::pair<const float*, int64_t>> t;
-  const float* get(const std::string& k, int64_t numel) {
-    auto it = t.find(k);
-    if (it == t.end()) { g_etd_err = "missing weight '" + k + "'"; return nullptr; }
-    if (it->second.second != numel) { g_etd_err = "weight '" + k + "' has " + std::to_string(it->second.second) + " elements, expected " + std::to_string(numel); return nullptr; }
-    return it->second.first;
-  }
-};
-
 int up_bf16(DevPool& pool, e16** dst, const float* src, size_t n) {
   std::vector<uint16_t> h(n);
   for (size_t i = 0; i < n; ++i) h[i] = f2bf(src[i]);
-  ETD_TRY(pool.alloc(dst, n));
-  HIP_TRY(hipMemcpy(*dst, h.data(), n * 2, hipMemcpyHostToDevice));
-  return ETD_OK;
+  return pool.upload(dst, h.data(), n);
 }
-int up_f32(DevPool& pool, float** dst, const float* src, size_t n) {
-  ETD_TRY(pool.alloc(dst, n));
-  HIP_TRY(hipMemcpy(*dst, src, n * 4, hipMemcpyHostToDevice));
-  return ETD_OK;
-}
-int load_lin(DevPool& pool, Loader& L, const std::string& pfx, int out_f, int in_f, LinW* w) {
+int load_lin(DevPool& pool, const WeightTable& L, const std::string& pfx, int out_f, int in_f, LinW* w) {
   const float* W = L.get(pfx + ".weight", (int64_t)out_f * in_f);
   const float* b = L.get(pfx + ".bias", out_f);
   if (!W || !b) return ETD_EINVAL;
   ETD_TRY(up_bf16(pool, &w->W, W, (size_t)out_f * in_f));
-  ETD_TRY(up_f32(pool, &w->b, b, out_f));
+  ETD_TRY(pool.upload(&w->b, b, out_f));
   return ETD_OK;
 }
 // concatenate several [256][256] linears along the output dim
-int load_cat(DevPool& pool, Loader& L, const std::vector<std::string>& pfx, LinW* w, std::vector<float>* keepW = nullptr, std::vector<float>* keepB = nullptr) {
+int load_cat(DevPool& pool, const WeightTable& L, const std::vector<std::string>& pfx, LinW* w, std::vector<float>* keepW = nullptr, std::vector<float>* keepB = nullptr) {
   std::vector<float> W, b;
   for (auto& p : pfx) {
     const float* Wi = L.get(p + ".weight", 256 * 256);
@@ -123,41 +88,37 @@ int load_cat(DevPool& pool, Loader& L, const std::vector<std::string>& pfx, LinW
     b.insert(b.end(), bi, bi + 256);
   }
   ETD_TRY(up_bf16(pool, &w->W, W.data(), W.size()));
-  ETD_TRY(up_f32(pool, &w->b, b.data(), b.size()));
+  ETD_TRY(pool.upload(&w->b, b.data(), b.size()));
   if (keepW) *keepW = W;
   if (keepB) *keepB = b;
   return ETD_OK;
 }
-int load_ln(DevPool& pool, Loader& L, const std::string& pfx, float** g, float** b) {
+int load_ln(DevPool& pool, const WeightTable& L, const std::string& pfx, float** g, float** b) {
   const float* gw = L.get(pfx + ".weight", 256);
   const float* bw = L.get(pfx + ".bias", 256);
   if (!gw || !bw) return ETD_EINVAL;
-  ETD_TRY(up_f32(pool, g, gw, 256));
-  ETD_TRY(up_f32(pool, b, bw, 256));
+  ETD_TRY(pool.upload(g, gw, 256));
+  ETD_TRY(pool.upload(b, bw, 256));
   return ETD_OK;
 }
 // fc_1 / fc_2 of a position-wise feed-forward block in the fused kernel's fragment-ordered stream
-int load_ffn_stream(DevPool& pool, Loader& L, const std::string& p, e16** dst) {
+int load_ffn_stream(DevPool& pool, const WeightTable& L, const std::string& p, e16** dst) {
   const float* W1 = L.get(p + ".fc_1.weight", 512 * 256);
   const float* W2 = L.get(p + ".fc_2.weight", 256 * 512);
   if (!W1 || !W2) return ETD_EINVAL;
   std::vector<uint16_t> h((size_t)16 * 32 * 64 * 8);
   pack_ffn_weights(W1, W2, h.data(), f2bf);
-  ETD_TRY(pool.alloc(dst, h.size()));
-  HIP_TRY(hipMemcpy(*dst, h.data(), h.size() * 2, hipMemcpyHostToDevice));
-  return ETD_OK;
+  return pool.upload(dst, h.data(), h.size());
 }
 // one [256][256] Linear as a k_proj256 block (rows permuted for row-major / LayerNorm blocks, natural for V^T blocks)
-int load_proj_block(DevPool& pool, Loader& L, const std::string& name, bool permute_rows, e16** dst) {
+int load_proj_block(DevPool& pool, const WeightTable& L, const std::string& name, bool permute_rows, e16** dst) {
   const float* W = L.get(name + ".weight", 256 * 256);
   if (!W) return ETD_EINVAL;
   std::vector<uint16_t> h((size_t)256 * 256);
   pack_proj_weights(W, permute_rows, h.data(), f2bf);
-  ETD_TRY(pool.alloc(dst, h.size()));
-  HIP_TRY(hipMemcpy(*dst, h.data(), h.size() * 2, hipMemcpyHostToDevice));
-  return ETD_OK;
+  return pool.upload(dst, h.data(), h.size());
 }
-int load_enc_layer(DevPool& pool, Loader& L, const std::string& p, EncLayerW* w) {
+int load_enc_layer(DevPool& pool, const WeightTable& L, const std::string& p, EncLayerW* w) {
   ETD_TRY(load_ffn_stream(pool, L, p + ".positionwise_feedforward", &w->ffn));
   ETD_TRY(load_proj_block(pool, L, p + ".self_attention.fc_q", true, &w->pq));
   ETD_TRY(load_proj_block(pool, L, p + ".self_attention.fc_k", true, &w->pk));
@@ -170,8 +131,7 @@ int load_enc_layer(DevPool& pool, Loader& L, const std::string& p, EncLayerW* w)
     if (!Wq || !Wk || !Wv || !Wo || !W1 || !W2) return ETD_EINVAL;
     std::vector<uint16_t> h((size_t)32 * 16384);
     pack_enc_layer_weights(Wq, Wk, Wv, Wo, W1, W2, h.data(), f2bf);
-    ETD_TRY(pool.alloc(&w->lw, h.size()));
-    HIP_TRY(hipMemcpy(w->lw, h.data(), h.size() * 2, hipMemcpyHostToDevice));
+    ETD_TRY(pool.upload(&w->lw, h.data(), h.size()));
   }
   ETD_TRY(load_cat(pool, L, {p + ".self_attention.fc_q", p + ".self_attention.fc_k", p + ".self_attention.fc_v"}, &w->qkv));
   ETD_TRY(load_lin(pool, L, p + ".self_attention.fc_o", 256, 256, &w->o));
@@ -180,7 +140,7 @@ int load_enc_layer(DevPool& pool, Loader& L, const std::string& p, EncLayerW* w)
   ETD_TRY(load_ln(pool, L, p + ".layer_norm", &w->g, &w->be));
   return ETD_OK;
 }
-int load_heads(DevPool& pool, Loader& L, const std::string& sfx, LinW* w) {
+int load_heads(DevPool& pool, const WeightTable& L, const std::string& sfx, LinW* w) {
   std::vector<float> W(160 * 256, 0.f), b(160, 0.f);
   const float* vw = L.get("decoder.fc_velocity_" + sfx + ".weight", 128 * 256);
   const float* vb = L.get("decoder.fc_velocity_" + sfx + ".bias", 128);
@@ -196,7 +156,7 @@ int load_heads(DevPool& pool, Loader& L, const std::string& sfx, LinW* w) {
     b[128 + i] = hb[0];
   }
   ETD_TRY(up_bf16(pool, &w->W, W.data(), W.size()));
-  ETD_TRY(up_f32(pool, &w->b, b.data(), b.size()));
+  ETD_TRY(pool.upload(&w->b, b.data(), b.size()));
   return ETD_OK;
 }
 
@@ -219,21 +179,20 @@ extern "C" int etd_extractor_create(const etd_ext_cfg* cfg, const char* const* n
   if (c.precision == 0 && (c.n_frame < 32 || c.n_frame % 32 || c.n_note < 4 || c.n_note % 4 || c.n_note > 128))
     ETD_FAIL(ETD_EINVAL, "extractor_create: the 16-bit serving mode needs n_frame %% 32 == 0, n_note %% 4 == 0 and <= 128");
   if (c.n_frame < 1 || c.n_note < 1 || c.max_windows < 1) ETD_FAIL(ETD_EINVAL, "extractor_create: need n_frame >= 1, n_note >= 1, max_windows >= 1");
+  if (c.precision != 0 && c.precision != 1) ETD_FAIL(ETD_EINVAL, "extractor_create: precision must be 0 (e16) or 1 (fp32 parity mode)");
   etd_ext* e = new etd_ext();
   e->cfg = c; e->nf = c.n_frame; e->nn = c.n_note; e->margin = c.n_margin; e->wb = c.max_windows;
   e->fc = c.chunk_frames > 0 ? c.chunk_frames : c.n_frame;   // measured: whole-window launches beat MALL-sized chunks (2.9 vs 4.4 ms/window)
   if (const char* s = ETD_XENV("ETD_CHUNK_FRAMES")) e->fc = atoi(s);
   if (e->fc > e->nf) e->fc = e->nf;
   if (e->fc < 1) e->fc = e->nf;
-  Loader L;
-  for (int i = 0; i < n; ++i) L.t[names[i]] = {host_ptrs[i], numels[i]};
+  const WeightTable L(names, host_ptrs, numels, n);
   DevPool& P = e->pool;
-  auto fail = [&](int rc) { e->pool.free_all(); delete e; return rc; };
-  if (c.precision != 0 && c.precision != 1) { delete e; ETD_FAIL(ETD_EINVAL, "extractor_create: precision must be 0 (e16) or 1 (fp32 parity mode)"); }
+  auto fail = [&](int rc) { e->pool.free_all(); ext32_destroy(e->f32); delete e; return rc; };
+  auto sync = [] { if (hipDeviceSynchronize() == hipSuccess) return ETD_OK; g_etd_err = "extractor_create: device synchronisation failed"; return ETD_EHIP; };
   if (c.precision == 1) {
-    const int rc = ext32_create(c, L.t, &e->f32);
-    if (rc) return fail(rc);
-    if (hipDeviceSynchronize() != hipSuccess) { g_etd_err = "extractor_create: device synchronisation failed"; if (e->f32) ext32_destroy(e->f32); return fail(ETD_EHIP); }
+    ETD_TRY_OR(fail, ext32_create(c, L, &e->f32));
+    ETD_TRY_OR(fail, sync());
     *out = e;
     return ETD_OK;
   }
@@ -284,43 +243,42 @@ extern "C" int etd_extractor_create(const etd_ext_cfg* cfg, const char* const* n
       }
     }
 #endif
-    int rc = up_bf16(P, &e->Wf, Wf.data(), Wf.size()); if (rc) return fail(rc);
-    rc = up_f32(P, &e->bfold, bf.data(), 256); if (rc) return fail(rc);
-    rc = up_bf16(P, &e->pos_freq_enc, pe, 256 * 256); if (rc) return fail(rc);
+    ETD_TRY_OR(fail, up_bf16(P, &e->Wf, Wf.data(), Wf.size()));
+    ETD_TRY_OR(fail, P.upload(&e->bfold, bf.data(), 256));
+    ETD_TRY_OR(fail, up_bf16(P, &e->pos_freq_enc, pe, 256 * 256));
   }
-  for (int i = 0; i < 3; ++i) { int rc = load_enc_layer(P, L, "encoder.layers_freq." + std::to_string(i), &e->enc[i]); if (rc) return fail(rc); }
-  for (int i = 0; i < 3; ++i) { int rc = load_enc_layer(P, L, "decoder.layers_time." + std::to_string(i), &e->tim[i]); if (rc) return fail(rc); }
+  for (int i = 0; i < 3; ++i) ETD_TRY_OR(fail, load_enc_layer(P, L, "encoder.layers_freq." + std::to_string(i), &e->enc[i]));
+  for (int i = 0; i < 3; ++i) ETD_TRY_OR(fail, load_enc_layer(P, L, "decoder.layers_time." + std::to_string(i), &e->tim[i]));
   // ---- frequency decoder
   std::vector<float> kvW, kvB;
   for (int i = 0; i < 3; ++i) {
     const std::string p = i == 0 ? std::string("decoder.layer_zero_freq") : "decoder.layers_freq." + std::to_string(i - 1);
     DecLayerW& w = e->dec[i];
-    int rc;
     w.has_self = i > 0;
     if (w.has_self) {
-      rc = load_cat(P, L, {p + ".self_attention.fc_q", p + ".self_attention.fc_k", p + ".self_attention.fc_v"}, &w.qkv_s); if (rc) return fail(rc);
-      rc = load_lin(P, L, p + ".self_attention.fc_o", 256, 256, &w.o_s); if (rc) return fail(rc);
-      rc = load_proj_block(P, L, p + ".self_attention.fc_q", true, &w.pq); if (rc) return fail(rc);
-      rc = load_proj_block(P, L, p + ".self_attention.fc_k", true, &w.pk); if (rc) return fail(rc);
-      rc = load_proj_block(P, L, p + ".self_attention.fc_v", false, &w.pv); if (rc) return fail(rc);
-      rc = load_proj_block(P, L, p + ".self_attention.fc_o", true, &w.po); if (rc) return fail(rc);
+      ETD_TRY_OR(fail, load_cat(P, L, {p + ".self_attention.fc_q", p + ".self_attention.fc_k", p + ".self_attention.fc_v"}, &w.qkv_s));
+      ETD_TRY_OR(fail, load_lin(P, L, p + ".self_attention.fc_o", 256, 256, &w.o_s));
+      ETD_TRY_OR(fail, load_proj_block(P, L, p + ".self_attention.fc_q", true, &w.pq));
+      ETD_TRY_OR(fail, load_proj_block(P, L, p + ".self_attention.fc_k", true, &w.pk));
+      ETD_TRY_OR(fail, load_proj_block(P, L, p + ".self_attention.fc_v", false, &w.pv));
+      ETD_TRY_OR(fail, load_proj_block(P, L, p + ".self_attention.fc_o", true, &w.po));
     }
-    rc = load_proj_block(P, L, p + ".encoder_attention.fc_q", true, &w.pqc); if (rc) return fail(rc);
-    rc = load_proj_block(P, L, p + ".encoder_attention.fc_k", true, &w.pkc); if (rc) return fail(rc);
-    rc = load_proj_block(P, L, p + ".encoder_attention.fc_v", false, &w.pvc); if (rc) return fail(rc);
-    rc = load_proj_block(P, L, p + ".encoder_attention.fc_o", true, &w.poc); if (rc) return fail(rc);
-    rc = load_lin(P, L, p + ".encoder_attention.fc_q", 256, 256, &w.q_c); if (rc) return fail(rc);
+    ETD_TRY_OR(fail, load_proj_block(P, L, p + ".encoder_attention.fc_q", true, &w.pqc));
+    ETD_TRY_OR(fail, load_proj_block(P, L, p + ".encoder_attention.fc_k", true, &w.pkc));
+    ETD_TRY_OR(fail, load_proj_block(P, L, p + ".encoder_attention.fc_v", false, &w.pvc));
+    ETD_TRY_OR(fail, load_proj_block(P, L, p + ".encoder_attention.fc_o", true, &w.poc));
+    ETD_TRY_OR(fail, load_lin(P, L, p + ".encoder_attention.fc_q", 256, 256, &w.q_c));
     std::vector<float> W1, b1;
-    rc = load_cat(P, L, {p + ".encoder_attention.fc_k", p + ".encoder_attention.fc_v"}, &w.kv_c, &W1, &b1); if (rc) return fail(rc);
+    ETD_TRY_OR(fail, load_cat(P, L, {p + ".encoder_attention.fc_k", p + ".encoder_attention.fc_v"}, &w.kv_c, &W1, &b1));
     kvW.insert(kvW.end(), W1.begin(), W1.end()); kvB.insert(kvB.end(), b1.begin(), b1.end());
-    rc = load_lin(P, L, p + ".encoder_attention.fc_o", 256, 256, &w.o_c); if (rc) return fail(rc);
-    rc = load_lin(P, L, p + ".positionwise_feedforward.fc_1", 512, 256, &w.f1); if (rc) return fail(rc);
-    rc = load_lin(P, L, p + ".positionwise_feedforward.fc_2", 256, 512, &w.f2); if (rc) return fail(rc);
-    rc = load_ffn_stream(P, L, p + ".positionwise_feedforward", &w.ffn); if (rc) return fail(rc);
-    rc = load_ln(P, L, p + ".layer_norm", &w.g, &w.be); if (rc) return fail(rc);
+    ETD_TRY_OR(fail, load_lin(P, L, p + ".encoder_attention.fc_o", 256, 256, &w.o_c));
+    ETD_TRY_OR(fail, load_lin(P, L, p + ".positionwise_feedforward.fc_1", 512, 256, &w.f1));
+    ETD_TRY_OR(fail, load_lin(P, L, p + ".positionwise_feedforward.fc_2", 256, 512, &w.f2));
+    ETD_TRY_OR(fail, load_ffn_stream(P, L, p + ".positionwise_feedforward", &w.ffn));
+    ETD_TRY_OR(fail, load_ln(P, L, p + ".layer_norm", &w.g, &w.be));
   }
-  { int rc = up_bf16(P, &e->Wkv_all, kvW.data(), kvW.size()); if (rc) return fail(rc);
-    rc = up_f32(P, &e->bkv_all, kvB.data(), kvB.size()); if (rc) return fail(rc); }
+  ETD_TRY_OR(fail, up_bf16(P, &e->Wkv_all, kvW.data(), kvW.size()));
+  ETD_TRY_OR(fail, P.upload(&e->bkv_all, kvB.data(), kvB.size()));
   {
     const int nn = e->nn;
     const float* pe = L.get("decoder.pos_embedding_freq.weight", (int64_t)nn * 256);
@@ -336,12 +294,12 @@ extern "C" int etd_extractor_create(const etd_ext_cfg* cfg, const char* const* n
         for (int k = 0; k < 256; ++k) s += (double)pe[r * 256 + k] * qw[o * 256 + k];
         q0[(size_t)r * 256 + o] = (float)s;
       }
-    int rc = up_bf16(P, &e->q0, q0.data(), q0.size()); if (rc) return fail(rc);
-    rc = up_bf16(P, &e->trg0, pe, (size_t)nn * 256); if (rc) return fail(rc);
-    rc = up_f32(P, &e->pos_time, pt, (size_t)e->nf * 256); if (rc) return fail(rc);
+    ETD_TRY_OR(fail, up_bf16(P, &e->q0, q0.data(), q0.size()));
+    ETD_TRY_OR(fail, up_bf16(P, &e->trg0, pe, (size_t)nn * 256));
+    ETD_TRY_OR(fail, P.upload(&e->pos_time, pt, (size_t)e->nf * 256));
   }
-  { int rc = load_heads(P, L, "time", &e->head_time); if (rc) return fail(rc);
-    rc = load_heads(P, L, "freq", &e->head_freq); if (rc) return fail(rc); }
+  ETD_TRY_OR(fail, load_heads(P, L, "time", &e->head_time));
+  ETD_TRY_OR(fail, load_heads(P, L, "freq", &e->head_freq));
 
   // ---- workspaces
   const size_t MTe = (size_t)e->wb * e->fc * 256;           // encoder tokens per chunk
@@ -349,28 +307,26 @@ extern "C" int etd_extractor_create(const etd_ext_cfg* cfg, const char* const* n
   const size_t MT = MTe > MTt ? MTe : MTt;
   const size_t MQ = (size_t)e->wb * e->fc * e->nn;          // freq-decoder query tokens per chunk
   e->MT = MT; e->MQ = MQ; e->MTe = MTe;
-  int rc = 0;
-  rc = rc ? rc : P.alloc(&e->X, MT * 256);
-  rc = rc ? rc : P.alloc(&e->X1, MT * 256);
-  rc = rc ? rc : P.alloc(&e->QK, MT * 512);
-  rc = rc ? rc : P.alloc(&e->VT, MT * 256, true);
-  rc = rc ? rc : P.alloc(&e->AO, MT * 256);
-  rc = rc ? rc : P.alloc(&e->HF, MT * 512);
-  rc = rc ? rc : P.alloc(&e->Kc, 3 * MTe * 256);
-  rc = rc ? rc : P.alloc(&e->VTc, 3 * MTe * 256, true);
-  rc = rc ? rc : P.alloc(&e->Tq, MQ * 256);
-  rc = rc ? rc : P.alloc(&e->T1, MQ * 256);
-  rc = rc ? rc : P.alloc(&e->Tfreq, MQ * 256);
-  rc = rc ? rc : P.alloc(&e->QKd, MQ * 512);
-  rc = rc ? rc : P.alloc(&e->VTd, (size_t)e->wb * e->fc * 4 * 64 * 128, true);   // S = nn <= 128 padded to 128; pad stays 0
-  rc = rc ? rc : P.alloc(&e->AOd, MQ * 256);
-  rc = rc ? rc : P.alloc(&e->HFd, MQ * 512);
-  rc = rc ? rc : P.alloc(&e->Qd, MQ * 256);
-  rc = rc ? rc : P.alloc(&e->TI, MTt * 256);
-  rc = rc ? rc : P.alloc(&e->KVimg, MT * 512);
-  rc = rc ? rc : P.alloc(&e->KVcimg, 3 * MTe * 512);
-  if (rc) return fail(rc);
-  if (hipDeviceSynchronize() != hipSuccess) { g_etd_err = "extractor_create: device synchronisation failed"; return fail(ETD_EHIP); }
+  ETD_TRY_OR(fail, P.alloc(&e->X, MT * 256));
+  ETD_TRY_OR(fail, P.alloc(&e->X1, MT * 256));
+  ETD_TRY_OR(fail, P.alloc(&e->QK, MT * 512));
+  ETD_TRY_OR(fail, P.alloc(&e->VT, MT * 256, true));
+  ETD_TRY_OR(fail, P.alloc(&e->AO, MT * 256));
+  ETD_TRY_OR(fail, P.alloc(&e->HF, MT * 512));
+  ETD_TRY_OR(fail, P.alloc(&e->Kc, 3 * MTe * 256));
+  ETD_TRY_OR(fail, P.alloc(&e->VTc, 3 * MTe * 256, true));
+  ETD_TRY_OR(fail, P.alloc(&e->Tq, MQ * 256));
+  ETD_TRY_OR(fail, P.alloc(&e->T1, MQ * 256));
+  ETD_TRY_OR(fail, P.alloc(&e->Tfreq, MQ * 256));
+  ETD_TRY_OR(fail, P.alloc(&e->QKd, MQ * 512));
+  ETD_TRY_OR(fail, P.alloc(&e->VTd, (size_t)e->wb * e->fc * 4 * 64 * 128, true));   // S = nn <= 128 padded to 128; pad stays 0
+  ETD_TRY_OR(fail, P.alloc(&e->AOd, MQ * 256));
+  ETD_TRY_OR(fail, P.alloc(&e->HFd, MQ * 512));
+  ETD_TRY_OR(fail, P.alloc(&e->Qd, MQ * 256));
+  ETD_TRY_OR(fail, P.alloc(&e->TI, MTt * 256));
+  ETD_TRY_OR(fail, P.alloc(&e->KVimg, MT * 512));
+  ETD_TRY_OR(fail, P.alloc(&e->KVcimg, 3 * MTe * 512));
+  ETD_TRY_OR(fail, sync());
   *out = e;
   return ETD_OK;
 }

@@ -5,7 +5,6 @@
 // any ragged batch and across chunks.  DESIGN.md "Beat-Transformer engine" has the bounds, the layout and the FLOP formula.
 #include <cmath>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
@@ -270,17 +269,17 @@ __global__ __launch_bounds__(256) void k_beat_tempo(const float* __restrict__ pa
 // ================================================================================================ host: the engine
 namespace {
 
-struct G3Lin { uint16_t* Wp = nullptr; float* b = nullptr; int N = 0, Npad = 0, K = 0, w_log2 = 0, x_log2 = 0; };
 struct TimeLayer { float *ln1g, *ln1b, *ln2g, *ln2b, *Er; G3Lin qkv, l1, l2; };
 struct InstrLayer { float *ln1g, *ln1b, *ln2g, *ln2b; G3Lin inp, outp, l1, l2; };
-
-struct HostW { const float* p; int64_t n; };
+// the checkpoint's tensors of one layer (host pointers into the caller's arrays)
+struct TimeHostW { const float *Wq[3], *bq[3], *Er, *W1, *c1, *W2, *c2, *g1, *b1, *g2, *b2; };
+struct InstrHostW { const float *Wi, *bi, *Wo, *bo, *W1, *c1, *W2, *c2, *g1, *b1, *g2, *b2; };
 
 }  // namespace
 
 struct etd_beat {
   etd_beat_cfg cfg;
-  std::vector<void*> allocs;               // weights (freed in destroy)
+  DevPool pool;                            // weights (freed in destroy)
   float *c1w = nullptr, *c1b = nullptr;
   G3Lin c2, c3;
   std::vector<TimeLayer> tl;
@@ -296,33 +295,9 @@ struct etd_beat {
 
 namespace {
 
-int alloc_dev(etd_beat* e, void** p, size_t bytes) {
-  HIP_TRY(hipMalloc(p, bytes + 256));
-  e->allocs.push_back(*p);
-  return ETD_OK;
-}
-int up(etd_beat* e, float** dst, const float* src, size_t n) {
-  ETD_TRY(alloc_dev(e, (void**)dst, n * 4));
-  HIP_TRY(hipMemcpy(*dst, src, n * 4, hipMemcpyHostToDevice));
-  return ETD_OK;
-}
-// W [N][K] (already in the GEMM's k order) + bias -> planes and a bias padded to Npad; x_bound: provable bound of the GEMM's input elements
-int up_lin(etd_beat* e, G3Lin* L, const float* W, const float* b, int N, int K, float x_bound) {
-  L->N = N; L->K = K; L->Npad = (N + 127) / 128 * 128;
-  std::vector<uint16_t> planes(g3_packed_elems(L->Npad, K));
-  L->w_log2 = g3_pack_weights_host(W, N, L->Npad, K, planes.data());
-  L->x_log2 = g3_scale_log2(x_bound);
-  ETD_TRY(alloc_dev(e, (void**)&L->Wp, planes.size() * 2));
-  HIP_TRY(hipMemcpy(L->Wp, planes.data(), planes.size() * 2, hipMemcpyHostToDevice));
-  std::vector<float> bp(L->Npad, 0.f);
-  memcpy(bp.data(), b, (size_t)N * 4);
-  return up(e, &L->b, bp.data(), bp.size());
-}
-
+// launch_gemm3 at every row count, on purpose: the outputs are then bit-identical across batch layouts
 int gemm(const G3Lin& L, const float* X, int M, int epi, float* Y, float* resid, hipStream_t st, int ldx = 0) {
-  DGemmArgs a{};
-  a.X = X; a.ldx = ldx ? ldx : L.K; a.M = M; a.N = L.N; a.K = L.K; a.Npad = L.Npad; a.bias = L.b;
-  a.Wp = L.Wp; a.w_log2 = L.w_log2; a.x_log2 = L.x_log2;
+  DGemmArgs a = g3_lin_args(L, X, ldx ? ldx : L.K, M);
   a.Y = Y; a.ldy = L.N;
   if (epi == DEPI_RESID) { a.hin = resid; a.hout = resid; a.add = nullptr; }
   return launch_gemm3(a, epi, st);
@@ -453,99 +428,92 @@ extern "C" int etd_beat_create(const etd_beat_cfg* cfg, const char* const* names
   if (c.ntoken < 1 || c.ntoken > 64) ETD_FAIL(ETD_EINVAL, "beat_create: ntoken = %d (1 .. 64)", c.ntoken);
   if (c.tempo_out < 1 || c.tempo_out > 65536) ETD_FAIL(ETD_EINVAL, "beat_create: tempo_out = %d", c.tempo_out);
   if (c.max_rows < 1 || c.max_rows > (1 << 24)) ETD_FAIL(ETD_EINVAL, "beat_create: max_rows = %d (1 .. 2^24)", c.max_rows);
-  std::map<std::string, HostW> W;
-  for (int i = 0; i < n; ++i) {
-    if (!names[i]) ETD_FAIL(ETD_EINVAL, "beat_create: null name %d", i);
-    W[names[i]] = {host_ptrs[i], numels[i]};
-  }
+  const WeightTable T(names, host_ptrs, numels, n);
+  if (T.null_name >= 0) ETD_FAIL(ETD_EINVAL, "beat_create: null name %d", T.null_name);
   const int D = 256, H = c.d_hid;
-  // every key the model reads, with its element count, checked before anything touches the GPU
-  std::vector<std::pair<std::string, int64_t>> need = {{"conv1.weight", 32 * 15}, {"conv1.bias", 32}, {"conv2.weight", 64 * 32 * 12}, {"conv2.bias", 64},
-                                                       {"conv3.weight", (int64_t)D * 64 * 18}, {"conv3.bias", D}, {"out_linear.weight", (int64_t)c.ntoken * D},
-                                                       {"out_linear.bias", c.ntoken}, {"out_linear_t.weight", (int64_t)c.tempo_out * D}, {"out_linear_t.bias", c.tempo_out}};
+  // every tensor the model reads, fetched with its element count before anything touches the GPU; the first failure is the one reported
+  bool ok = true;
+  auto get = [&](const std::string& k, int64_t numel) {
+    const float* p = ok ? T.get(k, numel) : nullptr;
+    if (ok && !p) { ok = false; g_etd_err = "beat_create: " + g_etd_err; }
+    return p;
+  };
+  const float *w1 = get("conv1.weight", 32 * 15), *b1 = get("conv1.bias", 32), *w2 = get("conv2.weight", 64 * 32 * 12), *b2 = get("conv2.bias", 64);
+  const float *w3 = get("conv3.weight", (int64_t)D * 64 * 18), *b3 = get("conv3.bias", D);
+  const float *ow = get("out_linear.weight", (int64_t)c.ntoken * D), *ob = get("out_linear.bias", c.ntoken);
+  const float *tw = get("out_linear_t.weight", (int64_t)c.tempo_out * D), *tb = get("out_linear_t.bias", c.tempo_out);
+  std::vector<TimeHostW> tlw(c.nlayers);
+  std::vector<InstrHostW> ilw;
   for (int l = 0; l < c.nlayers; ++l) {
     const std::string p = "Transformer_layers.time_attention_" + std::to_string(l) + ".";
-    for (const char* m : {"query", "key", "value"}) { need.push_back({p + "self_attn." + m + ".weight", (int64_t)D * D}); need.push_back({p + "self_attn." + m + ".bias", D}); }
-    need.push_back({p + "self_attn.Er", 8 * 32 * 5});
-    need.push_back({p + "linear1.weight", (int64_t)H * D}); need.push_back({p + "linear1.bias", H});
-    need.push_back({p + "linear2.weight", (int64_t)D * H}); need.push_back({p + "linear2.bias", D});
-    for (const char* m : {"norm1", "norm2"}) { need.push_back({p + m + ".weight", D}); need.push_back({p + m + ".bias", D}); }
+    TimeHostW& t = tlw[l];
+    const char* parts[3] = {"query", "key", "value"};
+    for (int j = 0; j < 3; ++j) { t.Wq[j] = get(p + "self_attn." + parts[j] + ".weight", (int64_t)D * D); t.bq[j] = get(p + "self_attn." + parts[j] + ".bias", D); }
+    t.Er = get(p + "self_attn.Er", 8 * 32 * 5);
+    t.W1 = get(p + "linear1.weight", (int64_t)H * D); t.c1 = get(p + "linear1.bias", H);
+    t.W2 = get(p + "linear2.weight", (int64_t)D * H); t.c2 = get(p + "linear2.bias", D);
+    t.g1 = get(p + "norm1.weight", D); t.b1 = get(p + "norm1.bias", D); t.g2 = get(p + "norm2.weight", D); t.b2 = get(p + "norm2.bias", D);
     if (l >= 3 && l <= 5) {
       const std::string q = "Transformer_layers.instr_attention_" + std::to_string(l) + ".";
-      need.push_back({q + "self_attn.in_proj_weight", (int64_t)3 * D * D}); need.push_back({q + "self_attn.in_proj_bias", 3 * D});
-      need.push_back({q + "self_attn.out_proj.weight", (int64_t)D * D}); need.push_back({q + "self_attn.out_proj.bias", D});
-      need.push_back({q + "linear1.weight", (int64_t)H * D}); need.push_back({q + "linear1.bias", H});
-      need.push_back({q + "linear2.weight", (int64_t)D * H}); need.push_back({q + "linear2.bias", D});
-      for (const char* m : {"norm1", "norm2"}) { need.push_back({q + m + ".weight", D}); need.push_back({q + m + ".bias", D}); }
+      ilw.emplace_back();
+      InstrHostW& i = ilw.back();
+      i.Wi = get(q + "self_attn.in_proj_weight", (int64_t)3 * D * D); i.bi = get(q + "self_attn.in_proj_bias", 3 * D);
+      i.Wo = get(q + "self_attn.out_proj.weight", (int64_t)D * D); i.bo = get(q + "self_attn.out_proj.bias", D);
+      i.W1 = get(q + "linear1.weight", (int64_t)H * D); i.c1 = get(q + "linear1.bias", H);
+      i.W2 = get(q + "linear2.weight", (int64_t)D * H); i.c2 = get(q + "linear2.bias", D);
+      i.g1 = get(q + "norm1.weight", D); i.b1 = get(q + "norm1.bias", D); i.g2 = get(q + "norm2.weight", D); i.b2 = get(q + "norm2.bias", D);
     }
   }
-  for (const auto& kv : need) {
-    auto it = W.find(kv.first);
-    if (it == W.end()) ETD_FAIL(ETD_EINVAL, "beat_create: missing weight '%s'", kv.first.c_str());
-    if (it->second.n != kv.second || !it->second.p)
-      ETD_FAIL(ETD_EINVAL, "beat_create: weight '%s' has %lld elements, expected %lld", kv.first.c_str(), (long long)it->second.n, (long long)kv.second);
-  }
-  auto get = [&](const std::string& k) { return W.at(k).p; };
+  if (!ok) return ETD_EINVAL;
 
   etd_beat* e = new etd_beat();
   e->cfg = c;
-  auto fail = [&](int rc) { for (void* p : e->allocs) (void)hipFree(p); delete e; return rc; };
-#define BT(x) do { const int _rc = (x); if (_rc != ETD_OK) return fail(_rc); } while (0)
+  DevPool& P = e->pool;
+  auto fail = [&](int rc) { P.free_all(); delete e; return rc; };
   // conv1 as [co][kt * 3 + kw]; its output bound: |b| + 80 ||w||_1 (features |x| <= 80, the precondition)
-  const float* w1 = get("conv1.weight"); const float* b1 = get("conv1.bias");
-  BT(up(e, &e->c1w, w1, 32 * 15)); BT(up(e, &e->c1b, b1, 32));
+  ETD_TRY_OR(fail, P.upload(&e->c1w, w1, 32 * 15)); ETD_TRY_OR(fail, P.upload(&e->c1b, b1, 32));
   const float bx1 = g3_bound_linear(w1, b1, 32, 15, 80.f);
   {  // conv2: [co][ci][0][kw] -> [co][kw * 32 + ci]
-    const float* w = get("conv2.weight");
     std::vector<float> p((size_t)64 * BEAT_K2);
-    for (int co = 0; co < 64; ++co) for (int ci = 0; ci < 32; ++ci) for (int kw = 0; kw < 12; ++kw) p[(size_t)co * BEAT_K2 + kw * 32 + ci] = w[(co * 32 + ci) * 12 + kw];
-    BT(up_lin(e, &e->c2, p.data(), get("conv2.bias"), 64, BEAT_K2, bx1));
-    const float bx2 = g3_bound_linear(p.data(), get("conv2.bias"), 64, BEAT_K2, bx1);
+    for (int co = 0; co < 64; ++co) for (int ci = 0; ci < 32; ++ci) for (int kw = 0; kw < 12; ++kw) p[(size_t)co * BEAT_K2 + kw * 32 + ci] = w2[(co * 32 + ci) * 12 + kw];
+    ETD_TRY_OR(fail, g3_lin_upload(P, p.data(), b2, 64, BEAT_K2, bx1, &e->c2));
+    const float bx2 = g3_bound_linear(p.data(), b2, 64, BEAT_K2, bx1);
     // conv3: [co][ci][kt][kw] -> [co][kt * 384 + kw * 64 + ci]
-    const float* w3 = get("conv3.weight");
     std::vector<float> p3((size_t)D * BEAT_K3);
     for (int co = 0; co < D; ++co) for (int ci = 0; ci < 64; ++ci) for (int kt = 0; kt < 3; ++kt) for (int kw = 0; kw < 6; ++kw)
       p3[(size_t)co * BEAT_K3 + kt * 384 + kw * 64 + ci] = w3[((co * 64 + ci) * 3 + kt) * 6 + kw];
-    BT(up_lin(e, &e->c3, p3.data(), get("conv3.bias"), D, BEAT_K3, bx2));
+    ETD_TRY_OR(fail, g3_lin_upload(P, p3.data(), b3, D, BEAT_K3, bx2, &e->c3));
   }
   e->tl.resize(c.nlayers);
   for (int l = 0; l < c.nlayers; ++l) {
-    const std::string p = "Transformer_layers.time_attention_" + std::to_string(l) + ".";
+    const TimeHostW& t = tlw[l];
     TimeLayer& L = e->tl[l];
-    const float *g1 = get(p + "norm1.weight"), *bb1 = get(p + "norm1.bias"), *g2 = get(p + "norm2.weight"), *bb2 = get(p + "norm2.bias");
-    BT(up(e, &L.ln1g, g1, D)); BT(up(e, &L.ln1b, bb1, D)); BT(up(e, &L.ln2g, g2, D)); BT(up(e, &L.ln2b, bb2, D));
-    BT(up(e, &L.Er, get(p + "self_attn.Er"), 8 * 32 * 5));
+    ETD_TRY_OR(fail, P.upload(&L.ln1g, t.g1, D)); ETD_TRY_OR(fail, P.upload(&L.ln1b, t.b1, D)); ETD_TRY_OR(fail, P.upload(&L.ln2g, t.g2, D)); ETD_TRY_OR(fail, P.upload(&L.ln2b, t.b2, D));
+    ETD_TRY_OR(fail, P.upload(&L.Er, t.Er, 8 * 32 * 5));
     std::vector<float> wq((size_t)3 * D * D), bq(3 * D);
-    const char* parts[3] = {"query", "key", "value"};
     for (int j = 0; j < 3; ++j) {
-      memcpy(wq.data() + (size_t)j * D * D, get(p + "self_attn." + parts[j] + ".weight"), (size_t)D * D * 4);
-      memcpy(bq.data() + j * D, get(p + "self_attn." + parts[j] + ".bias"), D * 4);
+      memcpy(wq.data() + (size_t)j * D * D, t.Wq[j], (size_t)D * D * 4);
+      memcpy(bq.data() + j * D, t.bq[j], D * 4);
     }
-    BT(up_lin(e, &L.qkv, wq.data(), bq.data(), 3 * D, D, g3_bound_ln(g1, bb1, D)));
-    const float *W1 = get(p + "linear1.weight"), *c1 = get(p + "linear1.bias");
-    BT(up_lin(e, &L.l1, W1, c1, H, D, g3_bound_ln(g2, bb2, D)));
-    BT(up_lin(e, &L.l2, get(p + "linear2.weight"), get(p + "linear2.bias"), D, H, g3_bound_linear_of_ln(W1, c1, H, D, g2, bb2)));      // |gelu(y)| <= |y|
+    ETD_TRY_OR(fail, g3_lin_upload(P, wq.data(), bq.data(), 3 * D, D, g3_bound_ln(t.g1, t.b1, D), &L.qkv));
+    ETD_TRY_OR(fail, g3_lin_upload(P, t.W1, t.c1, H, D, g3_bound_ln(t.g2, t.b2, D), &L.l1));
+    ETD_TRY_OR(fail, g3_lin_upload(P, t.W2, t.c2, D, H, g3_bound_linear_of_ln(t.W1, t.c1, H, D, t.g2, t.b2), &L.l2));      // |gelu(y)| <= |y|
   }
-  for (int l = 3; l <= 5 && l < c.nlayers; ++l) {
-    const std::string q = "Transformer_layers.instr_attention_" + std::to_string(l) + ".";
+  for (const InstrHostW& i : ilw) {
     e->il.emplace_back();
     InstrLayer& I = e->il.back();
-    const float *g1 = get(q + "norm1.weight"), *bb1 = get(q + "norm1.bias"), *g2 = get(q + "norm2.weight"), *bb2 = get(q + "norm2.bias");
-    BT(up(e, &I.ln1g, g1, D)); BT(up(e, &I.ln1b, bb1, D)); BT(up(e, &I.ln2g, g2, D)); BT(up(e, &I.ln2b, bb2, D));
-    const float *Wi = get(q + "self_attn.in_proj_weight"), *bi = get(q + "self_attn.in_proj_bias");
-    BT(up_lin(e, &I.inp, Wi, bi, 3 * D, D, g3_bound_ln(g1, bb1, D)));
+    ETD_TRY_OR(fail, P.upload(&I.ln1g, i.g1, D)); ETD_TRY_OR(fail, P.upload(&I.ln1b, i.b1, D)); ETD_TRY_OR(fail, P.upload(&I.ln2g, i.g2, D)); ETD_TRY_OR(fail, P.upload(&I.ln2b, i.b2, D));
+    ETD_TRY_OR(fail, g3_lin_upload(P, i.Wi, i.bi, 3 * D, D, g3_bound_ln(i.g1, i.b1, D), &I.inp));
     std::vector<float> rb(3 * D);
-    g3_row_bounds_of_ln(Wi, bi, 3 * D, D, g1, bb1, rb.data());
+    g3_row_bounds_of_ln(i.Wi, i.bi, 3 * D, D, i.g1, i.b1, rb.data());
     float bv = 0.f;
     for (int j = 2 * D; j < 3 * D; ++j) bv = fmaxf(bv, rb[j]);        // attention output: a convex combination of value rows
-    BT(up_lin(e, &I.outp, get(q + "self_attn.out_proj.weight"), get(q + "self_attn.out_proj.bias"), D, D, bv));
-    const float *W1 = get(q + "linear1.weight"), *c1 = get(q + "linear1.bias");
-    BT(up_lin(e, &I.l1, W1, c1, H, D, g3_bound_ln(g2, bb2, D)));
-    BT(up_lin(e, &I.l2, get(q + "linear2.weight"), get(q + "linear2.bias"), D, H, g3_bound_linear_of_ln(W1, c1, H, D, g2, bb2)));      // |relu(y)| <= |y|
+    ETD_TRY_OR(fail, g3_lin_upload(P, i.Wo, i.bo, D, D, bv, &I.outp));
+    ETD_TRY_OR(fail, g3_lin_upload(P, i.W1, i.c1, H, D, g3_bound_ln(i.g2, i.b2, D), &I.l1));
+    ETD_TRY_OR(fail, g3_lin_upload(P, i.W2, i.c2, D, H, g3_bound_linear_of_ln(i.W1, i.c1, H, D, i.g2, i.b2), &I.l2));      // |relu(y)| <= |y|
   }
-  BT(up(e, &e->ow, get("out_linear.weight"), (size_t)c.ntoken * D)); BT(up(e, &e->ob, get("out_linear.bias"), c.ntoken));
-  BT(up(e, &e->tw, get("out_linear_t.weight"), (size_t)c.tempo_out * D)); BT(up(e, &e->tb, get("out_linear_t.bias"), c.tempo_out));
-#undef BT
+  ETD_TRY_OR(fail, P.upload(&e->ow, ow, (size_t)c.ntoken * D)); ETD_TRY_OR(fail, P.upload(&e->ob, ob, c.ntoken));
+  ETD_TRY_OR(fail, P.upload(&e->tw, tw, (size_t)c.tempo_out * D)); ETD_TRY_OR(fail, P.upload(&e->tb, tb, c.tempo_out));
   *out = e;
   return ETD_OK;
 }
@@ -553,7 +521,7 @@ extern "C" int etd_beat_create(const etd_beat_cfg* cfg, const char* const* names
 extern "C" void etd_beat_destroy(etd_beat* e) {
   if (!e) return;
   (void)hipDeviceSynchronize();
-  for (void* p : e->allocs) (void)hipFree(p);
+  e->pool.free_all();
   if (e->ws) (void)hipFree(e->ws);
   if (e->tab) (void)hipFree(e->tab);
   delete e;

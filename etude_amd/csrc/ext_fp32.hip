@@ -15,9 +15,8 @@
 
 namespace {
 
-struct Lin32 { uint16_t* Wp = nullptr; float* b = nullptr; int N = 0, Npad = 0, K = 0, w_log2 = 0, x_log2 = 0; };   // weights as hi / lo f16 planes (g3_pack_weights_host)
-struct Enc32 { Lin32 qkv, o, f1, f2; float *g = nullptr, *be = nullptr; int q_log2 = 0, k_log2 = 0, v_log2 = 0; };
-struct Dec32 { Lin32 qkv_s, o_s, q_c, kv_c, o_c, f1, f2; float *g = nullptr, *be = nullptr; bool has_self = false;
+struct Enc32 { G3Lin qkv, o, f1, f2; float *g = nullptr, *be = nullptr; int q_log2 = 0, k_log2 = 0, v_log2 = 0; };
+struct Dec32 { G3Lin qkv_s, o_s, q_c, kv_c, o_c, f1, f2; float *g = nullptr, *be = nullptr; bool has_self = false;
                int qs_log2 = 0, ks_log2 = 0, vs_log2 = 0, qc_log2 = 0, kc_log2 = 0, vc_log2 = 0; };
 // what is known about a GEMM input at load time: the output of a LayerNorm with (g, b) over n features, or anything bounded elementwise by `elem`
 struct InB { const float* g = nullptr; const float* b = nullptr; int n = 256; float elem = 0.f; };
@@ -31,79 +30,52 @@ struct Ext32 {
   int H = 256, PF = 512, NB = 256, NH = 4, taps = 65, LE = 3, LD = 3, NVEL = 128, HLD = 256;     // hid, pf, bins, heads, 2 margin + 1, layer counts, velocities, head logits row pitch
   bool dflt = true;                                                    // the reference's default architecture: the specialised forms of the small kernels
   float emb_scale = 16.f;                                              // sqrt(hid_dim)  amt_apc.py:66,101,204
-  std::vector<void*> allocs;
+  DevPool pool;
   float *Wf = nullptr, *bfold = nullptr, *pos_freq_enc = nullptr;      // folded conv+linear [hid][taps], bias [hid], [bins][hid]
   std::vector<Enc32> enc, tim;
   std::vector<Dec32> dec;
   float *q0 = nullptr, *trg0 = nullptr, *pos_time = nullptr;
-  Lin32 head_time, head_freq;
+  G3Lin head_time, head_freq;
   // one window of workspaces
   float *X = nullptr, *X1 = nullptr, *QKV = nullptr, *AO = nullptr, *HF = nullptr, *T = nullptr, *KV = nullptr;
   float *D0 = nullptr, *D1 = nullptr, *D2 = nullptr, *Qd = nullptr, *TI = nullptr, *HL = nullptr;
   size_t Me = 0, Mq = 0;
-
-  template <typename Tp> int alloc(Tp** p, size_t n) {
-    void* q = nullptr;
-    HIP_TRY(hipMalloc(&q, n * sizeof(Tp) + 256));
-    allocs.push_back(q);
-    *p = (Tp*)q;
-    return ETD_OK;
-  }
 };
 
 namespace {
 
-const float* wget(const WeightMap& w, const std::string& k, int64_t numel) {
-  auto it = w.find(k);
-  if (it == w.end()) { g_etd_err = "missing weight '" + k + "'"; return nullptr; }
-  if (it->second.second != numel) { g_etd_err = "weight '" + k + "' has " + std::to_string(it->second.second) + " elements, expected " + std::to_string(numel); return nullptr; }
-  return it->second.first;
-}
-int up(Ext32* e, float** dst, const float* src, size_t n) {
-  ETD_TRY(e->alloc(dst, n));
-  HIP_TRY(hipMemcpy(*dst, src, n * 4, hipMemcpyHostToDevice));
-  return ETD_OK;
-}
 // several [out_i][K] linears stacked along the output dimension, rows padded with zeros to a multiple of 128; `in` describes the input (plane scale of X and
 // the bounds of the outputs, one per stacked linear, which become the plane scales of whatever consumes them)
-int load_stack(Ext32* e, const WeightMap& w, const std::vector<std::string>& pfx, const std::vector<int>& outs, int K, const InB& in, Lin32* l, std::vector<float>* out_bounds = nullptr) {
+int load_stack(Ext32* e, const WeightTable& w, const std::vector<std::string>& pfx, const std::vector<int>& outs, int K, const InB& in, G3Lin* l, std::vector<float>* out_bounds = nullptr) {
   int N = 0;
   for (int o : outs) N += o;
-  const int Npad = (N + 127) / 128 * 128;
-  std::vector<float> W((size_t)N * K, 0.f), b(Npad, 0.f);
+  std::vector<float> W((size_t)N * K, 0.f), b(N, 0.f);
   int r = 0;
   if (out_bounds) out_bounds->clear();
   for (size_t i = 0; i < pfx.size(); ++i) {
-    const float* Wi = wget(w, pfx[i] + ".weight", (int64_t)outs[i] * K);
-    const float* bi = wget(w, pfx[i] + ".bias", outs[i]);
+    const float* Wi = w.get(pfx[i] + ".weight", (int64_t)outs[i] * K);
+    const float* bi = w.get(pfx[i] + ".bias", outs[i]);
     if (!Wi || !bi) return ETD_EINVAL;
     memcpy(W.data() + (size_t)r * K, Wi, (size_t)outs[i] * K * 4);
     memcpy(b.data() + r, bi, (size_t)outs[i] * 4);
     if (out_bounds) out_bounds->push_back(in.g ? g3_bound_linear_of_ln(Wi, bi, outs[i], K, in.g, in.b) : g3_bound_linear(Wi, bi, outs[i], K, in.elem));
     r += outs[i];
   }
-  l->N = N; l->Npad = Npad; l->K = K;
-  std::vector<uint16_t> planes(g3_packed_elems(Npad, K));
-  l->w_log2 = g3_pack_weights_host(W.data(), N, Npad, K, planes.data());
-  l->x_log2 = g3_scale_log2(in_bound(in));
-  ETD_TRY(e->alloc(&l->Wp, planes.size()));
-  HIP_TRY(hipMemcpy(l->Wp, planes.data(), planes.size() * 2, hipMemcpyHostToDevice));
-  ETD_TRY(up(e, &l->b, b.data(), b.size()));
-  return ETD_OK;
+  return g3_lin_upload(e->pool, W.data(), b.data(), N, K, in_bound(in), l);
 }
-int load_ln(Ext32* e, const WeightMap& w, const std::string& p, float** g, float** b) {
-  const float* gw = wget(w, p + ".weight", e->H);
-  const float* bw = wget(w, p + ".bias", e->H);
+int load_ln(Ext32* e, const WeightTable& w, const std::string& p, float** g, float** b) {
+  const float* gw = w.get(p + ".weight", e->H);
+  const float* bw = w.get(p + ".bias", e->H);
   if (!gw || !bw) return ETD_EINVAL;
-  ETD_TRY(up(e, g, gw, e->H));
-  ETD_TRY(up(e, b, bw, e->H));
+  ETD_TRY(e->pool.upload(g, gw, e->H));
+  ETD_TRY(e->pool.upload(b, bw, e->H));
   return ETD_OK;
 }
 // one EncoderLayer (amt_apc.py:236-259); `in` = what is known about its input; *out = its output (the layer's own LayerNorm)
-int load_enc(Ext32* e, const WeightMap& w, const std::string& p, const InB& in, Enc32* l, InB* out) {
+int load_enc(Ext32* e, const WeightTable& w, const std::string& p, const InB& in, Enc32* l, InB* out) {
   const int H = e->H, PF = e->PF;
-  const float* gw = wget(w, p + ".layer_norm.weight", H);
-  const float* bw = wget(w, p + ".layer_norm.bias", H);
+  const float* gw = w.get(p + ".layer_norm.weight", H);
+  const float* bw = w.get(p + ".layer_norm.bias", H);
   if (!gw || !bw) return ETD_EINVAL;
   const InB ln{gw, bw, H, 0.f};
   std::vector<float> ob;
@@ -275,9 +247,9 @@ __global__ void k32_freq2time(const float* __restrict__ src, float* __restrict__
 }
 
 // ================================================================================================ launch helpers
-int gemm32(const float* X, int ldx, const Lin32& w, int M, float* Y, int ldy, hipStream_t st, int epi = DEPI_BIAS) {
-  DGemmArgs a = {};
-  a.X = X; a.ldx = ldx; a.Wp = w.Wp; a.w_log2 = w.w_log2; a.x_log2 = w.x_log2; a.bias = w.b; a.M = M; a.N = w.N; a.Npad = w.Npad; a.K = w.K; a.Y = Y; a.ldy = ldy;
+int gemm32(const float* X, int ldx, const G3Lin& w, int M, float* Y, int ldy, hipStream_t st, int epi = DEPI_BIAS) {
+  DGemmArgs a = g3_lin_args(w, X, ldx, M);
+  a.Y = Y; a.ldy = ldy;
   return launch_gemm3(a, epi, st);
 }
 int add_ln(const Ext32* e, const float* A, const float* R, int r_mod, const float* g, const float* b, float* Y, int M, hipStream_t st) {
@@ -318,7 +290,7 @@ int tap32(const Ext32* e, void* const* tap, int stage, int layer, const float* s
 
 }  // namespace
 
-int ext32_create(const etd_ext_cfg& c, const WeightMap& w, Ext32** out) {
+int ext32_create(const etd_ext_cfg& c, const WeightTable& w, Ext32** out) {
   if (c.hid_dim < 64 || c.hid_dim % 64 || c.hid_dim > 512 || c.n_heads * 64 != c.hid_dim || c.pf_dim < 32 || c.pf_dim % 32 || c.n_bin < 32 || c.n_bin % 32 ||
       c.n_margin < 0 || c.n_margin > 64 || c.cnn_channel < 1 || c.cnn_kernel < 1 || c.cnn_kernel > 2 * c.n_margin + 1 || c.n_layers_enc < 1 || c.n_layers_dec < 1 ||
       c.n_velocity < 1 || c.n_velocity > 128)
@@ -335,11 +307,11 @@ int ext32_create(const etd_ext_cfg& c, const WeightMap& w, Ext32** out) {
   auto fail = [&](int rc) { ext32_destroy(e); return rc; };
   float x0_bound = 0.f;
   {
-    const float* cw = wget(w, "encoder.conv.weight", (int64_t)CH * CK);
-    const float* cb = wget(w, "encoder.conv.bias", CH);
-    const float* tw = wget(w, "encoder.tok_embedding_freq.weight", (int64_t)H * CH * P);
-    const float* tb = wget(w, "encoder.tok_embedding_freq.bias", H);
-    const float* pe = wget(w, "encoder.pos_embedding_freq.weight", (int64_t)NB * H);
+    const float* cw = w.get("encoder.conv.weight", (int64_t)CH * CK);
+    const float* cb = w.get("encoder.conv.bias", CH);
+    const float* tw = w.get("encoder.tok_embedding_freq.weight", (int64_t)H * CH * P);
+    const float* tb = w.get("encoder.tok_embedding_freq.bias", H);
+    const float* pe = w.get("encoder.pos_embedding_freq.weight", (int64_t)NB * H);
     if (!cw || !cb || !tw || !tb || !pe) return fail(ETD_EINVAL);
     // Conv2d(1, CH, (1, CK)) then Linear(CH * P, hid) over the unfolded taps = ONE [hid][taps] map, folded in double       amt_apc.py:79-99
     std::vector<float> Wf((size_t)H * taps), bf(H);
@@ -356,9 +328,9 @@ int ext32_create(const etd_ext_cfg& c, const WeightMap& w, Ext32** out) {
       for (int t = 0; t < taps; ++t) Wf[(size_t)o * taps + t] = (float)fold[t];
       bf[o] = (float)bacc;
     }
-    int rc = up(e, &e->Wf, Wf.data(), Wf.size()); if (rc) return fail(rc);
-    rc = up(e, &e->bfold, bf.data(), H); if (rc) return fail(rc);
-    rc = up(e, &e->pos_freq_enc, pe, (size_t)NB * H); if (rc) return fail(rc);
+    ETD_TRY_OR(fail, e->pool.upload(&e->Wf, Wf.data(), Wf.size()));
+    ETD_TRY_OR(fail, e->pool.upload(&e->bfold, bf.data(), H));
+    ETD_TRY_OR(fail, e->pool.upload(&e->pos_freq_enc, pe, (size_t)NB * H));
     // bound of the embedding (acc + b) * sqrt(hid) + pos for log-mel features in [-F, F]: log(mel + 1e-8) >= -18.4, and |audio| <= 1 keeps it below 15; the padding value
     // of the HFT_Transformer wrapper is -80
     const float F = fmaxf(fabsf(c.min_value), 32.f);
@@ -367,16 +339,16 @@ int ext32_create(const etd_ext_cfg& c, const WeightMap& w, Ext32** out) {
     x0_bound = e->emb_scale * g3_bound_linear(Wf.data(), bf.data(), H, taps, F) + pmax;
   }
   InB cur{nullptr, nullptr, H, x0_bound};
-  for (int i = 0; i < e->LE; ++i) { int rc = load_enc(e, w, "encoder.layers_freq." + std::to_string(i), cur, &e->enc[i], &cur); if (rc) return fail(rc); }
+  for (int i = 0; i < e->LE; ++i) ETD_TRY_OR(fail, load_enc(e, w, "encoder.layers_freq." + std::to_string(i), cur, &e->enc[i], &cur));
   const InB enc_out = cur;
   const int nn = e->nn;
-  const float* pe_d = wget(w, "decoder.pos_embedding_freq.weight", (int64_t)nn * H);
-  const float* pt = wget(w, "decoder.pos_embedding_time.weight", (int64_t)e->nf * H);
+  const float* pe_d = w.get("decoder.pos_embedding_freq.weight", (int64_t)nn * H);
+  const float* pt = w.get("decoder.pos_embedding_time.weight", (int64_t)e->nf * H);
   if (!pe_d || !pt) return fail(ETD_EINVAL);
   float q0_bound = 0.f;
   {
-    const float* qw = wget(w, "decoder.layer_zero_freq.encoder_attention.fc_q.weight", (int64_t)H * H);
-    const float* qb = wget(w, "decoder.layer_zero_freq.encoder_attention.fc_q.bias", H);
+    const float* qw = w.get("decoder.layer_zero_freq.encoder_attention.fc_q.weight", (int64_t)H * H);
+    const float* qb = w.get("decoder.layer_zero_freq.encoder_attention.fc_q.bias", H);
     if (!qw || !qb) return fail(ETD_EINVAL);
     std::vector<float> q0((size_t)nn * H);          // layer-zero queries are input independent: fc_q(pos_embedding_freq)   amt_apc.py:168-175
     for (int r = 0; r < nn; ++r)
@@ -386,9 +358,9 @@ int ext32_create(const etd_ext_cfg& c, const WeightMap& w, Ext32** out) {
         q0[(size_t)r * H + o] = s + qb[o];
         q0_bound = fmaxf(q0_bound, fabsf(s + qb[o]));
       }
-    int rc = up(e, &e->q0, q0.data(), q0.size()); if (rc) return fail(rc);
-    rc = up(e, &e->trg0, pe_d, (size_t)nn * H); if (rc) return fail(rc);
-    rc = up(e, &e->pos_time, pt, (size_t)e->nf * H); if (rc) return fail(rc);
+    ETD_TRY_OR(fail, e->pool.upload(&e->q0, q0.data(), q0.size()));
+    ETD_TRY_OR(fail, e->pool.upload(&e->trg0, pe_d, (size_t)nn * H));
+    ETD_TRY_OR(fail, e->pool.upload(&e->pos_time, pt, (size_t)e->nf * H));
   }
   // frequency decoder (amt_apc.py:261-320): layer 0 = cross attention of the constant note queries + FFN; the others = self attention, cross attention, FFN; one LayerNorm per layer
   InB dcur{};     // layers 1 ..: the previous layer's LayerNorm output
@@ -396,57 +368,49 @@ int ext32_create(const etd_ext_cfg& c, const WeightMap& w, Ext32** out) {
     const std::string p = i == 0 ? std::string("decoder.layer_zero_freq") : "decoder.layers_freq." + std::to_string(i - 1);
     Dec32& d = e->dec[i];
     d.has_self = i > 0;
-    const float* gw = wget(w, p + ".layer_norm.weight", H);
-    const float* bw = wget(w, p + ".layer_norm.bias", H);
+    const float* gw = w.get(p + ".layer_norm.weight", H);
+    const float* bw = w.get(p + ".layer_norm.bias", H);
     if (!gw || !bw) return fail(ETD_EINVAL);
     const InB ln{gw, bw, H, 0.f};
     std::vector<float> ob;
-    int rc;
     if (d.has_self) {
-      rc = load_stack(e, w, {p + ".self_attention.fc_q", p + ".self_attention.fc_k", p + ".self_attention.fc_v"}, {H, H, H}, H, dcur, &d.qkv_s, &ob); if (rc) return fail(rc);
+      ETD_TRY_OR(fail, load_stack(e, w, {p + ".self_attention.fc_q", p + ".self_attention.fc_k", p + ".self_attention.fc_v"}, {H, H, H}, H, dcur, &d.qkv_s, &ob));
       d.qs_log2 = g3_scale_log2(ob[0]); d.ks_log2 = g3_scale_log2(ob[1]); d.vs_log2 = g3_scale_log2(ob[2]);
-      rc = load_stack(e, w, {p + ".self_attention.fc_o"}, {H}, H, InB{nullptr, nullptr, H, ob[2]}, &d.o_s); if (rc) return fail(rc);
+      ETD_TRY_OR(fail, load_stack(e, w, {p + ".self_attention.fc_o"}, {H}, H, InB{nullptr, nullptr, H, ob[2]}, &d.o_s));
     }
-    // cross-attention queries: layer 0 the precomputed q0 (no GEMM at run time: the Lin32 is loaded for its bias / shape only), the others fc_q of the self-attention block's LayerNorm output
-    rc = load_stack(e, w, {p + ".encoder_attention.fc_q"}, {H}, H, d.has_self ? ln : InB{nullptr, nullptr, H, 1.f}, &d.q_c, &ob); if (rc) return fail(rc);
+    // cross-attention queries: layer 0 the precomputed q0 (no GEMM at run time: the G3Lin is loaded for its bias / shape only), the others fc_q of the self-attention block's LayerNorm output
+    ETD_TRY_OR(fail, load_stack(e, w, {p + ".encoder_attention.fc_q"}, {H}, H, d.has_self ? ln : InB{nullptr, nullptr, H, 1.f}, &d.q_c, &ob));
     d.qc_log2 = g3_scale_log2(d.has_self ? ob[0] : q0_bound);
-    rc = load_stack(e, w, {p + ".encoder_attention.fc_k", p + ".encoder_attention.fc_v"}, {H, H}, H, enc_out, &d.kv_c, &ob); if (rc) return fail(rc);
+    ETD_TRY_OR(fail, load_stack(e, w, {p + ".encoder_attention.fc_k", p + ".encoder_attention.fc_v"}, {H, H}, H, enc_out, &d.kv_c, &ob));
     d.kc_log2 = g3_scale_log2(ob[0]); d.vc_log2 = g3_scale_log2(ob[1]);
-    rc = load_stack(e, w, {p + ".encoder_attention.fc_o"}, {H}, H, InB{nullptr, nullptr, H, ob[1]}, &d.o_c); if (rc) return fail(rc);
-    rc = load_stack(e, w, {p + ".positionwise_feedforward.fc_1"}, {PF}, H, ln, &d.f1, &ob); if (rc) return fail(rc);
-    rc = load_stack(e, w, {p + ".positionwise_feedforward.fc_2"}, {H}, PF, InB{nullptr, nullptr, PF, ob[0]}, &d.f2); if (rc) return fail(rc);
-    rc = load_ln(e, w, p + ".layer_norm", &d.g, &d.be); if (rc) return fail(rc);
+    ETD_TRY_OR(fail, load_stack(e, w, {p + ".encoder_attention.fc_o"}, {H}, H, InB{nullptr, nullptr, H, ob[1]}, &d.o_c));
+    ETD_TRY_OR(fail, load_stack(e, w, {p + ".positionwise_feedforward.fc_1"}, {PF}, H, ln, &d.f1, &ob));
+    ETD_TRY_OR(fail, load_stack(e, w, {p + ".positionwise_feedforward.fc_2"}, {H}, PF, InB{nullptr, nullptr, PF, ob[0]}, &d.f2));
+    ETD_TRY_OR(fail, load_ln(e, w, p + ".layer_norm", &d.g, &d.be));
     dcur = ln;
   }
-  {
-    int rc = load_stack(e, w, {"decoder.fc_velocity_freq", "decoder.fc_onset_freq", "decoder.fc_offset_freq", "decoder.fc_mpe_freq"}, {e->NVEL, 1, 1, 1}, H, dcur, &e->head_freq);
-    if (rc) return fail(rc);
-  }
+  ETD_TRY_OR(fail, load_stack(e, w, {"decoder.fc_velocity_freq", "decoder.fc_onset_freq", "decoder.fc_offset_freq", "decoder.fc_mpe_freq"}, {e->NVEL, 1, 1, 1}, H, dcur, &e->head_freq));
   // time decoder (amt_apc.py:203-220): its input is freq-decoder output * sqrt(hid) + pos_embedding_time
   float ptmax = 0.f;
   for (size_t i = 0; i < (size_t)e->nf * H; ++i) ptmax = fmaxf(ptmax, fabsf(pt[i]));
   cur = InB{nullptr, nullptr, H, e->emb_scale * in_bound(dcur) + ptmax};
-  for (int i = 0; i < e->LD; ++i) { int rc = load_enc(e, w, "decoder.layers_time." + std::to_string(i), cur, &e->tim[i], &cur); if (rc) return fail(rc); }
-  {
-    int rc = load_stack(e, w, {"decoder.fc_velocity_time", "decoder.fc_onset_time", "decoder.fc_offset_time", "decoder.fc_mpe_time"}, {e->NVEL, 1, 1, 1}, H, cur, &e->head_time);
-    if (rc) return fail(rc);
-  }
+  for (int i = 0; i < e->LD; ++i) ETD_TRY_OR(fail, load_enc(e, w, "decoder.layers_time." + std::to_string(i), cur, &e->tim[i], &cur));
+  ETD_TRY_OR(fail, load_stack(e, w, {"decoder.fc_velocity_time", "decoder.fc_onset_time", "decoder.fc_offset_time", "decoder.fc_mpe_time"}, {e->NVEL, 1, 1, 1}, H, cur, &e->head_time));
   const size_t Me = (size_t)e->nf * NB, Mq = (size_t)e->nf * e->nn, Mx = Me > Mq ? Me : Mq;
   e->Me = Me; e->Mq = Mq;
-  int rc = 0;
-  rc = rc ? rc : e->alloc(&e->X, Me * H); rc = rc ? rc : e->alloc(&e->X1, Mx * H); rc = rc ? rc : e->alloc(&e->QKV, Mx * 3 * H);
-  rc = rc ? rc : e->alloc(&e->AO, Mx * H); rc = rc ? rc : e->alloc(&e->HF, Mx * PF); rc = rc ? rc : e->alloc(&e->T, Mx * H);
-  rc = rc ? rc : e->alloc(&e->KV, (size_t)e->LD * Me * 2 * H);
-  rc = rc ? rc : e->alloc(&e->D0, Mq * H); rc = rc ? rc : e->alloc(&e->D1, Mq * H); rc = rc ? rc : e->alloc(&e->D2, Mq * H);
-  rc = rc ? rc : e->alloc(&e->Qd, Mq * H); rc = rc ? rc : e->alloc(&e->TI, Mq * H); rc = rc ? rc : e->alloc(&e->HL, Mq * (size_t)e->HLD);
-  if (rc) return fail(rc);
+  DevPool& pool = e->pool;
+  ETD_TRY_OR(fail, pool.alloc(&e->X, Me * H)); ETD_TRY_OR(fail, pool.alloc(&e->X1, Mx * H)); ETD_TRY_OR(fail, pool.alloc(&e->QKV, Mx * 3 * H));
+  ETD_TRY_OR(fail, pool.alloc(&e->AO, Mx * H)); ETD_TRY_OR(fail, pool.alloc(&e->HF, Mx * PF)); ETD_TRY_OR(fail, pool.alloc(&e->T, Mx * H));
+  ETD_TRY_OR(fail, pool.alloc(&e->KV, (size_t)e->LD * Me * 2 * H));
+  ETD_TRY_OR(fail, pool.alloc(&e->D0, Mq * H)); ETD_TRY_OR(fail, pool.alloc(&e->D1, Mq * H)); ETD_TRY_OR(fail, pool.alloc(&e->D2, Mq * H));
+  ETD_TRY_OR(fail, pool.alloc(&e->Qd, Mq * H)); ETD_TRY_OR(fail, pool.alloc(&e->TI, Mq * H)); ETD_TRY_OR(fail, pool.alloc(&e->HL, Mq * (size_t)e->HLD));
   *out = e;
   return ETD_OK;
 }
 
 void ext32_destroy(Ext32* e) {
   if (!e) return;
-  for (void* p : e->allocs) (void)hipFree(p);
+  e->pool.free_all();
   delete e;
 }
 

@@ -1,3 +1,3 @@
 #pragma once
-#include "common.h"
+#include "host_util.h"
 #include "../../include/etude_hip.h"

@@ -149,14 +149,8 @@ struct etd_frontend {
   float2* tw = nullptr;
   int *mel_start = nullptr, *mel_len = nullptr, *mel_off = nullptr;
   float* mel_w = nullptr;
+  DevPool pool;              // the tables above
 };
-
-template <typename T>
-static int upload(T** dst, const T* src, size_t n) {
-  HIP_TRY(hipMalloc((void**)dst, n * sizeof(T) + 16));
-  HIP_TRY(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
-  return ETD_OK;
-}
 
 extern "C" int etd_frontend_create(int sr_in, int sr_out, int orig, int nw, int K, int width, const float* kernT_host,
                                    int n_fft, int hop, const float* window_host, int n_mels, const int* mel_start,
@@ -164,34 +158,32 @@ extern "C" int etd_frontend_create(int sr_in, int sr_out, int orig, int nw, int 
   if (!out || n_fft < 64 || n_fft > 4096 || (n_fft & (n_fft - 1)) || hop <= 0 || n_mels <= 0 || n_mels > 1024)
     ETD_FAIL(ETD_EINVAL, "frontend_create: bad n_fft/hop/n_mels");
   if (sr_in != sr_out && (!kernT_host || K <= 0 || nw <= 0 || orig <= 0)) ETD_FAIL(ETD_EINVAL, "frontend_create: bad resampler table");
+  std::vector<int> off(n_mels);
+  int tot = 0;
+  for (int m = 0; m < n_mels; ++m) {
+    if (mel_start[m] < 0 || mel_len[m] < 0 || mel_start[m] + mel_len[m] > n_fft / 2 + 1) ETD_FAIL(ETD_EINVAL, "frontend_create: mel filter %d out of range", m);
+    off[m] = tot; tot += mel_len[m];
+  }
   etd_frontend* f = new etd_frontend();
   f->sr_in = sr_in; f->sr_out = sr_out; f->orig = orig; f->nw = nw; f->K = K; f->width = width;
   f->n_fft = n_fft; f->hop = hop; f->n_mels = n_mels; f->log_offset = log_offset;
   f->lg = 0; while ((1 << f->lg) < n_fft) ++f->lg;
-  if (sr_in != sr_out) ETD_TRY(upload(&f->kernT, kernT_host, (size_t)K * nw));
-  ETD_TRY(upload(&f->window, window_host, (size_t)n_fft));
+  DevPool& P = f->pool;
+  auto fail = [&](int rc) { P.free_all(); delete f; return rc; };
+  if (sr_in != sr_out) ETD_TRY_OR(fail, P.upload(&f->kernT, kernT_host, (size_t)K * nw));
+  ETD_TRY_OR(fail, P.upload(&f->window, window_host, (size_t)n_fft));
   {
-    float2* tw = new float2[n_fft / 2];
+    std::vector<float2> tw(n_fft / 2);
     for (int k = 0; k < n_fft / 2; ++k) {
       const double ang = -2.0 * 3.14159265358979323846 * (double)k / (double)n_fft;
       tw[k] = make_float2((float)cos(ang), (float)sin(ang));
     }
-    int rc = upload(&f->tw, tw, (size_t)n_fft / 2);
-    delete[] tw;
-    ETD_TRY(rc);
+    ETD_TRY_OR(fail, P.upload(&f->tw, tw.data(), tw.size()));
   }
-  int* off = new int[n_mels];
-  int tot = 0;
-  for (int m = 0; m < n_mels; ++m) {
-    if (mel_start[m] < 0 || mel_len[m] < 0 || mel_start[m] + mel_len[m] > n_fft / 2 + 1) { delete[] off; ETD_FAIL(ETD_EINVAL, "frontend_create: mel filter %d out of range", m); }
-    off[m] = tot; tot += mel_len[m];
-  }
-  int rc = upload(&f->mel_start, mel_start, (size_t)n_mels);
-  if (!rc) rc = upload(&f->mel_len, mel_len, (size_t)n_mels);
-  if (!rc) rc = upload(&f->mel_off, off, (size_t)n_mels);
-  if (!rc) rc = upload(&f->mel_w, mel_w_host, (size_t)(tot > 0 ? tot : 1));
-  delete[] off;
-  ETD_TRY(rc);
+  ETD_TRY_OR(fail, P.upload(&f->mel_start, mel_start, (size_t)n_mels));
+  ETD_TRY_OR(fail, P.upload(&f->mel_len, mel_len, (size_t)n_mels));
+  ETD_TRY_OR(fail, P.upload(&f->mel_off, off.data(), (size_t)n_mels));
+  ETD_TRY_OR(fail, P.upload(&f->mel_w, mel_w_host, (size_t)(tot > 0 ? tot : 1)));
   *out = f;
   return ETD_OK;
 }
@@ -199,8 +191,7 @@ extern "C" int etd_frontend_create(int sr_in, int sr_out, int orig, int nw, int 
 extern "C" void etd_frontend_destroy(etd_frontend* f) {
   if (!f) return;
   (void)hipDeviceSynchronize();   // kernels of this handle may still be in flight
-  (void)hipFree(f->kernT); (void)hipFree(f->window); (void)hipFree(f->tw);
-  (void)hipFree(f->mel_start); (void)hipFree(f->mel_len); (void)hipFree(f->mel_off); (void)hipFree(f->mel_w);
+  f->pool.free_all();
   delete f;
 }
 

@@ -16,6 +16,7 @@
 // Reference ops: F.linear in etude/models/amt_apc.py:322-392 and HF modeling_gpt_neox.py:195-281 (fp32, no autocast: etude_decoder.py:333).
 #pragma once
 #include "dec_kernels.h"
+#include "host_util.h"
 
 // ETD_NO_GEMM3 (measurement: the round-4 fp32-MFMA / VALU kernel sequence instead) is read ONCE per process, here, for every call site
 bool g3_enabled();
@@ -26,6 +27,13 @@ bool g3_enabled();
 // Returns log2 of the scale the planes carry (max |s w| in [2^14, 2^15)).
 int g3_pack_weights_host(const float* W, int N, int Npad, int K, uint16_t* dst);
 static inline size_t g3_packed_elems(int Npad, int K) { return (size_t)Npad * K * 2; }
+
+// a linear layer as k_gemm3 reads it: W [N][K] as packed planes, the bias padded with zeros to Npad = N rounded up to 128, log2 of the plane scales of W and of its input
+struct G3Lin { uint16_t* Wp = nullptr; float* b = nullptr; int N = 0, Npad = 0, K = 0, w_log2 = 0, x_log2 = 0; };
+// pack W (K % 32 == 0), allocate and copy the planes, then the padded bias (null: zeros); x_bound: a provable bound of the input's elements
+int g3_lin_upload(DevPool& pool, const float* W, const float* bias_or_null, int N, int K, float x_bound, G3Lin* l);
+// DGemmArgs of Y = epi(X W^T + b) over M rows of X (row stride ldx); the caller adds the epilogue's fields and picks launch_gemm3 / launch_gemm3_s
+DGemmArgs g3_lin_args(const G3Lin& l, const float* X, int ldx, int M);
 
 // ---- bounds (host, load time).  LayerNorm output y = z g + b with sum z^2 <= n, |z_k| <= sqrt(n - 1):
 float g3_bound_ln(const float* g, const float* b, int n);                                   // max_k sqrt(n-1) |g_k| + |b_k|

@@ -34,6 +34,21 @@ int g3_pack_weights_host(const float* W, int N, int Npad, int K, uint16_t* dst) 
     }
   return lg;
 }
+int g3_lin_upload(DevPool& pool, const float* W, const float* bias_or_null, int N, int K, float x_bound, G3Lin* l) {
+  l->N = N; l->K = K; l->Npad = (N + 127) / 128 * 128;
+  std::vector<uint16_t> planes(g3_packed_elems(l->Npad, K));
+  l->w_log2 = g3_pack_weights_host(W, N, l->Npad, K, planes.data());
+  l->x_log2 = g3_scale_log2(x_bound);
+  ETD_TRY(pool.upload(&l->Wp, planes.data(), planes.size()));
+  std::vector<float> b(l->Npad, 0.f);
+  if (bias_or_null) memcpy(b.data(), bias_or_null, (size_t)N * 4);
+  return pool.upload(&l->b, b.data(), b.size());
+}
+DGemmArgs g3_lin_args(const G3Lin& l, const float* X, int ldx, int M) {
+  DGemmArgs a = {};
+  a.X = X; a.ldx = ldx; a.M = M; a.N = l.N; a.Npad = l.Npad; a.K = l.K; a.Wp = l.Wp; a.w_log2 = l.w_log2; a.x_log2 = l.x_log2; a.bias = l.b;
+  return a;
+}
 float g3_bound_ln(const float* g, const float* b, int n) {
   float mx = 0.f;
   const float z = sqrtf((float)(n - 1));
@@ -704,28 +719,24 @@ extern "C" int etd_debug_gemm3(const float* x_dev, int M, int K, const float* w_
                                const float* ln_g_host, const float* ln_b_host, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   if (!x_dev || !w_host || !y_dev || M < 1 || N < 1 || K < 32 || K % 32) ETD_FAIL(ETD_EINVAL, "debug_gemm3: bad arguments");
-  const int Npad = (N + 127) / 128 * 128;
-  std::vector<uint16_t> planes(g3_packed_elems(Npad, K));
-  const int wl = g3_pack_weights_host(w_host, N, Npad, K, planes.data());
-  std::vector<float> b(Npad, 0.f);
-  if (bias_host) memcpy(b.data(), bias_host, (size_t)N * 4);
-  uint16_t* wp = nullptr; float* bd = nullptr; float* lnd = nullptr;
-  HIP_TRY(hipMalloc((void**)&wp, planes.size() * 2));
-  if (hipMalloc((void**)&bd, b.size() * 4) != hipSuccess || hipMalloc((void**)&lnd, (size_t)2 * K * 4) != hipSuccess) { (void)hipFree(wp); (void)hipFree(bd); ETD_FAIL(ETD_EHIP, "debug_gemm3: hipMalloc"); }
-  int rc = ETD_OK;
-  if (hipMemcpy(wp, planes.data(), planes.size() * 2, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(bd, b.data(), b.size() * 4, hipMemcpyHostToDevice) != hipSuccess) rc = ETD_EHIP;
+  DevPool pool;                                                        // this call's buffers
+  auto done = [&](int rc) { pool.free_all(); return rc; };
+  G3Lin l;
+  float* lnd = nullptr;
+  ETD_TRY_OR(done, g3_lin_upload(pool, w_host, bias_host, N, K, x_bound, &l));
+  ETD_TRY_OR(done, pool.alloc(&lnd, (size_t)2 * K));
   const bool ln = ln_g_host && ln_b_host;
-  if (rc == ETD_OK && ln && (hipMemcpy(lnd, ln_g_host, (size_t)K * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(lnd + K, ln_b_host, (size_t)K * 4, hipMemcpyHostToDevice) != hipSuccess)) rc = ETD_EHIP;
-  if (rc == ETD_OK) {
-    DGemmArgs a = {};
-    a.X = x_dev; a.ldx = K; a.Wp = wp; a.w_log2 = wl; a.x_log2 = g3_scale_log2(x_bound); a.bias = bd; a.M = M; a.N = N; a.Npad = Npad; a.K = K; a.Y = y_dev; a.ldy = N;
-    if (ln) { a.ln_g = lnd; a.ln_b = lnd + K; a.ln_eps = 1e-5f; }       // (x_bound then bounds the LayerNorm OUTPUT; the fused LayerNorm exists in the small-M kernel only)
-    const int epi = gelu ? DEPI_GELU : DEPI_BIAS;
-    rc = gemm3_s_takes(a, epi) ? launch_gemm3_s(a, epi, st) : launch_gemm3(a, epi, st);
+  if (ln) {
+    ETD_TRY_OR(done, ETD_HIP_RC(hipMemcpy(lnd, ln_g_host, (size_t)K * 4, hipMemcpyHostToDevice)));
+    ETD_TRY_OR(done, ETD_HIP_RC(hipMemcpy(lnd + K, ln_b_host, (size_t)K * 4, hipMemcpyHostToDevice)));
   }
+  DGemmArgs a = g3_lin_args(l, x_dev, K, M);
+  a.Y = y_dev; a.ldy = N;
+  if (ln) { a.ln_g = lnd; a.ln_b = lnd + K; a.ln_eps = 1e-5f; }       // (x_bound then bounds the LayerNorm OUTPUT; the fused LayerNorm exists in the small-M kernel only)
+  const int epi = gelu ? DEPI_GELU : DEPI_BIAS;
+  int rc = gemm3_s_takes(a, epi) ? launch_gemm3_s(a, epi, st) : launch_gemm3(a, epi, st);
   if (hipStreamSynchronize(st) != hipSuccess && rc == ETD_OK) { g_etd_err = "debug_gemm3: kernel failed"; rc = ETD_EHIP; }
-  (void)hipFree(wp); (void)hipFree(bd); (void)hipFree(lnd);
-  return rc;
+  return done(rc);
 }
 extern "C" int etd_debug_attn3(const float* q_dev, const float* k_dev, const float* v_dev, float* o_dev, int n_seq, int n_heads, int Sq, int Sk, float q_bound, float k_bound, float v_bound,
                                int causal, const int32_t* lens_host, void* stream) {

@@ -1,0 +1,84 @@
+// Host-side plumbing every engine's create / destroy path shares: the checkpoint's weight table, the list of device allocations a handle owns,
+// the fp32 -> 16-bit conversions of the weight packers, and the "on error, free the half-built handle" macro.  Nothing here is on a hot path.
+#pragma once
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "common.h"
+
+// In a create function, between `new` and `*out = handle`: every fallible call goes through this, so that nothing returns past `fail`
+// (a callable taking the error code, freeing what the handle owns and returning the code).
+#define ETD_TRY_OR(fail, x)                  \
+  do {                                       \
+    const int _rc = (x);                     \
+    if (_rc != ETD_OK) return fail(_rc);     \
+  } while (0)
+// a HIP call as an error code (HIP_TRY's message), for ETD_TRY_OR
+#define ETD_HIP_RC(x) etd_hip_rc((x), #x, __FILE__, __LINE__)
+inline int etd_hip_rc(hipError_t e, const char* what, const char* file, int line) {
+  if (e == hipSuccess) return ETD_OK;
+  char b[512];
+  snprintf(b, sizeof(b), "%s:%d %s -> %s", file, line, what, hipGetErrorString(e));
+  g_etd_err = b;
+  return ETD_EHIP;
+}
+
+// name -> (host pointer, element count) of a checkpoint, as the C ABI passes it
+struct WeightTable {
+  std::map<std::string, std::pair<const float*, int64_t>> t;
+  int null_name = -1;                      // index of the first null entry of `names` (skipped), or -1
+  WeightTable(const char* const* names, const float* const* host_ptrs, const int64_t* numels, int n) {
+    for (int i = 0; i < n; ++i) {
+      if (names[i]) t[names[i]] = {host_ptrs[i], numels[i]};
+      else if (null_name < 0) null_name = i;
+    }
+  }
+  // the tensor `k` of exactly `numel` elements, or null with g_etd_err set
+  const float* get(const std::string& k, int64_t numel) const {
+    auto it = t.find(k);
+    if (it == t.end()) { g_etd_err = "missing weight '" + k + "'"; return nullptr; }
+    if (it->second.second != numel || !it->second.first) {
+      g_etd_err = "weight '" + k + "' has " + std::to_string(it->second.second) + " elements, expected " + std::to_string(numel);
+      return nullptr;
+    }
+    return it->second.first;
+  }
+};
+
+// every device allocation a handle owns, in allocation order; each carries 256 bytes of slack (kernels read whole vectors / tiles at the end of a buffer)
+struct DevPool {
+  std::vector<void*> ptrs;
+  std::vector<size_t> bytes;               // parallel to ptrs, slack included
+  template <typename T> int alloc(T** p, size_t n, bool zero = false) {
+    void* q = nullptr;
+    const size_t nb = n * sizeof(T) + 256;
+    HIP_TRY(hipMalloc(&q, nb));
+    ptrs.push_back(q); bytes.push_back(nb);
+    if (zero) HIP_TRY(hipMemset(q, 0, nb));
+    *p = (T*)q;
+    return ETD_OK;
+  }
+  // allocate + copy n elements from the host (S: the host-side type of the same size, e.g. uint16_t bits of a 16-bit float)
+  template <typename T, typename S> int upload(T** dst, const S* src, size_t n) {
+    static_assert(sizeof(T) == sizeof(S), "upload: element sizes differ");
+    ETD_TRY(alloc(dst, n));
+    HIP_TRY(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
+    return ETD_OK;
+  }
+  size_t mark() const { return ptrs.size(); }
+  void free_from(size_t m) {               // the allocations made since mark() returned m
+    for (size_t i = m; i < ptrs.size(); ++i) (void)hipFree(ptrs[i]);
+    ptrs.resize(m); bytes.resize(m);
+  }
+  void free_all() { free_from(0); }
+};
+
+// fp32 -> 16-bit operand bits, round to nearest even, NaN kept
+inline uint16_t f32_to_bf16_bits(float f) {
+  uint32_t u; memcpy(&u, &f, 4);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
+  return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+inline uint16_t f32_to_f16_bits(float f) { const _Float16 h = (_Float16)f; uint16_t u; memcpy(&u, &h, 2); return u; }
