@@ -50,6 +50,20 @@ class BeatCfg(_SizedCfg):
                                        "n_mels", "tempo_out", "max_rows")]
 
 
+class G3Case(_SizedCfg):
+    """etd_debug_g3_case of include/etude_hip_debug.h: one k_gemm3 / k_gemm3_s launch with any epilogue, strides and row metadata"""
+    _fields_ = [("struct_bytes", C.c_int), ("kernel", C.c_int), ("epi", C.c_int)] + [(n, C.c_int) for n in ("M", "N", "K", "ldx", "ldy")] + \
+               [("X", C.c_void_p), ("x_elems", C.c_longlong), ("W", C.c_void_p), ("bias", C.c_void_p), ("x_bound", C.c_float),
+                ("ln_g", C.c_void_p), ("ln_b", C.c_void_p), ("ln_eps", C.c_float), ("Y", C.c_void_p), ("y_elems", C.c_longlong),
+                ("add", C.c_void_p), ("hin", C.c_void_p), ("hout", C.c_void_p), ("h_elems", C.c_longlong),
+                ("pos", C.c_void_p), ("slot", C.c_void_p), ("active", C.c_void_p)] + [(n, C.c_int) for n in ("n_heads", "max_ctx", "n_slots", "rope_rows")] + \
+               [("rope_cos", C.c_void_p), ("rope_sin", C.c_void_p), ("Q", C.c_void_p), ("q_elems", C.c_longlong), ("Kc", C.c_void_p), ("Vc", C.c_void_p), ("kv_elems", C.c_longlong)]
+
+
+G3_KERNEL_AUTO, G3_KERNEL_TILE, G3_KERNEL_SMALL = 0, 1, 2                                            # ETD_G3_KERNEL_*
+G3_EPI = {"bias": 0, "gelu": 1, "resid": 2, "logits": 3, "qkv": 4, "relu": 6}                        # ETD_G3_EPI_*
+
+
 class Job(C.Structure):
     _fields_ = [("x_ids", C.c_void_p), ("x_offsets", C.c_void_p), ("n_bars", C.c_int), ("attrs4", C.c_void_p), ("ready", C.c_void_p)]
 
@@ -99,6 +113,9 @@ SIGNATURES = {
     "etd_debug_kernel_loop": (C.c_int, [C.c_int, C.c_int, C.c_void_p]),
     "etd_debug_g3_bounds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
     "etd_debug_gemm3": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "etd_debug_gemm3_case": (C.c_int, [C.POINTER(G3Case), C.c_void_p]),
+    "etd_debug_ln_rows_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "etd_debug_g3_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_int32)]),
     "etd_debug_attn3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     "etd_debug_empty_launch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "etd_frontend_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,

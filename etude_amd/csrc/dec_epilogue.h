@@ -43,8 +43,11 @@ __device__ __forceinline__ void dgemm_epilogue(const DGemmArgs& a, const f32x16&
     if (part < 2 && dbase == 0) {
       // partial RoPE on dims [0, 2*rot_half): pair (d, d + rot_half); with rot_half == 8 both sit in
       // this lane: d = (i&3) + 4h  (i < 4)  and d + 8 = register i + 4
-      const float* cs = a.rope_cos + (long long)pos * a.rot_half;
-      const float* sn = a.rope_sin + (long long)pos * a.rot_half;
+      // (the tables have max_ctx rows: a finished stream riding along as an inactive row can sit at pos == max_ctx -- etd_decoder_begin_bars allows a final length of
+      //  max_ctx -- and stores no K / V below; its Q is never used)
+      const int pt = pos < a.max_ctx ? pos : a.max_ctx - 1;
+      const float* cs = a.rope_cos + (long long)pt * a.rot_half;
+      const float* sn = a.rope_sin + (long long)pt * a.rot_half;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int d = i + 4 * h;

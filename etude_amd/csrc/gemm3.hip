@@ -123,7 +123,9 @@ __device__ __forceinline__ void g3_store_block(const DGemmArgs& a, const f32x16 
   int head = 0, part = 0;
   if constexpr (EPI == DEPI_QKV) { head = nb / 192; part = (nb - head * 192) >> 6; }
   int pos_l = 0;
-  if constexpr (EPI == DEPI_QKV) pos_l = a.rows.pos[m < p_M ? m : p_M - 1];
+  // (RoPE table row, clamped to the table's [max_ctx] rows: a finished stream that rides along in a decode step as an inactive row sits at pos = its final length,
+  //  which etd_decoder_begin_bars lets reach max_ctx itself -- such a row stores no K / V below, and its Q is never used)
+  if constexpr (EPI == DEPI_QKV) { pos_l = a.rows.pos[m < p_M ? m : p_M - 1]; pos_l = pos_l < a.max_ctx ? pos_l : a.max_ctx - 1; }
 #pragma unroll
   for (int tf = 0; tf < 2; ++tf) {
     float v[16];
@@ -441,7 +443,7 @@ bool gemm3_s_takes(const DGemmArgs& a, int epi) {
 int launch_gemm3_s(const DGemmArgs& a, int epi, hipStream_t st) {
   if (!gemm3_s_takes(a, epi) || !a.X || (a.ldx % 4) || ((uintptr_t)a.X & 15) || a.N > a.Npad) ETD_FAIL(ETD_EINVAL, "gemm3_s: bad shape M=%d N=%d Npad=%d K=%d", a.M, a.N, a.Npad, a.K);
   if (epi == DEPI_QKV && (a.rot_half != 8 || a.N % 192)) ETD_FAIL(ETD_EINVAL, "gemm3_s: QKV epilogue needs head_dim 64 and rotary_ndims 16");
-  if (epi == DEPI_RESID && (a.N % 4)) ETD_FAIL(ETD_EINVAL, "gemm3_s: resid needs N %% 4 == 0");
+  if (epi == DEPI_RESID && ((a.N % 4) || !a.add)) ETD_FAIL(ETD_EINVAL, "gemm3_s: resid needs N %% 4 == 0 and a non-null `add` (dgemm_epilogue reads it unconditionally)");
   ETD_LAUNCH_FILTER("k_gemm3_s");
   ProfScope ps("k_gemm3_s", st, 2.0 * a.M * a.N * a.K, (double)a.Npad * a.K * 4);
   const int wtiles = a.Npad / 32;
@@ -715,28 +717,104 @@ int launch_attn3(const Attn3Args& a, hipStream_t st) {
 
 // ================================================================================================ test hooks (include/etude_hip_debug.h)
 #include "../../include/etude_hip_debug.h"
-extern "C" int etd_debug_gemm3(const float* x_dev, int M, int K, const float* w_host, const float* bias_host, int N, float x_bound, int gelu, float* y_dev,
-                               const float* ln_g_host, const float* ln_b_host, void* stream) {
+static_assert(ETD_G3_EPI_BIAS == DEPI_BIAS && ETD_G3_EPI_GELU == DEPI_GELU && ETD_G3_EPI_RESID == DEPI_RESID && ETD_G3_EPI_LOGITS == DEPI_LOGITS && ETD_G3_EPI_QKV == DEPI_QKV &&
+              ETD_G3_EPI_RELU == DEPI_RELU, "etude_hip_debug.h: ETD_G3_EPI_* are the DEPI_* values");
+extern "C" int etd_debug_gemm3_case(const etd_debug_g3_case* c, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  if (!x_dev || !w_host || !y_dev || M < 1 || N < 1 || K < 32 || K % 32) ETD_FAIL(ETD_EINVAL, "debug_gemm3: bad arguments");
+  if (!c) ETD_FAIL(ETD_EINVAL, "debug_gemm3_case: null case");
+  if (c->struct_bytes != (int)sizeof(etd_debug_g3_case)) ETD_FAIL(ETD_EINVAL, "debug_gemm3_case: etd_debug_g3_case of %d bytes, expected %d", c->struct_bytes, (int)sizeof(etd_debug_g3_case));
+  const int M = c->M, N = c->N, K = c->K, epi = c->epi;
+  auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+  if (c->kernel < ETD_G3_KERNEL_AUTO || c->kernel > ETD_G3_KERNEL_SMALL) ETD_FAIL(ETD_EINVAL, "debug_gemm3_case: kernel %d", c->kernel);
+  if (epi != DEPI_BIAS && epi != DEPI_GELU && epi != DEPI_RELU && epi != DEPI_RESID && epi != DEPI_LOGITS && epi != DEPI_QKV) ETD_FAIL(ETD_EINVAL, "debug_gemm3_case: epilogue %d", epi);
+  if (M < 1 || N < 1 || K < 32 || K % 32 || M > (1 << 20) || N > (1 << 20) || K > (1 << 20) || !c->W) ETD_FAIL(ETD_EINVAL, "debug_gemm3_case: bad shape M=%d N=%d K=%d", M, N, K);
+  if (!c->X || !al16(c->X) || c->ldx < 4 || c->ldx % 4 || c->ldx > (1 << 20) || (long long)(M - 1) * c->ldx + K > c->x_elems)
+    ETD_FAIL(ETD_EINVAL, "debug_gemm3_case: X rows ((M - 1) ldx + K = %lld floats) do not fit x_elems = %lld, or X / ldx = %d misaligned", (long long)(M - 1) * c->ldx + K, c->x_elems, c->ldx);
+  if (!(c->x_bound >= 0.f) || !std::isfinite(c->x_bound)) ETD_FAIL(ETD_EINVAL, "debug_gemm3_case: x_bound");
+  const bool ln = c->ln_g || c->ln_b;
+  if (ln && (!c->ln_g || !c->ln_b || !(c->ln_eps >= 0.f))) ETD_FAIL(ETD_EINVAL, "debug_gemm3_case: ln_g, ln_b and ln_eps go together");
+  if (epi == DEPI_RESID) {
+    if (N % 4 || !c->hin || !c->hout || !al16(c->hin) || !al16(c->hout) || !al16(c->add) || (long long)M * N > c->h_elems)
+      ETD_FAIL(ETD_EINVAL, "debug_gemm3_case: RESID needs N %% 4 == 0 and 16-byte aligned hin / hout (/ add) of M N = %lld <= h_elems = %lld floats", (long long)M * N, c->h_elems);
+  } else if (epi == DEPI_QKV) {
+    if (c->n_heads < 1 || N != c->n_heads * 192 || c->max_ctx < 1 || c->n_slots < 1 || c->rope_rows < 1 || !c->pos || !c->slot || !c->active || !c->rope_cos || !c->rope_sin)
+      ETD_FAIL(ETD_EINVAL, "debug_gemm3_case: QKV needs N == n_heads * 192, max_ctx, n_slots, rope_rows >= 1, row metadata and RoPE tables");
+    if (!c->Q || !c->Kc || !c->Vc || !al16(c->Q) || !al16(c->Kc) || !al16(c->Vc) || (long long)M * c->n_heads * 64 > c->q_elems ||
+        (long long)c->n_slots * c->n_heads * c->max_ctx * 64 > c->kv_elems)
+      ETD_FAIL(ETD_EINVAL, "debug_gemm3_case: Q [M][heads * 64] / Kc, Vc [n_slots][heads][max_ctx][64] do not fit q_elems = %lld / kv_elems = %lld", c->q_elems, c->kv_elems);
+    for (int i = 0; i < M; ++i)
+      if (c->pos[i] < 0 || c->pos[i] >= c->rope_rows || c->slot[i] < 0 || c->slot[i] >= c->n_slots)
+        ETD_FAIL(ETD_EINVAL, "debug_gemm3_case: row %d has pos %d (rope_rows %d), slot %d (n_slots %d)", i, c->pos[i], c->rope_rows, c->slot[i], c->n_slots);
+  } else {
+    if (!c->Y || !al16(c->Y) || c->ldy < N || c->ldy > (1 << 20) || (long long)(M - 1) * c->ldy + N > c->y_elems)
+      ETD_FAIL(ETD_EINVAL, "debug_gemm3_case: Y rows ((M - 1) ldy + N = %lld floats) do not fit y_elems = %lld, or ldy = %d < N", (long long)(M - 1) * c->ldy + N, c->y_elems, c->ldy);
+  }
   DevPool pool;                                                        // this call's buffers
   auto done = [&](int rc) { pool.free_all(); return rc; };
   G3Lin l;
-  float* lnd = nullptr;
-  ETD_TRY_OR(done, g3_lin_upload(pool, w_host, bias_host, N, K, x_bound, &l));
-  ETD_TRY_OR(done, pool.alloc(&lnd, (size_t)2 * K));
-  const bool ln = ln_g_host && ln_b_host;
-  if (ln) {
-    ETD_TRY_OR(done, ETD_HIP_RC(hipMemcpy(lnd, ln_g_host, (size_t)K * 4, hipMemcpyHostToDevice)));
-    ETD_TRY_OR(done, ETD_HIP_RC(hipMemcpy(lnd + K, ln_b_host, (size_t)K * 4, hipMemcpyHostToDevice)));
+  ETD_TRY_OR(done, g3_lin_upload(pool, c->W, c->bias, N, K, c->x_bound, &l));
+  DGemmArgs a = g3_lin_args(l, c->X, c->ldx, M);
+  if (epi == DEPI_LOGITS && !c->bias) a.bias = nullptr;                // (as head_logits does: the lm head has no bias)
+  if (ln) {                                                            // (x_bound then bounds the LayerNorm OUTPUT; the fused LayerNorm exists in the small-M kernel only)
+    float *gd = nullptr, *bd = nullptr;
+    ETD_TRY_OR(done, pool.upload(&gd, c->ln_g, (size_t)K));
+    ETD_TRY_OR(done, pool.upload(&bd, c->ln_b, (size_t)K));
+    a.ln_g = gd; a.ln_b = bd; a.ln_eps = c->ln_eps;
   }
-  DGemmArgs a = g3_lin_args(l, x_dev, K, M);
-  a.Y = y_dev; a.ldy = N;
-  if (ln) { a.ln_g = lnd; a.ln_b = lnd + K; a.ln_eps = 1e-5f; }       // (x_bound then bounds the LayerNorm OUTPUT; the fused LayerNorm exists in the small-M kernel only)
-  const int epi = gelu ? DEPI_GELU : DEPI_BIAS;
-  int rc = gemm3_s_takes(a, epi) ? launch_gemm3_s(a, epi, st) : launch_gemm3(a, epi, st);
-  if (hipStreamSynchronize(st) != hipSuccess && rc == ETD_OK) { g_etd_err = "debug_gemm3: kernel failed"; rc = ETD_EHIP; }
+  if (epi == DEPI_RESID) { a.add = c->add; a.hin = c->hin; a.hout = c->hout; }
+  else if (epi == DEPI_QKV) {
+    int *pd = nullptr, *sd = nullptr, *ad = nullptr;
+    float *cd = nullptr, *nd = nullptr;
+    ETD_TRY_OR(done, pool.upload(&pd, c->pos, (size_t)M));
+    ETD_TRY_OR(done, pool.upload(&sd, c->slot, (size_t)M));
+    ETD_TRY_OR(done, pool.upload(&ad, c->active, (size_t)M));
+    ETD_TRY_OR(done, pool.upload(&cd, c->rope_cos, (size_t)c->rope_rows * 8));
+    ETD_TRY_OR(done, pool.upload(&nd, c->rope_sin, (size_t)c->rope_rows * 8));
+    a.rows = DecRows{sd, pd, ad, nullptr};
+    a.rope_cos = cd; a.rope_sin = nd; a.rot_half = 8; a.Q = c->Q; a.Kc = c->Kc; a.Vc = c->Vc;
+    a.slot_stride = (long long)c->n_heads * c->max_ctx * 64; a.max_ctx = c->max_ctx; a.n_heads = c->n_heads;
+  } else { a.Y = c->Y; a.ldy = c->ldy; }
+  const bool takes = gemm3_s_takes(a, epi);
+  if (c->kernel == ETD_G3_KERNEL_SMALL && !takes) { g_etd_err = "debug_gemm3_case: k_gemm3_s does not take this shape"; return done(ETD_EINVAL); }
+  const bool small = c->kernel == ETD_G3_KERNEL_SMALL || (c->kernel == ETD_G3_KERNEL_AUTO && takes);
+  int rc = small ? launch_gemm3_s(a, epi, st) : launch_gemm3(a, epi, st);     // (both refuse what they cannot do: a fused LayerNorm on k_gemm3, a null `add` on k_gemm3_s)
+  if (hipStreamSynchronize(st) != hipSuccess && rc == ETD_OK) { g_etd_err = "debug_gemm3_case: kernel failed"; rc = ETD_EHIP; }
   return done(rc);
+}
+extern "C" int etd_debug_gemm3(const float* x_dev, int M, int K, const float* w_host, const float* bias_host, int N, float x_bound, int gelu, float* y_dev,
+                               const float* ln_g_host, const float* ln_b_host, void* stream) {
+  if (M < 1 || N < 1 || K < 32) ETD_FAIL(ETD_EINVAL, "debug_gemm3: bad arguments");
+  etd_debug_g3_case c = {};
+  c.struct_bytes = (int)sizeof(c); c.kernel = ETD_G3_KERNEL_AUTO; c.epi = gelu ? DEPI_GELU : DEPI_BIAS;
+  c.M = M; c.N = N; c.K = K; c.ldx = K; c.ldy = N; c.X = x_dev; c.x_elems = (long long)M * K; c.W = w_host; c.bias = bias_host; c.x_bound = x_bound;
+  if (ln_g_host && ln_b_host) { c.ln_g = ln_g_host; c.ln_b = ln_b_host; c.ln_eps = 1e-5f; }
+  c.Y = y_dev; c.y_elems = (long long)M * N;
+  return etd_debug_gemm3_case(&c, stream);
+}
+extern "C" int etd_debug_ln_rows_f32(const float* h_dev, int M, int H, const float* g1_host, const float* b1_host, const float* g2_host, const float* b2_host, float eps,
+                                     float* x1_dev, float* x2_dev, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const bool two = g2_host || b2_host || x2_dev;
+  if (!h_dev || !g1_host || !b1_host || !x1_dev || M < 1 || M > (1 << 24) || H < 256 || H % 256 || H > 1024 || (two && (!g2_host || !b2_host || !x2_dev)) || !(eps >= 0.f) ||
+      (((uintptr_t)h_dev | (uintptr_t)x1_dev | (uintptr_t)x2_dev) & 15))
+    ETD_FAIL(ETD_EINVAL, "debug_ln_rows_f32: bad arguments");
+  DevPool pool;
+  auto done = [&](int rc) { pool.free_all(); return rc; };
+  float *g1 = nullptr, *b1 = nullptr, *g2 = nullptr, *b2 = nullptr;
+  ETD_TRY_OR(done, pool.upload(&g1, g1_host, (size_t)H));
+  ETD_TRY_OR(done, pool.upload(&b1, b1_host, (size_t)H));
+  if (two) { ETD_TRY_OR(done, pool.upload(&g2, g2_host, (size_t)H)); ETD_TRY_OR(done, pool.upload(&b2, b2_host, (size_t)H)); }
+  int rc = launch_ln_rows_f32(h_dev, M, H, g1, b1, g2, b2, eps, x1_dev, x2_dev, st);
+  if (hipStreamSynchronize(st) != hipSuccess && rc == ETD_OK) { g_etd_err = "debug_ln_rows_f32: kernel failed"; rc = ETD_EHIP; }
+  return done(rc);
+}
+extern "C" int etd_debug_g3_pack(const float* W, int N, int K, uint16_t* planes_out, long long cap, long long* n_out, int32_t* log2_out) {
+  if (!W || !n_out || !log2_out || N < 1 || K < 32 || K % 32 || N > (1 << 20) || K > (1 << 20) || cap < 0 || (cap > 0 && !planes_out)) ETD_FAIL(ETD_EINVAL, "debug_g3_pack: bad arguments");
+  const int Npad = (N + 127) / 128 * 128;
+  *n_out = (long long)g3_packed_elems(Npad, K);
+  if (*n_out > cap) ETD_FAIL(ETD_ENOMEM, "debug_g3_pack: %lld plane elements, capacity %lld", *n_out, cap);
+  *log2_out = g3_pack_weights_host(W, N, Npad, K, planes_out);
+  return ETD_OK;
 }
 extern "C" int etd_debug_attn3(const float* q_dev, const float* k_dev, const float* v_dev, float* o_dev, int n_seq, int n_heads, int Sq, int Sk, float q_bound, float k_bound, float v_bound,
                                int causal, const int32_t* lens_host, void* stream) {

@@ -69,6 +69,36 @@ int etd_debug_decoder_step_logits(etd_dec*, int on, float* out_host, int n_activ
  * x_bound then bounds the LayerNorm output); everything else the 128 x 128 tile kernel (k_gemm3, no fused LayerNorm). */
 int etd_debug_gemm3(const float* x_dev, int M, int K, const float* w_host, const float* bias_host, int N, float x_bound, int gelu, float* y_dev,
                     const float* ln_g_host, const float* ln_b_host, void* stream);
+/* test hook (tests/test_gpu_gemm3_epilogues.py): ONE launch of k_gemm3 / k_gemm3_s with any epilogue, row strides and row metadata, through the code the engines
+ * use (g3_lin_upload, g3_lin_args, launch_gemm3 / launch_gemm3_s).  Everything is validated on the host first -- every extent against the allocation sizes the caller
+ * states, every slot / position against n_slots / rope_rows -- and a case that does not hold is ETD_EINVAL before anything is launched. */
+enum { ETD_G3_KERNEL_AUTO = 0 /* gemm3_s_takes decides, as the decoder does */, ETD_G3_KERNEL_TILE = 1 /* k_gemm3 */, ETD_G3_KERNEL_SMALL = 2 /* k_gemm3_s */ };
+enum { ETD_G3_EPI_BIAS = 0, ETD_G3_EPI_GELU = 1, ETD_G3_EPI_RESID = 2, ETD_G3_EPI_LOGITS = 3, ETD_G3_EPI_QKV = 4, ETD_G3_EPI_RELU = 6 };
+typedef struct etd_debug_g3_case {
+  int struct_bytes;                            /* sizeof(etd_debug_g3_case) of the caller */
+  int kernel, epi;                             /* ETD_G3_KERNEL_*, ETD_G3_EPI_* */
+  int M, N, K, ldx, ldy;                       /* row i of X = the K floats at X + i * ldx (ldx < K: overlapping rows); ldy >= N: BIAS / GELU / RELU / LOGITS */
+  const float* X; long long x_elems;           /* device; floats allocated: (M - 1) ldx + K must fit */
+  const float* W; const float* bias;           /* host [N][K], [N] or NULL (LOGITS never reads it) */
+  float x_bound;                               /* bound of |x| (of the LayerNorm output when ln_g is set) for the plane scale */
+  const float* ln_g; const float* ln_b; float ln_eps;      /* host [K] or NULL: LayerNorm over K fused in front (k_gemm3_s only) */
+  float* Y; long long y_elems;                 /* device; (M - 1) ldy + N must fit */
+  const float* add; const float* hin; float* hout; long long h_elems;      /* RESID, device [M][N] each (h_elems floats): hout = (y + add) + hin; add NULL = 0 (k_gemm3 only);
+                                                                              hin == hout is allowed */
+  const int32_t* pos; const int32_t* slot; const int32_t* active;          /* QKV, host [M]: 0 <= pos < rope_rows, 0 <= slot < n_slots */
+  int n_heads, max_ctx, n_slots, rope_rows;    /* N == n_heads * 192; rows with pos >= max_ctx or active == 0 write no K / V */
+  const float* rope_cos; const float* rope_sin;            /* host [rope_rows][8] */
+  float* Q; long long q_elems;                 /* device [M][n_heads * 64] */
+  float* Kc; float* Vc; long long kv_elems;    /* device [n_slots][n_heads][max_ctx][64] each */
+} etd_debug_g3_case;
+int etd_debug_gemm3_case(const etd_debug_g3_case* c, void* stream);
+/* test hook: launch_ln_rows_f32 -- x1 = LayerNorm(h; g1, b1), x2 = LayerNorm(h; g2, b2) over rows of H features (h, x1, x2 device [M][H]; g / b host [H]; g2, b2, x2 all NULL or all set) */
+int etd_debug_ln_rows_f32(const float* h_dev, int M, int H, const float* g1_host, const float* b1_host, const float* g2_host, const float* b2_host, float eps,
+                          float* x1_dev, float* x2_dev, void* stream);
+/* host-only test hook: g3_pack_weights_host of W [N][K] (K % 32 == 0) -- planes_out receives the f16 bit patterns in the streaming order
+ * [Npad / 128 tile][K / 32 chunk][hi | lo][128 rows][32 k], Npad = N rounded up to 128; *n_out = their number (also when cap is too small: ETD_ENOMEM); *log2_out = log2 of the scale */
+int etd_debug_g3_pack(const float* W, int N, int K, uint16_t* planes_out, long long cap, long long* n_out, int32_t* log2_out);
+
 /* o = softmax(q k^T / 8) v per (sequence, head), head_dim 64: q / o [n_seq][Sq][heads * 64], k / v [n_seq][Sk][heads * 64] device fp32; causal != 0: query t sees keys 0 .. t
  * through the RAGGED path (K / V then laid out as a KV cache [n_seq slots][heads][Sk][64], lens_host[n_seq] prompt lengths <= Sq == Sk, q / o rows packed prompt after prompt) */
 int etd_debug_attn3(const float* q_dev, const float* k_dev, const float* v_dev, float* o_dev, int n_seq, int n_heads, int Sq, int Sk, float q_bound, float k_bound, float v_bound,
