@@ -144,15 +144,9 @@ int load_vec(etd_dec* d, const WeightTable& L, const std::string& name, int n, f
   return d->pool.upload(dst, p, n);
 }
 
-// ---- one forward pass over M rows.  `rows` describes each row (slot, position, active); the embeddings are in
-// d->h.  Returns (in *hfinal) the buffer that holds the last layer's output (before the final LayerNorm).
-//
-// fp32 weights, or M == 1: fp32 activations, LayerNorm fused into the GEMM prologues (k_dgemm / k_dgemm_s / k_dgemv).
-// d16 weights, M > 1:     k_ln_rows -> d16 activations -> big-tile MFMA GEMM (k_linear decoder modes, M > 512, the
-//                          batched prefill) or the K-split skinny GEMM (M <= 512, the batched decode step).
+// ---- one forward pass over M rows.  `rows` describes each row (slot, position, active); the embeddings are in d->h.  One function per kernel sequence
+// below (forward_x3 / _plain / _skinny16 / _prefill16); forward_rows picks one per call and returns (in *hfinal) the buffer that holds the last layer's output.
 struct PrefillInfo { int n; const int* seq_row0; const int* seq_len; int max_len; double attn_flops; };
-// "Only each prompt's last position is needed" (begin_bars): the last layer then runs its attention, MLP and residual for
-// those n rows only -- on the decode-step kernels -- after the big QKV GEMM has put every position's K/V into the cache.
 // ---- step trace (diagnostic): hash of every row of a buffer -> trace[step % cap][off + slab * M + row]
 __global__ __launch_bounds__(64) void k_trace_rows(const unsigned* buf, long long row_stride, int words, long long slab_stride, int M,
                                                    unsigned* trace, const int* step, int cap, long long wps, int off) {
@@ -192,306 +186,315 @@ static int trace_rows(etd_dec* d, const void* buf, long long row_stride, int wor
 }
 
 static inline bool fused_pmlp_on() { const char* e = getenv("ETD_FUSED_PMLP"); return !e || atoi(e) > 0; }
+// "Only each prompt's last position is needed" (begin_bars): the last layer then runs its attention, MLP and residual for
+// those n rows only -- on the decode-step kernels -- after the big QKV GEMM has put every position's K/V into the cache.
 struct LastOnly { int n; const int* idx; DecRows rows; };
+constexpr int DS_K_SPLITS = 5;      // the (down | dense) GEMM of the skinny sequence and of the last-rows tail splits K over this many workgroups, each over a multiple of 64 * 8 columns
+static inline bool ksplit_fits(const etd_dec* d) { return (d->I + d->H) % (DS_K_SPLITS * 64 * 8) == 0; }
+// ... and the fused step kernels (k_dstep_qkv_up, k_dstep_head) are built for hidden 512: the shape test of the fused decode step and of the last-rows tail
+static inline bool step_shape(const etd_dec* d) { return ksplit_fits(d) && d->H == 512; }
+#ifdef ETD_EXPERIMENTS
+static inline bool rowfin_on() { static const bool on = getenv("ETD_ROWFIN") && atoi(getenv("ETD_ROWFIN")) > 0; return on; }     // the in-launch row finish (skinny_attn_down): read once per process
+#else
+static inline bool rowfin_on() { return false; }          // (measured dead end: built with -DETD_EXPERIMENTS only)
+#endif
 
-static DGemmArgs g3_args(const float* X, int ldx, const Lin& w, int M) {
-  DGemmArgs a = g3_lin_args(w.g3, X, ldx, M);
-  a.W = w.W;               // (the weight-streaming kernels of the last layer's tail read the fp32 rows)
+// ---- argument builders: what every launch of a kind shares; the call sites add the fields of their epilogue
+// Y = epi(X W^T + b) over M rows of X.  fp32 weights: W = the fp32 rows of the weight-streaming kernels, Wp = the planes of k_gemm3; 16-bit: W row-major, Wf in fragment order
+static DGemmArgs lin_args(const Lin& w, const float* X, int ldx, int M) {
+  DGemmArgs a = {};
+  a.X = X; a.ldx = ldx; a.M = M; a.W = w.W; a.Wf = w.Wf; a.bias = w.b; a.N = w.N; a.Npad = w.Npad; a.K = w.K; a.Wp = w.g3.Wp; a.w_log2 = w.g3.w_log2; a.x_log2 = w.g3.x_log2;
   return a;
+}
+static inline void* kv_layer(const etd_dec* d, void* cache, int l) { return (char*)cache + (size_t)l * d->layer_stride * (d->bf16w ? 2 : 4); }
+static DGemmArgs qkv_args(const etd_dec* d, int l, const float* X, const DecRows& rows, int M) {      // fused QKV of layer l + RoPE + KV append
+  DGemmArgs q = lin_args(d->layers[l].qkv, X, d->H, M);
+  q.rows = rows; q.rope_cos = d->rope_cos; q.rope_sin = d->rope_sin; q.rot_half = 8; q.Q = d->Q;
+  q.Kc = kv_layer(d, d->Kc, l); q.Vc = kv_layer(d, d->Vc, l); q.slot_stride = d->slot_stride; q.max_ctx = d->ctx; q.n_heads = d->nh;
+  return q;
+}
+static DAttnArgs attn_args(const etd_dec* d, int l, const DecRows& rows, int M) {      // causal attention of `rows` against layer l's KV cache
+  DAttnArgs at = {};
+  at.Q = d->Q; at.Kc = kv_layer(d, d->Kc, l); at.Vc = kv_layer(d, d->Vc, l); at.slot_stride = d->slot_stride; at.max_ctx = d->ctx; at.n_heads = d->nh;
+  at.rows = rows; at.M = M; at.scale = 0.125f; at.bytes_hint = d->attn_bytes_hint;
+  return at;
+}
+static inline void attn_step_pairs(const etd_dec* d, DAttnArgs* at) { at->row_sp = d->row_sp; at->identity = d->rows_identity ? 1 : 0; }     // decode step: the step's (slot, pos) pairs
+static inline void attn_stamp(const etd_dec* d, int l, DAttnArgs* at) { at->stamp = d->stamp_on ? d->stamp_dev : nullptr; at->stamp_par = l & 1; }
+// LayerNorm parameters and destinations of layer l + 1 (the last kernel of a 16-bit layer also writes the next layer's LayerNorm rows), or nulls after the last layer
+struct NextLn { const float *g1, *b1, *g2, *b2; d16 *x1, *x2; };
+static NextLn next_ln(const etd_dec* d, int l) {
+  const Layer* nx = l + 1 < d->L ? &d->layers[l + 1] : nullptr;
+  return nx ? NextLn{nx->ln1g, nx->ln1b, nx->ln2g, nx->ln2b, d->X1b, d->X2b} : NextLn{};
+}
+// ---- launches that several 16-bit sequences share
+static int ln_rows16(etd_dec* d, int l, const float* h, int M, hipStream_t st) {
+  const Layer& w = d->layers[l];      // both LayerNorms of layer l -> X1b / X2b
+  return launch_ln_rows(h, M, d->H, w.ln1g, w.ln1b, w.ln2g, w.ln2b, d->cfg.layer_norm_eps, d->X1b, d->X2b, st);
+}
+// k_dattn per (row, head): fp32 rows to AO, 16-bit rows to Ob (row stride ldob, 0 = hidden; null: none)
+static int layer_dattn(etd_dec* d, int l, const DecRows& rows, int M, d16* Ob, int ldob, hipStream_t st) {
+  DAttnArgs at = attn_args(d, l, rows, M); at.O = d->AO; at.Ob = Ob; at.ldob = ldob;
+  if (rows.slot == d->row_slot) { attn_step_pairs(d, &at); attn_stamp(d, l, &at); }
+  return launch_dattn(at, d->bf16w, st);
+}
+// QKV (+RoPE, KV append) and MLP up (+GELU -> Xcat) of the LayerNorm rows in X1b / X2b share one launch
+static int step_qkv_up(etd_dec* d, int l, const float* X, const DecRows& rows, int M, hipStream_t st) {
+  DGemmArgs q = qkv_args(d, l, X, rows, M); q.Xb = d->X1b; q.Y = d->qkv_raw; q.ldy = 3 * d->H;
+  DGemmArgs up = lin_args(d->layers[l].up, X, d->H, M); up.Xb = d->X2b; up.Y = d->M1; up.Yb = d->Xcat; up.ldy = d->I + d->H;
+  return launch_dstep_qkv_up(q, up, st);
+}
+// the row kernel: hout = sum of nslab split-K slabs + (b2 + bd) + hin, and the next layer's two LayerNorms
+static int resid_ln(etd_dec* d, int l, int nslab, const float* hin, float* hout, int M, const NextLn& nx, hipStream_t st) {
+  return launch_resid_ln_rows(d->Pk, nslab, d->layers[l].cat.b, nullptr, hin, hout, M, d->H, nx.g1, nx.b1, nx.g2, nx.b2, d->cfg.layer_norm_eps, nx.x1, nx.x2, st);
+}
+// (down | dense) projection with K split over workgroups, then ONE row kernel: partial sums + bias + residual and the
+// next layer's two LayerNorms.  (Folding that row kernel into the GEMM's last-arriving workgroup was measured: the
+// serial read of 5 slabs x 32 rows costs 3x the kernel boundary it saves.)
+static int down_splitk(etd_dec* d, int l, const float* hin, float* hout, int M, const NextLn& nx, hipStream_t st) {
+  DGemmArgs dn = lin_args(d->layers[l].cat, d->M1, d->I + d->H, M); dn.Xb = d->Xcat; dn.hin = hin; dn.hout = hout; dn.k_splits = DS_K_SPLITS; dn.Y = d->Pk; dn.ldy = d->H;
+  ETD_TRY(launch_dgemm(dn, DEPI_PARTIAL, true, st));
+  return resid_ln(d, l, DS_K_SPLITS, hin, hout, M, nx, st);
+}
+// k_linear's decoder modes: M 16-bit rows X [M][w.K] against w in fragment order; `dec` carries what the epilogue reads
+static int linear16(const Lin& w, const d16* X, int M, const DGemmArgs& dec, int epi, hipStream_t st) {
+  LinArgs a = {};
+  a.X = (const e16*)X; a.ldx = w.K; a.W = (const e16*)w.Wf;     /* (LinArgs carries the extractor's element type; the decoder modes of k_linear read these as d16) */
+  a.bias = w.b; a.M = M; a.N = w.N; a.K = w.K; a.vt_block = -1; a.dec = dec;
+  return launch_linear_dec(a, epi, st);
 }
 
 // ---- fp32 mode, >= G3_MIN_ROWS rows: the layer as LayerNorm rows -> QKV (+RoPE, KV append) -> attention -> dense -> up + GELU -> down + residual with every
 // contraction on the f16 matrix cores at fp32 grade (csrc/gemm3.h).  Prefill: ragged causal attention over the prompts straight from the fp32 cache rows the QKV
 // epilogue has just written, and the last layer's tail only for each prompt's last position; decode step: k_dattn<float> per (row, head).
 static int gemm3_auto(const DGemmArgs& a, int epi, hipStream_t st) { return gemm3_s_takes(a, epi) ? launch_gemm3_s(a, epi, st) : launch_gemm3(a, epi, st); }
-int forward_body_x3(etd_dec* d, int M, const DecRows& rows, float** hfinal, hipStream_t st, const PrefillInfo* pf, const LastOnly* lo, bool* compact) {
+// last layer: every position's K / V is in the cache now; attention, MLP and residual are needed for the prompts' last rows only (on the weight-streaming kernels).
+// gather rows -> attention -> dense -> up + GELU -> down + residual: hout rows 0 .. n-1 = the prompts' last positions, in prompt order
+static int x3_last_rows(etd_dec* d, const LastOnly& lo, const float* hin, float* hout, hipStream_t st) {
+  const int n = lo.n, l = d->L - 1, H = d->H; const Layer& w = d->layers[l];
+  ETD_TRY(launch_gather_rows(hin, lo.idx, n, H, d->hlast, st)); ETD_TRY(launch_gather_rows(d->Q, lo.idx, n, H, d->t_q, st));
+  DAttnArgs at = attn_args(d, l, lo.rows, n); at.Q = d->t_q; at.O = d->t_ao; at.bytes_hint = 0;
+  ETD_TRY(launch_dattn(at, false, st));
+  DGemmArgs de = lin_args(w.dense, d->t_ao, H, n); de.Y = d->t_do; de.ldy = H;
+  ETD_TRY(launch_dgemm(de, DEPI_BIAS, false, st));
+  DGemmArgs up = lin_args(w.up, d->hlast, H, n); up.Y = d->t_m1; up.ldy = d->I; up.ln_g = w.ln2g; up.ln_b = w.ln2b; up.ln_eps = d->cfg.layer_norm_eps;
+  ETD_TRY(launch_dgemm(up, DEPI_GELU, false, st));
+  DGemmArgs dn = lin_args(w.down, d->t_m1, d->I, n); dn.add = d->t_do; dn.hin = d->hlast; dn.hout = hout;
+  return launch_dgemm(dn, DEPI_RESID, false, st);
+}
+// every other layer, after its QKV: attention (prefill: ragged causal attn3; decode step: k_dattn) -> dense -> up + GELU -> down + residual
+static int x3_layer_rest(etd_dec* d, int l, const DecRows& rows, int M, const PrefillInfo* pf, const float* hin, float* hout, hipStream_t st) {
+  const Layer& w = d->layers[l]; const int H = d->H;
+  if (pf) {
+    Attn3Args t = {};
+    t.Q = d->Q; t.ldq = H; t.K = (const float*)kv_layer(d, d->Kc, l); t.V = (const float*)kv_layer(d, d->Vc, l); t.O = d->AO; t.ldo = H; t.n_seq = pf->n; t.n_heads = d->nh;
+    t.seq_row0 = pf->seq_row0; t.seq_len = pf->seq_len; t.row_slot = rows.slot; t.slot_stride = d->slot_stride; t.max_ctx = d->ctx; t.max_len = pf->max_len;
+    t.scale = 0.125f; t.q_log2 = w.q_log2; t.k_log2 = w.k_log2; t.v_log2 = w.v_log2; t.flops_hint = pf->attn_flops;
+    ETD_TRY(launch_attn3(t, st));
+  } else {
+    DAttnArgs at = attn_args(d, l, rows, M);
+    at.O = d->AO; attn_stamp(d, l, &at);
+    if (rows.slot == d->row_slot) attn_step_pairs(d, &at);
+    ETD_TRY(launch_dattn(at, false, st));
+  }
+  DGemmArgs de = lin_args(w.dense, d->AO, H, M); de.Y = d->DO; de.ldy = H;      // (attention output: a convex combination of V rows)
+  ETD_TRY(gemm3_auto(de, DEPI_BIAS, st));
+  DGemmArgs up = lin_args(w.up, d->X2f, H, M); up.Y = d->M1; up.ldy = d->I;
+  ETD_TRY(gemm3_auto(up, DEPI_GELU, st));
+  DGemmArgs dn = lin_args(w.down, d->M1, d->I, M); dn.add = d->DO; dn.hin = hin; dn.hout = hout;
+  return gemm3_auto(dn, DEPI_RESID, st);
+}
+static int forward_x3(etd_dec* d, int M, const DecRows& rows, const PrefillInfo* pf, const LastOnly* lo, hipStream_t st, float** hfinal, bool* compact) {
+  const bool tail = lo && pf && lo->n >= 1 && lo->n < G3_MIN_ROWS && lo->n <= d->S;
   float* hin = d->h; float* hout = d->h2;
-  const int H = d->H;
   for (int l = 0; l < d->L; ++l) {
     const Layer& w = d->layers[l];
-    void* Kl = (char*)d->Kc + (size_t)l * d->layer_stride * 4;
-    void* Vl = (char*)d->Vc + (size_t)l * d->layer_stride * 4;
-    ETD_TRY(launch_ln_rows_f32(hin, M, H, w.ln1g, w.ln1b, w.ln2g, w.ln2b, d->cfg.layer_norm_eps, d->X1f, d->X2f, st));
-    DGemmArgs q = g3_args(d->X1f, H, w.qkv, M);
-    q.rows = rows; q.rope_cos = d->rope_cos; q.rope_sin = d->rope_sin; q.rot_half = 8; q.Q = d->Q;
-    q.Kc = Kl; q.Vc = Vl; q.slot_stride = d->slot_stride; q.max_ctx = d->ctx; q.n_heads = d->nh;
-    ETD_TRY(gemm3_auto(q, DEPI_QKV, st));
-    if (l == d->L - 1 && lo && pf && lo->n >= 1 && lo->n < G3_MIN_ROWS && lo->n <= d->S) {
-      // last layer: every position's K / V is in the cache now; attention, MLP and residual are needed for the prompts' last rows only
-      const int n = lo->n;
-      ETD_TRY(launch_gather_rows(hin, lo->idx, n, H, d->hlast, st));
-      ETD_TRY(launch_gather_rows(d->Q, lo->idx, n, H, d->t_q, st));
-      DAttnArgs at = {};
-      at.Q = d->t_q; at.Kc = Kl; at.Vc = Vl; at.slot_stride = d->slot_stride; at.max_ctx = d->ctx; at.n_heads = d->nh;
-      at.rows = lo->rows; at.M = n; at.O = d->t_ao; at.scale = 0.125f; at.bytes_hint = 0;
-      ETD_TRY(launch_dattn(at, false, st));
-      DGemmArgs de = g3_args(d->t_ao, H, w.dense, n); de.Y = d->t_do; de.ldy = H;
-      ETD_TRY(launch_dgemm(de, DEPI_BIAS, false, st));
-      DGemmArgs up = g3_args(d->hlast, H, w.up, n); up.Y = d->t_m1; up.ldy = d->I; up.ln_g = w.ln2g; up.ln_b = w.ln2b; up.ln_eps = d->cfg.layer_norm_eps;
-      ETD_TRY(launch_dgemm(up, DEPI_GELU, false, st));
-      DGemmArgs dn = g3_args(d->t_m1, d->I, w.down, n); dn.add = d->t_do; dn.hin = d->hlast; dn.hout = hout;
-      ETD_TRY(launch_dgemm(dn, DEPI_RESID, false, st));
-      *hfinal = hout;                          // rows 0 .. n-1 = the prompts' last positions, in prompt order
-      if (compact) *compact = true;
-      return ETD_OK;
-    }
-    if (pf) {
-      Attn3Args t = {};
-      t.Q = d->Q; t.ldq = H; t.K = (const float*)Kl; t.V = (const float*)Vl; t.O = d->AO; t.ldo = H; t.n_seq = pf->n; t.n_heads = d->nh;
-      t.seq_row0 = pf->seq_row0; t.seq_len = pf->seq_len; t.row_slot = rows.slot; t.slot_stride = d->slot_stride; t.max_ctx = d->ctx; t.max_len = pf->max_len;
-      t.scale = 0.125f; t.q_log2 = w.q_log2; t.k_log2 = w.k_log2; t.v_log2 = w.v_log2; t.flops_hint = pf->attn_flops;
-      ETD_TRY(launch_attn3(t, st));
-    } else {
-      DAttnArgs at = {};
-      at.Q = d->Q; at.Kc = Kl; at.Vc = Vl; at.slot_stride = d->slot_stride; at.max_ctx = d->ctx; at.n_heads = d->nh;
-      at.rows = rows; at.M = M; at.O = d->AO; at.scale = 0.125f; at.bytes_hint = d->attn_bytes_hint;
-      if (rows.slot == d->row_slot) { at.row_sp = d->row_sp; at.identity = d->rows_identity ? 1 : 0; }
-      at.stamp = d->stamp_on ? d->stamp_dev : nullptr; at.stamp_par = l & 1;
-      ETD_TRY(launch_dattn(at, false, st));
-    }
-    DGemmArgs de = g3_args(d->AO, H, w.dense, M); de.Y = d->DO; de.ldy = H;      // (attention output: a convex combination of V rows)
-    ETD_TRY(gemm3_auto(de, DEPI_BIAS, st));
-    DGemmArgs up = g3_args(d->X2f, H, w.up, M); up.Y = d->M1; up.ldy = d->I;
-    ETD_TRY(gemm3_auto(up, DEPI_GELU, st));
-    DGemmArgs dn = g3_args(d->M1, d->I, w.down, M); dn.add = d->DO; dn.hin = hin; dn.hout = hout;
-    ETD_TRY(gemm3_auto(dn, DEPI_RESID, st));
-    float* t = hin; hin = hout; hout = t;
+    ETD_TRY(launch_ln_rows_f32(hin, M, d->H, w.ln1g, w.ln1b, w.ln2g, w.ln2b, d->cfg.layer_norm_eps, d->X1f, d->X2f, st));
+    ETD_TRY(gemm3_auto(qkv_args(d, l, d->X1f, rows, M), DEPI_QKV, st));
+    ETD_TRY(tail && l == d->L - 1 ? x3_last_rows(d, *lo, hin, hout, st) : x3_layer_rest(d, l, rows, M, pf, hin, hout, st));
+    std::swap(hin, hout);
+  }
+  *hfinal = hin; if (tail) *compact = true;
+  return ETD_OK;
+}
+
+// ---- plain sequence (fp32 weights below G3_MIN_ROWS rows, one row outside the fused step, 16-bit geometries the two 16-bit sequences below do not take):
+// QKV -> attention -> dense -> up + GELU -> down + residual, one launch_dgemm each.  act16 (16-bit weights, M > 1): k_ln_rows first and 16-bit activations between
+// the GEMMs; otherwise fp32 activations with the LayerNorms fused into the GEMM prologues (k_dgemm / k_dgemm_s / k_dgemv)
+static int forward_plain(etd_dec* d, int M, const DecRows& rows, bool act16, hipStream_t st, float** hfinal) {
+  float* hin = d->h; float* hout = d->h2; const float eps = d->cfg.layer_norm_eps;
+  for (int l = 0; l < d->L; ++l) {
+    const Layer& w = d->layers[l];
+    if (act16) ETD_TRY(ln_rows16(d, l, hin, M, st));
+    DGemmArgs q = qkv_args(d, l, hin, rows, M); q.Y = d->qkv_raw; q.ldy = 3 * d->H;
+    if (act16) q.Xb = d->X1b; else { q.ln_g = w.ln1g; q.ln_b = w.ln1b; q.ln_eps = eps; }
+    ETD_TRY(launch_dgemm(q, DEPI_QKV, d->bf16w, st));
+    ETD_TRY(layer_dattn(d, l, rows, M, act16 ? d->AOb : nullptr, 0, st));
+    DGemmArgs de = lin_args(w.dense, d->AO, d->H, M); de.Y = d->DO; de.ldy = d->H; if (act16) de.Xb = d->AOb;
+    ETD_TRY(launch_dgemm(de, DEPI_BIAS, d->bf16w, st));
+    DGemmArgs up = lin_args(w.up, hin, d->H, M); up.Y = d->M1; up.ldy = d->I;
+    if (act16) { up.Xb = d->X2b; up.Yb = d->M1b; } else { up.ln_g = w.ln2g; up.ln_b = w.ln2b; up.ln_eps = eps; }
+    ETD_TRY(launch_dgemm(up, DEPI_GELU, d->bf16w, st));
+    DGemmArgs dn = lin_args(w.down, d->M1, d->I, M); dn.add = d->DO; dn.hin = hin; dn.hout = hout; if (act16) dn.Xb = d->M1b;      // parallel residual: h = (mlp + attn) + h   (modeling_gpt_neox.py:272)
+    ETD_TRY(launch_dgemm(dn, DEPI_RESID, d->bf16w, st));
+    std::swap(hin, hout);
   }
   *hfinal = hin;
   return ETD_OK;
 }
 
-int forward_body(etd_dec* d, int M, const DecRows& rows, float** hfinal, hipStream_t st, const PrefillInfo* pf = nullptr, bool ln0_done = false,
-                 const LastOnly* lo = nullptr, bool* compact = nullptr, bool is_step = false) {
-  if (compact) *compact = false;
-  if (!d->bf16w && M >= G3_MIN_ROWS && d->X1f && d->layers[0].qkv.g3.Wp && d->layers[0].down.g3.Wp && g3_enabled()) return forward_body_x3(d, M, rows, hfinal, st, pf, lo, compact);
+// ---- 16-bit skinny sequence (a decode step of any row count, a prefill of <= DS_MAX_ROWS rows): QKV | up in one launch, attention.dense folded into the down projection
+// ([W2 | Wd] [gelu(..) ; attn] + (b2 + bd): one GEMM and no fp32 round trip of the dense output) as split-K slabs, then the row kernel.
+// Step trace after the QKV | up launch of layer l: Q, GELU(up) and the K / V rows (record layout: ETD_TRACE_LAYER)
+static int trace_qkv_up(etd_dec* d, int l, int M, hipStream_t st) {
+  if (!d->trace) return ETD_OK;
+  ETD_TRY(trace_rows(d, d->Q, d->H, d->H, 1, 0, M, l * ETD_TRACE_LAYER * M, st));
+  if (l == 0) HIP_TRY(hipMemcpyAsync(d->trace_q, d->Q, (size_t)M * d->H * 4, hipMemcpyDeviceToDevice, st));
+  ETD_TRY(trace_rows(d, d->Xcat, (d->I + d->H) / 2, d->I / 2, 1, 0, M, l * ETD_TRACE_LAYER * M + M, st));
+  if (d->nh == 8) {
+    hipLaunchKernelGGL(k_trace_kv, dim3(M, 8), dim3(64), 0, st, (const unsigned*)kv_layer(d, d->Kc, l), (const unsigned*)kv_layer(d, d->Vc, l), d->slot_stride / 2, d->ctx,
+                       d->row_slot, d->row_pos, M, d->trace, d->trace_step, d->trace_cap, trace_wps(d, M), l * ETD_TRACE_LAYER * M + 17 * M);
+    HIP_TRY(hipGetLastError());
+  }
+  return ETD_OK;
+}
+// decode step: attention (+ its share of attention.dense) and the MLP down projection in ONE launch, then the row kernel
+static int skinny_attn_down(etd_dec* d, int l, const DecRows& rows, int M, const float* hin, float* hout, hipStream_t st) {
+  const Layer& w = d->layers[l]; const NextLn nx = next_ln(d, l);
+  const int ksd = d->I / 512;      // slabs of the down projection; one more per head from the attention workgroups
+  DAttnArgs at = attn_args(d, l, rows, M);
+  attn_step_pairs(d, &at); attn_stamp(d, l, &at); at.pair = d->step_pair ? 1 : 0;
+  at.dense_w = (const d16*)w.dense_hw; at.dense_out = d->Pk + (size_t)ksd * M * d->H; at.dbg = (d->trace && l == 0) ? d->trace_dbg : nullptr;
+  DGemmArgs dn = lin_args(w.cat, nullptr, d->I + d->H, M); dn.Xb = d->Xcat; dn.k_splits = ksd; dn.Y = d->Pk; dn.ldy = d->H;
+  // ETD_ROWFIN=1: the row kernel (split-K sum + bias + residual + next LayerNorms) rides in the attention launch -- the last
+  // contributor of a row finishes it (DRowFin; 17 launches per step instead of 25, bit-identical results).  Measured round 2
+  // ((history: 4ac2f57) tools/runs/r2_run21/24/27.sh): a step of one engine 0.197 -> 0.185 ms, four engines stepping 9.9 -> 10.1 engine-steps/ms,
+  // but the JOB 569-575 -> 567 audio-s/s (the attention workgroups live 19 instead of 15.5 us and hold 128 registers per
+  // wave while the other engines' prefill GEMMs want the same CUs).  Off by default.
+  if (rowfin_on() && ksd + d->nh == 12 && M <= DS_STEP_MAX_ROWS) {
+    DRowFin fin = {};
+    fin.cnt = d->row_cnt + (size_t)l * DS_STEP_MAX_ROWS; fin.target = d->nh + 16 * ksd; fin.P = d->Pk; fin.nslab = 12;
+    fin.bias = w.cat.b; fin.hin = hin; fin.hout = hout; fin.eps = d->cfg.layer_norm_eps;
+    fin.g1 = nx.g1; fin.b1 = nx.b1; fin.g2 = nx.g2; fin.b2 = nx.b2; fin.x1 = nx.x1; fin.x2 = nx.x2;
+    return launch_dstep_attn_down(at, dn, &fin, st);
+  }
+  ETD_TRY(launch_dstep_attn_down(at, dn, nullptr, st));
+  if (d->trace && ksd + d->nh == 12) ETD_TRY(trace_rows(d, d->Pk, d->H, d->H, 12, (long long)M * d->H, M, l * ETD_TRACE_LAYER * M + 2 * M, st));
+  if (d->trace && l == 0 && ksd + d->nh == 12) HIP_TRY(hipMemcpyAsync(d->trace_pk, d->Pk, (size_t)12 * M * d->H * 4, hipMemcpyDeviceToDevice, st));
+  ETD_TRY(resid_ln(d, l, ksd + d->nh, hin, hout, M, nx, st));
+  if (d->trace) {
+    ETD_TRY(trace_rows(d, hout, d->H, d->H, 1, 0, M, l * ETD_TRACE_LAYER * M + 14 * M, st));
+    if (nx.x1) {
+      ETD_TRY(trace_rows(d, d->X1b, d->H / 2, d->H / 2, 1, 0, M, l * ETD_TRACE_LAYER * M + 15 * M, st));
+      ETD_TRY(trace_rows(d, d->X2b, d->H / 2, d->H / 2, 1, 0, M, l * ETD_TRACE_LAYER * M + 16 * M, st));
+    }
+  }
+  return ETD_OK;
+}
+// ln0_done: X1b / X2b already hold layer 0's LayerNorm rows (the fused step: written by the previous step's head kernel)
+static int forward_skinny16(etd_dec* d, int M, const DecRows& rows, bool ln0_done, hipStream_t st, float** hfinal) {
+  const bool attn_down = rows.slot == d->row_slot && d->H == 512 && d->nh == 8 && d->I % 512 == 0 && d->I / 512 + d->nh <= 12 && d->layers[0].dense_hw &&
+                         d->ctx >= 256 && !getenv("ETD_NO_ATTN_DOWN");
   float* hin = d->h; float* hout = d->h2;
-  const size_t esz = d->bf16w ? 2 : 4;
-  const bool bpipe = d->bf16w && (M > 1 || is_step);     // (is_step with M == 1: the fused step kernels for a single stream, ETD_FUSED_M1)
-  // a decode step (is_step: one row per stream, M <= DS_STEP_MAX_ROWS) stays on the fused step kernels whatever its row count
-  const bool big = bpipe && !is_step && M > DS_MAX_ROWS && d->layers[0].qkv.Wf && d->layers[0].up.Wf && d->layers[0].cat.Wf;
-  bool ln_ready = false;            // X1b / X2b already hold this layer's LayerNorm rows (written by the previous layer's k_dmlp_fused)
+  if (!ln0_done) ETD_TRY(ln_rows16(d, 0, hin, M, st));
   for (int l = 0; l < d->L; ++l) {
-    const Layer& w = d->layers[l];
-    void* Kl = (char*)d->Kc + (size_t)l * d->layer_stride * esz;
-    void* Vl = (char*)d->Vc + (size_t)l * d->layer_stride * esz;
-    const bool small = bpipe && !big && (d->I + d->H) % (5 * 64 * 8) == 0;            // decode step: split-K down projection + fused (partial-sum, residual, next LayerNorm) kernel
-    const bool catk = small || big;     // attention.dense folded into the down projection: [W2 | Wd] [gelu(..) ; attn] + (b2 + bd), one GEMM and no fp32 round trip of the dense output
-    // batched prefill on the fused MLP kernel: it also writes the NEXT layer's LayerNorm rows, so only layer 0 needs the row kernel
-    // ON by default, ETD_FUSED_PMLP=0 turns it off (read at create time for the packed stream, and per call so that the A/B test can toggle it): measured round 2
-    // ((history: 4ac2f57) tools/runs/r2_run47.sh) at 195 us per launch against 166 + 16 us for the launches it replaces, +1.3 % in the job -- csrc/dec_fused.hip
-    const bool fmlp = big && w.mlp_frag && d->H == 512 && d->I == 2048 && fused_pmlp_on();
-    if (bpipe && (!small || (l == 0 && !ln0_done)) && !ln_ready) ETD_TRY(launch_ln_rows(hin, M, d->H, w.ln1g, w.ln1b, w.ln2g, w.ln2b, d->cfg.layer_norm_eps, d->X1b, d->X2b, st));
-    ln_ready = false;
-    // ---- fused QKV + RoPE + KV append
-    DGemmArgs q = {};
-    q.X = hin; q.ldx = d->H; q.W = w.qkv.W; q.Wf = w.qkv.Wf; q.bias = w.qkv.b; q.M = M; q.N = w.qkv.N; q.Npad = w.qkv.Npad; q.K = d->H;
-    q.Wp = w.qkv.g3.Wp; q.w_log2 = w.qkv.g3.w_log2; q.x_log2 = w.qkv.g3.x_log2;
-    if (bpipe) q.Xb = d->X1b; else { q.ln_g = w.ln1g; q.ln_b = w.ln1b; q.ln_eps = d->cfg.layer_norm_eps; }
-    q.Y = d->qkv_raw; q.ldy = 3 * d->H;
-    q.rows = rows; q.rope_cos = d->rope_cos; q.rope_sin = d->rope_sin; q.rot_half = 8; q.Q = d->Q;
-    q.Kc = Kl; q.Vc = Vl; q.slot_stride = d->slot_stride; q.max_ctx = d->ctx; q.n_heads = d->nh;
-    const bool mfma_attn = big && pf != nullptr;
-    if (mfma_attn) q.Qb = d->Qb;       // (K / V: the attention reads the cache rows this epilogue writes)
-    if (big) {
-      static const bool pqkv_on = !getenv("ETD_NO_PQKV");
-      if (mfma_attn && pqkv_on && M >= 49152 && d->H == 512 && d->nh == 8 && w.qkv.N == 1536) {
-        // QKV with the token block stationary in registers and the weights streamed through LDS (csrc/dec_prefill.hip): 256-token workgroups that walk all 48 weight
-        // tiles -- from ~192 workgroups up (below that k_linear's 128 x 256 tiles fill the chip better: 6 466 rows 24 us against 86)
-        PQkvArgs pa = {};
-        pa.X = d->X1b; pa.ldx = d->H; pa.Wf = (const d16*)w.qkv.Wf; pa.bias = w.qkv.b; pa.M = M; pa.N = w.qkv.N; pa.rows = rows;
-        pa.rope_cos = d->rope_cos; pa.rope_sin = d->rope_sin; pa.Qb = d->Qb; pa.Kc = (d16*)Kl; pa.Vc = (d16*)Vl; pa.slot_stride = d->slot_stride;
-        pa.max_ctx = d->ctx; pa.n_heads = d->nh;
-        ETD_TRY(launch_pqkv(pa, st));
-      } else {
-        LinArgs a = {};
-        a.X = (const e16*)d->X1b; a.ldx = d->H; a.W = (const e16*)w.qkv.Wf;     /* (LinArgs carries the extractor's element type; the decoder modes of k_linear read these as d16) */ a.bias = w.qkv.b; a.M = M; a.N = w.qkv.N; a.K = d->H; a.vt_block = -1; a.dec = q;
-        ETD_TRY(launch_linear_dec(a, DEPI_QKV, st));
-      }
-      if (l == d->L - 1 && lo && mfma_attn && lo->n > 1 && lo->n <= DS_STEP_MAX_ROWS && d->H == 512 && (d->I + d->H) % (5 * 64 * 8) == 0 && !getenv("ETD_NO_LAST_ONLY")) {
-        // last layer, last positions only: every position's K/V is in the cache now; what remains of the layer is needed for
-        // n rows, not M (attention, MLP up, (down | dense), residual = 9 % of the prefill's FLOPs at 8 layers)
-        const int n = lo->n;
-        ETD_TRY(launch_gather_rows(hin, lo->idx, n, d->H, d->hlast, st));
-        ETD_TRY(launch_ln_rows(d->hlast, n, d->H, w.ln1g, w.ln1b, w.ln2g, w.ln2b, d->cfg.layer_norm_eps, d->X1b, d->X2b, st));
-        DGemmArgs q2 = q;
-        q2.X = d->hlast; q2.M = n; q2.rows = lo->rows; q2.Xb = d->X1b; q2.Qb = nullptr;
-        DGemmArgs up2 = {};
-        up2.X = d->hlast; up2.ldx = d->H; up2.W = w.up.W; up2.Wf = w.up.Wf; up2.bias = w.up.b; up2.M = n; up2.N = d->I; up2.Npad = w.up.Npad; up2.K = d->H;
-        up2.Y = d->M1; up2.Xb = d->X2b; up2.Yb = d->Xcat; up2.ldy = d->I + d->H;
-        ETD_TRY(launch_dstep_qkv_up(q2, up2, st));
-        DAttnArgs at = {};
-        at.Q = d->Q; at.Kc = Kl; at.Vc = Vl; at.slot_stride = d->slot_stride; at.max_ctx = d->ctx; at.n_heads = d->nh;
-        at.rows = lo->rows; at.M = n; at.O = d->AO; at.Ob = d->Xcat + d->I; at.ldob = d->I + d->H; at.scale = 0.125f; at.bytes_hint = 0;
-        ETD_TRY(launch_dattn(at, d->bf16w, st));
-        DGemmArgs dn2 = {};
-        dn2.X = d->M1; dn2.Xb = d->Xcat; dn2.ldx = d->I + d->H; dn2.W = w.cat.W; dn2.bias = w.cat.b; dn2.M = n; dn2.N = d->H; dn2.Npad = w.cat.Npad; dn2.K = d->I + d->H;
-        dn2.hin = d->hlast; dn2.hout = hout; dn2.k_splits = 5; dn2.Y = d->Pk; dn2.ldy = d->H;
-        ETD_TRY(launch_dgemm(dn2, DEPI_PARTIAL, true, st));
-        ETD_TRY(launch_resid_ln_rows(d->Pk, 5, w.cat.b, nullptr, d->hlast, hout, n, d->H, nullptr, nullptr, nullptr, nullptr, d->cfg.layer_norm_eps, nullptr, nullptr, st));
-        *hfinal = hout;                        // rows 0 .. n-1 = the prompts' last positions, in prompt order
-        if (compact) *compact = true;
-        return ETD_OK;
-      }
-    } else if (small) {
-      // decode step: QKV (+RoPE, KV append) and MLP up (+GELU -> Xcat) share one launch
-      DGemmArgs up = {};
-      up.X = hin; up.ldx = d->H; up.W = w.up.W; up.Wf = w.up.Wf; up.bias = w.up.b; up.M = M; up.N = d->I; up.Npad = w.up.Npad; up.K = d->H;
-      up.Y = d->M1; up.Xb = d->X2b; up.Yb = d->Xcat; up.ldy = d->I + d->H;
-      ETD_TRY(launch_dstep_qkv_up(q, up, st));
-      if (d->trace) {
-        ETD_TRY(trace_rows(d, d->Q, d->H, d->H, 1, 0, M, l * ETD_TRACE_LAYER * M, st));
-        if (l == 0) HIP_TRY(hipMemcpyAsync(d->trace_q, d->Q, (size_t)M * d->H * 4, hipMemcpyDeviceToDevice, st));
-        ETD_TRY(trace_rows(d, d->Xcat, (d->I + d->H) / 2, d->I / 2, 1, 0, M, l * ETD_TRACE_LAYER * M + M, st));
-        if (d->nh == 8) {
-          hipLaunchKernelGGL(k_trace_kv, dim3(M, 8), dim3(64), 0, st, (const unsigned*)Kl, (const unsigned*)Vl, d->slot_stride / 2, d->ctx, d->row_slot, d->row_pos, M,
-                             d->trace, d->trace_step, d->trace_cap, trace_wps(d, M), l * ETD_TRACE_LAYER * M + 17 * M);
-          HIP_TRY(hipGetLastError());
-        }
-      }
-    } else {
-      ETD_TRY(launch_dgemm(q, DEPI_QKV, d->bf16w, st));
-    }
-    // ---- decode step: attention (+ its share of attention.dense) and the MLP down projection in ONE launch, then the row kernel
-    const bool attn_down = small && rows.slot == d->row_slot && d->H == 512 && d->nh == 8 && d->I % 512 == 0 && d->I / 512 + d->nh <= 12 && w.dense_hw &&
-                           d->ctx >= 256 && !getenv("ETD_NO_ATTN_DOWN");
-    if (attn_down) {
-      DAttnArgs at = {};
-      at.Q = d->Q; at.Kc = Kl; at.Vc = Vl; at.slot_stride = d->slot_stride; at.max_ctx = d->ctx; at.n_heads = d->nh;
-      at.rows = rows; at.M = M; at.scale = 0.125f; at.bytes_hint = d->attn_bytes_hint;
-      at.pair = d->step_pair ? 1 : 0;
-      at.stamp = d->stamp_on ? d->stamp_dev : nullptr; at.stamp_par = l & 1;
-      at.row_sp = d->row_sp; at.identity = d->rows_identity ? 1 : 0;
-      const int ksd = d->I / 512;
-      at.dense_w = (const d16*)w.dense_hw; at.dense_out = d->Pk + (size_t)ksd * M * d->H;
-      at.dbg = (d->trace && l == 0) ? d->trace_dbg : nullptr;
-      DGemmArgs dn = {};
-      dn.Xb = d->Xcat; dn.ldx = d->I + d->H; dn.W = w.cat.W; dn.K = d->I + d->H; dn.M = M; dn.N = d->H; dn.Npad = d->H;
-      dn.k_splits = ksd; dn.Y = d->Pk; dn.ldy = d->H;
-      const Layer* nx = l + 1 < d->L ? &d->layers[l + 1] : nullptr;
-      // ETD_ROWFIN=1: the row kernel (split-K sum + bias + residual + next LayerNorms) rides in the attention launch -- the last
-      // contributor of a row finishes it (DRowFin; 17 launches per step instead of 25, bit-identical results).  Measured round 2
-      // ((history: 4ac2f57) tools/runs/r2_run21/24/27.sh): a step of one engine 0.197 -> 0.185 ms, four engines stepping 9.9 -> 10.1 engine-steps/ms,
-      // but the JOB 569-575 -> 567 audio-s/s (the attention workgroups live 19 instead of 15.5 us and hold 128 registers per
-      // wave while the other engines' prefill GEMMs want the same CUs).  Off by default.
-#ifdef ETD_EXPERIMENTS
-      static const bool rowfin = getenv("ETD_ROWFIN") && atoi(getenv("ETD_ROWFIN")) > 0;
-#else
-      constexpr bool rowfin = false;          // (measured dead end: built with -DETD_EXPERIMENTS only)
-#endif
-      if (rowfin && ksd + d->nh == 12 && M <= DS_STEP_MAX_ROWS) {
-        DRowFin fin = {};
-        fin.cnt = d->row_cnt + (size_t)l * DS_STEP_MAX_ROWS; fin.target = d->nh + 16 * ksd; fin.P = d->Pk; fin.nslab = 12;
-        fin.bias = w.cat.b; fin.hin = hin; fin.hout = hout; fin.eps = d->cfg.layer_norm_eps;
-        if (nx) { fin.g1 = nx->ln1g; fin.b1 = nx->ln1b; fin.g2 = nx->ln2g; fin.b2 = nx->ln2b; fin.x1 = d->X1b; fin.x2 = d->X2b; }
-        ETD_TRY(launch_dstep_attn_down(at, dn, &fin, st));
-      } else {
-        ETD_TRY(launch_dstep_attn_down(at, dn, nullptr, st));
-        if (d->trace && ksd + d->nh == 12) ETD_TRY(trace_rows(d, d->Pk, d->H, d->H, 12, (long long)M * d->H, M, l * ETD_TRACE_LAYER * M + 2 * M, st));
-        if (d->trace && l == 0 && ksd + d->nh == 12) HIP_TRY(hipMemcpyAsync(d->trace_pk, d->Pk, (size_t)12 * M * d->H * 4, hipMemcpyDeviceToDevice, st));
-        ETD_TRY(launch_resid_ln_rows(d->Pk, ksd + d->nh, w.cat.b, nullptr, hin, hout, M, d->H, nx ? nx->ln1g : nullptr, nx ? nx->ln1b : nullptr,
-                                     nx ? nx->ln2g : nullptr, nx ? nx->ln2b : nullptr, d->cfg.layer_norm_eps, nx ? d->X1b : nullptr, nx ? d->X2b : nullptr, st));
-        if (d->trace) {
-          ETD_TRY(trace_rows(d, hout, d->H, d->H, 1, 0, M, l * ETD_TRACE_LAYER * M + 14 * M, st));
-          if (nx) {
-            ETD_TRY(trace_rows(d, d->X1b, d->H / 2, d->H / 2, 1, 0, M, l * ETD_TRACE_LAYER * M + 15 * M, st));
-            ETD_TRY(trace_rows(d, d->X2b, d->H / 2, d->H / 2, 1, 0, M, l * ETD_TRACE_LAYER * M + 16 * M, st));
-          }
-        }
-      }
-      float* t = hin; hin = hout; hout = t;
-      continue;
-    }
-    // ---- causal attention against the slot's KV cache
-    if (mfma_attn) {
-      // ragged causal MFMA flash attention over the prompts of all streams at once, K / V straight from the cache rows (csrc/dec_prefill.hip)
-      PAttnArgs t = {};
-      t.Q = d->Qb; t.ldq = d->H; t.Kc = (const d16*)Kl; t.Vc = (const d16*)Vl; t.slot_stride = d->slot_stride; t.max_ctx = d->ctx; t.n_heads = d->nh;
-      t.O = d->Xcat + d->I; t.ldo = d->I + d->H; t.seq_row0 = pf->seq_row0; t.seq_len = pf->seq_len; t.row_slot = rows.slot;
-      t.n_seq = pf->n; t.max_len = pf->max_len; t.scale_log2e = 0.125f * 1.4426950408889634f; t.flops_hint = pf->attn_flops;
-      ETD_TRY(launch_pattn(t, st));
-    } else {
-      DAttnArgs at = {};
-      at.Q = d->Q; at.Kc = Kl; at.Vc = Vl; at.slot_stride = d->slot_stride; at.max_ctx = d->ctx; at.n_heads = d->nh;
-      at.rows = rows; at.M = M; at.O = d->AO;
-      at.Ob = bpipe ? d->AOb : nullptr; at.scale = 0.125f; at.bytes_hint = d->attn_bytes_hint;
-      if (rows.slot == d->row_slot) { at.row_sp = d->row_sp; at.identity = d->rows_identity ? 1 : 0; at.stamp = d->stamp_on ? d->stamp_dev : nullptr; at.stamp_par = l & 1; }     // decode step: the step's (slot, pos) pairs
-      if (catk) { at.Ob = d->Xcat + d->I; at.ldob = d->I + d->H; }
-      ETD_TRY(launch_dattn(at, d->bf16w, st));
-    }
-    // ---- attention.dense
-    DGemmArgs de = {};
-    de.X = d->AO; de.ldx = d->H; de.W = w.dense.W; de.bias = w.dense.b; de.M = M; de.N = d->H; de.Npad = w.dense.Npad; de.K = d->H;
-    de.Y = d->DO; de.ldy = d->H; de.Wp = w.dense.g3.Wp; de.w_log2 = w.dense.g3.w_log2; de.x_log2 = w.dense.g3.x_log2;
-    if (bpipe) de.Xb = d->AOb;
-    if (!catk) {                // (otherwise attention.dense is folded into the (down | dense) GEMM below)
-      ETD_TRY(launch_dgemm(de, DEPI_BIAS, d->bf16w, st));
-    }
-    // ---- MLP up + GELU
-    DGemmArgs up = {};
-    up.X = hin; up.ldx = d->H; up.W = w.up.W; up.bias = w.up.b; up.M = M; up.N = d->I; up.Npad = w.up.Npad; up.K = d->H;
-    up.Y = d->M1; up.ldy = d->I; up.Wp = w.up.g3.Wp; up.w_log2 = w.up.g3.w_log2; up.x_log2 = w.up.g3.x_log2;
-    if (bpipe) { up.Xb = d->X2b; up.Yb = d->M1b; if (catk) { up.Yb = d->Xcat; up.ldy = d->I + d->H; } } else { up.ln_g = w.ln2g; up.ln_b = w.ln2b; up.ln_eps = d->cfg.layer_norm_eps; }
-    if (fmlp) {
-      // up + GELU, (down | dense), residual and the next layer's LayerNorms: one launch, the hidden layer never leaves the CU
-      const Layer* nx = l + 1 < d->L ? &d->layers[l + 1] : nullptr;
-      DMlpArgs ma = {};
-      ma.X2 = d->X2b; ma.AO = d->Xcat + d->I; ma.ldao = d->I + d->H; ma.hin = hin; ma.hout = hout; ma.Wm = (const d16*)w.mlp_frag;
-      ma.b_up = w.up.b; ma.b_cat = w.cat.b; ma.eps = d->cfg.layer_norm_eps; ma.M = M;
-      if (nx) { ma.g1 = nx->ln1g; ma.b1 = nx->ln1b; ma.g2 = nx->ln2g; ma.b2 = nx->ln2b; ma.nx1 = d->X1b; ma.nx2 = d->X2b; }
-      ETD_TRY(launch_dmlp_fused(ma, st));
-      ln_ready = nx != nullptr;
-      float* t = hin; hin = hout; hout = t;
-      continue;
-    }
-    if (big) {
-      LinArgs a = {};
-      a.X = (const e16*)d->X2b; a.ldx = d->H; a.W = (const e16*)w.up.Wf; a.bias = w.up.b; a.M = M; a.N = d->I; a.K = d->H; a.vt_block = -1; a.dec = up;
-      ETD_TRY(launch_linear_dec(a, DEPI_GELU, st));
-    } else if (!small) {        // (decode step: already issued together with QKV)
-      ETD_TRY(launch_dgemm(up, DEPI_GELU, d->bf16w, st));
-    }
-    // ---- MLP down + parallel residual: h = (mlp + attn) + h   (modeling_gpt_neox.py:272)
-    DGemmArgs dn = {};
-    dn.X = d->M1; dn.ldx = d->I; dn.W = w.down.W; dn.bias = w.down.b; dn.M = M; dn.N = d->H; dn.Npad = w.down.Npad; dn.K = d->I;
-    dn.add = d->DO; dn.hin = hin; dn.hout = hout; dn.Wp = w.down.g3.Wp; dn.w_log2 = w.down.g3.w_log2; dn.x_log2 = w.down.g3.x_log2;
-    if (bpipe) dn.Xb = d->M1b;
-    if (big) {
-      dn.add = nullptr;
-      LinArgs a = {};
-      a.X = (const e16*)d->Xcat; a.ldx = d->I + d->H; a.W = (const e16*)w.cat.Wf; a.bias = w.cat.b; a.M = M; a.N = d->H; a.K = d->I + d->H; a.vt_block = -1; a.dec = dn;
-      ETD_TRY(launch_linear_dec(a, DEPI_RESID, st));
-    } else if (small) {
-      // (down | dense) projection with K split over workgroups, then ONE row kernel: partial sums + bias + residual and the
-      // next layer's two LayerNorms.  (Folding that row kernel into the GEMM's last-arriving workgroup was measured: the
-      // serial read of 5 slabs x 32 rows costs 3x the kernel boundary it saves.)
-      dn.Xb = d->Xcat; dn.ldx = d->I + d->H; dn.W = w.cat.W; dn.K = d->I + d->H; dn.Npad = w.cat.Npad;
-      dn.k_splits = 5; dn.Y = d->Pk; dn.ldy = d->H;
-      ETD_TRY(launch_dgemm(dn, DEPI_PARTIAL, true, st));
-      const Layer* nx = l + 1 < d->L ? &d->layers[l + 1] : nullptr;
-      ETD_TRY(launch_resid_ln_rows(d->Pk, 5, w.cat.b, nullptr, hin, hout, M, d->H, nx ? nx->ln1g : nullptr, nx ? nx->ln1b : nullptr,
-                                   nx ? nx->ln2g : nullptr, nx ? nx->ln2b : nullptr, d->cfg.layer_norm_eps, nx ? d->X1b : nullptr, nx ? d->X2b : nullptr, st));
-    } else {
-      ETD_TRY(launch_dgemm(dn, DEPI_RESID, d->bf16w, st));
-    }
-    float* t = hin; hin = hout; hout = t;
+    ETD_TRY(step_qkv_up(d, l, hin, rows, M, st));
+    ETD_TRY(trace_qkv_up(d, l, M, st));
+    if (attn_down) ETD_TRY(skinny_attn_down(d, l, rows, M, hin, hout, st));
+    else { ETD_TRY(layer_dattn(d, l, rows, M, d->Xcat + d->I, d->I + d->H, st)); ETD_TRY(down_splitk(d, l, hin, hout, M, next_ln(d, l), st)); }
+    std::swap(hin, hout);
   }
   *hfinal = hin;
   return ETD_OK;
+}
+
+// ---- 16-bit big prefill sequence (more than DS_MAX_ROWS rows): k_ln_rows -> QKV on the big-tile MFMA GEMM (k_linear decoder modes) or k_pqkv -> ragged MFMA flash
+// attention (pf; without it k_dattn per row) -> the fused MLP kernel, or up + GELU and (down | dense) + residual as two k_linear launches
+static int prefill16_qkv(etd_dec* d, int l, const float* hin, const DecRows& rows, int M, bool mfma_attn, hipStream_t st) {
+  const Layer& w = d->layers[l];
+  DGemmArgs q = qkv_args(d, l, hin, rows, M); q.Xb = d->X1b; q.Y = d->qkv_raw; q.ldy = 3 * d->H;
+  if (mfma_attn) q.Qb = d->Qb;       // (K / V: the attention reads the cache rows this epilogue writes)
+  static const bool pqkv_on = !getenv("ETD_NO_PQKV");
+  if (!(mfma_attn && pqkv_on && M >= 49152 && d->H == 512 && d->nh == 8 && w.qkv.N == 1536)) return linear16(w.qkv, d->X1b, M, q, DEPI_QKV, st);
+  // QKV with the token block stationary in registers and the weights streamed through LDS (csrc/dec_prefill.hip): 256-token workgroups that walk all 48 weight
+  // tiles -- from ~192 workgroups up (below that k_linear's 128 x 256 tiles fill the chip better: 6 466 rows 24 us against 86)
+  PQkvArgs pa = {};
+  pa.X = d->X1b; pa.ldx = d->H; pa.Wf = (const d16*)w.qkv.Wf; pa.bias = w.qkv.b; pa.M = M; pa.N = w.qkv.N; pa.rows = rows;
+  pa.rope_cos = d->rope_cos; pa.rope_sin = d->rope_sin; pa.Qb = d->Qb; pa.Kc = (d16*)q.Kc; pa.Vc = (d16*)q.Vc; pa.slot_stride = d->slot_stride; pa.max_ctx = d->ctx; pa.n_heads = d->nh;
+  return launch_pqkv(pa, st);
+}
+// every other layer, after its QKV: attention into the block of Xcat behind GELU(up), then the MLP with attention.dense folded in, and the residual
+static int prefill16_layer_rest(etd_dec* d, int l, const DecRows& rows, int M, const PrefillInfo* pf, bool fmlp, const float* hin, float* hout, hipStream_t st) {
+  const Layer& w = d->layers[l];
+  if (pf) {
+    // ragged causal MFMA flash attention over the prompts of all streams at once, K / V straight from the cache rows (csrc/dec_prefill.hip)
+    PAttnArgs t = {};
+    t.Q = d->Qb; t.ldq = d->H; t.Kc = (const d16*)kv_layer(d, d->Kc, l); t.Vc = (const d16*)kv_layer(d, d->Vc, l); t.slot_stride = d->slot_stride; t.max_ctx = d->ctx; t.n_heads = d->nh;
+    t.O = d->Xcat + d->I; t.ldo = d->I + d->H; t.seq_row0 = pf->seq_row0; t.seq_len = pf->seq_len; t.row_slot = rows.slot;
+    t.n_seq = pf->n; t.max_len = pf->max_len; t.scale_log2e = 0.125f * 1.4426950408889634f; t.flops_hint = pf->attn_flops;
+    ETD_TRY(launch_pattn(t, st));
+  } else ETD_TRY(layer_dattn(d, l, rows, M, d->Xcat + d->I, d->I + d->H, st));
+  if (fmlp) {
+    // up + GELU, (down | dense), residual and the next layer's LayerNorms: one launch, the hidden layer never leaves the CU
+    const NextLn nx = next_ln(d, l); DMlpArgs ma = {};
+    ma.X2 = d->X2b; ma.AO = d->Xcat + d->I; ma.ldao = d->I + d->H; ma.hin = hin; ma.hout = hout; ma.Wm = (const d16*)w.mlp_frag;
+    ma.b_up = w.up.b; ma.b_cat = w.cat.b; ma.eps = d->cfg.layer_norm_eps; ma.M = M;
+    ma.g1 = nx.g1; ma.b1 = nx.b1; ma.g2 = nx.g2; ma.b2 = nx.b2; ma.nx1 = nx.x1; ma.nx2 = nx.x2;
+    return launch_dmlp_fused(ma, st);
+  }
+  DGemmArgs up = {}; up.Yb = d->Xcat; up.ldy = d->I + d->H;      // (what k_linear's GELU and RESID epilogues read of `dec`)
+  ETD_TRY(linear16(w.up, d->X2b, M, up, DEPI_GELU, st));
+  DGemmArgs dn = {}; dn.N = d->H; dn.hin = hin; dn.hout = hout;
+  return linear16(w.cat, d->Xcat, M, dn, DEPI_RESID, st);
+}
+// last layer, last positions only: every position's K/V is in the cache now; what remains of the layer is needed for
+// n rows, not M (attention, MLP up, (down | dense), residual = 9 % of the prefill's FLOPs at 8 layers) and runs on the skinny sequence's kernels.
+// gather rows -> k_ln_rows -> QKV | up -> attention -> split-K (down | dense) -> row kernel: hout rows 0 .. n-1 = the prompts' last positions, in prompt order
+static int prefill16_last_rows(etd_dec* d, const LastOnly& lo, const float* hin, float* hout, hipStream_t st) {
+  const int n = lo.n, l = d->L - 1;
+  ETD_TRY(launch_gather_rows(hin, lo.idx, n, d->H, d->hlast, st));
+  ETD_TRY(ln_rows16(d, l, d->hlast, n, st));
+  ETD_TRY(step_qkv_up(d, l, d->hlast, lo.rows, n, st));
+  DAttnArgs at = attn_args(d, l, lo.rows, n); at.O = d->AO; at.Ob = d->Xcat + d->I; at.ldob = d->I + d->H; at.bytes_hint = 0;
+  ETD_TRY(launch_dattn(at, d->bf16w, st));
+  return down_splitk(d, l, d->hlast, hout, n, NextLn{}, st);
+}
+static int forward_prefill16(etd_dec* d, int M, const DecRows& rows, const PrefillInfo* pf, const LastOnly* lo, hipStream_t st, float** hfinal, bool* compact) {
+  // batched prefill on the fused MLP kernel: it also writes the NEXT layer's LayerNorm rows, so only layer 0 needs the row kernel
+  // ON by default, ETD_FUSED_PMLP=0 turns it off (read at create time for the packed stream, and per call so that the A/B test can toggle it): measured round 2
+  // ((history: 4ac2f57) tools/runs/r2_run47.sh) at 195 us per launch against 166 + 16 us for the launches it replaces, +1.3 % in the job -- csrc/dec_fused.hip
+  const bool fmlp = d->layers[0].mlp_frag && d->H == 512 && d->I == 2048 && fused_pmlp_on();
+  const bool tail = lo && pf && lo->n > 1 && lo->n <= DS_STEP_MAX_ROWS && step_shape(d) && !getenv("ETD_NO_LAST_ONLY");
+  float* hin = d->h; float* hout = d->h2;
+  for (int l = 0; l < d->L; ++l) {
+    if (l == 0 || !fmlp) ETD_TRY(ln_rows16(d, l, hin, M, st));
+    ETD_TRY(prefill16_qkv(d, l, hin, rows, M, pf != nullptr, st));
+    ETD_TRY(tail && l == d->L - 1 ? prefill16_last_rows(d, *lo, hin, hout, st) : prefill16_layer_rest(d, l, rows, M, pf, fmlp, hin, hout, st));
+    std::swap(hin, hout);
+  }
+  *hfinal = hin; if (tail) *compact = true;
+  return ETD_OK;
+}
+
+// ---- picks the sequence, once per call.  *hfinal = the buffer that holds the last layer's output (before the final LayerNorm); lo (with compact): the last layer may run for the prompts' last rows alone, *compact says whether it did
+static int forward_rows(etd_dec* d, int M, const DecRows& rows, const PrefillInfo* pf, const LastOnly* lo, hipStream_t st, float** hfinal, bool* compact) {
+  if (compact) *compact = false; else lo = nullptr;
+  const Layer& w0 = d->layers[0];
+  if (!d->bf16w && M >= G3_MIN_ROWS && d->X1f && w0.qkv.g3.Wp && w0.down.g3.Wp && g3_enabled()) return forward_x3(d, M, rows, pf, lo, st, hfinal, compact);
+  const bool act16 = d->bf16w && M > 1;
+  if (act16 && M > DS_MAX_ROWS && w0.qkv.Wf && w0.up.Wf && w0.cat.Wf) return forward_prefill16(d, M, rows, pf, lo, st, hfinal, compact);
+  if (act16 && ksplit_fits(d)) return forward_skinny16(d, M, rows, false, st, hfinal);
+  return forward_plain(d, M, rows, act16, st, hfinal);
 }
 
 // final LayerNorm + lm_head for `n` rows of X (fp32 [n][H]) -> logits [n][V]
 int head_logits(etd_dec* d, const float* X, int n, float* logits, hipStream_t st) {
-  if (!d->bf16w && n >= G3_MIN_ROWS && d->X1f && d->head.g3.Wp && g3_enabled()) {
-    ETD_TRY(launch_ln_rows_f32(X, n, d->H, d->lnfg, d->lnfb, nullptr, nullptr, d->cfg.layer_norm_eps, d->X1f, nullptr, st));
-    DGemmArgs lm = g3_args(d->X1f, d->H, d->head, n);
-    lm.bias = nullptr; lm.Y = logits; lm.ldy = d->V;
-    return launch_gemm3(lm, DEPI_LOGITS, st);
-  }
-  DGemmArgs lm = {};
-  lm.X = X; lm.ldx = d->H; lm.W = d->head.W; lm.bias = nullptr; lm.M = n; lm.N = d->V; lm.Npad = d->head.Npad; lm.K = d->H;
-  lm.ln_g = d->lnfg; lm.ln_b = d->lnfb; lm.ln_eps = d->cfg.layer_norm_eps; lm.Y = logits; lm.ldy = d->V;
-  lm.Wp = d->head.g3.Wp; lm.w_log2 = d->head.g3.w_log2; lm.x_log2 = d->head.g3.x_log2;
+  const bool g3 = !d->bf16w && n >= G3_MIN_ROWS && d->X1f && d->head.g3.Wp && g3_enabled();
+  if (g3) ETD_TRY(launch_ln_rows_f32(X, n, d->H, d->lnfg, d->lnfb, nullptr, nullptr, d->cfg.layer_norm_eps, d->X1f, nullptr, st));
+  DGemmArgs lm = lin_args(d->head, g3 ? d->X1f : X, d->H, n);
+  lm.bias = nullptr; lm.Y = logits; lm.ldy = d->V;
+  if (g3) return launch_gemm3(lm, DEPI_LOGITS, st);
+  lm.ln_g = d->lnfg; lm.ln_b = d->lnfb; lm.ln_eps = d->cfg.layer_norm_eps;
   return launch_dgemm(lm, DEPI_LOGITS, d->bf16w, st);
 }
 
@@ -598,8 +601,7 @@ int stage_and_forward(etd_dec* d, int n, const int32_t* slots, const int32_t* T,
   PrefillInfo pf{n, sg->seq_row0, sg->seq_len, max_len, aflops};
   const bool can_mfma_attn = (d->bf16w ? d->Qb != nullptr : d->X1f != nullptr) && !ETD_XENV("ETD_NO_MFMA_PREFILL_ATTN");
   LastOnly lo{n, sg->last_idx, DecRows{sg->last_slot, sg->last_pos, sg->last_active}};
-  ETD_TRY(forward_body(d, M, e.rows, hfinal, st, can_mfma_attn ? &pf : nullptr, false, last_only ? &lo : nullptr, last_only));
-  return ETD_OK;
+  return forward_rows(d, M, e.rows, can_mfma_attn ? &pf : nullptr, &lo, st, hfinal, last_only);
 }
 
 // KV cache, activation workspaces and stream state of one handle (everything that is not a weight)
@@ -924,6 +926,13 @@ extern "C" void etd_decoder_destroy(etd_dec* d) {
   delete d;
 }
 
+// token choice + stream state update from d->logits for M rows (the caller adds the sampling fields)
+static DArgmaxArgs argmax_args(const etd_dec* d, const DecRows& rows, int M) {
+  DArgmaxArgs am = {};
+  am.logits = d->logits; am.ldl = d->V; am.V = d->V; am.M = M; am.rows = rows; am.eos = d->eos; am.limit = d->limit;
+  am.cur_tok = d->cur_tok; am.len = d->len; am.done = d->done; am.n_out = d->n_out; am.out_tok = d->out_tok; am.out_cap = d->out_cap;
+  return am;
+}
 extern "C" int etd_decoder_begin_bars(etd_dec* d, int n, const int32_t* slots, const int32_t* T, const int32_t* ids, const int32_t* cls,
                                       const int32_t* attrs4, const int32_t* tgt_attrs4, const int32_t* eos_ids, const int32_t* limits, void* stream) {
   hipStream_t st = (hipStream_t)stream;
@@ -945,12 +954,7 @@ extern "C" int etd_decoder_begin_bars(etd_dec* d, int n, const int32_t* slots, c
   }
   // the row-finish counters (ETD_ROWFIN=1) are zero between launches by construction (the last arriver resets its word); a launch
   // that died half way would leave them poisoned for good, so every bar starts from zero anyway (16 KiB, on the stream)
-#ifdef ETD_EXPERIMENTS
-  static const bool rowfin_on = getenv("ETD_ROWFIN") && atoi(getenv("ETD_ROWFIN")) > 0;
-#else
-  constexpr bool rowfin_on = false;
-#endif
-  if (rowfin_on && d->row_cnt) HIP_TRY(hipMemsetAsync(d->row_cnt, 0, (size_t)d->L * DS_STEP_MAX_ROWS * sizeof(int), st));
+  if (rowfin_on() && d->row_cnt) HIP_TRY(hipMemsetAsync(d->row_cnt, 0, (size_t)d->L * DS_STEP_MAX_ROWS * sizeof(int), st));
   Staged sg; float* hf = nullptr;
   bool compact = false;
   ETD_TRY(stage_and_forward(d, n, slots, T, ids, cls, attrs4, init.data(), &sg, &hf, st, &compact));
@@ -961,11 +965,7 @@ extern "C" int etd_decoder_begin_bars(etd_dec* d, int n, const int32_t* slots, c
     ETD_TRY(launch_gather_rows(hf, sg.last_idx, n, d->H, d->hlast, st));
     ETD_TRY(head_logits(d, d->hlast, n, d->logits, st));
   }
-  DArgmaxArgs am = {};
-  am.logits = d->logits; am.ldl = d->V; am.V = d->V; am.M = n;
-  am.rows = DecRows{sg.last_slot, sg.last_pos, sg.last_active};
-  am.cur_tok = d->cur_tok; am.len = d->len; am.done = d->done; am.n_out = d->n_out; am.out_tok = d->out_tok; am.out_cap = d->out_cap;
-  am.eos = d->eos; am.limit = d->limit;
+  DArgmaxArgs am = argmax_args(d, DecRows{sg.last_slot, sg.last_pos, sg.last_active}, n);
   if (d->sampling) { am.samp = d->samp_dev; am.rng_key = d->rng_key; }
   ETD_TRY(launch_dargmax(am, st));
   return ETD_OK;
@@ -993,6 +993,22 @@ extern "C" int etd_decoder_begin_bar(etd_dec* d, int slot, const int32_t* ids, c
   return etd_decoder_begin_bars(d, 1, &sl, &tt, ids, cls, attrs4, tgt_attrs4, &eo, &li, stream);
 }
 
+// the fused step's last launch: final LayerNorm + lm_head + token choice + stream state of `M` rows of hf, then the next step's rows, embeddings and layer-0 LayerNorms
+static DHeadArgs head_args(const etd_dec* d, const float* hf, int M, int vpad) {
+  const Layer& w0 = d->layers[0];
+  DHeadArgs hd = {};
+  hd.hfin = hf; hd.M = M; hd.H = d->H; hd.V = d->V; hd.Vpad = vpad;
+  hd.lnf_g = d->lnfg; hd.lnf_b = d->lnfb; hd.eps = d->cfg.layer_norm_eps; hd.Whead = (const d16*)d->head_frag;
+  hd.row_slot = d->row_slot; hd.row_pos = d->row_pos; hd.row_active = d->row_active; hd.row_sp = d->row_sp;
+  hd.cur_tok = d->cur_tok; hd.len = d->len; hd.done = d->done; hd.n_out = d->n_out; hd.out_tok = d->out_tok; hd.out_cap = d->out_cap;
+  hd.eos = d->eos; hd.limit = d->limit; hd.tgt_attrs = d->tgt_attrs; hd.tgt_proj = d->tgt_proj; hd.tgt_cls = 2; hd.n_bins = d->cfg.num_attribute_bins;
+  hd.word = d->word; hd.cls_emb = d->cls_emb; hd.attr_tab = d->attr_tab;
+  hd.g1 = w0.ln1g; hd.b1 = w0.ln1b; hd.g2 = w0.ln2g; hd.b2 = w0.ln2b;
+  hd.h = d->h; hd.x1 = d->X1b; hd.x2 = d->X2b;
+  hd.samp = d->samp_dev; hd.rng_key = d->rng_key;             // the device-side config selects greedy / sampling
+  hd.logits_dbg = d->logits_dbg_on ? d->logits_dbg : nullptr;
+  return hd;
+}
 extern "C" int etd_decoder_step(etd_dec* d, const int32_t* slots, int n_active, int n_steps, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   if (!d || !slots || n_active < 1 || n_active > d->S || n_steps < 1) ETD_FAIL(ETD_EINVAL, "decoder_step: bad args");
@@ -1027,7 +1043,7 @@ extern "C" int etd_decoder_step(etd_dec* d, const int32_t* slots, int n_active, 
   // A single stream steps on the fused kernels too (round 3; ETD_FUSED_M1=0: the GEMV sequence of rounds 1-2): 25 launches per step instead of ~36 and the same
   // arithmetic as inside a batch -- one job of 92 bars x 48 tokens 1.09 -> 0.66 s (tools/runs3/r3_run20.sh), every decoder golden unchanged.
   static const bool fused_m1 = !(ETD_XENV("ETD_FUSED_M1") && atoi(ETD_XENV("ETD_FUSED_M1")) == 0);
-  const bool fused = d->bf16w && (n_active > 1 || fused_m1) && n_active <= DS_STEP_MAX_ROWS && (d->I + d->H) % (5 * 64 * 8) == 0 && d->H == 512 && vpad <= 256 &&
+  const bool fused = d->bf16w && (n_active > 1 || fused_m1) && n_active <= DS_STEP_MAX_ROWS && step_shape(d) && vpad <= 256 &&
                      vpad <= d->head.Npad && d->head_frag && !ETD_XENV("ETD_NO_FUSED_STEP");
   d->last_step_fused = fused;
   d->stamp_on = d->stamp_armed && d->stamp_skip <= 0;          // (a whole call is stamped or not: the scheduler issues one bar's steps per call)
@@ -1055,21 +1071,9 @@ extern "C" int etd_decoder_step(etd_dec* d, const int32_t* slots, int n_active, 
     const DecRows rows{d->row_slot, d->row_pos, d->row_active};
     if (!fused) ETD_TRY(embed(s_));
     float* hf = nullptr;
-    ETD_TRY(forward_body(d, n_active, rows, &hf, s_, nullptr, fused, nullptr, nullptr, fused));
+    ETD_TRY(fused ? forward_skinny16(d, n_active, rows, true, s_, &hf) : forward_rows(d, n_active, rows, nullptr, nullptr, s_, &hf, nullptr));
     if (fused) {
-      const Layer& w0 = d->layers[0];
-      DHeadArgs hd = {};
-      hd.hfin = hf; hd.M = n_active; hd.H = d->H; hd.V = d->V; hd.Vpad = vpad;
-      hd.lnf_g = d->lnfg; hd.lnf_b = d->lnfb; hd.eps = d->cfg.layer_norm_eps; hd.Whead = (const d16*)d->head_frag;
-      hd.row_slot = d->row_slot; hd.row_pos = d->row_pos; hd.row_active = d->row_active; hd.row_sp = d->row_sp;
-      hd.cur_tok = d->cur_tok; hd.len = d->len; hd.done = d->done; hd.n_out = d->n_out; hd.out_tok = d->out_tok; hd.out_cap = d->out_cap;
-      hd.eos = d->eos; hd.limit = d->limit; hd.tgt_attrs = d->tgt_attrs; hd.tgt_proj = d->tgt_proj; hd.tgt_cls = 2; hd.n_bins = d->cfg.num_attribute_bins;
-      hd.word = d->word; hd.cls_emb = d->cls_emb; hd.attr_tab = d->attr_tab;
-      hd.g1 = w0.ln1g; hd.b1 = w0.ln1b; hd.g2 = w0.ln2g; hd.b2 = w0.ln2b;
-      hd.h = d->h; hd.x1 = d->X1b; hd.x2 = d->X2b;
-      hd.samp = d->samp_dev; hd.rng_key = d->rng_key;             // the device-side config selects greedy / sampling
-      hd.logits_dbg = d->logits_dbg_on ? d->logits_dbg : nullptr;
-      ETD_TRY(launch_dstep_head(hd, s_));
+      ETD_TRY(launch_dstep_head(head_args(d, hf, n_active, vpad), s_));
       if (d->trace) {
         ETD_TRY(trace_rows(d, d->h, d->H, d->H, 1, 0, n_active, ETD_TRACE_LAYER * d->L * n_active, s_));
         ETD_TRY(trace_rows(d, d->cur_tok, 1, 1, 1, 0, n_active, ETD_TRACE_LAYER * d->L * n_active + n_active, s_));
@@ -1078,11 +1082,7 @@ extern "C" int etd_decoder_step(etd_dec* d, const int32_t* slots, int n_active, 
       return ETD_OK;
     }
     ETD_TRY(head_logits(d, hf, n_active, d->logits, s_));
-    DArgmaxArgs am = {};
-    am.logits = d->logits; am.ldl = d->V; am.V = d->V; am.M = n_active;
-    am.rows = rows;
-    am.cur_tok = d->cur_tok; am.len = d->len; am.done = d->done; am.n_out = d->n_out; am.out_tok = d->out_tok; am.out_cap = d->out_cap;
-    am.eos = d->eos; am.limit = d->limit;
+    DArgmaxArgs am = argmax_args(d, rows, n_active);
     am.samp = d->samp_dev; am.rng_key = d->rng_key;
     ETD_TRY(launch_dargmax(am, s_));
     return ETD_OK;
@@ -1090,8 +1090,7 @@ extern "C" int etd_decoder_step(etd_dec* d, const int32_t* slots, int n_active, 
   if (fused) {
     // rows, embeddings and first-layer LayerNorms of the FIRST step of this call (every later step gets them from the head kernel)
     ETD_TRY(embed(st));
-    const Layer& w0 = d->layers[0];
-    ETD_TRY(launch_ln_rows(d->h, n_active, d->H, w0.ln1g, w0.ln1b, w0.ln2g, w0.ln2b, d->cfg.layer_norm_eps, d->X1b, d->X2b, st));
+    ETD_TRY(ln_rows16(d, 0, d->h, n_active, st));
   }
   // The step is ~50 short dependent kernels: replay it as a hipGraph (captured once per n_active; every
   // kernel argument is a fixed workspace/state pointer, the slot list lives in device memory).  Capture needs
