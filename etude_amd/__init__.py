@@ -7,7 +7,9 @@ Drop-in surfaces (same names/signatures as the reference):
     etude_amd.Vocab / Event         <- etude.data.vocab
     etude_amd.HFT_Transformer       <- etude.models.hft_transformer.HFT_Transformer (prepare.py's transcriber)
     etude_amd.TinyREMITokenizer     <- etude.data.tokenizer.TinyREMITokenizer (native encode / split / decode_to_notes)
-    etude_amd.BeatDetector          <- etude.data.beat_detector.BeatDetector (the Beat-Transformer model; madmom's DBN stays the caller's)
+    etude_amd.BeatDetector          <- etude.data.beat_detector.BeatDetector (the Beat-Transformer model; tracker="native" decodes with the library's own DBN)
+    etude_amd.DBNBeatTracker / DBNDownBeatTracker  <- madmom's DBNBeatTrackingProcessor / DBNDownBeatTrackingProcessor (csrc/dbn.hip)
+    etude_amd.BeatAnalyzer          <- etude.data.beat_analyzer.BeatAnalyzer (beat_pred.json -> tempo.json; host Python)
 All arithmetic runs in libetude_hip.so (hand-written HIP, see csrc/); importing the heavy
 modules is lazy so that `import etude_amd` works on a box without a GPU.
 """
@@ -21,7 +23,7 @@ _os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 __all__ = ["AMTAPC_Extractor", "EtudeDecoder", "EtudeDecoderConfig", "load_etude_decoder", "Vocab", "Event",
            "ExtractorConfig", "DecoderConfig", "HFT_Transformer", "HFTConfig", "TinyREMITokenizer", "run_engines",
-           "BeatDetector", "BeatDetectorConfig", "BeatDetectorModelConfig"]
+           "BeatDetector", "BeatDetectorConfig", "BeatDetectorModelConfig", "DBNBeatTracker", "DBNDownBeatTracker", "BeatAnalyzer", "structuralize_many"]
 
 
 def __getattr__(name):
@@ -43,6 +45,12 @@ def __getattr__(name):
     if name == "BeatDetector":
         from .beat import BeatDetector
         return BeatDetector
+    if name in ("DBNBeatTracker", "DBNDownBeatTracker"):
+        from . import dbn
+        return getattr(dbn, name)
+    if name in ("BeatAnalyzer", "structuralize_many"):
+        from . import beat_analyzer
+        return getattr(beat_analyzer, name)
     if name in ("ExtractorConfig", "DecoderConfig", "HFTConfig", "BeatDetectorConfig", "BeatDetectorModelConfig"):
         from . import config
         return getattr(config, name)

@@ -50,6 +50,12 @@ class BeatCfg(_SizedCfg):
                                        "n_mels", "tempo_out", "max_rows")]
 
 
+class DbnCfg(_SizedCfg):
+    _fields_ = [("struct_bytes", C.c_int), ("fps", C.c_double), ("min_bpm", C.c_double), ("max_bpm", C.c_double), ("transition_lambda", C.c_double),
+                ("observation_lambda", C.c_double), ("threshold", C.c_double), ("correct", C.c_int), ("num_tempi", C.c_int), ("n_bars", C.c_int),
+                ("beats_per_bar", C.c_int * 8)]
+
+
 class G3Case(_SizedCfg):
     """etd_debug_g3_case of include/etude_hip_debug.h: one k_gemm3 / k_gemm3_s launch with any epilogue, strides and row metadata"""
     _fields_ = [("struct_bytes", C.c_int), ("kernel", C.c_int), ("epi", C.c_int)] + [(n, C.c_int) for n in ("M", "N", "K", "ldx", "ldy")] + \
@@ -199,6 +205,13 @@ SIGNATURES = {
     "etd_beat_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_i64_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "etd_beat_flops": (C.c_double, [C.c_void_p, C.c_longlong]),
     "etd_beat_debug_taps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "etd_dbn_describe": (C.c_int, [C.POINTER(DbnCfg), C.c_int, C.c_void_p, C.c_int, c_int_p, c_int_p, c_int_p, C.c_void_p, C.c_void_p]),
+    "etd_dbn_workspace_bytes": (C.c_longlong, [C.POINTER(DbnCfg), C.c_longlong, C.c_int]),
+    "etd_dbn_create": (C.c_int, [C.POINTER(DbnCfg), C.POINTER(C.c_void_p)]),
+    "etd_dbn_destroy": (None, [C.c_void_p]),
+    "etd_dbn_track": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, c_i64_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
+                                C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong), C.c_void_p]),
+    "etd_dbn_debug_viterbi": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.POINTER(C.c_double)]),
     "etd_debug_decoder_trace_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.POINTER(C.c_int), C.c_void_p]),
 }
 

@@ -1,8 +1,10 @@
 """Beat-Transformer beat / downbeat activations on the MI355X: ``BeatDetector`` <- etude.data.beat_detector.BeatDetector.
 
 ``BeatDetector(config, model_path, device).detect(input_npy_path, output_json_path, cleanup_input)`` (etude/data/beat_detector.py:99-164): the model
-(Demixed_DilatedTransformerModel, etude/models/beat_transformer.py) runs in libetude_hip.so (csrc/beat.hip, exact-parity fp32-grade arithmetic); madmom's DBN
-trackers that turn the activations into beat times are the caller's and are imported lazily by ``detect``.
+(Demixed_DilatedTransformerModel, etude/models/beat_transformer.py) runs in libetude_hip.so (csrc/beat.hip, exact-parity fp32-grade arithmetic).  The DBN trackers
+that turn the activations into beat times are, by default (``tracker="madmom"``), madmom's, imported lazily by ``detect``; ``tracker="native"`` uses the library's
+own (csrc/dbn.hip, etude_amd/dbn.py) on the logits where they lie on the device, and ``detect_many`` (native only) does so for many songs in one ragged model pass
+plus one tracking call.
 
 Other entry points: ``activations(features)`` -> (beat, downbeat) float32 arrays (what the reference hands to madmom), ``activations_many([features, ...])`` (one
 ragged pass for many songs: prepare.py's use), ``forward(x [B][instr][T][128])`` -> (logits [B][T][ntoken], tempo [B][300]).
@@ -79,8 +81,12 @@ def check_state_dict(sd: Dict, cfg) -> None:
 
 class BeatDetector:
     def __init__(self, config: Optional[BeatDetectorConfig] = None, model_path: Union[str, Path, None] = None, device: Union[str, torch.device] = "auto",
-                 state_dict: Optional[Dict] = None, max_rows: int = 1 << 17):
+                 state_dict: Optional[Dict] = None, max_rows: int = 1 << 17, tracker: str = "madmom"):
         self.config = config if config is not None else BeatDetectorConfig()
+        if tracker not in ("madmom", "native"):
+            raise ValueError(f"BeatDetector: tracker must be 'madmom' or 'native', got {tracker!r}")
+        self.tracker = tracker
+        self._dbn = None
         if device == "auto":
             device = "cuda"
         self.device = torch.device(device)
@@ -180,7 +186,62 @@ class BeatDetector:
         down = DBNDownBeatTrackingProcessor(beats_per_bar=c.beats_per_bar, min_bpm=c.min_bpm, max_bpm=c.max_bpm, fps=self.fps, threshold=c.threshold)
         return beat, down
 
+    def _native(self):
+        """the library's DBN trackers for this config (beat HMM + one bar HMM per beats_per_bar entry), created on first use"""
+        if self._dbn is None:
+            from .dbn import DBNEngine
+            c = self.config
+            self._dbn = DBNEngine(self.fps, c.min_bpm, c.max_bpm, c.threshold, list(c.beats_per_bar), self.device)
+        return self._dbn
+
+    def _detect_native(self, songs: Sequence) -> List[Dict]:
+        """one ragged model pass + one tracking call; the activations never leave the device"""
+        from .dbn import IN_ACTIVATIONS
+        dbn = self._native()
+        feat, Ts = self._songs_to_device(songs)
+        logits, _ = self._run(feat, Ts, want_tempo=False)
+        act = torch.sigmoid(logits[:, :2]).contiguous()          # the same fp32 sigmoid activations() returns
+        out = []
+        for beats, rows, _ in dbn.track(act, Ts, IN_ACTIVATIONS):
+            down = rows[rows[:, 1] == 1][:, 0]
+            out.append({"beat_pred": (beats.astype(np.float64) / self.fps).tolist(), "downbeat_pred": (down.astype(np.float64) / self.fps).tolist()})
+        return out
+
+    @staticmethod
+    def _write_json(results: Dict, output_json_path) -> None:
+        output_file = Path(output_json_path)
+        output_file.parent.mkdir(parents=True, exist_ok=True)
+        with open(output_file, "w") as f:
+            json.dump(results, f, indent=4)
+
+    def detect_many(self, features_or_paths: Sequence, output_json_paths: Optional[Sequence] = None, cleanup_input: bool = False) -> List[Dict]:
+        """``detect`` for many songs with the native trackers: entries are [instr][T][128] feature arrays or paths of .npy files holding them; ``output_json_paths``
+        (one per song, entries may be None) are written like ``detect`` writes its own; ``cleanup_input`` unlinks the entries that were paths."""
+        if output_json_paths is not None and len(output_json_paths) != len(features_or_paths):
+            raise ValueError("detect_many: one output path per song")
+        if len(features_or_paths) == 0:
+            return []
+        paths = [Path(f) if isinstance(f, (str, Path)) else None for f in features_or_paths]
+        songs = [np.load(p) if p is not None else f for p, f in zip(paths, features_or_paths)]
+        results = self._detect_native(songs)
+        for i, r in enumerate(results):
+            if output_json_paths is not None and output_json_paths[i]:
+                self._write_json(r, output_json_paths[i])
+        if cleanup_input:
+            for p in paths:
+                if p is not None and p.exists():
+                    p.unlink()
+        return results
+
     def detect(self, input_npy_path: Union[str, Path], output_json_path: Optional[Union[str, Path]] = None, cleanup_input: bool = True) -> Dict:
+        if self.tracker == "native":
+            input_file = Path(input_npy_path)
+            results = self._detect_native([np.load(input_file)])[0]
+            if output_json_path:
+                self._write_json(results, output_json_path)
+            if cleanup_input and input_file.exists():
+                input_file.unlink()
+            return results
         beat_tracker, downbeat_tracker = self._trackers()          # (before any GPU work: a missing madmom fails here)
         input_file = Path(input_npy_path)
         features = np.load(input_file)

@@ -4,8 +4,9 @@ What ``InferencePipeline.run`` does for one song and one attribute tuple (/root/
 
     stage 1  extractor.extract(origin.wav -> extract.json)                      infer.py:82-97
              analyze_volume(origin.wav -> volume.json)                           infer.py:99-104
-    stage 2  beat detection -> tempo.json   (not run here: the caller supplies tempo.json.  The Beat-Transformer model itself now exists as
-             etude_amd.BeatDetector; source separation and madmom's DBN stay outside the library)
+    stage 2  beat detection -> tempo.json   (by default the caller supplies tempo.json.  With ``features=`` -- the clips' separated-stem mel-dB features -- and a
+             ``beat_detector`` the stage runs here: BeatDetector.detect_many (Beat-Transformer + the native DBN trackers) -> BeatAnalyzer, one tempo per clip;
+             source separation and the features themselves stay outside the library)
     stage 3  TinyREMITokenizer(tempo.json).encode(extract.json) -> vocab.encode_sequence -> split_sequence_into_bars
              -> model.generate(bars, attributes) -> tokenizer.decode_to_notes(events, volume.json) -> note_to_midi   infer.py:180-207
 
@@ -62,7 +63,8 @@ class ClipBatchPipeline:
     by the clips (list of regions) or one per clip."""
 
     def __init__(self, extractors, decoders, vocab, tempo, attrs: Sequence[Dict[str, int]], sample_rate: int = 44100,
-                 force_bar_tokens: int = 0, temperature: float = 0.0, post_workers: int = 8, **generate_kwargs):
+                 force_bar_tokens: int = 0, temperature: float = 0.0, post_workers: int = 8, beat_detector=None, **generate_kwargs):
+        self.beat_detector = beat_detector      # BeatDetector(tracker="native"): only used when run() / extract_stage() get `features`
         self.exs = list(extractors)
         self.decs = list(decoders)
         self.vocab = vocab
@@ -97,7 +99,18 @@ class ClipBatchPipeline:
         bi, bo = tk.split_ids_into_packed_bars(ids, self.bos, self.eos)         # split_sequence_into_bars
         return ClipConditions(notes, volume, PackedBars(bi, bo), tk)
 
-    def extract_stage(self, wavs: Sequence[torch.Tensor]) -> List[ClipConditions]:
+    def structuralize(self, features: Sequence) -> None:
+        """stage 2 from the clips' [instr][T][128] features: replaces the supplied tempo by one tempo.json content per clip"""
+        if self.beat_detector is None:
+            raise ValueError("features= needs a beat_detector (etude_amd.BeatDetector(tracker='native'))")
+        from .beat_analyzer import structuralize_many
+        self.tempo = [list(t) for t in structuralize_many(self.beat_detector, features)]
+
+    def extract_stage(self, wavs: Sequence[torch.Tensor], features: Optional[Sequence] = None) -> List[ClipConditions]:
+        if features is not None:
+            if len(features) != len(wavs):
+                raise ValueError("features: one entry per clip")
+            self.structuralize(features)
         out: List[Optional[ClipConditions]] = [None] * len(wavs)
         errs: list = []
         n = len(self.exs)
@@ -153,9 +166,9 @@ class ClipBatchPipeline:
         with ThreadPoolExecutor(self.post_workers) as pool:
             return list(pool.map(one, range(len(results))))
 
-    def run(self, wavs: Sequence[torch.Tensor]) -> dict:
+    def run(self, wavs: Sequence[torch.Tensor], features: Optional[Sequence] = None) -> dict:
         t0 = time.perf_counter()
-        conds = self.extract_stage(wavs)
+        conds = self.extract_stage(wavs, features)
         t1 = time.perf_counter()
         results, stats = self.decode_stage(conds)
         torch.cuda.synchronize(self.dev)

@@ -398,3 +398,34 @@ def beat_features(seed: int, T: int, instr: int = 5, n_mels: int = 128) -> np.nd
         x = -60.0 + 55.0 * env * (0.3 + 0.7 * shape) + 6.0 * rng.standard_normal((1, T, n_mels))
         out[i] = np.clip(x, -80.0, 0.0)[0]
     return out
+
+
+def beat_activations(seed: int, T: int, bpm_segments=((None, 120.0),), beats_per_bar: int = 4, jitter: float = 0.0, noise=(0.01, 0.1),
+                     fps: float = 44100 / 1024, start: float = 0.5):
+    """Planted pulse trains for the DBN tracker tests -> (act [T][2] float32 of (beat, downbeat) activations, planted [n][2] int64 of (frame, beat number)).
+
+    ``bpm_segments``: (seconds or None = to the end, bpm) pieces played one after the other from ``start`` seconds; ``jitter``: standard deviation in seconds of each
+    beat's displacement.  The beat column peaks (0.8-0.95, 35 % of it on either neighbour) at every beat, the downbeat column at bar starts (90 % of the beat's peak,
+    so that beat - downbeat stays positive); the floors are uniform in ``noise`` (beat) and 0.3 x ``noise`` (downbeat)."""
+    rng = np.random.default_rng(seed)
+    beat = rng.uniform(noise[0], noise[1], T)
+    down = 0.3 * rng.uniform(noise[0], noise[1], T)
+    times, t, end = [], float(start), T / fps
+    for secs, bpm in bpm_segments:
+        stop = end if secs is None else min(end, t + secs)
+        while t < stop:
+            times.append(t)
+            t += 60.0 / bpm
+    planted, prev = [], -3
+    for n, tt in enumerate(times):
+        f = int(round((tt + (rng.normal(0.0, jitter) if jitter else 0.0)) * fps))
+        if f < 1 or f > T - 2 or f - prev < 4:
+            continue
+        prev = f
+        p = rng.uniform(0.8, 0.95)
+        beat[f - 1:f + 2] = np.array([0.35, 1.0, 0.35]) * p
+        number = n % beats_per_bar + 1
+        if number == 1:
+            down[f - 1:f + 2] = np.array([0.35, 1.0, 0.35]) * p * 0.9
+        planted.append((f, number))
+    return np.stack([beat, down], axis=1).astype(np.float32), np.array(planted, np.int64).reshape(-1, 2)

@@ -339,6 +339,46 @@ int etd_beat_forward(etd_beat*, const float* feat_dev, int n_seq, const int64_t*
 /* algorithmic FLOPs of one song of T frames (the reference's full convolutions; formula in DESIGN.md) */
 double etd_beat_flops(etd_beat*, long long T);
 
+/* ------------------------------------------------------------------ DBN beat / downbeat tracking (activations -> beat frames; fp64 log-space Viterbi on the device)
+ * What BeatDetector.detect does with the activations (etude/data/beat_detector.py:133-150): madmom 0.16's DBNBeatTrackingProcessor and DBNDownBeatTrackingProcessor,
+ * restated from their published description (DESIGN.md 4c is the contract; parity with madmom itself is unpinned).  HMM 0 is the beat HMM, HMM 1 + i the bar HMM of
+ * beats_per_bar[i] beats.  Not implemented: online mode, correct = 0, per-beat transition_lambda lists. */
+typedef struct etd_dbn etd_dbn;
+typedef struct {
+  int struct_bytes;       /* sizeof(etd_dbn_cfg) of the caller: a mismatch is ETD_EINVAL */
+  double fps, min_bpm, max_bpm;
+  double transition_lambda;   /* 100 */
+  double observation_lambda;  /* 16; must be > 1 */
+  double threshold;           /* activations below it are trimmed from both ends (compared in fp32); 0 = no trimming */
+  int correct;                /* 1: a beat sits on the strongest frame of its beat-state run (the only mode) */
+  int num_tempi;              /* 0 = every integer interval; else that many log-spaced ones */
+  int n_bars;                 /* bar HMMs: entries of beats_per_bar in use, 0..8 */
+  int beats_per_bar[8];       /* each 1..8 */
+} etd_dbn_cfg;
+/* HOST ONLY (no GPU): the state space of one HMM.  intervals_out [cap] (may be NULL), *n_intervals, *n_states, *num_beats; optional logtrans_out [n][n]
+ * (from-major: log probability of last state of interval `from` -> first state of interval `to` of the next beat, -inf = no edge) and pointers_out [n_states]
+ * (density index per state).  ETD_EINVAL for a bad config: min_bpm >= max_bpm, non-positive fps, beats_per_bar outside 1..8, observation_lambda <= 1.  Any size is described;
+ * etd_dbn_create and etd_dbn_workspace_bytes also refuse (ETD_EINVAL, the message names the count) more than 255 intervals or an HMM of more than 8 192 states. */
+int etd_dbn_describe(const etd_dbn_cfg* cfg, int hmm_index, int32_t* intervals_out, int cap, int* n_intervals, int* n_states, int* num_beats,
+                     double* logtrans_out, uint8_t* pointers_out);
+/* HOST ONLY: device workspace bytes one song of T frames needs for HMM hmm_index (-1: all HMMs of the config).  Backpointers are kept for first states only,
+ * [T][num_beats * n_intervals] bytes: there is no [T][n_states] array.  Negative (ETD_EINVAL) for a bad config. */
+long long etd_dbn_workspace_bytes(const etd_dbn_cfg* cfg, long long T, int hmm_index);
+int etd_dbn_create(const etd_dbn_cfg* cfg, etd_dbn** out);
+void etd_dbn_destroy(etd_dbn*);
+/* in_dev: [sum T_s][2] fp32 device, the n_seq songs back to back; input_kind says what the two columns are: the (beat, downbeat) activations, the logits
+ * etd_beat_forward writes (sigmoid applied inside, fp32) -- in both cases the downbeat tracker sees (max(beat - downbeat, 0), downbeat), as detect() builds it --
+ * or that combined pair itself, as madmom's DBNDownBeatTrackingProcessor takes it (the beat tracker then sees column 0).
+ * Results on the host, song after song: beat_frames[beat_offsets[s] .. beat_offsets[s + 1]) = the beat tracker's beat frames (time = frame / fps);
+ * down_frames / down_numbers [down_offsets[s] ..) = the downbeat tracker's (frame, beat number in the bar) rows of the most likely bar length, bar_choice[s]
+ * (may be NULL) = its index in beats_per_bar or -1 (no rows).  needed[0], needed[1] = total beats / rows: when beat_cap or down_cap is short the call fails with
+ * ETD_ENOMEM and the offsets and `needed` are valid (the contract of etd_mpe2note).  A song's result depends on that song alone.  Synchronous. */
+enum { ETD_DBN_IN_ACTIVATIONS = 0, ETD_DBN_IN_LOGITS = 1, ETD_DBN_IN_COMBINED = 2 };
+int etd_dbn_track(etd_dbn*, const float* in_dev, int input_kind, int n_seq, const int64_t* T_host,
+                  int32_t* beat_frames, long long beat_cap, int64_t* beat_offsets,
+                  int32_t* down_frames, int32_t* down_numbers, long long down_cap, int64_t* down_offsets,
+                  int32_t* bar_choice, long long* needed, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -112,6 +112,10 @@ int etd_debug_g3_bounds(const float* W, const float* c, int N, int K, const floa
  * global row order) to front_dev / layer0_dev (NULL = off). */
 int etd_beat_debug_taps(etd_beat*, float* front_dev, float* layer0_dev);
 
+/* test hook: the Viterbi kernel of etd_dbn_track alone, on supplied densities: densities_dev fp64 device [T][K] (K = 2 for HMM 0, 3 for a bar HMM; -inf allowed)
+ * -> path_out host int32 [T] (state per frame) and *logprob_out (host).  Synchronous, default stream. */
+int etd_dbn_debug_viterbi(etd_dbn*, int hmm_index, const double* densities_dev, long long T, int32_t* path_out, double* logprob_out);
+
 #ifdef __cplusplus
 }
 #endif
