@@ -56,6 +56,10 @@ class DbnCfg(_SizedCfg):
                 ("beats_per_bar", C.c_int * 8)]
 
 
+class StemFeatCfg(_SizedCfg):
+    _fields_ = [("struct_bytes", C.c_int), ("n_fft", C.c_int), ("hop", C.c_int), ("n_mels", C.c_int), ("framing", C.c_int), ("amin", C.c_float), ("top_db", C.c_float)]
+
+
 class G3Case(_SizedCfg):
     """etd_debug_g3_case of include/etude_hip_debug.h: one k_gemm3 / k_gemm3_s launch with any epilogue, strides and row metadata"""
     _fields_ = [("struct_bytes", C.c_int), ("kernel", C.c_int), ("epi", C.c_int)] + [(n, C.c_int) for n in ("M", "N", "K", "ldx", "ldy")] + \
@@ -212,6 +216,11 @@ SIGNATURES = {
     "etd_dbn_track": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, c_i64_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
                                 C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong), C.c_void_p]),
     "etd_dbn_debug_viterbi": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.POINTER(C.c_double)]),
+    "etd_stemfeat_create": (C.c_int, [C.POINTER(StemFeatCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "etd_stemfeat_destroy": (None, [C.c_void_p]),
+    "etd_stemfeat_num_frames": (C.c_longlong, [C.c_void_p, C.c_longlong]),
+    "etd_stemfeat_workspace_bytes": (C.c_longlong, [C.c_void_p, C.c_int, C.c_int, c_i64_p]),
+    "etd_stemfeat_run": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, c_i64_p, C.c_void_p, C.c_void_p]),
     "etd_debug_decoder_trace_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.POINTER(C.c_int), C.c_void_p]),
 }
 

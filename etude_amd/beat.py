@@ -4,7 +4,8 @@
 (Demixed_DilatedTransformerModel, etude/models/beat_transformer.py) runs in libetude_hip.so (csrc/beat.hip, exact-parity fp32-grade arithmetic).  The DBN trackers
 that turn the activations into beat times are, by default (``tracker="madmom"``), madmom's, imported lazily by ``detect``; ``tracker="native"`` uses the library's
 own (csrc/dbn.hip, etude_amd/dbn.py) on the logits where they lie on the device, and ``detect_many`` (native only) does so for many songs in one ragged model pass
-plus one tracking call.
+plus one tracking call.  ``detect_stems_many`` / ``activations_from_stems_many`` start one step earlier, from the separated stems: ``etude_amd.StemFeatures`` makes the
+features on the device and they go straight into the model.
 
 Other entry points: ``activations(features)`` -> (beat, downbeat) float32 arrays (what the reference hands to madmom), ``activations_many([features, ...])`` (one
 ragged pass for many songs: prepare.py's use), ``forward(x [B][instr][T][128])`` -> (logits [B][T][ntoken], tempo [B][300]).
@@ -196,9 +197,14 @@ class BeatDetector:
 
     def _detect_native(self, songs: Sequence) -> List[Dict]:
         """one ragged model pass + one tracking call; the activations never leave the device"""
+        self._native()
+        feat, Ts = self._songs_to_device(songs)
+        return self._detect_packed(feat, Ts)
+
+    def _detect_packed(self, feat: torch.Tensor, Ts: Sequence[int]) -> List[Dict]:
+        """the same from features already packed on the device (``_run``'s layout), range-checked by the caller"""
         from .dbn import IN_ACTIVATIONS
         dbn = self._native()
-        feat, Ts = self._songs_to_device(songs)
         logits, _ = self._run(feat, Ts, want_tempo=False)
         act = torch.sigmoid(logits[:, :2]).contiguous()          # the same fp32 sigmoid activations() returns
         out = []
@@ -231,6 +237,58 @@ class BeatDetector:
             for p in paths:
                 if p is not None and p.exists():
                     p.unlink()
+        return results
+
+    # ------------------------------------------------------------------ from separated stems (etude_amd.StemFeatures: the features are made on the device)
+    def _stem_features(self, stem_features=None):
+        if stem_features is None:
+            if getattr(self, "_stemfeat", None) is None:
+                from .stemfeat import StemFeatures
+                self._stemfeat = StemFeatures(device=self.device)
+            stem_features = self._stemfeat
+        if stem_features.n_mels != 128:
+            raise ValueError(f"stem_features: the model reads 128 mel bands, this StemFeatures makes {stem_features.n_mels}")
+        return stem_features
+
+    def _features_from_stems(self, stems_list: Sequence, stem_features=None) -> Tuple[torch.Tensor, List[int]]:
+        """stems -> the packed device feature buffer ``_run`` reads: written once by the feature kernels, checked where it lies (a NaN or Inf sample, or a
+        StemFeatures with top_db > 80, is refused here, before the model launches), never copied or concatenated"""
+        sf = self._stem_features(stem_features)
+        for i, x in enumerate(stems_list):
+            if hasattr(x, "shape") and len(x.shape) == 3 and x.shape[0] != self.instr:
+                raise ValueError(f"song {i}: stems must be [instr={self.instr}][channels][N], got {tuple(x.shape)}")
+        feat, Ts = sf.features_many(stems_list)
+        if feat.device != self.device:
+            raise ValueError(f"stem_features works on {feat.device}, the detector on {self.device}")
+        _check_range(feat, "stem features")
+        return feat, Ts
+
+    def activations_from_stems_many(self, stems_list: Sequence, stem_features=None) -> List[Tuple[np.ndarray, np.ndarray]]:
+        """``activations_many`` from the songs' separated stems [instr][channels][N_s] (device or host tensors, numpy arrays)"""
+        if len(stems_list) == 0:
+            return []
+        feat, Ts = self._features_from_stems(stems_list, stem_features)
+        logits, _ = self._run(feat, Ts, want_tempo=False)
+        act = torch.sigmoid(logits).cpu().numpy()
+        out, o = [], 0
+        for T in Ts:
+            out.append((np.ascontiguousarray(act[o:o + T, 0]), np.ascontiguousarray(act[o:o + T, 1])))
+            o += T
+        return out
+
+    def detect_stems_many(self, stems_list: Sequence, output_json_paths: Optional[Sequence] = None, stem_features=None) -> List[Dict]:
+        """``detect_many`` from the songs' separated stems: features (``stem_features``, default ``StemFeatures()`` = the Demucs branch of run_separation.py), model and
+        the native trackers in one pass each, with nothing but the beat frames coming back from the device"""
+        if output_json_paths is not None and len(output_json_paths) != len(stems_list):
+            raise ValueError("detect_stems_many: one output path per song")
+        if len(stems_list) == 0:
+            return []
+        self._native()
+        feat, Ts = self._features_from_stems(stems_list, stem_features)
+        results = self._detect_packed(feat, Ts)
+        for i, r in enumerate(results):
+            if output_json_paths is not None and output_json_paths[i]:
+                self._write_json(r, output_json_paths[i])
         return results
 
     def detect(self, input_npy_path: Union[str, Path], output_json_path: Optional[Union[str, Path]] = None, cleanup_input: bool = True) -> Dict:

@@ -1,4 +1,5 @@
-"""beat_pred.json -> tempo.json: ``BeatAnalyzer`` <- etude.data.beat_analyzer.BeatAnalyzer, and ``structuralize_many`` (detect_many + analyze_data).
+"""beat_pred.json -> tempo.json: ``BeatAnalyzer`` <- etude.data.beat_analyzer.BeatAnalyzer, ``structuralize_many`` (detect_many + analyze_data) and
+``structuralize_stems_many`` (the same from separated stems).
 
 Host Python with no hot path (a few hundred beats per song).  The behaviour is the reference class's, restated: the same float operations in the same order (numpy's
 diff / mean / std on the same lists), so that the regions agree to the last bit (tests/test_beat_analyzer_cpu.py against the reference's own output).  The steps,
@@ -158,3 +159,8 @@ class BeatAnalyzer:
 def structuralize_many(detector, features_list: Sequence) -> List[List[Dict]]:
     """stage 2 of infer.py for many songs: ``detector.detect_many`` (native trackers) then ``BeatAnalyzer.analyze_data`` -> one tempo.json content per song"""
     return [BeatAnalyzer().analyze_data(r) for r in detector.detect_many(features_list)]
+
+
+def structuralize_stems_many(detector, stems_list: Sequence, stem_features=None) -> List[List[Dict]]:
+    """the same from the songs' separated stems [instr][channels][N]: ``detector.detect_stems_many`` (features, model and trackers on the device) then ``analyze_data``"""
+    return [BeatAnalyzer().analyze_data(r) for r in detector.detect_stems_many(stems_list, stem_features=stem_features)]

@@ -1,0 +1,386 @@
+// Stem mel-dB features on the GPU: separated stems [instr][channels][N] -> [instr][T][n_mels] dB features, the input of etd_beat_forward (DESIGN.md 4d is the
+// contract).  Replaces the host step of scripts/run_separation.py:124-141, 163-183 (channel mean, librosa.stft, |X|^2, Slaney mel, power_to_db(ref=np.max)).
+//
+// A ragged batch of songs runs in three launches, whatever the number of songs and stems:
+//   k_sf_frames  one workgroup per SF_FRAMES consecutive frames of one (song, stem): channel mean -> window -> real FFT in LDS -> power -> CSR mel; writes the mel
+//                POWER into the output buffer and the workgroup's maximum into a side array
+//   k_sf_max     one workgroup per (song, stem): the maximum of its workgroups' maxima (exact in any order)
+//   k_sf_db      in place: 10 log10(max(amin, S)) - 10 log10(max(amin, ref)), clamped at -top_db
+// Everything but the maximum is computed per frame from that stem's samples in a fixed order, so a stem's features are bit-identical alone and in any batch.
+//
+// The FFT: a real frame of n_fft samples is the complex sequence z[i] = x[2i] + i x[2i + 1] of M = n_fft / 2 points; one Stockham (self-sorting, out-of-place
+// between two LDS buffers) FFT of M points -- a radix-2 stage first when log2 M is odd (its twiddles are all 1), then radix-4 stages -- and a split pass
+// X[k] = E[k] + W^k O[k] give the n_fft / 2 + 1 bins.  n_fft = 4096: 6 passes and barriers where the radix-2 complex FFT of the full frame takes 12.
+// Twiddles come from tables built in fp64 on the host (every power is looked up, none is formed by multiplication on the device).
+#include "stemfeat.h"
+#include "prof.h"
+
+#include <cmath>
+
+namespace {
+
+struct SfArgs {
+  const SfSong* tab; int n_songs, instr, channels;
+  int n_fft, lgM, hop, lead, reflect;
+  const float* window; const float2* twM; const float2* twS;
+  const int* mel_start; const int* mel_len; const int* mel_off; const float* mel_w; int n_mels;
+  float* feat; float* wgmax;
+};
+
+// the song whose workgroup range holds b (blk0 ascending; b < total)
+__device__ __forceinline__ int sf_song_of(const SfSong* tab, int n_songs, long long b) {
+  int lo = 0, hi = n_songs - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (tab[mid].blk0 <= b) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// (xr + i xi)(wr + i wi) as four multiplies, a subtraction and an addition of their own (the roundings of the plain expression under -ffp-contract=off).  Left to the
+// SLP vectoriser the products are paired crosswise into v_pk_mul_f32 ... op_sel:[0,1], the packed form kept out of this library (tests/test_isa_guard.py).
+__device__ __forceinline__ void sf_cmul(float xr, float xi, float wr, float wi, float& yr, float& yi) {
+  float a, b, c, d;
+  asm volatile("v_mul_f32 %0, %1, %2" : "=v"(a) : "v"(xr), "v"(wr));
+  asm volatile("v_mul_f32 %0, %1, %2" : "=v"(b) : "v"(xi), "v"(wi));
+  asm volatile("v_mul_f32 %0, %1, %2" : "=v"(c) : "v"(xr), "v"(wi));
+  asm volatile("v_mul_f32 %0, %1, %2" : "=v"(d) : "v"(xi), "v"(wr));
+  yr = a - b;
+  yi = c + d;
+}
+
+__global__ __launch_bounds__(SF_THREADS) void k_sf_frames(const SfArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  __shared__ float red[SF_THREADS / 64];
+  const int M = a.n_fft >> 1, PM = SF_PAD(M) + 1, tid = threadIdx.x;
+  float *sr = sm, *si = sm + PM, *dr = sm + 2 * PM, *di = sm + 3 * PM;
+  float2* tw = (float2*)(sm + 4 * PM);                 // exp(-2 pi i n / M), n < M, at SF_PAD(n)
+  const long long b = blockIdx.x;
+  const int s = sf_song_of(a.tab, a.n_songs, b);
+  const SfSong sg = a.tab[s];
+  const long long local = b - sg.blk0;
+  const int stem = (int)(local / sg.cps);
+  const long long t0 = (local - (long long)stem * sg.cps) * SF_FRAMES;
+  const float* wav = sg.wav + (long long)stem * a.channels * sg.N;
+  float* out = a.feat + sg.feat_off + (long long)stem * sg.T * a.n_mels;
+  const float fch = (float)a.channels;
+  for (int n = tid; n < M; n += SF_THREADS) tw[SF_PAD(n)] = a.twM[n];
+  float mx = 0.f;                                      // (mel power is >= 0)
+  for (int f = 0; f < SF_FRAMES; ++f) {
+    const long long t = t0 + f;
+    if (t >= sg.T) break;                              // (uniform over the workgroup)
+    // ---- channel mean, window, even / odd samples -> real / imaginary part
+    for (int i = tid; i < a.n_fft; i += SF_THREADS) {
+      long long idx = t * a.hop - a.lead + i;
+      bool inside = idx >= 0 && idx < sg.N;
+      if (a.reflect) {                                 // (N > n_fft / 2 is checked on the host: one reflection lands inside)
+        if (idx < 0) idx = -idx;
+        if (idx >= sg.N) idx = 2 * (sg.N - 1) - idx;
+        inside = true;
+      }
+      float v = 0.f;
+      if (inside) {
+        v = wav[idx];
+        for (int c = 1; c < a.channels; ++c) v += wav[(long long)c * sg.N + idx];
+        v = (v / fch) * a.window[i];
+      }
+      ((i & 1) ? si : sr)[SF_PAD(i >> 1)] = v;
+    }
+    __syncthreads();
+    // ---- Stockham FFT of M complex points
+    int Ns = 1, lgNs = 0;
+    if (a.lgM & 1) {
+      for (int j = tid; j < (M >> 1); j += SF_THREADS) {
+        const int i0 = SF_PAD(j), i1 = SF_PAD(j + (M >> 1));
+        const float ar = sr[i0], ai = si[i0], br = sr[i1], bi = si[i1];
+        const int o0 = SF_PAD(2 * j), o1 = SF_PAD(2 * j + 1);
+        dr[o0] = ar + br; di[o0] = ai + bi;
+        dr[o1] = ar - br; di[o1] = ai - bi;
+      }
+      __syncthreads();
+      float* q = sr; sr = dr; dr = q; q = si; si = di; di = q;
+      Ns = 2; lgNs = 1;
+    }
+    const int Q = M >> 2;
+    for (; Ns < M; Ns <<= 2, lgNs += 2) {
+      const int st = M >> (lgNs + 2);                  // twiddle stride: w^r = exp(-2 pi i k r / (4 Ns)) = tw[k r st]
+      for (int j = tid; j < Q; j += SF_THREADS) {
+        const int k = j & (Ns - 1), j0 = ((j - k) << 2) + k;
+        const int i0 = SF_PAD(j), i1 = SF_PAD(j + Q), i2 = SF_PAD(j + 2 * Q), i3 = SF_PAD(j + 3 * Q);
+        const float2 w1 = tw[SF_PAD(k * st)], w2 = tw[SF_PAD(2 * k * st)], w3 = tw[SF_PAD(3 * k * st)];
+        const float v0r = sr[i0], v0i = si[i0];
+        float v1r, v1i, v2r, v2i, v3r, v3i;
+        sf_cmul(sr[i1], si[i1], w1.x, w1.y, v1r, v1i);
+        sf_cmul(sr[i2], si[i2], w2.x, w2.y, v2r, v2i);
+        sf_cmul(sr[i3], si[i3], w3.x, w3.y, v3r, v3i);
+        const float a0r = v0r + v2r, a0i = v0i + v2i, a1r = v0r - v2r, a1i = v0i - v2i;
+        const float a2r = v1r + v3r, a2i = v1i + v3i;
+        const float a3r = v1i - v3i, a3i = -(v1r - v3r);          // -i (v1 - v3)
+        const int o0 = SF_PAD(j0), o1 = SF_PAD(j0 + Ns), o2 = SF_PAD(j0 + 2 * Ns), o3 = SF_PAD(j0 + 3 * Ns);
+        dr[o0] = a0r + a2r; di[o0] = a0i + a2i;
+        dr[o1] = a1r + a3r; di[o1] = a1i + a3i;
+        dr[o2] = a0r - a2r; di[o2] = a0i - a2i;
+        dr[o3] = a1r - a3r; di[o3] = a1i - a3i;
+      }
+      __syncthreads();
+      float* q = sr; sr = dr; dr = q; q = si; si = di; di = q;
+    }
+    // ---- split pass: X[k] = E + W^k O, E = (Z[k] + conj Z[M - k]) / 2, O = -i (Z[k] - conj Z[M - k]) / 2, W = exp(-2 pi i / n_fft); power into the free buffer
+    float* pw = dr;                                    // [M + 1], unpadded
+    for (int k = tid; k <= M; k += SF_THREADS) {
+      const int ia = SF_PAD(k & (M - 1)), ib = SF_PAD((M - k) & (M - 1));
+      const float ar = sr[ia], ai = si[ia], br = sr[ib], bi = -si[ib];
+      const float er = 0.5f * (ar + br), ei = 0.5f * (ai + bi);
+      const float orr = 0.5f * (ai - bi), oi = -0.5f * (ar - br);
+      const float2 w = a.twS[k];
+      float pr, pi;
+      sf_cmul(orr, oi, w.x, w.y, pr, pi);
+      const float xr = er + pr, xi = ei + pi;
+      float p0, p1;
+      asm volatile("v_mul_f32 %0, %1, %1" : "=v"(p0) : "v"(xr));
+      asm volatile("v_mul_f32 %0, %1, %1" : "=v"(p1) : "v"(xi));
+      pw[k] = p0 + p1;
+    }
+    __syncthreads();
+    for (int m = tid; m < a.n_mels; m += SF_THREADS) {
+      const int s0 = a.mel_start[m], n = a.mel_len[m], o = a.mel_off[m];
+      float acc = 0.f;
+      for (int i = 0; i < n; ++i) acc = fmaf(pw[s0 + i], a.mel_w[o + i], acc);
+      out[t * a.n_mels + m] = acc;
+      mx = fmaxf(mx, acc);
+    }
+    __syncthreads();                                   // (the next frame's samples overwrite the buffers pw may live in)
+  }
+  mx = wave_max(mx);
+  if ((tid & 63) == 0) red[tid >> 6] = mx;
+  __syncthreads();
+  if (tid == 0) {
+    float v = red[0];
+    for (int w = 1; w < SF_THREADS / 64; ++w) v = fmaxf(v, red[w]);
+    a.wgmax[b] = v;
+  }
+}
+
+__global__ __launch_bounds__(SF_THREADS) void k_sf_max(const SfSong* __restrict__ tab, int instr, const float* __restrict__ wgmax, float* __restrict__ ref) {
+  __shared__ float red[SF_THREADS / 64];
+  const int s = blockIdx.x / instr, stem = blockIdx.x % instr, tid = threadIdx.x;
+  const long long n = tab[s].cps;
+  const float* p = wgmax + tab[s].blk0 + (long long)stem * n;
+  float mx = 0.f;
+  for (long long i = tid; i < n; i += SF_THREADS) mx = fmaxf(mx, p[i]);
+  mx = wave_max(mx);
+  if ((tid & 63) == 0) red[tid >> 6] = mx;
+  __syncthreads();
+  if (tid == 0) {
+    float v = red[0];
+    for (int w = 1; w < SF_THREADS / 64; ++w) v = fmaxf(v, red[w]);
+    ref[blockIdx.x] = v;
+  }
+}
+
+// y = 10 log10(max(amin, S)) - 10 log10(max(amin, ref)); the stem's largest S gives exactly 0 (the same expression on both sides), so max(y) = 0 and power_to_db's
+// second clamp max(y, max(y) - top_db) is max(y, -top_db).  A NaN or infinite S (a non-finite sample) stays NaN: fmaxf would drop it and hide it from the range check.
+__global__ __launch_bounds__(SF_THREADS) void k_sf_db(const SfSong* __restrict__ tab, int instr, int n_mels, const float* __restrict__ ref, float amin, float top_db,
+                                                       float* __restrict__ feat) {
+  const int s = blockIdx.y / instr, stem = blockIdx.y % instr;
+  const long long n = tab[s].T * n_mels;
+  float* p = feat + tab[s].feat_off + (long long)stem * n;
+  const float r = 10.f * log10f(fmaxf(amin, ref[blockIdx.y]));
+  for (long long i = (long long)blockIdx.x * SF_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * SF_THREADS) {
+    const float S = p[i];
+    float y = fmaxf(10.f * log10f(fmaxf(amin, S)) - r, -top_db);
+    if (!(S <= 3.402823466e+38f)) y = __builtin_nanf("");
+    p[i] = y;
+  }
+}
+
+bool finite_all(const float* p, size_t n) {
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(p[i])) return false;
+  return true;
+}
+
+}  // namespace
+
+struct etd_stemfeat {
+  etd_stemfeat_cfg cfg;
+  int M = 0, lgM = 0, lead = 0;
+  // host tables (create needs no GPU); uploaded by the first run
+  std::vector<float> window, mel_w;
+  std::vector<float2> twM, twS;
+  std::vector<int> mel_start, mel_len, mel_off;
+  bool on_dev = false;
+  DevPool pool;
+  float *d_window = nullptr, *d_mel_w = nullptr;
+  float2 *d_twM = nullptr, *d_twS = nullptr;
+  int *d_mel_start = nullptr, *d_mel_len = nullptr, *d_mel_off = nullptr;
+  // per-call workspace, grown on demand: per-workgroup maxima + per-(song, stem) maxima, and the song table
+  float* ws = nullptr; long long ws_floats = 0;
+  SfSong* tab = nullptr; int tab_cap = 0;
+};
+
+namespace {
+
+// fills tab (when not null) and the totals; ETD_EINVAL for a bad shape
+int sf_plan(const etd_stemfeat* h, int n_songs, int instr, const int64_t* N_host, std::vector<SfSong>* tab, long long* blocks, long long* frames, long long* maxT) {
+  if (!h || !N_host || n_songs < 1 || instr < 1) ETD_FAIL(ETD_EINVAL, "stemfeat: null argument, n_songs < 1 or instr < 1");
+  if ((long long)n_songs * instr > 65535) ETD_FAIL(ETD_EINVAL, "stemfeat: more than 65535 (song, stem) pairs in one call (%d x %d)", n_songs, instr);
+  long long b = 0, fr = 0, mt = 0;
+  for (int s = 0; s < n_songs; ++s) {
+    const long long N = N_host[s];
+    if (N < 1) ETD_FAIL(ETD_EINVAL, "stemfeat: song %d has N = %lld (need >= 1)", s, N);
+    if (N > (1LL << 40)) ETD_FAIL(ETD_EINVAL, "stemfeat: song %d has N = %lld (> 2^40)", s, N);
+    if (h->cfg.framing == ETD_STEMFEAT_LIBROSA_REFLECT && N <= h->cfg.n_fft / 2)
+      ETD_FAIL(ETD_EINVAL, "stemfeat: song %d has N = %lld <= n_fft / 2 = %d (reflect padding undefined)", s, N, h->cfg.n_fft / 2);
+    const long long T = 1 + (N + 2 * h->lead - h->cfg.n_fft) / h->cfg.hop;
+    const long long cps = (T + SF_FRAMES - 1) / SF_FRAMES;
+    if (tab) (*tab)[s] = SfSong{nullptr, N, T, fr * instr * h->cfg.n_mels, b, cps};
+    b += cps * instr; fr += T; mt = T > mt ? T : mt;
+    if (b > 0x7fffffffLL) ETD_FAIL(ETD_EINVAL, "stemfeat: more than 2^31 - 1 workgroups in one call");
+  }
+  *blocks = b; *frames = fr; *maxT = mt;
+  return ETD_OK;
+}
+
+int sf_upload(etd_stemfeat* h) {
+  if (h->on_dev) return ETD_OK;
+  DevPool& P = h->pool;
+  const size_t m0 = P.mark();
+  auto fail = [&](int rc) { P.free_from(m0); return rc; };
+  ETD_TRY_OR(fail, P.upload(&h->d_window, h->window.data(), h->window.size()));
+  ETD_TRY_OR(fail, P.upload(&h->d_twM, h->twM.data(), h->twM.size()));
+  ETD_TRY_OR(fail, P.upload(&h->d_twS, h->twS.data(), h->twS.size()));
+  ETD_TRY_OR(fail, P.upload(&h->d_mel_start, h->mel_start.data(), h->mel_start.size()));
+  ETD_TRY_OR(fail, P.upload(&h->d_mel_len, h->mel_len.data(), h->mel_len.size()));
+  ETD_TRY_OR(fail, P.upload(&h->d_mel_off, h->mel_off.data(), h->mel_off.size()));
+  ETD_TRY_OR(fail, P.upload(&h->d_mel_w, h->mel_w.data(), h->mel_w.size()));
+  h->on_dev = true;
+  return ETD_OK;
+}
+
+}  // namespace
+
+extern "C" int etd_stemfeat_create(const etd_stemfeat_cfg* cfg, const float* window_host, const int32_t* mel_start, const int32_t* mel_len,
+                                   const float* mel_w_host, etd_stemfeat** out) {
+  if (!cfg || !out) ETD_FAIL(ETD_EINVAL, "stemfeat_create: null argument");
+  if (cfg->struct_bytes != (int)sizeof(etd_stemfeat_cfg))
+    ETD_FAIL(ETD_EINVAL, "stemfeat_create: etd_stemfeat_cfg is %d bytes here, the caller's is %d -- caller built against another etude_hip.h", (int)sizeof(etd_stemfeat_cfg), cfg->struct_bytes);
+  const int n_fft = cfg->n_fft;
+  if (n_fft < 64 || n_fft > 4096 || (n_fft & (n_fft - 1))) ETD_FAIL(ETD_EINVAL, "stemfeat_create: n_fft = %d must be a power of two in 64 .. 4096", n_fft);
+  if (cfg->hop < 1 || cfg->hop > (1 << 20)) ETD_FAIL(ETD_EINVAL, "stemfeat_create: hop = %d must be in 1 .. 2^20", cfg->hop);
+  if (cfg->n_mels < 1 || cfg->n_mels > 1024) ETD_FAIL(ETD_EINVAL, "stemfeat_create: n_mels = %d must be in 1 .. 1024", cfg->n_mels);
+  if (cfg->framing != ETD_STEMFEAT_LIBROSA && cfg->framing != ETD_STEMFEAT_LIBROSA_REFLECT && cfg->framing != ETD_STEMFEAT_SPLEETER)
+    ETD_FAIL(ETD_EINVAL, "stemfeat_create: framing = %d is not one of ETD_STEMFEAT_*", cfg->framing);
+  if (!(cfg->amin > 0.f) || !std::isfinite(cfg->amin) || !(cfg->top_db > 0.f) || !std::isfinite(cfg->top_db))
+    ETD_FAIL(ETD_EINVAL, "stemfeat_create: amin and top_db must be positive and finite");
+  if (!window_host || !mel_start || !mel_len || !mel_w_host) ETD_FAIL(ETD_EINVAL, "stemfeat_create: null table");
+  if (!finite_all(window_host, (size_t)n_fft)) ETD_FAIL(ETD_EINVAL, "stemfeat_create: the window holds a non-finite value");
+  std::vector<int> off(cfg->n_mels);
+  long long tot = 0;
+  for (int m = 0; m < cfg->n_mels; ++m) {
+    if (mel_start[m] < 0 || mel_len[m] < 0 || (long long)mel_start[m] + mel_len[m] > n_fft / 2 + 1)
+      ETD_FAIL(ETD_EINVAL, "stemfeat_create: mel band %d covers bins [%d, %d + %d), outside 0 .. %d", m, mel_start[m], mel_start[m], mel_len[m], n_fft / 2);
+    off[m] = (int)tot; tot += mel_len[m];
+  }
+  if (!finite_all(mel_w_host, (size_t)tot)) ETD_FAIL(ETD_EINVAL, "stemfeat_create: the mel weights hold a non-finite value");
+  for (long long i = 0; i < tot; ++i)
+    if (mel_w_host[i] < 0.f) ETD_FAIL(ETD_EINVAL, "stemfeat_create: mel weight %lld is negative", i);
+  etd_stemfeat* h = new etd_stemfeat();
+  h->cfg = *cfg;
+  h->M = n_fft / 2;
+  while ((1 << h->lgM) < h->M) ++h->lgM;
+  h->lead = cfg->framing == ETD_STEMFEAT_SPLEETER ? n_fft : n_fft / 2;
+  h->window.assign(window_host, window_host + n_fft);
+  h->mel_start.assign(mel_start, mel_start + cfg->n_mels);
+  h->mel_len.assign(mel_len, mel_len + cfg->n_mels);
+  h->mel_off = off;
+  h->mel_w.assign(mel_w_host, mel_w_host + tot);
+  if (h->mel_w.empty()) h->mel_w.push_back(0.f);
+  const double pi = 3.14159265358979323846;
+  h->twM.resize(h->M);
+  for (int n = 0; n < h->M; ++n) h->twM[n] = make_float2((float)cos(-2.0 * pi * n / h->M), (float)sin(-2.0 * pi * n / h->M));
+  h->twS.resize(h->M + 1);
+  for (int k = 0; k <= h->M; ++k) h->twS[k] = make_float2((float)cos(-2.0 * pi * k / n_fft), (float)sin(-2.0 * pi * k / n_fft));
+  *out = h;
+  return ETD_OK;
+}
+
+extern "C" void etd_stemfeat_destroy(etd_stemfeat* h) {
+  if (!h) return;
+  if (h->on_dev || h->ws || h->tab) {
+    (void)hipDeviceSynchronize();   // kernels of this handle may still be in flight
+    h->pool.free_all();
+    if (h->ws) (void)hipFree(h->ws);
+    if (h->tab) (void)hipFree(h->tab);
+  }
+  delete h;
+}
+
+extern "C" long long etd_stemfeat_num_frames(const etd_stemfeat* h, long long N) {
+  if (!h || N < 1) { g_etd_err = "stemfeat_num_frames: null handle or N < 1"; return ETD_EINVAL; }
+  return 1 + (N + 2 * h->lead - h->cfg.n_fft) / h->cfg.hop;
+}
+
+extern "C" long long etd_stemfeat_workspace_bytes(const etd_stemfeat* h, int n_songs, int instr, const int64_t* N_host) {
+  long long blocks = 0, frames = 0, maxT = 0;
+  const int rc = sf_plan(h, n_songs, instr, N_host, nullptr, &blocks, &frames, &maxT);
+  if (rc != ETD_OK) return rc;
+  return (blocks + (long long)n_songs * instr) * 4 + (long long)n_songs * (long long)sizeof(SfSong);
+}
+
+extern "C" int etd_stemfeat_run(etd_stemfeat* h, const float* const* wav_ptrs, int n_songs, int instr, int channels, const int64_t* N_host, float* feat_dev, void* stream) {
+  if (!h || !wav_ptrs || !feat_dev || channels < 1) ETD_FAIL(ETD_EINVAL, "stemfeat_run: null argument or channels < 1");
+  hipStream_t st = (hipStream_t)stream;
+  std::vector<SfSong> tab((size_t)(n_songs > 0 ? n_songs : 0));
+  long long blocks = 0, frames = 0, maxT = 0;
+  ETD_TRY(sf_plan(h, n_songs, instr, N_host, &tab, &blocks, &frames, &maxT));
+  for (int s = 0; s < n_songs; ++s) {
+    if (!wav_ptrs[s]) ETD_FAIL(ETD_EINVAL, "stemfeat_run: song %d has a null pointer", s);
+    tab[s].wav = wav_ptrs[s];
+  }
+  ETD_TRY(sf_upload(h));
+  const long long pairs = (long long)n_songs * instr;
+  if (blocks + pairs > h->ws_floats) {
+    HIP_TRY(hipStreamSynchronize(st));
+    if (h->ws) { (void)hipFree(h->ws); h->ws = nullptr; h->ws_floats = 0; }
+    HIP_TRY(hipMalloc((void**)&h->ws, (size_t)(blocks + pairs) * 4));
+    h->ws_floats = blocks + pairs;
+  }
+  if (n_songs > h->tab_cap) {
+    HIP_TRY(hipStreamSynchronize(st));
+    if (h->tab) { (void)hipFree(h->tab); h->tab = nullptr; h->tab_cap = 0; }
+    HIP_TRY(hipMalloc((void**)&h->tab, (size_t)n_songs * sizeof(SfSong)));
+    h->tab_cap = n_songs;
+  }
+  HIP_TRY(hipMemcpyAsync(h->tab, tab.data(), tab.size() * sizeof(SfSong), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));                   // (tab is host memory of this call)
+  float* wgmax = h->ws;
+  float* ref = h->ws + blocks;
+  const etd_stemfeat_cfg& c = h->cfg;
+  SfArgs a;
+  a.tab = h->tab; a.n_songs = n_songs; a.instr = instr; a.channels = channels;
+  a.n_fft = c.n_fft; a.lgM = h->lgM; a.hop = c.hop; a.lead = h->lead; a.reflect = c.framing == ETD_STEMFEAT_LIBROSA_REFLECT ? 1 : 0;
+  a.window = h->d_window; a.twM = h->d_twM; a.twS = h->d_twS;
+  a.mel_start = h->d_mel_start; a.mel_len = h->d_mel_len; a.mel_off = h->d_mel_off; a.mel_w = h->d_mel_w; a.n_mels = c.n_mels;
+  a.feat = feat_dev; a.wgmax = wgmax;
+  const double fr = (double)frames * instr;
+  {
+    // 5 N log2 N flops of an M-point complex FFT + the split pass + the CSR product; bytes: every sample once + the mel power written
+    ProfScope ps("k_sf_frames", st, fr * (5.0 * h->M * h->lgM + 12.0 * h->M + 2.0 * (double)h->mel_w.size()),
+                 fr * ((double)c.hop * channels * 4 + (double)c.n_mels * 4));
+    const size_t lds = (size_t)6 * (SF_PAD(h->M) + 1) * sizeof(float);
+    hipLaunchKernelGGL(k_sf_frames, dim3((unsigned)blocks), dim3(SF_THREADS), lds, st, a);
+  }
+  {
+    ProfScope ps("k_sf_max", st, 0, (double)blocks * 4);
+    hipLaunchKernelGGL(k_sf_max, dim3((unsigned)pairs), dim3(SF_THREADS), 0, st, h->tab, instr, wgmax, ref);
+  }
+  {
+    ProfScope ps("k_sf_db", st, 0, fr * c.n_mels * 8);
+    long long gx = (maxT * c.n_mels + SF_THREADS * 4 - 1) / (SF_THREADS * 4);
+    if (gx > 65535) gx = 65535;
+    hipLaunchKernelGGL(k_sf_db, dim3((unsigned)gx, (unsigned)pairs), dim3(SF_THREADS), 0, st, h->tab, instr, c.n_mels, ref, c.amin, c.top_db, feat_dev);
+  }
+  HIP_TRY(hipGetLastError());
+  return ETD_OK;
+}

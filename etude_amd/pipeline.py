@@ -6,7 +6,7 @@ What ``InferencePipeline.run`` does for one song and one attribute tuple (/root/
              analyze_volume(origin.wav -> volume.json)                           infer.py:99-104
     stage 2  beat detection -> tempo.json   (by default the caller supplies tempo.json.  With ``features=`` -- the clips' separated-stem mel-dB features -- and a
              ``beat_detector`` the stage runs here: BeatDetector.detect_many (Beat-Transformer + the native DBN trackers) -> BeatAnalyzer, one tempo per clip;
-             source separation and the features themselves stay outside the library)
+             with ``stems=`` -- the clips' separated stems -- the features are made here too (etude_amd.StemFeatures); only source separation itself stays outside)
     stage 3  TinyREMITokenizer(tempo.json).encode(extract.json) -> vocab.encode_sequence -> split_sequence_into_bars
              -> model.generate(bars, attributes) -> tokenizer.decode_to_notes(events, volume.json) -> note_to_midi   infer.py:180-207
 
@@ -64,7 +64,7 @@ class ClipBatchPipeline:
 
     def __init__(self, extractors, decoders, vocab, tempo, attrs: Sequence[Dict[str, int]], sample_rate: int = 44100,
                  force_bar_tokens: int = 0, temperature: float = 0.0, post_workers: int = 8, beat_detector=None, **generate_kwargs):
-        self.beat_detector = beat_detector      # BeatDetector(tracker="native"): only used when run() / extract_stage() get `features`
+        self.beat_detector = beat_detector      # BeatDetector(tracker="native"): only used when run() / extract_stage() get `features` or `stems`
         self.exs = list(extractors)
         self.decs = list(decoders)
         self.vocab = vocab
@@ -106,11 +106,24 @@ class ClipBatchPipeline:
         from .beat_analyzer import structuralize_many
         self.tempo = [list(t) for t in structuralize_many(self.beat_detector, features)]
 
-    def extract_stage(self, wavs: Sequence[torch.Tensor], features: Optional[Sequence] = None) -> List[ClipConditions]:
+    def structuralize_stems(self, stems: Sequence) -> None:
+        """stage 2 from the clips' separated stems [instr][channels][N]: the features are made on the device (etude_amd.StemFeatures) and go straight into the model"""
+        if self.beat_detector is None:
+            raise ValueError("stems= needs a beat_detector (etude_amd.BeatDetector(tracker='native'))")
+        from .beat_analyzer import structuralize_stems_many
+        self.tempo = [list(t) for t in structuralize_stems_many(self.beat_detector, stems)]
+
+    def extract_stage(self, wavs: Sequence[torch.Tensor], features: Optional[Sequence] = None, stems: Optional[Sequence] = None) -> List[ClipConditions]:
+        if features is not None and stems is not None:
+            raise ValueError("give the clips' features or their stems, not both")
         if features is not None:
             if len(features) != len(wavs):
                 raise ValueError("features: one entry per clip")
             self.structuralize(features)
+        if stems is not None:
+            if len(stems) != len(wavs):
+                raise ValueError("stems: one entry per clip")
+            self.structuralize_stems(stems)
         out: List[Optional[ClipConditions]] = [None] * len(wavs)
         errs: list = []
         n = len(self.exs)
@@ -166,9 +179,9 @@ class ClipBatchPipeline:
         with ThreadPoolExecutor(self.post_workers) as pool:
             return list(pool.map(one, range(len(results))))
 
-    def run(self, wavs: Sequence[torch.Tensor], features: Optional[Sequence] = None) -> dict:
+    def run(self, wavs: Sequence[torch.Tensor], features: Optional[Sequence] = None, stems: Optional[Sequence] = None) -> dict:
         t0 = time.perf_counter()
-        conds = self.extract_stage(wavs, features)
+        conds = self.extract_stage(wavs, features, stems)
         t1 = time.perf_counter()
         results, stats = self.decode_stage(conds)
         torch.cuda.synchronize(self.dev)

@@ -24,6 +24,8 @@
  *   etd_beat_forward      Demixed_DilatedTransformerModel.forward      etude/models/beat_transformer.py:56-106,
  *                         (conv front end + 9 dilated layers + 3       etude/models/layers/dilated_transformer_layer.py:37-180
  *                         instrument layers + beat / tempo heads)      (BeatDetector.detect's model call: etude/data/beat_detector.py:121-127)
+ *   etd_stemfeat_run      process_stems_to_spectrogram (stft + mel +    scripts/run_separation.py:124-141, 163-183
+ *                         power_to_db per separated stem)
  *
  * Conventions: every function returns 0 on success or a negative errno-style code (ETD_E*); the
  * message is available from etd_last_error() (thread-local).  "dev" pointers are device (HBM)
@@ -378,6 +380,39 @@ int etd_dbn_track(etd_dbn*, const float* in_dev, int input_kind, int n_seq, cons
                   int32_t* beat_frames, long long beat_cap, int64_t* beat_offsets,
                   int32_t* down_frames, int32_t* down_numbers, long long down_cap, int64_t* down_offsets,
                   int32_t* bar_choice, long long* needed, void* stream);
+
+/* ------------------------------------------------------------------ stem mel-dB features (separated stems -> the input of etd_beat_forward)
+ * What scripts/run_separation.py:124-141, 163-183 does on the host per stem: channel mean, librosa.stft(n_fft = 4096, hop_length = 1024), |X|^2, the Slaney mel
+ * filterbank, librosa.power_to_db(ref = np.max).  DESIGN.md 4d is the contract (parity with librosa itself is unpinned).  Frame t of a stem covers mono samples
+ * [t * hop - lead, + n_fft); T = 1 + (N + 2 * lead - n_fft) / hop. */
+typedef struct etd_stemfeat etd_stemfeat;
+enum {
+  ETD_STEMFEAT_LIBROSA = 0,          /* lead = n_fft / 2, zeros outside the signal (librosa >= 0.10, center = True, pad_mode = "constant"): T = 1 + N / hop */
+  ETD_STEMFEAT_LIBROSA_REFLECT = 1,  /* lead = n_fft / 2, reflection without edge repeat (librosa < 0.10); N <= n_fft / 2 is refused */
+  ETD_STEMFEAT_SPLEETER = 2          /* lead = n_fft, zeros (Spleeter 2.x Separator._stft: n_fft zeros on both ends, center = False): T = 1 + (N + n_fft) / hop */
+};
+typedef struct {
+  int struct_bytes;       /* sizeof(etd_stemfeat_cfg) of the caller: a mismatch is ETD_EINVAL */
+  int n_fft;              /* a power of two in 64 .. 4096 */
+  int hop, n_mels;
+  int framing;            /* ETD_STEMFEAT_* */
+  float amin, top_db;     /* power_to_db: 1e-10, 80 */
+} etd_stemfeat_cfg;
+/* Tables from the host layer: window_host [n_fft] (periodic Hann) and the mel filterbank in CSR form as for etd_frontend_create: band m covers power-spectrum bins
+ * [mel_start[m], + mel_len[m]) with weights mel_w[sum(mel_len[:m]) ...].  A band outside 0 .. n_fft / 2, a negative or non-finite weight, a non-finite window value
+ * or a bad config is ETD_EINVAL with a message.  Needs no GPU: the tables go to the device with the first etd_stemfeat_run. */
+int etd_stemfeat_create(const etd_stemfeat_cfg* cfg, const float* window_host, const int32_t* mel_start, const int32_t* mel_len, const float* mel_w_host,
+                        etd_stemfeat** out);
+void etd_stemfeat_destroy(etd_stemfeat*);
+/* HOST ONLY: frames of a stem of N >= 1 samples (negative = ETD_EINVAL) */
+long long etd_stemfeat_num_frames(const etd_stemfeat*, long long N);
+/* HOST ONLY: bytes of device workspace a call with these songs makes the handle hold (per-workgroup and per-stem maxima, the song table); negative = ETD_EINVAL */
+long long etd_stemfeat_workspace_bytes(const etd_stemfeat*, int n_songs, int instr, const int64_t* N_host);
+/* wav_ptrs: HOST array of n_songs DEVICE pointers, song s = planar [instr][channels][N_host[s]] fp32 (the songs are not concatenated).  feat_dev: the songs'
+ * [instr][T_s][n_mels] fp32 blocks back to back -- exactly etd_beat_forward's input.  Three launches whatever n_songs and instr are.  A (song, stem)'s features depend on
+ * that stem's samples alone: bit-identical alone, in any batch and in any order.  Every output lies in [-top_db, 0]; a NaN or infinite sample leaves NaN in the
+ * frames it reaches (the caller's range check finds it).  Synchronises `stream` once at the start (song table upload). */
+int etd_stemfeat_run(etd_stemfeat*, const float* const* wav_ptrs, int n_songs, int instr, int channels, const int64_t* N_host, float* feat_dev, void* stream);
 
 #ifdef __cplusplus
 }
