@@ -10,6 +10,8 @@ Drop-in surfaces (same names/signatures as the reference):
     etude_amd.BeatDetector          <- etude.data.beat_detector.BeatDetector (the Beat-Transformer model; tracker="native" decodes with the library's own DBN)
     etude_amd.DBNBeatTracker / DBNDownBeatTracker  <- madmom's DBNBeatTrackingProcessor / DBNDownBeatTrackingProcessor (csrc/dbn.hip)
     etude_amd.StemFeatures          <- process_stems_to_spectrogram of scripts/run_separation.py (stems -> mel-dB features; csrc/stemfeat.hip)
+    etude_amd.AudioAligner          <- etude.data.aligner.AudioAligner behind the feature extraction (exact DTW, transposition search, wp.json cache; csrc/dtw.hip)
+    etude_amd.WPDCalculator         <- etude.evaluation.metrics.wpd.WPDCalculator (host arithmetic on the warping path)
     etude_amd.BeatAnalyzer          <- etude.data.beat_analyzer.BeatAnalyzer (beat_pred.json -> tempo.json; host Python)
 All arithmetic runs in libetude_hip.so (hand-written HIP, see csrc/); importing the heavy
 modules is lazy so that `import etude_amd` works on a box without a GPU.
@@ -25,7 +27,8 @@ _os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 __all__ = ["AMTAPC_Extractor", "EtudeDecoder", "EtudeDecoderConfig", "load_etude_decoder", "Vocab", "Event",
            "ExtractorConfig", "DecoderConfig", "HFT_Transformer", "HFTConfig", "TinyREMITokenizer", "run_engines",
            "BeatDetector", "BeatDetectorConfig", "BeatDetectorModelConfig", "DBNBeatTracker", "DBNDownBeatTracker", "BeatAnalyzer", "structuralize_many",
-           "structuralize_stems_many", "StemFeatures", "mel_filterbank"]
+           "structuralize_stems_many", "StemFeatures", "mel_filterbank", "AudioAligner", "align_features", "align_features_many", "align_and_filter_many",
+           "WPDCalculator", "wpd_many"]
 
 
 def __getattr__(name):
@@ -53,6 +56,12 @@ def __getattr__(name):
     if name in ("StemFeatures", "mel_filterbank"):
         from . import stemfeat
         return getattr(stemfeat, name)
+    if name in ("AudioAligner", "align_features", "align_features_many", "align_and_filter_many"):
+        from . import aligner
+        return getattr(aligner, name)
+    if name in ("WPDCalculator", "wpd_many"):
+        from . import evaluation
+        return getattr(evaluation, name)
     if name in ("BeatAnalyzer", "structuralize_many", "structuralize_stems_many"):
         from . import beat_analyzer
         return getattr(beat_analyzer, name)

@@ -60,6 +60,11 @@ class StemFeatCfg(_SizedCfg):
     _fields_ = [("struct_bytes", C.c_int), ("n_fft", C.c_int), ("hop", C.c_int), ("n_mels", C.c_int), ("framing", C.c_int), ("amin", C.c_float), ("top_db", C.c_float)]
 
 
+class DtwCfg(_SizedCfg):
+    _fields_ = [("struct_bytes", C.c_int), ("cens_window", C.c_int), ("cens_decimation", C.c_int), ("reserved", C.c_int), ("step_weights", C.c_double * 3),
+                ("shift_weights", C.c_double * 3), ("alpha", C.c_float), ("norm_threshold", C.c_float)]
+
+
 class G3Case(_SizedCfg):
     """etd_debug_g3_case of include/etude_hip_debug.h: one k_gemm3 / k_gemm3_s launch with any epilogue, strides and row metadata"""
     _fields_ = [("struct_bytes", C.c_int), ("kernel", C.c_int), ("epi", C.c_int)] + [(n, C.c_int) for n in ("M", "N", "K", "ldx", "ldy")] + \
@@ -221,6 +226,14 @@ SIGNATURES = {
     "etd_stemfeat_num_frames": (C.c_longlong, [C.c_void_p, C.c_longlong]),
     "etd_stemfeat_workspace_bytes": (C.c_longlong, [C.c_void_p, C.c_int, C.c_int, c_i64_p]),
     "etd_stemfeat_run": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, c_i64_p, C.c_void_p, C.c_void_p]),
+    "etd_dtw_create": (C.c_int, [C.POINTER(DtwCfg), C.POINTER(C.c_void_p)]),
+    "etd_dtw_destroy": (None, [C.c_void_p]),
+    "etd_dtw_limits": (C.c_int, [c_int_p, c_int_p, C.POINTER(C.c_longlong), c_int_p]),
+    "etd_dtw_workspace_bytes": (C.c_longlong, [C.c_void_p, C.c_int, c_i64_p, c_i64_p, C.POINTER(C.c_longlong), c_i64_p]),
+    "etd_dtw_align": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, c_i64_p, c_i64_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
+    "etd_dtw_debug_cost": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_longlong, C.c_longlong, C.c_int, C.c_void_p]),
+    "etd_dtw_debug_path": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_longlong, C.c_longlong, C.c_int, C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong)]),
+    "etd_dtw_debug_total": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_longlong, C.c_longlong, C.c_int, C.POINTER(C.c_double)]),
     "etd_debug_decoder_trace_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.POINTER(C.c_int), C.c_void_p]),
 }
 

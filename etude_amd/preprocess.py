@@ -90,3 +90,73 @@ def save_volume_map(volume_map: np.ndarray, output_path: Union[str, Path]):
     output_path.parent.mkdir(parents=True, exist_ok=True)
     with open(output_path, "w") as f:
         json.dump(np.asarray(volume_map).tolist(), f)
+
+
+# ---- stage 3 host functions (etude/utils/preprocess.py:14-114): the reference's float operations in the same order, scipy's interp1d restated with numpy
+
+def compute_wp_std(time_map: list) -> float:
+    """etude/utils/preprocess.py:14-19 (WP-Std of Music2MIDI): the standard deviation of origin time - cover time over the map; inf for an empty map."""
+    if not time_map:
+        return float("inf")
+    return np.std([pair[0] - pair[1] for pair in time_map])
+
+
+def _interp_linear(x: np.ndarray, y: np.ndarray, x_new: float, below: float, above: float) -> float:
+    """scipy.interpolate.interp1d(x, y, kind="linear", bounds_error=False, fill_value=(below, above)) at one point: x sorted first (stable), the bracket from
+    searchsorted clipped to 1 .. len - 1, slope * (x_new - x_lo) + y_lo; the fill values strictly outside [x[0], x[-1]]."""
+    if x.shape[0] < 2:
+        raise ValueError("x and y arrays must have at least 2 entries")
+    order = np.argsort(x, kind="mergesort")
+    x, y = x[order], y[order]
+    hi = int(np.clip(np.searchsorted(x, x_new), 1, len(x) - 1))
+    lo = hi - 1
+    slope = (y[hi] - y[lo]) / (x[hi] - x[lo])
+    v = slope * (x_new - x[lo]) + y[lo]
+    if x_new < x[0]:
+        v = below
+    if x_new > x[-1]:
+        v = above
+    return v
+
+
+def create_time_map_from_downbeats(downbeats, align_result: dict, feature_rate: int = 50) -> list:
+    """etude/utils/preprocess.py:21-58: [origin downbeat time, cover time on the warping path] for every downbeat not past the path's end."""
+    wp = align_result["wp"]
+    t_origin = wp[1] / feature_rate
+    t_cover = wp[0] / feature_rate
+    if t_origin.shape[0] < 2:
+        raise ValueError("x and y arrays must have at least 2 entries")      # (interp1d's own refusal, raised where the reference builds the interpolator)
+    time_map = []
+    for db_time in downbeats:
+        if db_time <= t_origin[-1]:
+            time_map.append([float(db_time), float(_interp_linear(t_origin, t_cover, db_time, t_cover[0], t_cover[-1]))])
+    return time_map
+
+
+def weakly_align(transcription_notes: list, time_map: list) -> list:
+    """etude/utils/preprocess.py:60-114: every note's onset moves from the cover's timeline to the origin's, linearly inside its segment of the time map (sorted in
+    place by cover time, as the reference does); the duration is kept.  A note before the first anchor, or in a segment shorter than 1e-6 s, is dropped; the last
+    anchor opens a segment of 10 s."""
+    if not time_map or not transcription_notes:
+        return []
+    out = []
+    time_map.sort(key=lambda p: p[1])
+    k = 0
+    for note in sorted(transcription_notes, key=lambda n: n["onset"]):
+        t_on = note["onset"]
+        dur = note["offset"] - t_on
+        while k + 1 < len(time_map) and t_on >= time_map[k + 1][1]:
+            k += 1
+        s1, p1 = time_map[k]
+        if k + 1 < len(time_map):
+            s2, p2 = time_map[k + 1]
+        else:
+            s2, p2 = s1 + 10, p1 + 10
+        seg = p2 - p1
+        if seg < 1e-6:
+            continue
+        if p1 <= t_on < p2:
+            rel = (t_on - p1) / seg
+            onset = s1 + rel * (s2 - s1)
+            out.append({"pitch": note["pitch"], "onset": onset, "offset": onset + dur, "velocity": note["velocity"]})
+    return out

@@ -26,6 +26,9 @@
  *                         instrument layers + beat / tempo heads)      (BeatDetector.detect's model call: etude/data/beat_detector.py:121-127)
  *   etd_stemfeat_run      process_stems_to_spectrogram (stft + mel +    scripts/run_separation.py:124-141, 163-183
  *                         power_to_db per separated stem)
+ *   etd_dtw_align         AudioAligner._compute_warping_path behind the  etude/data/aligner.py:106-133
+ *                         features: CENS, optimal chroma shift, DTW,
+ *                         strictly monotonic path, pitch_shift
  *
  * Conventions: every function returns 0 on success or a negative errno-style code (ETD_E*); the
  * message is available from etd_last_error() (thread-local).  "dev" pointers are device (HBM)
@@ -413,6 +416,41 @@ long long etd_stemfeat_workspace_bytes(const etd_stemfeat*, int n_songs, int ins
  * that stem's samples alone: bit-identical alone, in any batch and in any order.  Every output lies in [-top_db, 0]; a NaN or infinite sample leaves NaN in the
  * frames it reaches (the caller's range check finds it).  Synchronises `stream` once at the start (song table upload). */
 int etd_stemfeat_run(etd_stemfeat*, const float* const* wav_ptrs, int n_songs, int instr, int channels, const int64_t* N_host, float* feat_dev, void* stream);
+
+/* ------------------------------------------------------------------ DTW alignment (chroma + DLNCO features of a cover and its origin -> warping path, pitch shift)
+ * What AudioAligner._compute_warping_path does behind the feature extraction (etude/data/aligner.py:106-133): quantized_chroma_to_CENS(.., 201, 50, ..),
+ * compute_optimal_chroma_shift, shift_chroma_vectors, sync_via_mrmsdtw(step_weights = [1.5, 1.5, 2.0], alpha = 0.5), make_path_strictly_monotonic and the
+ * pitch_shift rule.  Where synctoolbox approximates the optimum inside multi-resolution constraint regions, this is the exact full-resolution DTW.  DESIGN.md 4e is
+ * the contract (parity with synctoolbox itself is unpinned).  Sequence 1 is the cover, sequence 2 the origin. */
+typedef struct etd_dtw etd_dtw;
+typedef struct {
+  int struct_bytes;          /* sizeof(etd_dtw_cfg) of the caller: a mismatch is ETD_EINVAL */
+  int cens_window;           /* 201: points of the Hann window (symmetric, scaled to sum 1) that smooths every pitch row; odd, 1 .. 4095 */
+  int cens_decimation;       /* 50: every cens_decimation-th smoothed frame is a CENS frame, starting at 0 */
+  int reserved;              /* 0 */
+  double step_weights[3];    /* (1.5, 1.5, 2.0): weights of the steps (1,0), (0,1), (1,1) of the final DTW (aligner.py:43) */
+  double shift_weights[3];   /* (1, 1, 1): ... of the 12 CENS DTWs of the transposition search (compute_optimal_chroma_shift) */
+  float alpha;               /* 0.5: C = alpha (2 - <c1, c2>) + (1 - alpha) ||o1 - o2|| */
+  float norm_threshold;      /* 1e-3: a chroma / CENS column with a smaller L2 norm becomes the constant unit vector */
+} etd_dtw_cfg;
+/* AudioAligner.__init__ (aligner.py:31-45).  Needs no GPU: the window goes to the device with the first call.  A bad config is ETD_EINVAL. */
+int etd_dtw_create(const etd_dtw_cfg* cfg, etd_dtw** out);
+void etd_dtw_destroy(etd_dtw*);
+/* HOST ONLY: the constants of this build: rows of a row block, cells per backpointer word, frames per side and pairs per call it accepts (any may be NULL) */
+int etd_dtw_limits(int* row_block, int* cells_per_word, long long* max_frames, int* max_pairs);
+/* HOST ONLY: bytes of device workspace a call with these pairs needs (formula in DESIGN.md 4e; dominated by the 2-bit backpointers, N1 * ceil(N2 / 16) * 4 bytes
+ * per pair); *result_ints (may be NULL) = int32 elements of its result buffer, result_offsets [n_pairs] (may be NULL) = where each pair's block starts in it.
+ * Negative = ETD_EINVAL: n_pairs outside 1 .. 4096, a side of no frames, or one of more than 65 536 frames (the message names the count). */
+long long etd_dtw_workspace_bytes(const etd_dtw*, int n_pairs, const int64_t* N1_host, const int64_t* N2_host, long long* result_ints, int64_t* result_offsets);
+/* The body of _compute_warping_path for n_pairs pairs in five launches.  feat_ptrs: HOST array [n_pairs][4] of DEVICE pointers: cover quantized chroma, cover DLNCO
+ * (both fp32 [12][N1]), origin quantized chroma, origin DLNCO (fp32 [12][N2]); finite, chroma >= 0 (the caller checks).  workspace_dev: 256-byte aligned device
+ * memory of >= etd_dtw_workspace_bytes; result_dev: 8-byte aligned device int32 [>= *result_ints].  Pair p's block, at result_offsets[p], with cap = min(N1, N2) + 1:
+ *   [0] L = path length  [1] opt = the chroma shift applied to the origin  [2] pitch_shift = (-opt) mod 12, minus 12 above 6  [3] points of the unfiltered path
+ *   [4..5] D[-1,-1] of the final DTW (one double)  [6..7] 0     [8 .. 8 + L) wp[0] = cover frames     [8 + cap .. 8 + cap + L) wp[1] = origin frames, increasing.
+ * result_host (may be NULL): the whole result copied there, the one copy to the host.  A pair's result depends on that pair alone: bit-identical alone, in any
+ * batch and in any order.  Synchronous: returns when `stream` has drained. */
+int etd_dtw_align(etd_dtw*, const float* const* feat_ptrs, int n_pairs, const int64_t* N1_host, const int64_t* N2_host, void* workspace_dev, long long workspace_bytes,
+                  int32_t* result_dev, long long result_ints, int32_t* result_host, void* stream);
 
 #ifdef __cplusplus
 }

@@ -116,6 +116,14 @@ int etd_beat_debug_taps(etd_beat*, float* front_dev, float* layer0_dev);
  * -> path_out host int32 [T] (state per frame) and *logprob_out (host).  Synchronous, default stream. */
 int etd_dbn_debug_viterbi(etd_dbn*, int hmm_index, const double* densities_dev, long long T, int32_t* path_out, double* logprob_out);
 
+/* test hooks of etd_dtw_align, one pair each, feat_ptrs as there ([4] device pointers); synchronous, default stream, buffers of their own.
+ * _cost: the fp32 cost matrix [N1][N2] the final DTW would see with the origin shifted by `shift` (0..11), formed by the kernel's own cost function -> cost_dev (device);
+ *        more than 2^22 cells is ETD_EINVAL.  _total: D[-1,-1] of the final DTW with that shift (no transposition search) -> *total_host. */
+int etd_dtw_debug_cost(etd_dtw*, const float* const* feat_ptrs, long long N1, long long N2, int shift, float* cost_dev);
+int etd_dtw_debug_total(etd_dtw*, const float* const* feat_ptrs, long long N1, long long N2, int shift, double* total_host);
+/* ... and its unfiltered step path, LAST point first: path_host int32 [cap][2] of (cover frame, origin frame), *n_out = points (<= N1 + N2 - 1); ETD_ENOMEM when cap is short */
+int etd_dtw_debug_path(etd_dtw*, const float* const* feat_ptrs, long long N1, long long N2, int shift, int32_t* path_host, long long cap, long long* n_out);
+
 #ifdef __cplusplus
 }
 #endif
