@@ -11,8 +11,10 @@ on real embedded frames of a synthetic window and rounds to bf16 exactly where c
     X1     LayerNorm output (operand of the feed-forward block AND its residual)
     H      hidden activations relu(fc_1)             Y     the layer output
 
-Prints rms(err) / rms(ref) and max|err| of the layer output per site.  usage: python tools/diag_rounding_budget.py [n_frames=16]"""
-import math
+Prints rms(err) / rms(ref) and max|err| of the layer output per site.  usage: python tools/diag_rounding_budget.py [n_frames=16]
+
+`python tools/diag_rounding_budget.py stages [n_frames=8]` prints instead what every layer costs in IEEE half from its exact 16-bit input, against float64.
+The rounding sites are those of tests/hft_stage_ref.py: this script and the GPU stage tests share one emulation."""
 import sys
 from pathlib import Path
 
@@ -23,6 +25,7 @@ import torch.nn.functional as F
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 from etude_amd import synth  # noqa: E402
 from oracle import hft  # noqa: E402
+from tests.hft_stage_ref import encoder_layer  # noqa: E402
 
 
 def bf(x):
@@ -30,32 +33,42 @@ def bf(x):
 
 
 def layer(sd, pfx, x, sites, n_heads=4):
-    r = lambda name, v: bf(v) if name in sites else v      # noqa: E731
-    w = lambda k: r("W", sd[k])                            # noqa: E731
-    lin = lambda p, v: F.linear(v, w(p + ".weight"), sd[p + ".bias"])      # noqa: E731
-    ln = lambda v: F.layer_norm(v, (v.shape[-1],), sd[pfx + ".layer_norm.weight"], sd[pfx + ".layer_norm.bias"], 1e-5)      # noqa: E731
-    x = r("X", x)
-    B, hid = x.shape[0], x.shape[-1]
-    hd = hid // n_heads
-    sa = pfx + ".self_attention"
-    split = lambda v: v.view(B, -1, n_heads, hd).permute(0, 2, 1, 3)      # noqa: E731
-    Q = r("Q", split(lin(sa + ".fc_q", x)) / math.sqrt(hd))
-    K = r("K", split(lin(sa + ".fc_k", x)))
-    V = r("V", split(lin(sa + ".fc_v", x)))
-    s = torch.matmul(Q, K.permute(0, 1, 3, 2))
-    p = torch.exp(s - s.max(-1, keepdim=True).values)
-    den = p.sum(-1, keepdim=True)                     # the kernel sums the fp32 numerators, then rounds them for the PV product
-    o = torch.matmul(r("P", p), V) / den
-    o = r("O", o).permute(0, 2, 1, 3).contiguous().view(B, -1, hid)
-    x1 = r("X1", ln(x + lin(sa + ".fc_o", o)))
-    ff = pfx + ".positionwise_feedforward"
-    hdn = r("H", torch.relu(lin(ff + ".fc_1", x1)))
-    return r("Y", ln(x1 + lin(ff + ".fc_2", hdn)))
+    """the layer with bf16 roundings at `sites`: tests/hft_stage_ref.py, the emulation the GPU stage tests take their bounds from"""
+    return encoder_layer(sd, pfx, x, n_heads, sites=sites, dtype=torch.bfloat16)
+
+
+def stage_table(nfr):
+    """Every layer from its EXACT 16-bit input (the oracle's own tap rounded to IEEE half), float64, all sites on: what one stage costs when nothing
+    accumulates -- the budget tests/test_gpu_extractor_stages.py holds the device to."""
+    from tests.hft_stage_ref import CKPT_SEED, FEAT_SEED, ENC_SITES
+    print(f"n_frame {nfr}, checkpoint seed {CKPT_SEED}, window_features({FEAT_SEED}, ...), IEEE-half sites {' '.join(sorted(ENC_SITES))}")
+    print("layer (from its exact 16-bit input)   bench ckpt max / rms      cal ckpt max / rms        max |output|")
+    d = hft.HftDims(n_frame=nfr)
+    x = torch.from_numpy(synth.window_features(FEAT_SEED, 1, 256, nfr + 2 * d.n_margin))
+    rows = {}
+    for make in (synth.extractor_state_dict, synth.extractor_state_dict_cal):
+        sd = {k: torch.from_numpy(v) for k, v in make(CKPT_SEED, dict(n_frame=nfr)).items()}
+        taps = {}
+        hft.model_forward(sd, x, d, taps)
+        sd64 = {k: v.double() for k, v in sd.items()}
+        for pfx, src, fold in (("encoder.layers_freq.0", "embed", True), ("encoder.layers_freq.1", "enc0", True), ("encoder.layers_freq.2", "enc1", True),
+                               ("decoder.layers_time.0", "time_in", False), ("decoder.layers_time.1", "time0", False)):
+            xin = taps[src].half().double()
+            ref = encoder_layer(sd64, pfx, xin, d.n_heads, fold_log2e=fold)
+            emu = encoder_layer(sd64, pfx, xin, d.n_heads, sites=ENC_SITES, dtype=torch.float16, fold_log2e=fold)
+            e = emu - ref
+            rows.setdefault(pfx, []).append((float(e.abs().max()), float(e.pow(2).mean().sqrt()), float(ref.abs().max())))
+    for pfx, ((bm, br, bt), (cm, cr, ct)) in rows.items():
+        print(f"{pfx:36s}  {bm:.1e} / {br:.1e}         {cm:.1e} / {cr:.1e}         {min(bt, ct):.1f} - {max(bt, ct):.1f}")
 
 
 def main():
-    nfr = int(sys.argv[1]) if len(sys.argv) > 1 else 16
     torch.set_num_threads(8)
+    if len(sys.argv) > 1 and sys.argv[1] == "stages":
+        with torch.no_grad():
+            stage_table(int(sys.argv[2]) if len(sys.argv) > 2 else 8)
+        return
+    nfr = int(sys.argv[1]) if len(sys.argv) > 1 else 16
     sd = {k: torch.from_numpy(v) for k, v in synth.extractor_state_dict(0).items()}
     d = hft.HftDims()
     x = torch.from_numpy(synth.window_features(5, 1))
