@@ -202,6 +202,8 @@ SIGNATURES = {
     "etd_decoder_stamp_log": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong), C.c_void_p]),
     "etd_debug_decoder_force_pair": (C.c_int, [C.c_void_p, C.c_int]),
     "etd_debug_decoder_step_logits": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "etd_debug_decoder_bar_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "etd_debug_sample_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_ulonglong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "etd_debug_decoder_checksum": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int, C.c_void_p]),
     "etd_debug_decoder_kv_rowsums": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
     "etd_debug_decoder_trace_begin": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),

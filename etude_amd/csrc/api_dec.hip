@@ -88,6 +88,7 @@ struct etd_dec {
   int force_pair = -1;                           // test hook (etd_debug_decoder_force_pair): -1 = the rule above, 0 / 1 = one-row / paired-rows attention form
   unsigned long long* stamp_dev = nullptr;       // device-side span accumulator of k_dstep_attn_down (etd_decoder_stamp); its own allocation
   bool stamp_on = false, stamp_armed = false; long long stamp_skip = 0;      // armed: requested; on: this call's steps are stamped (after `stamp_skip` more steps)
+  int bar_logit_rows = 0;                        // test hook (etd_debug_decoder_bar_logits): rows of d->logits the latest begin_bars left
   float* logits_dbg = nullptr; bool logits_dbg_on = false, last_step_fused = false;   // test hook: the fused step's logits [S][V] (etd_debug_decoder_step_logits)
   // teacher-forced scoring (etd_decoder_score): own buffers, allocated by the first score call and freed with the handle (the generate path never touches them).
   // sc_i = [labels Mcap][row list Mcap + score_hb][seq row0 S][seq len S] (uploaded per chunk) then [argmax Mcap][seq tokens S][seq hits S];
@@ -968,6 +969,7 @@ extern "C" int etd_decoder_begin_bars(etd_dec* d, int n, const int32_t* slots, c
   DArgmaxArgs am = argmax_args(d, DecRows{sg.last_slot, sg.last_pos, sg.last_active}, n);
   if (d->sampling) { am.samp = d->samp_dev; am.rng_key = d->rng_key; }
   ETD_TRY(launch_dargmax(am, st));
+  d->bar_logit_rows = n;
   return ETD_OK;
 }
 
@@ -1212,6 +1214,14 @@ extern "C" int etd_debug_decoder_step_logits(etd_dec* d, int on, float* out_host
   }
   if (on && !d->logits_dbg) HIP_TRY(hipMalloc((void**)&d->logits_dbg, (size_t)d->S * d->V * 4));
   d->logits_dbg_on = on != 0;
+  return ETD_OK;
+}
+
+// test hook: the [n][V] last-position logits the latest begin_bars drew its first tokens from (they stay in the workspace)
+extern "C" int etd_debug_decoder_bar_logits(etd_dec* d, float* out_host, int n, void* stream) {
+  if (!d || !out_host || n < 1 || n > d->bar_logit_rows) ETD_FAIL(ETD_EINVAL, "bar_logits: bad arguments (the latest begin_bars had %d streams)", d ? d->bar_logit_rows : 0);
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  HIP_TRY(hipMemcpy(out_host, d->logits, (size_t)n * d->V * 4, hipMemcpyDeviceToHost));
   return ETD_OK;
 }
 

@@ -209,4 +209,7 @@ struct DArgmaxArgs {
   const DSampleCfg* samp; const unsigned long long* rng_key;   // [slots]; samp == null -> greedy
 };
 int launch_dargmax(const DArgmaxArgs& a, hipStream_t st);
+// test hook: the sampler alone (wave_sample, one wave per row) on M rows of V <= 256 logits with row stride ld; per-row keys and draw counters
+extern "C" int etd_debug_sample_rows(const float* logits_dev, int M, int V, int ld, float temperature, float top_p, unsigned long long seed,
+                                     const unsigned long long* keys_dev, const unsigned* ctrs_dev, int* out_tok_dev, void* stream);
 

@@ -2051,3 +2051,22 @@ int launch_dargmax(const DArgmaxArgs& a, hipStream_t st) {
   return ETD_OK;
 }
 
+// test hook (tests/test_gpu_sampling_exact.py): the draw alone.  One wave per row calls the SAME wave_sample with LDS scratch as
+// k_dargmax does and stores the token; no stream state is read or written.
+__global__ void k_sample_rows(const float* logits, int V, int ld, float inv_temp, float top_p, unsigned long long seed, const unsigned long long* keys,
+                              const unsigned* ctrs, int* out_tok) {
+  __shared__ float sp[256], ss[256];
+  __shared__ int si[256];
+  const int m = blockIdx.x, lane = threadIdx.x;
+  const int tok = wave_sample(logits + (long long)m * ld, V, lane, inv_temp, top_p, seed, keys[m], ctrs[m], sp, ss, si);
+  if (lane == 0) out_tok[m] = tok;
+}
+extern "C" int etd_debug_sample_rows(const float* logits_dev, int M, int V, int ld, float temperature, float top_p, unsigned long long seed,
+                                     const unsigned long long* keys_dev, const unsigned* ctrs_dev, int* out_tok_dev, void* stream) {
+  if (!logits_dev || !keys_dev || !ctrs_dev || !out_tok_dev || M < 1 || V < 1 || V > 256 || ld < V || !(temperature > 0.f) || !(top_p == top_p))
+    ETD_FAIL(ETD_EINVAL, "debug_sample_rows: bad arguments (needs 1 <= V <= 256, ld >= V, temperature > 0)");
+  hipLaunchKernelGGL(k_sample_rows, dim3(M), dim3(64), 0, (hipStream_t)stream, logits_dev, V, ld, 1.0f / temperature, top_p, seed, keys_dev, ctrs_dev, out_tok_dev);
+  HIP_TRY(hipGetLastError());
+  return ETD_OK;
+}
+

@@ -542,6 +542,13 @@ class EtudeDecoder:
                        "etd_debug_decoder_step_logits")
         return out
 
+    def debug_bar_logits(self, n: int) -> np.ndarray:
+        """Test hook: the last-position logits [n, V] the latest begin_bars chose its first tokens from (row i = its i-th stream)."""
+        out = np.zeros((n, self.config.vocab_size), np.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().etd_debug_decoder_bar_logits(self._h, out.ctypes.data, n, self._stream()), "etd_debug_decoder_bar_logits")
+        return out
+
     def close(self):
         if getattr(self, "_h", None):
             _lib.lib().etd_decoder_destroy(self._h)

@@ -62,6 +62,13 @@ int etd_debug_decoder_force_pair(etd_dec*, int mode);
 /* test hook: switch the per-step logit store of the decode step on / off and (out_host != NULL) copy out the LAST step's logits
  * [n_active][vocab] fp32 -- the fused bf16 step keeps its logits in LDS otherwise.  Stamped / logged steps use their own captured graphs. */
 int etd_debug_decoder_step_logits(etd_dec*, int on, float* out_host, int n_active, void* stream);
+/* test hook: the last-position logits [n][vocab] fp32 that the latest etd_decoder_begin_bars chose its n first tokens from (row i = the
+ * call's i-th stream).  Valid until the next begin_bars, prefill or unfused decode step. */
+int etd_debug_decoder_bar_logits(etd_dec*, float* out_host, int n, void* stream);
+/* test hook (tests/test_gpu_sampling_exact.py): the sampler alone.  Token of each of M rows of V <= 256 device logits (row stride ld >= V) drawn by
+ * the decoder's own sampling routine with per-row keys and draw counters (device arrays); temperature > 0.  No decoder state is involved. */
+int etd_debug_sample_rows(const float* logits_dev, int M, int V, int ld, float temperature, float top_p, unsigned long long seed,
+                          const unsigned long long* keys_dev, const unsigned* ctrs_dev, int* out_tok_dev, void* stream);
 
 /* test hooks of the fp32-grade f16-split kernels (csrc/gemm3.h; tests/test_gpu_gemm3.py):
  * y[M][N] = x[M][K] w[N][K]^T + bias (x, y device fp32 row-major; w, bias host; x_bound = bound of |x| for the plane scale; gelu != 0: erf-GELU epilogue).
