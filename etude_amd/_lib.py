@@ -45,6 +45,13 @@ class DecCfg(_SizedCfg):
                 ("max_streams", C.c_int), ("max_ctx", C.c_int), ("precision", C.c_int), ("max_prefill_rows", C.c_int)]
 
 
+class DecTaps(_SizedCfg):
+    """etd_debug_dec_taps (include/etude_hip_debug.h): device destinations of the 16-bit decoder's stage taps"""
+    PTRS = ("hin", "ln1", "ln2", "q", "qb", "xcat", "slabs", "hout", "step_slot", "step_pos", "next_h", "next_ln1", "next_ln2", "next_pos")
+    _fields_ = [("struct_bytes", C.c_int), ("layer_mask", C.c_uint)] + [(n, C.c_int) for n in ("rows", "hidden", "intermediate", "slab_cap", "slices")] + \
+               [(n, C.c_void_p) for n in PTRS]
+
+
 class BeatCfg(_SizedCfg):
     _fields_ = [("struct_bytes", C.c_int)] + [(n, C.c_int) for n in ("attn_len", "instr", "ntoken", "dmodel", "nhead", "d_hid", "nlayers", "norm_first",
                                        "n_mels", "tempo_out", "max_rows")]
@@ -210,6 +217,8 @@ SIGNATURES = {
     "etd_debug_decoder_trace_slabs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p]),
     "etd_debug_decoder_trace_lanes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p]),
     "etd_debug_decoder_trace_q": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p]),
+    "etd_debug_decoder_stage_taps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "etd_debug_decoder_peek_kv_many": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "etd_debug_decoder_peek_kv": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "etd_beat_create": (C.c_int, [C.POINTER(BeatCfg), C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), c_i64_p, C.c_int, C.POINTER(C.c_void_p)]),
     "etd_beat_destroy": (None, [C.c_void_p]),

@@ -96,6 +96,7 @@ struct etd_dec {
   int* sc_i = nullptr; float* sc_f = nullptr; double* sc_d = nullptr; float* sc_x = nullptr; int score_hb = 0;
   // weight sharing (etd_decoder_clone): a clone reads the owner's weight buffers and has its own KV cache, workspaces and
   // stream state.  `pool` of an owner = weights first (n_weight_allocs of them), then its workspaces; a clone's = workspaces only.
+  etd_debug_dec_taps taps = {}; bool taps_on = false;      // test hook (etd_debug_decoder_stage_taps): device destinations of the 16-bit sequences' stage outputs
   etd_dec* weights_owner = nullptr;              // null: this handle owns its weights
   size_t n_weight_allocs = 0;
   int n_clones = 0; bool zombie = false;         // owner destroyed while clones are alive: weights freed with the last clone
@@ -186,6 +187,42 @@ static int trace_rows(etd_dec* d, const void* buf, long long row_stride, int wor
   return ETD_OK;
 }
 
+// ---- stage taps (etd_debug_decoder_stage_taps): every copy below follows the launch that produced its source, on the same stream.  With taps off
+// tap_slice is -1 and nothing is enqueued.
+// slice of layer l in the caller's buffers, -1 when the layer is not tapped; tail: the slice behind the layers', the last-rows tail of a batched prefill
+static inline int tap_slice(const etd_dec* d, int l, bool tail = false) {
+  if (!d->taps_on || !((d->taps.layer_mask >> l) & 1u)) return -1;
+  return tail ? __builtin_popcount(d->taps.layer_mask) : __builtin_popcount(d->taps.layer_mask & ((1u << l) - 1u));
+}
+static int tap_copy(void* dst, int slice, size_t slice_bytes, const void* src, size_t bytes, hipStream_t st) {
+  if (slice < 0 || !dst) return ETD_OK;
+  HIP_TRY(hipMemcpyAsync((char*)dst + (size_t)slice * slice_bytes, src, bytes, hipMemcpyDeviceToDevice, st));
+  return ETD_OK;
+}
+// M rows of `width` elements of `esz` bytes into slice `s` of a [slices][taps.rows][width] buffer
+static int tap_rows(const etd_dec* d, void* dst, int s, const void* src, int M, int width, int esz, hipStream_t st) {
+  return tap_copy(dst, s, (size_t)d->taps.rows * width * esz, src, (size_t)M * width * esz, st);
+}
+static int tap_layer_in(const etd_dec* d, int s, const float* hin, int M, hipStream_t st) {      // residual stream and LayerNorm rows entering a layer
+  if (s < 0) return ETD_OK;
+  ETD_TRY(tap_rows(d, d->taps.hin, s, hin, M, d->H, 4, st));
+  ETD_TRY(tap_rows(d, d->taps.ln1, s, d->X1b, M, d->H, 2, st));
+  return tap_rows(d, d->taps.ln2, s, d->X2b, M, d->H, 2, st);
+}
+static int tap_xcat(const etd_dec* d, int s, int M, hipStream_t st) { return tap_rows(d, d->taps.xcat, s, d->Xcat, M, d->I + d->H, 2, st); }
+static int tap_slabs(const etd_dec* d, int s, int nslab, int M, hipStream_t st) {
+  return tap_copy(d->taps.slabs, s, (size_t)d->taps.slab_cap * d->taps.rows * d->H * 4, d->Pk, (size_t)nslab * M * d->H * 4, st);
+}
+// the caller's stated sizes against a call of M rows whose split-K launches write nslab slabs: checked before the call launches anything
+static int taps_fit(const etd_dec* d, int M, int nslab, bool tail = false /* the call may run the last-rows tail of a batched prefill */) {
+  if (!d->taps_on) return ETD_OK;
+  const int need = __builtin_popcount(d->taps.layer_mask) + (tail && ((d->taps.layer_mask >> (d->L - 1)) & 1u) ? 1 : 0);
+  if (need > d->taps.slices) ETD_FAIL(ETD_EINVAL, "stage taps: the call writes %d slices, the tap buffers hold %d", need, d->taps.slices);
+  if (M > d->taps.rows) ETD_FAIL(ETD_EINVAL, "stage taps: a call of %d rows, the tap buffers hold %d", M, d->taps.rows);
+  if (d->taps.slabs && (long long)nslab * M > (long long)d->taps.slab_cap * d->taps.rows) ETD_FAIL(ETD_EINVAL, "stage taps: %d slabs of %d rows exceed slab_cap %d x rows %d", nslab, M, d->taps.slab_cap, d->taps.rows);
+  return ETD_OK;
+}
+
 static inline bool fused_pmlp_on() { const char* e = getenv("ETD_FUSED_PMLP"); return !e || atoi(e) > 0; }
 // "Only each prompt's last position is needed" (begin_bars): the last layer then runs its attention, MLP and residual for
 // those n rows only -- on the decode-step kernels -- after the big QKV GEMM has put every position's K/V into the cache.
@@ -252,10 +289,12 @@ static int resid_ln(etd_dec* d, int l, int nslab, const float* hin, float* hout,
 // (down | dense) projection with K split over workgroups, then ONE row kernel: partial sums + bias + residual and the
 // next layer's two LayerNorms.  (Folding that row kernel into the GEMM's last-arriving workgroup was measured: the
 // serial read of 5 slabs x 32 rows costs 3x the kernel boundary it saves.)
-static int down_splitk(etd_dec* d, int l, const float* hin, float* hout, int M, const NextLn& nx, hipStream_t st) {
+static int down_splitk(etd_dec* d, int l, const float* hin, float* hout, int M, const NextLn& nx, hipStream_t st, int ts = -1 /* tap slice */) {
   DGemmArgs dn = lin_args(d->layers[l].cat, d->M1, d->I + d->H, M); dn.Xb = d->Xcat; dn.hin = hin; dn.hout = hout; dn.k_splits = DS_K_SPLITS; dn.Y = d->Pk; dn.ldy = d->H;
   ETD_TRY(launch_dgemm(dn, DEPI_PARTIAL, true, st));
-  return resid_ln(d, l, DS_K_SPLITS, hin, hout, M, nx, st);
+  ETD_TRY(tap_slabs(d, ts, DS_K_SPLITS, M, st));
+  ETD_TRY(resid_ln(d, l, DS_K_SPLITS, hin, hout, M, nx, st));
+  return tap_rows(d, d->taps.hout, ts, hout, M, d->H, 4, st);
 }
 // k_linear's decoder modes: M 16-bit rows X [M][w.K] against w in fragment order; `dec` carries what the epilogue reads
 static int linear16(const Lin& w, const d16* X, int M, const DGemmArgs& dec, int epi, hipStream_t st) {
@@ -360,7 +399,7 @@ static int trace_qkv_up(etd_dec* d, int l, int M, hipStream_t st) {
   return ETD_OK;
 }
 // decode step: attention (+ its share of attention.dense) and the MLP down projection in ONE launch, then the row kernel
-static int skinny_attn_down(etd_dec* d, int l, const DecRows& rows, int M, const float* hin, float* hout, hipStream_t st) {
+static int skinny_attn_down(etd_dec* d, int l, const DecRows& rows, int M, const float* hin, float* hout, hipStream_t st, int ts) {
   const Layer& w = d->layers[l]; const NextLn nx = next_ln(d, l);
   const int ksd = d->I / 512;      // slabs of the down projection; one more per head from the attention workgroups
   DAttnArgs at = attn_args(d, l, rows, M);
@@ -380,9 +419,12 @@ static int skinny_attn_down(etd_dec* d, int l, const DecRows& rows, int M, const
     return launch_dstep_attn_down(at, dn, &fin, st);
   }
   ETD_TRY(launch_dstep_attn_down(at, dn, nullptr, st));
+  ETD_TRY(tap_xcat(d, ts, M, st));
+  ETD_TRY(tap_slabs(d, ts, ksd + d->nh, M, st));
   if (d->trace && ksd + d->nh == 12) ETD_TRY(trace_rows(d, d->Pk, d->H, d->H, 12, (long long)M * d->H, M, l * ETD_TRACE_LAYER * M + 2 * M, st));
   if (d->trace && l == 0 && ksd + d->nh == 12) HIP_TRY(hipMemcpyAsync(d->trace_pk, d->Pk, (size_t)12 * M * d->H * 4, hipMemcpyDeviceToDevice, st));
   ETD_TRY(resid_ln(d, l, ksd + d->nh, hin, hout, M, nx, st));
+  ETD_TRY(tap_rows(d, d->taps.hout, ts, hout, M, d->H, 4, st));
   if (d->trace) {
     ETD_TRY(trace_rows(d, hout, d->H, d->H, 1, 0, M, l * ETD_TRACE_LAYER * M + 14 * M, st));
     if (nx.x1) {
@@ -399,10 +441,17 @@ static int forward_skinny16(etd_dec* d, int M, const DecRows& rows, bool ln0_don
   float* hin = d->h; float* hout = d->h2;
   if (!ln0_done) ETD_TRY(ln_rows16(d, 0, hin, M, st));
   for (int l = 0; l < d->L; ++l) {
+    const int ts = tap_slice(d, l);
+    ETD_TRY(tap_layer_in(d, ts, hin, M, st));
     ETD_TRY(step_qkv_up(d, l, hin, rows, M, st));
+    ETD_TRY(tap_rows(d, d->taps.q, ts, d->Q, M, d->H, 4, st));
     ETD_TRY(trace_qkv_up(d, l, M, st));
-    if (attn_down) ETD_TRY(skinny_attn_down(d, l, rows, M, hin, hout, st));
-    else { ETD_TRY(layer_dattn(d, l, rows, M, d->Xcat + d->I, d->I + d->H, st)); ETD_TRY(down_splitk(d, l, hin, hout, M, next_ln(d, l), st)); }
+    if (attn_down) ETD_TRY(skinny_attn_down(d, l, rows, M, hin, hout, st, ts));
+    else {
+      ETD_TRY(layer_dattn(d, l, rows, M, d->Xcat + d->I, d->I + d->H, st));
+      ETD_TRY(tap_xcat(d, ts, M, st));
+      ETD_TRY(down_splitk(d, l, hin, hout, M, next_ln(d, l), st, ts));
+    }
     std::swap(hin, hout);
   }
   *hfinal = hin;
@@ -426,7 +475,7 @@ static int prefill16_qkv(etd_dec* d, int l, const float* hin, const DecRows& row
 }
 // every other layer, after its QKV: attention into the block of Xcat behind GELU(up), then the MLP with attention.dense folded in, and the residual
 static int prefill16_layer_rest(etd_dec* d, int l, const DecRows& rows, int M, const PrefillInfo* pf, bool fmlp, const float* hin, float* hout, hipStream_t st) {
-  const Layer& w = d->layers[l];
+  const Layer& w = d->layers[l]; const int ts = tap_slice(d, l);
   if (pf) {
     // ragged causal MFMA flash attention over the prompts of all streams at once, K / V straight from the cache rows (csrc/dec_prefill.hip)
     PAttnArgs t = {};
@@ -441,24 +490,31 @@ static int prefill16_layer_rest(etd_dec* d, int l, const DecRows& rows, int M, c
     ma.X2 = d->X2b; ma.AO = d->Xcat + d->I; ma.ldao = d->I + d->H; ma.hin = hin; ma.hout = hout; ma.Wm = (const d16*)w.mlp_frag;
     ma.b_up = w.up.b; ma.b_cat = w.cat.b; ma.eps = d->cfg.layer_norm_eps; ma.M = M;
     ma.g1 = nx.g1; ma.b1 = nx.b1; ma.g2 = nx.g2; ma.b2 = nx.b2; ma.nx1 = nx.x1; ma.nx2 = nx.x2;
-    return launch_dmlp_fused(ma, st);
+    ETD_TRY(tap_xcat(d, ts, M, st));
+    ETD_TRY(launch_dmlp_fused(ma, st));
+    return tap_rows(d, d->taps.hout, ts, hout, M, d->H, 4, st);
   }
   DGemmArgs up = {}; up.Yb = d->Xcat; up.ldy = d->I + d->H;      // (what k_linear's GELU and RESID epilogues read of `dec`)
   ETD_TRY(linear16(w.up, d->X2b, M, up, DEPI_GELU, st));
+  ETD_TRY(tap_xcat(d, ts, M, st));
   DGemmArgs dn = {}; dn.N = d->H; dn.hin = hin; dn.hout = hout;
-  return linear16(w.cat, d->Xcat, M, dn, DEPI_RESID, st);
+  ETD_TRY(linear16(w.cat, d->Xcat, M, dn, DEPI_RESID, st));
+  return tap_rows(d, d->taps.hout, ts, hout, M, d->H, 4, st);
 }
 // last layer, last positions only: every position's K/V is in the cache now; what remains of the layer is needed for
 // n rows, not M (attention, MLP up, (down | dense), residual = 9 % of the prefill's FLOPs at 8 layers) and runs on the skinny sequence's kernels.
 // gather rows -> k_ln_rows -> QKV | up -> attention -> split-K (down | dense) -> row kernel: hout rows 0 .. n-1 = the prompts' last positions, in prompt order
 static int prefill16_last_rows(etd_dec* d, const LastOnly& lo, const float* hin, float* hout, hipStream_t st) {
-  const int n = lo.n, l = d->L - 1;
+  const int n = lo.n, l = d->L - 1, ts = tap_slice(d, l, true);
   ETD_TRY(launch_gather_rows(hin, lo.idx, n, d->H, d->hlast, st));
   ETD_TRY(ln_rows16(d, l, d->hlast, n, st));
+  ETD_TRY(tap_layer_in(d, ts, d->hlast, n, st));
   ETD_TRY(step_qkv_up(d, l, d->hlast, lo.rows, n, st));
+  ETD_TRY(tap_rows(d, d->taps.q, ts, d->Q, n, d->H, 4, st));
   DAttnArgs at = attn_args(d, l, lo.rows, n); at.O = d->AO; at.Ob = d->Xcat + d->I; at.ldob = d->I + d->H; at.bytes_hint = 0;
   ETD_TRY(launch_dattn(at, d->bf16w, st));
-  return down_splitk(d, l, d->hlast, hout, n, NextLn{}, st);
+  ETD_TRY(tap_xcat(d, ts, n, st));
+  return down_splitk(d, l, d->hlast, hout, n, NextLn{}, st, ts);
 }
 static int forward_prefill16(etd_dec* d, int M, const DecRows& rows, const PrefillInfo* pf, const LastOnly* lo, hipStream_t st, float** hfinal, bool* compact) {
   // batched prefill on the fused MLP kernel: it also writes the NEXT layer's LayerNorm rows, so only layer 0 needs the row kernel
@@ -469,7 +525,10 @@ static int forward_prefill16(etd_dec* d, int M, const DecRows& rows, const Prefi
   float* hin = d->h; float* hout = d->h2;
   for (int l = 0; l < d->L; ++l) {
     if (l == 0 || !fmlp) ETD_TRY(ln_rows16(d, l, hin, M, st));
+    const int ts = tap_slice(d, l);
+    ETD_TRY(tap_layer_in(d, ts, hin, M, st));
     ETD_TRY(prefill16_qkv(d, l, hin, rows, M, pf != nullptr, st));
+    ETD_TRY(pf ? tap_rows(d, d->taps.qb, ts, d->Qb, M, d->H, 2, st) : tap_rows(d, d->taps.q, ts, d->Q, M, d->H, 4, st));
     ETD_TRY(tail && l == d->L - 1 ? prefill16_last_rows(d, *lo, hin, hout, st) : prefill16_layer_rest(d, l, rows, M, pf, fmlp, hin, hout, st));
     std::swap(hin, hout);
   }
@@ -548,6 +607,7 @@ int stage_and_forward(etd_dec* d, int n, const int32_t* slots, const int32_t* T,
   }
   if (Mtot > d->Mcap) ETD_FAIL(ETD_EINVAL, "prefill: %lld prompt rows exceed max_prefill_rows=%d", Mtot, d->Mcap);
   const int M = (int)Mtot;
+  ETD_TRY(taps_fit(d, M, DS_K_SPLITS, n > 1 && M > DS_MAX_ROWS));      // (a superset of forward_prefill16's `tail`)
   for (int i = 0; i < M; ++i) {
     if (ids[i] < 0 || ids[i] >= d->V || cls[i] < 0 || cls[i] >= d->cfg.num_classes) ETD_FAIL(ETD_EINVAL, "prefill: token/class id out of range at row %d", i);
     for (int k = 0; k < 4; ++k) if (attrs4[(size_t)k * M + i] < 0 || attrs4[(size_t)k * M + i] >= d->cfg.num_attribute_bins) ETD_FAIL(ETD_EINVAL, "prefill: attribute bin out of range at row %d", i);
@@ -1015,6 +1075,7 @@ extern "C" int etd_decoder_step(etd_dec* d, const int32_t* slots, int n_active, 
   hipStream_t st = (hipStream_t)stream;
   if (!d || !slots || n_active < 1 || n_active > d->S || n_steps < 1) ETD_FAIL(ETD_EINVAL, "decoder_step: bad args");
   for (int i = 0; i < n_active; ++i) ETD_TRY(check_slot(d, slots[i]));
+  ETD_TRY(taps_fit(d, n_active, std::max(d->I / 512 + d->nh, DS_K_SPLITS)));      // (before the slot list is uploaded: a tapped call that does not fit launches nothing)
   if ((int)d->last_slots.size() != n_active || memcmp(d->last_slots.data(), slots, (size_t)n_active * 4)) {
     d->last_slots.assign(slots, slots + n_active);
     HIP_TRY(hipMemcpyAsync(d->slots_dev, d->last_slots.data(), (size_t)n_active * 4, hipMemcpyHostToDevice, st));
@@ -1072,10 +1133,20 @@ extern "C" int etd_decoder_step(etd_dec* d, const int32_t* slots, int n_active, 
     ++eager_step;
     const DecRows rows{d->row_slot, d->row_pos, d->row_active};
     if (!fused) ETD_TRY(embed(s_));
+    if (fused && d->taps_on) {
+      if (d->taps.step_slot) HIP_TRY(hipMemcpyAsync(d->taps.step_slot, d->row_slot, (size_t)n_active * 4, hipMemcpyDeviceToDevice, s_));
+      if (d->taps.step_pos) HIP_TRY(hipMemcpyAsync(d->taps.step_pos, d->row_pos, (size_t)n_active * 4, hipMemcpyDeviceToDevice, s_));
+    }
     float* hf = nullptr;
     ETD_TRY(fused ? forward_skinny16(d, n_active, rows, true, s_, &hf) : forward_rows(d, n_active, rows, nullptr, nullptr, s_, &hf, nullptr));
     if (fused) {
       ETD_TRY(launch_dstep_head(head_args(d, hf, n_active, vpad), s_));
+      if (d->taps_on) {
+        ETD_TRY(tap_rows(d, d->taps.next_h, 0, d->h, n_active, d->H, 4, s_));
+        ETD_TRY(tap_rows(d, d->taps.next_ln1, 0, d->X1b, n_active, d->H, 2, s_));
+        ETD_TRY(tap_rows(d, d->taps.next_ln2, 0, d->X2b, n_active, d->H, 2, s_));
+        ETD_TRY(tap_rows(d, d->taps.next_pos, 0, d->row_pos, n_active, 1, 4, s_));
+      }
       if (d->trace) {
         ETD_TRY(trace_rows(d, d->h, d->H, d->H, 1, 0, n_active, ETD_TRACE_LAYER * d->L * n_active, s_));
         ETD_TRY(trace_rows(d, d->cur_tok, 1, 1, 1, 0, n_active, ETD_TRACE_LAYER * d->L * n_active + n_active, s_));
@@ -1515,6 +1586,36 @@ extern "C" int etd_debug_decoder_peek_kv(etd_dec* d, int layer, int slot, int he
   HIP_TRY(hipMemcpyAsync(k_out, (const char*)d->Kc + off, (size_t)n_pos * 128, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(v_out, (const char*)d->Vc + off, (size_t)n_pos * 128, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
+  return ETD_OK;
+}
+extern "C" int etd_debug_decoder_peek_kv_many(etd_dec* d, int layer, int n, const int32_t* slots, int n_pos, unsigned short* k_out, unsigned short* v_out, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!d || !d->bf16w || layer < 0 || layer >= d->L || n < 1 || !slots || n_pos < 1 || n_pos > d->ctx || !k_out || !v_out) ETD_FAIL(ETD_EINVAL, "peek_kv_many: bad args");
+  for (int i = 0; i < n; ++i) ETD_TRY(check_slot(d, slots[i]));
+  for (int i = 0; i < n; ++i) {
+    const size_t off = ((size_t)layer * d->layer_stride + (size_t)slots[i] * d->slot_stride) * 2, dst = (size_t)i * d->nh * n_pos * 64;
+    // [heads][max_ctx][64] -> [heads][n_pos][64]
+    HIP_TRY(hipMemcpy2DAsync(k_out + dst, (size_t)n_pos * 128, (const char*)d->Kc + off, (size_t)d->ctx * 128, (size_t)n_pos * 128, (size_t)d->nh, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpy2DAsync(v_out + dst, (size_t)n_pos * 128, (const char*)d->Vc + off, (size_t)d->ctx * 128, (size_t)n_pos * 128, (size_t)d->nh, hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  return ETD_OK;
+}
+extern "C" int etd_debug_decoder_stage_taps(etd_dec* d, const etd_debug_dec_taps* t, void* stream) {
+  if (!d || !d->bf16w) ETD_FAIL(ETD_EINVAL, "stage_taps: 16-bit handles only");
+  if (t) {
+    if (t->struct_bytes != (int)sizeof(etd_debug_dec_taps)) ETD_FAIL(ETD_EINVAL, "stage_taps: etd_debug_dec_taps of %d bytes, this library expects %d", t->struct_bytes, (int)sizeof(etd_debug_dec_taps));
+    if (d->L > 31 || t->layer_mask >> d->L) ETD_FAIL(ETD_EINVAL, "stage_taps: layer_mask %#x names a layer beyond the model's %d", t->layer_mask, d->L);
+    if (t->rows < 1 || t->hidden != d->H || t->intermediate != d->I || (t->slabs && t->slab_cap < 1))
+      ETD_FAIL(ETD_EINVAL, "stage_taps: buffers stated for rows %d, hidden %d, intermediate %d, slab_cap %d; the model has hidden %d, intermediate %d", t->rows, t->hidden, t->intermediate, t->slab_cap, d->H, d->I);
+    if (t->slices < __builtin_popcount(t->layer_mask)) ETD_FAIL(ETD_EINVAL, "stage_taps: layer_mask %#x needs %d slices, the buffers are stated to hold %d", t->layer_mask, __builtin_popcount(t->layer_mask), t->slices);
+    if (rowfin_on()) ETD_FAIL(ETD_EINVAL, "stage_taps: not with ETD_ROWFIN=1 (the in-launch row finish leaves no slabs to tap)");
+  }
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  for (auto& kv : d->graphs) (void)hipGraphExecDestroy(kv.second);       // captured steps hold the copies of the taps they were captured with, or none
+  d->graphs.clear();
+  d->taps_on = t != nullptr;
+  d->taps = t ? *t : etd_debug_dec_taps{};
   return ETD_OK;
 }
 extern "C" int etd_debug_decoder_trace_read(etd_dec* d, unsigned* out_host, long long cap_words, int n_active, int* steps_done, void* stream) {

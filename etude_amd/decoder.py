@@ -549,6 +549,30 @@ class EtudeDecoder:
             _lib.check(_lib.lib().etd_debug_decoder_bar_logits(self._h, out.ctypes.data, n, self._stream()), "etd_debug_decoder_bar_logits")
         return out
 
+    def debug_stage_taps(self, layer_mask: int = 0, rows: int = 0, slab_cap: int = 0, slices: int = 0, **bufs: torch.Tensor) -> None:
+        """Test hook (etd_debug_decoder_stage_taps): register device tensors as the destinations of the 16-bit sequences' stage outputs, named as the members of
+        etd_debug_dec_taps and shaped [slices, rows, width] (include/etude_hip_debug.h); no tensors = taps off.  The caller keeps the tensors alive."""
+        with torch.cuda.device(self.device):
+            if not bufs:
+                _lib.check(_lib.lib().etd_debug_decoder_stage_taps(self._h, None, self._stream()), "etd_debug_decoder_stage_taps")
+                return
+            t = _lib.DecTaps(layer_mask=layer_mask, rows=rows, hidden=self.config.hidden_size, intermediate=self.config.intermediate_size, slab_cap=slab_cap, slices=slices)
+            for k, v in bufs.items():
+                if k not in _lib.DecTaps.PTRS or not (v.is_cuda and v.is_contiguous()):
+                    raise ValueError(f"debug_stage_taps: {k} must name a tap and be a contiguous device tensor")
+                setattr(t, k, v.data_ptr())
+            _lib.check(_lib.lib().etd_debug_decoder_stage_taps(self._h, C.byref(t), self._stream()), "etd_debug_decoder_stage_taps")
+
+    def debug_peek_kv(self, layer: int, slots, n_pos: int):
+        """Test hook: (K, V) cache rows of one layer for the listed slots, positions 0 .. n_pos - 1, all heads: two [n, heads, n_pos, 64] tensors of the operand type."""
+        sl = np.ascontiguousarray(slots, np.int32)
+        shape = (len(sl), self.config.num_attention_heads, n_pos, 64)
+        k, v = np.zeros(shape, np.uint16), np.zeros(shape, np.uint16)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().etd_debug_decoder_peek_kv_many(self._h, layer, len(sl), sl.ctypes.data, n_pos, k.ctypes.data, v.ctypes.data, self._stream()),
+                       "etd_debug_decoder_peek_kv_many")
+        return tuple(torch.from_numpy(x.view(np.int16)).view(self.operand_dtype) for x in (k, v))
+
     def close(self):
         if getattr(self, "_h", None):
             _lib.lib().etd_decoder_destroy(self._h)

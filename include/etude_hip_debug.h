@@ -65,6 +65,35 @@ int etd_debug_decoder_step_logits(etd_dec*, int on, float* out_host, int n_activ
 /* test hook: the last-position logits [n][vocab] fp32 that the latest etd_decoder_begin_bars chose its n first tokens from (row i = the
  * call's i-th stream).  Valid until the next begin_bars, prefill or unfused decode step. */
 int etd_debug_decoder_bar_logits(etd_dec*, float* out_host, int n, void* stream);
+/* test hook (tests/test_gpu_decoder_stages.py): float taps of every stage of the 16-bit sequences (fused decode step, skinny sequence, batched prefill and
+ * its last-rows tail).  While registered, each launch's output is copied (hipMemcpyAsync, device to device, right behind the launch) into the caller's DEVICE
+ * buffers; a NULL member is off, etd_debug_decoder_stage_taps(d, NULL, ..) switches everything off.  Only layers in `layer_mask` are tapped; layer l's slice of a
+ * buffer is slice popcount(layer_mask & ((1 << l) - 1)), and ONE MORE slice behind them belongs to the last-rows tail of a batched prefill (the last layer on the
+ * prompts' last rows only, when that layer is in the mask).  Every buffer is [slices][rows][width] of the stated type; a call of M rows fills rows 0 .. M - 1 of
+ * a slice (the tail: 0 .. n - 1).  `slabs` is [slices][slab_cap * rows * hidden] floats and receives the launch's split-K slabs as [n_slab][M][hidden], contiguous
+ * (fused step: intermediate / 512 down slabs, then one dense slab per head; split-K down projection: 5).  In a multi-step call the last step's taps stay.
+ * The sizes the caller states (rows, slices, hidden, intermediate, slab_cap) are checked against every call BEFORE anything is launched: a call that does not fit is
+ * ETD_EINVAL.  Registering or clearing taps drops the captured step graphs, so a tapped step never replays a production graph and the reverse. */
+typedef struct etd_debug_dec_taps {
+  int struct_bytes;                   /* sizeof(etd_debug_dec_taps) of the caller */
+  unsigned layer_mask;
+  int rows, hidden, intermediate, slab_cap;
+  int slices;                         /* slices every buffer holds: a call that would write more (layers in the mask, + 1 for a batched prefill's tail) is ETD_EINVAL */
+  float* hin;                         /* fp32 [slices][rows][hidden]: residual stream entering the layer */
+  void *ln1, *ln2;                    /* 16-bit [slices][rows][hidden]: the layer's two LayerNorm rows (X1b, X2b) */
+  float* q;                           /* fp32 [slices][rows][hidden]: RoPE'd queries (step, skinny sequence, tail) */
+  void* qb;                           /* 16-bit [slices][rows][hidden]: RoPE'd queries of the batched prefill */
+  void* xcat;                         /* 16-bit [slices][rows][intermediate + hidden]: GELU(up) | attention output as the layer left it (the fused step writes no
+                                         attention block, the fused prefill MLP no GELU block: those columns are stale) */
+  float* slabs;                       /* fp32, see above */
+  float* hout;                        /* fp32 [slices][rows][hidden]: residual stream leaving the layer */
+  int32_t *step_slot, *step_pos;      /* int32 [rows]: the fused step's row -> (slot, position) as its layers read them */
+  float* next_h; void *next_ln1, *next_ln2; int32_t* next_pos;      /* fused step's head kernel: next step's embeddings fp32 [rows][hidden], layer-0 LayerNorm rows, positions */
+} etd_debug_dec_taps;
+int etd_debug_decoder_stage_taps(etd_dec*, const etd_debug_dec_taps* taps, void* stream);
+/* test hook: K and V cache rows of one layer, all heads: for each of n listed slots positions 0 .. n_pos - 1 -> k_out / v_out host [n][heads][n_pos][64] 16-bit patterns */
+int etd_debug_decoder_peek_kv_many(etd_dec*, int layer, int n, const int32_t* slots, int n_pos, unsigned short* k_out, unsigned short* v_out, void* stream);
+
 /* test hook (tests/test_gpu_sampling_exact.py): the sampler alone.  Token of each of M rows of V <= 256 device logits (row stride ld >= V) drawn by
  * the decoder's own sampling routine with per-row keys and draw counters (device arrays); temperature > 0.  No decoder state is involved. */
 int etd_debug_sample_rows(const float* logits_dev, int M, int V, int ld, float temperature, float top_p, unsigned long long seed,

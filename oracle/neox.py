@@ -105,7 +105,7 @@ def transformer(sd, h, d: NeoxDims, kv: Optional[List[Tuple[torch.Tensor, torch.
         ctx = k.shape[2]
         mask = torch.arange(ctx)[None, :] > (torch.arange(T)[:, None] + past)
         w = w.masked_fill(mask[None, None], float("-inf"))
-        w = torch.softmax(w, dim=-1, dtype=torch.float32)
+        w = torch.softmax(w, dim=-1, dtype=torch.promote_types(w.dtype, torch.float32))      # fp32 as HF does; a float64 state dict stays float64
         a = torch.matmul(w, v).transpose(1, 2).reshape(B, T, H)
         a = F.linear(a, sd[p + "attention.dense.weight"], sd[p + "attention.dense.bias"])
         x2 = F.layer_norm(h, (H,), sd[p + "post_attention_layernorm.weight"], sd[p + "post_attention_layernorm.bias"], d.layer_norm_eps)

@@ -14,7 +14,10 @@ on real embedded frames of a synthetic window and rounds to bf16 exactly where c
 Prints rms(err) / rms(ref) and max|err| of the layer output per site.  usage: python tools/diag_rounding_budget.py [n_frames=16]
 
 `python tools/diag_rounding_budget.py stages [n_frames=8]` prints instead what every layer costs in IEEE half from its exact 16-bit input, against float64.
-The rounding sites are those of tests/hft_stage_ref.py: this script and the GPU stage tests share one emulation."""
+The rounding sites are those of tests/hft_stage_ref.py: this script and the GPU stage tests share one emulation.
+
+`python tools/diag_rounding_budget.py decoder-stages [tokens=65]` does the same for the 16-bit decoder, per layer and stage, with the sites of
+tests/dec_stage_ref.py (the budget tests/test_gpu_decoder_stages.py holds the device to), for both synthetic weight sets."""
 import sys
 from pathlib import Path
 
@@ -62,8 +65,63 @@ def stage_table(nfr):
         print(f"{pfx:36s}  {bm:.1e} / {br:.1e}         {cm:.1e} / {cr:.1e}         {min(bt, ct):.1f} - {max(bt, ct):.1f}")
 
 
+def decoder_stage_table(T):
+    """Every decoder stage from its exact input (the float64 chain's own activations, rounded where the device hands the stage a 16-bit tensor), all sites of
+    the batched prefill on: E_max / E_rms per layer."""
+    from tests import dec_stage_ref as sr
+    from tests._util import neox_dims
+    d = neox_dims({})
+    ids, cls, a4 = (torch.from_numpy(np.ascontiguousarray(v).astype(np.int64)) for v in sr.prompts(sr.PROMPT_SEED, [T])[0])
+    kw = dict(sites=sr.ALL_SITES, dtype=torch.float16)
+    half = lambda v: v.half().double()      # noqa: E731
+    e = lambda emu, ref: f"{float((emu - ref).abs().max()):.1e} / {float((emu - ref).pow(2).mean().sqrt()):.1e}"      # noqa: E731
+    for weights in ("bench", "ctx"):
+        sd = {k: v.double() for k, v in sr.state_dict(weights).items()}
+        print(f"{weights} weights, one prompt of {T} tokens, IEEE-half sites {' '.join(sorted(sr.ALL_SITES))}: E_max / E_rms per stage from its exact input")
+        print("prefill sites (Qb, P; k_pattn, k_dmlp_fused) | step sites (fp32 Q, k_dattn / k_dstep_attn_down, split-K slabs)")
+        print("layer  ln                   qkv Q                K append             V append             attn                 mlp hout           | "
+              "step Q               up GELU              step attn            dense slabs          down slabs")
+        h, pos = sr.embed(sd, ids, cls, a4), torch.arange(T)
+        for l in range(d.num_hidden_layers):
+            x1, x2 = sr.layer_norms(sd, l, h, d.layer_norm_eps)
+            ln = e(torch.cat(sr.layer_norms(sd, l, h, d.layer_norm_eps, **kw), 1), torch.cat([x1, x2], 1))
+            x1, x2 = half(x1), half(x2)
+            q, k, v = sr.qkv(sd, l, x1, pos, d.num_attention_heads)
+            qe, ke, ve = sr.qkv(sd, l, x1, pos, d.num_attention_heads, q_site="Qb", **kw)
+            q32 = q
+            q, K, V = half(q), half(k).transpose(0, 1), half(v).transpose(0, 1)
+            nk = list(range(1, T + 1))
+            o = sr.attention(q, K, V, nk)
+            oe = sr.attention(q, K, V, nk, p_site="P", **kw)
+            o16 = half(o)
+            hout = sr.mlp_resid(sd, l, x2, o16, h)
+            # the step's / skinny sequence's stages (STEP_SITES) from the same exact inputs: fp32 queries, GELU(up), attention with fp32 numerators, the per-head
+            # dense slabs and the split-K slabs of the (down | dense) projection
+            skw = dict(sites=sr.STEP_SITES, dtype=torch.float16)
+            nh = d.num_attention_heads
+            g = sr.gelu_up(sd, l, x2)
+            os_ = sr.attention(q32, K, V, nk)
+            xcat = torch.cat([half(g), half(os_)], 1)
+            step = (e(sr.qkv(sd, l, x1, pos, nh, **skw)[0], q32), e(sr.gelu_up(sd, l, x2, **skw), g), e(sr.attention(q32, K, V, nk, **skw), os_),
+                    e(sr.dense_slabs(sd, l, sr.attention(q32, K, V, nk, **skw), nh, **skw), sr.dense_slabs(sd, l, os_, nh)),
+                    e(sr.down_slabs(sd, l, xcat, 5, **skw), sr.down_slabs(sd, l, xcat, 5)))
+            print(f"{l:5d}  {ln:19s}  {e(qe, q):19s}  {e(ke, k):19s}  {e(ve, v):19s}  {e(oe, o):19s}  {e(sr.mlp_resid(sd, l, x2, o16, h, **kw), hout):19s}| " +
+                  "  ".join(f"{x:19s}" for x in step))
+            h = hout
+        ref = sr.head_logits(sd, h, d.layer_norm_eps)
+        print(f"head logits {e(sr.head_logits(sd, h, d.layer_norm_eps, **kw), ref)} (max |logit| {float(ref.abs().max()):.1f})")
+        tok = ref.argmax(-1)
+        nh_ = sr.next_embed(sd, tok, torch.tensor(sr.TGT_ATTRS)[:, None].expand(4, T))
+        print(f"head next ln {e(torch.cat(sr.layer_norms(sd, 0, nh_, d.layer_norm_eps, **kw), 1), torch.cat(sr.layer_norms(sd, 0, nh_, d.layer_norm_eps), 1))}"
+              " (slab sum + bias + residual and the next embedding have no 16-bit site: E = 0, held to n 2^-24 sum |terms|)")
+
+
 def main():
     torch.set_num_threads(8)
+    if len(sys.argv) > 1 and sys.argv[1] == "decoder-stages":
+        with torch.no_grad():
+            decoder_stage_table(int(sys.argv[2]) if len(sys.argv) > 2 else 65)
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "stages":
         with torch.no_grad():
             stage_table(int(sys.argv[2]) if len(sys.argv) > 2 else 8)
