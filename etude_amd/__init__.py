@@ -10,6 +10,7 @@ Drop-in surfaces (same names/signatures as the reference):
     etude_amd.BeatDetector          <- etude.data.beat_detector.BeatDetector (the Beat-Transformer model; tracker="native" decodes with the library's own DBN)
     etude_amd.DBNBeatTracker / DBNDownBeatTracker  <- madmom's DBNBeatTrackingProcessor / DBNDownBeatTrackingProcessor (csrc/dbn.hip)
     etude_amd.StemFeatures          <- process_stems_to_spectrogram of scripts/run_separation.py (stems -> mel-dB features; csrc/stemfeat.hip)
+    etude_amd.AlignFeatures         <- the feature extraction in front of the aligner (synctoolbox's pitch filterbank, chroma, DLNCO; csrc/alignfeat.hip)
     etude_amd.AudioAligner          <- etude.data.aligner.AudioAligner behind the feature extraction (exact DTW, transposition search, wp.json cache; csrc/dtw.hip)
     etude_amd.WPDCalculator         <- etude.evaluation.metrics.wpd.WPDCalculator (host arithmetic on the warping path)
     etude_amd.BeatAnalyzer          <- etude.data.beat_analyzer.BeatAnalyzer (beat_pred.json -> tempo.json; host Python)
@@ -28,7 +29,7 @@ __all__ = ["AMTAPC_Extractor", "EtudeDecoder", "EtudeDecoderConfig", "load_etude
            "ExtractorConfig", "DecoderConfig", "HFT_Transformer", "HFTConfig", "TinyREMITokenizer", "run_engines",
            "BeatDetector", "BeatDetectorConfig", "BeatDetectorModelConfig", "DBNBeatTracker", "DBNDownBeatTracker", "BeatAnalyzer", "structuralize_many",
            "structuralize_stems_many", "StemFeatures", "mel_filterbank", "AudioAligner", "align_features", "align_features_many", "align_and_filter_many",
-           "WPDCalculator", "wpd_many"]
+           "WPDCalculator", "wpd_many", "AlignFeatures", "ellip_bandpass_sos", "pitch_filterbank", "align_audio_many", "align_and_filter_audio_many"]
 
 
 def __getattr__(name):
@@ -56,7 +57,10 @@ def __getattr__(name):
     if name in ("StemFeatures", "mel_filterbank"):
         from . import stemfeat
         return getattr(stemfeat, name)
-    if name in ("AudioAligner", "align_features", "align_features_many", "align_and_filter_many"):
+    if name in ("AlignFeatures", "ellip_bandpass_sos", "pitch_filterbank"):
+        from . import alignfeat
+        return getattr(alignfeat, name)
+    if name in ("AudioAligner", "align_features", "align_features_many", "align_and_filter_many", "align_audio_many", "align_and_filter_audio_many"):
         from . import aligner
         return getattr(aligner, name)
     if name in ("WPDCalculator", "wpd_many"):

@@ -72,6 +72,15 @@ class DtwCfg(_SizedCfg):
                 ("shift_weights", C.c_double * 3), ("alpha", C.c_float), ("norm_threshold", C.c_float)]
 
 
+class AlignFeatCfg(_SizedCfg):
+    _fields_ = [("struct_bytes", C.c_int)] + [(n, C.c_int) for n in ("sample_rate", "hop", "fir_taps", "decimation", "chunk", "n_banks", "reserved")]
+
+
+# etd_alignfeat_debug_layout's int64 [24] (include/etude_hip_debug.h), in order
+ALIGNFEAT_LAYOUT = ("T", "n0", "n1", "n2", "nc0", "nc1", "nc2", "nm0", "nm1", "nm2", "off_x1", "off_x2", "off_u", "off_y", "off_st", "off_E", "off_nov", "off_ph",
+                    "off_pf", "off_L", "off_g", "off_G", "off_D", "out_off")
+
+
 class G3Case(_SizedCfg):
     """etd_debug_g3_case of include/etude_hip_debug.h: one k_gemm3 / k_gemm3_s launch with any epilogue, strides and row metadata"""
     _fields_ = [("struct_bytes", C.c_int), ("kernel", C.c_int), ("epi", C.c_int)] + [(n, C.c_int) for n in ("M", "N", "K", "ldx", "ldy")] + \
@@ -245,6 +254,13 @@ SIGNATURES = {
     "etd_dtw_debug_cost": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_longlong, C.c_longlong, C.c_int, C.c_void_p]),
     "etd_dtw_debug_path": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_longlong, C.c_longlong, C.c_int, C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong)]),
     "etd_dtw_debug_total": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_longlong, C.c_longlong, C.c_int, C.POINTER(C.c_double)]),
+    "etd_alignfeat_limits": (C.c_int, [c_int_p, c_int_p, C.POINTER(C.c_longlong), c_int_p, c_int_p]),
+    "etd_alignfeat_create": (C.c_int, [C.POINTER(AlignFeatCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "etd_alignfeat_destroy": (None, [C.c_void_p]),
+    "etd_alignfeat_num_frames": (C.c_longlong, [C.c_void_p, C.c_longlong]),
+    "etd_alignfeat_workspace_bytes": (C.c_longlong, [C.c_void_p, C.c_int, c_i64_p]),
+    "etd_alignfeat_run": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, c_i64_p, c_i32_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "etd_alignfeat_debug_layout": (C.c_int, [C.c_void_p, C.c_int, c_i64_p, C.c_int, c_i64_p, C.c_int]),
     "etd_debug_decoder_trace_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.POINTER(C.c_int), C.c_void_p]),
 }
 

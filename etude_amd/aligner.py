@@ -198,6 +198,25 @@ def align_features(cover_feats: Feats, origin_feats: Feats, device="cuda") -> Di
     return align_features_many([(cover_feats, origin_feats)], device)[0]
 
 
+def align_audio_many(pairs_of_wavs: Sequence[Tuple], tuning_offsets: Optional[Sequence[Tuple[float, float]]] = None, device="cuda", features=None) -> List[Dict]:
+    """From audio: pairs of (cover samples, origin samples), mono at 22 050 Hz (arrays or tensors) -> the result dicts of ``align_features_many``.  The features of
+    both sides of every pair come from ONE ``AlignFeatures.features_many`` call (csrc/alignfeat.hip), then one ragged DTW call.  tuning_offsets: per pair
+    (cover cents, origin cents), default 0 (``estimate_tuning`` is the caller's).  features: an ``AlignFeatures`` to use (default: one per device, made once)."""
+    if len(pairs_of_wavs) == 0:
+        return []
+    if tuning_offsets is not None and len(tuning_offsets) != len(pairs_of_wavs):
+        raise ValueError(f"align_audio_many: {len(pairs_of_wavs)} pairs but {len(tuning_offsets)} tuning offset pairs")
+    if features is None:
+        from .alignfeat import default_align_features
+        features = default_align_features(device)
+    wavs = [w for pair in pairs_of_wavs for w in pair]
+    if len(wavs) != 2 * len(pairs_of_wavs):
+        raise ValueError("align_audio_many: every pair is (cover samples, origin samples)")
+    tun = None if tuning_offsets is None else [float(t) for pair in tuning_offsets for t in pair]
+    feats = features.features_many(wavs, tun)
+    return align_features_many([(feats[2 * i], feats[2 * i + 1]) for i in range(len(pairs_of_wavs))], device)
+
+
 class AudioAligner:
     """etude.data.aligner.AudioAligner: same attributes, same cache-first ``align`` and the same rich ``wp.json`` format.  ``feature_fn(path) -> (quantized chroma,
     DLNCO)`` supplies what the reference's ``_get_features`` computes; without it a cache miss is a logged None."""
@@ -233,6 +252,9 @@ class AudioAligner:
 
     def align_features_many(self, pairs: Sequence[Tuple[Feats, Feats]]) -> List[Dict]:
         return align_features_many(pairs, self.device)
+
+    def align_audio_many(self, pairs_of_wavs: Sequence[Tuple], tuning_offsets: Optional[Sequence[Tuple[float, float]]] = None, features=None) -> List[Dict]:
+        return align_audio_many(pairs_of_wavs, tuning_offsets, self.device, features)
 
     def _load_from_cache(self, song_dir, version_key: str) -> Optional[Dict]:
         path = Path(song_dir) / "wp.json"
@@ -294,4 +316,14 @@ def align_and_filter_many(aligner: AudioAligner, pairs: Sequence[Tuple[Feats, Fe
     if not (len(pairs) == len(downbeats_list) == len(notes_list)):
         raise ValueError("align_and_filter_many: pairs, downbeats_list and notes_list differ in length")
     results = aligner.align_features_many(pairs)
+    return filter_and_weakly_align(results, downbeats_list, notes_list, wp_std_threshold, names, aligner.feature_rate)
+
+
+def align_and_filter_audio_many(aligner: AudioAligner, pairs_of_wavs: Sequence[Tuple], downbeats_list: Sequence[Sequence[float]], notes_list: Sequence[List[Dict]],
+                                wp_std_threshold: float, names: Optional[Sequence[str]] = None, tuning_offsets: Optional[Sequence[Tuple[float, float]]] = None,
+                                features=None) -> Tuple[List[Optional[List[Dict]]], List[Dict]]:
+    """``align_and_filter_many`` from audio: pairs of (cover samples, origin samples) as for ``align_audio_many``."""
+    if not (len(pairs_of_wavs) == len(downbeats_list) == len(notes_list)):
+        raise ValueError("align_and_filter_audio_many: pairs_of_wavs, downbeats_list and notes_list differ in length")
+    results = aligner.align_audio_many(pairs_of_wavs, tuning_offsets, features)
     return filter_and_weakly_align(results, downbeats_list, notes_list, wp_std_threshold, names, aligner.feature_rate)

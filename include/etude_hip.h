@@ -452,6 +452,44 @@ long long etd_dtw_workspace_bytes(const etd_dtw*, int n_pairs, const int64_t* N1
 int etd_dtw_align(etd_dtw*, const float* const* feat_ptrs, int n_pairs, const int64_t* N1_host, const int64_t* N2_host, void* workspace_dev, long long workspace_bytes,
                   int32_t* result_dev, long long result_ints, int32_t* result_host, void* stream);
 
+/* ------------------------------------------------------------------ alignment features (mono audio at 22 050 Hz -> quantised chroma + DLNCO, the input of etd_dtw_align)
+ * The feature extraction in front of the DTW, modelled on synctoolbox's published pipeline (audio_to_pitch_features, pitch_to_chroma, quantize_chroma,
+ * audio_to_pitch_onset_features, pitch_onset_features_to_DLNCO): rate tiers 22 050 / 4 410 / 882 Hz, 88 zero-phase elliptic band-passes (pitches 21 .. 108, an fp64
+ * recurrence whose time axis is split exactly into chunks), pitch energy, chroma, onset novelty, peaks, DLNCO.  DESIGN.md 4f is the contract (parity with synctoolbox
+ * itself is unpinned); estimate_tuning and decoding audio stay the caller's. */
+typedef struct etd_alignfeat etd_alignfeat;
+typedef struct {
+  int struct_bytes;          /* sizeof(etd_alignfeat_cfg) of the caller: a mismatch is ETD_EINVAL */
+  int sample_rate;           /* 22050 */
+  int hop;                   /* 441: samples per feature frame (50 Hz) */
+  int fir_taps;              /* 481: taps of the decimation filter */
+  int decimation;            /* 5: between two tiers */
+  int chunk;                 /* samples per chunk of the filter's time axis: must equal etd_alignfeat_limits' (apow_host holds that power) */
+  int n_banks;               /* filterbanks (one per tuning offset) in the tables below, 1 .. 64 */
+  int reserved;              /* 0 */
+} etd_alignfeat_cfg;
+/* HOST ONLY: the constants of this build: samples per chunk, sections per band, samples per song, songs per call, filterbanks per handle (any may be NULL) */
+int etd_alignfeat_limits(int* chunk, int* max_sections, long long* max_samples, int* max_songs, int* max_banks);
+/* Tables from the host layer, all host memory: fir_host [481] fp32 (the decimation filter, sum 1); sos_host [n_banks][88][6][6] fp64, band b = pitch 21 + b, section
+ * k = (b0, b1, b2, 1, a1, a2) (scipy's layout; sections >= n_sections[b] are ignored); n_sections [n_banks][88], 1 .. 6; apow_host [n_banks][88][12][12] fp64: the
+ * `chunk`-th power of the cascade's one-step state matrix (state = z0, z1 of section 0, of section 1, ...; transposed direct form II), zero outside the used block.
+ * More than 6 sections, a non-finite value, a0 != 1, a pole on or outside the unit circle or a bad config is ETD_EINVAL with a message.  Needs no GPU: the tables go to
+ * the device with the first etd_alignfeat_run. */
+int etd_alignfeat_create(const etd_alignfeat_cfg* cfg, const float* fir_host, const double* sos_host, const int32_t* n_sections, const double* apow_host,
+                         etd_alignfeat** out);
+void etd_alignfeat_destroy(etd_alignfeat*);
+/* HOST ONLY: feature frames of a song of N >= 1 samples, ceil(N / 441) (negative = ETD_EINVAL) */
+long long etd_alignfeat_num_frames(const etd_alignfeat*, long long N);
+/* HOST ONLY: bytes of device workspace a call with these songs needs (formula in DESIGN.md 4f; about 12.5 bytes per band sample, 1.1 GB for three minutes);
+ * negative = ETD_EINVAL: n_songs outside 1 .. 4096, N < 1 or N above the limit */
+long long etd_alignfeat_workspace_bytes(const etd_alignfeat*, int n_songs, const int64_t* N_host);
+/* wav_ptrs: HOST array of n_songs DEVICE pointers, song s = N_host[s] mono fp32 samples, finite (the caller checks); bank_host [n_songs]: the filterbank (tuning) of
+ * each song.  chroma_dev / dlnco_dev: the songs' [12][T_s] fp32 blocks back to back.  workspace_dev: 256-byte aligned device memory of workspace_bytes >=
+ * etd_alignfeat_workspace_bytes (too small is ETD_EINVAL); afterwards it holds every intermediate stage (etd_alignfeat_debug_layout).  A song's features depend on its
+ * samples and its filterbank alone: bit-identical alone, in any batch and in any order.  Synchronises `stream` once at the start (song table upload). */
+int etd_alignfeat_run(etd_alignfeat*, const float* const* wav_ptrs, int n_songs, const int64_t* N_host, const int32_t* bank_host, float* chroma_dev, float* dlnco_dev,
+                      void* workspace_dev, long long workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

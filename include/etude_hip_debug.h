@@ -160,6 +160,14 @@ int etd_dtw_debug_total(etd_dtw*, const float* const* feat_ptrs, long long N1, l
 /* ... and its unfiltered step path, LAST point first: path_host int32 [cap][2] of (cover frame, origin frame), *n_out = points (<= N1 + N2 - 1); ETD_ENOMEM when cap is short */
 int etd_dtw_debug_path(etd_dtw*, const float* const* feat_ptrs, long long N1, long long N2, int shift, int32_t* path_host, long long cap, long long* n_out);
 
+/* HOST ONLY test hook: the stage taps of etd_alignfeat_run.  After a run the caller's workspace holds every intermediate stage of every song; this returns where song
+ * `song` of a call with these lengths keeps them: out int64 [24] =
+ *   [0] T  [1..3] samples of tiers 0, 1, 2  [4..6] chunks  [7..9] novelty frames  then BYTE offsets into the workspace: [10] x1 fp32  [11] x2 fp32
+ *   [12] u fp64 (forward-filtered bands)  [13] y fp32 (zero-phase bands)  [14] chunk states fp64 [.][12]  [15] E fp32 [88][T]  [16] novelty fp32  [17] peak height fp32
+ *   (0 = no peak)  [18] peak frame int32  [19] L = log(1 + 10000 CO) fp32 [12][T]  [20] g  [21] G fp32 [T]  [22] D fp32 [12][T];  [23] floats before the song's block
+ *   in chroma_dev / dlnco_dev.  Per-band arrays hold bands 0 .. 87 in order, bands 0 .. 38 with tier 2's count, 39 .. 74 with tier 1's, 75 .. 87 with tier 0's. */
+int etd_alignfeat_debug_layout(const etd_alignfeat*, int n_songs, const int64_t* N_host, int song, int64_t* out, int n_out);
+
 #ifdef __cplusplus
 }
 #endif
