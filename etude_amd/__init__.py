@@ -11,6 +11,7 @@ Drop-in surfaces (same names/signatures as the reference):
     etude_amd.DBNBeatTracker / DBNDownBeatTracker  <- madmom's DBNBeatTrackingProcessor / DBNDownBeatTrackingProcessor (csrc/dbn.hip)
     etude_amd.StemFeatures          <- process_stems_to_spectrogram of scripts/run_separation.py (stems -> mel-dB features; csrc/stemfeat.hip)
     etude_amd.AlignFeatures         <- the feature extraction in front of the aligner (synctoolbox's pitch filterbank, chroma, DLNCO; csrc/alignfeat.hip)
+    etude_amd.TuningEstimator / estimate_tuning  <- synctoolbox's estimate_tuning, the first call of AudioAligner._compute_alignment (csrc/tuning.hip)
     etude_amd.AudioAligner          <- etude.data.aligner.AudioAligner behind the feature extraction (exact DTW, transposition search, wp.json cache; csrc/dtw.hip)
     etude_amd.WPDCalculator         <- etude.evaluation.metrics.wpd.WPDCalculator (host arithmetic on the warping path)
     etude_amd.BeatAnalyzer          <- etude.data.beat_analyzer.BeatAnalyzer (beat_pred.json -> tempo.json; host Python)
@@ -29,7 +30,8 @@ __all__ = ["AMTAPC_Extractor", "EtudeDecoder", "EtudeDecoderConfig", "load_etude
            "ExtractorConfig", "DecoderConfig", "HFT_Transformer", "HFTConfig", "TinyREMITokenizer", "run_engines",
            "BeatDetector", "BeatDetectorConfig", "BeatDetectorModelConfig", "DBNBeatTracker", "DBNDownBeatTracker", "BeatAnalyzer", "structuralize_many",
            "structuralize_stems_many", "StemFeatures", "mel_filterbank", "AudioAligner", "align_features", "align_features_many", "align_and_filter_many",
-           "WPDCalculator", "wpd_many", "AlignFeatures", "ellip_bandpass_sos", "pitch_filterbank", "align_audio_many", "align_and_filter_audio_many"]
+           "WPDCalculator", "wpd_many", "AlignFeatures", "ellip_bandpass_sos", "pitch_filterbank", "align_audio_many", "align_and_filter_audio_many",
+           "TuningEstimator", "estimate_tuning"]
 
 
 def __getattr__(name):
@@ -60,6 +62,9 @@ def __getattr__(name):
     if name in ("AlignFeatures", "ellip_bandpass_sos", "pitch_filterbank"):
         from . import alignfeat
         return getattr(alignfeat, name)
+    if name in ("TuningEstimator", "estimate_tuning"):
+        from . import tuning
+        return getattr(tuning, name)
     if name in ("AudioAligner", "align_features", "align_features_many", "align_and_filter_many", "align_audio_many", "align_and_filter_audio_many"):
         from . import aligner
         return getattr(aligner, name)

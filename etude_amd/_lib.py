@@ -76,6 +76,13 @@ class AlignFeatCfg(_SizedCfg):
     _fields_ = [("struct_bytes", C.c_int)] + [(n, C.c_int) for n in ("sample_rate", "hop", "fir_taps", "decimation", "chunk", "n_banks", "reserved")]
 
 
+class TuningCfg(_SizedCfg):
+    _fields_ = [("struct_bytes", C.c_int)] + [(n, C.c_int) for n in ("sample_rate", "n_fft", "hop")]
+
+
+# etd_tuning_debug_layout's int64 [7] (include/etude_hip_debug.h), in order
+TUNING_LAYOUT = ("F", "G", "off_part", "off_Y", "off_Yi", "off_R", "off_sim")
+
 # etd_alignfeat_debug_layout's int64 [24] (include/etude_hip_debug.h), in order
 ALIGNFEAT_LAYOUT = ("T", "n0", "n1", "n2", "nc0", "nc1", "nc2", "nm0", "nm1", "nm2", "off_x1", "off_x2", "off_u", "off_y", "off_st", "off_E", "off_nov", "off_ph",
                     "off_pf", "off_L", "off_g", "off_G", "off_D", "out_off")
@@ -261,6 +268,13 @@ SIGNATURES = {
     "etd_alignfeat_workspace_bytes": (C.c_longlong, [C.c_void_p, C.c_int, c_i64_p]),
     "etd_alignfeat_run": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, c_i64_p, c_i32_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
     "etd_alignfeat_debug_layout": (C.c_int, [C.c_void_p, C.c_int, c_i64_p, C.c_int, c_i64_p, C.c_int]),
+    "etd_tuning_limits": (C.c_int, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), c_int_p]),
+    "etd_tuning_create": (C.c_int, [C.POINTER(TuningCfg), C.POINTER(C.c_void_p)]),
+    "etd_tuning_destroy": (None, [C.c_void_p]),
+    "etd_tuning_workspace_bytes": (C.c_longlong, [C.c_void_p, C.c_int, c_i64_p]),
+    "etd_tuning_run": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, c_i64_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "etd_tuning_debug_layout": (C.c_int, [C.c_void_p, C.c_int, c_i64_p, C.c_int, c_i64_p, C.c_int]),
+    "etd_tuning_debug_power": (C.c_int, [C.c_void_p, C.c_int, c_i32_p, C.c_int, C.c_void_p]),
     "etd_debug_decoder_trace_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.POINTER(C.c_int), C.c_void_p]),
 }
 

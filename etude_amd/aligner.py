@@ -4,8 +4,9 @@ The reference aligns a cover to its origin with synctoolbox: CENS features -> co
 a host needs) -> make_path_strictly_monotonic.  Here the exact full-resolution DTW runs in libetude_hip.so (csrc/dtw.hip, DESIGN.md 4e is the contract): one wave per
 pair for a ragged batch of pairs, the 12 transposition problems in a launch of their own, 2-bit backpointers, and one copy of O(N1 + N2) integers to the host per call.
 
-What stays the caller's is the feature extraction in front (estimate_tuning, audio_to_pitch_features, audio_to_pitch_onset_features, DLNCO: synctoolbox's multirate
-IIR filterbank): ``AudioAligner(feature_fn=...)`` takes it as a callable path -> (quantized chroma [12][N], DLNCO [12][N]); without one a cache miss returns None.
+The feature extraction in front (estimate_tuning, audio_to_pitch_features, audio_to_pitch_onset_features, DLNCO: synctoolbox's multirate IIR filterbank) enters
+``AudioAligner(feature_fn=...)`` as a callable path -> (quantized chroma [12][N], DLNCO [12][N]); without one a cache miss returns None.  The library's own is
+``AlignFeatures.as_feature_fn(load_fn, tuning_fn="estimate")`` (csrc/alignfeat.hip, csrc/tuning.hip); ``align_audio_many(pairs, "estimate")`` is the batch form.
 """
 from __future__ import annotations
 
@@ -198,13 +199,14 @@ def align_features(cover_feats: Feats, origin_feats: Feats, device="cuda") -> Di
     return align_features_many([(cover_feats, origin_feats)], device)[0]
 
 
-def align_audio_many(pairs_of_wavs: Sequence[Tuple], tuning_offsets: Optional[Sequence[Tuple[float, float]]] = None, device="cuda", features=None) -> List[Dict]:
+def align_audio_many(pairs_of_wavs: Sequence[Tuple], tuning_offsets: Union[None, str, Sequence[Tuple[float, float]]] = None, device="cuda", features=None) -> List[Dict]:
     """From audio: pairs of (cover samples, origin samples), mono at 22 050 Hz (arrays or tensors) -> the result dicts of ``align_features_many``.  The features of
     both sides of every pair come from ONE ``AlignFeatures.features_many`` call (csrc/alignfeat.hip), then one ragged DTW call.  tuning_offsets: per pair
-    (cover cents, origin cents), default 0 (``estimate_tuning`` is the caller's).  features: an ``AlignFeatures`` to use (default: one per device, made once)."""
+    (cover cents, origin cents), default 0; ``"estimate"`` estimates every side's on the device first (``etude_amd.tuning``, DESIGN.md 4g: the reference's two
+    ``estimate_tuning`` calls; every side then needs N >= 32 768).  features: an ``AlignFeatures`` to use (default: one per device, made once)."""
     if len(pairs_of_wavs) == 0:
         return []
-    if tuning_offsets is not None and len(tuning_offsets) != len(pairs_of_wavs):
+    if tuning_offsets is not None and not isinstance(tuning_offsets, str) and len(tuning_offsets) != len(pairs_of_wavs):
         raise ValueError(f"align_audio_many: {len(pairs_of_wavs)} pairs but {len(tuning_offsets)} tuning offset pairs")
     if features is None:
         from .alignfeat import default_align_features
@@ -212,7 +214,7 @@ def align_audio_many(pairs_of_wavs: Sequence[Tuple], tuning_offsets: Optional[Se
     wavs = [w for pair in pairs_of_wavs for w in pair]
     if len(wavs) != 2 * len(pairs_of_wavs):
         raise ValueError("align_audio_many: every pair is (cover samples, origin samples)")
-    tun = None if tuning_offsets is None else [float(t) for pair in tuning_offsets for t in pair]
+    tun = tuning_offsets if tuning_offsets is None or isinstance(tuning_offsets, str) else [float(t) for pair in tuning_offsets for t in pair]
     feats = features.features_many(wavs, tun)
     return align_features_many([(feats[2 * i], feats[2 * i + 1]) for i in range(len(pairs_of_wavs))], device)
 
@@ -253,7 +255,7 @@ class AudioAligner:
     def align_features_many(self, pairs: Sequence[Tuple[Feats, Feats]]) -> List[Dict]:
         return align_features_many(pairs, self.device)
 
-    def align_audio_many(self, pairs_of_wavs: Sequence[Tuple], tuning_offsets: Optional[Sequence[Tuple[float, float]]] = None, features=None) -> List[Dict]:
+    def align_audio_many(self, pairs_of_wavs: Sequence[Tuple], tuning_offsets: Union[None, str, Sequence[Tuple[float, float]]] = None, features=None) -> List[Dict]:
         return align_audio_many(pairs_of_wavs, tuning_offsets, self.device, features)
 
     def _load_from_cache(self, song_dir, version_key: str) -> Optional[Dict]:
@@ -320,9 +322,9 @@ def align_and_filter_many(aligner: AudioAligner, pairs: Sequence[Tuple[Feats, Fe
 
 
 def align_and_filter_audio_many(aligner: AudioAligner, pairs_of_wavs: Sequence[Tuple], downbeats_list: Sequence[Sequence[float]], notes_list: Sequence[List[Dict]],
-                                wp_std_threshold: float, names: Optional[Sequence[str]] = None, tuning_offsets: Optional[Sequence[Tuple[float, float]]] = None,
+                                wp_std_threshold: float, names: Optional[Sequence[str]] = None, tuning_offsets: Union[None, str, Sequence[Tuple[float, float]]] = None,
                                 features=None) -> Tuple[List[Optional[List[Dict]]], List[Dict]]:
-    """``align_and_filter_many`` from audio: pairs of (cover samples, origin samples) as for ``align_audio_many``."""
+    """``align_and_filter_many`` from audio: pairs of (cover samples, origin samples) and tuning_offsets (``"estimate"`` included) as for ``align_audio_many``."""
     if not (len(pairs_of_wavs) == len(downbeats_list) == len(notes_list)):
         raise ValueError("align_and_filter_audio_many: pairs_of_wavs, downbeats_list and notes_list differ in length")
     results = aligner.align_audio_many(pairs_of_wavs, tuning_offsets, features)

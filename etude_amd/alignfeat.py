@@ -3,7 +3,8 @@
 Modelled on synctoolbox's published pipeline (audio_to_pitch_features, pitch_to_chroma, quantize_chroma, audio_to_pitch_onset_features,
 pitch_onset_features_to_DLNCO): three rate tiers, 88 zero-phase elliptic band-passes (the hot path: csrc/alignfeat.hip splits the recurrence's time axis
 exactly into chunks), pitch energy, chroma, onset novelty, peaks, DLNCO.  DESIGN.md 4f is the contract; tests/alignfeat_np.py restates it in fp64 numpy.
-synctoolbox is not a dependency and parity with it is unpinned; ``estimate_tuning`` and decoding audio files stay the caller's.
+synctoolbox is not a dependency and parity with it is unpinned; ``tuning_offsets="estimate"`` takes each song's offset from ``etude_amd.tuning`` (DESIGN.md 4g);
+decoding and resampling audio files stay the caller's.
 
 The filter design (``ellip_bandpass_sos``) is numpy fp64 of its own -- the package does not depend on scipy; tests/test_alignfeat_cpu.py holds it to
 ``scipy.signal.ellipord`` / ``ellip``.
@@ -285,8 +286,8 @@ class _Handle:
 class AlignFeatures:
     """Mono audio at 22 050 Hz -> (quantised chroma, DLNCO), both [12][ceil(N / 441)] float32 device tensors: what ``DTWEngine`` aligns.
 
-    A song is a 1-d float32 array or tensor (host or device), finite, N >= 1, with a tuning offset in cents (|t| <= 50, default 0: ``estimate_tuning`` is the
-    caller's).  ``workspace_budget`` bytes bound the device workspace of one launch sequence: ``features_many`` splits a call into sub-batches under it, which changes
+    A song is a 1-d float32 array or tensor (host or device), finite, N >= 1, with a tuning offset in cents (|t| <= 50, default 0; ``"estimate"`` asks the
+    device estimator of ``etude_amd.tuning``, which needs N >= 32 768).  ``workspace_budget`` bytes bound the device workspace of one launch sequence: ``features_many`` splits a call into sub-batches under it, which changes
     no song's bits.  Constructing needs no GPU; ``features_many`` does: there is no CPU path."""
 
     def __init__(self, device: Union[str, torch.device] = "cuda", workspace_budget: int = DEFAULT_WORKSPACE_BUDGET):
@@ -369,11 +370,19 @@ class AlignFeatures:
             _lib.check(self._lib.etd_alignfeat_run(hd.h, ptrs, n, N_arr, banks, C.c_void_p(chroma.data_ptr()), C.c_void_p(dlnco.data_ptr()),
                                                    C.c_void_p(ws.data_ptr()), ws.numel() * ws.element_size(), C.c_void_p(st)), "etd_alignfeat_run")
 
-    def features_many(self, wavs: Sequence, tuning_offsets: Optional[Sequence[float]] = None) -> List[Tuple[torch.Tensor, torch.Tensor]]:
+    def features_many(self, wavs: Sequence, tuning_offsets: Union[None, str, Sequence[float]] = None) -> List[Tuple[torch.Tensor, torch.Tensor]]:
         """songs [N_s] -> [(quantised chroma [12][T_s], DLNCO [12][T_s])] as device tensors.  A song's features depend on its samples and its tuning offset alone:
-        bit-identical alone, in any batch, in any order and under any workspace budget."""
+        bit-identical alone, in any batch, in any order and under any workspace budget.  ``tuning_offsets="estimate"``: every song's offset is estimated on the
+        device first (``TuningEstimator``, N >= 32 768), from the same uploaded samples."""
         if len(wavs) == 0:
             return []
+        estimate = isinstance(tuning_offsets, str)
+        if estimate:
+            if tuning_offsets != "estimate":
+                raise ValueError(f"features_many: tuning_offsets is a sequence of cents, None or \"estimate\", got {tuning_offsets!r}")
+            from .tuning import default_tuning_estimator
+            songs = default_tuning_estimator(self._device()).check_songs(wavs)          # (its checks include those below; the samples are uploaded once)
+            return self._features_checked(songs, [float(t) for t in default_tuning_estimator(self._device()).estimate_device(songs)[0]])
         if tuning_offsets is None:
             tuning_offsets = [0.0] * len(wavs)
         if len(tuning_offsets) != len(wavs):
@@ -392,6 +401,10 @@ class AlignFeatures:
         bad = torch.stack([torch.isfinite(t).all() for t in songs]).logical_not().nonzero().flatten().tolist()      # (one host synchronisation for the call)
         if bad:
             raise ValueError(f"song {bad[0]}: holds a non-finite sample")
+        return self._features_checked(songs, tuning_offsets)
+
+    def _features_checked(self, songs: List[torch.Tensor], tuning_offsets: Sequence[float]) -> List[Tuple[torch.Tensor, torch.Tensor]]:
+        dev = self._device()
         Ns = [int(t.numel()) for t in songs]
         out: List[Tuple[torch.Tensor, torch.Tensor]] = []
         with torch.cuda.device(dev):
@@ -412,11 +425,16 @@ class AlignFeatures:
     def features(self, wav, tuning_offset: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor]:
         return self.features_many([wav], [tuning_offset])[0]
 
-    def as_feature_fn(self, load_fn: Callable, tuning_fn: Optional[Callable] = None) -> Callable:
+    def as_feature_fn(self, load_fn: Callable, tuning_fn: Union[None, str, Callable] = None) -> Callable:
         """-> the ``path -> (quantised chroma, DLNCO)`` callable ``AudioAligner(feature_fn=...)`` takes.  load_fn(path) -> mono samples at 22 050 Hz (decoding and
-        resampling are the caller's); tuning_fn(path, samples) -> cents, default 0."""
+        resampling are the caller's); tuning_fn(path, samples) -> cents, default 0; ``tuning_fn="estimate"`` estimates it on the device."""
+        if isinstance(tuning_fn, str) and tuning_fn != "estimate":
+            raise ValueError(f"as_feature_fn: tuning_fn is a callable, None or \"estimate\", got {tuning_fn!r}")
+
         def fn(path):
             x = load_fn(path)
+            if isinstance(tuning_fn, str):
+                return self.features_many([x], "estimate")[0]
             return self.features(x, 0.0 if tuning_fn is None else float(tuning_fn(path, x)))
         return fn
 

@@ -1,0 +1,162 @@
+"""Tuning estimation on the MI355X: ``TuningEstimator`` -- mono audio at 22 050 Hz -> the deviation from 440 Hz equal temperament in whole cents (-50 .. 49), the
+``tuning_offset`` of ``AlignFeatures``' filterbanks.
+
+Stands in for ``estimate_tuning(audio, fs)`` of the reference's ``AudioAligner._compute_alignment`` (etude/data/aligner.py:100-101), modelled on synctoolbox's routine
+with its defaults: a long-window STFT (csrc/tuning.hip: a 16 384-point real FFT in LDS per frame, the hot path), log compression, the sum over time in a fixed order,
+a not-a-knot cubic spline onto a 1-cent axis, a local average, rectification and a comb.  DESIGN.md 4g is the contract; tests/tuning_np.py restates it in fp64 numpy.
+synctoolbox is not a dependency and parity with it is unpinned.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, List, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+
+from . import _lib
+
+FS = 22050
+N_FFT = 16384
+HOP = 8192
+N_THETA = 100
+
+
+def limits() -> dict:
+    """Host only: the constants of the built library"""
+    lo, hi, ms = C.c_longlong(), C.c_longlong(), C.c_int()
+    _lib.check(_lib.lib().etd_tuning_limits(C.byref(lo), C.byref(hi), C.byref(ms)), "etd_tuning_limits")
+    return dict(min_samples=lo.value, max_samples=hi.value, max_songs=ms.value)
+
+
+class TuningEstimator:
+    """Mono audio at 22 050 Hz -> tuning in cents, an integer in -50 .. 49, and the comb similarity ``sim[100]`` it is the first maximum of.
+
+    A song is a 1-d float32 array or tensor (host or device), finite, 32 768 <= N <= 2^27.  Constructing needs no GPU; ``estimate_many`` does: there is no CPU path."""
+
+    def __init__(self, device: Union[str, torch.device] = "cuda"):
+        self.device = torch.device("cuda" if device == "auto" else device)
+        self._lib = _lib.lib()
+        self.limits = limits()
+        cfg = _lib.TuningCfg(sample_rate=FS, n_fft=N_FFT, hop=HOP)
+        h = C.c_void_p()
+        _lib.check(self._lib.etd_tuning_create(C.byref(cfg), C.byref(h)), "etd_tuning_create")
+        self.h = h
+
+    def __del__(self):
+        h = getattr(self, "h", None)
+        if h is not None and h.value:
+            self._lib.etd_tuning_destroy(h)
+            self.h = None
+
+    def num_frames(self, N: int) -> int:
+        if N < self.limits["min_samples"]:
+            raise ValueError(f"num_frames: N must be >= {self.limits['min_samples']} (two windows), got {N}")
+        return 1 + int(N) // HOP
+
+    def workspace_bytes(self, Ns: Sequence[int]) -> int:
+        arr = (C.c_int64 * len(Ns))(*[int(n) for n in Ns])
+        b = int(self._lib.etd_tuning_workspace_bytes(self.h, len(Ns), arr))
+        if b < 0:
+            _lib.check(b, "etd_tuning_workspace_bytes")
+        return b
+
+    def layout(self, Ns: Sequence[int], song: int) -> dict:
+        """test hook (host arithmetic): where song `song` of a call with these lengths keeps its stages in the workspace (byte offsets), its frames and groups"""
+        arr = (C.c_int64 * len(Ns))(*[int(n) for n in Ns])
+        out = (C.c_int64 * len(_lib.TUNING_LAYOUT))()
+        _lib.check(self._lib.etd_tuning_debug_layout(self.h, len(Ns), arr, int(song), out, len(_lib.TUNING_LAYOUT)), "etd_tuning_debug_layout")
+        return dict(zip(_lib.TUNING_LAYOUT, [int(v) for v in out]))
+
+    def tap_power(self, song: int, frames: Sequence[int], power: Union[torch.Tensor, None]) -> None:
+        """test hook: the following runs also write P[f][0 .. 8192] of these frames (at most 8) of song `song` to `power` (device float32 [len(frames)][8193]);
+        ``power=None`` turns it off"""
+        if power is None:
+            _lib.check(self._lib.etd_tuning_debug_power(self.h, 0, None, 0, None), "etd_tuning_debug_power")
+            return
+        arr = (C.c_int32 * len(frames))(*[int(f) for f in frames])
+        if power.dtype != torch.float32 or power.numel() < len(frames) * (N_FFT // 2 + 1) or not power.is_contiguous():
+            raise ValueError("tap_power: power must be a contiguous float32 tensor of [len(frames)][8193]")
+        _lib.check(self._lib.etd_tuning_debug_power(self.h, int(song), arr, len(frames), C.c_void_p(power.data_ptr())), "etd_tuning_debug_power")
+
+    def _device(self) -> torch.device:
+        if self.device.type != "cuda" or not torch.cuda.is_available():
+            raise _lib.EtudeHipError("etude_amd.TuningEstimator needs a ROCm GPU (device='cuda'); there is no CPU path")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        return self.device
+
+    def run_raw(self, songs: Sequence[torch.Tensor], tuning: torch.Tensor, sim: torch.Tensor, ws: torch.Tensor) -> None:
+        """one launch sequence on checked device tensors with the caller's buffers (tests put canaries around them): tuning int32 [n], sim float64 [n][100]"""
+        n = len(songs)
+        ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in songs])
+        N_arr = (C.c_int64 * n)(*[int(t.numel()) for t in songs])
+        dev = self._device()
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(self._lib.etd_tuning_run(self.h, ptrs, n, N_arr, C.c_void_p(tuning.data_ptr() if tuning is not None else None),
+                                                C.c_void_p(sim.data_ptr() if sim is not None else None), C.c_void_p(ws.data_ptr()), ws.numel() * ws.element_size(),
+                                                C.c_void_p(st)), "etd_tuning_run")
+
+    def check_songs(self, wavs: Sequence) -> List[torch.Tensor]:
+        """the input checks (1-d, the length limits, finite with ONE host synchronisation) -> the songs as contiguous float32 device tensors"""
+        for i, x in enumerate(wavs):
+            shp = tuple(x.shape) if hasattr(x, "shape") else None
+            if shp is None or len(shp) != 1:
+                raise ValueError(f"song {i}: need mono samples [N], got shape {shp}")
+            if shp[0] < self.limits["min_samples"]:
+                raise ValueError(f"song {i}: N = {shp[0]} is shorter than two windows ({self.limits['min_samples']} samples): the tuning cannot be estimated")
+            if shp[0] > self.limits["max_samples"]:
+                raise ValueError(f"song {i}: N = {shp[0]} is above the engine's {self.limits['max_samples']} samples")
+        dev = self._device()
+        songs = [torch.as_tensor(x).detach().to(dev, torch.float32).contiguous() for x in wavs]
+        bad = torch.stack([torch.isfinite(t).all() for t in songs]).logical_not().nonzero().flatten().tolist()      # (one host synchronisation for the call)
+        if bad:
+            raise ValueError(f"song {bad[0]}: holds a non-finite sample")
+        return songs
+
+    def estimate_device(self, songs: Sequence[torch.Tensor]) -> Tuple[np.ndarray, torch.Tensor]:
+        """checked device songs -> (tuning int64 [n] on the host, sim float64 [n][100] on the device)"""
+        dev = self._device()
+        tun, sims = [], []
+        with torch.cuda.device(dev):
+            for i0 in range(0, len(songs), self.limits["max_songs"]):
+                group = songs[i0: i0 + self.limits["max_songs"]]
+                tuning = torch.empty(len(group), dtype=torch.int32, device=dev)
+                sim = torch.empty(len(group), N_THETA, dtype=torch.float64, device=dev)
+                ws = torch.empty(self.workspace_bytes([int(t.numel()) for t in group]), dtype=torch.uint8, device=dev)
+                self.run_raw(group, tuning, sim, ws)
+                tun.append(tuning)
+                sims.append(sim)
+            for t in songs:
+                t.record_stream(torch.cuda.current_stream(dev))
+        return torch.cat(tun).cpu().numpy().astype(np.int64), torch.cat(sims)
+
+    def estimate_many(self, wavs: Sequence, details: bool = False):
+        """songs [N_s] -> tuning in cents, int64 [n]; with ``details`` also sim float64 [n][100] (host).  A song's numbers depend on its samples alone: bit-identical
+        alone, in any batch and in any order."""
+        if len(wavs) == 0:
+            return (np.zeros(0, np.int64), np.zeros((0, N_THETA))) if details else np.zeros(0, np.int64)
+        tun, sim = self.estimate_device(self.check_songs(wavs))
+        return (tun, sim.cpu().numpy()) if details else tun
+
+    def estimate(self, wav) -> int:
+        return int(self.estimate_many([wav])[0])
+
+
+_default: Dict[str, TuningEstimator] = {}
+
+
+def default_tuning_estimator(device="cuda") -> TuningEstimator:
+    """one ``TuningEstimator`` per device, made once"""
+    key = str(torch.device(device))
+    if key not in _default:
+        _default[key] = TuningEstimator(device)
+    return _default[key]
+
+
+def estimate_tuning(x, Fs: int = FS) -> int:
+    """the reference's call shape: ``estimate_tuning(audio, fs)`` -> cents.  The engine is fixed to 22 050 Hz."""
+    if int(Fs) != FS or Fs != int(Fs):
+        raise ValueError(f"estimate_tuning: the engine is fixed to Fs = {FS}, got {Fs} (resampling is the caller's)")
+    return default_tuning_estimator().estimate(x)

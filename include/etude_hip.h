@@ -29,6 +29,8 @@
  *   etd_dtw_align         AudioAligner._compute_warping_path behind the  etude/data/aligner.py:106-133
  *                         features: CENS, optimal chroma shift, DTW,
  *                         strictly monotonic path, pitch_shift
+ *   etd_tuning_run        estimate_tuning(audio, fs) of                  etude/data/aligner.py:100-101
+ *                         AudioAligner._compute_alignment
  *
  * Conventions: every function returns 0 on success or a negative errno-style code (ETD_E*); the
  * message is available from etd_last_error() (thread-local).  "dev" pointers are device (HBM)
@@ -456,7 +458,7 @@ int etd_dtw_align(etd_dtw*, const float* const* feat_ptrs, int n_pairs, const in
  * The feature extraction in front of the DTW, modelled on synctoolbox's published pipeline (audio_to_pitch_features, pitch_to_chroma, quantize_chroma,
  * audio_to_pitch_onset_features, pitch_onset_features_to_DLNCO): rate tiers 22 050 / 4 410 / 882 Hz, 88 zero-phase elliptic band-passes (pitches 21 .. 108, an fp64
  * recurrence whose time axis is split exactly into chunks), pitch energy, chroma, onset novelty, peaks, DLNCO.  DESIGN.md 4f is the contract (parity with synctoolbox
- * itself is unpinned); estimate_tuning and decoding audio stay the caller's. */
+ * itself is unpinned); the tuning offset comes from etd_tuning_run or the caller, decoding and resampling audio stay the caller's. */
 typedef struct etd_alignfeat etd_alignfeat;
 typedef struct {
   int struct_bytes;          /* sizeof(etd_alignfeat_cfg) of the caller: a mismatch is ETD_EINVAL */
@@ -489,6 +491,35 @@ long long etd_alignfeat_workspace_bytes(const etd_alignfeat*, int n_songs, const
  * samples and its filterbank alone: bit-identical alone, in any batch and in any order.  Synchronises `stream` once at the start (song table upload). */
 int etd_alignfeat_run(etd_alignfeat*, const float* const* wav_ptrs, int n_songs, const int64_t* N_host, const int32_t* bank_host, float* chroma_dev, float* dlnco_dev,
                       void* workspace_dev, long long workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------ tuning estimation (mono audio at 22 050 Hz -> cents off 440 Hz equal temperament, the tuning_offset
+ * of etd_alignfeat's filterbanks).  estimate_tuning of AudioAligner._compute_alignment (etude/data/aligner.py:100-101), modelled on synctoolbox's routine with its
+ * defaults: STFT (n_fft 16 384, hop 8 192, periodic Hann, centred, zero padding), log(1 + 100 |X|^2) summed over time in a fixed order, a not-a-knot cubic spline onto a
+ * 1-cent axis from MIDI 24 to 108, minus its 101-point local average, rectified, and a comb of 84 teeth 100 cents apart shifted over theta = -50 .. 49.  DESIGN.md 4g
+ * is the contract (parity with synctoolbox or libfmp is unpinned). */
+typedef struct etd_tuning etd_tuning;
+typedef struct {
+  int struct_bytes;          /* sizeof(etd_tuning_cfg) of the caller: a mismatch is ETD_EINVAL */
+  int sample_rate;           /* 22050 */
+  int n_fft;                 /* 16384 */
+  int hop;                   /* 8192 */
+} etd_tuning_cfg;
+/* HOST ONLY: the constants of this build: fewest and most samples per song, songs per call (any may be NULL) */
+int etd_tuning_limits(long long* min_samples, long long* max_samples, int* max_songs);
+/* Forms every table on the host in fp64 (window, twiddles, the spline's pivots, the log-frequency axis).  Needs no GPU: the tables go to the device with the first
+ * etd_tuning_run.  A config other than the one above is ETD_EINVAL. */
+int etd_tuning_create(const etd_tuning_cfg* cfg, etd_tuning** out);
+void etd_tuning_destroy(etd_tuning*);
+/* HOST ONLY: bytes of device workspace a call with these songs needs (formula in DESIGN.md 4g; 32 KB per 8 frames, 0.5 MB per 3-minute song); negative = ETD_EINVAL:
+ * n_songs outside 1 .. 4096, N < 32 768 (two windows) or N above the limit */
+long long etd_tuning_workspace_bytes(const etd_tuning*, int n_songs, const int64_t* N_host);
+/* wav_ptrs: HOST array of n_songs DEVICE pointers, song s = N_host[s] mono fp32 samples, finite (the caller checks).  tuning_dev: DEVICE int32 [n_songs], cents in
+ * -50 .. 49; sim_dev: DEVICE fp64 [n_songs][100], the comb similarity of theta = -50 .. 49 (tuning = -50 + its first maximum).  workspace_dev: 256-byte aligned device
+ * memory of workspace_bytes >= etd_tuning_workspace_bytes; afterwards it holds the stages Y, Yi, R and sim of every song (etd_tuning_debug_layout).  Refused with
+ * ETD_EINVAL and a message before anything is launched: N < 32 768, too many songs, a workspace that is too small, a NULL output.  Three launches whatever n_songs;
+ * a song's numbers depend on its samples alone: bit-identical alone, in any batch and in any order.  Synchronises `stream` once at the start (song table upload). */
+int etd_tuning_run(etd_tuning*, const float* const* wav_ptrs, int n_songs, const int64_t* N_host, int32_t* tuning_dev, double* sim_dev, void* workspace_dev,
+                   long long workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -168,6 +168,15 @@ int etd_dtw_debug_path(etd_dtw*, const float* const* feat_ptrs, long long N1, lo
  *   in chroma_dev / dlnco_dev.  Per-band arrays hold bands 0 .. 87 in order, bands 0 .. 38 with tier 2's count, 39 .. 74 with tier 1's, 75 .. 87 with tier 0's. */
 int etd_alignfeat_debug_layout(const etd_alignfeat*, int n_songs, const int64_t* N_host, int song, int64_t* out, int n_out);
 
+/* HOST ONLY test hook: the stage taps of etd_tuning_run.  After a run the caller's workspace holds the stages of every song; this returns where song `song` of a call
+ * with these lengths keeps them: out int64 [7] = [0] frames F = 1 + N / 8192  [1] groups of 8 frames  then BYTE offsets into the workspace: [2] the groups' partial
+ * sums fp32 [groups][8193]  [3] Y fp32 [8193]  [4] Yi fp64 [8400]  [5] R fp64 [8400]  [6] sim fp64 [100]. */
+int etd_tuning_debug_layout(const etd_tuning*, int n_songs, const int64_t* N_host, int song, int64_t* out, int n_out);
+/* test hook: during the following etd_tuning_run calls the frame kernel also writes the power P[f][0 .. 8192] (fp32) of frames frames_host[0 .. n_frames) of song
+ * `song` to power_dev [n_frames][8193] (device); n_frames 1 .. 8; a frame the song does not have makes the run ETD_EINVAL.  power_dev = NULL turns it off.  No
+ * launch is added either way. */
+int etd_tuning_debug_power(etd_tuning*, int song, const int32_t* frames_host, int n_frames, float* power_dev);
+
 #ifdef __cplusplus
 }
 #endif
