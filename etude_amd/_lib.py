@@ -80,6 +80,11 @@ class TuningCfg(_SizedCfg):
     _fields_ = [("struct_bytes", C.c_int)] + [(n, C.c_int) for n in ("sample_rate", "n_fft", "hop")]
 
 
+class RhythmCfg(_SizedCfg):
+    _fields_ = ([("struct_bytes", C.c_int)] + [(n, C.c_int) for n in ("top_k", "precision_digits", "n_gram", "n_clusters", "n_random")]
+                + [("min_ioi", C.c_double), ("max_ioi", C.c_double), ("random_host", C.POINTER(C.c_double))])
+
+
 # etd_tuning_debug_layout's int64 [7] (include/etude_hip_debug.h), in order
 TUNING_LAYOUT = ("F", "G", "off_part", "off_Y", "off_Yi", "off_R", "off_sim")
 
@@ -275,6 +280,12 @@ SIGNATURES = {
     "etd_tuning_run": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, c_i64_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
     "etd_tuning_debug_layout": (C.c_int, [C.c_void_p, C.c_int, c_i64_p, C.c_int, c_i64_p, C.c_int]),
     "etd_tuning_debug_power": (C.c_int, [C.c_void_p, C.c_int, c_i32_p, C.c_int, C.c_void_p]),
+    "etd_rhythm_limits": (C.c_int, [c_int_p, c_int_p, c_int_p, c_int_p]),
+    "etd_rhythm_create": (C.c_int, [C.POINTER(RhythmCfg), C.POINTER(C.c_void_p)]),
+    "etd_rhythm_destroy": (None, [C.c_void_p]),
+    "etd_rhythm_check": (C.c_int, [C.c_void_p, c_i64_p, C.c_int]),
+    "etd_rhythm_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_i64_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "etd_rhythm_debug_logioi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "etd_debug_decoder_trace_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.POINTER(C.c_int), C.c_void_p]),
 }
 

@@ -31,6 +31,7 @@
  *                         strictly monotonic path, pitch_shift
  *   etd_tuning_run        estimate_tuning(audio, fs) of                  etude/data/aligner.py:100-101
  *                         AudioAligner._compute_alignment
+ *   etd_rhythm_run        RGCCalculator / IPECalculator .calculate       etude/evaluation/metrics/rgc.py, ipe.py
  *
  * Conventions: every function returns 0 on success or a negative errno-style code (ETD_E*); the
  * message is available from etd_last_error() (thread-local).  "dev" pointers are device (HBM)
@@ -520,6 +521,45 @@ long long etd_tuning_workspace_bytes(const etd_tuning*, int n_songs, const int64
  * a song's numbers depend on its samples alone: bit-identical alone, in any batch and in any order.  Synchronises `stream` once at the start (song table upload). */
 int etd_tuning_run(etd_tuning*, const float* const* wav_ptrs, int n_songs, const int64_t* N_host, int32_t* tuning_dev, double* sim_dev, void* workspace_dev,
                    long long workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------ rhythm metrics (note onsets -> Rhythmic Grid Consistency and IOI Pattern Entropy).
+ * RGCCalculator.calculate and IPECalculator.calculate (etude/evaluation/metrics/rgc.py, ipe.py) behind get_onsets_from_file, with the KMeans of scikit-learn the second
+ * one fits (n_clusters = min(8, distinct log-IOIs), random_state 42, one k-means++ start, Lloyd, max_iter 300, tol 1e-4) restated in fp64 in a fixed order.  DESIGN.md
+ * 4h is the contract. */
+typedef struct etd_rhythm etd_rhythm;
+typedef struct {
+  int struct_bytes;          /* sizeof(etd_rhythm_cfg) of the caller: a mismatch is ETD_EINVAL */
+  int top_k;                 /* 8: the most common rounded IOIs the grid is inferred from, 1 .. 64 */
+  int precision_digits;      /* 4: decimals the IOIs are rounded to before they are counted, 0 .. 9 */
+  int n_gram;                /* 8: symbols per n-gram, 1 .. 16 */
+  int n_clusters;            /* 8: most clusters (symbols), 1 .. 8 */
+  int n_random;              /* 29: doubles in random_host */
+  double min_ioi, max_ioi;   /* 0.0625, 4.0: the IOIs are clipped to this range before the logarithm */
+  const double* random_host; /* the first 29 doubles of numpy.random.RandomState(42).random_sample(): the only random numbers KMeans(random_state=42) draws, each in
+                              * [0, 1); copied by etd_rhythm_create.  No generator runs on the device. */
+} etd_rhythm_cfg;
+/* HOST ONLY: the constants of this build: onsets per cover (8 192), covers per call, the largest top_k and n_gram (any may be NULL) */
+int etd_rhythm_limits(int* max_onsets, int* max_covers, int* max_top_k, int* max_n_gram);
+/* Needs no GPU.  A value outside the ranges above is ETD_EINVAL. */
+int etd_rhythm_create(const etd_rhythm_cfg* cfg, etd_rhythm** out);
+void etd_rhythm_destroy(etd_rhythm*);
+/* A ragged batch: cover b is onsets_dev[offsets[b] .. offsets[b + 1]) (DEVICE fp64, seconds, ascending and unique -- np.unique of the note onsets; fewer than two is
+ * a valid cover with an error status); offsets_dev: DEVICE int64 [n_covers + 1], offsets_host: the same numbers on the HOST (offsets[0] = 0).  out_dev: DEVICE fp64
+ * [n_covers][3] = rgc_score, inferred_tau, ipe_score (NaN where the metric has none); status_dev: DEVICE int32 [n_covers]:
+ *   bits 0 .. 3   RGC: 0 ok, 1 "Not enough onsets for IOI calculation.", 2 "Not enough IOIs to analyze.", 3 "Not enough unique IOIs to determine a grid.",
+ *                 4 "Could not infer a valid rhythmic grid period (tau).", 5 the onsets are not ascending, unique, finite and below 2^50 / 10^precision_digits apart
+ *   bits 4 .. 7   IPE: 0 ok, 1 as above, 3 "Could not quantize IOI sequence into symbols." (fewer than two distinct clipped log-IOIs), 5 as above
+ *   bit 8         relocated: Lloyd's iteration met an empty cluster; the samples that move are picked by distance descending, then lowest index, where scikit-learn's
+ *                 argpartition leaves the order of equally far samples open
+ *   bits 12 .. 15 the clusters k, bits 16 .. 24 Lloyd's iterations
+ * Refused with ETD_EINVAL and a message before anything is launched: a cover above 8 192 onsets, n_covers outside 1 .. 2^20, decreasing offsets, a NULL output.  ONE
+ * launch whatever n_covers, one workgroup per cover, the working set in LDS.  A cover's numbers depend on its onsets alone: bit-identical alone, in any batch and
+ * from run to run.  Asynchronous on `stream`. */
+/* HOST ONLY: what etd_rhythm_run refuses about the shape of a call, with its message, before anything touches the device: n_covers outside 1 .. 2^20,
+ * offsets_host[0] != 0, decreasing offsets, a cover above 8 192 onsets */
+int etd_rhythm_check(const etd_rhythm*, const int64_t* offsets_host, int n_covers);
+int etd_rhythm_run(etd_rhythm*, const double* onsets_dev, const int64_t* offsets_dev, const int64_t* offsets_host, int n_covers, double* out_dev, int32_t* status_dev,
+                   void* stream);
 
 #ifdef __cplusplus
 }

@@ -177,6 +177,12 @@ int etd_tuning_debug_layout(const etd_tuning*, int n_songs, const int64_t* N_hos
  * launch is added either way. */
 int etd_tuning_debug_power(etd_tuning*, int song, const int32_t* frames_host, int n_frames, float* power_dev);
 
+/* test hook: during the following etd_rhythm_run calls the kernel also copies out what it clustered: logioi_dev (DEVICE fp64, as long as onsets_dev): the centred,
+ * clipped log-IOIs of cover b at [offsets[b] .. offsets[b + 1] - 1) -- the device's own logarithm, which may differ from numpy's by an ulp --; labels_dev (DEVICE
+ * int8, same layout): the final labels; centres_dev (DEVICE fp64 [n_covers][8]): the final centres on the centred axis, NaN past k.  Entries of covers without an IPE
+ * score are left untouched.  All three NULL turns it off.  No launch is added either way. */
+int etd_rhythm_debug_logioi(etd_rhythm*, double* logioi_dev, signed char* labels_dev, double* centres_dev);
+
 #ifdef __cplusplus
 }
 #endif
