@@ -57,6 +57,13 @@ class BeatCfg(_SizedCfg):
                                        "n_mels", "tempo_out", "max_rows")]
 
 
+class BeatTaps(_SizedCfg):
+    """etd_debug_beat_taps (include/etude_hip_debug.h): device destinations of the Beat-Transformer engine's stage taps"""
+    PTRS = ("c1", "c2", "x3", "c3", "front", "ln1", "qkv", "skip", "x_attn", "tacc", "ln2", "hid", "x_ffn", "iln1", "iqkv", "iao", "ix_attn", "iln2", "ihid", "ix_ffn", "part")
+    _fields_ = [("struct_bytes", C.c_int), ("layer_mask", C.c_uint)] + [(n, C.c_int) for n in ("rows", "frames", "segs", "d_hid", "slices", "islices")] + \
+               [(n, C.c_void_p) for n in PTRS]
+
+
 class DbnCfg(_SizedCfg):
     _fields_ = [("struct_bytes", C.c_int), ("fps", C.c_double), ("min_bpm", C.c_double), ("max_bpm", C.c_double), ("transition_lambda", C.c_double),
                 ("observation_lambda", C.c_double), ("threshold", C.c_double), ("correct", C.c_int), ("num_tempi", C.c_int), ("n_bars", C.c_int),
@@ -246,6 +253,7 @@ SIGNATURES = {
     "etd_beat_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_i64_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "etd_beat_flops": (C.c_double, [C.c_void_p, C.c_longlong]),
     "etd_beat_debug_taps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "etd_beat_debug_stage_taps": (C.c_int, [C.c_void_p, C.c_void_p]),
     "etd_dbn_describe": (C.c_int, [C.POINTER(DbnCfg), C.c_int, C.c_void_p, C.c_int, c_int_p, c_int_p, c_int_p, C.c_void_p, C.c_void_p]),
     "etd_dbn_workspace_bytes": (C.c_longlong, [C.POINTER(DbnCfg), C.c_longlong, C.c_int]),
     "etd_dbn_create": (C.c_int, [C.POINTER(DbnCfg), C.POINTER(C.c_void_p)]),

@@ -330,3 +330,23 @@ class BeatDetector:
         """test hook: following calls copy the token rows after the front end / time layer 0 into these [rows][256] device tensors (None = off)"""
         _lib.check(self._lib.etd_beat_debug_taps(self._h, C.c_void_p(front.data_ptr()) if front is not None else None,
                                                  C.c_void_p(layer0.data_ptr()) if layer0 is not None else None), "etd_beat_debug_taps")
+
+    def debug_stage_taps(self, layer_mask: int = 0, rows: int = 0, frames: int = 0, segs: int = 0, slices: int = 0, islices: int = 0, **bufs: torch.Tensor) -> None:
+        """Test hook (etd_beat_debug_stage_taps): register contiguous fp32 device tensors as the destinations of every launch's output, named as the members of
+        etd_debug_beat_taps and shaped as include/etude_hip_debug.h states; no tensors = taps off.  The caller keeps the tensors alive."""
+        if not bufs:
+            _lib.check(self._lib.etd_beat_debug_stage_taps(self._h, None), "etd_beat_debug_stage_taps")
+            return
+        t = _lib.BeatTaps(layer_mask=int(layer_mask), rows=int(rows), frames=int(frames), segs=int(segs), d_hid=int(self.config.model.d_hid), slices=int(slices),
+                          islices=int(islices))
+        per = {"tacc": frames, "part": segs}
+        width = dict(c1=42 * 32, c2=42 * 64, x3=3 * 1152, c3=3 * 256, qkv=768, iqkv=768, hid=t.d_hid, ihid=t.d_hid)
+        for k, v in bufs.items():
+            if k not in _lib.BeatTaps.PTRS or v.device != self.device or v.dtype != torch.float32 or not v.is_contiguous():
+                raise ValueError(f"debug_stage_taps: {k} must name a tap and be a contiguous fp32 device tensor")
+            n_sl = 1 if k in ("c1", "c2", "x3", "c3", "front", "part") else islices if k.startswith("i") else slices
+            need = n_sl * per.get(k, rows) * width.get(k, 256)
+            if v.numel() < need:
+                raise ValueError(f"debug_stage_taps: {k} holds {v.numel()} floats, the stated sizes need {need}")
+            setattr(t, k, v.data_ptr())
+        _lib.check(self._lib.etd_beat_debug_stage_taps(self._h, C.byref(t)), "etd_beat_debug_stage_taps")

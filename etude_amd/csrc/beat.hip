@@ -10,6 +10,7 @@
 
 #include "beat.h"
 #include "etude_hip.h"
+#include "etude_hip_debug.h"
 #include "prof.h"
 
 // ================================================================================================ device: song tables
@@ -291,6 +292,7 @@ struct etd_beat {
   float *x = nullptr, *xa = nullptr, *qkv = nullptr, *skip = nullptr, *hid = nullptr, *c1 = nullptr, *c2o = nullptr, *x3 = nullptr, *c3o = nullptr, *tacc = nullptr, *part = nullptr;
   int* tab = nullptr; int tab_cap = 0;
   float *tap_front = nullptr, *tap_l0 = nullptr;     // etd_beat_debug_taps
+  etd_debug_beat_taps st = {}; bool st_on = false;   // etd_beat_debug_stage_taps
 };
 
 namespace {
@@ -337,59 +339,91 @@ int ensure_ws(etd_beat* e, long long rows, int n_seq, hipStream_t st) {
 }
 
 // the model on one chunk of whole songs
-int run_chunk(etd_beat* e, const float* feat_dev, const BeatChunk& c, int max_seg, float* logits_dev, float* tempo_dev, hipStream_t st) {
+// (seg_base, segs: the chunk's first tempo partial sum in the call's order and their number -- only the stage taps need them on the host)
+int run_chunk(etd_beat* e, const float* feat_dev, const BeatChunk& c, int max_seg, int seg_base, int segs, float* logits_dev, float* tempo_dev, hipStream_t st) {
   const etd_beat_cfg& k = e->cfg;
   const int R = c.rows, F = c.frames;
   const double fR = R;
+  // ---- stage taps (etd_beat_debug_stage_taps): every copy follows the launch that produced its source, on the same stream, into slice `sl` of a buffer of `total`
+  // units per slice at the chunk's global offset `base`; a NULL member is off.  With taps off none of this runs.
+  const etd_debug_beat_taps& tp = e->st;
+  const bool ton = e->st_on;
+  auto tap = [&](float* dst, int sl, long long total, long long base, const float* src, long long n, long long width) -> int {
+    if (!dst) return ETD_OK;
+    HIP_TRY(hipMemcpyAsync(dst + ((long long)sl * total + base) * width, src, (size_t)(n * width) * 4, hipMemcpyDeviceToDevice, st));
+    return ETD_OK;
+  };
+  auto rtap = [&](float* dst, int sl, const float* src, long long width) { return tap(dst, sl, tp.rows, c.row_base, src, R, width); };
   {  // conv front end
     ProfScope ps("k_beat_conv1", st, fR * BEAT_W1 * BEAT_C1 * 3 * 15 * 2, fR * (BEAT_MELS * 4 + BEAT_W1 * BEAT_C1 * 4));
     hipLaunchKernelGGL(k_beat_conv1, dim3(nblk((long long)R * BEAT_W1 * BEAT_C1)), dim3(256), 0, st, feat_dev + (long long)c.row_base * BEAT_MELS, c, e->c1w, e->c1b, e->c1);
     HIP_TRY(hipGetLastError());
   }
+  if (ton) ETD_TRY(rtap(tp.c1, 0, e->c1, BEAT_W1 * BEAT_C1));
   ETD_TRY(gemm(e->c2, e->c1, R * BEAT_W1, DEPI_BIAS, e->c2o, nullptr, st, BEAT_C1));      // row r 42 + col = the patch at (r 42 + col) 32
+  if (ton) ETD_TRY(rtap(tp.c2, 0, e->c2o, BEAT_W1 * BEAT_C2));
   {
     ProfScope ps("k_beat_patch3", st, 0.0, fR * 3 * BEAT_K3 * 4 * 2);
     hipLaunchKernelGGL(k_beat_patch3, dim3(nblk((long long)R * 3 * BEAT_K3)), dim3(256), 0, st, e->c2o, c, e->x3);
     HIP_TRY(hipGetLastError());
   }
+  if (ton) ETD_TRY(rtap(tp.x3, 0, e->x3, 3 * BEAT_K3));
   ETD_TRY(gemm(e->c3, e->x3, R * 3, DEPI_BIAS, e->c3o, nullptr, st));
+  if (ton) ETD_TRY(rtap(tp.c3, 0, e->c3o, 3 * 256));
   {
     ProfScope ps("k_beat_pool3", st, 0.0, fR * 4 * 256 * 4);
     hipLaunchKernelGGL(k_beat_pool3, dim3(nblk((long long)R * 256)), dim3(256), 0, st, e->c3o, R, e->x);
     HIP_TRY(hipGetLastError());
   }
   if (e->tap_front) HIP_TRY(hipMemcpyAsync(e->tap_front + (long long)c.row_base * 256, e->x, (size_t)R * 256 * 4, hipMemcpyDeviceToDevice, st));
+  if (ton) ETD_TRY(rtap(tp.front, 0, e->x, 256));
   for (int l = 0; l < k.nlayers; ++l) {
     const TimeLayer& L = e->tl[l];
+    const bool tl = ton && ((tp.layer_mask >> l) & 1u);
+    const int sl = __builtin_popcount(tp.layer_mask & ((1u << l) - 1u)), isl = __builtin_popcount(tp.layer_mask & 0x38u & ((1u << l) - 1u));
     ETD_TRY(launch_ln_rows_f32(e->x, R, 256, L.ln1g, L.ln1b, nullptr, nullptr, 1e-5f, e->xa, nullptr, st));
+    if (tl) ETD_TRY(rtap(tp.ln1, sl, e->xa, 256));
     ETD_TRY(gemm(L.qkv, e->xa, R, DEPI_BIAS, e->qkv, nullptr, st));
+    if (tl) ETD_TRY(rtap(tp.qkv, sl, e->qkv, 768));
     {
       ProfScope ps("k_beat_dattn", st, fR * BEAT_HEADS * BEAT_TAPS * BEAT_HEAD_DIM * 6, fR * (768 * 4 * 3 + 256 * 4 * 3));
       hipLaunchKernelGGL(k_beat_dattn, dim3(nblk((long long)R * BEAT_HEADS)), dim3(256), 0, st, e->qkv, c, L.Er, 1 << l, e->skip, e->x);
       HIP_TRY(hipGetLastError());
     }
+    if (tl) { ETD_TRY(rtap(tp.skip, sl, e->skip, 256)); ETD_TRY(rtap(tp.x_attn, sl, e->x, 256)); }
     {
       ProfScope ps("k_beat_skipacc", st, fR * 256, fR * 256 * 4 + (double)F * 256 * 8);
       hipLaunchKernelGGL(k_beat_skipacc, dim3(nblk((long long)F * 256)), dim3(256), 0, st, e->skip, c, l == 0 ? 1 : 0, e->tacc);
       HIP_TRY(hipGetLastError());
     }
+    if (tl) ETD_TRY(tap(tp.tacc, sl, tp.frames, c.frame_base, e->tacc, F, 256));
     ETD_TRY(launch_ln_rows_f32(e->x, R, 256, L.ln2g, L.ln2b, nullptr, nullptr, 1e-5f, e->xa, nullptr, st));
+    if (tl) ETD_TRY(rtap(tp.ln2, sl, e->xa, 256));
     ETD_TRY(gemm(L.l1, e->xa, R, DEPI_GELU, e->hid, nullptr, st));
+    if (tl) ETD_TRY(rtap(tp.hid, sl, e->hid, k.d_hid));
     ETD_TRY(gemm(L.l2, e->hid, R, DEPI_RESID, nullptr, e->x, st));
+    if (tl) ETD_TRY(rtap(tp.x_ffn, sl, e->x, 256));
     if (l == 0 && e->tap_l0) HIP_TRY(hipMemcpyAsync(e->tap_l0 + (long long)c.row_base * 256, e->x, (size_t)R * 256 * 4, hipMemcpyDeviceToDevice, st));
     if (l >= 3 && l <= 5) {
       const InstrLayer& I = e->il[l - 3];
       ETD_TRY(launch_ln_rows_f32(e->x, R, 256, I.ln1g, I.ln1b, nullptr, nullptr, 1e-5f, e->xa, nullptr, st));
+      if (tl) ETD_TRY(rtap(tp.iln1, isl, e->xa, 256));
       ETD_TRY(gemm(I.inp, e->xa, R, DEPI_BIAS, e->qkv, nullptr, st));
+      if (tl) ETD_TRY(rtap(tp.iqkv, isl, e->qkv, 768));
       {
         ProfScope ps("k_beat_iattn", st, fR * BEAT_HEADS * k.instr * BEAT_HEAD_DIM * 4, fR * (768 * 4 * (1 + 2 * k.instr) / 1.0 + 256 * 4));
         hipLaunchKernelGGL(k_beat_iattn, dim3(nblk((long long)F * BEAT_HEADS * k.instr)), dim3(256), 0, st, e->qkv, c, e->skip);
         HIP_TRY(hipGetLastError());
       }
+      if (tl) ETD_TRY(rtap(tp.iao, isl, e->skip, 256));
       ETD_TRY(gemm(I.outp, e->skip, R, DEPI_RESID, nullptr, e->x, st));
+      if (tl) ETD_TRY(rtap(tp.ix_attn, isl, e->x, 256));
       ETD_TRY(launch_ln_rows_f32(e->x, R, 256, I.ln2g, I.ln2b, nullptr, nullptr, 1e-5f, e->xa, nullptr, st));
+      if (tl) ETD_TRY(rtap(tp.iln2, isl, e->xa, 256));
       ETD_TRY(gemm(I.l1, e->xa, R, DEPI_RELU, e->hid, nullptr, st));
+      if (tl) ETD_TRY(rtap(tp.ihid, isl, e->hid, k.d_hid));
       ETD_TRY(gemm(I.l2, e->hid, R, DEPI_RESID, nullptr, e->x, st));
+      if (tl) ETD_TRY(rtap(tp.ix_ffn, isl, e->x, 256));
     }
   }
   {
@@ -401,6 +435,7 @@ int run_chunk(etd_beat* e, const float* feat_dev, const BeatChunk& c, int max_se
     ProfScope ps("k_beat_tempo", st, (double)F * 256 + (double)c.count * 256 * 2 * k.tempo_out, (double)F * 256 * 4 + (double)k.tempo_out * 256 * 4);
     hipLaunchKernelGGL(k_beat_tempo_part, dim3((unsigned)max_seg, (unsigned)c.count), dim3(256), 0, st, e->tacc, c, e->part);
     HIP_TRY(hipGetLastError());
+    if (ton) ETD_TRY(tap(tp.part, 0, tp.segs, seg_base, e->part, segs, 256));
     hipLaunchKernelGGL(k_beat_tempo, dim3((unsigned)c.count), dim3(256), 0, st, e->part, c, e->tw, e->tb, k.tempo_out, tempo_dev);
     HIP_TRY(hipGetLastError());
   }
@@ -541,6 +576,9 @@ extern "C" int etd_beat_forward(etd_beat* e, const float* feat_dev, int n_seq, c
     if (rows > (1LL << 30)) ETD_FAIL(ETD_EINVAL, "beat_forward: more than 2^30 rows in one call");
   }
   tab[n_seq] = (int)rows; tab[2 * n_seq + 1] = (int)frames; tab[3 * n_seq + 2] = (int)segs;
+  if (e->st_on && (rows > e->st.rows || frames > e->st.frames || segs > e->st.segs))       // checked before anything is launched
+    ETD_FAIL(ETD_EINVAL, "beat_forward: stage taps registered for %d rows, %d frames, %d segments; this call has %lld, %lld, %lld", e->st.rows, e->st.frames, e->st.segs, rows,
+             frames, segs);
   const long long cap = big > e->cfg.max_rows ? big : e->cfg.max_rows;        // a song longer than max_rows gets a workspace of its own size
   ETD_TRY(ensure_ws(e, cap, n_seq, st));
   HIP_TRY(hipMemcpyAsync(e->tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, st));
@@ -555,7 +593,8 @@ extern "C" int etd_beat_forward(etd_beat* e, const float* feat_dev, int n_seq, c
     c.row0 = row0; c.frame0 = frame0; c.seg0 = seg0; c.first = s; c.count = s1 - s; c.row_base = tab[s]; c.frame_base = tab[n_seq + 1 + s];
     c.rows = (int)r; c.frames = (int)(r / ni); c.instr = ni;
     const int max_seg = (int)((maxT + BEAT_SEG - 1) / BEAT_SEG);
-    ETD_TRY(run_chunk(e, feat_dev, c, max_seg, logits_dev, tempo_dev, st));
+    const int seg_base = tab[2 * (n_seq + 1) + s];
+    ETD_TRY(run_chunk(e, feat_dev, c, max_seg, seg_base, tab[2 * (n_seq + 1) + s1] - seg_base, logits_dev, tempo_dev, st));
     s = s1;
   }
   return ETD_OK;
@@ -576,5 +615,25 @@ extern "C" double etd_beat_flops(etd_beat* e, long long T) {
 extern "C" int etd_beat_debug_taps(etd_beat* e, float* front_dev, float* layer0_dev) {
   if (!e) ETD_FAIL(ETD_EINVAL, "beat_debug_taps: null handle");
   e->tap_front = front_dev; e->tap_l0 = layer0_dev;
+  return ETD_OK;
+}
+
+extern "C" int etd_beat_debug_stage_taps(etd_beat* e, const etd_debug_beat_taps* t) {
+  if (!e) ETD_FAIL(ETD_EINVAL, "beat_debug_stage_taps: null handle");
+  if (t && t->struct_bytes != (int)sizeof(etd_debug_beat_taps))      // first: no other member of a struct of another size is read
+    ETD_FAIL(ETD_EINVAL, "beat_debug_stage_taps: etd_debug_beat_taps of %d bytes, this library expects %d", t->struct_bytes, (int)sizeof(etd_debug_beat_taps));
+  if (t && t->layer_mask == 0 && !t->c1 && !t->c2 && !t->x3 && !t->c3 && !t->front && !t->part) t = nullptr;      // nothing to tap: off
+  if (t) {
+    const int L = e->cfg.nlayers;
+    if (t->layer_mask >> L) ETD_FAIL(ETD_EINVAL, "beat_debug_stage_taps: layer_mask %#x names a layer beyond the model's %d", t->layer_mask, L);
+    if (t->rows < 1 || t->frames < 1 || t->segs < 1 || t->d_hid != e->cfg.d_hid)
+      ETD_FAIL(ETD_EINVAL, "beat_debug_stage_taps: buffers stated for rows %d, frames %d, segs %d, d_hid %d; the model has d_hid %d", t->rows, t->frames, t->segs, t->d_hid, e->cfg.d_hid);
+    const int need = __builtin_popcount(t->layer_mask), ineed = __builtin_popcount(t->layer_mask & 0x38u);
+    if (t->slices < need || t->islices < ineed)
+      ETD_FAIL(ETD_EINVAL, "beat_debug_stage_taps: layer_mask %#x needs %d time and %d instrument slices, the buffers are stated to hold %d and %d", t->layer_mask, need, ineed,
+               t->slices, t->islices);
+  }
+  e->st = t ? *t : etd_debug_beat_taps{};
+  e->st_on = t != nullptr;
   return ETD_OK;
 }

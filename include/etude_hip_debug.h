@@ -147,6 +147,26 @@ int etd_debug_g3_bounds(const float* W, const float* c, int N, int K, const floa
 /* test hook: during the following etd_beat_forward calls copy the token rows after the conv front end and after time layer 0 ([rows][256], rows in the call's
  * global row order) to front_dev / layer0_dev (NULL = off). */
 int etd_beat_debug_taps(etd_beat*, float* front_dev, float* layer0_dev);
+/* test hook (tests/test_gpu_beat_stages.py): fp32 taps of every launch of the Beat-Transformer engine.  While registered, etd_beat_forward copies each launch's output
+ * out of the shared workspace (hipMemcpyAsync, device to device, right behind the launch, on the call's stream) into the caller's DEVICE buffers, in the call's global
+ * row ((song, instr, t)), frame ((song, t)) and tempo-segment order, whatever the chunking; the outputs of the call are bit-identical with taps on and off.  A NULL member
+ * is off; etd_beat_debug_stage_taps(e, NULL), or a struct with a zero layer_mask and no front-end / part pointer, switches everything off.  Only the time layers in
+ * `layer_mask` are tapped: layer l's slice of a per-layer buffer is slice popcount(layer_mask & ((1 << l) - 1)), and of an instrument-layer buffer (layers 3 .. 5)
+ * popcount(layer_mask & 0x38 & ((1 << l) - 1)).  The sizes the caller states are checked against every call BEFORE anything is launched (a call with more rows,
+ * frames or segments than stated is ETD_EINVAL), the geometry at registration. */
+typedef struct etd_debug_beat_taps {
+  int struct_bytes;                   /* sizeof(etd_debug_beat_taps) of the caller */
+  unsigned layer_mask;
+  int rows, frames, segs;             /* every buffer's extent per slice: rows = instr x frames of the call, segs = sum over songs of ceil(T / 128) */
+  int d_hid;
+  int slices, islices;                /* slices the per-layer / per-instrument-layer buffers hold */
+  float *c1, *c2, *x3, *c3, *front;   /* front end: [rows][42][32] conv1 + pool + ReLU, [rows * 42][64] conv2 + bias (columns 31 .. 41 of a row read past it), [rows * 3][1152]
+                                         conv3 patches, [rows * 3][256] conv3 + bias, [rows][256] tokens */
+  float *ln1, *qkv, *skip, *x_attn, *tacc, *ln2, *hid, *x_ffn;      /* time layer: [slices][rows][256 | 768 | 256 | 256], tacc [slices][frames][256], [slices][rows][256 | d_hid | 256] */
+  float *iln1, *iqkv, *iao, *ix_attn, *iln2, *ihid, *ix_ffn;        /* instrument layer: [islices][rows][256 | 768 | 256 | 256 | 256 | d_hid | 256] */
+  float* part;                        /* [segs][256] tempo partial sums (calls with a tempo output) */
+} etd_debug_beat_taps;
+int etd_beat_debug_stage_taps(etd_beat*, const etd_debug_beat_taps* taps);
 
 /* test hook: the Viterbi kernel of etd_dbn_track alone, on supplied densities: densities_dev fp64 device [T][K] (K = 2 for HMM 0, 3 for a bar HMM; -inf allowed)
  * -> path_out host int32 [T] (state per frame) and *logprob_out (host).  Synchronous, default stream. */

@@ -4,7 +4,7 @@
 Runs only where the reference checkout is available (never on the GPU box).  Weights are ``etude_amd.synth.beat_state_dict`` loaded with ``strict=True`` (the key
 names and shapes are checked against the reference class as a side effect); inputs are ``synth.beat_features``, regenerated from their seeds by the tests, and each
 fixture stores the input's sha256 so that drift in ``synth`` is caught.  Outputs are data only: logits, tempo head and, for T = 37, the conv front-end and
-layer-0 activations (captured by forward hooks).  No weights are written.
+layer-0 activations (captured by forward hooks); ARCHS adds two other architectures (logits and tempo only).  No weights are written.
 
 Usage:  python tests/golden/make_golden_beat.py --reference DIR
 """
@@ -26,6 +26,8 @@ from etude_amd import synth  # noqa: E402
 WEIGHT_SEED = 7
 CASES = [(1, 101), (5, 102), (37, 103), (300, 104), (1100, 105)]        # (T, feature seed), B = 1
 BATCH = (2, 64, (201, 202))                                             # B = 2 forward: T, feature seeds
+# other architectures (logits and tempo only): name, the constructor arguments that differ, T, feature seed, weight seed
+ARCHS = [("archA", dict(instr=3, nlayers=5, d_hid=512, ntoken=3), 70, 301, 11), ("archB", dict(instr=8, nlayers=11), 40, 302, 12)]
 
 
 def sha(a: np.ndarray) -> str:
@@ -73,6 +75,24 @@ def main():
     np.savez_compressed(HERE / "beat_B2.npz", T=np.int64(T), seeds=np.array(seeds, np.int64), weight_seed=np.int64(WEIGHT_SEED),
                         feat_sha256=np.array([sha(f) for f in feats]), logits=logits.numpy().astype(np.float32), tempo=tempo.numpy().astype(np.float32))
     print("beat_B2.npz")
+    arch_goldens(Demixed_DilatedTransformerModel)
+
+
+def arch_goldens(Model):
+    for name, over, T, seed, wseed in ARCHS:
+        dims = synth.beat_dims(**over)
+        model = Model(attn_len=5, instr=dims["instr"], ntoken=dims["ntoken"], dmodel=256, nhead=8, d_hid=dims["d_hid"], nlayers=dims["nlayers"], norm_first=True)
+        sd = synth.beat_state_dict(wseed, dims)
+        model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
+        model.eval()
+        feat = synth.beat_features(seed, T, instr=dims["instr"])
+        with torch.no_grad():
+            logits, tempo = model(torch.from_numpy(feat)[None])
+        lg = logits[0].numpy()
+        assert lg.shape == (T, dims["ntoken"]) and lg.std(0).min() > 1e-2 * max(1.0, np.abs(lg).max()), (name, lg.std(0))
+        np.savez_compressed(HERE / f"beat_{name}.npz", T=np.int64(T), seed=np.int64(seed), weight_seed=np.int64(wseed), feat_sha256=np.array(sha(feat)),
+                            logits=lg.astype(np.float32), tempo=tempo[0].numpy().astype(np.float32), **{k: np.int64(v) for k, v in over.items()})
+        print(f"beat_{name}.npz  {over}  max|logit| {np.abs(lg).max():.3f}  std over frames {lg.std(0)}")
 
 
 if __name__ == "__main__":

@@ -54,6 +54,22 @@ def test_restatement_matches_batch_golden(golden_dir, sd):
         assert np.abs(r["tempo"] - g["tempo"][b]).max() <= 1e-5 * max(1.0, float(np.abs(g["tempo"][b]).max()))
 
 
+@pytest.mark.parametrize("name", ["archA", "archB"])
+def test_restatement_matches_reference_goldens_of_other_architectures(golden_dir, name):
+    """archA: instr 3, nlayers 5 (instrument layers 3 and 4 only), d_hid 512, ntoken 3 at T = 70; archB: instr 8, nlayers 11 at T = 40 (tests/golden/make_golden_beat.py)"""
+    g = np.load(golden_dir / f"beat_{name}.npz")
+    over = {k: int(g[k]) for k in ("instr", "nlayers", "d_hid", "ntoken") if k in g}
+    assert over == (dict(instr=3, nlayers=5, d_hid=512, ntoken=3) if name == "archA" else dict(instr=8, nlayers=11))
+    dims = synth.beat_dims(**over)
+    T = int(g["T"])
+    feat = synth.beat_features(int(g["seed"]), T, instr=dims["instr"])
+    assert _sha(feat) == str(g["feat_sha256"]), "synth.beat_features drifted from the goldens"
+    r = beat_np.forward(synth.beat_state_dict(int(g["weight_seed"]), dims), feat, nlayers=dims["nlayers"])
+    assert r["logits"].shape == g["logits"].shape == (T, dims["ntoken"])
+    assert np.abs(r["logits"] - g["logits"]).max() <= 1e-5 * max(1.0, float(np.abs(g["logits"]).max()))
+    assert np.abs(r["tempo"] - g["tempo"]).max() <= 1e-5 * max(1.0, float(np.abs(g["tempo"]).max()))
+
+
 def test_goldens_are_small_and_nondegenerate(golden_dir):
     for p in sorted(golden_dir.glob("beat_*.npz")):
         assert p.stat().st_size < 512 * 1024, p.name
