@@ -15,6 +15,7 @@ Drop-in surfaces (same names/signatures as the reference):
     etude_amd.AudioAligner          <- etude.data.aligner.AudioAligner behind the feature extraction (exact DTW, transposition search, wp.json cache; csrc/dtw.hip)
     etude_amd.WPDCalculator         <- etude.evaluation.metrics.wpd.WPDCalculator (host arithmetic on the warping path)
     etude_amd.RGCCalculator / IPECalculator / RhythmMetrics  <- etude.evaluation.metrics.rgc / ipe (a ragged batch of note lists; csrc/rhythm.hip)
+    etude_amd.EtudeDataset / BarAttributes / attribute_adherence  <- etude.data.dataset.EtudeDataset (bar attributes, bin edges, training samples; csrc/attributes.hip)
     etude_amd.BeatAnalyzer          <- etude.data.beat_analyzer.BeatAnalyzer (beat_pred.json -> tempo.json; host Python)
 All arithmetic runs in libetude_hip.so (hand-written HIP, see csrc/); importing the heavy
 modules is lazy so that `import etude_amd` works on a box without a GPU.
@@ -33,7 +34,7 @@ __all__ = ["AMTAPC_Extractor", "EtudeDecoder", "EtudeDecoderConfig", "load_etude
            "structuralize_stems_many", "StemFeatures", "mel_filterbank", "AudioAligner", "align_features", "align_features_many", "align_and_filter_many",
            "WPDCalculator", "wpd_many", "AlignFeatures", "ellip_bandpass_sos", "pitch_filterbank", "align_audio_many", "align_and_filter_audio_many",
            "TuningEstimator", "estimate_tuning", "RhythmMetrics", "RGCCalculator", "IPECalculator", "get_onsets_from_file", "rhythm_metrics_for_notes",
-           "evaluate_many"]
+           "evaluate_many", "BarAttributes", "EtudeDataset", "split_into_bars", "calculate_bin_edges", "save_bin_edges", "load_bin_edges", "attribute_adherence"]
 
 
 def __getattr__(name):
@@ -70,6 +71,9 @@ def __getattr__(name):
     if name in ("RhythmMetrics", "RGCCalculator", "IPECalculator", "get_onsets_from_file", "rhythm_metrics_for_notes", "evaluate_many"):
         from . import rhythm
         return getattr(rhythm, name)
+    if name in ("BarAttributes", "EtudeDataset", "split_into_bars", "calculate_bin_edges", "save_bin_edges", "load_bin_edges", "attribute_adherence"):
+        from . import attributes
+        return getattr(attributes, name)
     if name in ("AudioAligner", "align_features", "align_features_many", "align_and_filter_many", "align_audio_many", "align_and_filter_audio_many"):
         from . import aligner
         return getattr(aligner, name)

@@ -92,6 +92,10 @@ class RhythmCfg(_SizedCfg):
                 + [("min_ioi", C.c_double), ("max_ioi", C.c_double), ("random_host", C.POINTER(C.c_double))])
 
 
+class AttrCfg(_SizedCfg):
+    _fields_ = [("struct_bytes", C.c_int), ("type_pos", C.c_int), ("type_note", C.c_int), ("type_duration", C.c_int)]
+
+
 # etd_tuning_debug_layout's int64 [7] (include/etude_hip_debug.h), in order
 TUNING_LAYOUT = ("F", "G", "off_part", "off_Y", "off_Yi", "off_R", "off_sim")
 
@@ -294,6 +298,12 @@ SIGNATURES = {
     "etd_rhythm_check": (C.c_int, [C.c_void_p, c_i64_p, C.c_int]),
     "etd_rhythm_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_i64_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "etd_rhythm_debug_logioi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "etd_attr_limits": (C.c_int, [c_int_p, c_int_p, c_int_p, c_int_p]),
+    "etd_attr_create": (C.c_int, [C.POINTER(AttrCfg), C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "etd_attr_destroy": (None, [C.c_void_p]),
+    "etd_attr_check": (C.c_int, [C.c_void_p, c_i64_p, C.c_int]),
+    "etd_attr_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_i64_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, c_i64_p, C.c_int, C.c_void_p, C.c_int,
+                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "etd_debug_decoder_trace_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.POINTER(C.c_int), C.c_void_p]),
 }
 

@@ -13,6 +13,7 @@
 // debugger; nothing in the library calls it there.
 #include "rhythm.h"
 #include "prof.h"
+#include "np_sum.h"
 
 #include <cmath>
 
@@ -39,56 +40,6 @@ struct RhShared {
 namespace {
 
 typedef unsigned long long u64;
-
-// numpy's add.reduce over n <= 128 contiguous doubles a(i): below 8 sequential, else eight accumulators over whole groups of 8, combined pairwise, then the remainder
-template <class F>
-RH_HD double rh_sum_leaf(int n, F a) {
-  if (n < 8) {
-    double res = 0.0;
-    for (int i = 0; i < n; ++i) res += a(i);
-    return res;
-  }
-  double r0 = a(0), r1 = a(1), r2 = a(2), r3 = a(3), r4 = a(4), r5 = a(5), r6 = a(6), r7 = a(7);
-  int i = 8;
-  for (; i < n - (n % 8); i += 8) {
-    r0 += a(i); r1 += a(i + 1); r2 += a(i + 2); r3 += a(i + 3); r4 += a(i + 4); r5 += a(i + 5); r6 += a(i + 6); r7 += a(i + 7);
-  }
-  double res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
-  for (; i < n; ++i) res += a(i);
-  return res;
-}
-
-// ... over any n: above 128 split at n / 2 rounded down to a multiple of 8, left + right (the recursion unrolled onto a small stack; one lane runs it)
-template <class F>
-RH_HD double rh_sum_np(int n, F a) {
-  struct Fr { int off, n, stage; double left; };
-  Fr st[20];
-  int sp = 0;
-  st[sp].off = 0; st[sp].n = n; st[sp].stage = 0; st[sp].left = 0.0; ++sp;
-  double ret = 0.0;
-  while (sp > 0) {
-    Fr& f = st[sp - 1];
-    if (f.stage == 0) {
-      if (f.n <= 128) {
-        const int off = f.off;
-        ret = rh_sum_leaf(f.n, [&](int i) { return a(off + i); });
-        --sp;
-        continue;
-      }
-      int n2 = f.n / 2; n2 -= n2 % 8;
-      f.stage = 1;
-      st[sp].off = f.off; st[sp].n = n2; st[sp].stage = 0; st[sp].left = 0.0; ++sp;
-    } else if (f.stage == 1) {
-      int n2 = f.n / 2; n2 -= n2 % 8;
-      f.left = ret; f.stage = 2;
-      st[sp].off = f.off + n2; st[sp].n = f.n - n2; st[sp].stage = 0; st[sp].left = 0.0; ++sp;
-    } else {
-      ret = f.left + ret;
-      --sp;
-    }
-  }
-  return ret;
-}
 
 // ascending bitonic sort of P (a power of two) keys in LDS; the caller has synchronised; synchronised on return
 RH_HD void rh_sort(u64* key, int P, int tid, int T) {
@@ -241,7 +192,7 @@ RH_HD void rh_cover(const RhArgs& a, int b, double* X, u64* K, unsigned char* L,
             double v = -1.0;                                 // (skipped: below 0.01)
             if (!(tc < 0.01)) {
               const double* top = s->top;
-              v = rh_sum_leaf(n_top, [&](int j) { const double r = top[j] / tc; return fabs(r - rint(r)); }) / (double)n_top;
+              v = np_sum_leaf(n_top, [&](int j) { const double r = top[j] / tc; return fabs(r - rint(r)); }) / (double)n_top;
             }
             s->dred[c] = v;
           }
@@ -282,7 +233,7 @@ RH_HD void rh_cover(const RhArgs& a, int b, double* X, u64* K, unsigned char* L,
         ipe = 3;
       } else {
         double* D = (double*)K;                              // the k-means++ distances take the keys' place
-        if (tid == 0) s->mean = rh_sum_np(m, [&](int i) { return X[i]; }) / (double)m;
+        if (tid == 0) s->mean = np_sum_all(m, [&](int i) { return X[i]; }) / (double)m;
         RH_SYNC();
         const double mean = s->mean;
         for (int i = tid; i < m; i += T) {
@@ -292,7 +243,7 @@ RH_HD void rh_cover(const RhArgs& a, int b, double* X, u64* K, unsigned char* L,
         }
         RH_SYNC();
         if (tid == 0) {
-          s->tol = (rh_sum_np(m, [&](int i) { return X[i] * X[i]; }) / (double)m) * 1e-4;
+          s->tol = (np_sum_all(m, [&](int i) { return X[i] * X[i]; }) / (double)m) * 1e-4;
           // the first centre: RandomState.choice with uniform p: cdf = cumsum(1 / m) / cdf[-1], searchsorted(side = right)
           const double p = 1.0 / (double)m;
           double last = 0.0;

@@ -32,6 +32,8 @@
  *   etd_tuning_run        estimate_tuning(audio, fs) of                  etude/data/aligner.py:100-101
  *                         AudioAligner._compute_alignment
  *   etd_rhythm_run        RGCCalculator / IPECalculator .calculate       etude/evaluation/metrics/rgc.py, ipe.py
+ *   etd_attr_run          EtudeDataset._extract_bar_features,             etude/data/dataset.py:204-270, 335-339
+ *                         _compute_musical_attributes, _get_attribute_bin_id
  *
  * Conventions: every function returns 0 on success or a negative errno-style code (ETD_E*); the
  * message is available from etd_last_error() (thread-local).  "dev" pointers are device (HBM)
@@ -560,6 +562,44 @@ void etd_rhythm_destroy(etd_rhythm*);
 int etd_rhythm_check(const etd_rhythm*, const int64_t* offsets_host, int n_covers);
 int etd_rhythm_run(etd_rhythm*, const double* onsets_dev, const int64_t* offsets_dev, const int64_t* offsets_host, int n_covers, double* out_dev, int32_t* status_dev,
                    void* stream);
+
+/* ------------------------------------------------------------------ bar attributes (token ids of (condition bar, target bar) pairs -> the four attributes the decoder is
+ * conditioned on).  EtudeDataset._extract_bar_features, _compute_musical_attributes and _get_attribute_bin_id (etude/data/dataset.py:204-270, 335-339) for a ragged batch
+ * of pairs: integer counting plus one fp64 mean per pair, the mean's terms in ascending Pos value and numpy's order.  DESIGN.md 4i is the contract. */
+typedef struct etd_attr etd_attr;
+typedef struct {
+  int struct_bytes;          /* sizeof(etd_attr_cfg) of the caller: a mismatch is ETD_EINVAL */
+  int type_pos;              /* 1, 2, 3: the codes the event table uses for Pos, Note and Duration events (TinyREMITokenizer.event_table); every other code is an */
+  int type_note;             /* event the attributes ignore */
+  int type_duration;
+} etd_attr_cfg;
+/* HOST ONLY: the constants of this build: tokens per bar (4 096), pairs and bars per call (2^20), the widest range of Pos values a vocabulary may hold (4 096), edges
+ * per attribute (2); any may be NULL */
+int etd_attr_limits(int* max_bar_tokens, int* max_pairs, int* max_pos_range, int* max_edges);
+/* event_table_host: int32 [vocab_size][2] = (type, value) per token id.  The per-pair table in LDS is sized here from the range of the Pos values; a range above 4 096,
+ * a Duration value that could overflow the int32 total, or type codes that coincide are ETD_EINVAL.  With a GPU the table is copied to the current device here; without
+ * one the handle still serves etd_attr_check, and etd_attr_run refuses it. */
+int etd_attr_create(const etd_attr_cfg* cfg, const int32_t* event_table_host, int vocab_size, etd_attr** out);
+void etd_attr_destroy(etd_attr*);
+/* HOST ONLY: what etd_attr_run refuses about one side's bars, with its message, before anything touches the device: n_bars outside 1 .. 2^20, offsets_host[0] != 0,
+ * decreasing offsets, a bar above 4 096 tokens */
+int etd_attr_check(const etd_attr*, const int64_t* offsets_host, int n_bars);
+/* Source bar b is src_ids_dev[src_offsets[b] .. src_offsets[b + 1]) (DEVICE int32 ids; offsets: DEVICE int64 [n_src_bars + 1] and the same numbers on the HOST), the
+ * target side likewise, in the same id buffer or another.  Pair i takes source bar src_index_dev[i] and target bar tgt_index_dev[i] (DEVICE int32 [n_pairs]); a NULL
+ * index is the identity and needs n_bars == n_pairs -- the index lets the condition bars of a song be uploaded once for all its attribute tuples.
+ * features_dev: DEVICE int32 [n_pairs][6] = note_count, pos_event_count, total_duration_in_16ths of the source, then of the target.  attributes_dev: DEVICE fp64
+ * [n_pairs][4] = relative_polyphony, relative_rhythmic_intensity, relative_note_sustain, pitch_overlap_ratio (_MODEL_ATTRIBUTES order).  edges_host: HOST fp64 [4][2]
+ * with n_edges_host int32 [4] (0 .. 2 ascending finite edges per attribute, np.unique's output; no edges = bin 1) and bins_dev: DEVICE int32 [n_pairs][4] =
+ * np.digitize(value, edges); all three NULL = raw values only.  status_dev: DEVICE int32 [n_pairs]:
+ *   bit 0         an id outside [0, vocab_size) in either bar: it counts as an event the attributes ignore, the table is not read
+ *   bit 1         a bar index outside its side's bars: that bar counts as empty
+ *   bits 8 .. 20  the positions that hold a note in either bar (the terms of the pitch-overlap mean)
+ * Refused with ETD_EINVAL and a message before anything is launched: what etd_attr_check refuses, n_pairs outside 1 .. 2^20, edges that are not ascending and finite,
+ * a NULL output, a handle created without a GPU.  ONE launch whatever n_pairs, one wavefront per pair, nothing allocated, no synchronisation.  A pair's numbers depend on
+ * its two bars alone: bit-identical alone, in any batch and from run to run.  Asynchronous on `stream`. */
+int etd_attr_run(etd_attr*, const int32_t* src_ids_dev, const int64_t* src_offsets_dev, const int64_t* src_offsets_host, int n_src_bars, const int32_t* src_index_dev,
+                 const int32_t* tgt_ids_dev, const int64_t* tgt_offsets_dev, const int64_t* tgt_offsets_host, int n_tgt_bars, const int32_t* tgt_index_dev, int n_pairs,
+                 const double* edges_host, const int32_t* n_edges_host, int32_t* features_dev, double* attributes_dev, int32_t* bins_dev, int32_t* status_dev, void* stream);
 
 #ifdef __cplusplus
 }
