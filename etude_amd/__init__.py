@@ -34,7 +34,8 @@ __all__ = ["AMTAPC_Extractor", "EtudeDecoder", "EtudeDecoderConfig", "load_etude
            "structuralize_stems_many", "StemFeatures", "mel_filterbank", "AudioAligner", "align_features", "align_features_many", "align_and_filter_many",
            "WPDCalculator", "wpd_many", "AlignFeatures", "ellip_bandpass_sos", "pitch_filterbank", "align_audio_many", "align_and_filter_audio_many",
            "TuningEstimator", "estimate_tuning", "RhythmMetrics", "RGCCalculator", "IPECalculator", "get_onsets_from_file", "rhythm_metrics_for_notes",
-           "evaluate_many", "BarAttributes", "EtudeDataset", "split_into_bars", "calculate_bin_edges", "save_bin_edges", "load_bin_edges", "attribute_adherence"]
+           "evaluate_many", "BarAttributes", "EtudeDataset", "split_into_bars", "calculate_bin_edges", "save_bin_edges", "load_bin_edges", "attribute_adherence",
+           "DecoderTrainer", "cosine_schedule_with_warmup", "init_decoder_state"]
 
 
 def __getattr__(name):
@@ -83,6 +84,9 @@ def __getattr__(name):
     if name in ("BeatAnalyzer", "structuralize_many", "structuralize_stems_many"):
         from . import beat_analyzer
         return getattr(beat_analyzer, name)
+    if name in ("DecoderTrainer", "cosine_schedule_with_warmup", "init_decoder_state"):
+        from . import train
+        return getattr(train, name)
     if name in ("ExtractorConfig", "DecoderConfig", "HFTConfig", "BeatDetectorConfig", "BeatDetectorModelConfig"):
         from . import config
         return getattr(config, name)

@@ -304,6 +304,23 @@ SIGNATURES = {
     "etd_attr_check": (C.c_int, [C.c_void_p, c_i64_p, C.c_int]),
     "etd_attr_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_i64_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, c_i64_p, C.c_int, C.c_void_p, C.c_int,
                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "etd_dtrain_workspace_bytes": (C.c_longlong, [C.POINTER(DecCfg), C.c_int]),
+    "etd_dtrain_create": (C.c_int, [C.POINTER(DecCfg), C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), c_i64_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.POINTER(C.c_void_p)]),
+    "etd_dtrain_destroy": (None, [C.c_void_p]),
+    "etd_dtrain_bytes": (C.c_longlong, [C.c_void_p, C.c_int]),
+    "etd_dtrain_forward_backward": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_float, c_f32_p, c_i32_p, C.c_void_p]),
+    "etd_dtrain_zero_grad": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "etd_dtrain_grad_norm": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
+    "etd_dtrain_clip_and_step": (C.c_int, [C.c_void_p] + [C.c_double] * 6 + [C.POINTER(C.c_double), C.c_void_p]),
+    "etd_dtrain_set_step": (C.c_int, [C.c_void_p, C.c_longlong]),
+    "etd_dtrain_get_step": (C.c_longlong, [C.c_void_p]),
+    "etd_dtrain_read_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "etd_dtrain_read_grad": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "etd_dtrain_read_moment": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "etd_dtrain_write_moment": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "etd_debug_dtrain_gemm": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "etd_debug_dtrain_attn": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "etd_debug_decoder_trace_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.POINTER(C.c_int), C.c_void_p]),
 }
 

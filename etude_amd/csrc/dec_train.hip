@@ -1,0 +1,985 @@
+// Training engine of the EtudeDecoder: forward with saved activations, backward of F.cross_entropy for every parameter, gradient accumulation, global-norm
+// clipping and AdamW (dec_train.h).  The model is the reference's (etude/models/etude_decoder.py:148-206 over HF GPT-NeoX) in its fp32 arithmetic;
+// dropout is 0 in the reference's configuration, so train mode computes what eval mode computes.
+//
+// Arithmetic: fp32 operands and fp32 accumulation everywhere.  The linear layers' products (forward, input gradient, weight gradient) run on
+// v_mfma_f32_32x32x2_f32; the attention kernels keep one query (or key) row per lane and use fmaf chains.  The f16-split planes of gemm3.h are not used: they
+// need a proven bound of their operands, which gradients do not have.
+// Order: no floating-point atomics.  Every sum -- a GEMM's K chain, a column reduction over the batch rows, an embedding row's gradient, the norm -- runs in an
+// order fixed by the shapes of the call, so the same call on the same inputs gives the same bits.
+#include "dec_train.h"
+
+#include <math.h>
+
+#include <algorithm>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "etude_hip.h"
+#include "etude_hip_debug.h"
+#include "host_util.h"
+#include "prof.h"
+
+#define ETD_IGNORE_LABEL (-100)
+
+// ================================================================================================
+// the GEMM family
+// ================================================================================================
+#define TG_BK 32
+#define TG_CH 8      // accumulator chains per output element
+#define TG_LD 65     // 64 + 1: a wave that stores 32 consecutive k of two rows hits 64 distinct (bank, half) pairs
+
+// AKC / BKC: k is the contiguous index of the operand in memory (decides which way the 256 threads sweep the tile, so that global loads coalesce)
+template <bool KC>
+__device__ __forceinline__ void tg_coords(int t, int r, int& i, int& k) {
+  if (KC) { k = t & 31; i = (t >> 5) + 8 * r; }
+  else { i = t & 63; k = (t >> 6) + 4 * r; }
+}
+
+template <bool AKC, bool BKC>
+__global__ __launch_bounds__(256) void k_tgemm(int M, int N, int K, const float* __restrict__ A, long long sai, long long sak, const float* __restrict__ B,
+                                               long long sbk, long long sbj, const float* __restrict__ bias, float* __restrict__ C, int ldc, int accumulate) {
+  __shared__ float As[TG_BK][TG_LD], Bs[TG_BK][TG_LD];
+  const int t = threadIdx.x, l = t & 63, w = t >> 6;
+  const int i0 = blockIdx.y * 64, j0 = blockIdx.x * 64;
+  const int wr = w >> 1, wc = w & 1, half = l >> 5, l31 = l & 31;
+  float ra[8], rb[8];
+  // TG_CH accumulator chains: MFMA j of every K tile adds into chain j % TG_CH, and the chains are added pairwise at the end.  Each output element's sum is then
+  // TG_CH interleaved chains of K / TG_CH terms instead of one of K terms -- the rounding error of a long batch-row reduction (dW over thousands of rows) grows
+  // with the chain's length -- in an order that the shape alone fixes.
+  f32x16 acc[TG_CH];
+#pragma unroll
+  for (int c = 0; c < TG_CH; ++c)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[c][r] = 0.f;
+#define TG_LOAD(k0)                                                                                         \
+  _Pragma("unroll") for (int r = 0; r < 8; ++r) {                                                           \
+    int i, k;                                                                                               \
+    tg_coords<AKC>(t, r, i, k);                                                                             \
+    const long long gi = i0 + i, gk = (k0) + k;                                                             \
+    ra[r] = (gi < M && gk < K) ? A[gi * sai + gk * sak] : 0.f;                                              \
+    tg_coords<BKC>(t, r, i, k);                                                                             \
+    const long long gj = j0 + i, gk2 = (k0) + k;                                                            \
+    rb[r] = (gj < N && gk2 < K) ? B[gk2 * sbk + gj * sbj] : 0.f;                                            \
+  }
+  TG_LOAD(0)
+  for (int k0 = 0; k0 < K; k0 += TG_BK) {
+    __syncthreads();                                   // the previous tile has been read
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      int i, k;
+      tg_coords<AKC>(t, r, i, k);
+      As[k][i] = ra[r];
+      tg_coords<BKC>(t, r, i, k);
+      Bs[k][i] = rb[r];
+    }
+    __syncthreads();
+    if (k0 + TG_BK < K) { TG_LOAD(k0 + TG_BK) }        // the next tile's loads fly while this one is multiplied
+#pragma unroll
+    for (int kk = 0; kk < TG_BK; kk += 2)
+      acc[(kk >> 1) % TG_CH] = __builtin_amdgcn_mfma_f32_32x32x2f32(As[kk + half][wr * 32 + l31], Bs[kk + half][wc * 32 + l31], acc[(kk >> 1) % TG_CH], 0, 0, 0);
+  }
+#undef TG_LOAD
+#pragma unroll
+  for (int w2 = 1; w2 < TG_CH; w2 *= 2)
+#pragma unroll
+    for (int c = 0; c + w2 < TG_CH; c += 2 * w2)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[c][r] += acc[c + w2][r];
+  const int col = j0 + wc * 32 + l31;
+  if (col < N) {
+    const float bv = bias ? bias[col] : 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int row = i0 + wr * 32 + acc_row(r, half);
+      if (row < M) {
+        float* p = C + (long long)row * ldc + col;
+        float v = acc[0][r] + bv;
+        if (accumulate) v = *p + v;
+        *p = v;
+      }
+    }
+  }
+}
+
+int launch_tgemm(int form, int M, int N, int K, const float* A, int lda, const float* B, int ldb, const float* bias, float* C, int ldc, bool accumulate,
+                 hipStream_t st) {
+  if (M < 1 || N < 1 || K < 1 || !A || !B || !C) ETD_FAIL(ETD_EINVAL, "tgemm: bad shape M=%d N=%d K=%d", M, N, K);
+  const int a_row = form == ETD_TG_TN ? M : K, b_row = form == ETD_TG_NT ? K : N;
+  if (lda < a_row || ldb < b_row || ldc < N) ETD_FAIL(ETD_EINVAL, "tgemm: a row stride is shorter than its row (lda=%d ldb=%d ldc=%d)", lda, ldb, ldc);
+  const dim3 grid((N + 63) / 64, (M + 63) / 64), block(256);
+  if (grid.y > 65535u) ETD_FAIL(ETD_EINVAL, "tgemm: M=%d is above 65535 row tiles", M);
+  const int acc = accumulate ? 1 : 0;
+  switch (form) {
+    case ETD_TG_NT: hipLaunchKernelGGL((k_tgemm<true, true>), grid, block, 0, st, M, N, K, A, (long long)lda, 1LL, B, 1LL, (long long)ldb, bias, C, ldc, acc); break;
+    case ETD_TG_NN: hipLaunchKernelGGL((k_tgemm<true, false>), grid, block, 0, st, M, N, K, A, (long long)lda, 1LL, B, (long long)ldb, 1LL, bias, C, ldc, acc); break;
+    case ETD_TG_TN: hipLaunchKernelGGL((k_tgemm<false, false>), grid, block, 0, st, M, N, K, A, 1LL, (long long)lda, B, (long long)ldb, 1LL, bias, C, ldc, acc); break;
+    default: ETD_FAIL(ETD_EINVAL, "tgemm: unknown form %d", form);
+  }
+  HIP_TRY(hipGetLastError());
+  return ETD_OK;
+}
+
+// ================================================================================================
+// attention: one row per lane, the other side's tile in LDS (every lane reads the same LDS address: a broadcast)
+// ================================================================================================
+// loads rows [t0, t0 + 64) x 64 floats of one head's slice (row stride ld floats) into tile[64][16] float4; rows at or past `len` read as 0
+__device__ __forceinline__ void tile_load(f32x4 (*tile)[16], const float* __restrict__ base, long long ld, int t0, int len, int lane) {
+  for (int e = lane; e < 64 * 16; e += 64) {
+    const int r = e >> 4, c = e & 15;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (t0 + r < len) v = *(const f32x4*)(base + (long long)(t0 + r) * ld + 4 * c);
+    tile[r][c] = v;
+  }
+}
+__device__ __forceinline__ float dot64(const float (&a)[64], const f32x4* __restrict__ row) {
+  float d = 0.f;
+#pragma unroll
+  for (int c = 0; c < 16; ++c) {
+    const f32x4 k4 = row[c];
+    d = fmaf(a[4 * c], k4[0], d); d = fmaf(a[4 * c + 1], k4[1], d); d = fmaf(a[4 * c + 2], k4[2], d); d = fmaf(a[4 * c + 3], k4[3], d);
+  }
+  return d;
+}
+__device__ __forceinline__ void axpy64(float (&acc)[64], float s, const f32x4* __restrict__ row) {
+#pragma unroll
+  for (int c = 0; c < 16; ++c) {
+    const f32x4 v4 = row[c];
+    acc[4 * c] = fmaf(s, v4[0], acc[4 * c]); acc[4 * c + 1] = fmaf(s, v4[1], acc[4 * c + 1]);
+    acc[4 * c + 2] = fmaf(s, v4[2], acc[4 * c + 2]); acc[4 * c + 3] = fmaf(s, v4[3], acc[4 * c + 3]);
+  }
+}
+__device__ __forceinline__ void row_load(float (&a)[64], const float* __restrict__ p) {
+#pragma unroll
+  for (int c = 0; c < 16; ++c) {
+    const f32x4 v = *(const f32x4*)(p + 4 * c);
+    a[4 * c] = v[0]; a[4 * c + 1] = v[1]; a[4 * c + 2] = v[2]; a[4 * c + 3] = v[3];
+  }
+}
+__device__ __forceinline__ void row_store(float* __restrict__ p, const float (&a)[64], float s) {
+#pragma unroll
+  for (int c = 0; c < 16; ++c) {
+    const f32x4 v = {a[4 * c] * s, a[4 * c + 1] * s, a[4 * c + 2] * s, a[4 * c + 3] * s};
+    *(f32x4*)(p + 4 * c) = v;
+  }
+}
+
+// grid (query tiles, heads, sequences), 64 threads: lane = query row
+__global__ __launch_bounds__(64) void k_tattn_fwd(const float* __restrict__ qkv, int nh, const int* __restrict__ row0, const int* __restrict__ lens,
+                                                  float* __restrict__ O, float* __restrict__ lse) {
+  __shared__ f32x4 Ks[64][16], Vs[64][16];
+  const int qt = blockIdx.x, h = blockIdx.y, s = blockIdx.z, lane = threadIdx.x;
+  const int len = lens[s];
+  if (qt * 64 >= len) return;                          // (uniform)
+  const long long ld = 3LL * nh * 64;
+  const float* base = qkv + (long long)row0[s] * ld + (long long)h * 192;
+  const int qi = qt * 64 + lane;
+  const bool valid = qi < len;
+  float q[64], o[64];
+#pragma unroll
+  for (int d = 0; d < 64; ++d) { q[d] = 0.f; o[d] = 0.f; }
+  if (valid) row_load(q, base + (long long)qi * ld);
+  float m = -INFINITY, lsum = 0.f;
+  for (int kt = 0; kt <= qt; ++kt) {
+    __syncthreads();
+    tile_load(Ks, base + 64, ld, kt * 64, len, lane);
+    tile_load(Vs, base + 128, ld, kt * 64, len, lane);
+    __syncthreads();
+    if (!valid) continue;
+    const int kbase = kt * 64;
+    for (int c = 0; c < 64; c += 16) {
+      if (kbase + c > qi) break;
+      float sc[16], cm = m;
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const float d = dot64(q, Ks[c + j]) * 0.125f;
+        sc[j] = (kbase + c + j <= qi) ? d : -INFINITY;
+        cm = fmaxf(cm, sc[j]);
+      }
+      const float alpha = expf(m - cm);              // (m = -inf on the first chunk: exp(-inf) = 0, and key 0 is never masked, so cm is finite)
+      lsum *= alpha;
+#pragma unroll
+      for (int d = 0; d < 64; ++d) o[d] *= alpha;
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const float p = expf(sc[j] - cm);
+        lsum += p;
+        axpy64(o, p, Vs[c + j]);
+      }
+      m = cm;
+    }
+  }
+  if (valid) {
+    const long long r = row0[s] + qi;
+    row_store(O + r * nh * 64 + h * 64, o, 1.f / lsum);
+    lse[r * nh + h] = m + logf(lsum);
+  }
+}
+
+// dQ and D: grid (query tiles, heads, sequences), lane = query row.  dq is written in the rotated space of q.
+__global__ __launch_bounds__(64) void k_tattn_dq(const float* __restrict__ qkv, const float* __restrict__ O, const float* __restrict__ lse,
+                                                 const float* __restrict__ dO, int nh, const int* __restrict__ row0, const int* __restrict__ lens,
+                                                 float* __restrict__ Dbuf, float* __restrict__ dqkv) {
+  __shared__ f32x4 Ks[64][16], Vs[64][16];
+  const int qt = blockIdx.x, h = blockIdx.y, s = blockIdx.z, lane = threadIdx.x;
+  const int len = lens[s];
+  if (qt * 64 >= len) return;
+  const long long ld = 3LL * nh * 64;
+  const float* base = qkv + (long long)row0[s] * ld + (long long)h * 192;
+  const int qi = qt * 64 + lane;
+  const bool valid = qi < len;
+  const long long r = (long long)row0[s] + (valid ? qi : 0);
+  float q[64], go[64], dq[64];
+#pragma unroll
+  for (int d = 0; d < 64; ++d) { q[d] = 0.f; go[d] = 0.f; dq[d] = 0.f; }
+  float D = 0.f, L = 0.f;
+  if (valid) {
+    row_load(q, base + (long long)qi * ld);
+    row_load(go, dO + r * nh * 64 + h * 64);
+    const float* orow = O + r * nh * 64 + h * 64;
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+      const f32x4 v = *(const f32x4*)(orow + 4 * c);
+      D = fmaf(go[4 * c], v[0], D); D = fmaf(go[4 * c + 1], v[1], D); D = fmaf(go[4 * c + 2], v[2], D); D = fmaf(go[4 * c + 3], v[3], D);
+    }
+    L = lse[r * nh + h];
+    Dbuf[r * nh + h] = D;
+  }
+  for (int kt = 0; kt <= qt; ++kt) {
+    __syncthreads();
+    tile_load(Ks, base + 64, ld, kt * 64, len, lane);
+    tile_load(Vs, base + 128, ld, kt * 64, len, lane);
+    __syncthreads();
+    if (!valid) continue;
+    const int kbase = kt * 64;
+    const int jn = min(64, qi - kbase + 1);           // keys kbase .. qi
+    for (int j = 0; j < jn; ++j) {
+      const float p = expf(dot64(q, Ks[j]) * 0.125f - L);
+      const float dp = dot64(go, Vs[j]);
+      axpy64(dq, p * (dp - D), Ks[j]);
+    }
+  }
+  if (valid) row_store(dqkv + r * ld + (long long)h * 192, dq, 0.125f);
+}
+
+// dK and dV: grid (key tiles, heads, sequences), lane = key row; queries ascending
+__global__ __launch_bounds__(64) void k_tattn_dkv(const float* __restrict__ qkv, const float* __restrict__ lse, const float* __restrict__ dO,
+                                                  const float* __restrict__ Dbuf, int nh, const int* __restrict__ row0, const int* __restrict__ lens,
+                                                  float* __restrict__ dqkv) {
+  __shared__ f32x4 Qs[64][16], Gs[64][16];
+  __shared__ float Ls[64], Ds[64];
+  const int kt = blockIdx.x, h = blockIdx.y, s = blockIdx.z, lane = threadIdx.x;
+  const int len = lens[s];
+  if (kt * 64 >= len) return;
+  const long long ld = 3LL * nh * 64, r0 = row0[s];
+  const float* base = qkv + r0 * ld + (long long)h * 192;
+  const float* gbase = dO + r0 * nh * 64 + h * 64;
+  const int kj = kt * 64 + lane;
+  const bool valid = kj < len;
+  float k[64], v[64], dk[64], dv[64];
+#pragma unroll
+  for (int d = 0; d < 64; ++d) { k[d] = 0.f; v[d] = 0.f; dk[d] = 0.f; dv[d] = 0.f; }
+  if (valid) { row_load(k, base + (long long)kj * ld + 64); row_load(v, base + (long long)kj * ld + 128); }
+  const int n_tiles = (len + 63) / 64;
+  for (int qt = kt; qt < n_tiles; ++qt) {
+    __syncthreads();
+    tile_load(Qs, base, ld, qt * 64, len, lane);
+    tile_load(Gs, gbase, (long long)nh * 64, qt * 64, len, lane);
+    {
+      const int qi = qt * 64 + lane;
+      Ls[lane] = qi < len ? lse[(r0 + qi) * nh + h] : 0.f;
+      Ds[lane] = qi < len ? Dbuf[(r0 + qi) * nh + h] : 0.f;
+    }
+    __syncthreads();
+    if (!valid) continue;
+    const int in = min(64, len - qt * 64);
+    const int i_first = max(0, kj - qt * 64);          // queries at or after this key
+    for (int i = i_first; i < in; ++i) {
+      const float p = expf(dot64(k, Qs[i]) * 0.125f - Ls[i]);
+      axpy64(dv, p, Gs[i]);
+      const float dp = dot64(v, Gs[i]);
+      axpy64(dk, p * (dp - Ds[i]), Qs[i]);
+    }
+  }
+  if (valid) {
+    row_store(dqkv + (r0 + kj) * ld + (long long)h * 192 + 64, dk, 0.125f);
+    row_store(dqkv + (r0 + kj) * ld + (long long)h * 192 + 128, dv, 1.f);
+  }
+}
+
+static int attn_grid(int nh, int n_seq, int max_len, dim3* g) {
+  if (nh < 1 || n_seq < 1 || max_len < 1) ETD_FAIL(ETD_EINVAL, "train attention: bad shape heads=%d sequences=%d length=%d", nh, n_seq, max_len);
+  if (n_seq > 65535 || nh > 65535) ETD_FAIL(ETD_EINVAL, "train attention: more than 65535 sequences or heads in one call");
+  *g = dim3((max_len + 63) / 64, nh, n_seq);
+  return ETD_OK;
+}
+int launch_tattn_fwd(const float* qkv, int nh, const int* row0, const int* len, int n_seq, int max_len, float* O, float* lse, hipStream_t st) {
+  dim3 g;
+  ETD_TRY(attn_grid(nh, n_seq, max_len, &g));
+  hipLaunchKernelGGL(k_tattn_fwd, g, dim3(64), 0, st, qkv, nh, row0, len, O, lse);
+  HIP_TRY(hipGetLastError());
+  return ETD_OK;
+}
+int launch_tattn_bwd(const float* qkv, const float* O, const float* lse, const float* dO, int nh, const int* row0, const int* len, int n_seq, int max_len,
+                     float* Dbuf, float* dqkv, hipStream_t st) {
+  dim3 g;
+  ETD_TRY(attn_grid(nh, n_seq, max_len, &g));
+  hipLaunchKernelGGL(k_tattn_dq, g, dim3(64), 0, st, qkv, O, lse, dO, nh, row0, len, Dbuf, dqkv);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_tattn_dkv, g, dim3(64), 0, st, qkv, lse, dO, Dbuf, nh, row0, len, dqkv);
+  HIP_TRY(hipGetLastError());
+  return ETD_OK;
+}
+
+// ================================================================================================
+// row and elementwise kernels
+// ================================================================================================
+// rotate-half RoPE on the first 16 dims of q and k of every head, in place; sign = +1 forward, -1 the inverse rotation (backward).  tab [max_pos][16] = cos | sin
+__global__ void k_trope(float* __restrict__ qkv, int nh, int M, const int* __restrict__ pos, const float* __restrict__ tab, float sign) {
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;      // (row, head, q|k, i < 8)
+  if (e >= (long long)M * nh * 16) return;
+  const int i = (int)(e & 7), which = (int)((e >> 3) & 1), h = (int)((e >> 4) % nh);
+  const long long r = (e >> 4) / nh;
+  float* p = qkv + r * 3LL * nh * 64 + (long long)h * 192 + which * 64;
+  const float c = tab[pos[r] * 16 + i], sn = sign * tab[pos[r] * 16 + 8 + i];
+  const float x1 = p[i], x2 = p[i + 8];
+  p[i] = x1 * c - x2 * sn;
+  p[i + 8] = x2 * c + x1 * sn;
+}
+
+// LayerNorm statistics of each row + up to two normalised outputs (the two LayerNorms of a GPT-NeoX layer read the same input).  One wave per row.
+__global__ __launch_bounds__(64) void k_tln_fwd(const float* __restrict__ x, int M, int H, float eps, float* __restrict__ mean, float* __restrict__ rstd,
+                                                const float* __restrict__ g1, const float* __restrict__ b1, float* __restrict__ y1,
+                                                const float* __restrict__ g2, const float* __restrict__ b2, float* __restrict__ y2) {
+  const int r = blockIdx.x, lane = threadIdx.x;
+  const float* xr = x + (long long)r * H;
+  float s = 0.f;
+  for (int c = lane; c < H; c += 64) s += xr[c];
+  const float mu = wave_sum(s) / (float)H;
+  float q = 0.f;
+  for (int c = lane; c < H; c += 64) { const float d = xr[c] - mu; q = fmaf(d, d, q); }
+  const float rs = 1.f / sqrtf(wave_sum(q) / (float)H + eps);
+  if (lane == 0 && mean) { mean[r] = mu; rstd[r] = rs; }
+  for (int c = lane; c < H; c += 64) {
+    const float xh = (xr[c] - mu) * rs;
+    if (y1) y1[(long long)r * H + c] = xh * g1[c] + b1[c];
+    if (y2) y2[(long long)r * H + c] = xh * g2[c] + b2[c];
+  }
+}
+// dx += rstd * (dy g - mean(dy g) - xhat mean(dy g xhat)); one wave per row
+__global__ __launch_bounds__(64) void k_tln_bwd(const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ mean,
+                                                const float* __restrict__ rstd, const float* __restrict__ g, int H, float* __restrict__ dx) {
+  const int r = blockIdx.x, lane = threadIdx.x;
+  const float* xr = x + (long long)r * H;
+  const float* dr = dy + (long long)r * H;
+  const float mu = mean[r], rs = rstd[r];
+  float a = 0.f, b = 0.f;
+  for (int c = lane; c < H; c += 64) {
+    const float dg = dr[c] * g[c];
+    a += dg;
+    b = fmaf(dg, (xr[c] - mu) * rs, b);
+  }
+  a = wave_sum(a) / (float)H;
+  b = wave_sum(b) / (float)H;
+  for (int c = lane; c < H; c += 64) {
+    const float xh = (xr[c] - mu) * rs;
+    dx[(long long)r * H + c] += rs * (dr[c] * g[c] - a - xh * b);
+  }
+}
+
+__device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
+__global__ void k_tgelu(const float* __restrict__ x, float* __restrict__ y, long long n) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) y[i] = gelu_f(x[i]);
+}
+// dy *= gelu'(x) = Phi(x) + x phi(x)
+__global__ void k_tgelu_bwd(const float* __restrict__ x, float* __restrict__ dy, long long n) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float v = x[i];
+  const float cdf = 0.5f * (1.f + erff(v * 0.70710678118654752440f));
+  const float pdf = 0.39894228040143267794f * expf(-0.5f * v * v);
+  dy[i] *= cdf + v * pdf;
+}
+// h_next = (mlp + attn) + h: the order of HF's parallel residual
+__global__ void k_tadd3(const float* __restrict__ m, const float* __restrict__ a, const float* __restrict__ h, float* __restrict__ out, long long n) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = (m[i] + a[i]) + h[i];
+}
+// the four attribute embeddings side by side: A[r][k * E + e] = table_k[attr_k[r]][e]
+__global__ void k_tembed_gather(const int* __restrict__ attrs4, int M, int E, const float* t0, const float* t1, const float* t2, const float* t3,
+                                float* __restrict__ A) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long long)M * 4 * E) return;
+  const int c = (int)(i % (4 * E)), k = c / E, e = c % E;
+  const long long r = i / (4 * E);
+  const float* t = k == 0 ? t0 : k == 1 ? t1 : k == 2 ? t2 : t3;
+  A[i] = t[(long long)attrs4[(long long)k * M + r] * E + e];
+}
+// h = (word + class) + projected attributes (already in h)
+__global__ void k_tembed_sum(const int* __restrict__ ids, const int* __restrict__ cls, const float* __restrict__ word, const float* __restrict__ cemb, int H,
+                             float* __restrict__ h, long long n) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const long long r = i / H;
+  const int c = (int)(i % H);
+  h[i] = (word[(long long)ids[r] * H + c] + cemb[(long long)cls[r] * H + c]) + h[i];
+}
+
+// cross-entropy of one row, in place: logits -> (softmax - onehot) * scale, or zeros where the label is -100; row_loss = lse - logit[label] (0 where ignored)
+__global__ __launch_bounds__(64) void k_tce(float* __restrict__ logits, int V, const int* __restrict__ labels, float scale, float* __restrict__ row_loss) {
+  const int r = blockIdx.x, lane = threadIdx.x;
+  float* lg = logits + (long long)r * V;
+  const int lab = labels[r];
+  if (lab == ETD_IGNORE_LABEL) {                       // (uniform)
+    for (int v = lane; v < V; v += 64) lg[v] = 0.f;
+    if (lane == 0) row_loss[r] = 0.f;
+    return;
+  }
+  float mx = -INFINITY;
+  for (int v = lane; v < V; v += 64) mx = fmaxf(mx, lg[v]);
+  mx = wave_max(mx);
+  float s = 0.f;
+  for (int v = lane; v < V; v += 64) s += expf(lg[v] - mx);
+  s = wave_sum(s);
+  const float at = lg[lab];
+  for (int v = lane; v < V; v += 64) {
+    const float p = expf(lg[v] - mx) / s;
+    lg[v] = (p - (v == lab ? 1.f : 0.f)) * scale;
+  }
+  if (lane == 0) row_loss[r] = (mx + logf(s)) - at;
+}
+
+// Column reductions over the batch rows: 32 columns x 8 row slices per workgroup; slice s adds rows s, s + 8, .. in ascending order and the 8 partial sums are
+// added in slice order.  MODE 0: g0[c] += sum_r dy[r][c] (a bias gradient).  MODE 1: also g1[c] += sum_r dy[r][c] xhat[r][c] (LayerNorm: g0 = bias, g1 = gain).
+template <int MODE>
+__global__ __launch_bounds__(256) void k_tcolred(const float* __restrict__ dy, int ld, int M, int N, const float* __restrict__ x, const float* __restrict__ mean,
+                                                 const float* __restrict__ rstd, float* __restrict__ g0, float* __restrict__ g1) {
+  __shared__ float p0[8][32], p1[8][32];
+  const int t = threadIdx.x, c = blockIdx.x * 32 + (t & 31), s = t >> 5;
+  float a0 = 0.f, a1 = 0.f;
+  if (c < N)
+    for (int r = s; r < M; r += 8) {
+      const float v = dy[(long long)r * ld + c];
+      a0 += v;
+      if (MODE == 1) a1 = fmaf(v, (x[(long long)r * N + c] - mean[r]) * rstd[r], a1);
+    }
+  p0[s][t & 31] = a0; p1[s][t & 31] = a1;
+  __syncthreads();
+  if (s == 0 && c < N) {
+    float t0 = p0[0][t], t1 = p1[0][t];
+    for (int k = 1; k < 8; ++k) { t0 += p0[k][t]; t1 += p1[k][t]; }
+    g0[c] += t0;
+    if (MODE == 1) g1[c] += t1;
+  }
+}
+
+// Embedding gradients.  The batch rows are grouped by table row on the host (a stable counting sort): segment g = rows order[start[g] .. start[g] + count[g]) ascending,
+// all with index seg_id[g]; the padding row has no segment.  grid (segments, column blocks of 64), 4 row slices, summed as in k_tcolred.
+__global__ __launch_bounds__(256) void k_tembed_grad(const float* __restrict__ src, int ld, int col0, int width, const int* __restrict__ order,
+                                                     const int* __restrict__ seg_id, const int* __restrict__ seg_start, const int* __restrict__ seg_count,
+                                                     float* __restrict__ grad) {
+  __shared__ float part[4][64];
+  const int g = blockIdx.x, t = threadIdx.x, c = blockIdx.y * 64 + (t & 63), s = t >> 6;
+  const int st = seg_start[g], n = seg_count[g];
+  float a = 0.f;
+  if (c < width)
+    for (int k = s; k < n; k += 4) a += src[(long long)order[st + k] * ld + col0 + c];
+  part[s][t & 63] = a;
+  __syncthreads();
+  if (s == 0 && c < width) grad[(long long)seg_id[g] * width + c] += ((part[0][t] + part[1][t]) + part[2][t]) + part[3][t];
+}
+
+// ================================================================================================
+// optimizer
+// ================================================================================================
+#define TN_BLOCKS 256
+// fp64 partial sums of squares: block b owns elements [b * chunk, (b + 1) * chunk), thread t every 256th of them; the 256 thread sums are added in thread order
+__global__ __launch_bounds__(256) void k_tsumsq(const float* __restrict__ g, long long n, long long chunk, double* __restrict__ partial) {
+  __shared__ double ps[256];
+  const long long b0 = (long long)blockIdx.x * chunk, b1 = b0 + chunk < n ? b0 + chunk : n;
+  double a = 0.0;
+  for (long long i = b0 + threadIdx.x; i < b1; i += 256) { const double v = (double)g[i]; a += v * v; }
+  ps[threadIdx.x] = a;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double tot = 0.0;
+    for (int i = 0; i < 256; ++i) tot += ps[i];
+    partial[blockIdx.x] = tot;
+  }
+}
+
+#pragma clang fp contract(off)
+// a v_mul_f32 of its own: left to itself the SLP vectoriser pairs this kernel's independent multiplies into v_pk_mul_f32 with a crossed op_sel, the packed form
+// tests/test_isa_guard.py keeps out of the library (merge_sum in dec_kernels.hip)
+__device__ __forceinline__ float mul_scalar(float a, float b) {
+  float r;
+  asm volatile("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+// clip_grad_norm_'s g *= coef, then torch.optim.AdamW's single-tensor step, one element per thread.  1 - beta1 and 1 - beta2 arrive as the host's double differences
+// rounded once, as torch passes them: formed here from the rounded betas, 1.f - 0.98f is 9.5e-7 (relative) short of 0.02 and every update 7e-7 too long -- a bias
+// that showed as a loss below the fp64 trajectory's at every step.
+__global__ void k_tadamw(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long long n, float coef, float decay,
+                         float one_minus_beta1, float beta2, float one_minus_beta2, float step_size, float bc2_sqrt, float eps) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float gi = mul_scalar(g[i], coef);
+  float pi = mul_scalar(p[i], decay);                                  // p.mul_(1 - lr * weight_decay)
+  const float mi = m[i] + mul_scalar(gi - m[i], one_minus_beta1);       // exp_avg.lerp_(grad, 1 - beta1)
+  const float vi = mul_scalar(v[i], beta2) + mul_scalar(one_minus_beta2, gi) * gi;   // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
+  const float denom = sqrtf(vi) / bc2_sqrt + eps;
+  pi = pi - step_size * (mi / denom);                        // p.addcdiv_(exp_avg, denom, value = -step_size)
+  p[i] = pi; g[i] = gi; m[i] = mi; v[i] = vi;
+}
+#pragma clang fp contract(on)
+
+// ================================================================================================
+// the engine
+// ================================================================================================
+struct TParam { std::string name; size_t off, n; };
+struct TLayer { size_t ln1_w, ln1_b, ln2_w, ln2_b, qkv_w, qkv_b, d_w, d_b, f1_w, f1_b, f2_w, f2_b; };
+
+struct etd_dtrain {
+  etd_dec_cfg cfg;
+  int pad_token = 0, pad_class = 0, pad_attr = 0, max_rows = 0;
+  int V = 0, H = 0, I = 0, L = 0, nh = 0, E = 0, NB = 0, NC = 0;
+  std::vector<TParam> params;
+  std::map<std::string, int> index;
+  size_t n_total = 0, n_train = 0;                    // floats in the flat buffers; the first n_train are trained (transformer.embed_in.weight sits behind them)
+  size_t word = 0, cemb = 0, attr[4] = {0, 0, 0, 0}, proj_w = 0, proj_b = 0, lnf_w = 0, lnf_b = 0, head = 0;
+  std::vector<TLayer> layers;
+  float *P = nullptr, *G = nullptr, *M1 = nullptr, *M2 = nullptr;
+  // saved activations
+  float *A4 = nullptr, *dA4 = nullptr, *hs = nullptr, *mean = nullptr, *rstd = nullptr, *qkv = nullptr, *lse = nullptr, *att = nullptr, *pre = nullptr, *hf = nullptr;
+  // workspace
+  float *logits = nullptr, *wI = nullptr, *wH1 = nullptr, *wH2 = nullptr, *wH3 = nullptr, *dqkv = nullptr, *Dbuf = nullptr, *row_loss = nullptr, *rope = nullptr;
+  double* partial = nullptr;
+  int* ints = nullptr;
+  size_t n_ints = 0;
+  std::vector<float> h_row_loss;
+  std::vector<int> h_ints;
+  long long step = 0;
+  size_t workspace_bytes = 0;
+  DevPool pool;
+};
+
+static size_t tp_add(etd_dtrain* d, const std::string& name, size_t n) {
+  const size_t off = d->n_total;
+  d->index[name] = (int)d->params.size();
+  d->params.push_back({name, off, n});
+  d->n_total += (n + 63) / 64 * 64;                    // 256-byte alignment of every tensor; the gaps stay 0 in all four buffers
+  return off;
+}
+
+static int dtrain_check_cfg(const etd_dec_cfg* c, int max_rows) {
+  if (!c) ETD_FAIL(ETD_EINVAL, "etd_dtrain_create: null config");
+  if (c->struct_bytes != (int)sizeof(etd_dec_cfg)) ETD_FAIL(ETD_EINVAL, "etd_dtrain_create: etd_dec_cfg of %d bytes, this library's has %d", c->struct_bytes, (int)sizeof(etd_dec_cfg));
+  if (c->vocab_size < 1 || c->hidden_size < 1 || c->num_hidden_layers < 0 || c->num_attention_heads < 1 || c->intermediate_size < 1 || c->num_classes < 1 ||
+      c->attribute_emb_dim < 1 || c->num_attribute_bins < 1 || c->max_position_embeddings < 1)
+    ETD_FAIL(ETD_EINVAL, "etd_dtrain_create: a dimension is not positive");
+  if (c->hidden_size != 64 * c->num_attention_heads) ETD_FAIL(ETD_EINVAL, "etd_dtrain_create: head_dim must be 64 (hidden %d, heads %d)", c->hidden_size, c->num_attention_heads);
+  if ((int)(64 * c->rotary_pct) != 16) ETD_FAIL(ETD_EINVAL, "etd_dtrain_create: 16 rotary dims only (rotary_pct %g)", c->rotary_pct);
+  if (c->hidden_size % 256) ETD_FAIL(ETD_EINVAL, "etd_dtrain_create: hidden_size %d is not a multiple of 256", c->hidden_size);
+  if (c->intermediate_size % 128) ETD_FAIL(ETD_EINVAL, "etd_dtrain_create: intermediate_size %d is not a multiple of 128", c->intermediate_size);
+  if (max_rows < 1 || max_rows > (1 << 22)) ETD_FAIL(ETD_EINVAL, "etd_dtrain_create: max_rows %d outside 1 .. 2^22", max_rows);
+  return ETD_OK;
+}
+
+extern "C" long long etd_dtrain_workspace_bytes(const etd_dec_cfg* c, int max_rows) {
+  if (dtrain_check_cfg(c, max_rows) != ETD_OK) return ETD_EINVAL;
+  const long long H = c->hidden_size, I = c->intermediate_size, L = c->num_hidden_layers, nh = c->num_attention_heads, V = c->vocab_size, E = c->attribute_emb_dim;
+  const long long saved = 8 * E + (L + 1) * H + L * (2 + 3 * H + nh + H + I) + 2 + H;      // floats per row kept from forward to backward
+  const long long work = V + I + 3 * H + 3 * H + nh + 1;                                     // floats per row of scratch
+  return 4 * (saved + work) * (long long)max_rows;
+}
+
+extern "C" int etd_dtrain_create(const etd_dec_cfg* cfg, const char* const* names, const float* const* host_ptrs, const int64_t* numels, int n,
+                                 int pad_token_id, int pad_class_id, int attribute_pad_id, int max_rows, etd_dtrain** out) {
+  if (!out) ETD_FAIL(ETD_EINVAL, "etd_dtrain_create: null out");
+  *out = nullptr;
+  ETD_TRY(dtrain_check_cfg(cfg, max_rows));
+  const etd_dec_cfg& c = *cfg;
+  if (pad_token_id < 0 || pad_token_id >= c.vocab_size || pad_class_id < 0 || pad_class_id >= c.num_classes || attribute_pad_id < 0 || attribute_pad_id >= c.num_attribute_bins)
+    ETD_FAIL(ETD_EINVAL, "etd_dtrain_create: a padding index lies outside its table");
+  if (!names || !host_ptrs || !numels || n < 1) ETD_FAIL(ETD_EINVAL, "etd_dtrain_create: no weights");
+  etd_dtrain* d = new etd_dtrain();
+  auto fail = [&](int rc) { d->pool.free_all(); delete d; return rc; };
+  d->cfg = c; d->pad_token = pad_token_id; d->pad_class = pad_class_id; d->pad_attr = attribute_pad_id; d->max_rows = max_rows;
+  d->V = c.vocab_size; d->H = c.hidden_size; d->I = c.intermediate_size; d->L = c.num_hidden_layers; d->nh = c.num_attention_heads;
+  d->E = c.attribute_emb_dim; d->NB = c.num_attribute_bins; d->NC = c.num_classes;
+  const size_t V = d->V, H = d->H, I = d->I, E = d->E;
+  d->word = tp_add(d, "word_embeddings.weight", V * H);
+  d->cemb = tp_add(d, "class_embeddings.weight", (size_t)d->NC * H);
+  static const char* attr_names[4] = {"pitch_overlap", "polyphony", "note_sustain", "rhythm_intensity"};      // the concat order of etude_decoder.py:171-176
+  for (int k = 0; k < 4; ++k) d->attr[k] = tp_add(d, std::string(attr_names[k]) + "_embeddings.weight", (size_t)d->NB * E);
+  d->proj_w = tp_add(d, "attribute_projection.weight", H * 4 * E);
+  d->proj_b = tp_add(d, "attribute_projection.bias", H);
+  for (int i = 0; i < d->L; ++i) {
+    const std::string p = "transformer.layers." + std::to_string(i) + ".";
+    TLayer y;
+    y.ln1_w = tp_add(d, p + "input_layernorm.weight", H); y.ln1_b = tp_add(d, p + "input_layernorm.bias", H);
+    y.ln2_w = tp_add(d, p + "post_attention_layernorm.weight", H); y.ln2_b = tp_add(d, p + "post_attention_layernorm.bias", H);
+    y.qkv_w = tp_add(d, p + "attention.query_key_value.weight", 3 * H * H); y.qkv_b = tp_add(d, p + "attention.query_key_value.bias", 3 * H);
+    y.d_w = tp_add(d, p + "attention.dense.weight", H * H); y.d_b = tp_add(d, p + "attention.dense.bias", H);
+    y.f1_w = tp_add(d, p + "mlp.dense_h_to_4h.weight", I * H); y.f1_b = tp_add(d, p + "mlp.dense_h_to_4h.bias", I);
+    y.f2_w = tp_add(d, p + "mlp.dense_4h_to_h.weight", H * I); y.f2_b = tp_add(d, p + "mlp.dense_4h_to_h.bias", H);
+    d->layers.push_back(y);
+  }
+  d->lnf_w = tp_add(d, "transformer.final_layer_norm.weight", H);
+  d->lnf_b = tp_add(d, "transformer.final_layer_norm.bias", H);
+  d->head = tp_add(d, "lm_head.weight", V * H);
+  d->n_train = d->n_total;
+  // GPTNeoXModel's own token table: part of the state dict, never read (the model is fed inputs_embeds), so autograd gives it no gradient and
+  // torch.optim.AdamW leaves it alone, weight decay included.  It is kept, saved and never changed.
+  tp_add(d, "transformer.embed_in.weight", V * H);
+  // host image of the parameters, checked before the device is touched
+  WeightTable wt(names, host_ptrs, numels, n);
+  std::vector<float> host(d->n_total, 0.f);
+  for (const TParam& p : d->params) {
+    const float* src = wt.get(p.name, (int64_t)p.n);
+    if (!src) return fail(ETD_EINVAL);
+    memcpy(host.data() + p.off, src, p.n * sizeof(float));
+  }
+  std::vector<float> rope((size_t)c.max_position_embeddings * 16);
+  for (int pos = 0; pos < c.max_position_embeddings; ++pos)
+    for (int i = 0; i < 8; ++i) {                      // modeling_gpt_neox.py:72-109 in fp32: inv_freq, pos * inv_freq, then cos / sin of that fp32 angle
+      const float inv = 1.0f / powf(c.rope_theta, (float)(2 * i) / 16.0f);
+      const float fr = (float)pos * inv;
+      rope[(size_t)pos * 16 + i] = (float)cos((double)fr);
+      rope[(size_t)pos * 16 + 8 + i] = (float)sin((double)fr);
+    }
+  // ---- device
+  DevPool& pl = d->pool;
+  ETD_TRY_OR(fail, (pl.upload<float, float>(&d->P, host.data(), d->n_total)));
+  ETD_TRY_OR(fail, pl.alloc(&d->G, d->n_total, true));
+  ETD_TRY_OR(fail, pl.alloc(&d->M1, d->n_total, true));
+  ETD_TRY_OR(fail, pl.alloc(&d->M2, d->n_total, true));
+  ETD_TRY_OR(fail, (pl.upload<float, float>(&d->rope, rope.data(), rope.size())));
+  const size_t R = (size_t)max_rows, Lz = (size_t)d->L, nh = (size_t)d->nh;
+  const size_t before = pl.mark();
+  ETD_TRY_OR(fail, pl.alloc(&d->A4, R * 4 * E));
+  ETD_TRY_OR(fail, pl.alloc(&d->dA4, R * 4 * E));
+  ETD_TRY_OR(fail, pl.alloc(&d->hs, (Lz + 1) * R * H));
+  ETD_TRY_OR(fail, pl.alloc(&d->mean, (Lz + 1) * R));
+  ETD_TRY_OR(fail, pl.alloc(&d->rstd, (Lz + 1) * R));
+  ETD_TRY_OR(fail, pl.alloc(&d->qkv, std::max<size_t>(Lz, 1) * R * 3 * H));
+  ETD_TRY_OR(fail, pl.alloc(&d->lse, std::max<size_t>(Lz, 1) * R * nh));
+  ETD_TRY_OR(fail, pl.alloc(&d->att, std::max<size_t>(Lz, 1) * R * H));
+  ETD_TRY_OR(fail, pl.alloc(&d->pre, std::max<size_t>(Lz, 1) * R * I));
+  ETD_TRY_OR(fail, pl.alloc(&d->hf, R * H));
+  ETD_TRY_OR(fail, pl.alloc(&d->logits, R * V));
+  ETD_TRY_OR(fail, pl.alloc(&d->wI, R * I));
+  ETD_TRY_OR(fail, pl.alloc(&d->wH1, R * H));
+  ETD_TRY_OR(fail, pl.alloc(&d->wH2, R * H));
+  ETD_TRY_OR(fail, pl.alloc(&d->wH3, R * H));
+  ETD_TRY_OR(fail, pl.alloc(&d->dqkv, R * 3 * H));
+  ETD_TRY_OR(fail, pl.alloc(&d->Dbuf, R * nh));
+  ETD_TRY_OR(fail, pl.alloc(&d->row_loss, R));
+  ETD_TRY_OR(fail, pl.alloc(&d->partial, (size_t)TN_BLOCKS));
+  // ints: ids, cls, attrs4 [4], labels, pos (8 R) | row0, len (2 R) | six sort orders (6 R) | segments: id, start, count of at most V + NC + 4 NB table rows
+  d->n_ints = 16 * R + 3 * (V + (size_t)d->NC + 4 * (size_t)d->NB);
+  ETD_TRY_OR(fail, pl.alloc(&d->ints, d->n_ints));
+  for (size_t i = before; i < pl.bytes.size(); ++i) d->workspace_bytes += pl.bytes[i];
+  d->h_row_loss.resize(R);
+  *out = d;
+  return ETD_OK;
+}
+
+extern "C" void etd_dtrain_destroy(etd_dtrain* d) {
+  if (!d) return;
+  d->pool.free_all();
+  delete d;
+}
+
+extern "C" long long etd_dtrain_bytes(const etd_dtrain* d, int what) {
+  if (!d) return ETD_EINVAL;
+  return what == 0 ? (long long)d->workspace_bytes : (long long)(4 * d->n_total * sizeof(float));      // 0: activations + scratch; 1: weights, gradients, two moments
+}
+
+static inline dim3 ew_grid(long long n) { return dim3((unsigned)((n + 255) / 256)); }
+
+// stable grouping of M rows by table index: order / segments appended to `ints` at (o_order, o_seg ..); returns the number of segments (the padding row has none)
+static int group_rows(const int32_t* idx, int M, int n_rows, int pad, int* order, int* seg_id, int* seg_start, int* seg_count) {
+  std::vector<int> cnt(n_rows + 1, 0);
+  for (int r = 0; r < M; ++r) ++cnt[idx[r] + 1];
+  for (int i = 0; i < n_rows; ++i) cnt[i + 1] += cnt[i];
+  std::vector<int> at(cnt.begin(), cnt.end() - 1);
+  for (int r = 0; r < M; ++r) order[at[idx[r]]++] = r;
+  int ns = 0;
+  for (int i = 0; i < n_rows; ++i) {
+    const int c = cnt[i + 1] - cnt[i];
+    if (c == 0 || i == pad) continue;
+    seg_id[ns] = i; seg_start[ns] = cnt[i]; seg_count[ns] = c; ++ns;
+  }
+  return ns;
+}
+
+extern "C" int etd_dtrain_forward_backward(etd_dtrain* d, int n, const int32_t* T, const int32_t* ids, const int32_t* cls, const int32_t* attrs4,
+                                           const int32_t* labels, float loss_scale, float* loss_out, int32_t* n_scored_out, void* stream) {
+  if (!d || !T || !ids || !cls || !attrs4 || !labels || !loss_out || !n_scored_out) ETD_FAIL(ETD_EINVAL, "etd_dtrain_forward_backward: null argument");
+  if (n < 1 || n > 65535) ETD_FAIL(ETD_EINVAL, "etd_dtrain_forward_backward: %d sequences (1 .. 65535)", n);
+  long long Ml = 0;
+  int max_len = 0;
+  for (int s = 0; s < n; ++s) {
+    if (T[s] < 1 || T[s] > d->cfg.max_position_embeddings) ETD_FAIL(ETD_EINVAL, "etd_dtrain_forward_backward: sequence %d has %d rows (1 .. max_position_embeddings = %d)", s, T[s], d->cfg.max_position_embeddings);
+    Ml += T[s];
+    max_len = std::max(max_len, (int)T[s]);
+  }
+  if (Ml > d->max_rows) ETD_FAIL(ETD_EINVAL, "etd_dtrain_forward_backward: %lld rows, the workspace was sized for %d", Ml, d->max_rows);
+  const int M = (int)Ml;
+  int scored = 0;
+  for (int r = 0; r < M; ++r) {
+    if (ids[r] < 0 || ids[r] >= d->V) ETD_FAIL(ETD_EINVAL, "etd_dtrain_forward_backward: token id %d out of range [0, %d) at row %d", ids[r], d->V, r);
+    if (cls[r] < 0 || cls[r] >= d->NC) ETD_FAIL(ETD_EINVAL, "etd_dtrain_forward_backward: class id %d out of range [0, %d) at row %d", cls[r], d->NC, r);
+    for (int k = 0; k < 4; ++k)
+      if (attrs4[(size_t)k * M + r] < 0 || attrs4[(size_t)k * M + r] >= d->NB)
+        ETD_FAIL(ETD_EINVAL, "etd_dtrain_forward_backward: attribute bin %d out of range [0, %d) at row %d", attrs4[(size_t)k * M + r], d->NB, r);
+    if (labels[r] != ETD_IGNORE_LABEL && (labels[r] < 0 || labels[r] >= d->V)) ETD_FAIL(ETD_EINVAL, "etd_dtrain_forward_backward: label %d out of range at row %d", labels[r], r);
+    scored += labels[r] != ETD_IGNORE_LABEL;
+  }
+  *n_scored_out = scored;
+  if (scored == 0) {                                   // F.cross_entropy gives nan; train.py:169 skips the batch.  Nothing is launched: the gradients keep every bit.
+    *loss_out = NAN;
+    return ETD_OK;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int H = d->H, I = d->I, V = d->V, E = d->E, nh = d->nh, L = d->L;
+  const size_t R = (size_t)d->max_rows;
+  // ---- the call's integers, one upload
+  std::vector<int>& hi = d->h_ints;
+  hi.assign(d->n_ints, 0);
+  int* h_ids = hi.data(); int* h_cls = h_ids + R; int* h_at = h_cls + R; int* h_lab = h_at + 4 * R; int* h_pos = h_lab + R;
+  int* h_row0 = h_pos + R; int* h_len = h_row0 + R; int* h_ord = h_len + R; int* h_seg = h_ord + 6 * R;
+  memcpy(h_ids, ids, sizeof(int) * M); memcpy(h_cls, cls, sizeof(int) * M); memcpy(h_lab, labels, sizeof(int) * M);
+  for (int k = 0; k < 4; ++k) memcpy(h_at + (size_t)k * M, attrs4 + (size_t)k * M, sizeof(int) * M);
+  for (int s = 0, r = 0; s < n; ++s) {
+    h_row0[s] = r; h_len[s] = T[s];
+    for (int t = 0; t < T[s]; ++t) h_pos[r++] = t;
+  }
+  const size_t seg_cap = (size_t)V + d->NC + 4 * (size_t)d->NB;
+  int* h_sid = h_seg; int* h_sst = h_seg + seg_cap; int* h_scn = h_seg + 2 * seg_cap;
+  int seg0[7];
+  seg0[0] = 0;
+  seg0[1] = group_rows(ids, M, V, d->pad_token, h_ord, h_sid, h_sst, h_scn);
+  seg0[2] = seg0[1] + group_rows(cls, M, d->NC, d->pad_class, h_ord + R, h_sid + seg0[1], h_sst + seg0[1], h_scn + seg0[1]);
+  for (int k = 0; k < 4; ++k)
+    seg0[3 + k] = seg0[2 + k] + group_rows(attrs4 + (size_t)k * M, M, d->NB, d->pad_attr, h_ord + (2 + k) * R, h_sid + seg0[2 + k], h_sst + seg0[2 + k], h_scn + seg0[2 + k]);
+  HIP_TRY(hipMemcpyAsync(d->ints, hi.data(), sizeof(int) * d->n_ints, hipMemcpyHostToDevice, st));
+  const int* ii = d->ints;
+  const int *d_ids = ii, *d_cls = ii + R, *d_at = ii + 2 * R, *d_lab = ii + 6 * R, *d_pos = ii + 7 * R, *d_row0 = ii + 8 * R, *d_len = ii + 9 * R, *d_ord = ii + 10 * R;
+  const int *d_sid = ii + 16 * R, *d_sst = d_sid + seg_cap, *d_scn = d_sid + 2 * seg_cap;
+  float* P = d->P;
+  float* G = d->G;
+  const long long MH = (long long)M * H, MI = (long long)M * I;
+  const float eps = d->cfg.layer_norm_eps;
+  // ================================================================ forward
+  {
+    ProfScope ps("dtrain_forward", st);
+    hipLaunchKernelGGL(k_tembed_gather, ew_grid((long long)M * 4 * E), dim3(256), 0, st, d_at, M, E, P + d->attr[0], P + d->attr[1], P + d->attr[2], P + d->attr[3], d->A4);
+    ETD_TRY(launch_tgemm(ETD_TG_NT, M, H, 4 * E, d->A4, 4 * E, P + d->proj_w, 4 * E, P + d->proj_b, d->hs, H, false, st));
+    hipLaunchKernelGGL(k_tembed_sum, ew_grid(MH), dim3(256), 0, st, d_ids, d_cls, P + d->word, P + d->cemb, H, d->hs, MH);
+    for (int l = 0; l < L; ++l) {
+      const TLayer& y = d->layers[l];
+      float* h = d->hs + (size_t)l * R * H;
+      float* qkv = d->qkv + (size_t)l * R * 3 * H;
+      float* att = d->att + (size_t)l * R * H;
+      float* pre = d->pre + (size_t)l * R * I;
+      hipLaunchKernelGGL(k_tln_fwd, dim3(M), dim3(64), 0, st, h, M, H, eps, d->mean + (size_t)l * R, d->rstd + (size_t)l * R, P + y.ln1_w, P + y.ln1_b, d->wH1,
+                         P + y.ln2_w, P + y.ln2_b, d->wH2);
+      ETD_TRY(launch_tgemm(ETD_TG_NT, M, 3 * H, H, d->wH1, H, P + y.qkv_w, H, P + y.qkv_b, qkv, 3 * H, false, st));
+      hipLaunchKernelGGL(k_trope, ew_grid((long long)M * nh * 16), dim3(256), 0, st, qkv, nh, M, d_pos, d->rope, 1.f);
+      ETD_TRY(launch_tattn_fwd(qkv, nh, d_row0, d_len, n, max_len, att, d->lse + (size_t)l * R * nh, st));
+      ETD_TRY(launch_tgemm(ETD_TG_NT, M, H, H, att, H, P + y.d_w, H, P + y.d_b, d->wH1, H, false, st));          // wH1: attention branch
+      ETD_TRY(launch_tgemm(ETD_TG_NT, M, I, H, d->wH2, H, P + y.f1_w, H, P + y.f1_b, pre, I, false, st));
+      hipLaunchKernelGGL(k_tgelu, ew_grid(MI), dim3(256), 0, st, pre, d->wI, MI);
+      ETD_TRY(launch_tgemm(ETD_TG_NT, M, H, I, d->wI, I, P + y.f2_w, I, P + y.f2_b, d->wH3, H, false, st));       // wH3: MLP branch
+      hipLaunchKernelGGL(k_tadd3, ew_grid(MH), dim3(256), 0, st, d->wH3, d->wH1, h, h + R * H, MH);
+    }
+    hipLaunchKernelGGL(k_tln_fwd, dim3(M), dim3(64), 0, st, d->hs + (size_t)L * R * H, M, H, eps, d->mean + (size_t)L * R, d->rstd + (size_t)L * R,
+                       P + d->lnf_w, P + d->lnf_b, d->hf, (const float*)nullptr, (const float*)nullptr, (float*)nullptr);
+    ETD_TRY(launch_tgemm(ETD_TG_NT, M, V, H, d->hf, H, P + d->head, H, nullptr, d->logits, V, false, st));
+    hipLaunchKernelGGL(k_tce, dim3(M), dim3(64), 0, st, d->logits, V, d_lab, loss_scale / (float)scored, d->row_loss);
+    HIP_TRY(hipGetLastError());
+  }
+  // ================================================================ backward
+  {
+    ProfScope ps("dtrain_backward", st);
+    float* dh = d->wH1;                                // gradient of the residual stream
+    float* tx = d->wH2;                                // a recomputed LayerNorm output
+    float* dxn = d->wH3;                               // gradient of a LayerNorm output / of the attention output
+    ETD_TRY(launch_tgemm(ETD_TG_TN, V, H, M, d->logits, V, d->hf, H, nullptr, G + d->head, H, true, st));
+    ETD_TRY(launch_tgemm(ETD_TG_NN, M, H, V, d->logits, V, P + d->head, H, nullptr, dxn, H, false, st));
+    hipLaunchKernelGGL(k_tcolred<1>, dim3((H + 31) / 32), dim3(256), 0, st, dxn, H, M, H, d->hs + (size_t)L * R * H, d->mean + (size_t)L * R, d->rstd + (size_t)L * R,
+                       G + d->lnf_b, G + d->lnf_w);
+    HIP_TRY(hipMemsetAsync(dh, 0, sizeof(float) * MH, st));
+    hipLaunchKernelGGL(k_tln_bwd, dim3(M), dim3(64), 0, st, dxn, d->hs + (size_t)L * R * H, d->mean + (size_t)L * R, d->rstd + (size_t)L * R, P + d->lnf_w, H, dh);
+    for (int l = L - 1; l >= 0; --l) {
+      const TLayer& y = d->layers[l];
+      const float* h = d->hs + (size_t)l * R * H;
+      const float* mean = d->mean + (size_t)l * R;
+      const float* rstd = d->rstd + (size_t)l * R;
+      const float* qkv = d->qkv + (size_t)l * R * 3 * H;
+      const float* att = d->att + (size_t)l * R * H;
+      const float* pre = d->pre + (size_t)l * R * I;
+      // dh is d loss / d (mlp + attn + h): the gradient of both branch outputs, and (kept) of h through the residual
+      // ---- MLP branch
+      hipLaunchKernelGGL(k_tgelu, ew_grid(MI), dim3(256), 0, st, pre, d->wI, MI);
+      ETD_TRY(launch_tgemm(ETD_TG_TN, H, I, M, dh, H, d->wI, I, nullptr, G + y.f2_w, I, true, st));
+      hipLaunchKernelGGL(k_tcolred<0>, dim3((H + 31) / 32), dim3(256), 0, st, dh, H, M, H, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, G + y.f2_b, (float*)nullptr);
+      ETD_TRY(launch_tgemm(ETD_TG_NN, M, I, H, dh, H, P + y.f2_w, I, nullptr, d->wI, I, false, st));
+      hipLaunchKernelGGL(k_tgelu_bwd, ew_grid(MI), dim3(256), 0, st, pre, d->wI, MI);
+      hipLaunchKernelGGL(k_tln_fwd, dim3(M), dim3(64), 0, st, h, M, H, eps, (float*)nullptr, (float*)nullptr, P + y.ln2_w, P + y.ln2_b, tx,
+                         (const float*)nullptr, (const float*)nullptr, (float*)nullptr);
+      ETD_TRY(launch_tgemm(ETD_TG_TN, I, H, M, d->wI, I, tx, H, nullptr, G + y.f1_w, H, true, st));
+      hipLaunchKernelGGL(k_tcolred<0>, dim3((I + 31) / 32), dim3(256), 0, st, d->wI, I, M, I, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, G + y.f1_b, (float*)nullptr);
+      ETD_TRY(launch_tgemm(ETD_TG_NN, M, H, I, d->wI, I, P + y.f1_w, H, nullptr, dxn, H, false, st));
+      hipLaunchKernelGGL(k_tcolred<1>, dim3((H + 31) / 32), dim3(256), 0, st, dxn, H, M, H, h, mean, rstd, G + y.ln2_b, G + y.ln2_w);
+      // ---- attention branch (before dh takes the LayerNorm terms: both branches read the incoming dh)
+      ETD_TRY(launch_tgemm(ETD_TG_TN, H, H, M, dh, H, att, H, nullptr, G + y.d_w, H, true, st));
+      hipLaunchKernelGGL(k_tcolred<0>, dim3((H + 31) / 32), dim3(256), 0, st, dh, H, M, H, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, G + y.d_b, (float*)nullptr);
+      ETD_TRY(launch_tgemm(ETD_TG_NN, M, H, H, dh, H, P + y.d_w, H, nullptr, tx, H, false, st));                 // tx: d loss / d attention output
+      hipLaunchKernelGGL(k_tln_bwd, dim3(M), dim3(64), 0, st, dxn, h, mean, rstd, P + y.ln2_w, H, dh);            // (the MLP branch's LayerNorm, now that dh has been read)
+      ETD_TRY(launch_tattn_bwd(qkv, att, d->lse + (size_t)l * R * nh, tx, nh, d_row0, d_len, n, max_len, d->Dbuf, d->dqkv, st));
+      hipLaunchKernelGGL(k_trope, ew_grid((long long)M * nh * 16), dim3(256), 0, st, d->dqkv, nh, M, d_pos, d->rope, -1.f);
+      hipLaunchKernelGGL(k_tln_fwd, dim3(M), dim3(64), 0, st, h, M, H, eps, (float*)nullptr, (float*)nullptr, P + y.ln1_w, P + y.ln1_b, tx,
+                         (const float*)nullptr, (const float*)nullptr, (float*)nullptr);
+      ETD_TRY(launch_tgemm(ETD_TG_TN, 3 * H, H, M, d->dqkv, 3 * H, tx, H, nullptr, G + y.qkv_w, H, true, st));
+      hipLaunchKernelGGL(k_tcolred<0>, dim3((3 * H + 31) / 32), dim3(256), 0, st, d->dqkv, 3 * H, M, 3 * H, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, G + y.qkv_b, (float*)nullptr);
+      ETD_TRY(launch_tgemm(ETD_TG_NN, M, H, 3 * H, d->dqkv, 3 * H, P + y.qkv_w, H, nullptr, dxn, H, false, st));
+      hipLaunchKernelGGL(k_tcolred<1>, dim3((H + 31) / 32), dim3(256), 0, st, dxn, H, M, H, h, mean, rstd, G + y.ln1_b, G + y.ln1_w);
+      hipLaunchKernelGGL(k_tln_bwd, dim3(M), dim3(64), 0, st, dxn, h, mean, rstd, P + y.ln1_w, H, dh);
+    }
+    // ---- embeddings: dh is d loss / d inputs_embeds
+    ETD_TRY(launch_tgemm(ETD_TG_TN, H, 4 * E, M, dh, H, d->A4, 4 * E, nullptr, G + d->proj_w, 4 * E, true, st));
+    hipLaunchKernelGGL(k_tcolred<0>, dim3((H + 31) / 32), dim3(256), 0, st, dh, H, M, H, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, G + d->proj_b, (float*)nullptr);
+    ETD_TRY(launch_tgemm(ETD_TG_NN, M, 4 * E, H, dh, H, P + d->proj_w, 4 * E, nullptr, d->dA4, 4 * E, false, st));
+    if (seg0[1] > 0)
+      hipLaunchKernelGGL(k_tembed_grad, dim3(seg0[1], (H + 63) / 64), dim3(256), 0, st, dh, H, 0, H, d_ord, d_sid, d_sst, d_scn, G + d->word);
+    if (seg0[2] > seg0[1])
+      hipLaunchKernelGGL(k_tembed_grad, dim3(seg0[2] - seg0[1], (H + 63) / 64), dim3(256), 0, st, dh, H, 0, H, d_ord + R, d_sid + seg0[1], d_sst + seg0[1], d_scn + seg0[1], G + d->cemb);
+    for (int k = 0; k < 4; ++k)
+      if (seg0[3 + k] > seg0[2 + k])
+        hipLaunchKernelGGL(k_tembed_grad, dim3(seg0[3 + k] - seg0[2 + k], (E + 63) / 64), dim3(256), 0, st, d->dA4, 4 * E, k * E, E, d_ord + (2 + k) * R, d_sid + seg0[2 + k],
+                           d_sst + seg0[2 + k], d_scn + seg0[2 + k], G + d->attr[k]);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipMemcpyAsync(d->h_row_loss.data(), d->row_loss, sizeof(float) * M, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  double tot = 0.0;
+  for (int r = 0; r < M; ++r) tot += (double)d->h_row_loss[r];      // row order; rows that are not scored hold 0
+  *loss_out = (float)(tot / (double)scored);
+  return ETD_OK;
+}
+
+extern "C" int etd_dtrain_zero_grad(etd_dtrain* d, void* stream) {
+  if (!d) ETD_FAIL(ETD_EINVAL, "etd_dtrain_zero_grad: null handle");
+  HIP_TRY(hipMemsetAsync(d->G, 0, sizeof(float) * d->n_total, (hipStream_t)stream));
+  return ETD_OK;
+}
+
+static int grad_norm(etd_dtrain* d, hipStream_t st, double* out) {
+  const long long n = (long long)d->n_train, chunk = (n + TN_BLOCKS - 1) / TN_BLOCKS;
+  hipLaunchKernelGGL(k_tsumsq, dim3(TN_BLOCKS), dim3(256), 0, st, d->G, n, chunk, d->partial);
+  HIP_TRY(hipGetLastError());
+  double part[TN_BLOCKS];
+  HIP_TRY(hipMemcpyAsync(part, d->partial, sizeof(part), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  double tot = 0.0;
+  for (int i = 0; i < TN_BLOCKS; ++i) tot += part[i];
+  *out = sqrt(tot);
+  return ETD_OK;
+}
+
+extern "C" int etd_dtrain_grad_norm(etd_dtrain* d, double* norm, void* stream) {
+  if (!d || !norm) ETD_FAIL(ETD_EINVAL, "etd_dtrain_grad_norm: null argument");
+  return grad_norm(d, (hipStream_t)stream, norm);
+}
+
+extern "C" int etd_dtrain_clip_and_step(etd_dtrain* d, double max_norm, double lr, double beta1, double beta2, double eps, double weight_decay, double* norm_out,
+                                        void* stream) {
+  if (!d) ETD_FAIL(ETD_EINVAL, "etd_dtrain_clip_and_step: null handle");
+  if (!(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !(weight_decay >= 0.0))
+    ETD_FAIL(ETD_EINVAL, "etd_dtrain_clip_and_step: lr, eps, weight_decay must be >= 0 and the betas in [0, 1)");
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope ps("dtrain_optimizer", st);
+  double norm = 0.0;
+  ETD_TRY(grad_norm(d, st, &norm));
+  if (norm_out) *norm_out = norm;
+  double coef = 1.0;                                   // max_norm <= 0: no clipping
+  if (max_norm > 0.0) coef = std::min(1.0, max_norm / (norm + 1e-6));
+  d->step += 1;
+  const double bc1 = 1.0 - pow(beta1, (double)d->step), bc2 = 1.0 - pow(beta2, (double)d->step);
+  const long long n = (long long)d->n_train;
+  hipLaunchKernelGGL(k_tadamw, ew_grid(n), dim3(256), 0, st, d->P, d->G, d->M1, d->M2, n, (float)coef, (float)(1.0 - lr * weight_decay), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2),
+                     (float)(lr / bc1), (float)sqrt(bc2), (float)eps);
+  HIP_TRY(hipGetLastError());
+  return ETD_OK;
+}
+
+extern "C" int etd_dtrain_set_step(etd_dtrain* d, long long step) {
+  if (!d || step < 0) ETD_FAIL(ETD_EINVAL, "etd_dtrain_set_step: null handle or negative step");
+  d->step = step;
+  return ETD_OK;
+}
+extern "C" long long etd_dtrain_get_step(const etd_dtrain* d) { return d ? d->step : ETD_EINVAL; }
+
+// which: 0 parameter, 1 gradient, 2 exp_avg, 3 exp_avg_sq
+static int dtrain_io(etd_dtrain* d, const char* name, int which, float* out, const float* in, long long numel, hipStream_t st) {
+  if (!d || !name || (!out && !in)) ETD_FAIL(ETD_EINVAL, "etd_dtrain: null argument");
+  auto it = d->index.find(name);
+  if (it == d->index.end()) ETD_FAIL(ETD_EINVAL, "etd_dtrain: no parameter '%s'", name);
+  const TParam& p = d->params[it->second];
+  if ((long long)p.n != numel) ETD_FAIL(ETD_EINVAL, "etd_dtrain: '%s' has %zu elements, the buffer %lld", name, p.n, numel);
+  float* base = which == 0 ? d->P : which == 1 ? d->G : which == 2 ? d->M1 : d->M2;
+  if (out) HIP_TRY(hipMemcpyAsync(out, base + p.off, sizeof(float) * p.n, hipMemcpyDeviceToHost, st));
+  else HIP_TRY(hipMemcpyAsync(base + p.off, in, sizeof(float) * p.n, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return ETD_OK;
+}
+extern "C" int etd_dtrain_read_param(etd_dtrain* d, const char* name, float* out_host, long long numel, void* stream) {
+  return dtrain_io(d, name, 0, out_host, nullptr, numel, (hipStream_t)stream);
+}
+extern "C" int etd_dtrain_read_grad(etd_dtrain* d, const char* name, float* out_host, long long numel, void* stream) {
+  return dtrain_io(d, name, 1, out_host, nullptr, numel, (hipStream_t)stream);
+}
+extern "C" int etd_dtrain_read_moment(etd_dtrain* d, const char* name, int second, float* out_host, long long numel, void* stream) {
+  return dtrain_io(d, name, second ? 3 : 2, out_host, nullptr, numel, (hipStream_t)stream);
+}
+extern "C" int etd_dtrain_write_moment(etd_dtrain* d, const char* name, int second, const float* in_host, long long numel, void* stream) {
+  return dtrain_io(d, name, second ? 3 : 2, nullptr, in_host, numel, (hipStream_t)stream);
+}
+// ================================================================================================
+// debug entries (include/etude_hip_debug.h): the two kernels with tile edges, on their own inputs
+// ================================================================================================
+extern "C" int etd_debug_dtrain_gemm(int form, int M, int N, int K, const float* A_dev, int lda, const float* B_dev, int ldb, const float* bias_dev, float* C_dev,
+                                     int ldc, int accumulate, void* stream) {
+  return launch_tgemm(form, M, N, K, A_dev, lda, B_dev, ldb, bias_dev, C_dev, ldc, accumulate != 0, (hipStream_t)stream);
+}
+
+extern "C" int etd_debug_dtrain_attn(int n_seq, const int32_t* T_host, int n_heads, const float* qkv_dev, const float* dO_dev, float* O_dev, float* lse_dev,
+                                     float* dqkv_dev, void* stream) {
+  if (n_seq < 1 || n_seq > 65535 || !T_host || n_heads < 1 || !qkv_dev || !dO_dev || !O_dev || !lse_dev || !dqkv_dev) ETD_FAIL(ETD_EINVAL, "etd_debug_dtrain_attn: bad argument");
+  std::vector<int> h(2 * (size_t)n_seq);
+  long long M = 0;
+  int max_len = 0;
+  for (int s = 0; s < n_seq; ++s) {
+    if (T_host[s] < 1) ETD_FAIL(ETD_EINVAL, "etd_debug_dtrain_attn: empty sequence %d", s);
+    h[s] = (int)M; h[n_seq + s] = T_host[s];
+    M += T_host[s];
+    max_len = std::max(max_len, (int)T_host[s]);
+  }
+  if (M > (1 << 22)) ETD_FAIL(ETD_EINVAL, "etd_debug_dtrain_attn: %lld rows", M);
+  hipStream_t st = (hipStream_t)stream;
+  DevPool pl;
+  int* di = nullptr;
+  float* Dbuf = nullptr;
+  auto fail = [&](int rc) { (void)hipStreamSynchronize(st); pl.free_all(); return rc; };
+  ETD_TRY_OR(fail, pl.alloc(&di, h.size()));
+  ETD_TRY_OR(fail, pl.alloc(&Dbuf, (size_t)M * n_heads));
+  ETD_TRY_OR(fail, ETD_HIP_RC(hipMemcpyAsync(di, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice, st)));
+  ETD_TRY_OR(fail, launch_tattn_fwd(qkv_dev, n_heads, di, di + n_seq, n_seq, max_len, O_dev, lse_dev, st));
+  ETD_TRY_OR(fail, launch_tattn_bwd(qkv_dev, O_dev, lse_dev, dO_dev, n_heads, di, di + n_seq, n_seq, max_len, Dbuf, dqkv_dev, st));
+  return fail(ETD_HIP_RC(hipStreamSynchronize(st)));
+}

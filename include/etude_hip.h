@@ -601,6 +601,46 @@ int etd_attr_run(etd_attr*, const int32_t* src_ids_dev, const int64_t* src_offse
                  const int32_t* tgt_ids_dev, const int64_t* tgt_offsets_dev, const int64_t* tgt_offsets_host, int n_tgt_bars, const int32_t* tgt_index_dev, int n_pairs,
                  const double* edges_host, const int32_t* n_edges_host, int32_t* features_dev, double* attributes_dev, int32_t* bins_dev, int32_t* status_dev, void* stream);
 
+/* ------------------------------------------------------------------ decoder training (train.py: forward with saved activations, backward of the reference's
+ * cross-entropy loss for every parameter, gradient accumulation, clip_grad_norm_ and torch.optim.AdamW), all in fp32.  DESIGN.md 4j is the contract.
+ * The model is etd_decoder's in its exact-parity arithmetic (cfg.precision, max_streams, max_ctx and max_prefill_rows are not read); dropout is 0 in the reference's
+ * configuration, so train mode computes what eval mode computes.  No floating-point atomics anywhere: the same call on the same inputs gives the same bits. */
+typedef struct etd_dtrain etd_dtrain;
+/* HOST ONLY: bytes of saved activations and scratch a handle created with these arguments holds; negative = ETD_EINVAL (the limits of etd_dtrain_create) */
+long long etd_dtrain_workspace_bytes(const etd_dec_cfg* cfg, int max_rows);
+/* The config struct and state-dict names of etd_decoder_create.  Keeps plain fp32 master weights, gradients and AdamW's exp_avg / exp_avg_sq (zero) on the device.
+ * The padding_idx rows of the six embedding tables (pad_token_id, pad_class_id, attribute_pad_id) get a zero gradient, as nn.Embedding gives them.
+ * transformer.embed_in.weight is part of the state dict but never read: it gets no gradient and is never changed.  max_rows bounds the packed rows of one
+ * etd_dtrain_forward_backward call and sizes the workspace.  Limits: head_dim 64, 16 rotary dims, hidden % 256 == 0, intermediate % 128 == 0, any vocabulary, any
+ * number of layers; anything else, a missing weight or a wrong element count is ETD_EINVAL with a message before the device is touched. */
+int etd_dtrain_create(const etd_dec_cfg* cfg, const char* const* names, const float* const* host_ptrs, const int64_t* numels, int n,
+                      int pad_token_id, int pad_class_id, int attribute_pad_id, int max_rows, etd_dtrain** out);
+void etd_dtrain_destroy(etd_dtrain*);
+/* what = 0: bytes of saved activations and scratch; 1: bytes of weights + gradients + the two moments */
+long long etd_dtrain_bytes(const etd_dtrain*, int what);
+/* n sequences packed as for etd_decoder_score (T[n] rows each; ids / cls / labels int32 host [M = sum(T)], attrs4 int32 host [4][M] in C-ABI attribute order; a row's
+ * label is the token it should predict, NOT shifted, or -100).  *loss = F.cross_entropy's mean over the labelled rows, *n_scored their count, and
+ * loss_scale * d loss / d p is ADDED to every parameter's gradient (gradient accumulation passes 1 / grad_accum_steps).  A call with no labelled row returns
+ * *loss = nan and *n_scored = 0 and launches nothing: the accumulated gradients keep every bit (train.py:169 skips such a batch).  Out-of-range ids / classes / bins /
+ * labels, a sequence longer than max_position_embeddings or more rows than max_rows are ETD_EINVAL before anything runs.  Synchronous. */
+int etd_dtrain_forward_backward(etd_dtrain*, int n, const int32_t* T, const int32_t* ids, const int32_t* cls, const int32_t* attrs4, const int32_t* labels,
+                                float loss_scale, float* loss, int32_t* n_scored, void* stream);
+int etd_dtrain_zero_grad(etd_dtrain*, void* stream);
+/* L2 norm over all gradients: fp64 partial sums of the fp32 squares in a fixed order, one square root.  Synchronous. */
+int etd_dtrain_grad_norm(etd_dtrain*, double* norm, void* stream);
+/* torch.nn.utils.clip_grad_norm_ (g *= min(1, max_norm / (norm + 1e-6)); max_norm <= 0 = no clipping) followed by one torch.optim.AdamW step of the single-tensor path
+ * on every parameter (decoupled decay p *= 1 - lr * weight_decay on all of them: the reference passes model.parameters() as one group; bias corrections from the
+ * handle's step count, advanced here, in double on the host).  *norm (may be NULL) = the norm before clipping.  The gradients are left clipped, not zeroed. */
+int etd_dtrain_clip_and_step(etd_dtrain*, double max_norm, double lr, double beta1, double beta2, double eps, double weight_decay, double* norm, void* stream);
+/* the optimizer's step count (0 after create); set it, with etd_dtrain_write_moment, to resume */
+int etd_dtrain_set_step(etd_dtrain*, long long step);
+long long etd_dtrain_get_step(const etd_dtrain*);
+/* One tensor by its state-dict name, fp32 to / from the host; numel must be the tensor's.  second = 0: exp_avg, 1: exp_avg_sq.  Synchronous. */
+int etd_dtrain_read_param(etd_dtrain*, const char* name, float* out_host, long long numel, void* stream);
+int etd_dtrain_read_grad(etd_dtrain*, const char* name, float* out_host, long long numel, void* stream);
+int etd_dtrain_read_moment(etd_dtrain*, const char* name, int second, float* out_host, long long numel, void* stream);
+int etd_dtrain_write_moment(etd_dtrain*, const char* name, int second, const float* in_host, long long numel, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -203,6 +203,19 @@ int etd_tuning_debug_power(etd_tuning*, int song, const int32_t* frames_host, in
  * score are left untouched.  All three NULL turns it off.  No launch is added either way. */
 int etd_rhythm_debug_logioi(etd_rhythm*, double* logioi_dev, signed char* labels_dev, double* centres_dev);
 
+/* test hooks of the training engine (csrc/dec_train.hip), DEVICE fp32 buffers.
+ * The GEMM family: C [M][N] (row stride ldc) = (accumulate ? C : 0) + product (+ bias [N], may be NULL), in the three forms of a linear layer:
+ *   form 0  A [M][K] (lda) x B [N][K]^T (ldb)      Y  = X W^T
+ *   form 1  A [M][K] (lda) x B [K][N]   (ldb)      dX = dY W
+ *   form 2  A [K][M]^T (lda) x B [K][N] (ldb)      dW += dY^T X (the sum over K = batch rows in ascending order)
+ * A row stride shorter than its row is ETD_EINVAL.  Asynchronous. */
+int etd_debug_dtrain_gemm(int form, int M, int N, int K, const float* A_dev, int lda, const float* B_dev, int ldb, const float* bias_dev, float* C_dev, int ldc,
+                          int accumulate, void* stream);
+/* Causal attention forward + backward over n_seq packed sequences of T_host[s] rows, head_dim 64, no RoPE: qkv_dev [M][n_heads][q | k | v][64], dO_dev [M][n_heads * 64]
+ * -> O_dev [M][n_heads * 64], lse_dev [M][n_heads], dqkv_dev in qkv's layout (scale 1 / 8 on the scores).  Synchronous. */
+int etd_debug_dtrain_attn(int n_seq, const int32_t* T_host, int n_heads, const float* qkv_dev, const float* dO_dev, float* O_dev, float* lse_dev, float* dqkv_dev,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif
