@@ -158,6 +158,17 @@ extern "C" int etd_frontend_create(int sr_in, int sr_out, int orig, int nw, int 
   if (!out || n_fft < 64 || n_fft > 4096 || (n_fft & (n_fft - 1)) || hop <= 0 || n_mels <= 0 || n_mels > 1024)
     ETD_FAIL(ETD_EINVAL, "frontend_create: bad n_fft/hop/n_mels");
   if (sr_in != sr_out && (!kernT_host || K <= 0 || nw <= 0 || orig <= 0)) ETD_FAIL(ETD_EINVAL, "frontend_create: bad resampler table");
+  if (sr_in != sr_out) {
+    // k_resample keeps (RB-1)*orig + K input samples in dynamic LDS: a pair with a small gcd asks for more than a workgroup may have.
+    // Refuse it here, against what this device reports, before anything is uploaded or launched.
+    int dev = 0, lds_limit = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    HIP_TRY(hipDeviceGetAttribute(&lds_limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+    const long long span = (long long)(RB - 1) * orig + K;
+    if (span * (long long)sizeof(float) > (long long)lds_limit)
+      ETD_FAIL(ETD_EINVAL, "frontend_create: resampling %d -> %d Hz (orig %d, new %d) needs %lld bytes of LDS per workgroup, the device allows %d",
+               sr_in, sr_out, orig, nw, span * (long long)sizeof(float), lds_limit);
+  }
   std::vector<int> off(n_mels);
   int tot = 0;
   for (int m = 0; m < n_mels; ++m) {
@@ -228,6 +239,7 @@ extern "C" int etd_frontend_run(etd_frontend* f, const float* wav_dev, int chann
                        f->kernT, f->K, f->width, f->orig, f->nw, resampled_dev, n16);
   }
   }
+  HIP_TRY(hipGetLastError());            // a refused launch must not be followed by the STFT on an unwritten buffer
   if (!feat_dev) {                       // channel mean + resample only (analyze_volume needs no spectrogram)
     HIP_TRY(hipGetLastError());
     if (n_frames_out) *n_frames_out = 0;

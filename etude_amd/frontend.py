@@ -44,7 +44,12 @@ def _mel_csr(n_freqs: int, f_max: float, n_mels: int, sample_rate: int):
     up = slopes[:, 2:] / f_diff[1:]
     fb = torch.max(torch.zeros(1), torch.min(down, up))
     fb = fb * (2.0 / (f_pts[2:n_mels + 2] - f_pts[:n_mels])).unsqueeze(0)     # slaney
-    fb = fb.numpy()                                                             # [n_freqs, n_mels]
+    return _dense_to_csr(fb.numpy())                                            # [n_freqs, n_mels]
+
+
+def _dense_to_csr(fb: np.ndarray):
+    """Band m as the span from its first to its last non-zero weight (zeros inside the span are stored; an all-zero band has length 0)."""
+    n_mels = fb.shape[1]
     start = np.zeros(n_mels, np.int32)
     length = np.zeros(n_mels, np.int32)
     w = []

@@ -84,7 +84,9 @@ typedef struct etd_frontend etd_frontend;
  *   kernT_host [K][nw]   polyphase sinc kernel, transposed (k-major); orig/nw = sr_in/gcd, sr_out/gcd
  *   window_host[n_fft]   periodic Hann
  *   mel filterbank in CSR form: filter m covers power-spectrum bins [mel_start[m], +mel_len[m]) with
- *   weights mel_w[sum(mel_len[:m]) ...].  */
+ *   weights mel_w[sum(mel_len[:m]) ...].
+ * The resampler holds 7 * orig + K input samples in LDS: a rate pair whose span exceeds the device's per-workgroup
+ * shared-memory limit is refused here with ETD_EINVAL and a message naming the pair; nothing is uploaded or launched.  */
 int etd_frontend_create(int sr_in, int sr_out, int orig, int nw, int K, int width, const float* kernT_host,
                         int n_fft, int hop, const float* window_host, int n_mels, const int* mel_start,
                         const int* mel_len, const float* mel_w_host, float log_offset, etd_frontend** out);
