@@ -51,16 +51,6 @@ __host__ __device__ __forceinline__ long long af_frame(long long m, int tier, lo
   return f < T - 1 ? f : T - 1;
 }
 
-// the song whose workgroup range holds b (blk0 ascending; b < total)
-__device__ __forceinline__ int af_song_of(const AfSong* tab, int n_songs, long long b) {
-  int lo = 0, hi = n_songs - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (tab[mid].blk0 <= b) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
 // ---- decimation by 5: y[m] = sum_n h[n] x[5 m - n], n = -240 .. 240 ascending, zeros outside the signal (a term with a zero sample leaves the chain's value unchanged)
 __global__ __launch_bounds__(AF_THREADS) void k_af_decim(const AfArgs a, int tier) {
   const AfSong& sg = a.tab[blockIdx.y];
@@ -82,7 +72,7 @@ __global__ __launch_bounds__(AF_THREADS) void k_af_decim(const AfArgs a, int tie
 template <bool BACK, bool OUT>
 __global__ __launch_bounds__(AF_IIR_THREADS) void k_af_iir(const AfArgs a) {
   const long long blk = blockIdx.x;
-  const int s = af_song_of(a.tab, a.n_songs, blk);
+  const int s = song_of(a.tab, a.n_songs, blk);
   const AfSong& sg = a.tab[s];
   const long long local = blk - sg.blk0;
   int band; long long cb;

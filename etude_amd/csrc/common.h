@@ -134,4 +134,23 @@ __device__ __forceinline__ void wave_sum_n(float (&v)[N]) {
 #pragma unroll
   for (int j = 0; j < N; ++j) v[j] = wave_sum_lat(v[j]);
 }
+
+// Ragged batches: the song whose workgroup range holds b, in a per-call table whose entries carry their first workgroup blk0 (ascending; b < total)
+template <class Song>
+__device__ __forceinline__ int song_of(const Song* tab, int n_songs, long long b) {
+  int lo = 0, hi = n_songs - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (tab[mid].blk0 <= b) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// Band m of a filterbank in CSR form (bins start[m] .. start[m] + len[m] - 1, weights from w[off[m]]) over the spectrum pw: one fmaf chain, bins ascending
+__device__ __forceinline__ float csr_band(const float* pw, const int* start, const int* len, const int* off, const float* w, int m) {
+  const int s0 = start[m], n = len[m], o = off[m];
+  float acc = 0.f;
+  for (int i = 0; i < n; ++i) acc = fmaf(pw[s0 + i], w[o + i], acc);
+  return acc;
+}
 #endif

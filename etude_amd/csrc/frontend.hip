@@ -102,12 +102,8 @@ __global__ __launch_bounds__(256) void k_stft_mel(const float* __restrict__ x, l
   }
   for (int f = threadIdx.x; f <= half; f += blockDim.x) pw[f] = re[f] * re[f] + im[f] * im[f];
   __syncthreads();
-  for (int m = threadIdx.x; m < n_mels; m += blockDim.x) {
-    const int s0 = mel_start[m], n = mel_len[m], o = mel_off[m];
-    float acc = 0.f;
-    for (int i = 0; i < n; ++i) acc = fmaf(pw[s0 + i], mel_w[o + i], acc);
-    feat[t * n_mels + m] = logf(acc + log_offset);
-  }
+  for (int m = threadIdx.x; m < n_mels; m += blockDim.x)
+    feat[t * n_mels + m] = logf(csr_band(pw, mel_start, mel_len, mel_off, mel_w, m) + log_offset);
 }
 
 // ------------------------------------------------------------------------------------------------

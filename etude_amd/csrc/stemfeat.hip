@@ -8,10 +8,8 @@
 //   k_sf_db      in place: 10 log10(max(amin, S)) - 10 log10(max(amin, ref)), clamped at -top_db
 // Everything but the maximum is computed per frame from that stem's samples in a fixed order, so a stem's features are bit-identical alone and in any batch.
 //
-// The FFT: a real frame of n_fft samples is the complex sequence z[i] = x[2i] + i x[2i + 1] of M = n_fft / 2 points; one Stockham (self-sorting, out-of-place
-// between two LDS buffers) FFT of M points -- a radix-2 stage first when log2 M is odd (its twiddles are all 1), then radix-4 stages -- and a split pass
-// X[k] = E[k] + W^k O[k] give the n_fft / 2 + 1 bins.  n_fft = 4096: 6 passes and barriers where the radix-2 complex FFT of the full frame takes 12.
-// Twiddles come from tables built in fp64 on the host (every power is looked up, none is formed by multiplication on the device).
+// The FFT is the packed-real Stockham plan of csrc/lds_rfft.h (M = n_fft / 2 = 32 .. 2048 complex points, 256 threads) with the table exp(-2 pi i n / M) copied into
+// padded LDS once per workgroup, which is why a workgroup takes SF_FRAMES frames.
 #include "stemfeat.h"
 #include "prof.h"
 
@@ -27,36 +25,26 @@ struct SfArgs {
   float* feat; float* wgmax;
 };
 
-// the song whose workgroup range holds b (blk0 ascending; b < total)
-__device__ __forceinline__ int sf_song_of(const SfSong* tab, int n_songs, long long b) {
-  int lo = 0, hi = n_songs - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (tab[mid].blk0 <= b) lo = mid; else hi = mid - 1;
+// the workgroup's maximum of mx -> *dst, by thread 0 (red: one float per wave)
+__device__ __forceinline__ void sf_block_max(float mx, float* red, int tid, float* dst) {
+  mx = wave_max(mx);
+  if ((tid & 63) == 0) red[tid >> 6] = mx;
+  __syncthreads();
+  if (tid == 0) {
+    float v = red[0];
+    for (int w = 1; w < SF_THREADS / 64; ++w) v = fmaxf(v, red[w]);
+    *dst = v;
   }
-  return lo;
-}
-
-// (xr + i xi)(wr + i wi) as four multiplies, a subtraction and an addition of their own (the roundings of the plain expression under -ffp-contract=off).  Left to the
-// SLP vectoriser the products are paired crosswise into v_pk_mul_f32 ... op_sel:[0,1], the packed form kept out of this library (tests/test_isa_guard.py).
-__device__ __forceinline__ void sf_cmul(float xr, float xi, float wr, float wi, float& yr, float& yi) {
-  float a, b, c, d;
-  asm volatile("v_mul_f32 %0, %1, %2" : "=v"(a) : "v"(xr), "v"(wr));
-  asm volatile("v_mul_f32 %0, %1, %2" : "=v"(b) : "v"(xi), "v"(wi));
-  asm volatile("v_mul_f32 %0, %1, %2" : "=v"(c) : "v"(xr), "v"(wi));
-  asm volatile("v_mul_f32 %0, %1, %2" : "=v"(d) : "v"(xi), "v"(wr));
-  yr = a - b;
-  yi = c + d;
 }
 
 __global__ __launch_bounds__(SF_THREADS) void k_sf_frames(const SfArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   __shared__ float red[SF_THREADS / 64];
-  const int M = a.n_fft >> 1, PM = SF_PAD(M) + 1, tid = threadIdx.x;
+  const int M = a.n_fft >> 1, PM = RFFT_PM(M), tid = threadIdx.x;
   float *sr = sm, *si = sm + PM, *dr = sm + 2 * PM, *di = sm + 3 * PM;
-  float2* tw = (float2*)(sm + 4 * PM);                 // exp(-2 pi i n / M), n < M, at SF_PAD(n)
+  float2* tw = (float2*)(sm + 4 * PM);                 // exp(-2 pi i n / M), n < M, at RFFT_PAD(n)
   const long long b = blockIdx.x;
-  const int s = sf_song_of(a.tab, a.n_songs, b);
+  const int s = song_of(a.tab, a.n_songs, b);
   const SfSong sg = a.tab[s];
   const long long local = b - sg.blk0;
   const int stem = (int)(local / sg.cps);
@@ -64,7 +52,7 @@ __global__ __launch_bounds__(SF_THREADS) void k_sf_frames(const SfArgs a) {
   const float* wav = sg.wav + (long long)stem * a.channels * sg.N;
   float* out = a.feat + sg.feat_off + (long long)stem * sg.T * a.n_mels;
   const float fch = (float)a.channels;
-  for (int n = tid; n < M; n += SF_THREADS) tw[SF_PAD(n)] = a.twM[n];
+  for (int n = tid; n < M; n += SF_THREADS) tw[RFFT_PAD(n)] = a.twM[n];
   float mx = 0.f;                                      // (mel power is >= 0)
   for (int f = 0; f < SF_FRAMES; ++f) {
     const long long t = t0 + f;
@@ -84,81 +72,34 @@ __global__ __launch_bounds__(SF_THREADS) void k_sf_frames(const SfArgs a) {
         for (int c = 1; c < a.channels; ++c) v += wav[(long long)c * sg.N + idx];
         v = (v / fch) * a.window[i];
       }
-      ((i & 1) ? si : sr)[SF_PAD(i >> 1)] = v;
+      ((i & 1) ? si : sr)[RFFT_PAD(i >> 1)] = v;
     }
     __syncthreads();
-    // ---- Stockham FFT of M complex points
+    // ---- Stockham FFT of M complex points (the plan of lds_rfft.h): every pass goes from (sr, si) to (dr, di) and swaps them, so Z lands in (sr, si)
     int Ns = 1, lgNs = 0;
     if (a.lgM & 1) {
-      for (int j = tid; j < (M >> 1); j += SF_THREADS) {
-        const int i0 = SF_PAD(j), i1 = SF_PAD(j + (M >> 1));
-        const float ar = sr[i0], ai = si[i0], br = sr[i1], bi = si[i1];
-        const int o0 = SF_PAD(2 * j), o1 = SF_PAD(2 * j + 1);
-        dr[o0] = ar + br; di[o0] = ai + bi;
-        dr[o1] = ar - br; di[o1] = ai - bi;
-      }
+      for (int j = tid; j < (M >> 1); j += SF_THREADS) rfft::radix2(sr, si, dr, di, M, j);
       __syncthreads();
       float* q = sr; sr = dr; dr = q; q = si; si = di; di = q;
       Ns = 2; lgNs = 1;
     }
-    const int Q = M >> 2;
     for (; Ns < M; Ns <<= 2, lgNs += 2) {
-      const int st = M >> (lgNs + 2);                  // twiddle stride: w^r = exp(-2 pi i k r / (4 Ns)) = tw[k r st]
-      for (int j = tid; j < Q; j += SF_THREADS) {
-        const int k = j & (Ns - 1), j0 = ((j - k) << 2) + k;
-        const int i0 = SF_PAD(j), i1 = SF_PAD(j + Q), i2 = SF_PAD(j + 2 * Q), i3 = SF_PAD(j + 3 * Q);
-        const float2 w1 = tw[SF_PAD(k * st)], w2 = tw[SF_PAD(2 * k * st)], w3 = tw[SF_PAD(3 * k * st)];
-        const float v0r = sr[i0], v0i = si[i0];
-        float v1r, v1i, v2r, v2i, v3r, v3i;
-        sf_cmul(sr[i1], si[i1], w1.x, w1.y, v1r, v1i);
-        sf_cmul(sr[i2], si[i2], w2.x, w2.y, v2r, v2i);
-        sf_cmul(sr[i3], si[i3], w3.x, w3.y, v3r, v3i);
-        const float a0r = v0r + v2r, a0i = v0i + v2i, a1r = v0r - v2r, a1i = v0i - v2i;
-        const float a2r = v1r + v3r, a2i = v1i + v3i;
-        const float a3r = v1i - v3i, a3i = -(v1r - v3r);          // -i (v1 - v3)
-        const int o0 = SF_PAD(j0), o1 = SF_PAD(j0 + Ns), o2 = SF_PAD(j0 + 2 * Ns), o3 = SF_PAD(j0 + 3 * Ns);
-        dr[o0] = a0r + a2r; di[o0] = a0i + a2i;
-        dr[o1] = a1r + a3r; di[o1] = a1i + a3i;
-        dr[o2] = a0r - a2r; di[o2] = a0i - a2i;
-        dr[o3] = a1r - a3r; di[o3] = a1i - a3i;
-      }
+      for (int j = tid; j < (M >> 2); j += SF_THREADS) rfft::radix4(sr, si, dr, di, rfft::TwLds{tw}, M, Ns, M >> (lgNs + 2), j);
       __syncthreads();
       float* q = sr; sr = dr; dr = q; q = si; si = di; di = q;
     }
-    // ---- split pass: X[k] = E + W^k O, E = (Z[k] + conj Z[M - k]) / 2, O = -i (Z[k] - conj Z[M - k]) / 2, W = exp(-2 pi i / n_fft); power into the free buffer
+    // ---- split pass; the power goes into the free pair
     float* pw = dr;                                    // [M + 1], unpadded
-    for (int k = tid; k <= M; k += SF_THREADS) {
-      const int ia = SF_PAD(k & (M - 1)), ib = SF_PAD((M - k) & (M - 1));
-      const float ar = sr[ia], ai = si[ia], br = sr[ib], bi = -si[ib];
-      const float er = 0.5f * (ar + br), ei = 0.5f * (ai + bi);
-      const float orr = 0.5f * (ai - bi), oi = -0.5f * (ar - br);
-      const float2 w = a.twS[k];
-      float pr, pi;
-      sf_cmul(orr, oi, w.x, w.y, pr, pi);
-      const float xr = er + pr, xi = ei + pi;
-      float p0, p1;
-      asm volatile("v_mul_f32 %0, %1, %1" : "=v"(p0) : "v"(xr));
-      asm volatile("v_mul_f32 %0, %1, %1" : "=v"(p1) : "v"(xi));
-      pw[k] = p0 + p1;
-    }
+    for (int k = tid; k <= M; k += SF_THREADS) pw[k] = rfft::split_power(sr, si, a.twS, M, k);
     __syncthreads();
     for (int m = tid; m < a.n_mels; m += SF_THREADS) {
-      const int s0 = a.mel_start[m], n = a.mel_len[m], o = a.mel_off[m];
-      float acc = 0.f;
-      for (int i = 0; i < n; ++i) acc = fmaf(pw[s0 + i], a.mel_w[o + i], acc);
+      const float acc = csr_band(pw, a.mel_start, a.mel_len, a.mel_off, a.mel_w, m);
       out[t * a.n_mels + m] = acc;
       mx = fmaxf(mx, acc);
     }
     __syncthreads();                                   // (the next frame's samples overwrite the buffers pw may live in)
   }
-  mx = wave_max(mx);
-  if ((tid & 63) == 0) red[tid >> 6] = mx;
-  __syncthreads();
-  if (tid == 0) {
-    float v = red[0];
-    for (int w = 1; w < SF_THREADS / 64; ++w) v = fmaxf(v, red[w]);
-    a.wgmax[b] = v;
-  }
+  sf_block_max(mx, red, tid, a.wgmax + b);
 }
 
 __global__ __launch_bounds__(SF_THREADS) void k_sf_max(const SfSong* __restrict__ tab, int instr, const float* __restrict__ wgmax, float* __restrict__ ref) {
@@ -168,14 +109,7 @@ __global__ __launch_bounds__(SF_THREADS) void k_sf_max(const SfSong* __restrict_
   const float* p = wgmax + tab[s].blk0 + (long long)stem * n;
   float mx = 0.f;
   for (long long i = tid; i < n; i += SF_THREADS) mx = fmaxf(mx, p[i]);
-  mx = wave_max(mx);
-  if ((tid & 63) == 0) red[tid >> 6] = mx;
-  __syncthreads();
-  if (tid == 0) {
-    float v = red[0];
-    for (int w = 1; w < SF_THREADS / 64; ++w) v = fmaxf(v, red[w]);
-    ref[blockIdx.x] = v;
-  }
+  sf_block_max(mx, red, tid, ref + blockIdx.x);
 }
 
 // y = 10 log10(max(amin, S)) - 10 log10(max(amin, ref)); the stem's largest S gives exactly 0 (the same expression on both sides), so max(y) = 0 and power_to_db's
@@ -296,11 +230,7 @@ extern "C" int etd_stemfeat_create(const etd_stemfeat_cfg* cfg, const float* win
   h->mel_off = off;
   h->mel_w.assign(mel_w_host, mel_w_host + tot);
   if (h->mel_w.empty()) h->mel_w.push_back(0.f);
-  const double pi = 3.14159265358979323846;
-  h->twM.resize(h->M);
-  for (int n = 0; n < h->M; ++n) h->twM[n] = make_float2((float)cos(-2.0 * pi * n / h->M), (float)sin(-2.0 * pi * n / h->M));
-  h->twS.resize(h->M + 1);
-  for (int k = 0; k <= h->M; ++k) h->twS[k] = make_float2((float)cos(-2.0 * pi * k / n_fft), (float)sin(-2.0 * pi * k / n_fft));
+  rfft_twiddles(h->M, h->twM, h->twS);
   *out = h;
   return ETD_OK;
 }
@@ -368,7 +298,7 @@ extern "C" int etd_stemfeat_run(etd_stemfeat* h, const float* const* wav_ptrs, i
     // 5 N log2 N flops of an M-point complex FFT + the split pass + the CSR product; bytes: every sample once + the mel power written
     ProfScope ps("k_sf_frames", st, fr * (5.0 * h->M * h->lgM + 12.0 * h->M + 2.0 * (double)h->mel_w.size()),
                  fr * ((double)c.hop * channels * 4 + (double)c.n_mels * 4));
-    const size_t lds = (size_t)6 * (SF_PAD(h->M) + 1) * sizeof(float);
+    const size_t lds = (size_t)SF_LDS_FLOATS(h->M) * sizeof(float);
     hipLaunchKernelGGL(k_sf_frames, dim3((unsigned)blocks), dim3(SF_THREADS), lds, st, a);
   }
   {

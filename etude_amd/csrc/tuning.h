@@ -1,6 +1,7 @@
 // Tuning estimation (csrc/tuning.hip): the layout constants the kernels and the host side share.  DESIGN.md 4g is the contract.
 #pragma once
 #include "host_util.h"
+#include "lds_rfft.h"
 #include "../../include/etude_hip.h"
 #include "../../include/etude_hip_debug.h"
 
@@ -22,8 +23,8 @@
 #define TN_MAX_N (1LL << 27)        // samples per song, the limit of etd_alignfeat_*
 #define TN_MAX_SONGS 4096
 #define TN_MAX_TAPS 8               // frames whose power one call of the debug hook can tap
-// LDS index of complex point i (SF_PAD of stemfeat.h): one float of padding after every 32
-#define TN_PAD(i) ((i) + ((i) >> 5))
+// dynamic LDS of the frame kernel: the two buffer pairs of the FFT (4 x 8 449 floats; the twiddles stay in global memory)
+#define TN_LDS_BYTES (4 * RFFT_PM(TN_M) * (int)sizeof(float))
 
 // one song of a call (device table at the head of the workspace, built per call); the off_* are BYTE offsets into the workspace
 struct TnSong {

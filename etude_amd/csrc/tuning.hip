@@ -10,10 +10,9 @@
 //                average, rectification, the comb, the first maximum
 // No atomics, no flags, no spinning: a song's numbers depend on its own samples and the tables alone, in a fixed order.
 //
-// The FFT is the plan of csrc/stemfeat.hip at four times the size: the real frame is the complex sequence z[i] = x[2i] + i x[2i + 1] of M = 8 192 points, one Stockham
-// (self-sorting, out of place between two LDS buffers) FFT -- a radix-2 stage first (log2 M = 13 is odd; its twiddles are all 1), then six radix-4 stages -- and the split
-// pass X[k] = E[k] + W^k O[k].  The two buffers take 4 x 8 449 floats = 135 184 bytes, so the twiddle table (64 KB) cannot sit in LDS next to them as it does there: it
-// is read from global memory (it stays in the L2), every power looked up, none formed by multiplication on the device.
+// The FFT is the packed-real Stockham plan of csrc/lds_rfft.h at M = 8 192 complex points (log2 M = 13: the radix-2 stage, then six radix-4 stages) and 1 024 threads.
+// The two buffer pairs take 4 x 8 449 floats = 135 184 bytes, so the table exp(-2 pi i n / M) (64 KB) cannot sit in LDS next to them as it does for the stem features:
+// it is read from global memory (it stays in the L2).
 #include "tuning.h"
 #include "prof.h"
 
@@ -34,60 +33,20 @@ struct TnArgs {
   float* tap_P; int tap_song, tap_n; int tap_frame[TN_MAX_TAPS];
 };
 
-// the song whose workgroup range holds b (blk0 ascending; b < total)
-__device__ __forceinline__ int tn_song_of(const TnSong* tab, int n_songs, long long b) {
-  int lo = 0, hi = n_songs - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (tab[mid].blk0 <= b) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
-// (xr + i xi)(wr + i wi): sf_cmul of csrc/stemfeat.hip -- four multiplies of their own, so that the SLP vectoriser cannot pair them crosswise into the packed form
-// tests/test_isa_guard.py keeps out of this library
-__device__ __forceinline__ void tn_cmul(float xr, float xi, float wr, float wi, float& yr, float& yi) {
-  float a, b, c, d;
-  asm volatile("v_mul_f32 %0, %1, %2" : "=v"(a) : "v"(xr), "v"(wr));
-  asm volatile("v_mul_f32 %0, %1, %2" : "=v"(b) : "v"(xi), "v"(wi));
-  asm volatile("v_mul_f32 %0, %1, %2" : "=v"(c) : "v"(xr), "v"(wi));
-  asm volatile("v_mul_f32 %0, %1, %2" : "=v"(d) : "v"(xi), "v"(wr));
-  yr = a - b;
-  yi = c + d;
-}
-
-// one radix-4 Stockham stage over M points, Ns = 2^LG points per transform so far: (sr, si) -> (dr, di); 2 butterflies per thread
+// one radix-4 pass of the frame kernel, Ns = 2^LG points per transform so far, and its barrier; 2 butterflies per thread
 template <int LG>
-__device__ __forceinline__ void tn_radix4(const float* sr, const float* si, float* dr, float* di, const float2* __restrict__ tw, int tid) {
-  constexpr int Ns = 1 << LG, Q = TN_M >> 2, st = TN_M >> (LG + 2);          // twiddle stride: w^r = exp(-2 pi i k r / (4 Ns)) = tw[k r st]
-  for (int j = tid; j < Q; j += TN_THREADS) {
-    const int k = j & (Ns - 1), j0 = ((j - k) << 2) + k;
-    const int i0 = TN_PAD(j), i1 = TN_PAD(j + Q), i2 = TN_PAD(j + 2 * Q), i3 = TN_PAD(j + 3 * Q);
-    const float2 w1 = tw[k * st], w2 = tw[2 * k * st], w3 = tw[3 * k * st];
-    const float v0r = sr[i0], v0i = si[i0];
-    float v1r, v1i, v2r, v2i, v3r, v3i;
-    tn_cmul(sr[i1], si[i1], w1.x, w1.y, v1r, v1i);
-    tn_cmul(sr[i2], si[i2], w2.x, w2.y, v2r, v2i);
-    tn_cmul(sr[i3], si[i3], w3.x, w3.y, v3r, v3i);
-    const float a0r = v0r + v2r, a0i = v0i + v2i, a1r = v0r - v2r, a1i = v0i - v2i;
-    const float a2r = v1r + v3r, a2i = v1i + v3i;
-    const float a3r = v1i - v3i, a3i = -(v1r - v3r);          // -i (v1 - v3)
-    const int o0 = TN_PAD(j0), o1 = TN_PAD(j0 + Ns), o2 = TN_PAD(j0 + 2 * Ns), o3 = TN_PAD(j0 + 3 * Ns);
-    dr[o0] = a0r + a2r; di[o0] = a0i + a2i;
-    dr[o1] = a1r + a3r; di[o1] = a1i + a3i;
-    dr[o2] = a0r - a2r; di[o2] = a0i - a2i;
-    dr[o3] = a1r - a3r; di[o3] = a1i - a3i;
-  }
+__device__ __forceinline__ void tn_stage(const float* sr, const float* si, float* dr, float* di, const float2* __restrict__ tw, int tid) {
+  for (int j = tid; j < (TN_M >> 2); j += TN_THREADS) rfft::radix4(sr, si, dr, di, rfft::TwGlobal{tw}, TN_M, 1 << LG, TN_M >> (LG + 2), j);
   __syncthreads();
 }
 
 __global__ __launch_bounds__(TN_THREADS) void k_tn_frames(const TnArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  constexpr int M = TN_M, PM = TN_PAD(TN_M) + 1;
+  constexpr int M = TN_M, PM = RFFT_PM(TN_M);
   const int tid = threadIdx.x;
   float *ar = sm, *ai = sm + PM, *br = sm + 2 * PM, *bi = sm + 3 * PM;
   const long long b = blockIdx.x;
-  const int s = tn_song_of(a.tab, a.n_songs, b);
+  const int s = song_of(a.tab, a.n_songs, b);
   const TnSong& sg = a.tab[s];
   const long long g = b - sg.blk0, N = sg.N, F = sg.F;
   const float* wav = sg.wav;
@@ -101,26 +60,19 @@ __global__ __launch_bounds__(TN_THREADS) void k_tn_frames(const TnArgs a) {
       const long long i0 = base + 2 * i, i1 = i0 + 1;
       const float v0 = (i0 >= 0 && i0 < N) ? wav[i0] * a.window[2 * i] : 0.f;
       const float v1 = (i1 >= 0 && i1 < N) ? wav[i1] * a.window[2 * i + 1] : 0.f;
-      ar[TN_PAD(i)] = v0; ai[TN_PAD(i)] = v1;
+      ar[RFFT_PAD(i)] = v0; ai[RFFT_PAD(i)] = v1;
     }
     __syncthreads();
-    // ---- Stockham FFT of M complex points: A -> B -> A ... seven passes, the result lands in B
-    for (int j = tid; j < (M >> 1); j += TN_THREADS) {
-      const int i0 = TN_PAD(j), i1 = TN_PAD(j + (M >> 1));
-      const float xr = ar[i0], xi = ai[i0], yr = ar[i1], yi = ai[i1];
-      const int o0 = TN_PAD(2 * j), o1 = TN_PAD(2 * j + 1);
-      br[o0] = xr + yr; bi[o0] = xi + yi;
-      br[o1] = xr - yr; bi[o1] = xi - yi;
-    }
+    // ---- Stockham FFT of M complex points (the plan of lds_rfft.h, its sizes constants): A -> B -> A ... seven passes, so Z lands in B
+    for (int j = tid; j < (M >> 1); j += TN_THREADS) rfft::radix2(ar, ai, br, bi, M, j);
     __syncthreads();
-    tn_radix4<1>(br, bi, ar, ai, a.twM, tid);
-    tn_radix4<3>(ar, ai, br, bi, a.twM, tid);
-    tn_radix4<5>(br, bi, ar, ai, a.twM, tid);
-    tn_radix4<7>(ar, ai, br, bi, a.twM, tid);
-    tn_radix4<9>(br, bi, ar, ai, a.twM, tid);
-    tn_radix4<11>(ar, ai, br, bi, a.twM, tid);
-    // ---- split pass: X[k] = E + W^k O, E = (Z[k] + conj Z[M - k]) / 2, O = -i (Z[k] - conj Z[M - k]) / 2, W = exp(-2 pi i / n_fft); power, compression, the
-    // group's sum.  It reads B alone and the next frame's samples go to A, so no barrier stands between them.
+    tn_stage<1>(br, bi, ar, ai, a.twM, tid);
+    tn_stage<3>(ar, ai, br, bi, a.twM, tid);
+    tn_stage<5>(br, bi, ar, ai, a.twM, tid);
+    tn_stage<7>(ar, ai, br, bi, a.twM, tid);
+    tn_stage<9>(br, bi, ar, ai, a.twM, tid);
+    tn_stage<11>(ar, ai, br, bi, a.twM, tid);
+    // ---- split pass: power, compression, the group's sum.  It reads B alone and the next frame's samples go to A, so no barrier stands between them.
     int slot = -1;
     if (a.tap_P && s == a.tap_song) {
 #pragma unroll
@@ -132,18 +84,8 @@ __global__ __launch_bounds__(TN_THREADS) void k_tn_frames(const TnArgs a) {
     for (int j = 0; j < TN_BPT; ++j) {
       const int k = tid + j * TN_THREADS;
       if (k <= M) {
-        const int ia = TN_PAD(k & (M - 1)), ib = TN_PAD((M - k) & (M - 1));
-        const float zr = br[ia], zi = bi[ia], cr = br[ib], ci = -bi[ib];
-        const float er = 0.5f * (zr + cr), ei = 0.5f * (zi + ci);
-        const float orr = 0.5f * (zi - ci), oi = -0.5f * (zr - cr);
-        const float2 w = a.twS[k];
-        float pr, pi;
-        tn_cmul(orr, oi, w.x, w.y, pr, pi);
-        const float xr = er + pr, xi = ei + pi;
-        float p0, p1, p100;
-        asm volatile("v_mul_f32 %0, %1, %1" : "=v"(p0) : "v"(xr));
-        asm volatile("v_mul_f32 %0, %1, %1" : "=v"(p1) : "v"(xi));
-        const float P = p0 + p1;
+        const float P = rfft::split_power(br, bi, a.twS, M, k);
+        float p100;
         asm volatile("v_mul_f32 %0, %1, %2" : "=v"(p100) : "v"(P), "v"(100.f));          // (a product of its own: 1 + 100 P is not to become one fused operation)
         const float c = logf(1.f + p100);
         part[k] = q == 0 ? c : part[k] + c;
@@ -308,7 +250,7 @@ int tn_upload(etd_tuning* h) {
   ETD_TRY_OR(fail, P.upload(&h->d_tt, h->tt.data(), h->tt.size()));
   ETD_TRY_OR(fail, P.upload(&h->d_iv, h->iv.data(), h->iv.size()));
   // both kernels ask for more dynamic LDS than the 64 KB a launch gets without saying so
-  ETD_TRY_OR(fail, ETD_HIP_RC(hipFuncSetAttribute((const void*)k_tn_frames, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (TN_PAD(TN_M) + 1) * (int)sizeof(float))));
+  ETD_TRY_OR(fail, ETD_HIP_RC(hipFuncSetAttribute((const void*)k_tn_frames, hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES)));
   ETD_TRY_OR(fail, ETD_HIP_RC(hipFuncSetAttribute((const void*)k_tn_tail, hipFuncAttributeMaxDynamicSharedMemorySize, TN_BINS * (int)sizeof(double))));
   h->on_dev = true;
   return ETD_OK;
@@ -333,10 +275,7 @@ extern "C" int etd_tuning_create(const etd_tuning_cfg* cfg, etd_tuning** out) {
   const double pi = 3.14159265358979323846;
   h->window.resize(TN_NFFT);
   for (int n = 0; n < TN_NFFT; ++n) h->window[n] = (float)(0.5 - 0.5 * cos(2.0 * pi * n / TN_NFFT));
-  h->twM.resize(TN_M);
-  for (int n = 0; n < TN_M; ++n) h->twM[n] = make_float2((float)cos(-2.0 * pi * n / TN_M), (float)sin(-2.0 * pi * n / TN_M));
-  h->twS.resize(TN_M + 1);
-  for (int k = 0; k <= TN_M; ++k) h->twS[k] = make_float2((float)cos(-2.0 * pi * k / TN_NFFT), (float)sin(-2.0 * pi * k / TN_NFFT));
+  rfft_twiddles(TN_M, h->twM, h->twS);
   // the elimination's pivots: p_0 = 1 (upper 2), p_i = 4 - cp_{i-1} (upper 1), p_{n-1} = 1 - 2 cp_{n-2}
   const int n = TN_BINS;
   h->rp.resize(n); h->cp.resize(n);
@@ -430,7 +369,7 @@ extern "C" int etd_tuning_run(etd_tuning* h, const float* const* wav_ptrs, int n
   {
     // 5 M log2 M flops of the M-point complex FFT + the split pass and the logarithm; bytes: every sample twice (the windows overlap by half)
     ProfScope ps("k_tn_frames", st, frames * (5.0 * TN_M * TN_LGM + 20.0 * TN_M), frames * TN_NFFT * 4.0);
-    hipLaunchKernelGGL(k_tn_frames, dim3((unsigned)blocks), dim3(TN_THREADS), (size_t)4 * (TN_PAD(TN_M) + 1) * sizeof(float), st, a);
+    hipLaunchKernelGGL(k_tn_frames, dim3((unsigned)blocks), dim3(TN_THREADS), (size_t)TN_LDS_BYTES, st, a);
   }
   {
     ProfScope ps("k_tn_sum", st, 0, (double)blocks * TN_BINS * 4.0);

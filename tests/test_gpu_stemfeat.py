@@ -87,6 +87,20 @@ def test_smallest_transform():
     _check(_stems(16 * 20 + 3, 1, 1), "spleeter", n_fft=64, hop=16, n_mels=8)
 
 
+def test_even_log2_transform():
+    """log2 of the half length even (6, 8, 10): no radix-2 stage opens the plan, so the pass count and with it the buffer pair that holds the spectrum change parity;
+    n_fft = 2048 also has more butterflies per stage than threads"""
+    _check(_stems(32 * 40 + 5, 2, 2), "librosa", n_fft=128, hop=32, n_mels=16)
+    _check(_stems(32 * 40 + 5, 2, 2), "librosa_reflect", n_fft=128, hop=32, n_mels=16)
+    _check(_stems(128 * 30 + 11, 2, 2), "spleeter", n_fft=512, hop=128, n_mels=32)
+    _check(_stems(512 * 20 + 3, 2, 2), "librosa", n_fft=2048, hop=512, n_mels=64)
+
+
+def test_odd_log2_transform_1024():
+    """n_fft = 1024 (log2 of the half length = 9), the odd size between 256 and 4096"""
+    _check(_stems(256 * 20 + 3, 2, 2), "librosa_reflect", n_fft=1024, hop=256, n_mels=64)
+
+
 def test_edges_exact():
     x = _stems(MAIN_N)
     for framing in sn.FRAMINGS:
@@ -111,6 +125,23 @@ def test_invariance_bitwise():
     assert np.array_equal(rev.cpu().numpy(), np.concatenate([a.ravel() for a in alone[::-1]]))
     host, _ = sf.features_many([songs[0], torch.from_numpy(np.array(songs[1])), dev[2]])          # numpy, host tensor, device tensor
     assert np.array_equal(host.cpu().numpy(), packed.cpu().numpy())
+    again, _ = sf.features_many(dev)
+    assert torch.equal(again, packed)
+
+
+def test_invariance_bitwise_even_log2():
+    """the same at n_fft = 512 (no radix-2 stage): three songs of different lengths, whose last workgroups hold 3, 2 and 4 frames, alone, packed and reversed"""
+    sf = _sf("librosa", n_fft=512, hop=128, n_mels=32)
+    songs = [_stems(128 * 30 + 11, 2, 2, seed=1), _stems(128 * 57 + 100, 2, 2, seed=2), _stems(128 * 19 + 1, 2, 2, seed=3)]
+    dev = [torch.from_numpy(np.array(s)).cuda() for s in songs]
+    alone = [sf.features(d).cpu().numpy() for d in dev]
+    assert sorted(a.shape[1] % 4 for a in alone) == [0, 2, 3]          # (T = 31, 58, 20: a full last workgroup and two partial ones)
+    packed, Ts = sf.features_many(dev)
+    assert Ts == [a.shape[1] for a in alone] and packed.numel() == sum(a.size for a in alone)
+    assert np.array_equal(packed.cpu().numpy(), np.concatenate([a.ravel() for a in alone]))
+    rev, Tr = sf.features_many(dev[::-1])
+    assert Tr == Ts[::-1]
+    assert np.array_equal(rev.cpu().numpy(), np.concatenate([a.ravel() for a in alone[::-1]]))
     again, _ = sf.features_many(dev)
     assert torch.equal(again, packed)
 
