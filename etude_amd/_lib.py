@@ -114,6 +114,14 @@ class G3Case(_SizedCfg):
                [("rope_cos", C.c_void_p), ("rope_sin", C.c_void_p), ("Q", C.c_void_p), ("q_elems", C.c_longlong), ("Kc", C.c_void_p), ("Vc", C.c_void_p), ("kv_elems", C.c_longlong)]
 
 
+class Attn3Case(_SizedCfg):
+    """etd_debug_attn3_case of include/etude_hip_debug.h: one launch_attn3 call, strided or ragged causal, with every stride, slot and bound"""
+    _fields_ = [("struct_bytes", C.c_int)] + [(n, C.c_int) for n in ("n_seq", "n_heads", "Sq", "Sk")] + \
+               [f for x in "qkvo" for f in ((x.upper(), C.c_void_p), (x + "_elems", C.c_longlong), ("ld" + x, C.c_int), (x + "_seq", C.c_longlong))] + \
+               [(n, C.c_float) for n in ("q_bound", "k_bound", "v_bound")] + [("seq_len", C.c_void_p), ("slot_of_seq", C.c_void_p), ("slot_stride", C.c_longlong)] + \
+               [(n, C.c_int) for n in ("max_ctx", "n_slots", "row0")] + [("log2_out3", C.c_void_p)]
+
+
 G3_KERNEL_AUTO, G3_KERNEL_TILE, G3_KERNEL_SMALL = 0, 1, 2                                            # ETD_G3_KERNEL_*
 G3_EPI = {"bias": 0, "gelu": 1, "resid": 2, "logits": 3, "qkv": 4, "relu": 6}                        # ETD_G3_EPI_*
 
@@ -171,6 +179,9 @@ SIGNATURES = {
     "etd_debug_ln_rows_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "etd_debug_g3_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_int32)]),
     "etd_debug_attn3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
+    "etd_debug_attn3_case": (C.c_int, [C.POINTER(Attn3Case), C.c_void_p]),
+    "etd_debug_dattn_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.c_int, C.c_void_p]),
     "etd_debug_empty_launch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "etd_frontend_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                       C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.POINTER(C.c_void_p)]),

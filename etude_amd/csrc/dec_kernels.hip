@@ -2070,3 +2070,43 @@ extern "C" int etd_debug_sample_rows(const float* logits_dev, int M, int V, int 
   return ETD_OK;
 }
 
+// ================================================================================================ test hooks (include/etude_hip_debug.h)
+#include "host_util.h"
+#include "../../include/etude_hip_debug.h"
+extern "C" int etd_debug_dattn_f32(const float* q_dev, const float* kc_dev, const float* vc_dev, float* o_dev, long long qo_elems, long long kv_elems, int M, int n_heads, int n_slots,
+                                   int max_ctx, const int32_t* slot_host, const int32_t* pos_host, int form, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  auto al16 = [](const void* p) { return p && ((uintptr_t)p & 15) == 0; };
+  if (!al16(q_dev) || !al16(kc_dev) || !al16(vc_dev) || !al16(o_dev) || !slot_host || !pos_host || M < 1 || M > DS_STEP_MAX_ROWS || n_heads < 1 || n_heads > 64 || n_slots < 1 ||
+      n_slots > (1 << 16) || max_ctx < 1 || max_ctx > (1 << 20) || form < 0 || form > 2)
+    ETD_FAIL(ETD_EINVAL, "debug_dattn_f32: bad arguments");
+  const long long H = (long long)n_heads * 64;
+  if ((long long)M * H > qo_elems || (long long)n_slots * H * max_ctx > kv_elems)
+    ETD_FAIL(ETD_EINVAL, "debug_dattn_f32: q / o [M][heads * 64] or the caches [n_slots][heads][max_ctx][64] do not fit qo_elems = %lld / kv_elems = %lld", qo_elems, kv_elems);
+  for (int i = 0; i < M; ++i)
+    if (slot_host[i] < 0 || slot_host[i] >= n_slots || pos_host[i] < 0) ETD_FAIL(ETD_EINVAL, "debug_dattn_f32: row %d has slot %d (n_slots %d), pos %d", i, slot_host[i], n_slots, pos_host[i]);
+  if (form == 2) {                                                     // the promise behind `identity`: the kernel requests keys 0 .. 63 of slot i for row i before it reads the row's metadata
+    if (max_ctx < 64) ETD_FAIL(ETD_EINVAL, "debug_dattn_f32: the identity form needs max_ctx >= 64");
+    for (int i = 0; i < M; ++i) if (slot_host[i] != i) ETD_FAIL(ETD_EINVAL, "debug_dattn_f32: the identity form needs slot[i] == i (row %d has slot %d)", i, slot_host[i]);
+  }
+  DevPool pool;
+  auto done = [&](int rc) { pool.free_all(); return rc; };
+  DAttnArgs a = {};
+  a.Q = q_dev; a.Kc = kc_dev; a.Vc = vc_dev; a.slot_stride = H * max_ctx; a.max_ctx = max_ctx; a.n_heads = n_heads; a.M = M; a.O = o_dev; a.scale = 0.125f;
+  if (form == 0) {
+    std::vector<int> h((size_t)3 * M, 1);                              // [slot M][pos M][active M]
+    for (int i = 0; i < M; ++i) { h[i] = slot_host[i]; h[M + i] = pos_host[i]; }
+    int* meta = nullptr;
+    ETD_TRY_OR(done, pool.upload(&meta, h.data(), h.size()));
+    a.rows = DecRows{meta, meta + M, meta + 2 * M, nullptr};
+  } else {
+    std::vector<int> h((size_t)2 * M);
+    for (int i = 0; i < M; ++i) { h[2 * i] = slot_host[i]; h[2 * i + 1] = pos_host[i]; }
+    int* sp = nullptr;
+    ETD_TRY_OR(done, pool.upload(&sp, h.data(), h.size()));
+    a.row_sp = sp; a.identity = form == 2 ? 1 : 0;
+  }
+  int rc = launch_dattn(a, false, st);
+  if (hipStreamSynchronize(st) != hipSuccess && rc == ETD_OK) { g_etd_err = "debug_dattn_f32: kernel failed"; rc = ETD_EHIP; }
+  return done(rc);
+}

@@ -816,34 +816,82 @@ extern "C" int etd_debug_g3_pack(const float* W, int N, int K, uint16_t* planes_
   *log2_out = g3_pack_weights_host(W, N, Npad, K, planes_out);
   return ETD_OK;
 }
+extern "C" int etd_debug_attn3_case(const struct etd_debug_attn3_case* c, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!c) ETD_FAIL(ETD_EINVAL, "debug_attn3_case: null case");
+  if (c->struct_bytes != (int)sizeof(struct etd_debug_attn3_case)) ETD_FAIL(ETD_EINVAL, "debug_attn3_case: struct etd_debug_attn3_case of %d bytes, expected %d", c->struct_bytes, (int)sizeof(struct etd_debug_attn3_case));
+  const bool ragged = c->seq_len != nullptr;
+  auto al16 = [](const void* p) { return p && ((uintptr_t)p & 15) == 0; };
+  if (c->n_seq < 1 || c->n_seq > (1 << 16) || c->n_heads < 1 || c->n_heads > 64) ETD_FAIL(ETD_EINVAL, "debug_attn3_case: n_seq = %d, n_heads = %d", c->n_seq, c->n_heads);
+  if (!al16(c->Q) || !al16(c->K) || !al16(c->V) || !al16(c->O)) ETD_FAIL(ETD_EINVAL, "debug_attn3_case: Q, K, V, O must be 16-byte aligned device pointers");
+  const long long H = (long long)c->n_heads * 64;
+  auto bad_ld = [&](int ld) { return ld < H || ld % 4 || ld > (1 << 20); };
+  if (bad_ld(c->ldq) || bad_ld(c->ldo)) ETD_FAIL(ETD_EINVAL, "debug_attn3_case: ldq = %d / ldo = %d must be multiples of 4 in [n_heads * 64, 2^20]", c->ldq, c->ldo);
+  for (float b : {c->q_bound, c->k_bound, c->v_bound}) if (!(b >= 0.f) || !std::isfinite(b)) ETD_FAIL(ETD_EINVAL, "debug_attn3_case: bounds must be finite and >= 0");
+  Attn3Args a = {};
+  a.Q = c->Q; a.ldq = c->ldq; a.K = c->K; a.V = c->V; a.O = c->O; a.ldo = c->ldo; a.n_seq = c->n_seq; a.n_heads = c->n_heads; a.scale = 0.125f;
+  a.q_log2 = g3_scale_log2(c->q_bound); a.k_log2 = g3_scale_log2(c->k_bound); a.v_log2 = g3_scale_log2(c->v_bound);
+  if (c->log2_out3) { c->log2_out3[0] = a.q_log2; c->log2_out3[1] = a.k_log2; c->log2_out3[2] = a.v_log2; }
+  DevPool pool;                                                        // this call's row metadata
+  auto done = [&](int rc) { pool.free_all(); return rc; };
+  if (ragged) {
+    // queries: rows row0 .. row0 + M - 1 of Q / O; keys: positions 0 .. seq_len - 1 of the prompt's slot, every head
+    if (!c->slot_of_seq || c->max_ctx < 1 || c->max_ctx > (1 << 20) || c->n_slots < 1 || c->n_slots > (1 << 16) || c->row0 < 0 || c->row0 > (1 << 24) || c->slot_stride % 4 ||
+        c->slot_stride < H * c->max_ctx || c->slot_stride > (1LL << 40))
+      ETD_FAIL(ETD_EINVAL, "debug_attn3_case: ragged needs slot_of_seq, max_ctx, n_slots >= 1, row0 >= 0 and slot_stride %% 4 == 0, >= n_heads * max_ctx * 64");
+    const long long kv_need = (long long)(c->n_slots - 1) * c->slot_stride + H * c->max_ctx;
+    if (kv_need > c->k_elems || kv_need > c->v_elems)
+      ETD_FAIL(ETD_EINVAL, "debug_attn3_case: a cache of %d slots needs %lld floats, k_elems = %lld, v_elems = %lld", c->n_slots, kv_need, c->k_elems, c->v_elems);
+    long long M = 0; int mx = 0;
+    for (int s = 0; s < c->n_seq; ++s) {
+      if (c->seq_len[s] < 1 || c->seq_len[s] > c->max_ctx || c->slot_of_seq[s] < 0 || c->slot_of_seq[s] >= c->n_slots)
+        ETD_FAIL(ETD_EINVAL, "debug_attn3_case: prompt %d has length %d (max_ctx %d), slot %d (n_slots %d)", s, c->seq_len[s], c->max_ctx, c->slot_of_seq[s], c->n_slots);
+      M += c->seq_len[s]; mx = c->seq_len[s] > mx ? c->seq_len[s] : mx;
+    }
+    const long long rows = c->row0 + M;
+    if (rows > (1 << 24) || (rows - 1) * c->ldq + H > c->q_elems || (rows - 1) * c->ldo + H > c->o_elems)
+      ETD_FAIL(ETD_EINVAL, "debug_attn3_case: rows row0 .. row0 + %lld - 1 do not fit q_elems = %lld / o_elems = %lld", M, c->q_elems, c->o_elems);
+    std::vector<int> h((size_t)2 * c->n_seq + rows, 0);             // [seq_row0 n][seq_len n][row_slot row0 + M] (rows before row0 belong to no prompt of this call)
+    int row = c->row0;
+    for (int s = 0; s < c->n_seq; ++s) { h[s] = row; h[c->n_seq + s] = c->seq_len[s]; for (int t = 0; t < c->seq_len[s]; ++t) h[2 * c->n_seq + row++] = c->slot_of_seq[s]; }
+    int* meta = nullptr;
+    ETD_TRY_OR(done, pool.upload(&meta, h.data(), h.size()));
+    a.seq_row0 = meta; a.seq_len = meta + c->n_seq; a.row_slot = meta + 2 * c->n_seq; a.slot_stride = c->slot_stride; a.max_ctx = c->max_ctx; a.max_len = mx;
+  } else {
+    if (c->Sq < 1 || c->Sk < 1 || c->Sq > (1 << 20) || c->Sk > (1 << 20) || bad_ld(c->ldk) || bad_ld(c->ldv))
+      ETD_FAIL(ETD_EINVAL, "debug_attn3_case: strided needs Sq, Sk in [1, 2^20] and ldk = %d / ldv = %d multiples of 4 in [n_heads * 64, 2^20]", c->ldk, c->ldv);
+    // sequence s, row t, H floats: the last element read or written is (n_seq - 1) x_seq + (S - 1) ldx + H - 1
+    auto fits = [&](long long seq, int ld, int S, long long elems) { return seq >= 0 && seq % 4 == 0 && seq <= (1LL << 40) && (c->n_seq - 1) * seq + (long long)(S - 1) * ld + H <= elems; };
+    if (!fits(c->q_seq, c->ldq, c->Sq, c->q_elems) || !fits(c->k_seq, c->ldk, c->Sk, c->k_elems) || !fits(c->v_seq, c->ldv, c->Sk, c->v_elems) || !fits(c->o_seq, c->ldo, c->Sq, c->o_elems))
+      ETD_FAIL(ETD_EINVAL, "debug_attn3_case: n_seq sequences of Sq / Sk rows at these strides do not fit q / k / v / o_elems = %lld / %lld / %lld / %lld (or a *_seq stride is negative or no multiple of 4)",
+               c->q_elems, c->k_elems, c->v_elems, c->o_elems);
+    if (c->n_seq > 1 && c->o_seq < (long long)(c->Sq - 1) * c->ldo + H) ETD_FAIL(ETD_EINVAL, "debug_attn3_case: sequences of O overlap (o_seq = %lld)", c->o_seq);
+    a.ldk = c->ldk; a.ldv = c->ldv; a.q_seq = c->q_seq; a.k_seq = c->k_seq; a.v_seq = c->v_seq; a.o_seq = c->o_seq; a.Sq = c->Sq; a.Sk = c->Sk;
+  }
+  int rc = launch_attn3(a, st);
+  if (hipStreamSynchronize(st) != hipSuccess && rc == ETD_OK) { g_etd_err = "debug_attn3_case: kernel failed"; rc = ETD_EHIP; }
+  return done(rc);
+}
 extern "C" int etd_debug_attn3(const float* q_dev, const float* k_dev, const float* v_dev, float* o_dev, int n_seq, int n_heads, int Sq, int Sk, float q_bound, float k_bound, float v_bound,
                                int causal, const int32_t* lens_host, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
   if (!q_dev || !k_dev || !v_dev || !o_dev || n_seq < 1 || n_heads < 1 || Sq < 1 || Sk < 1) ETD_FAIL(ETD_EINVAL, "debug_attn3: bad arguments");
   const int H = n_heads * 64;
-  Attn3Args a = {};
-  a.Q = q_dev; a.ldq = H; a.K = k_dev; a.V = v_dev; a.O = o_dev; a.ldo = H; a.n_seq = n_seq; a.n_heads = n_heads; a.scale = 0.125f;
-  a.q_log2 = g3_scale_log2(q_bound); a.k_log2 = g3_scale_log2(k_bound); a.v_log2 = g3_scale_log2(v_bound);
-  int* meta = nullptr;
-  int rc = ETD_OK;
-  if (causal) {
+  struct etd_debug_attn3_case c = {};
+  c.struct_bytes = (int)sizeof(c); c.n_seq = n_seq; c.n_heads = n_heads; c.Sq = Sq; c.Sk = Sk;
+  c.Q = q_dev; c.ldq = H; c.K = k_dev; c.ldk = H; c.V = v_dev; c.ldv = H; c.O = o_dev; c.ldo = H; c.q_bound = q_bound; c.k_bound = k_bound; c.v_bound = v_bound;
+  c.k_elems = c.v_elems = (long long)n_seq * Sk * H;
+  std::vector<int32_t> slots;
+  if (causal) {                                                        // contiguous prompts, prompt s in slot s of a cache [n_seq][heads][Sk][64]
     if (!lens_host || Sq != Sk) ETD_FAIL(ETD_EINVAL, "debug_attn3: causal needs lens_host and Sq == Sk");
-    std::vector<int> h;                              // [seq_row0 n][seq_len n][row_slot M]
-    int M = 0, mx = 0;
-    for (int s = 0; s < n_seq; ++s) { if (lens_host[s] < 1 || lens_host[s] > Sq) ETD_FAIL(ETD_EINVAL, "debug_attn3: bad prompt length"); M += lens_host[s]; mx = lens_host[s] > mx ? lens_host[s] : mx; }
-    h.resize((size_t)2 * n_seq + M);
-    int row = 0;
-    for (int s = 0; s < n_seq; ++s) { h[s] = row; h[n_seq + s] = lens_host[s]; for (int t = 0; t < lens_host[s]; ++t) h[2 * n_seq + row++] = s; }
-    HIP_TRY(hipMalloc((void**)&meta, h.size() * 4));
-    if (hipMemcpy(meta, h.data(), h.size() * 4, hipMemcpyHostToDevice) != hipSuccess) rc = ETD_EHIP;
-    a.seq_row0 = meta; a.seq_len = meta + n_seq; a.row_slot = meta + 2 * n_seq; a.slot_stride = (long long)n_heads * Sk * 64; a.max_ctx = Sk; a.max_len = mx;
+    long long M = 0;
+    for (int s = 0; s < n_seq; ++s) { if (lens_host[s] < 1 || lens_host[s] > Sq) ETD_FAIL(ETD_EINVAL, "debug_attn3: bad prompt length"); M += lens_host[s]; slots.push_back(s); }
+    c.q_elems = c.o_elems = M * H;
+    c.seq_len = lens_host; c.slot_of_seq = slots.data(); c.slot_stride = (long long)n_heads * Sk * 64; c.max_ctx = Sk; c.n_slots = n_seq;
   } else {
-    a.ldk = H; a.ldv = H; a.q_seq = (long long)Sq * H; a.k_seq = (long long)Sk * H; a.v_seq = (long long)Sk * H; a.o_seq = (long long)Sq * H; a.Sq = Sq; a.Sk = Sk;
+    c.q_elems = c.o_elems = (long long)n_seq * Sq * H;
+    c.q_seq = c.o_seq = (long long)Sq * H; c.k_seq = c.v_seq = (long long)Sk * H;
   }
-  if (rc == ETD_OK) rc = launch_attn3(a, st);
-  if (hipStreamSynchronize(st) != hipSuccess && rc == ETD_OK) { g_etd_err = "debug_attn3: kernel failed"; rc = ETD_EHIP; }
-  if (meta) (void)hipFree(meta);
-  return rc;
+  return etd_debug_attn3_case(&c, stream);
 }
 
 // host-only test hook: the load-time bounds the plane scales come from (tests/test_host_logic.py checks that they bound)

@@ -139,6 +139,32 @@ int etd_debug_g3_pack(const float* W, int N, int K, uint16_t* planes_out, long l
  * through the RAGGED path (K / V then laid out as a KV cache [n_seq slots][heads][Sk][64], lens_host[n_seq] prompt lengths <= Sq == Sk, q / o rows packed prompt after prompt) */
 int etd_debug_attn3(const float* q_dev, const float* k_dev, const float* v_dev, float* o_dev, int n_seq, int n_heads, int Sq, int Sk, float q_bound, float k_bound, float v_bound,
                     int causal, const int32_t* lens_host, void* stream);
+/* test hook (tests/test_gpu_attn3.py): ONE launch_attn3 call with every Attn3Args field the engines set -- row strides, sequence strides, buffers that interleave
+ * Q | K | V, and for the ragged causal form the decoder's slots, slot stride and max_ctx.  seq_len == NULL is the strided form (every sequence Sq queries against Sk
+ * keys, sequence s at X + s * x_seq); otherwise sequence s is a prompt of seq_len[s] rows: its Q / O rows are the global rows row0 + (lengths before it) + t of Q / O
+ * (row stride ldq / ldo), its K / V rows positions 0 .. seq_len[s] - 1 of slot slot_of_seq[s] of a cache [n_slots][slot_stride], head h at h * max_ctx * 64 inside
+ * the slot; Sq, Sk and the *_seq strides are not read.  The plane scales are g3_scale_log2 of the three bounds and are returned in log2_out3 (host, may be NULL).
+ * Everything is validated on the host first: every element the kernel can read or write must lie inside the *_elems floats the caller states for that pointer, every
+ * slot inside n_slots; a case that does not hold is ETD_EINVAL before anything is launched.  Synchronous. */
+struct etd_debug_attn3_case {                  /* (the hook's own name: refer to it as `struct etd_debug_attn3_case`) */
+  int struct_bytes;                            /* sizeof(struct etd_debug_attn3_case) of the caller */
+  int n_seq, n_heads, Sq, Sk;
+  const float* Q; long long q_elems; int ldq; long long q_seq;      /* device; ld* >= n_heads * 64, multiples of 4 like the *_seq strides */
+  const float* K; long long k_elems; int ldk; long long k_seq;
+  const float* V; long long v_elems; int ldv; long long v_seq;
+  float* O; long long o_elems; int ldo; long long o_seq;            /* sequences of O must not overlap */
+  float q_bound, k_bound, v_bound;             /* bounds of |q|, |k|, |v| for the plane scales */
+  const int32_t* seq_len; const int32_t* slot_of_seq;               /* ragged causal: host [n_seq], 1 <= seq_len <= max_ctx, 0 <= slot_of_seq < n_slots */
+  long long slot_stride; int max_ctx, n_slots, row0;                /* slot_stride >= n_heads * max_ctx * 64, a multiple of 4; row0 >= 0: global row of the first prompt's first query */
+  int32_t* log2_out3;                          /* host [3] or NULL: q_log2, k_log2, v_log2 as used */
+};
+int etd_debug_attn3_case(const struct etd_debug_attn3_case* c, void* stream);
+/* test hook (tests/test_gpu_attn3.py): ONE launch_dattn call of the fp32 decode-step attention (k_dattn<float>): row i's query q_dev [M][n_heads * 64] against positions
+ * 0 .. min(pos_host[i], max_ctx - 1) of slot slot_host[i] of the fp32 caches kc_dev / vc_dev [n_slots][n_heads][max_ctx][64] (kv_elems floats each) -> o_dev
+ * [M][n_heads * 64] (q_dev, o_dev: qo_elems floats each).  form 0: DecRows slot / pos arrays; 1: (slot, pos) pairs in row_sp; 2: row_sp with the `identity` promise
+ * (row i is slot i), refused unless slot_host[i] == i and max_ctx >= 64, as launch_dattn's own rule implies.  Validated on the host first; synchronous. */
+int etd_debug_dattn_f32(const float* q_dev, const float* kc_dev, const float* vc_dev, float* o_dev, long long qo_elems, long long kv_elems, int M, int n_heads, int n_slots,
+                        int max_ctx, const int32_t* slot_host, const int32_t* pos_host, int form, void* stream);
 
 /* host-only test hook: the load-time bounds behind the plane scales of csrc/gemm3.h -- out4 = { bound of LayerNorm(.; g, b) over K features, bound of W LN(.) + c,
  * bound of W x + c for |x| <= elem_bound, largest |value| in the packed f16 planes of W }, log2_out4 = the scale logarithms chosen for the three bounds and for W */
