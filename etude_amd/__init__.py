@@ -16,6 +16,7 @@ Drop-in surfaces (same names/signatures as the reference):
     etude_amd.WPDCalculator         <- etude.evaluation.metrics.wpd.WPDCalculator (host arithmetic on the warping path)
     etude_amd.RGCCalculator / IPECalculator / RhythmMetrics  <- etude.evaluation.metrics.rgc / ipe (a ragged batch of note lists; csrc/rhythm.hip)
     etude_amd.EtudeDataset / BarAttributes / attribute_adherence  <- etude.data.dataset.EtudeDataset (bar attributes, bin edges, training samples; csrc/attributes.hip)
+    etude_amd.NoteRenderer / PianoVoice / align_notes_many  (no counterpart: the reference leaves rendering a cover's .mid to an external synthesiser; csrc/render.hip)
     etude_amd.BeatAnalyzer          <- etude.data.beat_analyzer.BeatAnalyzer (beat_pred.json -> tempo.json; host Python)
 All arithmetic runs in libetude_hip.so (hand-written HIP, see csrc/); importing the heavy
 modules is lazy so that `import etude_amd` works on a box without a GPU.
@@ -35,7 +36,8 @@ __all__ = ["AMTAPC_Extractor", "EtudeDecoder", "EtudeDecoderConfig", "load_etude
            "WPDCalculator", "wpd_many", "AlignFeatures", "ellip_bandpass_sos", "pitch_filterbank", "align_audio_many", "align_and_filter_audio_many",
            "TuningEstimator", "estimate_tuning", "RhythmMetrics", "RGCCalculator", "IPECalculator", "get_onsets_from_file", "rhythm_metrics_for_notes",
            "evaluate_many", "BarAttributes", "EtudeDataset", "split_into_bars", "calculate_bin_edges", "save_bin_edges", "load_bin_edges", "attribute_adherence",
-           "DecoderTrainer", "cosine_schedule_with_warmup", "init_decoder_state"]
+           "DecoderTrainer", "cosine_schedule_with_warmup", "init_decoder_state", "NoteRenderer", "PianoVoice", "default_note_renderer", "align_notes_many",
+           "read_midi_notes", "save_wav"]
 
 
 def __getattr__(name):
@@ -69,15 +71,21 @@ def __getattr__(name):
     if name in ("TuningEstimator", "estimate_tuning"):
         from . import tuning
         return getattr(tuning, name)
-    if name in ("RhythmMetrics", "RGCCalculator", "IPECalculator", "get_onsets_from_file", "rhythm_metrics_for_notes", "evaluate_many"):
+    if name in ("RhythmMetrics", "RGCCalculator", "IPECalculator", "get_onsets_from_file", "rhythm_metrics_for_notes", "evaluate_many", "read_midi_notes"):
         from . import rhythm
         return getattr(rhythm, name)
     if name in ("BarAttributes", "EtudeDataset", "split_into_bars", "calculate_bin_edges", "save_bin_edges", "load_bin_edges", "attribute_adherence"):
         from . import attributes
         return getattr(attributes, name)
-    if name in ("AudioAligner", "align_features", "align_features_many", "align_and_filter_many", "align_audio_many", "align_and_filter_audio_many"):
+    if name in ("AudioAligner", "align_features", "align_features_many", "align_and_filter_many", "align_audio_many", "align_and_filter_audio_many", "align_notes_many"):
         from . import aligner
         return getattr(aligner, name)
+    if name in ("NoteRenderer", "PianoVoice", "default_note_renderer"):
+        from . import render
+        return getattr(render, name)
+    if name == "save_wav":
+        from .extractor import save_wav
+        return save_wav
     if name in ("WPDCalculator", "wpd_many"):
         from . import evaluation
         return getattr(evaluation, name)

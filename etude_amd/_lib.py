@@ -92,6 +92,12 @@ class RhythmCfg(_SizedCfg):
                 + [("min_ioi", C.c_double), ("max_ioi", C.c_double), ("random_host", C.POINTER(C.c_double))])
 
 
+class RenderCfg(_SizedCfg):
+    _fields_ = ([("struct_bytes", C.c_int)] + [(n, C.c_int) for n in ("sample_rate", "partials", "flags")]
+                + [(n, C.c_double) for n in ("inharmonicity", "inharmonicity_step", "partial_rolloff", "velocity_power", "attack", "decay_base", "decay_halving",
+                                             "decay_partial", "release_tau", "release_len", "gain", "nyquist_fraction")])
+
+
 class AttrCfg(_SizedCfg):
     _fields_ = [("struct_bytes", C.c_int), ("type_pos", C.c_int), ("type_note", C.c_int), ("type_duration", C.c_int)]
 
@@ -315,6 +321,13 @@ SIGNATURES = {
     "etd_attr_check": (C.c_int, [C.c_void_p, c_i64_p, C.c_int]),
     "etd_attr_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_i64_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, c_i64_p, C.c_int, C.c_void_p, C.c_int,
                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "etd_render_limits": (C.c_int, [c_int_p, C.POINTER(C.c_longlong), c_int_p, c_int_p, c_int_p]),
+    "etd_render_create": (C.c_int, [C.POINTER(RenderCfg), C.POINTER(C.c_void_p)]),
+    "etd_render_destroy": (None, [C.c_void_p]),
+    "etd_render_bytes": (C.c_longlong, [C.c_void_p, C.c_int, c_i64_p, c_i64_p]),
+    "etd_render_run": (C.c_int, [C.c_void_p, C.c_void_p, c_i64_p, C.c_void_p, C.c_int, c_i64_p, c_i64_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "etd_render_peaks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "etd_render_debug_plan": (C.c_int, [C.c_void_p, C.c_void_p, c_i64_p, C.c_int, c_i64_p, C.c_void_p, C.c_void_p]),
     "etd_dtrain_workspace_bytes": (C.c_longlong, [C.POINTER(DecCfg), C.c_int]),
     "etd_dtrain_create": (C.c_int, [C.POINTER(DecCfg), C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), c_i64_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.POINTER(C.c_void_p)]),

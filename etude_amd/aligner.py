@@ -219,6 +219,46 @@ def align_audio_many(pairs_of_wavs: Sequence[Tuple], tuning_offsets: Union[None,
     return align_features_many([(feats[2 * i], feats[2 * i + 1]) for i in range(len(pairs_of_wavs))], device)
 
 
+def align_notes_many(pairs: Sequence[Tuple], tuning_offsets: Optional[Sequence[Tuple[float, float]]] = None, device="cuda", renderer=None, features=None) -> List[Dict]:
+    """From notes: pairs of (cover notes, origin) -> the result dicts of ``align_features_many``.  Cover notes: whatever ``NoteRenderer.render_many`` takes (a
+    NOTE_DTYPE array, a list of note dicts, a ``.json`` / ``.mid`` path); origin: mono samples at 22 050 Hz, or its features (quantised chroma, DLNCO) computed
+    before.  The covers are rendered on the device (csrc/render.hip) sub-batch after sub-batch under the renderer's budget, each sub-batch's samples go
+    straight into ``AlignFeatures.features_many`` (with the origins given as samples in the first one: ONE call when the covers fit one sub-batch) and are dropped,
+    then one ragged DTW call.  tuning_offsets: per pair (cover cents, origin cents), default 0: the cover is rendered AND analysed at its offset; the origin's
+    applies when it is given as samples."""
+    n = len(pairs)
+    if n == 0:
+        return []
+    if tuning_offsets is not None and len(tuning_offsets) != n:
+        raise ValueError(f"align_notes_many: {n} pairs but {len(tuning_offsets)} tuning offset pairs")
+    from .alignfeat import FS, default_align_features
+    from .render import default_note_renderer
+    renderer = renderer or default_note_renderer(device)
+    features = features or default_align_features(device)
+    if renderer.sample_rate != FS:
+        raise ValueError(f"align_notes_many: the renderer runs at {renderer.sample_rate} Hz, the alignment features need {FS}")
+    for i, pr in enumerate(pairs):
+        if len(pr) != 2:
+            raise ValueError(f"pair {i}: need (cover notes, origin)")
+    tun = [(0.0, 0.0)] * n if tuning_offsets is None else [(float(a), float(b)) for a, b in tuning_offsets]
+    packed = renderer.pack([c for c, _ in pairs], [t[0] for t in tun])
+    for i, N in enumerate(packed.num_samples):
+        if N < 1:
+            raise ValueError(f"pair {i}: the cover has no notes")
+    as_audio = [i for i, (_, o) in enumerate(pairs) if not (isinstance(o, (tuple, list)) and len(o) == 2)]
+    origin_feats: Dict[int, Feats] = {i: tuple(o) for i, (_, o) in enumerate(pairs) if i not in set(as_audio)}
+    cover_feats: Dict[int, Feats] = {}
+    first = True
+    for idx, samples in renderer.iter_rendered(packed):
+        extra = as_audio if first else []
+        feats = features.features_many(list(samples) + [pairs[i][1] for i in extra], [tun[i][0] for i in idx] + [tun[i][1] for i in extra])
+        cover_feats.update(zip(idx, feats[:len(idx)]))
+        origin_feats.update(zip(extra, feats[len(idx):]))
+        first = False
+        del samples
+    return align_features_many([(cover_feats[i], origin_feats[i]) for i in range(n)], device)
+
+
 class AudioAligner:
     """etude.data.aligner.AudioAligner: same attributes, same cache-first ``align`` and the same rich ``wp.json`` format.  ``feature_fn(path) -> (quantized chroma,
     DLNCO)`` supplies what the reference's ``_get_features`` computes; without it a cache miss is a logged None."""

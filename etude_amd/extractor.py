@@ -79,6 +79,26 @@ def read_wav(path: Union[str, Path]):
     raise ValueError(f"{path}: no data chunk")
 
 
+def save_wav(path: Union[str, Path], samples, sample_rate: int, peak: Optional[float] = None) -> float:
+    """mono samples (1-d array or tensor, host or device) -> 16-bit PCM WAV through the stdlib ``wave`` module: what ``read_wav`` reads back within half a 16-bit
+    step.  A sample s is stored as round(32768 s), at most 32767.  The samples are scaled only when their peak (``peak``, e.g. ``NoteRenderer.peaks_many``'s; None =
+    max |s| computed here) exceeds 1: then by 32767 / (32768 peak), so that the loudest sample is full scale.  -> the factor applied."""
+    if hasattr(samples, "detach"):
+        samples = samples.detach().cpu().numpy()
+    x = np.asarray(samples, np.float64)
+    if x.ndim != 1:
+        raise ValueError(f"save_wav: need mono samples [N], got shape {x.shape}")
+    if not np.isfinite(x).all():
+        raise ValueError("save_wav: the samples hold a non-finite value")
+    pk = float(np.max(np.abs(x))) if peak is None and x.size else float(peak or 0.0)
+    scale = 32767.0 / (32768.0 * pk) if pk > 1.0 else 1.0
+    q = np.clip(np.rint(x * (scale * 32768.0)), -32768, 32767).astype("<i2")
+    with _wave.open(str(path), "wb") as w:
+        w.setnchannels(1); w.setsampwidth(2); w.setframerate(int(sample_rate))
+        w.writeframes(q.tobytes())
+    return scale
+
+
 def write_wav_f32(path: Union[str, Path], wav: np.ndarray, sr: int) -> None:
     """float32 [C, L] -> IEEE-float WAV (test/bench helper)."""
     wav = np.asarray(wav, np.float32)

@@ -241,6 +241,73 @@ def read_midi_onsets(path) -> np.ndarray:
     return np.asarray(secs)[seg] + (ons - np.asarray(ticks)[seg]) * np.asarray(scales)[seg] if ons.size else np.zeros(0)
 
 
+def read_midi_notes(path) -> np.ndarray:
+    """The notes of a standard MIDI file as a NOTE_DTYPE array (onset, offset in seconds, pitch, velocity), for ``etude_amd.render``: every note-on with velocity > 0
+    outside channel 10 (the drums) paired with the next note-off -- or note-on with velocity 0 -- of its channel and key (overlapping notes of one key end first in,
+    first out; a note the file never ends stops at the file's last event), in the order of their onsets, ties in file order.  The parser, the supported files and the
+    tempo map are ``read_midi_onsets``'s."""
+    d = Path(path).read_bytes()
+    if d[:4] != b"MThd" or int.from_bytes(d[4:8], "big") < 6:
+        raise ValueError(f"{path}: not a standard MIDI file")
+    fmt, ntrk, div = (int.from_bytes(d[8 + 2 * i:10 + 2 * i], "big") for i in range(3))
+    if fmt > 1 or div & 0x8000 or div == 0:
+        raise ValueError(f"{path}: format {fmt} / division {div:#x} is not supported (formats 0 and 1, ticks per beat)")
+    p = 8 + int.from_bytes(d[4:8], "big")
+    tempi, notes, last_tick = [], [], 0
+    for _ in range(ntrk):
+        if d[p:p + 4] != b"MTrk":
+            raise ValueError(f"{path}: track header expected at byte {p}")
+        end = p + 8 + int.from_bytes(d[p + 4:p + 8], "big")
+        p += 8
+        tick, running = 0, 0
+        sounding: Dict[Tuple[int, int], List[int]] = {}      # (channel, key) -> indices into notes, oldest first
+        while p < end:
+            dt, p = _varlen(d, p)
+            tick += dt
+            b = d[p]
+            if b == 0xFF:
+                kind = d[p + 1]
+                ln, p = _varlen(d, p + 2)
+                if kind == 0x51 and ln == 3:
+                    tempi.append((tick, int.from_bytes(d[p:p + 3], "big")))
+                p += ln
+            elif b in (0xF0, 0xF7):
+                ln, p = _varlen(d, p + 1)
+                p += ln
+            else:
+                if b & 0x80:
+                    running, p = b, p + 1
+                kind, ch = running & 0xF0, running & 0x0F
+                n_data = 1 if kind in (0xC0, 0xD0) else 2
+                if ch != 9 and kind == 0x90 and d[p + 1] > 0:
+                    sounding.setdefault((ch, d[p]), []).append(len(notes))
+                    notes.append([tick, -1, d[p], d[p + 1]])
+                elif ch != 9 and kind in (0x80, 0x90) and sounding.get((ch, d[p])):
+                    notes[sounding[(ch, d[p])].pop(0)][1] = tick
+                p += n_data
+        last_tick = max(last_tick, tick)
+        p = end
+    tempi.sort(key=lambda x: x[0])
+    ticks, secs, scales = [0], [0.0], [500000 * 1e-6 / div]
+    for tk, us in tempi:
+        if tk == ticks[-1]:
+            scales[-1] = us * 1e-6 / div
+        else:
+            secs.append(secs[-1] + (tk - ticks[-1]) * scales[-1]); ticks.append(tk); scales.append(us * 1e-6 / div)
+    from .render import NOTE_DTYPE
+    out = np.zeros(len(notes), NOTE_DTYPE)
+    if notes:
+        a = np.asarray(notes, np.int64)
+        a[:, 1] = np.where(a[:, 1] < 0, last_tick, a[:, 1])
+
+        def seconds(t):
+            seg = np.searchsorted(np.asarray(ticks), t, side="right") - 1
+            return np.asarray(secs)[seg] + (t - np.asarray(ticks)[seg]) * np.asarray(scales)[seg]
+        out["onset"], out["offset"], out["pitch"], out["velocity"] = seconds(a[:, 0]), seconds(a[:, 1]), a[:, 2], a[:, 3]
+        out = out[np.argsort(a[:, 0], kind="stable")]
+    return out
+
+
 def get_onsets_from_file(file_path) -> np.ndarray:
     """``get_onsets_from_file`` of the reference (etude/evaluation/metrics/base_metric.py): the sorted, unique note onsets of a ``.mid`` or ``.json`` file; an empty
     array for a missing or unreadable file and below two notes."""
@@ -293,11 +360,48 @@ class IPECalculator:
         return self.calculate_many([file_path])[0]
 
 
+def _align_rendered(eval_dir: Path, keys: Sequence[Tuple[str, str]], results: List[Optional[Dict]], renderer, device) -> List[Optional[Dict]]:
+    """``evaluate_many(renderer=...)``: the alignment results with those of the covers that exist as notes only filled in.  Every origin's features are computed
+    once, whatever the number of its versions."""
+    from .aligner import align_notes_many
+    from .alignfeat import FS, default_align_features
+    from .extractor import read_wav
+    if renderer.sample_rate != FS:
+        raise ValueError(f"evaluate_many: the renderer runs at {renderer.sample_rate} Hz, the alignment features need {FS}")
+    todo = []
+    for i, (d, v) in enumerate(keys):
+        if results[i] is not None or (eval_dir / d / f"{v}.wav").exists() or not (eval_dir / d / "origin.wav").exists():
+            continue
+        mid, js = eval_dir / d / f"{v}.mid", eval_dir / d / f"{v}.json"
+        if mid.exists() or js.exists():
+            todo.append((i, d, mid if mid.exists() else js))
+    if not todo:
+        return results
+    songs = sorted({d for _, d, _ in todo})
+    wavs = []
+    for d in songs:
+        x, sr = read_wav(eval_dir / d / "origin.wav")
+        if sr != FS or x.shape[0] != 1:
+            raise ValueError(f"{eval_dir / d / 'origin.wav'}: {x.shape[0]} channel(s) at {sr} Hz; a rendered cover is aligned to a mono origin at {FS} Hz "
+                             f"(resample it first: FrontEnd(sr_in, {FS}).resample)")
+        wavs.append(x[0])
+    features = default_align_features(device)
+    origin = dict(zip(songs, features.features_many(wavs)))
+    out = list(results)
+    for (i, _, _), res in zip(todo, align_notes_many([(f, origin[d]) for _, d, f in todo], device=device, renderer=renderer, features=features)):
+        out[i] = res
+    return out
+
+
 def evaluate_many(eval_dir, metadata: Sequence[Dict], versions: Sequence[str], metrics: Sequence[str] = ("wpd", "rgc", "ipe"), aligner=None, device="cuda",
-                  wpd_subsample_step: int = 1, wpd_trim_seconds: float = 0, **rhythm_params) -> List[Dict]:
+                  wpd_subsample_step: int = 1, wpd_trim_seconds: float = 0, renderer=None, **rhythm_params) -> List[Dict]:
     """``EvaluationRunner.run`` of the reference (etude/evaluation/runner.py) -> its rows as dicts: ``song``, ``version``, then ``wpd_score``, ``rgc_score``,
     ``inferred_tau``, ``ipe_score`` where the metric succeeded; a row with no metric is dropped.  metadata: the loaded metadata list (``dir_name`` per song).  WPD
-    goes through ``AudioAligner.align`` and ``wpd_many`` as they stand; RGC and IPE of every (song, version) come from ONE device call."""
+    goes through ``AudioAligner.align`` and ``wpd_many`` as they stand; RGC and IPE of every (song, version) come from ONE device call.
+
+    renderer: a ``NoteRenderer`` (22 050 Hz).  With one, a (song, version) that ``align`` has no result for, whose ``{version}.wav`` is missing but whose ``.mid`` or
+    ``.json`` exists next to an ``origin.wav``, gets its WPD from the cover rendered on the device (``aligner.align_notes_many``; nothing is written to ``wp.json``).
+    ``origin.wav`` must already be mono at 22 050 Hz: resampling stays the caller's (``FrontEnd(sr_in, 22050).resample``)."""
     eval_dir = Path(eval_dir)
     keys = [(s["dir_name"], v) for s in metadata if s.get("dir_name") for v in versions]
     rows = [{"song": d, "version": v} for d, v in keys]
@@ -306,6 +410,8 @@ def evaluate_many(eval_dir, metadata: Sequence[Dict], versions: Sequence[str], m
         from .evaluation import wpd_many
         aligner = aligner or AudioAligner(device=device)
         results = [aligner.align(eval_dir / d / "origin.wav", eval_dir / d / f"{v}.wav", eval_dir / d) for d, v in keys]
+        if renderer is not None:
+            results = _align_rendered(eval_dir, keys, results, renderer, device)
         for row, res in zip(rows, wpd_many(results, wpd_subsample_step, wpd_trim_seconds)):
             if "error" not in res:
                 row.update(res)

@@ -643,6 +643,50 @@ int etd_dtrain_read_grad(etd_dtrain*, const char* name, float* out_host, long lo
 int etd_dtrain_read_moment(etd_dtrain*, const char* name, int second, float* out_host, long long numel, void* stream);
 int etd_dtrain_write_moment(etd_dtrain*, const char* name, int second, const float* in_host, long long numel, void* stream);
 
+/* ------------------------------------------------------------------ note renderer (note lists -> mono fp32 waveforms of this project's own piano voice, the audio
+ * the alignment features of a generated cover are computed from).  The voice is a contract of this project (restated in fp64 in tests/render_np.py):
+ * parity with pretty_midi.synthesize or a SoundFont player is not claimed.  No atomics anywhere: a cover's samples depend on its notes, tuning and rate alone. */
+typedef struct etd_render etd_render;
+typedef struct {
+  int struct_bytes;          /* sizeof(etd_render_cfg) of the caller: a mismatch is ETD_EINVAL */
+  int sample_rate;           /* 22050; 8000 .. 48000 */
+  int partials;              /* 8: partials k = 1 .. K of a note, 1 .. 16 */
+  int flags;                 /* 3: bit 0 = the decay exp(-tau / T_k), bit 1 = the release (off: a note ends at its offset) */
+  double inharmonicity;      /* 3.5e-4: B at pitch 60; f_k = k f0 sqrt(1 + B k^2) */
+  double inharmonicity_step; /* 10: B doubles every so many semitones */
+  double partial_rolloff;    /* 1.5: A_k = (velocity / 127)^velocity_power k^-partial_rolloff */
+  double velocity_power;     /* 2 */
+  double attack;             /* 0.004 s: min(tau / attack, 1) */
+  double decay_base;         /* 3.0 s: T at pitch 21 */
+  double decay_halving;      /* 24: T halves every so many semitones */
+  double decay_partial;      /* 0.25: T_k = T / (1 + decay_partial (k - 1)) */
+  double release_tau;        /* 0.06 s: behind the offset, exp(-u / release_tau) (1 - u / release_len) */
+  double release_len;        /* 0.48 s: a note is exactly 0 from offset + release_len on */
+  double gain;               /* 0.1 */
+  double nyquist_fraction;   /* 0.45: a partial at or above this fraction of the sample rate does not exist */
+} etd_render_cfg;
+/* HOST ONLY: the constants of this build: notes per cover (65 536), samples per cover (etd_alignfeat_limits' max_samples), partials (16), covers per call (4 096),
+ * samples a workgroup owns (1 024); any may be NULL */
+int etd_render_limits(int* max_notes, long long* max_samples, int* max_partials, int* max_covers, int* block);
+/* Needs no GPU.  A value outside the ranges above is ETD_EINVAL. */
+int etd_render_create(const etd_render_cfg* cfg, etd_render** out);
+void etd_render_destroy(etd_render*);
+/* HOST ONLY: bytes of device workspace a call with these covers needs (32 per cover, 8 per 1 024 samples, 472 per note, each part rounded up to 256); negative =
+ * ETD_EINVAL: n_covers outside 1 .. 4 096, a cover above the note or sample limit, decreasing offsets */
+long long etd_render_bytes(const etd_render*, int n_covers, const int64_t* note_offsets_host, const int64_t* num_samples_host);
+/* A ragged batch: cover b is notes_host[note_offsets_host[b] .. note_offsets_host[b + 1]) (HOST; sorted by onset, ties in the caller's order; 0 <= onset < offset,
+ * pitch 21 .. 108, velocity 1 .. 127), tuned by cents_host[b] (|c| <= 50; NULL = 0), and becomes the num_samples_host[b] fp32 samples at
+ * out_dev + sample_offsets_host[b] (DEVICE; offsets ascending, multiples of 4, covers not overlapping).  Every sample of every cover is written exactly once, zeros
+ * included; what lies between two covers is not touched.  Anything else is refused with ETD_EINVAL and a message naming the cover and the note before the device is
+ * touched.  Two launches (three above 2^23 blocks) and one upload; synchronises `stream` once (the upload).  A cover's samples are bit-identical alone, in any batch,
+ * in any order and from run to run. */
+int etd_render_run(etd_render*, const etd_note* notes_host, const int64_t* note_offsets_host, const double* cents_host, int n_covers, const int64_t* num_samples_host,
+                   const int64_t* sample_offsets_host, float* out_dev, void* workspace_dev, long long workspace_bytes, void* stream);
+/* peaks_dev[b] = max |x| over the num_samples_dev[b] samples at samples_dev + sample_offsets_dev[b] (both DEVICE int64 [n_covers]; 0 for an empty cover).  ONE launch,
+ * one workgroup per cover.  Asynchronous on `stream`. */
+int etd_render_peaks(etd_render*, const float* samples_dev, const int64_t* sample_offsets_dev, const int64_t* num_samples_dev, int n_covers, float* peaks_dev,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

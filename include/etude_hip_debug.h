@@ -242,6 +242,12 @@ int etd_debug_dtrain_gemm(int form, int M, int N, int K, const float* A_dev, int
 int etd_debug_dtrain_attn(int n_seq, const int32_t* T_host, int n_heads, const float* qkv_dev, const float* dO_dev, float* O_dev, float* lse_dev, float* dqkv_dev,
                           void* stream);
 
+/* test hook, HOST ONLY: the plan etd_render_run makes of a call, without a device: first_end_host int64 [notes][2] = per note the first sample it sounds on and the
+ * first it no longer does; ranges_host int32 [blocks][2] = per block of 1 024 samples (cover after cover) the candidate notes [lo, hi) of its cover.  Either may be
+ * NULL.  Refuses what etd_render_run refuses about the notes. */
+int etd_render_debug_plan(etd_render*, const etd_note* notes_host, const int64_t* note_offsets_host, int n_covers, const int64_t* num_samples_host,
+                          int64_t* first_end_host, int32_t* ranges_host);
+
 #ifdef __cplusplus
 }
 #endif
