@@ -98,6 +98,11 @@ class RenderCfg(_SizedCfg):
                                              "decay_partial", "release_tau", "release_len", "gain", "nyquist_fraction")])
 
 
+class SepCfg(_SizedCfg):
+    _fields_ = ([("struct_bytes", C.c_int)] + [(n, C.c_int) for n in ("n_instr", "n_channels", "n_fft", "hop", "T", "F")] + [("filters", C.c_int * 6)]
+                + [("separation_exponent", C.c_int), ("mask_eps", C.c_float), ("bn_eps", C.c_float), ("workspace_bytes", C.c_longlong)])
+
+
 class AttrCfg(_SizedCfg):
     _fields_ = [("struct_bytes", C.c_int), ("type_pos", C.c_int), ("type_note", C.c_int), ("type_duration", C.c_int)]
 
@@ -328,6 +333,17 @@ SIGNATURES = {
     "etd_render_run": (C.c_int, [C.c_void_p, C.c_void_p, c_i64_p, C.c_void_p, C.c_int, c_i64_p, c_i64_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
     "etd_render_peaks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "etd_render_debug_plan": (C.c_int, [C.c_void_p, C.c_void_p, c_i64_p, C.c_int, c_i64_p, C.c_void_p, C.c_void_p]),
+    "etd_sep_create": (C.c_int, [C.POINTER(SepCfg), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), c_i64_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "etd_sep_destroy": (None, [C.c_void_p]),
+    "etd_sep_num_frames": (C.c_longlong, [C.c_void_p, C.c_longlong]),
+    "etd_sep_unit_bytes": (C.c_longlong, [C.c_void_p]),
+    "etd_sep_workspace_bytes": (C.c_longlong, [C.c_void_p, C.c_int, c_i64_p]),
+    "etd_sep_run": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, c_i64_p, C.POINTER(C.c_void_p), C.c_void_p]),
+    "etd_sep_segment_flops": (C.c_double, [C.c_void_p]),
+    "etd_sep_debug_stft": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
+    "etd_sep_debug_layer": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "etd_sep_debug_mask": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
+    "etd_sep_debug_istft": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
     "etd_dtrain_workspace_bytes": (C.c_longlong, [C.POINTER(DecCfg), C.c_int]),
     "etd_dtrain_create": (C.c_int, [C.POINTER(DecCfg), C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), c_i64_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.POINTER(C.c_void_p)]),

@@ -291,6 +291,16 @@ class BeatDetector:
                 self._write_json(r, output_json_paths[i])
         return results
 
+    def detect_audio_many(self, separator, wavs: Sequence, output_json_paths: Optional[Sequence] = None) -> List[Dict]:
+        """``detect_stems_many`` from the songs' audio: ``separator`` (an ``etude_amd.StemSeparator`` with this model's instruments) makes the stems on the device,
+        ``StemFeatures(framing="spleeter")`` reads them where they lie, and the stems path takes over; no stem or feature visits the host"""
+        if len(separator.config.instruments) != self.instr:
+            raise ValueError(f"detect_audio_many: the separator makes {len(separator.config.instruments)} stems, the model reads {self.instr}")
+        if getattr(self, "_stemfeat_spleeter", None) is None or self._stemfeat_spleeter.sample_rate != separator.config.sample_rate:
+            from .stemfeat import StemFeatures
+            self._stemfeat_spleeter = StemFeatures(sample_rate=separator.config.sample_rate, framing="spleeter", device=self.device)
+        return self.detect_stems_many(separator.separate_many(wavs), output_json_paths, stem_features=self._stemfeat_spleeter)
+
     def detect(self, input_npy_path: Union[str, Path], output_json_path: Optional[Union[str, Path]] = None, cleanup_input: bool = True) -> Dict:
         if self.tracker == "native":
             input_file = Path(input_npy_path)

@@ -164,3 +164,8 @@ def structuralize_many(detector, features_list: Sequence) -> List[List[Dict]]:
 def structuralize_stems_many(detector, stems_list: Sequence, stem_features=None) -> List[List[Dict]]:
     """the same from the songs' separated stems [instr][channels][N]: ``detector.detect_stems_many`` (features, model and trackers on the device) then ``analyze_data``"""
     return [BeatAnalyzer().analyze_data(r) for r in detector.detect_stems_many(stems_list, stem_features=stem_features)]
+
+
+def structuralize_audio_many(detector, separator, wavs: Sequence) -> List[List[Dict]]:
+    """the same from the songs' audio [channels][N]: ``detector.detect_audio_many`` (separator, features, model and trackers on the device) then ``analyze_data``"""
+    return [BeatAnalyzer().analyze_data(r) for r in detector.detect_audio_many(separator, wavs)]

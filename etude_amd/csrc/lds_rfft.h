@@ -100,5 +100,31 @@ __device__ __forceinline__ float split_power(const float* zr, const float* zi, c
   return p0 + p1;
 }
 
+// ---- what the separator (csrc/separator.hip) adds: the complex bin of the split pass, and the inverse transform as an inverse split pass in front of the same stages.
+
+// the split pass for bin k <= M as a complex number: split_power's arithmetic up to X[k], returned instead of squared
+__device__ __forceinline__ void split_bin(const float* zr, const float* zi, const float2* twS, int M, int k, float& xr, float& xi) {
+  const int ia = RFFT_PAD(k & (M - 1)), ib = RFFT_PAD((M - k) & (M - 1));
+  const float ar = zr[ia], ai = zi[ia], br = zr[ib], bi = -zi[ib];
+  const float er = 0.5f * (ar + br), ei = 0.5f * (ai + bi);
+  const float orr = 0.5f * (ai - bi), oi = -0.5f * (ar - br);
+  const float2 w = twS[k];
+  float pr, pi;
+  cmul(orr, oi, w.x, w.y, pr, pi);
+  xr = er + pr;
+  xi = ei + pi;
+}
+
+// the inverse split pass for point k < M: from the bins a = X[k] and b = X[M - k] (k = 0: b = X[M]) to conj Z[k], Z = E + i O, E = (a + conj b) / 2,
+// O = conj(W^k) (a - conj b) / 2, w = twS[k].  The forward stages on conj Z give R with z[n] = conj(R[n]) / M: x[2n] = R.re / M, x[2n + 1] = -R.im / M.
+__device__ __forceinline__ void isplit_conj(float2 a, float2 b, float2 w, float& zr, float& zi) {
+  const float er = 0.5f * (a.x + b.x), ei = 0.5f * (a.y - b.y);
+  const float dr = 0.5f * (a.x - b.x), di = 0.5f * (a.y + b.y);
+  float pr, pi;
+  cmul(dr, di, w.x, -w.y, pr, pi);
+  zr = er - pi;
+  zi = -(ei + pr);
+}
+
 }  // namespace rfft
 #endif

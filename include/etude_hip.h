@@ -687,6 +687,47 @@ int etd_render_run(etd_render*, const etd_note* notes_host, const int64_t* note_
 int etd_render_peaks(etd_render*, const float* samples_dev, const int64_t* sample_offsets_dev, const int64_t* num_samples_dev, int n_covers, float* peaks_dev,
                      void* stream);
 
+/* ------------------------------------------------------------------ source separator (a song's audio -> its stems; csrc/separator.hip)
+ * A U-Net mask separator modelled on Spleeter 2.x's 5stems model: STFT, one six-level U-Net per instrument on the magnitudes below bin F, a softmax over the
+ * instruments, ratio masks, inverse STFT.  DESIGN.md 4m is the contract (tests/separator_np.py restates it; parity with Spleeter's TensorFlow graph and its
+ * checkpoints is unpinned).  fp32 operands and accumulation, no floating-point atomics: every sum runs in an order the shapes fix. */
+typedef struct etd_sep etd_sep;
+#define ETD_SEP_LEVELS 6
+#define ETD_SEP_MAX_INSTR 16
+#define ETD_SEP_MAX_CHANNELS 8
+typedef struct {
+  int struct_bytes;            /* sizeof(etd_sep_cfg) of the caller: a mismatch is ETD_EINVAL */
+  int n_instr;                 /* 1 .. ETD_SEP_MAX_INSTR */
+  int n_channels;              /* 1 .. ETD_SEP_MAX_CHANNELS */
+  int n_fft;                   /* a power of two in 1024 .. 4096 */
+  int hop;                     /* n_fft / 4 */
+  int T, F;                    /* frames per segment and bins the U-Net reads: multiples of 64, F <= n_fft / 2 */
+  int filters[ETD_SEP_LEVELS]; /* each >= 1 */
+  int separation_exponent;     /* 1 .. 8 (Spleeter: 2) */
+  float mask_eps, bn_eps;      /* positive, finite (1e-10, 1e-3) */
+  long long workspace_bytes;   /* budget of the handle's device workspace: songs are grouped and units sub-batched under it; one song with one unit is the floor; 0 = 4 GiB */
+} etd_sep_cfg;
+/* instr_names [n_instr] and the checkpoint as a weight table (HOST fp32): per instrument "{instr}.conv{l}.weight" [5][5][Cin][Cout], ".bias" [Cout] (l = 1 .. 6),
+ * "{instr}.deconv{j}.weight" [5][5][Cout][Cin], ".bias" (j = 1 .. 6), "{instr}.bn{n}.gamma / .beta / .mean / .var" (n = 1 .. 12: the encoder's six, then the
+ * decoder's), "{instr}.head.weight" [4][4][1][n_channels], ".bias".  A missing key or a wrong size is ETD_EINVAL with the key in the message.  Needs no GPU: the
+ * weights go to the device with the first run. */
+int etd_sep_create(const etd_sep_cfg* cfg, const char* const* instr_names, const char* const* names, const float* const* host_ptrs, const int64_t* numels, int n,
+                   etd_sep** out);
+void etd_sep_destroy(etd_sep*);
+/* HOST ONLY: STFT frames of a song of N >= 1 samples, 1 + (N + n_fft) / hop (negative = ETD_EINVAL) */
+long long etd_sep_num_frames(const etd_sep*, long long N);
+/* HOST ONLY: bytes of activations one (segment, instrument) unit of the U-Net holds */
+long long etd_sep_unit_bytes(const etd_sep*);
+/* HOST ONLY: bytes of device memory a call with these songs makes the handle hold: at most the budget, unless one song (spectra, magnitudes, mask logits, masked
+ * spectra) with one unit's activations needs more */
+long long etd_sep_workspace_bytes(const etd_sep*, int n_songs, const int64_t* N_host);
+/* wav_ptrs / out_ptrs: HOST arrays of n_songs DEVICE pointers; song s is planar [n_channels][N_host[s]] fp32 and becomes [n_instr][n_channels][N_host[s]] fp32 --
+ * etd_stemfeat_run's input.  A song's stems are bit-identical alone, in any batch, under any workspace budget and from run to run.  Synchronises `stream` when the
+ * workspace grows. */
+int etd_sep_run(etd_sep*, const float* const* wav_ptrs, int n_songs, const int64_t* N_host, float* const* out_ptrs, void* stream);
+/* FLOPs of the U-Nets of one segment, all instruments (2 per multiply-add that is not a structural zero) */
+double etd_sep_segment_flops(const etd_sep*);
+
 #ifdef __cplusplus
 }
 #endif

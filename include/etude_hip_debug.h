@@ -248,6 +248,21 @@ int etd_debug_dtrain_attn(int n_seq, const int32_t* T_host, int n_heads, const f
 int etd_render_debug_plan(etd_render*, const etd_note* notes_host, const int64_t* note_offsets_host, int n_covers, const int64_t* num_samples_host,
                           int64_t* first_end_host, int32_t* ranges_host);
 
+/* test hooks of the separator (csrc/separator.hip): each stage of etd_sep_run on a caller's input, with the launchers etd_sep_run uses.  DEVICE fp32 buffers; a
+ * complex number is two consecutive floats.  Asynchronous on `stream` once the handle's weights are on the device.
+ *   stft    wav [n_channels][N] -> X [n_channels][Tf][n_fft / 2 + 1] complex, Tf = etd_sep_num_frames(N)
+ *   layer   one U-Net layer of instrument `instr` on n_units inputs back to back.  kind 0: encoder l = layer (1 .. 6): x0 [T >> (l-1)][F >> (l-1)][Cin] ->
+ *           pre [T >> l][F >> l][Cout] (conv + bias) and act = ELU(a pre + s) (either may be NULL).  kind 1: decoder j = layer: x0 = the skip (j = 1: conv_6),
+ *           x1 = the previous decoder output (j = 1: NULL), both [T >> (7-j)][F >> (7-j)][.] -> act [T >> (6-j)][F >> (6-j)][Cout] = a ELU(deconv + bias) + s.
+ *           kind 2: the head: x0 [T][F][1] -> pre [T][F][n_channels].
+ *   mask    logits [segs][n_instr][T][F][n_channels], mag [segs * T][F][n_channels], X [n_channels][Tf][F] complex (segs = ceil(Tf / T)) ->
+ *           Y [n_instr][n_channels][Tf][F] complex
+ *   istft   Y [n_instr][n_channels][Tf][F] complex (bins >= F are zero), Tf = etd_sep_num_frames(N) -> out [n_instr][n_channels][N] */
+int etd_sep_debug_stft(etd_sep*, const float* wav_dev, long long N, float* X_dev, void* stream);
+int etd_sep_debug_layer(etd_sep*, int instr, int kind, int layer, const float* x0_dev, const float* x1_dev, int n_units, float* pre_dev, float* act_dev, void* stream);
+int etd_sep_debug_mask(etd_sep*, const float* logits_dev, const float* mag_dev, const float* X_dev, long long Tf, float* Y_dev, void* stream);
+int etd_sep_debug_istft(etd_sep*, const float* Y_dev, long long N, float* out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
