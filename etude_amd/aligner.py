@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._engine import Engine, i64, nonneg, ptrs
 
 log = logging.getLogger(__name__)
 
@@ -43,8 +44,9 @@ def make_cfg(step_weights=(1.5, 1.5, 2.0), shift_weights=(1.0, 1.0, 1.0), alpha:
     return cfg
 
 
-class DTWEngine:
+class DTWEngine(Engine):
     """One etd_dtw handle."""
+    _destroy = "etd_dtw_destroy"
 
     def __init__(self, device="cuda", **cfg):
         self.device = torch.device(device)
@@ -56,23 +58,14 @@ class DTWEngine:
         self._lib = _lib.lib()
         h = C.c_void_p()
         _lib.check(self._lib.etd_dtw_create(C.byref(self.cfg), C.byref(h)), "etd_dtw_create")
-        self._h = h
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            self._lib.etd_dtw_destroy(h)
-            self._h = None
+        self._adopt(h)
 
     # ---- sizes (host arithmetic)
     def workspace_bytes(self, N1s: Sequence[int], N2s: Sequence[int]) -> Tuple[int, int, np.ndarray]:
         """-> (workspace bytes, int32 elements of the result buffer, each pair's offset in it)"""
         n = len(N1s)
-        a, b = (C.c_int64 * n)(*[int(x) for x in N1s]), (C.c_int64 * n)(*[int(x) for x in N2s])
         r, off = C.c_longlong(), (C.c_int64 * max(n, 1))()
-        ws = int(self._lib.etd_dtw_workspace_bytes(self._h, n, a, b, C.byref(r), off))
-        if ws < 0:
-            _lib.check(ws, "etd_dtw_workspace_bytes")
+        ws = nonneg(self._lib.etd_dtw_workspace_bytes(self.h, n, i64(N1s), i64(N2s), C.byref(r), off), "etd_dtw_workspace_bytes")
         return ws, int(r.value), np.array(off[:n], np.int64)
 
     # ---- input checks
@@ -118,12 +111,10 @@ class DTWEngine:
                 ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
             if res is None:
                 res = torch.empty(res_ints, dtype=torch.int32, device=self.device)
-            ptrs = (C.c_void_p * (4 * n))(*[t.data_ptr() for ts in tensors for t in ts])
-            a, b = (C.c_int64 * n)(*N1s), (C.c_int64 * n)(*N2s)
             host = np.zeros(res_ints, np.int32)
-            st = torch.cuda.current_stream(self.device).cuda_stream
-            _lib.check(self._lib.etd_dtw_align(self._h, ptrs, n, a, b, C.c_void_p(ws.data_ptr()), ws.numel() * ws.element_size(), C.c_void_p(res.data_ptr()), res.numel(),
-                                               host.ctypes.data, C.c_void_p(st)), "etd_dtw_align")
+            _lib.check(self._lib.etd_dtw_align(self.h, ptrs([t for ts in tensors for t in ts]), n, i64(N1s), i64(N2s), C.c_void_p(ws.data_ptr()),
+                                               ws.numel() * ws.element_size(), C.c_void_p(res.data_ptr()), res.numel(), host.ctypes.data,
+                                               self._stream(self.device)), "etd_dtw_align")
         return host, off
 
     def align_many(self, pairs: Sequence[Tuple[Feats, Feats]], details: bool = False) -> List[Dict]:
@@ -150,31 +141,28 @@ class DTWEngine:
     def debug_cost(self, cover: Feats, origin: Feats, shift: int) -> np.ndarray:
         ts = self._pair(0, cover, origin)
         N1, N2 = int(ts[0].shape[1]), int(ts[2].shape[1])
-        ptrs = (C.c_void_p * 4)(*[t.data_ptr() for t in ts])
         with torch.cuda.device(self.device):
             out = torch.empty((N1, N2) if N1 * N2 <= (1 << 22) else (1,), dtype=torch.float32, device=self.device)
             torch.cuda.synchronize(self.device)
-            _lib.check(self._lib.etd_dtw_debug_cost(self._h, ptrs, N1, N2, int(shift), C.c_void_p(out.data_ptr())), "etd_dtw_debug_cost")
+            _lib.check(self._lib.etd_dtw_debug_cost(self.h, ptrs(ts), N1, N2, int(shift), C.c_void_p(out.data_ptr())), "etd_dtw_debug_cost")
             return out.cpu().numpy()
 
     def debug_path(self, cover: Feats, origin: Feats, shift: int) -> np.ndarray:
         """the unfiltered step path of the final DTW with `shift` -> int64 [2][n], increasing"""
         ts = self._pair(0, cover, origin)
         N1, N2 = int(ts[0].shape[1]), int(ts[2].shape[1])
-        ptrs = (C.c_void_p * 4)(*[t.data_ptr() for t in ts])
         buf, n = np.zeros((N1 + N2, 2), np.int32), C.c_longlong()
         with torch.cuda.device(self.device):
             torch.cuda.synchronize(self.device)
-            _lib.check(self._lib.etd_dtw_debug_path(self._h, ptrs, N1, N2, int(shift), buf.ctypes.data, N1 + N2, C.byref(n)), "etd_dtw_debug_path")
+            _lib.check(self._lib.etd_dtw_debug_path(self.h, ptrs(ts), N1, N2, int(shift), buf.ctypes.data, N1 + N2, C.byref(n)), "etd_dtw_debug_path")
         return buf[: n.value][::-1].T.astype(np.int64)
 
     def debug_total(self, cover: Feats, origin: Feats, shift: int) -> float:
         ts = self._pair(0, cover, origin)
-        ptrs = (C.c_void_p * 4)(*[t.data_ptr() for t in ts])
         tot = C.c_double()
         with torch.cuda.device(self.device):
             torch.cuda.synchronize(self.device)
-            _lib.check(self._lib.etd_dtw_debug_total(self._h, ptrs, int(ts[0].shape[1]), int(ts[2].shape[1]), int(shift), C.byref(tot)), "etd_dtw_debug_total")
+            _lib.check(self._lib.etd_dtw_debug_total(self.h, ptrs(ts), int(ts[0].shape[1]), int(ts[2].shape[1]), int(shift), C.byref(tot)), "etd_dtw_debug_total")
         return tot.value
 
 

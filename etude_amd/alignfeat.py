@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._engine import Engine, hold, i32, i64, mono_songs_to_device, nonneg, ptrs
 
 FS = 22050
 HOP = 441                      # 50 Hz features
@@ -260,8 +261,9 @@ def limits() -> dict:
     return dict(chunk=L.value, max_sections=ms.value, max_samples=mn.value, max_songs=mg.value, max_banks=mb.value)
 
 
-class _Handle:
+class _Handle(Engine):
     """one etd_alignfeat handle: the filterbanks of a fixed tuple of tuning offsets"""
+    _destroy = "etd_alignfeat_destroy"
 
     def __init__(self, lib, tunings: Tuple[float, ...], chunk: int):
         banks = [_bank(t, chunk) for t in tunings]
@@ -270,20 +272,13 @@ class _Handle:
         apow = np.ascontiguousarray(np.stack([b["apow"] for b in banks]))
         fir = decimation_fir()
         cfg = _lib.AlignFeatCfg(sample_rate=FS, hop=HOP, fir_taps=2 * FIR_HALF + 1, decimation=DECIM, chunk=chunk, n_banks=len(banks))
-        self._lib = lib
         h = C.c_void_p()
         _lib.check(lib.etd_alignfeat_create(C.byref(cfg), fir.ctypes.data, sos.ctypes.data, nsec.ctypes.data, apow.ctypes.data, C.byref(h)), "etd_alignfeat_create")
-        self.h = h
+        self._adopt(h)
         self.index = {t: i for i, t in enumerate(tunings)}
 
-    def __del__(self):
-        h = getattr(self, "h", None)
-        if h is not None and h.value:
-            self._lib.etd_alignfeat_destroy(h)
-            self.h = None
 
-
-class AlignFeatures:
+class AlignFeatures(Engine):
     """Mono audio at 22 050 Hz -> (quantised chroma, DLNCO), both [12][ceil(N / 441)] float32 device tensors: what ``DTWEngine`` aligns.
 
     A song is a 1-d float32 array or tensor (host or device), finite, N >= 1, with a tuning offset in cents (|t| <= 50, default 0; ``"estimate"`` asks the
@@ -298,6 +293,12 @@ class AlignFeatures:
         self.chunk = self.limits["chunk"]
         self._handles: Dict[Tuple[float, ...], _Handle] = {}
         self._handle((0.0,))
+
+    def close(self) -> None:
+        """this engine's handles are its ``_Handle`` objects, one per set of filterbanks: close them all (a later call makes the ones it needs again)"""
+        for hd in getattr(self, "_handles", {}).values():
+            hd.close()
+        self._handles = {}
 
     def _handle(self, tunings: Tuple[float, ...]) -> _Handle:
         """the handle that holds these tunings' filterbanks: an existing one whose banks include them all, else a new one (at most 8 are kept; the one made
@@ -317,25 +318,13 @@ class AlignFeatures:
         return T
 
     def workspace_bytes(self, Ns: Sequence[int]) -> int:
-        arr = (C.c_int64 * len(Ns))(*[int(n) for n in Ns])
-        b = int(self._lib.etd_alignfeat_workspace_bytes(self._handle((0.0,)).h, len(Ns), arr))
-        if b < 0:
-            _lib.check(b, "etd_alignfeat_workspace_bytes")
-        return b
+        return nonneg(self._lib.etd_alignfeat_workspace_bytes(self._handle((0.0,)).h, len(Ns), i64(Ns)), "etd_alignfeat_workspace_bytes")
 
     def layout(self, Ns: Sequence[int], song: int) -> dict:
         """test hook (host arithmetic): where song `song` of a call with these lengths keeps its intermediate stages in the workspace (byte offsets) and their counts"""
-        arr = (C.c_int64 * len(Ns))(*[int(n) for n in Ns])
         out = (C.c_int64 * len(_lib.ALIGNFEAT_LAYOUT))()
-        _lib.check(self._lib.etd_alignfeat_debug_layout(self._handle((0.0,)).h, len(Ns), arr, int(song), out, len(_lib.ALIGNFEAT_LAYOUT)), "etd_alignfeat_debug_layout")
+        _lib.check(self._lib.etd_alignfeat_debug_layout(self._handle((0.0,)).h, len(Ns), i64(Ns), int(song), out, len(_lib.ALIGNFEAT_LAYOUT)), "etd_alignfeat_debug_layout")
         return dict(zip(_lib.ALIGNFEAT_LAYOUT, [int(v) for v in out]))
-
-    def _device(self) -> torch.device:
-        if self.device.type != "cuda" or not torch.cuda.is_available():
-            raise _lib.EtudeHipError("etude_amd.AlignFeatures needs a ROCm GPU (device='cuda'); there is no CPU path")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        return self.device
 
     def _batches(self, Ns: Sequence[int], tunings: Optional[Sequence[float]] = None) -> List[List[int]]:
         """consecutive songs grouped so that every group's workspace fits the budget (a song that alone exceeds it is refused) and no group holds more songs or
@@ -361,14 +350,11 @@ class AlignFeatures:
         if len(distinct) > self.limits["max_banks"]:
             raise ValueError(f"run_raw: {len(distinct)} distinct tuning offsets in one launch sequence, a handle takes {self.limits['max_banks']} (features_many splits such a call)")
         hd = self._handle(distinct)
-        ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in songs])
-        N_arr = (C.c_int64 * n)(*[int(t.numel()) for t in songs])
-        banks = (C.c_int32 * n)(*[hd.index[float(t)] for t in tunings])
         dev = self._device()
         with torch.cuda.device(dev):
-            st = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(self._lib.etd_alignfeat_run(hd.h, ptrs, n, N_arr, banks, C.c_void_p(chroma.data_ptr()), C.c_void_p(dlnco.data_ptr()),
-                                                   C.c_void_p(ws.data_ptr()), ws.numel() * ws.element_size(), C.c_void_p(st)), "etd_alignfeat_run")
+            _lib.check(self._lib.etd_alignfeat_run(hd.h, ptrs(songs), n, i64([t.numel() for t in songs]), i32([hd.index[float(t)] for t in tunings]),
+                                                   C.c_void_p(chroma.data_ptr()), C.c_void_p(dlnco.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel() * ws.element_size(),
+                                                   self._stream(dev)), "etd_alignfeat_run")
 
     def features_many(self, wavs: Sequence, tuning_offsets: Union[None, str, Sequence[float]] = None) -> List[Tuple[torch.Tensor, torch.Tensor]]:
         """songs [N_s] -> [(quantised chroma [12][T_s], DLNCO [12][T_s])] as device tensors.  A song's features depend on its samples and its tuning offset alone:
@@ -390,18 +376,7 @@ class AlignFeatures:
         for i, t in enumerate(tuning_offsets):
             if not abs(float(t)) <= 50.0:
                 raise ValueError(f"song {i}: tuning_offset must be within +-50 cents, got {t}")
-        for i, x in enumerate(wavs):
-            shp = tuple(x.shape) if hasattr(x, "shape") else None
-            if shp is None or len(shp) != 1 or shp[0] < 1:
-                raise ValueError(f"song {i}: need mono samples [N >= 1], got shape {shp}")
-            if shp[0] > self.limits["max_samples"]:
-                raise ValueError(f"song {i}: N = {shp[0]} is above the engine's {self.limits['max_samples']} samples")
-        dev = self._device()
-        songs = [torch.as_tensor(x).detach().to(dev, torch.float32).contiguous() for x in wavs]
-        bad = torch.stack([torch.isfinite(t).all() for t in songs]).logical_not().nonzero().flatten().tolist()      # (one host synchronisation for the call)
-        if bad:
-            raise ValueError(f"song {bad[0]}: holds a non-finite sample")
-        return self._features_checked(songs, tuning_offsets)
+        return self._features_checked(mono_songs_to_device(wavs, self._device, 1, self.limits["max_samples"]), tuning_offsets)
 
     def _features_checked(self, songs: List[torch.Tensor], tuning_offsets: Sequence[float]) -> List[Tuple[torch.Tensor, torch.Tensor]]:
         dev = self._device()
@@ -418,8 +393,7 @@ class AlignFeatures:
                 for T in Ts:
                     out.append((chroma[off: off + 12 * T].view(12, T), dlnco[off: off + 12 * T].view(12, T)))
                     off += 12 * T
-            for t in songs:
-                t.record_stream(torch.cuda.current_stream(dev))
+            hold(songs, dev)
         return out
 
     def features(self, wav, tuning_offset: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor]:

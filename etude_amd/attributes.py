@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._engine import Engine
 
 SRC_CLASS_ID, TGT_CLASS_ID, PAD_CLASS_ID, ATTRIBUTE_PAD_ID = 1, 2, 0, 0
 MODEL_ATTRIBUTES = ["relative_polyphony", "relative_rhythmic_intensity", "relative_note_sustain", "pitch_overlap_ratio"]
@@ -72,10 +73,11 @@ def edges_arrays(edges, max_edges: int = 2) -> Tuple[np.ndarray, np.ndarray]:
     return e, n
 
 
-class BarAttributes:
+class BarAttributes(Engine):
     """Bar pairs -> structured arrays (``PAIR_DTYPE``: ``features`` int32 [6] = note_count, pos_event_count, total_duration_in_16ths of the source then of the target;
     ``attributes`` fp64 [4] in ``MODEL_ATTRIBUTES`` order; ``bins`` int32 [4], -1 without edges; ``status``).  Constructing needs no GPU; ``pairs_many`` does: there is
     no CPU path."""
+    _destroy = "etd_attr_destroy"
 
     def __init__(self, vocab, device: Union[str, torch.device] = "cuda"):
         from .tokenizer import TinyREMITokenizer
@@ -86,7 +88,6 @@ class BarAttributes:
         self.table = np.ascontiguousarray(np.stack([tab["type"], tab["value"]], axis=1).astype(np.int32))
         cfg = _lib.AttrCfg(type_pos=TYPE_POS, type_note=TYPE_NOTE, type_duration=TYPE_DURATION)
         h = C.c_void_p()
-        self.h = None
 
         def create():
             _lib.check(self._lib.etd_attr_create(C.byref(cfg), C.c_void_p(self.table.ctypes.data), len(self.table), C.byref(h)), "etd_attr_create")
@@ -95,20 +96,7 @@ class BarAttributes:
                 create()
         else:
             create()
-        self.h = h
-
-    def __del__(self):
-        h = getattr(self, "h", None)
-        if h is not None and h.value:
-            self._lib.etd_attr_destroy(h)
-            self.h = None
-
-    def _device(self) -> torch.device:
-        if self.device.type != "cuda" or not torch.cuda.is_available():
-            raise _lib.EtudeHipError("etude_amd.BarAttributes needs a ROCm GPU (device='cuda'); there is no CPU path")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        return self.device
+        self._adopt(h)
 
     def check_offsets(self, offsets: np.ndarray) -> None:
         """host only: the library's refusal of one side's bars (a bar above the token limit, too many bars), before anything touches the device"""
@@ -150,12 +138,11 @@ class BarAttributes:
             out = torch.empty(76 * P, dtype=torch.uint8, device=dev)      # fp64 [P][4] | int32 [P][6] | int32 [P][4] | int32 [P]
             base, ob = buf.data_ptr(), out.data_ptr()
             ptr = lambda o: C.c_void_p(base + o) if o is not None else None      # noqa: E731
-            st = torch.cuda.current_stream(dev).cuda_stream
             _lib.check(self._lib.etd_attr_run(
                 self.h, ptr(o_sids), ptr(o_soff), s_off.ctypes.data_as(_lib.c_i64_p), len(s_off) - 1, ptr(o_sidx),
                 ptr(o_tids), ptr(o_toff), t_off.ctypes.data_as(_lib.c_i64_p), len(t_off) - 1, ptr(o_tidx), P,
                 C.c_void_p(e_arr.ctypes.data) if e_arr is not None else None, C.c_void_p(n_arr.ctypes.data) if n_arr is not None else None,
-                C.c_void_p(ob + 32 * P), C.c_void_p(ob), C.c_void_p(ob + 56 * P) if e_arr is not None else None, C.c_void_p(ob + 72 * P), C.c_void_p(st)), "etd_attr_run")
+                C.c_void_p(ob + 32 * P), C.c_void_p(ob), C.c_void_p(ob + 56 * P) if e_arr is not None else None, C.c_void_p(ob + 72 * P), self._stream(dev)), "etd_attr_run")
             raw = out.cpu().numpy()
         res = np.empty(P, PAIR_DTYPE)
         res["attributes"] = raw[:32 * P].view(np.float64).reshape(P, 4)

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._engine import Engine, i64
 from .config import BeatDetectorConfig
 
 FEATURE_BOUND = 80.0
@@ -80,7 +81,9 @@ def check_state_dict(sd: Dict, cfg) -> None:
         raise RuntimeError(f"Error(s) in loading state_dict for Demixed_DilatedTransformerModel: size mismatch {bad[:4]}")
 
 
-class BeatDetector:
+class BeatDetector(Engine):
+    _destroy = "etd_beat_destroy"
+
     def __init__(self, config: Optional[BeatDetectorConfig] = None, model_path: Union[str, Path, None] = None, device: Union[str, torch.device] = "auto",
                  state_dict: Optional[Dict] = None, max_rows: int = 1 << 17, tracker: str = "madmom"):
         self.config = config if config is not None else BeatDetectorConfig()
@@ -91,10 +94,7 @@ class BeatDetector:
         if device == "auto":
             device = "cuda"
         self.device = torch.device(device)
-        if self.device.type != "cuda" or not torch.cuda.is_available():
-            raise _lib.EtudeHipError("etude_amd.BeatDetector needs a ROCm GPU (device='cuda'); there is no CPU path")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._device()
         if state_dict is None:
             if model_path is None:
                 raise ValueError("BeatDetector: model_path (or state_dict) is required")
@@ -111,15 +111,9 @@ class BeatDetector:
         with torch.cuda.device(self.device):
             _lib.check(lib.etd_beat_create(C.byref(cfg), names, ptrs, nums, n, C.byref(h)), "etd_beat_create")
         del keep
-        self._h = h
+        self._adopt(h)
         self._lib = lib
         self.instr, self.ntoken = m.instr, m.ntoken
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            self._lib.etd_beat_destroy(h)
-            self._h = None
 
     # ------------------------------------------------------------------ model
     def _run(self, feat: torch.Tensor, Ts: Sequence[int], want_tempo: bool = True):
@@ -127,11 +121,9 @@ class BeatDetector:
         n = len(Ts)
         logits = torch.empty((int(sum(Ts)), self.ntoken), dtype=torch.float32, device=self.device)
         tempo = torch.empty((n, 300), dtype=torch.float32, device=self.device) if want_tempo else None
-        T_arr = (C.c_int64 * n)(*[int(t) for t in Ts])
         with torch.cuda.device(self.device):
-            st = torch.cuda.current_stream(self.device).cuda_stream
-            _lib.check(self._lib.etd_beat_forward(self._h, C.c_void_p(feat.data_ptr()), n, T_arr, C.c_void_p(logits.data_ptr()),
-                                                  C.c_void_p(tempo.data_ptr()) if tempo is not None else None, C.c_void_p(st)), "etd_beat_forward")
+            _lib.check(self._lib.etd_beat_forward(self.h, C.c_void_p(feat.data_ptr()), n, i64(Ts), C.c_void_p(logits.data_ptr()),
+                                                  C.c_void_p(tempo.data_ptr()) if tempo is not None else None, self._stream(self.device)), "etd_beat_forward")
         return logits, tempo
 
     def _songs_to_device(self, songs: Sequence) -> Tuple[torch.Tensor, List[int]]:
@@ -334,18 +326,18 @@ class BeatDetector:
     # ------------------------------------------------------------------ measurement
     def flops(self, T: int) -> float:
         """algorithmic FLOPs of one song of T frames"""
-        return float(self._lib.etd_beat_flops(self._h, int(T)))
+        return float(self._lib.etd_beat_flops(self.h, int(T)))
 
     def debug_taps(self, front: Optional[torch.Tensor], layer0: Optional[torch.Tensor]) -> None:
         """test hook: following calls copy the token rows after the front end / time layer 0 into these [rows][256] device tensors (None = off)"""
-        _lib.check(self._lib.etd_beat_debug_taps(self._h, C.c_void_p(front.data_ptr()) if front is not None else None,
+        _lib.check(self._lib.etd_beat_debug_taps(self.h, C.c_void_p(front.data_ptr()) if front is not None else None,
                                                  C.c_void_p(layer0.data_ptr()) if layer0 is not None else None), "etd_beat_debug_taps")
 
     def debug_stage_taps(self, layer_mask: int = 0, rows: int = 0, frames: int = 0, segs: int = 0, slices: int = 0, islices: int = 0, **bufs: torch.Tensor) -> None:
         """Test hook (etd_beat_debug_stage_taps): register contiguous fp32 device tensors as the destinations of every launch's output, named as the members of
         etd_debug_beat_taps and shaped as include/etude_hip_debug.h states; no tensors = taps off.  The caller keeps the tensors alive."""
         if not bufs:
-            _lib.check(self._lib.etd_beat_debug_stage_taps(self._h, None), "etd_beat_debug_stage_taps")
+            _lib.check(self._lib.etd_beat_debug_stage_taps(self.h, None), "etd_beat_debug_stage_taps")
             return
         t = _lib.BeatTaps(layer_mask=int(layer_mask), rows=int(rows), frames=int(frames), segs=int(segs), d_hid=int(self.config.model.d_hid), slices=int(slices),
                           islices=int(islices))
@@ -359,4 +351,4 @@ class BeatDetector:
             if v.numel() < need:
                 raise ValueError(f"debug_stage_taps: {k} holds {v.numel()} floats, the stated sizes need {need}")
             setattr(t, k, v.data_ptr())
-        _lib.check(self._lib.etd_beat_debug_stage_taps(self._h, C.byref(t)), "etd_beat_debug_stage_taps")
+        _lib.check(self._lib.etd_beat_debug_stage_taps(self.h, C.byref(t)), "etd_beat_debug_stage_taps")

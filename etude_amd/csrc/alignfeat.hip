@@ -316,7 +316,6 @@ __global__ __launch_bounds__(AF_THREADS) void k_af_tail(const AfArgs a) {
   for (long long i = tid; i < 12 * T; i += AF_THREADS) out[i] = mx > 0.f ? D[i] / mx : D[i];
 }
 
-inline long long af_align(long long x) { return (x + 255) & ~255LL; }
 inline long long af_ceil(long long a, long long b) { return (a + b - 1) / b; }
 
 }  // namespace
@@ -326,7 +325,6 @@ struct etd_alignfeat {
   std::vector<float> fir;
   std::vector<double> sos, apow, hann;
   std::vector<int> nsec;
-  bool on_dev = false;
   DevPool pool;
   float* d_fir = nullptr;
   double *d_sos = nullptr, *d_apow = nullptr, *d_hann = nullptr;
@@ -339,7 +337,8 @@ namespace {
 int af_plan(const etd_alignfeat* h, int n_songs, const int64_t* N_host, std::vector<AfSong>* tab, long long* ws_bytes, long long* blocks, long long* maxT) {
   if (!h || !N_host) ETD_FAIL(ETD_EINVAL, "alignfeat: null argument");
   if (n_songs < 1 || n_songs > AF_MAX_SONGS) ETD_FAIL(ETD_EINVAL, "alignfeat: %d songs in one call (need 1 .. %d)", n_songs, AF_MAX_SONGS);
-  long long off = af_align((long long)n_songs * (long long)sizeof(AfSong)), blk = 0, out = 0, mt = 0;
+  WsCursor ws{ws_align((long long)n_songs * (long long)sizeof(AfSong))};
+  long long blk = 0, out = 0, mt = 0;
   for (int s = 0; s < n_songs; ++s) {
     const long long N = N_host[s];
     if (N < 1) ETD_FAIL(ETD_EINVAL, "alignfeat: song %d has N = %lld (need >= 1)", s, N);
@@ -356,37 +355,33 @@ int af_plan(const etd_alignfeat* h, int n_songs, const int64_t* N_host, std::vec
     g.blk0 = blk;
     blk += af_btotal(g.bpb);
     const long long samples = af_btotal(g.n), chunks = af_btotal(g.nc), nov = af_btotal(g.nm);
-    auto take = [&](long long bytes) { const long long o = off; off += af_align(bytes); return o; };
-    g.off_x1 = take(4 * g.n[1]); g.off_x2 = take(4 * g.n[2]);
-    g.off_u = take(8 * samples); g.off_y = take(4 * samples);
-    g.off_st = take(8 * AF_NS * chunks);
-    g.off_E = take(4 * AF_BANDS * g.T);
-    g.off_nov = take(4 * nov); g.off_ph = take(4 * nov); g.off_pf = take(4 * nov);
-    g.off_co = take(48 * g.T); g.off_g = take(4 * g.T); g.off_G = take(4 * g.T); g.off_D = take(48 * g.T);
+    g.off_x1 = ws.take(4 * g.n[1]); g.off_x2 = ws.take(4 * g.n[2]);
+    g.off_u = ws.take(8 * samples); g.off_y = ws.take(4 * samples);
+    g.off_st = ws.take(8 * AF_NS * chunks);
+    g.off_E = ws.take(4 * AF_BANDS * g.T);
+    g.off_nov = ws.take(4 * nov); g.off_ph = ws.take(4 * nov); g.off_pf = ws.take(4 * nov);
+    g.off_co = ws.take(48 * g.T); g.off_g = ws.take(4 * g.T); g.off_G = ws.take(4 * g.T); g.off_D = ws.take(48 * g.T);
     g.out_off = out;
     out += 12 * g.T;
     mt = g.T > mt ? g.T : mt;
     if (blk > 0x7fffffffLL) ETD_FAIL(ETD_EINVAL, "alignfeat: more than 2^31 - 1 workgroups in one call");
     if (tab) (*tab)[s] = g;
   }
-  if (ws_bytes) *ws_bytes = off;
+  if (ws_bytes) *ws_bytes = ws.off;
   if (blocks) *blocks = blk;
   if (maxT) *maxT = mt;
   return ETD_OK;
 }
 
 int af_upload(etd_alignfeat* h) {
-  if (h->on_dev) return ETD_OK;
   DevPool& P = h->pool;
-  const size_t m0 = P.mark();
-  auto fail = [&](int rc) { P.free_from(m0); return rc; };
-  ETD_TRY_OR(fail, P.upload(&h->d_fir, h->fir.data(), h->fir.size()));
-  ETD_TRY_OR(fail, P.upload(&h->d_sos, h->sos.data(), h->sos.size()));
-  ETD_TRY_OR(fail, P.upload(&h->d_apow, h->apow.data(), h->apow.size()));
-  ETD_TRY_OR(fail, P.upload(&h->d_hann, h->hann.data(), h->hann.size()));
-  ETD_TRY_OR(fail, P.upload(&h->d_nsec, h->nsec.data(), h->nsec.size()));
-  h->on_dev = true;
-  return ETD_OK;
+  return P.upload_once([&]() -> int {
+    ETD_TRY(P.upload(&h->d_fir, h->fir.data(), h->fir.size()));
+    ETD_TRY(P.upload(&h->d_sos, h->sos.data(), h->sos.size()));
+    ETD_TRY(P.upload(&h->d_apow, h->apow.data(), h->apow.size()));
+    ETD_TRY(P.upload(&h->d_hann, h->hann.data(), h->hann.size()));
+    return P.upload(&h->d_nsec, h->nsec.data(), h->nsec.size());
+  });
 }
 
 unsigned af_grid(long long count) {
@@ -408,16 +403,14 @@ extern "C" int etd_alignfeat_limits(int* chunk, int* max_sections, long long* ma
 extern "C" int etd_alignfeat_create(const etd_alignfeat_cfg* cfg, const float* fir_host, const double* sos_host, const int32_t* n_sections, const double* apow_host,
                                     etd_alignfeat** out) {
   if (!cfg || !out) ETD_FAIL(ETD_EINVAL, "alignfeat_create: null argument");
-  if (cfg->struct_bytes != (int)sizeof(etd_alignfeat_cfg))
-    ETD_FAIL(ETD_EINVAL, "alignfeat_create: etd_alignfeat_cfg is %d bytes here, the caller's is %d -- caller built against another etude_hip.h", (int)sizeof(etd_alignfeat_cfg), cfg->struct_bytes);
+  ETD_CHECK_CFG(cfg, etd_alignfeat_cfg, "alignfeat_create");
   if (cfg->sample_rate != 22050 || cfg->hop != AF_HOP || cfg->fir_taps != AF_TAPS || cfg->decimation != AF_DEC)
     ETD_FAIL(ETD_EINVAL, "alignfeat_create: this build is fixed to 22050 Hz, hop %d, %d taps, decimation %d (got %d, %d, %d, %d)", AF_HOP, AF_TAPS, AF_DEC,
              cfg->sample_rate, cfg->hop, cfg->fir_taps, cfg->decimation);
   if (cfg->chunk != AF_L) ETD_FAIL(ETD_EINVAL, "alignfeat_create: chunk = %d, this build's chunk (the power in apow) is %d", cfg->chunk, AF_L);
   if (cfg->n_banks < 1 || cfg->n_banks > AF_MAX_BANKS) ETD_FAIL(ETD_EINVAL, "alignfeat_create: n_banks = %d must be in 1 .. %d", cfg->n_banks, AF_MAX_BANKS);
   if (!fir_host || !sos_host || !n_sections || !apow_host) ETD_FAIL(ETD_EINVAL, "alignfeat_create: null table");
-  for (int i = 0; i < AF_TAPS; ++i)
-    if (!std::isfinite(fir_host[i])) ETD_FAIL(ETD_EINVAL, "alignfeat_create: the decimation filter holds a non-finite value");
+  if (!finite_all(fir_host, AF_TAPS)) ETD_FAIL(ETD_EINVAL, "alignfeat_create: the decimation filter holds a non-finite value");
   const long long nb = (long long)cfg->n_banks * AF_BANDS;
   for (long long b = 0; b < nb; ++b) {
     const int ns = n_sections[b];
@@ -425,14 +418,12 @@ extern "C" int etd_alignfeat_create(const etd_alignfeat_cfg* cfg, const float* f
     if (ns < 1) ETD_FAIL(ETD_EINVAL, "alignfeat_create: band %lld has %d sections (need >= 1)", b, ns);
     for (int k = 0; k < ns; ++k) {
       const double* c = sos_host + (b * AF_MAX_SEC + k) * 6;
-      for (int i = 0; i < 6; ++i)
-        if (!std::isfinite(c[i])) ETD_FAIL(ETD_EINVAL, "alignfeat_create: band %lld section %d holds a non-finite coefficient", b, k);
+      if (!finite_all(c, 6)) ETD_FAIL(ETD_EINVAL, "alignfeat_create: band %lld section %d holds a non-finite coefficient", b, k);
       if (c[3] != 1.0) ETD_FAIL(ETD_EINVAL, "alignfeat_create: band %lld section %d has a0 = %g (need 1)", b, k, c[3]);
       if (!(std::fabs(c[5]) < 1.0) || !(std::fabs(c[4]) < 1.0 + c[5]))
         ETD_FAIL(ETD_EINVAL, "alignfeat_create: band %lld section %d is unstable (a1 = %.17g, a2 = %.17g: a pole on or outside the unit circle)", b, k, c[4], c[5]);
     }
-    for (int i = 0; i < AF_NS * AF_NS; ++i)
-      if (!std::isfinite(apow_host[b * AF_NS * AF_NS + i])) ETD_FAIL(ETD_EINVAL, "alignfeat_create: band %lld's chunk matrix holds a non-finite value", b);
+    if (!finite_all(apow_host + b * AF_NS * AF_NS, AF_NS * AF_NS)) ETD_FAIL(ETD_EINVAL, "alignfeat_create: band %lld's chunk matrix holds a non-finite value", b);
   }
   etd_alignfeat* h = new etd_alignfeat();
   h->cfg = *cfg;
@@ -450,10 +441,7 @@ extern "C" int etd_alignfeat_create(const etd_alignfeat_cfg* cfg, const float* f
 
 extern "C" void etd_alignfeat_destroy(etd_alignfeat* h) {
   if (!h) return;
-  if (h->on_dev) {
-    (void)hipDeviceSynchronize();   // kernels of this handle may still be in flight
-    h->pool.free_all();
-  }
+  h->pool.release_uploaded();
   delete h;
 }
 
@@ -502,8 +490,7 @@ extern "C" int etd_alignfeat_run(etd_alignfeat* h, const float* const* wav_ptrs,
     samples += (double)af_btotal(tab[s].n);
   }
   ETD_TRY(af_upload(h));
-  HIP_TRY(hipMemcpyAsync(workspace_dev, tab.data(), tab.size() * sizeof(AfSong), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipStreamSynchronize(st));                   // (tab is host memory of this call)
+  ETD_TRY(upload_table(st, workspace_dev, tab));
   AfArgs a;
   a.tab = (const AfSong*)workspace_dev; a.n_songs = n_songs; a.ws = (char*)workspace_dev;
   a.fir = h->d_fir; a.sos = h->d_sos; a.nsec = h->d_nsec; a.apow = h->d_apow; a.hann = h->d_hann;

@@ -166,8 +166,7 @@ extern "C" int etd_attr_limits(int* max_bar_tokens, int* max_pairs, int* max_pos
 
 extern "C" int etd_attr_create(const etd_attr_cfg* cfg, const int32_t* event_table_host, int vocab_size, etd_attr** out) {
   if (!cfg || !event_table_host || !out) ETD_FAIL(ETD_EINVAL, "attr_create: null argument");
-  if (cfg->struct_bytes != (int)sizeof(etd_attr_cfg))
-    ETD_FAIL(ETD_EINVAL, "attr_create: etd_attr_cfg is %d bytes here, the caller's is %d -- caller built against another etude_hip.h", (int)sizeof(etd_attr_cfg), cfg->struct_bytes);
+  ETD_CHECK_CFG(cfg, etd_attr_cfg, "attr_create");
   if (vocab_size < 1) ETD_FAIL(ETD_EINVAL, "attr_create: vocab_size = %d (need >= 1)", vocab_size);
   if (cfg->type_pos < 0 || cfg->type_note < 0 || cfg->type_duration < 0 || cfg->type_pos == cfg->type_note || cfg->type_pos == cfg->type_duration || cfg->type_note == cfg->type_duration)
     ETD_FAIL(ETD_EINVAL, "attr_create: the event types of Pos, Note and Duration must be three different codes >= 0 (got %d, %d, %d)", cfg->type_pos, cfg->type_note, cfg->type_duration);

@@ -581,8 +581,7 @@ extern "C" int etd_beat_forward(etd_beat* e, const float* feat_dev, int n_seq, c
              frames, segs);
   const long long cap = big > e->cfg.max_rows ? big : e->cfg.max_rows;        // a song longer than max_rows gets a workspace of its own size
   ETD_TRY(ensure_ws(e, cap, n_seq, st));
-  HIP_TRY(hipMemcpyAsync(e->tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipStreamSynchronize(st));                   // (tab is host memory of this call)
+  ETD_TRY(upload_table(st, e->tab, tab));
   const int* row0 = e->tab; const int* frame0 = e->tab + n_seq + 1; const int* seg0 = e->tab + 2 * (n_seq + 1);
   int s = 0;
   while (s < n_seq) {      // chunks of whole songs, in order, up to cap rows each

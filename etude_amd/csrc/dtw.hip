@@ -392,8 +392,7 @@ int dtw_launch(etd_dtw* h, const float* const* ptrs, int n, const int64_t* N1, c
 
 extern "C" int etd_dtw_create(const etd_dtw_cfg* cfg, etd_dtw** out) {
   if (!cfg || !out) ETD_FAIL(ETD_EINVAL, "dtw_create: null argument");
-  if (cfg->struct_bytes != (int)sizeof(etd_dtw_cfg))
-    ETD_FAIL(ETD_EINVAL, "dtw_create: etd_dtw_cfg is %d bytes here, the caller's is %d -- caller built against another etude_hip.h", (int)sizeof(etd_dtw_cfg), cfg->struct_bytes);
+  ETD_CHECK_CFG(cfg, etd_dtw_cfg, "dtw_create");
   if (cfg->cens_window < 1 || cfg->cens_window > 4095 || !(cfg->cens_window & 1)) ETD_FAIL(ETD_EINVAL, "dtw_create: cens_window = %d must be odd, in 1 .. 4095", cfg->cens_window);
   if (cfg->cens_decimation < 1 || cfg->cens_decimation > 4096) ETD_FAIL(ETD_EINVAL, "dtw_create: cens_decimation = %d must be in 1 .. 4096", cfg->cens_decimation);
   for (int k = 0; k < 3; ++k)

@@ -1,6 +1,9 @@
 // Host-side plumbing every engine's create / destroy path shares: the checkpoint's weight table, the list of device allocations a handle owns,
-// the fp32 -> 16-bit conversions of the weight packers, and the "on error, free the half-built handle" macro.  Nothing here is on a hot path.
+// the fp32 -> 16-bit conversions of the weight packers, the "on error, free the half-built handle" macro, and what every batch engine's per-call host path
+// shares: the config-size refusal, the workspace cursor, the finiteness scan, the per-call table upload and the lazy upload of a handle's tables.
+// Nothing here is on a hot path.
 #pragma once
+#include <cmath>
 #include <cstring>
 #include <map>
 #include <string>
@@ -73,7 +76,51 @@ struct DevPool {
     ptrs.resize(m); bytes.resize(m);
   }
   void free_all() { free_from(0); }
+  // Lazy tables: an engine whose create needs no GPU keeps its tables on the host and every run starts with upload_once(body).  `body` (-> error code) allocates
+  // from this pool and runs once; if it fails, what it allocated is freed and the next run tries again.
+  bool uploaded = false;
+  template <typename F> int upload_once(F body) {
+    if (uploaded) return ETD_OK;
+    const size_t m0 = mark();
+    const int rc = body();
+    if (rc != ETD_OK) free_from(m0);
+    uploaded = rc == ETD_OK;
+    return rc;
+  }
+  // ... and its destroy: nothing to do for a handle that never ran
+  void release_uploaded() {
+    if (!uploaded) return;
+    (void)hipDeviceSynchronize();          // kernels of this handle may still be in flight
+    free_all();
+  }
 };
+
+// A config struct leads with struct_bytes = the caller's sizeof: any other layout is refused (`who`: the create function's name in the message)
+#define ETD_CHECK_CFG(cfg, type, who)                                                                                                                   \
+  do {                                                                                                                                                  \
+    if ((cfg)->struct_bytes != (int)sizeof(type))                                                                                                       \
+      ETD_FAIL(ETD_EINVAL, who ": " #type " is %d bytes here, the caller's is %d -- caller built against another etude_hip.h", (int)sizeof(type), (cfg)->struct_bytes); \
+  } while (0)
+
+// Per-call workspaces: every piece starts on a multiple of 256 bytes
+inline long long ws_align(long long bytes) { return (bytes + 255) & ~255LL; }
+struct WsCursor {
+  long long off = 0;                       // the next piece's offset; at the end, the bytes the pieces need
+  long long take(long long bytes) { const long long o = off; off += ws_align(bytes); return o; }
+};
+
+template <typename T> bool finite_all(const T* p, size_t n) {      // T: float or double
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(p[i])) return false;
+  return true;
+}
+
+// A per-call host table to the device on the call's stream.  The wait is the call's one synchronisation: `v` is host memory of this call and must outlive the copy.
+template <typename T> int upload_table(hipStream_t st, void* dst, const std::vector<T>& v) {
+  HIP_TRY(hipMemcpyAsync(dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return ETD_OK;
+}
 
 // fp32 -> 16-bit operand bits, round to nearest even, NaN kept
 inline uint16_t f32_to_bf16_bits(float f) {

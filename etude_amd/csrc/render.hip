@@ -158,7 +158,7 @@ __global__ __launch_bounds__(RN_THREADS) void k_render_peaks(const float* __rest
 }
 
 inline long long rn_blocks(long long N) { return (N + RN_BLOCK - 1) / RN_BLOCK; }
-inline long long rn_up(long long x, long long a) { return (x + a - 1) / a * a; }
+inline long long rn_up(long long x, long long a) { return (x + a - 1) / a * a; }      // (samples to RN_ALIGN; workspace bytes go through ws_align)
 
 }  // namespace
 
@@ -189,11 +189,11 @@ int rn_layout(const etd_render* h, int n_covers, const int64_t* note_off, const 
   }
   L->blocks = blocks; L->notes = note_off[n_covers];
   L->off_tab = 0;
-  L->off_rng = rn_up((long long)n_covers * (long long)sizeof(RnCover), 256);
-  L->off_head = rn_up(L->off_rng + blocks * (long long)sizeof(int2), 256);
+  L->off_rng = ws_align((long long)n_covers * (long long)sizeof(RnCover));
+  L->off_head = ws_align(L->off_rng + blocks * (long long)sizeof(int2));
   L->upload = L->off_head + L->notes * (long long)sizeof(RnHead);
-  L->off_rec = rn_up(L->upload, 256);
-  L->total = rn_up(L->off_rec + L->notes * (long long)sizeof(RnNote), 256);
+  L->off_rec = ws_align(L->upload);
+  L->total = ws_align(L->off_rec + L->notes * (long long)sizeof(RnNote));
   return ETD_OK;
 }
 
@@ -210,8 +210,7 @@ extern "C" int etd_render_limits(int* max_notes, long long* max_samples, int* ma
 
 extern "C" int etd_render_create(const etd_render_cfg* cfg, etd_render** out) {
   if (!cfg || !out) ETD_FAIL(ETD_EINVAL, "render_create: null argument");
-  if (cfg->struct_bytes != (int)sizeof(etd_render_cfg))
-    ETD_FAIL(ETD_EINVAL, "render_create: etd_render_cfg is %d bytes here, the caller's is %d -- caller built against another etude_hip.h", (int)sizeof(etd_render_cfg), cfg->struct_bytes);
+  ETD_CHECK_CFG(cfg, etd_render_cfg, "render_create");
   if (cfg->sample_rate < 8000 || cfg->sample_rate > 48000) ETD_FAIL(ETD_EINVAL, "render_create: sample_rate = %d (need 8000 .. 48000)", cfg->sample_rate);
   if (cfg->partials < 1 || cfg->partials > RN_MAX_PARTIALS) ETD_FAIL(ETD_EINVAL, "render_create: partials = %d (need 1 .. %d)", cfg->partials, RN_MAX_PARTIALS);
   const double pos[] = {cfg->inharmonicity_step, cfg->attack, cfg->decay_base, cfg->decay_halving, cfg->release_tau, cfg->release_len, cfg->gain, cfg->nyquist_fraction};
@@ -349,8 +348,7 @@ extern "C" int etd_render_run(etd_render* h, const etd_note* notes_host, const i
   if (L.blocks == 0) return ETD_OK;                // nothing to write
   hipStream_t st = (hipStream_t)stream;
   unsigned char* ws = (unsigned char*)workspace_dev;
-  HIP_TRY(hipMemcpyAsync(ws, h->stage.data(), (size_t)L.upload, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipStreamSynchronize(st));                   // (the stage is host memory of this call)
+  ETD_TRY(upload_table(st, ws, h->stage));          // (rn_plan sized the stage to L.upload bytes)
   h->used = true;
   RnNote* recs = reinterpret_cast<RnNote*>(ws + L.off_rec);
   if (L.notes > 0) {

@@ -461,8 +461,7 @@ extern "C" int etd_rhythm_limits(int* max_onsets, int* max_covers, int* max_top_
 
 extern "C" int etd_rhythm_create(const etd_rhythm_cfg* cfg, etd_rhythm** out) {
   if (!cfg || !out) ETD_FAIL(ETD_EINVAL, "rhythm_create: null argument");
-  if (cfg->struct_bytes != (int)sizeof(etd_rhythm_cfg))
-    ETD_FAIL(ETD_EINVAL, "rhythm_create: etd_rhythm_cfg is %d bytes here, the caller's is %d -- caller built against another etude_hip.h", (int)sizeof(etd_rhythm_cfg), cfg->struct_bytes);
+  ETD_CHECK_CFG(cfg, etd_rhythm_cfg, "rhythm_create");
   if (cfg->top_k < 1 || cfg->top_k > RH_MAX_TOPK) ETD_FAIL(ETD_EINVAL, "rhythm_create: top_k = %d (need 1 .. %d)", cfg->top_k, RH_MAX_TOPK);
   if (cfg->precision_digits < 0 || cfg->precision_digits > RH_MAX_DIGITS) ETD_FAIL(ETD_EINVAL, "rhythm_create: precision_digits = %d (need 0 .. %d)", cfg->precision_digits, RH_MAX_DIGITS);
   if (cfg->n_gram < 1 || cfg->n_gram > RH_MAX_NGRAM) ETD_FAIL(ETD_EINVAL, "rhythm_create: n_gram = %d (need 1 .. %d)", cfg->n_gram, RH_MAX_NGRAM);

@@ -301,12 +301,6 @@ __global__ __launch_bounds__(SEP_THREADS) void k_sep_ola(const float* __restrict
   out[e] = acc * (2.f / 3.f);
 }
 
-bool sep_finite(const float* p, size_t n) {
-  for (size_t i = 0; i < n; ++i)
-    if (!std::isfinite(p[i])) return false;
-  return true;
-}
-
 }  // namespace
 
 struct etd_sep {
@@ -322,7 +316,6 @@ struct etd_sep {
   std::vector<float2> twM, twS;
   std::vector<float> w_conv[ETD_SEP_LEVELS], b_conv[ETD_SEP_LEVELS], w_dec[ETD_SEP_LEVELS][4], b_dec[ETD_SEP_LEVELS], bn_a[2 * ETD_SEP_LEVELS], bn_s[2 * ETD_SEP_LEVELS];
   std::vector<float> w_head, b_head;
-  bool on_dev = false;
   DevPool pool;
   float* d_window = nullptr; float2 *d_twM = nullptr, *d_twS = nullptr;
   float *d_w_conv[ETD_SEP_LEVELS], *d_b_conv[ETD_SEP_LEVELS], *d_w_dec[ETD_SEP_LEVELS][4], *d_b_dec[ETD_SEP_LEVELS], *d_bn_a[2 * ETD_SEP_LEVELS], *d_bn_s[2 * ETD_SEP_LEVELS];
@@ -337,30 +330,25 @@ namespace {
 inline int sep_dec_taps(int p) { return p ? 3 : 2; }
 inline int sep_dec_tap(int p, int a) { return p ? 2 * a : 1 + 2 * a; }
 
-inline long long align256(long long b) { return (b + 255) & ~255LL; }
-
 int sep_upload(etd_sep* h) {
-  if (h->on_dev) return ETD_OK;
   DevPool& P = h->pool;
-  const size_t m0 = P.mark();
-  auto fail = [&](int rc) { P.free_from(m0); return rc; };
-  ETD_TRY_OR(fail, P.upload(&h->d_window, h->window.data(), h->window.size()));
-  ETD_TRY_OR(fail, P.upload(&h->d_twM, h->twM.data(), h->twM.size()));
-  ETD_TRY_OR(fail, P.upload(&h->d_twS, h->twS.data(), h->twS.size()));
-  for (int l = 0; l < ETD_SEP_LEVELS; ++l) {
-    ETD_TRY_OR(fail, P.upload(&h->d_w_conv[l], h->w_conv[l].data(), h->w_conv[l].size()));
-    ETD_TRY_OR(fail, P.upload(&h->d_b_conv[l], h->b_conv[l].data(), h->b_conv[l].size()));
-    for (int p = 0; p < 4; ++p) ETD_TRY_OR(fail, P.upload(&h->d_w_dec[l][p], h->w_dec[l][p].data(), h->w_dec[l][p].size()));
-    ETD_TRY_OR(fail, P.upload(&h->d_b_dec[l], h->b_dec[l].data(), h->b_dec[l].size()));
-  }
-  for (int n = 0; n < 2 * ETD_SEP_LEVELS; ++n) {
-    ETD_TRY_OR(fail, P.upload(&h->d_bn_a[n], h->bn_a[n].data(), h->bn_a[n].size()));
-    ETD_TRY_OR(fail, P.upload(&h->d_bn_s[n], h->bn_s[n].data(), h->bn_s[n].size()));
-  }
-  ETD_TRY_OR(fail, P.upload(&h->d_w_head, h->w_head.data(), h->w_head.size()));
-  ETD_TRY_OR(fail, P.upload(&h->d_b_head, h->b_head.data(), h->b_head.size()));
-  h->on_dev = true;
-  return ETD_OK;
+  return P.upload_once([&]() -> int {
+    ETD_TRY(P.upload(&h->d_window, h->window.data(), h->window.size()));
+    ETD_TRY(P.upload(&h->d_twM, h->twM.data(), h->twM.size()));
+    ETD_TRY(P.upload(&h->d_twS, h->twS.data(), h->twS.size()));
+    for (int l = 0; l < ETD_SEP_LEVELS; ++l) {
+      ETD_TRY(P.upload(&h->d_w_conv[l], h->w_conv[l].data(), h->w_conv[l].size()));
+      ETD_TRY(P.upload(&h->d_b_conv[l], h->b_conv[l].data(), h->b_conv[l].size()));
+      for (int p = 0; p < 4; ++p) ETD_TRY(P.upload(&h->d_w_dec[l][p], h->w_dec[l][p].data(), h->w_dec[l][p].size()));
+      ETD_TRY(P.upload(&h->d_b_dec[l], h->b_dec[l].data(), h->b_dec[l].size()));
+    }
+    for (int n = 0; n < 2 * ETD_SEP_LEVELS; ++n) {
+      ETD_TRY(P.upload(&h->d_bn_a[n], h->bn_a[n].data(), h->bn_a[n].size()));
+      ETD_TRY(P.upload(&h->d_bn_s[n], h->bn_s[n].data(), h->bn_s[n].size()));
+    }
+    ETD_TRY(P.upload(&h->d_w_head, h->w_head.data(), h->w_head.size()));
+    return P.upload(&h->d_b_head, h->b_head.data(), h->b_head.size());
+  });
 }
 
 int sep_launch(const SepLaunch& a, int n_units, const char* name, hipStream_t st) {
@@ -573,13 +561,13 @@ int sep_plan(const etd_sep* h, int n_songs, const int64_t* N_host, SepPlan* p) {
   const long long uw = nb * h->unit_floats * 4;
   work = uw > work ? uw : work;
   const long long plane = (long long)c.T * c.F * c.n_channels * 4;
-  long long o = 0;
-  p->off_X = o; o += align256(xf * 8);
-  p->off_mag = o; o += align256(segs * plane);
-  p->off_logits = o; o += align256(segs * c.n_instr * plane);
-  p->off_Y = o; o += align256(yf * 8);
-  p->off_work = o; o += align256(work);
-  p->total = o;
+  WsCursor ws;
+  p->off_X = ws.take(xf * 8);
+  p->off_mag = ws.take(segs * plane);
+  p->off_logits = ws.take(segs * c.n_instr * plane);
+  p->off_Y = ws.take(yf * 8);
+  p->off_work = ws.take(work);
+  p->total = ws.off;
   return ETD_OK;
 }
 
@@ -600,8 +588,7 @@ int sep_plan_call(const etd_sep* h, int n_songs, const int64_t* N_host, std::vec
 extern "C" int etd_sep_create(const etd_sep_cfg* cfg, const char* const* instr_names, const char* const* names, const float* const* host_ptrs, const int64_t* numels,
                               int n, etd_sep** out) {
   if (!cfg || !out || !instr_names || !names || !host_ptrs || !numels || n < 0) ETD_FAIL(ETD_EINVAL, "sep_create: null argument");
-  if (cfg->struct_bytes != (int)sizeof(etd_sep_cfg))
-    ETD_FAIL(ETD_EINVAL, "sep_create: etd_sep_cfg is %d bytes here, the caller's is %d -- caller built against another etude_hip.h", (int)sizeof(etd_sep_cfg), cfg->struct_bytes);
+  ETD_CHECK_CFG(cfg, etd_sep_cfg, "sep_create");
   const etd_sep_cfg& c = *cfg;
   if (c.n_instr < 1 || c.n_instr > ETD_SEP_MAX_INSTR) ETD_FAIL(ETD_EINVAL, "sep_create: n_instr = %d must be in 1 .. %d", c.n_instr, ETD_SEP_MAX_INSTR);
   if (c.n_channels < 1 || c.n_channels > ETD_SEP_MAX_CHANNELS) ETD_FAIL(ETD_EINVAL, "sep_create: n_channels = %d must be in 1 .. %d", c.n_channels, ETD_SEP_MAX_CHANNELS);
@@ -657,7 +644,7 @@ extern "C" int etd_sep_create(const etd_sep_cfg* cfg, const char* const* instr_n
   const int I = c.n_instr;
   auto need = [&](const std::string& key, int64_t numel) -> const float* {
     const float* p = wt.get(key, numel);
-    if (p && !sep_finite(p, (size_t)numel)) { g_etd_err = "weight '" + key + "' holds a non-finite value"; return nullptr; }
+    if (p && !finite_all(p, (size_t)numel)) { g_etd_err = "weight '" + key + "' holds a non-finite value"; return nullptr; }
     return p;
   };
   double flops = 0;
@@ -728,7 +715,7 @@ extern "C" int etd_sep_create(const etd_sep_cfg* cfg, const char* const* instr_n
 
 extern "C" void etd_sep_destroy(etd_sep* h) {
   if (!h) return;
-  if (h->on_dev || h->ws) {
+  if (h->pool.uploaded || h->ws) {
     (void)hipDeviceSynchronize();   // kernels of this handle may still be in flight
     h->pool.free_all();
     if (h->ws) (void)hipFree(h->ws);
@@ -845,7 +832,7 @@ extern "C" int etd_sep_debug_istft(etd_sep* h, const float* Y_dev, long long N, 
   const etd_sep_cfg& c = h->cfg;
   const long long Tf = 1 + (N + c.n_fft) / c.hop, rows = (long long)c.n_instr * c.n_channels;
   ETD_TRY(sep_upload(h));
-  ETD_TRY(sep_reserve(h, align256(rows * Tf * c.n_fft * 4), st));
+  ETD_TRY(sep_reserve(h, ws_align(rows * Tf * c.n_fft * 4), st));
   ETD_TRY(sep_istft(h, (const float2*)Y_dev, Tf, N, rows, (float*)h->ws, out_dev, st));
   HIP_TRY(hipGetLastError());
   return ETD_OK;

@@ -128,12 +128,6 @@ __global__ __launch_bounds__(SF_THREADS) void k_sf_db(const SfSong* __restrict__
   }
 }
 
-bool finite_all(const float* p, size_t n) {
-  for (size_t i = 0; i < n; ++i)
-    if (!std::isfinite(p[i])) return false;
-  return true;
-}
-
 }  // namespace
 
 struct etd_stemfeat {
@@ -143,7 +137,6 @@ struct etd_stemfeat {
   std::vector<float> window, mel_w;
   std::vector<float2> twM, twS;
   std::vector<int> mel_start, mel_len, mel_off;
-  bool on_dev = false;
   DevPool pool;
   float *d_window = nullptr, *d_mel_w = nullptr;
   float2 *d_twM = nullptr, *d_twS = nullptr;
@@ -177,19 +170,16 @@ int sf_plan(const etd_stemfeat* h, int n_songs, int instr, const int64_t* N_host
 }
 
 int sf_upload(etd_stemfeat* h) {
-  if (h->on_dev) return ETD_OK;
   DevPool& P = h->pool;
-  const size_t m0 = P.mark();
-  auto fail = [&](int rc) { P.free_from(m0); return rc; };
-  ETD_TRY_OR(fail, P.upload(&h->d_window, h->window.data(), h->window.size()));
-  ETD_TRY_OR(fail, P.upload(&h->d_twM, h->twM.data(), h->twM.size()));
-  ETD_TRY_OR(fail, P.upload(&h->d_twS, h->twS.data(), h->twS.size()));
-  ETD_TRY_OR(fail, P.upload(&h->d_mel_start, h->mel_start.data(), h->mel_start.size()));
-  ETD_TRY_OR(fail, P.upload(&h->d_mel_len, h->mel_len.data(), h->mel_len.size()));
-  ETD_TRY_OR(fail, P.upload(&h->d_mel_off, h->mel_off.data(), h->mel_off.size()));
-  ETD_TRY_OR(fail, P.upload(&h->d_mel_w, h->mel_w.data(), h->mel_w.size()));
-  h->on_dev = true;
-  return ETD_OK;
+  return P.upload_once([&]() -> int {
+    ETD_TRY(P.upload(&h->d_window, h->window.data(), h->window.size()));
+    ETD_TRY(P.upload(&h->d_twM, h->twM.data(), h->twM.size()));
+    ETD_TRY(P.upload(&h->d_twS, h->twS.data(), h->twS.size()));
+    ETD_TRY(P.upload(&h->d_mel_start, h->mel_start.data(), h->mel_start.size()));
+    ETD_TRY(P.upload(&h->d_mel_len, h->mel_len.data(), h->mel_len.size()));
+    ETD_TRY(P.upload(&h->d_mel_off, h->mel_off.data(), h->mel_off.size()));
+    return P.upload(&h->d_mel_w, h->mel_w.data(), h->mel_w.size());
+  });
 }
 
 }  // namespace
@@ -197,8 +187,7 @@ int sf_upload(etd_stemfeat* h) {
 extern "C" int etd_stemfeat_create(const etd_stemfeat_cfg* cfg, const float* window_host, const int32_t* mel_start, const int32_t* mel_len,
                                    const float* mel_w_host, etd_stemfeat** out) {
   if (!cfg || !out) ETD_FAIL(ETD_EINVAL, "stemfeat_create: null argument");
-  if (cfg->struct_bytes != (int)sizeof(etd_stemfeat_cfg))
-    ETD_FAIL(ETD_EINVAL, "stemfeat_create: etd_stemfeat_cfg is %d bytes here, the caller's is %d -- caller built against another etude_hip.h", (int)sizeof(etd_stemfeat_cfg), cfg->struct_bytes);
+  ETD_CHECK_CFG(cfg, etd_stemfeat_cfg, "stemfeat_create");
   const int n_fft = cfg->n_fft;
   if (n_fft < 64 || n_fft > 4096 || (n_fft & (n_fft - 1))) ETD_FAIL(ETD_EINVAL, "stemfeat_create: n_fft = %d must be a power of two in 64 .. 4096", n_fft);
   if (cfg->hop < 1 || cfg->hop > (1 << 20)) ETD_FAIL(ETD_EINVAL, "stemfeat_create: hop = %d must be in 1 .. 2^20", cfg->hop);
@@ -237,7 +226,7 @@ extern "C" int etd_stemfeat_create(const etd_stemfeat_cfg* cfg, const float* win
 
 extern "C" void etd_stemfeat_destroy(etd_stemfeat* h) {
   if (!h) return;
-  if (h->on_dev || h->ws || h->tab) {
+  if (h->pool.uploaded || h->ws || h->tab) {
     (void)hipDeviceSynchronize();   // kernels of this handle may still be in flight
     h->pool.free_all();
     if (h->ws) (void)hipFree(h->ws);
@@ -282,8 +271,7 @@ extern "C" int etd_stemfeat_run(etd_stemfeat* h, const float* const* wav_ptrs, i
     HIP_TRY(hipMalloc((void**)&h->tab, (size_t)n_songs * sizeof(SfSong)));
     h->tab_cap = n_songs;
   }
-  HIP_TRY(hipMemcpyAsync(h->tab, tab.data(), tab.size() * sizeof(SfSong), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipStreamSynchronize(st));                   // (tab is host memory of this call)
+  ETD_TRY(upload_table(st, h->tab, tab));
   float* wgmax = h->ws;
   float* ref = h->ws + blocks;
   const etd_stemfeat_cfg& c = h->cfg;

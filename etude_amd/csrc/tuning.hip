@@ -188,8 +188,6 @@ __global__ __launch_bounds__(TN_TAIL_THREADS) void k_tn_tail(const TnArgs a) {
   }
 }
 
-inline long long tn_align(long long x) { return (x + 255) & ~255LL; }
-
 }  // namespace
 
 struct etd_tuning {
@@ -197,7 +195,6 @@ struct etd_tuning {
   std::vector<float2> twM, twS;
   std::vector<double> rp, cp, tt;
   std::vector<int> iv;
-  bool on_dev = false;
   DevPool pool;
   float* d_window = nullptr;
   float2 *d_twM = nullptr, *d_twS = nullptr;
@@ -212,7 +209,8 @@ namespace {
 int tn_plan(const etd_tuning* h, int n_songs, const int64_t* N_host, std::vector<TnSong>* tab, long long* ws_bytes, long long* blocks) {
   if (!h || !N_host) ETD_FAIL(ETD_EINVAL, "tuning: null argument");
   if (n_songs < 1 || n_songs > TN_MAX_SONGS) ETD_FAIL(ETD_EINVAL, "tuning: %d songs in one call (need 1 .. %d)", n_songs, TN_MAX_SONGS);
-  long long off = tn_align((long long)n_songs * (long long)sizeof(TnSong)), blk = 0;
+  WsCursor ws{ws_align((long long)n_songs * (long long)sizeof(TnSong))};
+  long long blk = 0;
   for (int s = 0; s < n_songs; ++s) {
     const long long N = N_host[s];
     if (N < TN_MIN_N) ETD_FAIL(ETD_EINVAL, "tuning: song %d has N = %lld (need >= %d, two windows)", s, N, TN_MIN_N);
@@ -224,36 +222,33 @@ int tn_plan(const etd_tuning* h, int n_songs, const int64_t* N_host, std::vector
     g.G = (g.F + TN_GROUP - 1) / TN_GROUP;
     g.blk0 = blk;
     blk += g.G;
-    auto take = [&](long long bytes) { const long long o = off; off += tn_align(bytes); return o; };
-    g.off_part = take(4LL * TN_BINS * g.G);
-    g.off_Y = take(4LL * TN_BINS);
-    g.off_Yi = take(8LL * TN_LOGF);
-    g.off_R = take(8LL * TN_LOGF);
-    g.off_sim = take(8LL * TN_THETA);
+    g.off_part = ws.take(4LL * TN_BINS * g.G);
+    g.off_Y = ws.take(4LL * TN_BINS);
+    g.off_Yi = ws.take(8LL * TN_LOGF);
+    g.off_R = ws.take(8LL * TN_LOGF);
+    g.off_sim = ws.take(8LL * TN_THETA);
     if (tab) (*tab)[s] = g;
   }
-  if (ws_bytes) *ws_bytes = off;
+  if (ws_bytes) *ws_bytes = ws.off;
   if (blocks) *blocks = blk;
   return ETD_OK;
 }
 
 int tn_upload(etd_tuning* h) {
-  if (h->on_dev) return ETD_OK;
   DevPool& P = h->pool;
-  const size_t m0 = P.mark();
-  auto fail = [&](int rc) { P.free_from(m0); return rc; };
-  ETD_TRY_OR(fail, P.upload(&h->d_window, h->window.data(), h->window.size()));
-  ETD_TRY_OR(fail, P.upload(&h->d_twM, h->twM.data(), h->twM.size()));
-  ETD_TRY_OR(fail, P.upload(&h->d_twS, h->twS.data(), h->twS.size()));
-  ETD_TRY_OR(fail, P.upload(&h->d_rp, h->rp.data(), h->rp.size()));
-  ETD_TRY_OR(fail, P.upload(&h->d_cp, h->cp.data(), h->cp.size()));
-  ETD_TRY_OR(fail, P.upload(&h->d_tt, h->tt.data(), h->tt.size()));
-  ETD_TRY_OR(fail, P.upload(&h->d_iv, h->iv.data(), h->iv.size()));
-  // both kernels ask for more dynamic LDS than the 64 KB a launch gets without saying so
-  ETD_TRY_OR(fail, ETD_HIP_RC(hipFuncSetAttribute((const void*)k_tn_frames, hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES)));
-  ETD_TRY_OR(fail, ETD_HIP_RC(hipFuncSetAttribute((const void*)k_tn_tail, hipFuncAttributeMaxDynamicSharedMemorySize, TN_BINS * (int)sizeof(double))));
-  h->on_dev = true;
-  return ETD_OK;
+  return P.upload_once([&]() -> int {
+    ETD_TRY(P.upload(&h->d_window, h->window.data(), h->window.size()));
+    ETD_TRY(P.upload(&h->d_twM, h->twM.data(), h->twM.size()));
+    ETD_TRY(P.upload(&h->d_twS, h->twS.data(), h->twS.size()));
+    ETD_TRY(P.upload(&h->d_rp, h->rp.data(), h->rp.size()));
+    ETD_TRY(P.upload(&h->d_cp, h->cp.data(), h->cp.size()));
+    ETD_TRY(P.upload(&h->d_tt, h->tt.data(), h->tt.size()));
+    ETD_TRY(P.upload(&h->d_iv, h->iv.data(), h->iv.size()));
+    // both kernels ask for more dynamic LDS than the 64 KB a launch gets without saying so
+    HIP_TRY(hipFuncSetAttribute((const void*)k_tn_frames, hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
+    HIP_TRY(hipFuncSetAttribute((const void*)k_tn_tail, hipFuncAttributeMaxDynamicSharedMemorySize, TN_BINS * (int)sizeof(double)));
+    return ETD_OK;
+  });
 }
 
 }  // namespace
@@ -267,8 +262,7 @@ extern "C" int etd_tuning_limits(long long* min_samples, long long* max_samples,
 
 extern "C" int etd_tuning_create(const etd_tuning_cfg* cfg, etd_tuning** out) {
   if (!cfg || !out) ETD_FAIL(ETD_EINVAL, "tuning_create: null argument");
-  if (cfg->struct_bytes != (int)sizeof(etd_tuning_cfg))
-    ETD_FAIL(ETD_EINVAL, "tuning_create: etd_tuning_cfg is %d bytes here, the caller's is %d -- caller built against another etude_hip.h", (int)sizeof(etd_tuning_cfg), cfg->struct_bytes);
+  ETD_CHECK_CFG(cfg, etd_tuning_cfg, "tuning_create");
   if (cfg->sample_rate != TN_FS || cfg->n_fft != TN_NFFT || cfg->hop != TN_HOP)
     ETD_FAIL(ETD_EINVAL, "tuning_create: this build is fixed to %d Hz, n_fft %d, hop %d (got %d, %d, %d)", TN_FS, TN_NFFT, TN_HOP, cfg->sample_rate, cfg->n_fft, cfg->hop);
   etd_tuning* h = new etd_tuning();
@@ -299,10 +293,7 @@ extern "C" int etd_tuning_create(const etd_tuning_cfg* cfg, etd_tuning** out) {
 
 extern "C" void etd_tuning_destroy(etd_tuning* h) {
   if (!h) return;
-  if (h->on_dev) {
-    (void)hipDeviceSynchronize();   // kernels of this handle may still be in flight
-    h->pool.free_all();
-  }
+  h->pool.release_uploaded();
   delete h;
 }
 
@@ -358,8 +349,7 @@ extern "C" int etd_tuning_run(etd_tuning* h, const float* const* wav_ptrs, int n
       if (h->tap_frame[i] >= tab[h->tap_song].F) ETD_FAIL(ETD_EINVAL, "tuning_run: the power tap names frame %d of %lld", h->tap_frame[i], tab[h->tap_song].F);
   }
   ETD_TRY(tn_upload(h));
-  HIP_TRY(hipMemcpyAsync(workspace_dev, tab.data(), tab.size() * sizeof(TnSong), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipStreamSynchronize(st));                   // (tab is host memory of this call)
+  ETD_TRY(upload_table(st, workspace_dev, tab));
   TnArgs a;
   a.tab = (const TnSong*)workspace_dev; a.n_songs = n_songs; a.ws = (char*)workspace_dev;
   a.window = h->d_window; a.twM = h->d_twM; a.twS = h->d_twS; a.rp = h->d_rp; a.cp = h->d_cp; a.iv = h->d_iv; a.tt = h->d_tt;

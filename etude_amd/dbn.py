@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._engine import Engine, i64, nonneg
 
 IN_ACTIVATIONS, IN_LOGITS, IN_COMBINED = 0, 1, 2          # ETD_DBN_IN_*
 
@@ -48,14 +49,12 @@ def describe(cfg: "_lib.DbnCfg", hmm_index: int, tables: bool = False) -> dict:
 
 
 def workspace_bytes(cfg: "_lib.DbnCfg", T: int, hmm_index: int = -1) -> int:
-    n = int(_lib.lib().etd_dbn_workspace_bytes(C.byref(cfg), int(T), int(hmm_index)))
-    if n < 0:
-        _lib.check(n, "etd_dbn_workspace_bytes")
-    return n
+    return nonneg(_lib.lib().etd_dbn_workspace_bytes(C.byref(cfg), int(T), int(hmm_index)), "etd_dbn_workspace_bytes")
 
 
-class DBNEngine:
+class DBNEngine(Engine):
     """One etd_dbn handle: the beat HMM and one bar HMM per entry of ``beats_per_bar``."""
+    _destroy = "etd_dbn_destroy"
 
     def __init__(self, fps: float, min_bpm: float, max_bpm: float, threshold: float = 0.0, beats_per_bar: Sequence[int] = (), device="cuda", **model):
         self.device = torch.device(device)
@@ -70,13 +69,7 @@ class DBNEngine:
         h = C.c_void_p()
         with torch.cuda.device(self.device):
             _lib.check(self._lib.etd_dbn_create(C.byref(self.cfg), C.byref(h)), "etd_dbn_create")
-        self._h = h
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            self._lib.etd_dbn_destroy(h)
-            self._h = None
+        self._adopt(h)
 
     def track(self, x: torch.Tensor, Ts: Sequence[int], kind: int = IN_ACTIVATIONS) -> List[Tuple[np.ndarray, np.ndarray, int]]:
         """x: device fp32 [sum T][2], the songs back to back -> per song (beat frames [n] int32, downbeat rows [m][2] int32 of (frame, beat number), index of the
@@ -86,18 +79,18 @@ class DBNEngine:
             return []
         if x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != 2 or x.shape[0] != int(sum(Ts)) or not x.is_contiguous() or x.device != self.device:
             raise ValueError(f"track: need a contiguous fp32 [sum T = {int(sum(Ts))}][2] tensor on {self.device}, got {tuple(x.shape)} {x.dtype} on {x.device}")
-        T_arr = (C.c_int64 * n)(*[int(t) for t in Ts])
+        T_arr = i64(Ts)
         cap_b = cap_d = max(16, int(sum(Ts)) // max(1, int(60.0 * self.fps / self.cfg.max_bpm) - 1) + 2 * n)
         with torch.cuda.device(self.device):
-            st = torch.cuda.current_stream(self.device).cuda_stream
+            st = self._stream(self.device)
             while True:
                 bf = np.zeros(cap_b, np.int32)
                 df, dn = np.zeros(cap_d, np.int32), np.zeros(cap_d, np.int32)
                 bo, do = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
                 choice = np.zeros(n, np.int32)
                 need = (C.c_longlong * 2)()
-                rc = self._lib.etd_dbn_track(self._h, C.c_void_p(x.data_ptr()), int(kind), n, T_arr, bf.ctypes.data, cap_b, bo.ctypes.data,
-                                             df.ctypes.data, dn.ctypes.data, cap_d, do.ctypes.data, choice.ctypes.data, need, C.c_void_p(st))
+                rc = self._lib.etd_dbn_track(self.h, C.c_void_p(x.data_ptr()), int(kind), n, T_arr, bf.ctypes.data, cap_b, bo.ctypes.data,
+                                             df.ctypes.data, dn.ctypes.data, cap_d, do.ctypes.data, choice.ctypes.data, need, st)
                 if rc == -12 and (need[0] > cap_b or need[1] > cap_d):          # ETD_ENOMEM: the contract of etd_mpe2note
                     cap_b, cap_d = max(cap_b, int(need[0])), max(cap_d, int(need[1]))
                     continue
@@ -121,7 +114,7 @@ class DBNEngine:
         lp = C.c_double()
         with torch.cuda.device(self.device):
             torch.cuda.synchronize(self.device)
-            _lib.check(self._lib.etd_dbn_debug_viterbi(self._h, int(hmm_index), C.c_void_p(d.data_ptr()), d.shape[0], path.ctypes.data, C.byref(lp)),
+            _lib.check(self._lib.etd_dbn_debug_viterbi(self.h, int(hmm_index), C.c_void_p(d.data_ptr()), d.shape[0], path.ctypes.data, C.byref(lp)),
                        "etd_dbn_debug_viterbi")
         return path, lp.value
 

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._engine import Engine
 
 
 def _resample_table(sr_in: int, sr_out: int, lowpass_filter_width: int = 6, rolloff: float = 0.99):
@@ -48,7 +49,8 @@ def _mel_csr(n_freqs: int, f_max: float, n_mels: int, sample_rate: int):
 
 
 def _dense_to_csr(fb: np.ndarray):
-    """Band m as the span from its first to its last non-zero weight (zeros inside the span are stored; an all-zero band has length 0)."""
+    """fb [bins][n_mels] -> (start, length, weights): band m as the span from its first to its last non-zero weight (zeros inside the span are stored; an
+    all-zero band has length 0).  Also the CSR form of ``StemFeatures``' filterbank."""
     n_mels = fb.shape[1]
     start = np.zeros(n_mels, np.int32)
     length = np.zeros(n_mels, np.int32)
@@ -62,8 +64,9 @@ def _dense_to_csr(fb: np.ndarray):
     return start, length, wcat
 
 
-class FrontEnd:
+class FrontEnd(Engine):
     """wav (device, planar [C][L] fp32) -> log-mel features (device, [T][n_mels] fp32)."""
+    _destroy = "etd_frontend_destroy"
 
     def __init__(self, sr_in: int, sr_out: int = 16000, n_fft: int = 2048, hop: int = 256, n_mels: int = 256,
                  log_offset: float = 1e-8, pad_mode: str = "reflect", win_length: int | None = None):
@@ -86,26 +89,25 @@ class FrontEnd:
         _lib.check(lib.etd_frontend_create(self.sr_in, self.sr_out, orig, new, kt.shape[0], width, kt.ctypes.data, n_fft, hop,
                                            win.ctypes.data, n_mels, ms.ctypes.data, ml.ctypes.data, mw.ctypes.data,
                                            log_offset, C.byref(h)), "etd_frontend_create")
-        self._h = h
+        self._adopt(h)
         if pad_mode not in ("reflect", "constant"):
             raise ValueError(f"pad_mode {pad_mode!r}: only 'reflect' and 'constant' are implemented")
         _lib.check(lib.etd_frontend_set_pad_mode(h, 1 if pad_mode == "constant" else 0), "etd_frontend_set_pad_mode")
 
     def num_frames(self, n_in: int) -> int:
-        return int(_lib.lib().etd_frontend_num_frames(self._h, n_in))
+        return int(_lib.lib().etd_frontend_num_frames(self.h, n_in))
 
     def __call__(self, wav: torch.Tensor) -> torch.Tensor:
         assert wav.is_cuda and wav.dtype == torch.float32 and wav.dim() == 2 and wav.is_contiguous()
         lib = _lib.lib()
         c, n = wav.shape
-        n16 = int(lib.etd_frontend_resampled_len(self._h, n))
-        T = int(lib.etd_frontend_num_frames(self._h, n))
+        n16 = int(lib.etd_frontend_resampled_len(self.h, n))
+        T = int(lib.etd_frontend_num_frames(self.h, n))
         res = torch.empty(n16, dtype=torch.float32, device=wav.device)
         feat = torch.empty((T, self.n_mels), dtype=torch.float32, device=wav.device)
         out_t = C.c_longlong()
-        st = torch.cuda.current_stream(wav.device).cuda_stream
-        _lib.check(lib.etd_frontend_run(self._h, wav.data_ptr(), c, n, res.data_ptr(), feat.data_ptr(), T, C.byref(out_t),
-                                        C.c_void_p(st)), "etd_frontend_run")
+        _lib.check(lib.etd_frontend_run(self.h, wav.data_ptr(), c, n, res.data_ptr(), feat.data_ptr(), T, C.byref(out_t),
+                                        self._stream(wav.device)), "etd_frontend_run")
         self.last_resampled = res
         return feat
 
@@ -114,18 +116,6 @@ class FrontEnd:
         assert wav.is_cuda and wav.dtype == torch.float32 and wav.dim() == 2 and wav.is_contiguous()
         lib = _lib.lib()
         c, n = wav.shape
-        res = torch.empty(int(lib.etd_frontend_resampled_len(self._h, n)), dtype=torch.float32, device=wav.device)
-        st = torch.cuda.current_stream(wav.device).cuda_stream
-        _lib.check(lib.etd_frontend_run(self._h, wav.data_ptr(), c, n, res.data_ptr(), None, 0, None, C.c_void_p(st)), "etd_frontend_run")
+        res = torch.empty(int(lib.etd_frontend_resampled_len(self.h, n)), dtype=torch.float32, device=wav.device)
+        _lib.check(lib.etd_frontend_run(self.h, wav.data_ptr(), c, n, res.data_ptr(), None, 0, None, self._stream(wav.device)), "etd_frontend_run")
         return res
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.lib().etd_frontend_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

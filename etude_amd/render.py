@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._engine import Engine, nonneg
 
 NOTE_DTYPE = np.dtype([("onset", "<f8"), ("offset", "<f8"), ("pitch", "<i4"), ("velocity", "<i4")])   # == etd_note (extractor.NOTE_DTYPE)
 DEFAULT_WORKSPACE_BUDGET = 8 << 30
@@ -102,9 +103,10 @@ class Packed:
         return len(self.cents)
 
 
-class NoteRenderer:
+class NoteRenderer(Engine):
     """Note lists -> 1-d float32 device tensors.  ``workspace_budget`` bytes bound the samples plus the device workspace of one launch sequence: ``render_many``
     splits a call into sub-batches under it, which changes no cover's bits.  Constructing and ``pack`` need no GPU; rendering does: there is no CPU path."""
+    _destroy = "etd_render_destroy"
 
     def __init__(self, sample_rate: int = 22050, voice: PianoVoice = PianoVoice(), device: Union[str, torch.device] = "cuda",
                  workspace_budget: int = DEFAULT_WORKSPACE_BUDGET):
@@ -128,26 +130,7 @@ class NoteRenderer:
             _lib.check(self._lib.etd_render_create(C.byref(cfg), C.byref(h)), "etd_render_create")
         except _lib.EtudeHipError as e:
             raise ValueError(str(e)) from None
-        self.h = h
-
-    def close(self) -> None:
-        h = getattr(self, "h", None)
-        if h is not None and h.value:
-            self._lib.etd_render_destroy(h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:      # noqa: BLE001
-            pass
-
-    def _device(self) -> torch.device:
-        if self.device.type != "cuda" or not torch.cuda.is_available():
-            raise _lib.EtudeHipError("etude_amd.NoteRenderer needs a ROCm GPU (device='cuda'); there is no CPU path")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        return self.device
+        self._adopt(h)
 
     # ---- host
     def pack(self, notes_list: Sequence, tuning_cents: Optional[Sequence[float]] = None, num_samples: Union[None, int, Sequence[Optional[int]]] = None) -> Packed:
@@ -206,10 +189,7 @@ class NoteRenderer:
 
     def bytes_for(self, note_offsets: np.ndarray, N: np.ndarray) -> int:
         """host only: device workspace of one launch sequence"""
-        b = int(self._lib.etd_render_bytes(self.h, len(N), note_offsets.ctypes.data_as(_lib.c_i64_p), N.ctypes.data_as(_lib.c_i64_p)))
-        if b < 0:
-            _lib.check(b, "etd_render_bytes")
-        return b
+        return nonneg(self._lib.etd_render_bytes(self.h, len(N), note_offsets.ctypes.data_as(_lib.c_i64_p), N.ctypes.data_as(_lib.c_i64_p)), "etd_render_bytes")
 
     def batches(self, p: Packed) -> List[List[int]]:
         """consecutive covers grouped so that every group's samples and workspace fit the budget (a cover that alone exceeds it is refused) and no group holds
@@ -246,10 +226,9 @@ class NoteRenderer:
         with torch.cuda.device(dev):
             if ws is None:
                 ws = torch.empty(self.bytes_for(note_offsets, N), dtype=torch.uint8, device=dev)
-            st = torch.cuda.current_stream(dev).cuda_stream
             _lib.check(self._lib.etd_render_run(self.h, notes.ctypes.data, note_offsets.ctypes.data_as(_lib.c_i64_p), cents.ctypes.data, len(N),
                                                 N.ctypes.data_as(_lib.c_i64_p), sample_offsets.ctypes.data_as(_lib.c_i64_p), C.c_void_p(out.data_ptr()),
-                                                C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(st)), "etd_render_run")
+                                                C.c_void_p(ws.data_ptr()), ws.numel(), self._stream(dev)), "etd_render_run")
             ws.record_stream(torch.cuda.current_stream(dev))
 
     def iter_rendered(self, p: Packed) -> Iterator[Tuple[List[int], List[torch.Tensor]]]:

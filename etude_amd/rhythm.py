@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._engine import Engine
 
 RGC_ERRORS = {1: "Not enough onsets for IOI calculation.", 2: "Not enough IOIs to analyze.", 3: "Not enough unique IOIs to determine a grid.",
               4: "Could not infer a valid rhythmic grid period (tau)."}
@@ -30,9 +31,10 @@ def limits() -> dict:
     return dict(zip(("max_onsets", "max_covers", "max_top_k", "max_n_gram"), [x.value for x in v]))
 
 
-class RhythmMetrics:
+class RhythmMetrics(Engine):
     """Onset lists -> the reference's two result dicts merged.  A cover is any sequence of onsets in seconds (``np.unique`` sorts and de-duplicates it, as
     ``get_onsets_from_file`` does), at most 8 192 distinct ones.  Constructing needs no GPU; ``metrics_many`` does: there is no CPU path."""
+    _destroy = "etd_rhythm_destroy"
 
     def __init__(self, top_k: int = 8, precision_digits: int = 4, n_gram: int = 8, n_clusters: int = 8, min_ioi: float = 0.0625, max_ioi: float = 4.0,
                  device: Union[str, torch.device] = "cuda"):
@@ -45,21 +47,8 @@ class RhythmMetrics:
         cfg = _lib.RhythmCfg(n_random=N_RANDOM, random_host=self.random.ctypes.data_as(C.POINTER(C.c_double)), **self.params)
         h = C.c_void_p()
         _lib.check(self._lib.etd_rhythm_create(C.byref(cfg), C.byref(h)), "etd_rhythm_create")
-        self.h = h
+        self._adopt(h)
         self._tap = None
-
-    def __del__(self):
-        h = getattr(self, "h", None)
-        if h is not None and h.value:
-            self._lib.etd_rhythm_destroy(h)
-            self.h = None
-
-    def _device(self) -> torch.device:
-        if self.device.type != "cuda" or not torch.cuda.is_available():
-            raise _lib.EtudeHipError("etude_amd.RhythmMetrics needs a ROCm GPU (device='cuda'); there is no CPU path")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        return self.device
 
     def pack(self, onsets_list: Sequence) -> Tuple[np.ndarray, np.ndarray]:
         """host: every cover through ``np.unique`` -> (one int64 buffer holding the offsets [B + 1] and, behind them, the onsets' fp64 bits; the offsets).  Checks that
@@ -107,10 +96,9 @@ class RhythmMetrics:
                 tap = (torch.full((total,), float("nan"), dtype=torch.float64, device=dev), torch.full((total,), -1, dtype=torch.int8, device=dev),
                        torch.full((B, 8), float("nan"), dtype=torch.float64, device=dev))
                 _lib.check(self._lib.etd_rhythm_debug_logioi(self.h, *[C.c_void_p(t.data_ptr()) for t in tap]), "etd_rhythm_debug_logioi")
-            st = torch.cuda.current_stream(dev).cuda_stream
             off = np.ascontiguousarray(offsets, np.int64)
             _lib.check(self._lib.etd_rhythm_run(self.h, C.c_void_p(base + 8 * (B + 1)), C.c_void_p(base), off.ctypes.data_as(_lib.c_i64_p), B,
-                                                C.c_void_p(out.data_ptr()), C.c_void_p(status.data_ptr()), C.c_void_p(st)), "etd_rhythm_run")
+                                                C.c_void_p(out.data_ptr()), C.c_void_p(status.data_ptr()), self._stream(dev)), "etd_rhythm_run")
             res = out.cpu().numpy(), status.cpu().numpy()
             if tap is not None:
                 self._tap = dict(logioi=tap[0].cpu().numpy(), labels=tap[1].cpu().numpy(), centres=tap[2].cpu().numpy())

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._engine import Engine, hold, i64, nonneg, ptrs
 
 LEVELS = 6            # ETD_SEP_LEVELS
 MAX_INSTR = 16        # ETD_SEP_MAX_INSTR
@@ -138,7 +139,7 @@ def load_separator_state(path) -> Dict[str, np.ndarray]:
     return {k: np.ascontiguousarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v), np.float32) for k, v in sd.items()}
 
 
-class StemSeparator:
+class StemSeparator(Engine):
     """A song's audio -> its stems, on the device.
 
     A song is [n_channels][N] float32 (torch tensor on the device or the host, or a numpy array), or [N] mono (duplicated to n_channels), finite, N >= 1.
@@ -147,6 +148,7 @@ class StemSeparator:
     ``workspace_bytes`` bounds the device workspace: songs are grouped and (segment, instrument) units sub-batched under it; one song with one unit is the floor
     (``workspace_total_bytes`` tells what a call holds).
     Constructing needs no GPU; separating does: there is no CPU path."""
+    _destroy = "etd_sep_destroy"
 
     def __init__(self, config: Optional[SeparatorConfig] = None, state: Optional[Dict] = None, seed: int = 0, device: Union[str, torch.device] = "cuda",
                  workspace_bytes: int = 4 << 30):
@@ -173,46 +175,29 @@ class StemSeparator:
         h = C.c_void_p()
         _lib.check(self._lib.etd_sep_create(C.byref(ccfg), instr, names, ptrs, numels, n, C.byref(h)), "etd_sep_create")
         del keep
-        self._h = h
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            self._lib.etd_sep_destroy(h)
-            self._h = None
+        self._adopt(h)
 
     # ------------------------------------------------------------------ host arithmetic
     def num_frames(self, N: int) -> int:
-        Tf = int(self._lib.etd_sep_num_frames(self._h, int(N)))
+        Tf = int(self._lib.etd_sep_num_frames(self.h, int(N)))
         if Tf < 0:
             raise ValueError(f"num_frames: N must be >= 1, got {N}")
         return Tf
 
     @property
     def unit_bytes(self) -> int:
-        return int(self._lib.etd_sep_unit_bytes(self._h))
+        return int(self._lib.etd_sep_unit_bytes(self.h))
 
     def segment_flops(self) -> float:
-        return float(self._lib.etd_sep_segment_flops(self._h))
+        return float(self._lib.etd_sep_segment_flops(self.h))
 
     def workspace_total_bytes(self, Ns: Sequence[int]) -> int:
-        arr = (C.c_int64 * len(Ns))(*[int(n) for n in Ns])
-        b = int(self._lib.etd_sep_workspace_bytes(self._h, len(Ns), arr))
-        if b < 0:
-            _lib.check(b, "etd_sep_workspace_bytes")
-        return b
+        return nonneg(self._lib.etd_sep_workspace_bytes(self.h, len(Ns), i64(Ns)), "etd_sep_workspace_bytes")
 
     def save(self, path) -> None:
         torch.save({k: torch.from_numpy(v) for k, v in self.state.items()}, str(path))
 
     # ------------------------------------------------------------------ device
-    def _device(self) -> torch.device:
-        if self.device.type != "cuda" or not torch.cuda.is_available():
-            raise _lib.EtudeHipError("etude_amd.StemSeparator needs a ROCm GPU (device='cuda'); there is no CPU path")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        return self.device
-
     def _song_shape(self, i: int, x) -> tuple:
         shp = tuple(x.shape) if hasattr(x, "shape") else None
         if shp is None or len(shp) not in (1, 2):
@@ -231,27 +216,22 @@ class StemSeparator:
         dev = self._device()
         nc, ni = self.config.n_channels, len(self.config.instruments)
         songs = []
-        for i, x in enumerate(wavs):
+        for x in wavs:
             t = torch.as_tensor(x).to(dev, torch.float32)
             if t.dim() == 1:
                 t = t[None]
             if t.shape[0] == 1 and nc > 1:
                 t = t.expand(nc, -1)                   # mono: every channel is the one given
-            t = t.contiguous()
-            if not bool(torch.isfinite(t).all()):
-                raise ValueError(f"song {i}: the audio holds a non-finite value")
-            songs.append(t)
+            songs.append(t.contiguous())
+        bad = torch.stack([torch.isfinite(t).all() for t in songs]).logical_not().nonzero().flatten().tolist()      # (one host synchronisation for the call)
+        if bad:
+            raise ValueError(f"song {bad[0]}: the audio holds a non-finite value")
         n = len(songs)
         Ns = [s[-1] for s in shapes]
         outs = [torch.empty((ni, nc, N), dtype=torch.float32, device=dev) for N in Ns]
-        ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in songs])
-        optrs = (C.c_void_p * n)(*[t.data_ptr() for t in outs])
-        N_arr = (C.c_int64 * n)(*Ns)
         with torch.cuda.device(dev):
-            st = torch.cuda.current_stream(dev)
-            _lib.check(self._lib.etd_sep_run(self._h, ptrs, n, N_arr, optrs, C.c_void_p(st.cuda_stream)), "etd_sep_run")
-            for t in songs:          # (an uploaded copy may be freed right after this call: its memory stays valid for work queued on this stream)
-                t.record_stream(st)
+            _lib.check(self._lib.etd_sep_run(self.h, ptrs(songs), n, i64(Ns), ptrs(outs), self._stream(dev)), "etd_sep_run")
+            hold(songs, dev)
         return outs
 
     def separate(self, wav) -> Dict[str, np.ndarray]:
@@ -260,9 +240,6 @@ class StemSeparator:
         return {name: np.ascontiguousarray(out[i].T) for i, name in enumerate(self.config.instruments)}
 
     # ------------------------------------------------------------------ test hooks (include/etude_hip_debug.h)
-    def _stream(self, dev):
-        return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
     def debug_stft(self, wav: torch.Tensor) -> torch.Tensor:
         """[n_channels][N] device tensor -> X [n_channels][Tf][n_fft / 2 + 1] complex64"""
         dev = self._device()
@@ -270,7 +247,7 @@ class StemSeparator:
         N = int(wav.shape[1])
         X = torch.empty((self.config.n_channels, self.num_frames(N), self.config.n_fft // 2 + 1, 2), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            _lib.check(self._lib.etd_sep_debug_stft(self._h, C.c_void_p(wav.data_ptr()), N, C.c_void_p(X.data_ptr()), self._stream(dev)), "etd_sep_debug_stft")
+            _lib.check(self._lib.etd_sep_debug_stft(self.h, C.c_void_p(wav.data_ptr()), N, C.c_void_p(X.data_ptr()), self._stream(dev)), "etd_sep_debug_stft")
         return torch.view_as_complex(X)
 
     def debug_layer(self, instr: int, kind: int, layer: int, x0: torch.Tensor, x1: Optional[torch.Tensor] = None):
@@ -292,7 +269,7 @@ class StemSeparator:
         else:
             pre = torch.empty((n, cfg.T, cfg.F, cfg.n_channels), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            _lib.check(self._lib.etd_sep_debug_layer(self._h, int(instr), int(kind), int(layer), p(x0), p(x1), n, p(pre), p(act), self._stream(dev)), "etd_sep_debug_layer")
+            _lib.check(self._lib.etd_sep_debug_layer(self.h, int(instr), int(kind), int(layer), p(x0), p(x1), n, p(pre), p(act), self._stream(dev)), "etd_sep_debug_layer")
         return (pre, act) if kind == 0 else act if kind == 1 else pre
 
     def debug_mask(self, logits: torch.Tensor, mag: torch.Tensor, X: torch.Tensor) -> torch.Tensor:
@@ -304,7 +281,7 @@ class StemSeparator:
         Tf = int(X.shape[1])
         Y = torch.empty((len(cfg.instruments), cfg.n_channels, Tf, cfg.F, 2), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            _lib.check(self._lib.etd_sep_debug_mask(self._h, C.c_void_p(logits.data_ptr()), C.c_void_p(mag.data_ptr()), C.c_void_p(Xr.data_ptr()), Tf,
+            _lib.check(self._lib.etd_sep_debug_mask(self.h, C.c_void_p(logits.data_ptr()), C.c_void_p(mag.data_ptr()), C.c_void_p(Xr.data_ptr()), Tf,
                                                     C.c_void_p(Y.data_ptr()), self._stream(dev)), "etd_sep_debug_mask")
         return torch.view_as_complex(Y)
 
@@ -317,5 +294,5 @@ class StemSeparator:
             raise ValueError(f"debug_istft: Y has shape {tuple(Y.shape)}")
         out = torch.empty((len(cfg.instruments), cfg.n_channels, int(N)), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            _lib.check(self._lib.etd_sep_debug_istft(self._h, C.c_void_p(Yr.data_ptr()), int(N), C.c_void_p(out.data_ptr()), self._stream(dev)), "etd_sep_debug_istft")
+            _lib.check(self._lib.etd_sep_debug_istft(self.h, C.c_void_p(Yr.data_ptr()), int(N), C.c_void_p(out.data_ptr()), self._stream(dev)), "etd_sep_debug_istft")
         return out

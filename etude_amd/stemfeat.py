@@ -16,6 +16,8 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._engine import Engine, hold, i64, nonneg, ptrs
+from .frontend import _dense_to_csr
 
 FRAMINGS = {"librosa": 0, "librosa_reflect": 1, "spleeter": 2}          # ETD_STEMFEAT_*
 
@@ -48,20 +50,11 @@ def mel_filterbank(sr: int = 44100, n_fft: int = 4096, n_mels: int = 128, fmin: 
 
 
 def _csr(fb: np.ndarray):
-    """[n_mels][bins] -> (start, length, weights) of each band's span of non-zeros (zeros inside a span are kept)"""
-    start, length, w = [], [], []
-    for row in fb:
-        nz = np.flatnonzero(row)
-        if nz.size == 0:
-            start.append(0); length.append(0)
-            continue
-        start.append(int(nz[0])); length.append(int(nz[-1] - nz[0] + 1))
-        w.append(row[nz[0]:nz[-1] + 1])
-    weights = np.ascontiguousarray(np.concatenate(w) if w else np.zeros(1, np.float32), np.float32)
-    return np.asarray(start, np.int32), np.asarray(length, np.int32), weights
+    """[n_mels][bins] -> (start, length, weights) of each band's span of non-zeros (zeros inside a span are kept): the front end's, on its [bins][n_mels] layout"""
+    return _dense_to_csr(fb.T)
 
 
-class StemFeatures:
+class StemFeatures(Engine):
     """Separated stems -> the Beat-Transformer's mel-dB features, on the device.
 
     A song is [instr][channels][N] float32 (torch tensor on the device or the host, or a numpy array), finite, N >= 1.  Spleeter's ``{name: [N][channels]}`` dict maps
@@ -70,6 +63,7 @@ class StemFeatures:
     ``framing``: "librosa" (librosa.stft >= 0.10: centred frames, zeros outside the signal, T = 1 + N // hop), "librosa_reflect" (librosa < 0.10: reflection;
     N <= n_fft / 2 is refused) or "spleeter" (Spleeter 2.x's own STFT: n_fft zeros on both ends, T = 1 + (N + n_fft) // hop).
     Constructing needs no GPU (``num_frames`` is host arithmetic); ``features`` / ``features_many`` do: there is no CPU path."""
+    _destroy = "etd_stemfeat_destroy"
 
     def __init__(self, sample_rate: int = 44100, n_fft: int = 4096, hop: int = 1024, n_mels: int = 128, fmin: float = 30.0, fmax: float = 11000.0,
                  top_db: float = 80.0, amin: float = 1e-10, framing: str = "librosa", device: Union[str, torch.device] = "cuda"):
@@ -92,26 +86,13 @@ class StemFeatures:
         self._lib = _lib.lib()
         h = C.c_void_p()
         _lib.check(self._lib.etd_stemfeat_create(C.byref(cfg), window.ctypes.data, start.ctypes.data, length.ctypes.data, w.ctypes.data, C.byref(h)), "etd_stemfeat_create")
-        self._h = h
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            self._lib.etd_stemfeat_destroy(h)
-            self._h = None
+        self._adopt(h)
 
     def num_frames(self, N: int) -> int:
-        T = int(self._lib.etd_stemfeat_num_frames(self._h, int(N)))
+        T = int(self._lib.etd_stemfeat_num_frames(self.h, int(N)))
         if T < 0:
             raise ValueError(f"num_frames: N must be >= 1, got {N}")
         return T
-
-    def _device(self) -> torch.device:
-        if self.device.type != "cuda" or not torch.cuda.is_available():
-            raise _lib.EtudeHipError("etude_amd.StemFeatures needs a ROCm GPU (device='cuda'); there is no CPU path")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        return self.device
 
     def features_many(self, stems_list: Sequence) -> Tuple[torch.Tensor, List[int]]:
         """songs [instr][channels][N_s] -> (the songs' [instr][T_s][n_mels] blocks back to back in one flat device tensor, [T_s]): ``BeatDetector``'s packed input.
@@ -135,13 +116,10 @@ class StemFeatures:
         n, (instr, channels) = len(songs), shapes[0][:2]
         Ts = [self.num_frames(s[2]) for s in shapes]
         feat = torch.empty(instr * self.n_mels * sum(Ts), dtype=torch.float32, device=dev)
-        ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in songs])
-        N_arr = (C.c_int64 * n)(*[s[2] for s in shapes])
         with torch.cuda.device(dev):
-            st = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(self._lib.etd_stemfeat_run(self._h, ptrs, n, instr, channels, N_arr, C.c_void_p(feat.data_ptr()), C.c_void_p(st)), "etd_stemfeat_run")
-            for t in songs:          # (an uploaded copy may be freed right after this call: its memory stays valid for work queued on this stream)
-                t.record_stream(torch.cuda.current_stream(dev))
+            _lib.check(self._lib.etd_stemfeat_run(self.h, ptrs(songs), n, instr, channels, i64([s[2] for s in shapes]), C.c_void_p(feat.data_ptr()), self._stream(dev)),
+                       "etd_stemfeat_run")
+            hold(songs, dev)
         return feat, Ts
 
     def features(self, stems) -> torch.Tensor:
@@ -150,8 +128,4 @@ class StemFeatures:
         return feat.view(int(stems.shape[0]), Ts[0], self.n_mels)
 
     def workspace_bytes(self, Ns: Sequence[int], instr: int) -> int:
-        arr = (C.c_int64 * len(Ns))(*[int(n) for n in Ns])
-        b = int(self._lib.etd_stemfeat_workspace_bytes(self._h, len(Ns), int(instr), arr))
-        if b < 0:
-            _lib.check(b, "etd_stemfeat_workspace_bytes")
-        return b
+        return nonneg(self._lib.etd_stemfeat_workspace_bytes(self.h, len(Ns), int(instr), i64(Ns)), "etd_stemfeat_workspace_bytes")

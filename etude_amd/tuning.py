@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._engine import Engine, hold, i32, i64, mono_songs_to_device, nonneg, ptrs
 
 FS = 22050
 N_FFT = 16384
@@ -29,10 +30,11 @@ def limits() -> dict:
     return dict(min_samples=lo.value, max_samples=hi.value, max_songs=ms.value)
 
 
-class TuningEstimator:
+class TuningEstimator(Engine):
     """Mono audio at 22 050 Hz -> tuning in cents, an integer in -50 .. 49, and the comb similarity ``sim[100]`` it is the first maximum of.
 
     A song is a 1-d float32 array or tensor (host or device), finite, 32 768 <= N <= 2^27.  Constructing needs no GPU; ``estimate_many`` does: there is no CPU path."""
+    _destroy = "etd_tuning_destroy"
 
     def __init__(self, device: Union[str, torch.device] = "cuda"):
         self.device = torch.device("cuda" if device == "auto" else device)
@@ -41,13 +43,7 @@ class TuningEstimator:
         cfg = _lib.TuningCfg(sample_rate=FS, n_fft=N_FFT, hop=HOP)
         h = C.c_void_p()
         _lib.check(self._lib.etd_tuning_create(C.byref(cfg), C.byref(h)), "etd_tuning_create")
-        self.h = h
-
-    def __del__(self):
-        h = getattr(self, "h", None)
-        if h is not None and h.value:
-            self._lib.etd_tuning_destroy(h)
-            self.h = None
+        self._adopt(h)
 
     def num_frames(self, N: int) -> int:
         if N < self.limits["min_samples"]:
@@ -55,17 +51,12 @@ class TuningEstimator:
         return 1 + int(N) // HOP
 
     def workspace_bytes(self, Ns: Sequence[int]) -> int:
-        arr = (C.c_int64 * len(Ns))(*[int(n) for n in Ns])
-        b = int(self._lib.etd_tuning_workspace_bytes(self.h, len(Ns), arr))
-        if b < 0:
-            _lib.check(b, "etd_tuning_workspace_bytes")
-        return b
+        return nonneg(self._lib.etd_tuning_workspace_bytes(self.h, len(Ns), i64(Ns)), "etd_tuning_workspace_bytes")
 
     def layout(self, Ns: Sequence[int], song: int) -> dict:
         """test hook (host arithmetic): where song `song` of a call with these lengths keeps its stages in the workspace (byte offsets), its frames and groups"""
-        arr = (C.c_int64 * len(Ns))(*[int(n) for n in Ns])
         out = (C.c_int64 * len(_lib.TUNING_LAYOUT))()
-        _lib.check(self._lib.etd_tuning_debug_layout(self.h, len(Ns), arr, int(song), out, len(_lib.TUNING_LAYOUT)), "etd_tuning_debug_layout")
+        _lib.check(self._lib.etd_tuning_debug_layout(self.h, len(Ns), i64(Ns), int(song), out, len(_lib.TUNING_LAYOUT)), "etd_tuning_debug_layout")
         return dict(zip(_lib.TUNING_LAYOUT, [int(v) for v in out]))
 
     def tap_power(self, song: int, frames: Sequence[int], power: Union[torch.Tensor, None]) -> None:
@@ -74,46 +65,23 @@ class TuningEstimator:
         if power is None:
             _lib.check(self._lib.etd_tuning_debug_power(self.h, 0, None, 0, None), "etd_tuning_debug_power")
             return
-        arr = (C.c_int32 * len(frames))(*[int(f) for f in frames])
         if power.dtype != torch.float32 or power.numel() < len(frames) * (N_FFT // 2 + 1) or not power.is_contiguous():
             raise ValueError("tap_power: power must be a contiguous float32 tensor of [len(frames)][8193]")
-        _lib.check(self._lib.etd_tuning_debug_power(self.h, int(song), arr, len(frames), C.c_void_p(power.data_ptr())), "etd_tuning_debug_power")
-
-    def _device(self) -> torch.device:
-        if self.device.type != "cuda" or not torch.cuda.is_available():
-            raise _lib.EtudeHipError("etude_amd.TuningEstimator needs a ROCm GPU (device='cuda'); there is no CPU path")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        return self.device
+        _lib.check(self._lib.etd_tuning_debug_power(self.h, int(song), i32(frames), len(frames), C.c_void_p(power.data_ptr())), "etd_tuning_debug_power")
 
     def run_raw(self, songs: Sequence[torch.Tensor], tuning: torch.Tensor, sim: torch.Tensor, ws: torch.Tensor) -> None:
         """one launch sequence on checked device tensors with the caller's buffers (tests put canaries around them): tuning int32 [n], sim float64 [n][100]"""
         n = len(songs)
-        ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in songs])
-        N_arr = (C.c_int64 * n)(*[int(t.numel()) for t in songs])
         dev = self._device()
         with torch.cuda.device(dev):
-            st = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(self._lib.etd_tuning_run(self.h, ptrs, n, N_arr, C.c_void_p(tuning.data_ptr() if tuning is not None else None),
+            _lib.check(self._lib.etd_tuning_run(self.h, ptrs(songs), n, i64([t.numel() for t in songs]), C.c_void_p(tuning.data_ptr() if tuning is not None else None),
                                                 C.c_void_p(sim.data_ptr() if sim is not None else None), C.c_void_p(ws.data_ptr()), ws.numel() * ws.element_size(),
-                                                C.c_void_p(st)), "etd_tuning_run")
+                                                self._stream(dev)), "etd_tuning_run")
 
     def check_songs(self, wavs: Sequence) -> List[torch.Tensor]:
         """the input checks (1-d, the length limits, finite with ONE host synchronisation) -> the songs as contiguous float32 device tensors"""
-        for i, x in enumerate(wavs):
-            shp = tuple(x.shape) if hasattr(x, "shape") else None
-            if shp is None or len(shp) != 1:
-                raise ValueError(f"song {i}: need mono samples [N], got shape {shp}")
-            if shp[0] < self.limits["min_samples"]:
-                raise ValueError(f"song {i}: N = {shp[0]} is shorter than two windows ({self.limits['min_samples']} samples): the tuning cannot be estimated")
-            if shp[0] > self.limits["max_samples"]:
-                raise ValueError(f"song {i}: N = {shp[0]} is above the engine's {self.limits['max_samples']} samples")
-        dev = self._device()
-        songs = [torch.as_tensor(x).detach().to(dev, torch.float32).contiguous() for x in wavs]
-        bad = torch.stack([torch.isfinite(t).all() for t in songs]).logical_not().nonzero().flatten().tolist()      # (one host synchronisation for the call)
-        if bad:
-            raise ValueError(f"song {bad[0]}: holds a non-finite sample")
-        return songs
+        return mono_songs_to_device(wavs, self._device, self.limits["min_samples"], self.limits["max_samples"],
+                                    f"is shorter than two windows ({self.limits['min_samples']} samples): the tuning cannot be estimated")
 
     def estimate_device(self, songs: Sequence[torch.Tensor]) -> Tuple[np.ndarray, torch.Tensor]:
         """checked device songs -> (tuning int64 [n] on the host, sim float64 [n][100] on the device)"""
@@ -128,8 +96,7 @@ class TuningEstimator:
                 self.run_raw(group, tuning, sim, ws)
                 tun.append(tuning)
                 sims.append(sim)
-            for t in songs:
-                t.record_stream(torch.cuda.current_stream(dev))
+            hold(songs, dev)
         return torch.cat(tun).cpu().numpy().astype(np.int64), torch.cat(sims)
 
     def estimate_many(self, wavs: Sequence, details: bool = False):

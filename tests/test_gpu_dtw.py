@@ -207,7 +207,7 @@ def test_refusals():
     n0 = (C.c_int64 * 1)(0)
     n5 = (C.c_int64 * 1)(5)
     ptrs = (C.c_void_p * 4)(1, 1, 1, 1)
-    assert lib.etd_dtw_align(eng._h, ptrs, 1, n0, n5, C.c_void_p(256), 1 << 20, C.c_void_p(256), 1 << 10, None, None) == -22
+    assert lib.etd_dtw_align(eng.h, ptrs, 1, n0, n5, C.c_void_p(256), 1 << 20, C.c_void_p(256), 1 << 10, None, None) == -22
     cfg = make_cfg()
     cfg.struct_bytes += 8
     h = C.c_void_p()

@@ -101,13 +101,13 @@ def run(fe, wav, dev, features=True):
     wav = np.ascontiguousarray(wav, np.float32)
     c, L = wav.shape
     w = torch.from_numpy(wav).to(dev)
-    n = int(lib.etd_frontend_resampled_len(fe._h, L))
-    T = int(lib.etd_frontend_num_frames(fe._h, L))
+    n = int(lib.etd_frontend_resampled_len(fe.h, L))
+    T = int(lib.etd_frontend_num_frames(fe.h, L))
     assert n == fnp.resampled_len(L, fe.sr_in, fe.sr_out) and T == fnp.num_frames(n, fe.hop)
     res = Guarded(n, dev)
     feat = Guarded(T * fe.n_mels, dev) if features else None
     out_t = C.c_longlong(-1)
-    _lib.check(lib.etd_frontend_run(fe._h, w.data_ptr(), c, L, res.ptr, feat.ptr if features else None, T if features else 0, C.byref(out_t), None), "etd_frontend_run")
+    _lib.check(lib.etd_frontend_run(fe.h, w.data_ptr(), c, L, res.ptr, feat.ptr if features else None, T if features else 0, C.byref(out_t), None), "etd_frontend_run")
     r = res.read()
     assert out_t.value == (T if features else 0)
     return r, (feat.read().reshape(T, fe.n_mels) if features else None)
@@ -178,7 +178,7 @@ def test_length_formulas(dev, sr_in, sr_out):
     orig, new, _, _ = fnp.pair_dims(sr_in, sr_out)
     for L in list(range(0, 50)) + fnp.resample_lengths(sr_in, sr_out) + [orig * 1000 + 1, 2 ** 33 + 7]:
         n = -((-new * L) // orig)
-        assert lib.etd_frontend_resampled_len(fe._h, L) == n and lib.etd_frontend_num_frames(fe._h, L) == 1 + n // 256 == fe.num_frames(L)
+        assert lib.etd_frontend_resampled_len(fe.h, L) == n and lib.etd_frontend_num_frames(fe.h, L) == 1 + n // 256 == fe.num_frames(L)
 
 
 # ---------------------------------------------------------------------------------------------------- resampler and channel mean
@@ -418,10 +418,10 @@ def test_rms_on_the_devices_resampled_buffer(dev, channels):
     L = 2 * 8 * 1102 + 3
     wav = fnp.noisy_clip(4, channels, L, 44100) * np.linspace(0.1, 1.0, L, dtype=np.float32)[None]
     lib = _lib.lib()
-    n = int(lib.etd_frontend_resampled_len(fe._h, L))
+    n = int(lib.etd_frontend_resampled_len(fe.h, L))
     res = Guarded(n, dev)
     w = torch.from_numpy(np.ascontiguousarray(wav)).to(dev)
-    _lib.check(lib.etd_frontend_run(fe._h, w.data_ptr(), channels, L, res.ptr, None, 0, None, None), "etd_frontend_run")
+    _lib.check(lib.etd_frontend_run(fe.h, w.data_ptr(), channels, L, res.ptr, None, 0, None, None), "etd_frontend_run")
     r = res.read()
     check_first_stage(wav, 44100, 22050, r, "volume")
     got = rms(None, 2204, 1102, dev, x_dev=res.buf[GUARD:GUARD + n].view(torch.float32))
