@@ -540,7 +540,7 @@ static int forward_prefill16(etd_dec* d, int M, const DecRows& rows, const Prefi
 static int forward_rows(etd_dec* d, int M, const DecRows& rows, const PrefillInfo* pf, const LastOnly* lo, hipStream_t st, float** hfinal, bool* compact) {
   if (compact) *compact = false; else lo = nullptr;
   const Layer& w0 = d->layers[0];
-  if (!d->bf16w && M >= G3_MIN_ROWS && d->X1f && w0.qkv.g3.Wp && w0.down.g3.Wp && g3_enabled()) return forward_x3(d, M, rows, pf, lo, st, hfinal, compact);
+  if (!d->bf16w && M >= G3_MIN_ROWS && d->X1f && w0.qkv.g3.Wp && w0.down.g3.Wp) return forward_x3(d, M, rows, pf, lo, st, hfinal, compact);
   const bool act16 = d->bf16w && M > 1;
   if (act16 && M > DS_MAX_ROWS && w0.qkv.Wf && w0.up.Wf && w0.cat.Wf) return forward_prefill16(d, M, rows, pf, lo, st, hfinal, compact);
   if (act16 && ksplit_fits(d)) return forward_skinny16(d, M, rows, false, st, hfinal);
@@ -549,7 +549,7 @@ static int forward_rows(etd_dec* d, int M, const DecRows& rows, const PrefillInf
 
 // final LayerNorm + lm_head for `n` rows of X (fp32 [n][H]) -> logits [n][V]
 int head_logits(etd_dec* d, const float* X, int n, float* logits, hipStream_t st) {
-  const bool g3 = !d->bf16w && n >= G3_MIN_ROWS && d->X1f && d->head.g3.Wp && g3_enabled();
+  const bool g3 = !d->bf16w && n >= G3_MIN_ROWS && d->X1f && d->head.g3.Wp;
   if (g3) ETD_TRY(launch_ln_rows_f32(X, n, d->H, d->lnfg, d->lnfb, nullptr, nullptr, d->cfg.layer_norm_eps, d->X1f, nullptr, st));
   DGemmArgs lm = lin_args(d->head, g3 ? d->X1f : X, d->H, n);
   lm.bias = nullptr; lm.Y = logits; lm.ldy = d->V;
@@ -660,7 +660,7 @@ int stage_and_forward(etd_dec* d, int n, const int32_t* slots, const int32_t* T,
   e.rows = DecRows{sg->row_slot, sg->row_pos, sg->row_active, sg->row_seq};
   ETD_TRY(launch_dembed(e, st));
   PrefillInfo pf{n, sg->seq_row0, sg->seq_len, max_len, aflops};
-  const bool can_mfma_attn = (d->bf16w ? d->Qb != nullptr : d->X1f != nullptr) && !ETD_XENV("ETD_NO_MFMA_PREFILL_ATTN");
+  const bool can_mfma_attn = (d->bf16w ? d->Qb != nullptr : d->X1f != nullptr);
   LastOnly lo{n, sg->last_idx, DecRows{sg->last_slot, sg->last_pos, sg->last_active}};
   return forward_rows(d, M, e.rows, can_mfma_attn ? &pf : nullptr, &lo, st, hfinal, last_only);
 }
@@ -702,12 +702,10 @@ int alloc_workspaces(etd_dec* d) {
   ETD_TRY(P.alloc(&d->n_out, S, true)); ETD_TRY(P.alloc(&d->eos, S, true)); ETD_TRY(P.alloc(&d->limit, S, true));
   ETD_TRY(P.alloc(&d->tgt_proj, S * (size_t)d->H, true));
   ETD_TRY(P.alloc(&d->tgt_attrs, 4 * S, true)); ETD_TRY(P.alloc(&d->out_tok, S * d->out_cap, true));
-  if (!ETD_XENV("ETD_NO_PINNED")) {
-    d->pin_stage_ints = 10 * M + 13 * S;
-    if (hipHostMalloc((void**)&d->pin_stage, d->pin_stage_ints * 4, hipHostMallocDefault) != hipSuccess) { d->pin_stage = nullptr; (void)hipGetLastError(); }
-    if (hipHostMalloc((void**)&d->pin_rb, (2 * S + S * (size_t)d->out_cap) * 4, hipHostMallocDefault) != hipSuccess) { d->pin_rb = nullptr; (void)hipGetLastError(); }
-    if (d->pin_stage && hipEventCreateWithFlags(&d->pin_stage_evt, hipEventDisableTiming) != hipSuccess) { (void)hipHostFree(d->pin_stage); d->pin_stage = nullptr; d->pin_stage_evt = nullptr; }
-  }
+  d->pin_stage_ints = 10 * M + 13 * S;
+  if (hipHostMalloc((void**)&d->pin_stage, d->pin_stage_ints * 4, hipHostMallocDefault) != hipSuccess) { d->pin_stage = nullptr; (void)hipGetLastError(); }
+  if (hipHostMalloc((void**)&d->pin_rb, (2 * S + S * (size_t)d->out_cap) * 4, hipHostMallocDefault) != hipSuccess) { d->pin_rb = nullptr; (void)hipGetLastError(); }
+  if (d->pin_stage && hipEventCreateWithFlags(&d->pin_stage_evt, hipEventDisableTiming) != hipSuccess) { (void)hipHostFree(d->pin_stage); d->pin_stage = nullptr; d->pin_stage_evt = nullptr; }
   d->host_n_out.assign(S, 0);
   return ETD_OK;
 }
@@ -740,8 +738,8 @@ int layer_bounds(const WeightTable& L, const std::string& p, int H, int I, Layer
 
 }  // namespace
 
-// 1 when the library was built with -DETD_EXPERIMENTS: the measured dead ends (in-launch row finish, 8 / 16-wave attention workgroups, k_post_attn) are compiled in
-// and their environment switches are live; the shipped build has one path per precision and ignores those switches
+// 1 when the library was built with -DETD_EXPERIMENTS: the measured dead ends (in-launch row finish, 8 / 16-wave attention workgroups) are compiled in and their
+// switches (ETD_ROWFIN, ETD_AD_WAVES) are live, as are ETD_LAUNCH_LOG and ETD_NO_GRAPH; the shipped build has one path per precision and ignores those switches
 extern "C" int etd_has_experiments(void) {
 #ifdef ETD_EXPERIMENTS
   return 1;
@@ -1103,11 +1101,9 @@ extern "C" int etd_decoder_step(etd_dec* d, const int32_t* slots, int n_active, 
   // d16 batched decode step on the fused kernels: [embed + LayerNorm] once per call, then per step 4 launches per layer
   // (QKV|up, attention, down|dense, residual + LayerNorm) and one head launch that also prepares the next step's rows
   const int vpad = (d->V + 31) / 32 * 32;
-  // A single stream steps on the fused kernels too (round 3; ETD_FUSED_M1=0: the GEMV sequence of rounds 1-2): 25 launches per step instead of ~36 and the same
+  // A single stream steps on the fused kernels too (round 3; before: the GEMV sequence of rounds 1-2): 25 launches per step instead of ~36 and the same
   // arithmetic as inside a batch -- one job of 92 bars x 48 tokens 1.09 -> 0.66 s (tools/runs3/r3_run20.sh), every decoder golden unchanged.
-  static const bool fused_m1 = !(ETD_XENV("ETD_FUSED_M1") && atoi(ETD_XENV("ETD_FUSED_M1")) == 0);
-  const bool fused = d->bf16w && (n_active > 1 || fused_m1) && n_active <= DS_STEP_MAX_ROWS && step_shape(d) && vpad <= 256 &&
-                     vpad <= d->head.Npad && d->head_frag && !ETD_XENV("ETD_NO_FUSED_STEP");
+  const bool fused = d->bf16w && n_active <= DS_STEP_MAX_ROWS && step_shape(d) && vpad <= 256 && vpad <= d->head.Npad && d->head_frag;
   d->last_step_fused = fused;
   d->stamp_on = d->stamp_armed && d->stamp_skip <= 0;          // (a whole call is stamped or not: the scheduler issues one bar's steps per call)
   if (d->stamp_armed && d->stamp_skip > 0) d->stamp_skip -= n_steps;

@@ -48,12 +48,11 @@ struct etd_ext {
   float* pos_time = nullptr;   // [nf][256] fp32
   EncLayerW tim[3];
   LinW head_time, head_freq;   // [160][256]
-  e16* Wkv_all = nullptr; float* bkv_all = nullptr;   // the 3 cross-attention K/V projections, z-batched [3][512][256]
+  float* bkv_all = nullptr;    // biases of the 3 cross-attention K/V projections, [3][k 256 | v 256]
   // workspaces (e16 unless noted)
   size_t MT = 0, MQ = 0;       // token capacities
-  e16 *X = nullptr, *X1 = nullptr, *QK = nullptr, *VT = nullptr, *AO = nullptr, *HF = nullptr;
-  e16 *Kc = nullptr, *VTc = nullptr;              // [3][MTe][256] each
-  e16 *Tq = nullptr, *T1 = nullptr, *QKd = nullptr, *VTd = nullptr, *AOd = nullptr, *HFd = nullptr, *Qd = nullptr, *Tfreq = nullptr;
+  e16 *X = nullptr, *X1 = nullptr, *QK = nullptr, *VT = nullptr, *AO = nullptr;
+  e16 *Tq = nullptr, *T1 = nullptr, *QKd = nullptr, *VTd = nullptr, *AOd = nullptr, *Qd = nullptr, *Tfreq = nullptr;
   e16* TI = nullptr;          // time-decoder input [wb*nn*nf][256]
   e16 *KVimg = nullptr, *KVcimg = nullptr;   // K / V MFMA-fragment images for k_attn_frag: self-attention [MT * 512], cross-attention [3][MTe * 512]
   size_t MTe = 0;              // encoder chunk token capacity (wb*fc*256)
@@ -78,7 +77,7 @@ int load_lin(DevPool& pool, const WeightTable& L, const std::string& pfx, int ou
   return ETD_OK;
 }
 // concatenate several [256][256] linears along the output dim
-int load_cat(DevPool& pool, const WeightTable& L, const std::vector<std::string>& pfx, LinW* w, std::vector<float>* keepW = nullptr, std::vector<float>* keepB = nullptr) {
+int load_cat(DevPool& pool, const WeightTable& L, const std::vector<std::string>& pfx, LinW* w, std::vector<float>* keepB = nullptr) {
   std::vector<float> W, b;
   for (auto& p : pfx) {
     const float* Wi = L.get(p + ".weight", 256 * 256);
@@ -89,7 +88,6 @@ int load_cat(DevPool& pool, const WeightTable& L, const std::vector<std::string>
   }
   ETD_TRY(up_bf16(pool, &w->W, W.data(), W.size()));
   ETD_TRY(pool.upload(&w->b, b.data(), b.size()));
-  if (keepW) *keepW = W;
   if (keepB) *keepB = b;
   return ETD_OK;
 }
@@ -183,7 +181,6 @@ extern "C" int etd_extractor_create(const etd_ext_cfg* cfg, const char* const* n
   etd_ext* e = new etd_ext();
   e->cfg = c; e->nf = c.n_frame; e->nn = c.n_note; e->margin = c.n_margin; e->wb = c.max_windows;
   e->fc = c.chunk_frames > 0 ? c.chunk_frames : c.n_frame;   // measured: whole-window launches beat MALL-sized chunks (2.9 vs 4.4 ms/window)
-  if (const char* s = ETD_XENV("ETD_CHUNK_FRAMES")) e->fc = atoi(s);
   if (e->fc > e->nf) e->fc = e->nf;
   if (e->fc < 1) e->fc = e->nf;
   const WeightTable L(names, host_ptrs, numels, n);
@@ -250,7 +247,7 @@ extern "C" int etd_extractor_create(const etd_ext_cfg* cfg, const char* const* n
   for (int i = 0; i < 3; ++i) ETD_TRY_OR(fail, load_enc_layer(P, L, "encoder.layers_freq." + std::to_string(i), &e->enc[i]));
   for (int i = 0; i < 3; ++i) ETD_TRY_OR(fail, load_enc_layer(P, L, "decoder.layers_time." + std::to_string(i), &e->tim[i]));
   // ---- frequency decoder
-  std::vector<float> kvW, kvB;
+  std::vector<float> kvB;
   for (int i = 0; i < 3; ++i) {
     const std::string p = i == 0 ? std::string("decoder.layer_zero_freq") : "decoder.layers_freq." + std::to_string(i - 1);
     DecLayerW& w = e->dec[i];
@@ -268,16 +265,15 @@ extern "C" int etd_extractor_create(const etd_ext_cfg* cfg, const char* const* n
     ETD_TRY_OR(fail, load_proj_block(P, L, p + ".encoder_attention.fc_v", false, &w.pvc));
     ETD_TRY_OR(fail, load_proj_block(P, L, p + ".encoder_attention.fc_o", true, &w.poc));
     ETD_TRY_OR(fail, load_lin(P, L, p + ".encoder_attention.fc_q", 256, 256, &w.q_c));
-    std::vector<float> W1, b1;
-    ETD_TRY_OR(fail, load_cat(P, L, {p + ".encoder_attention.fc_k", p + ".encoder_attention.fc_v"}, &w.kv_c, &W1, &b1));
-    kvW.insert(kvW.end(), W1.begin(), W1.end()); kvB.insert(kvB.end(), b1.begin(), b1.end());
+    std::vector<float> b1;
+    ETD_TRY_OR(fail, load_cat(P, L, {p + ".encoder_attention.fc_k", p + ".encoder_attention.fc_v"}, &w.kv_c, &b1));
+    kvB.insert(kvB.end(), b1.begin(), b1.end());
     ETD_TRY_OR(fail, load_lin(P, L, p + ".encoder_attention.fc_o", 256, 256, &w.o_c));
     ETD_TRY_OR(fail, load_lin(P, L, p + ".positionwise_feedforward.fc_1", 512, 256, &w.f1));
     ETD_TRY_OR(fail, load_lin(P, L, p + ".positionwise_feedforward.fc_2", 256, 512, &w.f2));
     ETD_TRY_OR(fail, load_ffn_stream(P, L, p + ".positionwise_feedforward", &w.ffn));
     ETD_TRY_OR(fail, load_ln(P, L, p + ".layer_norm", &w.g, &w.be));
   }
-  ETD_TRY_OR(fail, up_bf16(P, &e->Wkv_all, kvW.data(), kvW.size()));
   ETD_TRY_OR(fail, P.upload(&e->bkv_all, kvB.data(), kvB.size()));
   {
     const int nn = e->nn;
@@ -312,16 +308,12 @@ extern "C" int etd_extractor_create(const etd_ext_cfg* cfg, const char* const* n
   ETD_TRY_OR(fail, P.alloc(&e->QK, MT * 512));
   ETD_TRY_OR(fail, P.alloc(&e->VT, MT * 256, true));
   ETD_TRY_OR(fail, P.alloc(&e->AO, MT * 256));
-  ETD_TRY_OR(fail, P.alloc(&e->HF, MT * 512));
-  ETD_TRY_OR(fail, P.alloc(&e->Kc, 3 * MTe * 256));
-  ETD_TRY_OR(fail, P.alloc(&e->VTc, 3 * MTe * 256, true));
   ETD_TRY_OR(fail, P.alloc(&e->Tq, MQ * 256));
   ETD_TRY_OR(fail, P.alloc(&e->T1, MQ * 256));
   ETD_TRY_OR(fail, P.alloc(&e->Tfreq, MQ * 256));
   ETD_TRY_OR(fail, P.alloc(&e->QKd, MQ * 512));
   ETD_TRY_OR(fail, P.alloc(&e->VTd, (size_t)e->wb * e->fc * 4 * 64 * 128, true));   // S = nn <= 128 padded to 128; pad stays 0
   ETD_TRY_OR(fail, P.alloc(&e->AOd, MQ * 256));
-  ETD_TRY_OR(fail, P.alloc(&e->HFd, MQ * 512));
   ETD_TRY_OR(fail, P.alloc(&e->Qd, MQ * 256));
   ETD_TRY_OR(fail, P.alloc(&e->TI, MTt * 256));
   ETD_TRY_OR(fail, P.alloc(&e->KVimg, MT * 512));
@@ -367,24 +359,6 @@ extern "C" double etd_extractor_window_flops(const etd_ext* e) {
 namespace {
 
 const float kScaleLog2e = 0.125f * 1.4426950408889634f;
-// ETD_NO_FUSED_FFN=1: the round-1 sequence (FFN1 launch, 512-wide hidden through HBM, FFN2 + LayerNorm launch) for A/B runs
-bool fused_ffn() { static const bool on = !ETD_XENV("ETD_NO_FUSED_FFN"); return on; }
-// ETD_NO_FUSED_PROJ=1: the K = 256 projections on round 1's k_linear tiles instead of k_proj256
-bool fused_proj() { static const bool on = !ETD_XENV("ETD_NO_FUSED_PROJ"); return on; }
-// ETD_NO_FUSED_LAYER=1: encoder layers as four launches (QKV, attention, fc_o + LN, FFN) instead of k_enc_layer
-bool fused_layer() { static const bool on = !ETD_XENV("ETD_NO_FUSED_LAYER"); return on; }
-// ETD_NO_FRAG_ATTN=1: attention on k_attn (K row-major, V^T) instead of k_attn_frag (K / V as MFMA-fragment images)
-bool frag_attn() { static const bool on = !ETD_XENV("ETD_NO_FRAG_ATTN") && !ETD_XENV("ETD_NO_FUSED_PROJ"); return on; }
-// ETD_POST_ATTN=1: fc_o + LayerNorm + feed-forward block of the decoder layers as ONE launch (k_post_attn).  Measured equal in time to the
-// two launches it replaces (0.319 vs 0.309 ms per window: its mid-kernel LayerNorm costs what the saved HBM round trip gains), so the
-// two-launch sequence stays the default
-// (a measured dead end: compiled with -DETD_EXPERIMENTS only)
-#ifdef ETD_EXPERIMENTS
-bool fused_post() { static const bool on = getenv("ETD_POST_ATTN") && atoi(getenv("ETD_POST_ATTN")) != 0 && !ETD_XENV("ETD_NO_FUSED_PROJ") && !ETD_XENV("ETD_NO_FUSED_FFN"); return on; }
-#else
-constexpr bool fused_post() { return false; }
-#endif
-
 ProjBlock pblock(const e16* Wf, const float* bias, int kind, e16* dst, int ldd, int relu = 0) {
   ProjBlock b = {}; b.Wf = Wf; b.bias = bias; b.kind = kind; b.relu = relu; b.dst = dst; b.ldd = ldd; return b;
 }
@@ -408,10 +382,7 @@ int proj_ln(const e16* X, int M, const e16* po, const float* bias, const e16* R,
 int enc_like_layer(etd_ext* e, const EncLayerW& w, e16* X, e16* X1, int M, int n_seq, int S, hipStream_t st,
                    e16* Yfinal /* where the 2nd LN writes (X to run in place) */) {
   // x = LN(x + MHA(x)); x = LN(x + FFN(x))          amt_apc.py:244-259
-  LinArgs a = {};
-  a.X = X; a.ldx = 256; a.W = w.qkv.W; a.bias = w.qkv.b; a.M = M; a.N = 768; a.K = 256;
-  a.Y = e->QK; a.ldy = 512; a.vt_block = 2; a.VT = e->VT; a.S = S; a.Spad = ((S + 63) / 64) * 64;
-  if (frag_attn() && S % 64 == 0 && M % 32 == 0) {
+  if (S % 64 == 0 && M % 32 == 0) {
     ProjArgs pa = {};
     pa.X = X; pa.ldx = 256; pa.M = M; pa.nblk = 3; pa.S = S; pa.kv_nstep = S / 64;
     pa.blk[0] = pblock(w.pq, w.qkv.b, PROJ_ROW, e->QK, 256);
@@ -423,38 +394,19 @@ int enc_like_layer(etd_ext* e, const EncLayerW& w, e16* X, e16* X1, int M, int n
     f.O = e->AO; f.ldo = 256; f.o_seq_stride = (long long)S * 256; f.n_seq = n_seq; f.Sq = S; f.Sk = S; f.scale_log2e = kScaleLog2e;
     ETD_TRY(launch_attn_frag(f, st));
   } else {
-  if (fused_proj()) ETD_TRY(proj_qkv(X, M, w.pq, w.pk, w.pv, w.qkv.b, e->QK, e->VT, S, a.Spad, st));
-  else ETD_TRY(launch_linear(a, 1, st));
-  AttnArgs t = {};
-  t.Q = e->QK; t.ldq = 512; t.q_seq_stride = (long long)S * 512;
-  t.K = e->QK + 256; t.ldk = 512; t.k_seq_stride = (long long)S * 512;
-  t.VT = e->VT; t.Spad = a.Spad;
-  t.O = e->AO; t.ldo = 256; t.o_seq_stride = (long long)S * 256;
-  t.n_seq = n_seq; t.Sq = S; t.Sk = S; t.scale_log2e = kScaleLog2e;
-  ETD_TRY(launch_attn(t, st));
+    const int Spad = ((S + 63) / 64) * 64;
+    ETD_TRY(proj_qkv(X, M, w.pq, w.pk, w.pv, w.qkv.b, e->QK, e->VT, S, Spad, st));
+    AttnArgs t = {};
+    t.Q = e->QK; t.ldq = 512; t.q_seq_stride = (long long)S * 512;
+    t.K = e->QK + 256; t.ldk = 512; t.k_seq_stride = (long long)S * 512;
+    t.VT = e->VT; t.Spad = Spad;
+    t.O = e->AO; t.ldo = 256; t.o_seq_stride = (long long)S * 256;
+    t.n_seq = n_seq; t.Sq = S; t.Sk = S; t.scale_log2e = kScaleLog2e;
+    ETD_TRY(launch_attn(t, st));
   }
-  LinArgs o = {};
-  o.X = e->AO; o.ldx = 256; o.W = w.o.W; o.bias = w.o.b; o.M = M; o.N = 256; o.K = 256; o.vt_block = -1;
-  o.R = X; o.ldr = 256; o.gamma = w.g; o.beta = w.be; o.Y = X1; o.ldy = 256;
-  if (fused_post()) {
-    PostAttnArgs pa = {e->AO, X, 0, w.po, w.ffn, w.o.b, w.g, w.be, w.f1.b, w.f2.b, Yfinal, M};
-    return launch_post_attn(pa, st);
-  }
-  if (fused_proj()) ETD_TRY(proj_ln(e->AO, M, w.po, w.o.b, X, 0, w.g, w.be, X1, st));
-  else ETD_TRY(launch_linear_ln(o, st));
-  if (fused_ffn()) {
-    FfnArgs f = {X1, w.ffn, w.f1.b, w.f2.b, w.g, w.be, Yfinal, M};
-    return launch_ffn_fused(f, st);
-  }
-  LinArgs f1 = {};
-  f1.X = X1; f1.ldx = 256; f1.W = w.f1.W; f1.bias = w.f1.b; f1.M = M; f1.N = 512; f1.K = 256; f1.vt_block = -1; f1.relu = 1;
-  f1.Y = e->HF; f1.ldy = 512;
-  ETD_TRY(launch_linear(f1, 1, st));
-  LinArgs f2 = {};
-  f2.X = e->HF; f2.ldx = 512; f2.W = w.f2.W; f2.bias = w.f2.b; f2.M = M; f2.N = 256; f2.K = 512; f2.vt_block = -1;
-  f2.R = X1; f2.ldr = 256; f2.gamma = w.g; f2.beta = w.be; f2.Y = Yfinal; f2.ldy = 256;
-  ETD_TRY(launch_linear_ln(f2, st));
-  return ETD_OK;
+  ETD_TRY(proj_ln(e->AO, M, w.po, w.o.b, X, 0, w.g, w.be, X1, st));
+  FfnArgs f = {X1, w.ffn, w.f1.b, w.f2.b, w.g, w.be, Yfinal, M};
+  return launch_ffn_fused(f, st);
 }
 
 struct Outs { float *on, *off, *mpe; int8_t* vel; };
@@ -475,45 +427,23 @@ int run_window_batch(etd_ext* e, const EmbedArgs& src_tmpl, int w0, int nw, long
     ea.Wf = e->Wf; ea.bf = e->bfold; ea.pos = e->pos_freq_enc; ea.Y = e->X; ea.w0 = w0; ea.n_win = nw; ea.f0 = f0; ea.fc = fc;
     ea.nf = nf; ea.margin = e->margin; ea.center = -8.0f; ea.pad_value = e->cfg.min_value;
     ETD_TRY(launch_embed(ea, st));
-    // diagnostic (tools/probe_race.py): stop the launch sequence early -- 1: after the embedding, 2: after the encoder layers (outputs are garbage)
-    static const int stop_stage = ETD_XENV("ETD_EXT_STOP_STAGE") ? atoi(ETD_XENV("ETD_EXT_STOP_STAGE")) : 0;
-    if (stop_stage == 1) return ETD_OK;
     const bool first = (w0 == 0 && f0 == 0);
     ETD_TRY(tap(e, 0, e->X, (size_t)Mtok * 512, first, st));
     for (int l = 0; l < 3; ++l) {
-      if (fused_layer()) {
-        const EncLayerW& w = e->enc[l];
-        EncLayerArgs la = {e->X, w.lw, w.qkv.b, w.o.b, w.g, w.be, w.f1.b, w.f2.b, e->X, nfr};
-        ETD_TRY(launch_enc_layer(la, st));
-      } else {
-        ETD_TRY(enc_like_layer(e, e->enc[l], e->X, e->X1, Mtok, nfr, 256, st, e->X));
-      }
+      const EncLayerW& w = e->enc[l];
+      EncLayerArgs la = {e->X, w.lw, w.qkv.b, w.o.b, w.g, w.be, w.f1.b, w.f2.b, e->X, nfr};
+      ETD_TRY(launch_enc_layer(la, st));
       ETD_TRY(tap(e, 1 + l, e->X, (size_t)Mtok * 512, first, st));
     }
-    if (stop_stage == 2) return ETD_OK;
-    // ---- cross-attention K/V of the encoder output for the 3 decoder layers, one z-batched launch pair
+    // ---- cross-attention K/V of the encoder output for the 3 decoder layers as MFMA-fragment images, in ONE launch: six blocks over the same token tile
     {
-      LinArgs a = {};
-      a.X = e->X; a.ldx = 256; a.W = e->Wkv_all; a.bias = e->bkv_all; a.M = Mtok; a.N = 512; a.K = 256;
-      a.Y = e->Kc; a.ldy = 256; a.vt_block = 1; a.VT = e->VTc; a.S = 256; a.Spad = 256;
-      a.wz = 512 * 256; a.bz = 512; a.yz = (long long)e->MTe * 256; a.vtz = (long long)e->MTe * 256;
-      if (fused_proj()) {
-        // the three decoder layers' K and V of the encoder output in ONE launch: six blocks over the same token tile
-        ProjArgs pa = {};
-        pa.X = e->X; pa.ldx = 256; pa.M = Mtok; pa.nblk = 6; pa.S = 256; pa.Spad = 256; pa.kv_nstep = 4;
-        for (int l = 0; l < 3; ++l) {
-          if (frag_attn()) {
-            pa.blk[2 * l] = pblock(e->dec[l].pkc, e->bkv_all + l * 512, PROJ_KFRAG, e->KVcimg + (size_t)l * e->MTe * 512, 0);
-            pa.blk[2 * l + 1] = pblock(e->dec[l].pvc, e->bkv_all + l * 512 + 256, PROJ_VFRAG, e->KVcimg + (size_t)l * e->MTe * 512, 0);
-          } else {
-            pa.blk[2 * l] = pblock(e->dec[l].pkc, e->bkv_all + l * 512, PROJ_ROW, e->Kc + (size_t)l * e->MTe * 256, 256);
-            pa.blk[2 * l + 1] = pblock(e->dec[l].pvc, e->bkv_all + l * 512 + 256, PROJ_VT, e->VTc + (size_t)l * e->MTe * 256, 0);
-          }
-        }
-        ETD_TRY(launch_proj256(pa, st));
-      } else {
-        ETD_TRY(launch_linear(a, 3, st));
+      ProjArgs pa = {};
+      pa.X = e->X; pa.ldx = 256; pa.M = Mtok; pa.nblk = 6; pa.S = 256; pa.Spad = 256; pa.kv_nstep = 4;
+      for (int l = 0; l < 3; ++l) {
+        pa.blk[2 * l] = pblock(e->dec[l].pkc, e->bkv_all + l * 512, PROJ_KFRAG, e->KVcimg + (size_t)l * e->MTe * 512, 0);
+        pa.blk[2 * l + 1] = pblock(e->dec[l].pvc, e->bkv_all + l * 512 + 256, PROJ_VFRAG, e->KVcimg + (size_t)l * e->MTe * 512, 0);
       }
+      ETD_TRY(launch_proj256(pa, st));
     }
     // ---- frequency decoder (amt_apc.py:168-177,261-320): queries = 88 note embeddings per frame
     // D0 = layer input/output, D1 = after self-attention LN, D2 = after cross-attention LN
@@ -524,79 +454,32 @@ int run_window_batch(etd_ext* e, const EmbedArgs& src_tmpl, int w0, int nw, long
       int r_mod = 0;
       if (l == 0) { cross_in = e->trg0; r_mod = nn; }
       if (w.has_self) {
-        LinArgs a = {};
-        a.X = D0; a.ldx = 256; a.W = w.qkv_s.W; a.bias = w.qkv_s.b; a.M = Mq; a.N = 768; a.K = 256;
-        a.Y = e->QKd; a.ldy = 512; a.vt_block = 2; a.VT = e->VTd; a.S = nn; a.Spad = 128;
-        if (fused_proj()) ETD_TRY(proj_qkv(D0, Mq, w.pq, w.pk, w.pv, w.qkv_s.b, e->QKd, e->VTd, nn, 128, st));
-        else ETD_TRY(launch_linear(a, 1, st));
+        ETD_TRY(proj_qkv(D0, Mq, w.pq, w.pk, w.pv, w.qkv_s.b, e->QKd, e->VTd, nn, 128, st));
         AttnArgs t = {};
         t.Q = e->QKd; t.ldq = 512; t.q_seq_stride = (long long)nn * 512;
         t.K = e->QKd + 256; t.ldk = 512; t.k_seq_stride = (long long)nn * 512;
         t.VT = e->VTd; t.Spad = 128; t.O = e->AOd; t.ldo = 256; t.o_seq_stride = (long long)nn * 256;
         t.n_seq = nfr; t.Sq = nn; t.Sk = nn; t.scale_log2e = kScaleLog2e;
         ETD_TRY(launch_attn(t, st));
-        LinArgs o = {};
-        o.X = e->AOd; o.ldx = 256; o.W = w.o_s.W; o.bias = w.o_s.b; o.M = Mq; o.N = 256; o.K = 256; o.vt_block = -1;
-        o.R = D0; o.ldr = 256; o.gamma = w.g; o.beta = w.be; o.Y = D1; o.ldy = 256;
-        if (fused_post()) {
-          PostAttnArgs pa = {e->AOd, D0, 0, w.po, nullptr, w.o_s.b, w.g, w.be, nullptr, nullptr, D1, Mq};
-          ETD_TRY(launch_post_attn(pa, st));
-        } else if (fused_proj()) ETD_TRY(proj_ln(e->AOd, Mq, w.po, w.o_s.b, D0, 0, w.g, w.be, D1, st));
-        else ETD_TRY(launch_linear_ln(o, st));
+        ETD_TRY(proj_ln(e->AOd, Mq, w.po, w.o_s.b, D0, 0, w.g, w.be, D1, st));
         cross_in = D1;
       }
-      AttnArgs t = {};
+      AttnFragArgs f = {};
       if (l == 0) {
-        t.Q = e->q0; t.ldq = 256; t.q_seq_stride = 0;       // constant queries, precomputed at load
+        f.Q = e->q0; f.ldq = 256; f.q_seq_stride = 0;       // constant queries, precomputed at load
       } else {
-        LinArgs q = {};
-        q.X = cross_in; q.ldx = 256; q.W = w.q_c.W; q.bias = w.q_c.b; q.M = Mq; q.N = 256; q.K = 256; q.vt_block = -1;
-        q.Y = e->Qd; q.ldy = 256;
-        if (fused_proj()) {
-          ProjArgs pa = {};
-          pa.X = cross_in; pa.ldx = 256; pa.M = Mq; pa.nblk = 1;
-          pa.blk[0] = pblock(w.pqc, w.q_c.b, PROJ_ROW, e->Qd, 256);
-          ETD_TRY(launch_proj256(pa, st));
-        } else {
-          ETD_TRY(launch_linear(q, 1, st));
-        }
-        t.Q = e->Qd; t.ldq = 256; t.q_seq_stride = (long long)nn * 256;
+        ProjArgs pa = {};
+        pa.X = cross_in; pa.ldx = 256; pa.M = Mq; pa.nblk = 1;
+        pa.blk[0] = pblock(w.pqc, w.q_c.b, PROJ_ROW, e->Qd, 256);
+        ETD_TRY(launch_proj256(pa, st));
+        f.Q = e->Qd; f.ldq = 256; f.q_seq_stride = (long long)nn * 256;
       }
-      t.K = e->Kc + (size_t)l * e->MTe * 256; t.ldk = 256; t.k_seq_stride = 256LL * 256;
-      t.VT = e->VTc + (size_t)l * e->MTe * 256; t.Spad = 256;
-      t.O = e->AOd; t.ldo = 256; t.o_seq_stride = (long long)nn * 256;
-      t.n_seq = nfr; t.Sq = nn; t.Sk = 256; t.scale_log2e = kScaleLog2e;
-      if (fused_proj() && frag_attn()) {
-        AttnFragArgs f = {};
-        f.Q = t.Q; f.ldq = t.ldq; f.q_seq_stride = t.q_seq_stride; f.KV = e->KVcimg + (size_t)l * e->MTe * 512;
-        f.O = e->AOd; f.ldo = 256; f.o_seq_stride = (long long)nn * 256; f.n_seq = nfr; f.Sq = nn; f.Sk = 256; f.scale_log2e = kScaleLog2e;
-        ETD_TRY(launch_attn_frag(f, st));
-      } else {
-        ETD_TRY(launch_attn(t, st));
-      }
-      LinArgs o = {};
-      o.X = e->AOd; o.ldx = 256; o.W = w.o_c.W; o.bias = w.o_c.b; o.M = Mq; o.N = 256; o.K = 256; o.vt_block = -1;
-      o.R = cross_in; o.ldr = 256; o.r_mod = r_mod; o.gamma = w.g; o.beta = w.be; o.Y = D2; o.ldy = 256;
-      if (fused_post()) {
-        PostAttnArgs pa = {e->AOd, cross_in, r_mod, w.poc, w.ffn, w.o_c.b, w.g, w.be, w.f1.b, w.f2.b, D0, Mq};
-        ETD_TRY(launch_post_attn(pa, st));
-      } else {
-      if (fused_proj()) ETD_TRY(proj_ln(e->AOd, Mq, w.poc, w.o_c.b, cross_in, r_mod, w.g, w.be, D2, st));
-      else ETD_TRY(launch_linear_ln(o, st));
-      if (fused_ffn()) {
-        FfnArgs f = {D2, w.ffn, w.f1.b, w.f2.b, w.g, w.be, D0, Mq};
-        ETD_TRY(launch_ffn_fused(f, st));
-      } else {
-      LinArgs f1 = {};
-      f1.X = D2; f1.ldx = 256; f1.W = w.f1.W; f1.bias = w.f1.b; f1.M = Mq; f1.N = 512; f1.K = 256; f1.vt_block = -1; f1.relu = 1;
-      f1.Y = e->HFd; f1.ldy = 512;
-      ETD_TRY(launch_linear(f1, 1, st));
-      LinArgs f2 = {};
-      f2.X = e->HFd; f2.ldx = 512; f2.W = w.f2.W; f2.bias = w.f2.b; f2.M = Mq; f2.N = 256; f2.K = 512; f2.vt_block = -1;
-      f2.R = D2; f2.ldr = 256; f2.gamma = w.g; f2.beta = w.be; f2.Y = D0; f2.ldy = 256;
-      ETD_TRY(launch_linear_ln(f2, st));
-      }
-      }
+      f.KV = e->KVcimg + (size_t)l * e->MTe * 512;
+      f.O = e->AOd; f.ldo = 256; f.o_seq_stride = (long long)nn * 256; f.n_seq = nfr; f.Sq = nn; f.Sk = 256; f.scale_log2e = kScaleLog2e;
+      ETD_TRY(launch_attn_frag(f, st));
+      ETD_TRY(proj_ln(e->AOd, Mq, w.poc, w.o_c.b, cross_in, r_mod, w.g, w.be, D2, st));
+      FfnArgs ff = {D2, w.ffn, w.f1.b, w.f2.b, w.g, w.be, D0, Mq};
+      ETD_TRY(launch_ffn_fused(ff, st));
       ETD_TRY(tap(e, 4 + l, D0, (size_t)Mq * 512, first, st));
     }
     // freq -> time layout of this chunk, *16 + pos_embedding_time (amt_apc.py:203-205); optional A heads (:186-189)

@@ -207,28 +207,6 @@ __device__ __forceinline__ void pm_group(d16x8 (&buf)[2][4], unsigned addr, f32x
   } while (0)
   PM_MFMA(0);
   // gelu_fast (dec_epilogue.h) by hand, the same operations in the same order, one half behind each of the group's first two MFMAs
-#ifdef ETD_GELU_AS
-  float x0 = 0.f, tt = 0.f, ee = 0.f;
-  if constexpr (GELU) {
-    // the bias word has landed (nothing younger than group J + 1's fragments is outstanding); bb is an operand of the wait so that no use of it moves above
-    if constexpr (!LAST) asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(bb) : : "memory"); else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bb) : : "memory");
-    x0 = g[GR < 0 ? 0 : GR] + bb;
-    const float z0 = fabsf(x0) * 0.70710678118654752440f;
-    tt = __builtin_amdgcn_rcpf(fmaf(0.3275911f, z0, 1.f));
-    ee = __builtin_amdgcn_exp2f(-1.4426950408889634f * z0 * z0);
-    PM_PIN(x0); PM_PIN(tt); PM_PIN(ee);
-  }
-  PM_MFMA(1);
-  if constexpr (GELU) {
-    PM_PIN(x0); PM_PIN(tt); PM_PIN(ee);
-    float p = fmaf(1.061405429f, tt, -1.453152027f);
-    p = fmaf(p, tt, 1.421413741f); p = fmaf(p, tt, -0.284496736f); p = fmaf(p, tt, 0.254829592f);
-    const float er = fmaf(-p * tt, ee, 1.f);
-    float r0 = 0.5f * x0 * (1.f + copysignf(er, x0));
-    PM_PIN(r0);
-    g[GR < 0 ? 0 : GR] = r0;
-  }
-#else
   float x0 = 0.f, uu = 0.f, ss = 0.f, qq = 0.f;
   if constexpr (GELU) {
     // the bias word has landed (nothing younger than group J + 1's fragments is outstanding); bb is an operand of the wait so that no use of it moves above
@@ -249,7 +227,6 @@ __device__ __forceinline__ void pm_group(d16x8 (&buf)[2][4], unsigned addr, f32x
     PM_PIN(r0);
     g[GR < 0 ? 0 : GR] = r0;
   }
-#endif
   PM_MFMA(2);
   if constexpr (ND >= 1) pm_dma<D0>(nx);
   PM_MFMA(3);

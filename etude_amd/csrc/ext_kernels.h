@@ -50,7 +50,7 @@ struct LinArgs {
   e16* VT; int S, Spad;             // VT[((seq*4+head)*64+d)*Spad + pos], seq = m / S, pos = m % S
   int relu;
   long long* tbuf;                   // ETD_LIN_STAMP: per-workgroup clock64 stamps [grid][16] (wave 0)
-  int dbg;                           // timing ablations (ETD_LIN_DBG): 1 = skip the epilogue, 2 = skip the K loop (results are garbage); 4 = V^T block with direct 8-byte stores (correct, slower)
+  int dbg;                           // always 0 (the launchers set it): the bits of closed timing ablations.  The field and the kernels' tests of it go with the next change to k_linear's code
   // z-batching (several weight sets over the same X): per-blockIdx.z element offsets
   long long wz, bz, yz, vtz;
   // LayerNorm epilogue (N == 256): Y = LN(acc + bias + R) * gamma + beta
@@ -164,18 +164,6 @@ struct EncLayerArgs {
 int launch_enc_layer(const EncLayerArgs& a, hipStream_t st);
 // Wq, Wk, Wv, Wo: [256][256]; W1 [512][256]; W2 [256][512] (fp32, nn.Linear layout) -> dst[32 * 16384] e16
 void pack_enc_layer_weights(const float* Wq, const float* Wk, const float* Wv, const float* Wo, const float* W1, const float* W2, uint16_t* dst, uint16_t (*f2bf)(float));
-
-// ---- the part of a layer behind its attention in one launch (csrc/ext_fused.hip: k_post_attn):
-//      x1 = LN(R + AO Wo^T + bo) and, when Wffn is set, y = LN(x1 + FFN(x1)) with the same (shared) LayerNorm
-struct PostAttnArgs {
-  const e16* AO;              // [M][256] attention output
-  const e16* R; int r_mod;    // residual rows (row = r_mod > 0 ? m % r_mod : m)
-  const e16* Wo;              // fc_o as a k_proj256 block (pack_proj_weights, rows permuted)
-  const e16* Wffn;            // k_ffn_fused's stream, or null: stop after the first LayerNorm
-  const float* bo; const float* gamma; const float* beta; const float* b1; const float* b2;
-  e16* Y; int M;
-};
-int launch_post_attn(const PostAttnArgs& a, hipStream_t st);      // (-DETD_EXPERIMENTS builds only)
 
 // ---- attention over K / V fragment images (csrc/ext_fused.hip: k_attn_frag); 4 heads x 64
 struct AttnFragArgs {

@@ -537,7 +537,6 @@ __global__ __launch_bounds__(256, 2) void k_linear(LinArgs a) {
 
 // token tiles padded to a multiple of 8 (one per XCD), times the feature blocks of the launch
 static unsigned lin_grid_x(int M, int nby) { return (unsigned)(((M + 127) / 128 + 7) / 8 * 8 * nby); }
-static int lin_dbg() { static const int v = ETD_XENV("ETD_LIN_DBG") ? atoi(ETD_XENV("ETD_LIN_DBG")) : 0; return v; }
 int launch_linear(const LinArgs& a, int nz, hipStream_t st) {
   if (a.K % 128 || a.N % 256 || a.M <= 0) ETD_FAIL(ETD_EINVAL, "linear: bad shape M=%d N=%d K=%d", a.M, a.N, a.K);
   if (a.vt_block >= 0 && (a.S % 4 || a.Spad % 4 || !a.VT)) ETD_FAIL(ETD_EINVAL, "linear: bad V^T args");
@@ -550,7 +549,7 @@ int launch_linear(const LinArgs& a, int nz, hipStream_t st) {
   const int n_plain = a.vt_block >= 0 ? a.vt_block : nblk;
   if (a.vt_block >= 0 && a.vt_block != nblk - 1) ETD_FAIL(ETD_EINVAL, "linear: V^T block must be the last block");
   if (n_plain > 0) {
-    LinArgs b = a; b.nb0 = 0; b.dbg = lin_dbg(); b.nby = n_plain;
+    LinArgs b = a; b.nb0 = 0; b.dbg = 0; b.nby = n_plain;
     static int stamp_left = getenv("ETD_LIN_STAMP") ? atoi(getenv("ETD_LIN_STAMP")) : 0;
     const unsigned gx = lin_grid_x(a.M, n_plain);
     if (stamp_left > 0 && nz == 1) {
@@ -580,7 +579,7 @@ int launch_linear(const LinArgs& a, int nz, hipStream_t st) {
     hipLaunchKernelGGL(k_linear<0>, dim3(gx, 1, nz), dim3(256), 0, st, b);
   }
   if (a.vt_block >= 0) {
-    LinArgs b = a; b.nb0 = a.vt_block; b.dbg = lin_dbg(); b.nby = 1;
+    LinArgs b = a; b.nb0 = a.vt_block; b.dbg = 0; b.nby = 1;
     hipLaunchKernelGGL(k_linear<1>, dim3(lin_grid_x(a.M, 1), 1, nz), dim3(256), 0, st, b);
   }
   HIP_TRY(hipGetLastError());
@@ -594,7 +593,7 @@ int launch_linear_dec(const LinArgs& a, int dec_epi, hipStream_t st) {
   ETD_LAUNCH_FILTER("k_linear_dec");
   ProfScope ps("k_linear_dec", st, 2.0 * a.M * a.N * a.K, ((double)a.M * a.K + (double)a.N * a.K) * 2);
   dim3 g(lin_grid_x(a.M, a.N / 256), 1, 1);
-  LinArgs b = a; b.nb0 = 0; b.dbg = lin_dbg(); b.nby = a.N / 256;
+  LinArgs b = a; b.nb0 = 0; b.dbg = 0; b.nby = a.N / 256;
   switch (dec_epi) {
     case DEPI_BIAS: hipLaunchKernelGGL(k_linear<10 + DEPI_BIAS>, g, dim3(256), 0, st, b); break;
     case DEPI_GELU: hipLaunchKernelGGL(k_linear<10 + DEPI_GELU>, g, dim3(256), 0, st, b); break;
@@ -612,7 +611,7 @@ int launch_linear_ln(const LinArgs& a, hipStream_t st) {
   ETD_LAUNCH_FILTER("k_linear_ln");
   ProfScope ps("k_linear_ln", st, 2.0 * a.M * a.N * a.K, ((double)a.M * a.K + (double)a.N * a.K + 2.0 * a.M * a.N) * 2);
   dim3 g(lin_grid_x(a.M, 1), 1, 1);
-  LinArgs b = a; b.nb0 = 0; b.dbg = lin_dbg(); b.nby = 1;
+  LinArgs b = a; b.nb0 = 0; b.dbg = 0; b.nby = 1;
   hipLaunchKernelGGL(k_linear<2>, g, dim3(256), 0, st, b);
   HIP_TRY(hipGetLastError());
   return ETD_OK;

@@ -90,7 +90,7 @@ int g3_scale_log2(float bound) {
 // of 32: the four planes of a chunk (X hi / lo converted from fp32 on the way in, W hi / lo copied from the packed stream) sit in 40 KiB of LDS as 80-byte rows (16
 // consecutive rows start on 16 different 16-byte bank groups: conflict-free ds_read_b128 fragments); the next chunk's global loads are in flight behind the chunk's 24
 // MFMAs; two or three workgroups per CU cover each other's barriers.
-// KC = k per chunk (32; 64 is kept as a template instance for -DG3_KC_MAX=64 measurement builds).  LDS rows are KC + 8 elements (80 / 144 bytes: conflict-free ds_read_b128).
+// KC = k per chunk (32 is the one instance: launch_gemm3 records what 64 measured).  LDS rows are KC + 8 elements (80 bytes: conflict-free ds_read_b128).
 template <int KC> struct G3Geom { static constexpr int LDR = KC + 8, PLANE = 128 * LDR, NB = KC / 32; };
 
 __device__ __forceinline__ f32x16 mfma16h(f16x8 a, f16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
@@ -195,11 +195,6 @@ __device__ __forceinline__ void g3_store_block(const DGemmArgs& a, const f32x16 
   __builtin_amdgcn_wave_barrier();                  // the tile is rewritten by the next block
 }
 
-// G3_ABL (measurement builds, ETD_FLAGS_GEMM3=-DG3_ABL=n; results are then wrong on purpose): 2 = no global loads inside the K loop, 4 = no MFMAs, 5 = no LDS stores
-// inside the K loop, 6 = no epilogue stores
-#ifndef G3_ABL
-#define G3_ABL 0
-#endif
 template <int EPI, int KC>
 __global__ __launch_bounds__(256, 2) void k_gemm3(const float* __restrict__ p_X, int p_ldx, const f16* __restrict__ p_Wp, int p_M, int p_K, float p_xs, float p_inv, DGemmArgs a) {
   using G = G3Geom<KC>;
@@ -251,9 +246,6 @@ __global__ __launch_bounds__(256, 2) void k_gemm3(const float* __restrict__ p_X,
   for (int kc = 0; kc < nchunk; ++kc) {
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
-#if G3_ABL == 5
-      if (kc > 0) continue;
-#endif
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         f16x4 hi, lo;
@@ -264,9 +256,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm3(const float* __restrict__ p_X,
       *reinterpret_cast<u32x4*>(Wl + so + b * 32) = wlr[b][0]; *reinterpret_cast<u32x4*>(Wl + so + b * 32 + 8) = wlr[b][1];
     }
     __syncthreads();
-#if G3_ABL != 2
     if (kc + 1 < nchunk) gload(kc + 1);
-#endif
 #pragma unroll
     for (int ks = 0; ks < KC / 16; ++ks) {
       f16x8 wh[2], wl[2], xh[2], xl[2];
@@ -281,20 +271,13 @@ __global__ __launch_bounds__(256, 2) void k_gemm3(const float* __restrict__ p_X,
       for (int tf = 0; tf < 2; ++tf)
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt) {
-#if G3_ABL == 4
-          acc[tf][tt][0] += (float)wl[tf][0] * (float)xh[tt][0] + (float)wh[tf][1] * (float)xl[tt][1];
-#else
           acc[tf][tt] = mfma16h(wl[tf], xh[tt], acc[tf][tt]);
           acc[tf][tt] = mfma16h(wh[tf], xl[tt], acc[tf][tt]);
           acc[tf][tt] = mfma16h(wh[tf], xh[tt], acc[tf][tt]);
-#endif
         }
     }
     __syncthreads();
   }
-#if G3_ABL == 6
-  if (acc[0][0][0] != 1.2345e30f) return;
-#endif
   float* stg = reinterpret_cast<float*>(sm) + wave * (32 * 68);
 #pragma unroll
   for (int tt = 0; tt < 2; ++tt) {
@@ -302,8 +285,6 @@ __global__ __launch_bounds__(256, 2) void k_gemm3(const float* __restrict__ p_X,
     g3_store_block<EPI>(a, blk, p_inv, stg, m0 + (wave & 1) * 64 + tt * 32, p_M, nt * 128 + (wave >> 1) * 64, lane);
   }
 }
-
-bool g3_enabled() { static const bool on = !ETD_XENV("ETD_NO_GEMM3"); return on; }
 
 int launch_gemm3(const DGemmArgs& a, int epi, hipStream_t st) {
   if (a.M <= 0 || a.Npad % 128 || a.K % 32 || a.N > a.Npad || !a.Wp || !a.X || (a.ldx % 4) || ((uintptr_t)a.X & 15)) ETD_FAIL(ETD_EINVAL, "gemm3: bad shape M=%d N=%d Npad=%d K=%d", a.M, a.N, a.Npad, a.K);
@@ -316,16 +297,7 @@ int launch_gemm3(const DGemmArgs& a, int epi, hipStream_t st) {
   const float xs = ldexpf(1.f, a.x_log2), inv = ldexpf(1.f, -(a.x_log2 + a.w_log2));
 // K per chunk: 32 (40 KiB of LDS, 154 registers: three workgroups per CU) measured 10 % faster than 64 (72 KiB, two per CU) on every shape of tools/bench_gemm3.py:
 // what bounds this kernel is the dependent chain load -> split -> LDS -> barrier -> fragments -> MFMA of a workgroup, covered by the other workgroups of the CU, not a pipe
-#ifndef G3_KC_MAX
-#define G3_KC_MAX 32
-#endif
-#if G3_KC_MAX >= 64      // (the KC = 64 instances -- 72 KiB of static LDS, six epilogues -- exist only in such a measurement build)
-  const bool k64 = a.K % 64 == 0;
-#define G3_LAUNCH(E) do { if (k64) hipLaunchKernelGGL((k_gemm3<E, 64>), g, dim3(256), 0, st, a.X, a.ldx, (const f16*)a.Wp, a.M, a.K, xs, inv, a); \
-                          else hipLaunchKernelGGL((k_gemm3<E, 32>), g, dim3(256), 0, st, a.X, a.ldx, (const f16*)a.Wp, a.M, a.K, xs, inv, a); } while (0)
-#else
 #define G3_LAUNCH(E) hipLaunchKernelGGL((k_gemm3<E, 32>), g, dim3(256), 0, st, a.X, a.ldx, (const f16*)a.Wp, a.M, a.K, xs, inv, a)
-#endif
   switch (epi) {
     case DEPI_BIAS: G3_LAUNCH(DEPI_BIAS); break;
     case DEPI_GELU: G3_LAUNCH(DEPI_GELU); break;
@@ -432,11 +404,8 @@ __global__ __launch_bounds__(64 * G3S_WAVES) void k_gemm3_s(int p_M, int p_Npad,
 
 // Which kernel: the 32 x 32-tile kernel up to 512 rows, and up to 2 048 rows when the output is at most 512 wide -- there k_gemm3's 128 x 128 tiles are a handful of
 // workgroups walking the whole K one after the other (measured, tools/bench_gemm3.py step: attention.dense 21.8 -> 12.1 us at 576 rows, 22.3 -> 20.3 at 1 728; the
-// K = 2 048 down projection 70.9 -> 29.5 and 71.7 -> 54.7; QKV and up, 1 536 / 2 048 wide, are faster on the tiles from 576 rows up).  ETD_G3S_MAX_ROWS overrides the row limit.
-static int g3s_max_rows(int npad) {
-  static const int v = ETD_XENV("ETD_G3S_MAX_ROWS") ? atoi(ETD_XENV("ETD_G3S_MAX_ROWS")) : 0;
-  return v > 0 ? v : (npad <= 512 ? 2048 : 512);
-}
+// K = 2 048 down projection 70.9 -> 29.5 and 71.7 -> 54.7; QKV and up, 1 536 / 2 048 wide, are faster on the tiles from 576 rows up).
+static int g3s_max_rows(int npad) { return npad <= 512 ? 2048 : 512; }
 bool gemm3_s_takes(const DGemmArgs& a, int epi) {
   return a.Wp && a.M >= 2 && a.M <= g3s_max_rows(a.Npad) && a.K % (128 * G3S_WAVES) == 0 && a.Npad % 128 == 0 && epi != DEPI_PARTIAL && !a.Xb && !a.Yb && !a.Qb && a.k_splits <= 1;
 }

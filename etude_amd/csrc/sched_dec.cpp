@@ -132,11 +132,6 @@ extern "C" int etd_decoder_run_jobs(etd_dec* d, const etd_sched_cfg* cfg, const 
   long long n_steps = 0;
   std::vector<int32_t> ids, cls, at[4], a4cat, slots, Ts, tg, eos, lim, dn, no, rd, cnt;
 
-  // ETD_SCHED_STATS=1: host time this engine spends with its queue EMPTY at bar boundaries (from the moment the poll reports
-  // finished bars to the moment the next bars' launches have been issued), printed once per call
-  const bool want_stats = ETD_XENV("ETD_SCHED_STATS") != nullptr;
-  double host_gap_us = 0, poll_us = 0, read_us = 0, begin_us = 0; long long n_gaps = 0;
-  auto now_us = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   // start the next bar of the given jobs (prefill in as few passes as the row budget allows); jobs that are finished are retired
   auto start_bars = [&](std::vector<int>& batch) -> int {
     std::vector<int> pend;
@@ -184,9 +179,7 @@ extern "C" int etd_decoder_run_jobs(etd_dec* d, const etd_sched_cfg* cfg, const 
       const size_t M = ids.size();
       a4cat.resize(4 * M);
       for (int k = 0; k < 4; ++k) memcpy(a4cat.data() + (size_t)k * M, at[k].data(), M * 4);
-      const double tb0 = want_stats ? now_us() : 0;
       ETD_TRY(etd_decoder_begin_bars(d, (int)slots.size(), slots.data(), Ts.data(), ids.data(), cls.data(), a4cat.data(), tg.data(), eos.data(), lim.data(), stream));
-      if (want_stats) begin_us += now_us() - tb0;
     }
     return ETD_OK;
   };
@@ -209,7 +202,6 @@ extern "C" int etd_decoder_run_jobs(etd_dec* d, const etd_sched_cfg* cfg, const 
     std::sort(active.begin(), active.end(), [&](int a, int b) { return J[a].slot < J[b].slot; });
     slots.resize(na); dn.resize(na); no.resize(na);
     for (int i = 0; i < na; ++i) slots[i] = J[active[i]].slot;
-    const double t_poll0 = want_stats ? now_us() : 0;
     if (skip_poll) {
       // right after start_bars: a restarted stream has produced exactly its first token (the prefill's), the others are where
       // the last poll left them -- the step launches go out behind the prefill without a host round trip in between.  (A first
@@ -220,8 +212,6 @@ extern "C" int etd_decoder_run_jobs(etd_dec* d, const etd_sched_cfg* cfg, const 
       ETD_TRY(etd_decoder_poll(d, slots.data(), na, dn.data(), no.data(), stream));
       for (int i = 0; i < na; ++i) J[active[i]].n_out_known = no[i];
     }
-    const double t_poll1 = want_stats ? now_us() : 0;
-    poll_us += t_poll1 - t_poll0;
     std::vector<int> done_jobs;
     for (int i = 0; i < na; ++i) if (dn[i]) done_jobs.push_back(active[i]);
     if (!done_jobs.empty()) {
@@ -230,7 +220,6 @@ extern "C" int etd_decoder_run_jobs(etd_dec* d, const etd_sched_cfg* cfg, const 
       for (int i = 0; i < nd; ++i) ds[i] = J[done_jobs[i]].slot;
       rd.resize((size_t)nd * cap); cnt.resize(nd);
       ETD_TRY(etd_decoder_read_many(d, nd, ds.data(), rd.data(), cap, cnt.data(), stream));
-      if (want_stats) read_us += now_us() - t_poll1;
       std::vector<int> again;
       for (int i = 0; i < nd; ++i) {
         Job& jb = J[done_jobs[i]];
@@ -250,7 +239,6 @@ extern "C" int etd_decoder_run_jobs(etd_dec* d, const etd_sched_cfg* cfg, const 
       }
       ETD_TRY(start_bars(again));
       for (int ji : again) J[ji].n_out_known = 1;
-      if (want_stats) { host_gap_us += now_us() - t_poll1; ++n_gaps; }
       skip_poll = true;
       continue;                                   // refill, then step without another poll
     }
@@ -263,8 +251,6 @@ extern "C" int etd_decoder_run_jobs(etd_dec* d, const etd_sched_cfg* cfg, const 
     ETD_TRY(etd_decoder_step(d, slots.data(), na, nstep, stream));
     n_steps += nstep;
   }
-  if (want_stats) fprintf(stderr, "[sched] %lld bar boundaries: queue empty on the host side for %.0f us each on average (token read-back %.0f us, begin_bars call %.0f us, rest = prompt assembly); %.1f ms waiting in polls\n",
-                          n_gaps, n_gaps ? host_gap_us / n_gaps : 0.0, n_gaps ? read_us / n_gaps : 0.0, n_gaps ? begin_us / n_gaps : 0.0, poll_us / 1e3);
   // pack results: per job [n_bars_done, len_0 .. len_{n-1}, tokens of bar 0, tokens of bar 1, ...]
   long long pos = 0;
   for (int i = 0; i < n_jobs; ++i) {
