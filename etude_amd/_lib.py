@@ -344,6 +344,23 @@ SIGNATURES = {
     "etd_sep_debug_layer": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "etd_sep_debug_mask": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
     "etd_sep_debug_istft": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
+    "etd_sep_magnitudes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
+    "etd_septrain_create": (C.c_int, [C.POINTER(SepCfg), C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), c_i64_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "etd_septrain_destroy": (None, [C.c_void_p]),
+    "etd_septrain_workspace_bytes": (C.c_longlong, [C.c_void_p, C.c_int]),
+    "etd_septrain_step_flops": (C.c_double, [C.c_void_p, C.c_int]),
+    "etd_septrain_forward_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p]),
+    "etd_septrain_zero_grad": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "etd_septrain_grad_norm": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
+    "etd_septrain_step": (C.c_int, [C.c_void_p] + [C.c_double] * 5 + [C.POINTER(C.c_double), C.c_void_p]),
+    "etd_septrain_set_step": (C.c_int, [C.c_void_p, C.c_longlong]),
+    "etd_septrain_get_step": (C.c_longlong, [C.c_void_p]),
+    "etd_septrain_read": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "etd_septrain_write_moment": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "etd_septrain_debug_dx": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "etd_septrain_debug_dw": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "etd_septrain_debug_norm": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "etd_septrain_debug_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.POINTER(C.c_double), C.c_void_p, C.c_void_p]),
     "etd_dtrain_workspace_bytes": (C.c_longlong, [C.POINTER(DecCfg), C.c_int]),
     "etd_dtrain_create": (C.c_int, [C.POINTER(DecCfg), C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), c_i64_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.POINTER(C.c_void_p)]),

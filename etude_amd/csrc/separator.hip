@@ -780,6 +780,20 @@ extern "C" int etd_sep_run(etd_sep* h, const float* const* wav_ptrs, int n_songs
   return ETD_OK;
 }
 
+extern "C" int etd_sep_magnitudes(etd_sep* h, const float* wav_dev, long long N, float* mag_dev, void* stream) {
+  if (!h || !wav_dev || !mag_dev || N < 1) ETD_FAIL(ETD_EINVAL, "sep_magnitudes: null argument or N < 1");
+  if (N > (1LL << 32)) ETD_FAIL(ETD_EINVAL, "sep_magnitudes: N = %lld (> 2^32)", N);
+  hipStream_t st = (hipStream_t)stream;
+  const etd_sep_cfg& c = h->cfg;
+  const long long Tf = 1 + (N + c.n_fft) / c.hop, segs = (Tf + c.T - 1) / c.T;
+  ETD_TRY(sep_upload(h));
+  ETD_TRY(sep_reserve(h, ws_align((long long)c.n_channels * Tf * c.F * 8), st));
+  HIP_TRY(hipMemsetAsync(mag_dev, 0, (size_t)(segs * c.T * c.F * c.n_channels * 4), st));      // the frames past the song's last are zeros
+  ETD_TRY(sep_stft(h, wav_dev, N, Tf, (float2*)h->ws, c.F, mag_dev, st));
+  HIP_TRY(hipGetLastError());
+  return ETD_OK;
+}
+
 // ================================================================================================ test hooks
 extern "C" int etd_sep_debug_stft(etd_sep* h, const float* wav_dev, long long N, float* X_dev, void* stream) {
   if (!h || !wav_dev || !X_dev || N < 1) ETD_FAIL(ETD_EINVAL, "sep_debug_stft: null argument or N < 1");

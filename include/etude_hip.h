@@ -728,6 +728,40 @@ long long etd_sep_workspace_bytes(const etd_sep*, int n_songs, const int64_t* N_
 int etd_sep_run(etd_sep*, const float* const* wav_ptrs, int n_songs, const int64_t* N_host, float* const* out_ptrs, void* stream);
 /* FLOPs of the U-Nets of one segment, all instruments (2 per multiply-add that is not a structural zero) */
 double etd_sep_segment_flops(const etd_sep*);
+/* audio -> the U-Net's input: wav [n_channels][N] DEVICE fp32 -> mag [ceil(Tf / T)][T][F][n_channels] DEVICE fp32, |X| below bin F of the song's Tf =
+ * etd_sep_num_frames(N) frames, zeros past the last (step 2 of etd_sep_run, by the same kernel).  Synchronises `stream` when the workspace grows. */
+int etd_sep_magnitudes(etd_sep*, const float* wav_dev, long long N, float* mag_dev, void* stream);
+
+/* ---- training of the source separator (csrc/separator_train.hip; DESIGN.md 4n is the contract, tests/separator_train_np.py restates it) ----------------------
+ * The U-Nets of etd_sep in training mode (every norm on the batch's statistics), the L1 loss on the softmax estimates, every gradient and torch.optim.Adam, in fp32
+ * with no atomics: the same call gives the same bits.  One call is one batch of B units: mix [B][T][F][n_channels], target [n_instr][B][T][F][n_channels], DEVICE
+ * fp32, finite and non-negative (the caller checks).  cfg.workspace_bytes is the budget of the per-call workspace (0 = 16 GiB): a batch that does not fit is
+ * ETD_EINVAL with the bytes needed, before anything is launched; there is no sub-batching.  separation_exponent and mask_eps take no part. */
+typedef struct etd_septrain etd_septrain;
+/* etd_sep_create's arguments and refusals (no GPU is touched); max_units bounds B (max_units * n_instr <= 16384) */
+int etd_septrain_create(const etd_sep_cfg* cfg, int max_units, const char* const* instr_names, const char* const* names, const float* const* host_ptrs,
+                        const int64_t* numels, int n, etd_septrain** out);
+void etd_septrain_destroy(etd_septrain*);
+/* HOST ONLY: bytes of workspace a call with B units holds */
+long long etd_septrain_workspace_bytes(const etd_septrain*, int B);
+/* HOST ONLY: convolution FLOPs of one forward + backward of B units (forward, input gradients, weight gradients; structural zeros not counted) */
+double etd_septrain_step_flops(const etd_septrain*, int B);
+/* Forward in training mode, *loss = (1 / (I B T F C)) sum |softmax_i(logits) mix - target_i| (an fp64 sum of per-workgroup fp32 partials in a fixed order), and, with
+ * backward != 0, loss_scale x its gradient ADDED to the handle's gradients.  frozen_stats != 0: the norms use the running statistics, which then do not move;
+ * otherwise they move once, r <- 0.99 r + 0.01 batch (biased variance).  Synchronous. */
+int etd_septrain_forward_backward(etd_septrain*, const float* mix_dev, const float* target_dev, int B, double loss_scale, int frozen_stats, int backward,
+                                  double* loss, void* stream);
+int etd_septrain_zero_grad(etd_septrain*, void* stream);
+/* L2 norm over all gradients (fp64 partial sums in a fixed order).  Synchronous. */
+int etd_septrain_grad_norm(etd_septrain*, double* norm, void* stream);
+/* clip_grad_norm_ when max_norm > 0, then one torch.optim.Adam step of the single-tensor path (no weight decay; bias corrections and 1 - beta in double on the
+ * host).  *norm (may be NULL) = the norm before clipping.  The gradients are left as they are (clipped), not zeroed. */
+int etd_septrain_step(etd_septrain*, double max_norm, double lr, double beta1, double beta2, double eps, double* norm, void* stream);
+int etd_septrain_set_step(etd_septrain*, long long step);
+long long etd_septrain_get_step(const etd_septrain*);
+/* One tensor by its state key, fp32 to / from the host.  which = 0: the state (running statistics included), 1: gradient, 2: exp_avg, 3: exp_avg_sq.  Synchronous. */
+int etd_septrain_read(etd_septrain*, const char* name, int which, float* out_host, long long numel, void* stream);
+int etd_septrain_write_moment(etd_septrain*, const char* name, int second, const float* in_host, long long numel, void* stream);
 
 #ifdef __cplusplus
 }

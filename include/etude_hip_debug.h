@@ -263,6 +263,21 @@ int etd_sep_debug_layer(etd_sep*, int instr, int kind, int layer, const float* x
 int etd_sep_debug_mask(etd_sep*, const float* logits_dev, const float* mag_dev, const float* X_dev, long long Tf, float* Y_dev, void* stream);
 int etd_sep_debug_istft(etd_sep*, const float* Y_dev, long long N, float* out_dev, void* stream);
 
+/* stage taps of separator training (csrc/separator_train.hip): each backward kernel on a caller's input, with the launchers etd_septrain_forward_backward uses.
+ * DEVICE fp32; every tensor holds B x n_instr units back to back, unit u = b * n_instr + instrument, each with its instrument's weights.
+ *   dx    kind 0: encoder layer l (2 .. 6): dy [T >> l][F >> l][Cout] -> out0 [T >> (l-1)][F >> (l-1)][Cin].  kind 1: decoder j: dy [2H][2W][Cout] (H = T >> (7-j))
+ *         -> out0 = the skip's gradient [H][W][C skip], out1 = the gradient of decoder j - 1's output [H][W][..] (j > 1).  kind 2: the head: dy [T][F][C] -> [T][F][1]
+ *   dw    the weight gradient of encoder `layer` (x0 = its input; layer 1: [B] units, shared by the instruments), decoder `layer` (x0 = skip, x1 = up, dy = the
+ *         gradient of the transposed convolution's output) or the head, ADDED to dw [n_instr][the state tensor's shape]
+ *   norm  norm n (1 .. 12) on x: the batch statistics, y = the normalised output (encoder: ELU(norm(x)); decoder: norm(ELU(x))), stats (may be NULL) = [mean | biased
+ *         variance], [n_instr][C] each; with dy: dx = the gradient at x, and gamma's / beta's gradients are ADDED to the handle's.  Moves no running statistic.
+ *   loss  logits [B][n_instr][T][F][C], mix [B][..], target [n_instr][B][..] -> *loss and dlogits = loss_scale x the gradient.  Synchronous. */
+int etd_septrain_debug_dx(etd_septrain*, int kind, int layer, const float* dy_dev, int B, float* out0_dev, float* out1_dev, void* stream);
+int etd_septrain_debug_dw(etd_septrain*, int kind, int layer, const float* x0_dev, const float* x1_dev, const float* dy_dev, int B, float* dw_dev, void* stream);
+int etd_septrain_debug_norm(etd_septrain*, int norm, const float* x_dev, int B, const float* dy_dev, float* y_dev, float* dx_dev, float* stats_dev, void* stream);
+int etd_septrain_debug_loss(etd_septrain*, const float* logits_dev, const float* mix_dev, const float* target_dev, int B, double loss_scale, double* loss,
+                            float* dlogits_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
