@@ -103,6 +103,10 @@ class SepCfg(_SizedCfg):
                 + [("separation_exponent", C.c_int), ("mask_eps", C.c_float), ("bn_eps", C.c_float), ("workspace_bytes", C.c_longlong)])
 
 
+class SepDataCfg(_SizedCfg):
+    _fields_ = [("struct_bytes", C.c_int)] + [(n, C.c_int) for n in ("n_instr", "n_channels", "T", "F")] + [("max_bytes", C.c_longlong)]
+
+
 class AttrCfg(_SizedCfg):
     _fields_ = [("struct_bytes", C.c_int), ("type_pos", C.c_int), ("type_note", C.c_int), ("type_duration", C.c_int)]
 
@@ -361,6 +365,19 @@ SIGNATURES = {
     "etd_septrain_debug_dw": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "etd_septrain_debug_norm": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "etd_septrain_debug_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.POINTER(C.c_double), C.c_void_p, C.c_void_p]),
+    "etd_septrain_set_dropout": (C.c_int, [C.c_void_p, C.c_double, C.c_ulonglong]),
+    "etd_septrain_set_dropout_calls": (C.c_int, [C.c_void_p, C.c_longlong]),
+    "etd_septrain_get_dropout_calls": (C.c_longlong, [C.c_void_p]),
+    "etd_septrain_debug_dropout": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p]),
+    "etd_sepdata_create": (C.c_int, [C.POINTER(SepDataCfg), C.POINTER(C.c_void_p)]),
+    "etd_sepdata_destroy": (None, [C.c_void_p]),
+    "etd_sepdata_track_bytes": (C.c_longlong, [C.c_void_p, C.c_longlong]),
+    "etd_sepdata_bytes": (C.c_longlong, [C.c_void_p]),
+    "etd_sepdata_num_tracks": (C.c_int, [C.c_void_p]),
+    "etd_sepdata_track_frames": (C.c_longlong, [C.c_void_p, C.c_int]),
+    "etd_sepdata_add_track": (C.c_int, [C.c_void_p, C.c_longlong, C.POINTER(C.c_void_p), c_int_p]),
+    "etd_sepdata_sum_stems": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_longlong, C.c_void_p, C.c_void_p]),
+    "etd_sepdata_gather": (C.c_int, [C.c_void_p, C.c_int, c_i32_p, c_i64_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p]),
     "etd_dtrain_workspace_bytes": (C.c_longlong, [C.POINTER(DecCfg), C.c_int]),
     "etd_dtrain_create": (C.c_int, [C.POINTER(DecCfg), C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), c_i64_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.POINTER(C.c_void_p)]),

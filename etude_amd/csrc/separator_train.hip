@@ -12,6 +12,8 @@
 //   k_st_ew                 normalise + ELU (encoder), ELU + normalise (decoder) and their backward passes, xhat recomputed from the saved pre-norm tensor
 //   k_st_loss               softmax over the instruments, |s_i mix - target_i| partials and dlogits in one pass
 //   k_st_sumsq / k_st_adam  the gradient norm and Adam, after dec_train.hip
+//   k_st_dropout            decoder dropout (levels 1 .. 3, only when p > 0): y <- keep ? y s : 0 in place with a Philox4x32-10 mask that is a function of the element
+//                           index, the level, the seed and the call counter; the backward pass runs the same kernel on dy, so no mask is stored
 //
 // fp32 throughout, no atomics: every sum runs in an order the shapes fix, so a call gives the same bits every time.
 #include "separator_train.h"
@@ -381,6 +383,38 @@ __global__ void k_st_ew(const StEw a) {
   }
 }
 
+// ================================================================================================ dropout
+// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3"): ten rounds of two 32 x 32 -> 64 multiplies, the key bumped by the Weyl constants
+// between rounds.  Integer multiplies, shifts and xors only.
+__device__ __forceinline__ void st_philox(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned out[4]) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0, hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+// one thread per four consecutive elements 4 g .. 4 g + 3 (one Philox block): out[e] = word(e & 3) < thr ? x[e] * s : 0.  out may be x.  vec: both pointers are
+// 16-byte aligned, so a whole group moves as one float4.
+__global__ __launch_bounds__(256) void k_st_dropout(const float* x, float* out, long long total, unsigned j, unsigned call, unsigned k0, unsigned k1, unsigned thr,
+                                                   float s, int vec) {
+  const long long g = (long long)blockIdx.x * 256 + threadIdx.x, e0 = 4 * g;
+  if (e0 >= total) return;
+  unsigned w[4];
+  st_philox((unsigned)(g & 0xffffffffLL), (unsigned)(g >> 32), j, call, k0, k1, w);
+  if (vec && e0 + 3 < total) {
+    float4 v = *reinterpret_cast<const float4*>(x + e0);
+    v.x = w[0] < thr ? v.x * s : 0.f; v.y = w[1] < thr ? v.y * s : 0.f; v.z = w[2] < thr ? v.z * s : 0.f; v.w = w[3] < thr ? v.w * s : 0.f;
+    *reinterpret_cast<float4*>(out + e0) = v;
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (e0 + i < total) out[e0 + i] = w[i] < thr ? x[e0 + i] * s : 0.f;
+  }
+}
+
 // ================================================================================================ loss
 // one (b, t, f, c) per thread: softmax over the instruments, sum_i |s_i mix - target_i|, dlogits_i = s_i (g_i - sum_j s_j g_j) with g_i = scale sign(s_i mix -
 // target_i) mix (sign(0) = 0).  The workgroup's 256 losses are added by a fixed tree.
@@ -478,6 +512,7 @@ struct etd_septrain {
   double* norm_part = nullptr;
   bool pack_dirty = true;
   long long step = 0;
+  double drop_p = 0.0; unsigned long long drop_seed = 0; long long drop_calls = 0;      // decoder dropout: off at p = 0; drop_calls counts the backward calls with p > 0
   char* ws = nullptr; long long ws_bytes = 0;
   int normC(int n) const { return n <= ETD_SEP_LEVELS ? Cenc[n] : Cdout[n - ETD_SEP_LEVELS]; }
 };
@@ -799,6 +834,20 @@ int st_loss(etd_septrain* h, const float* logits, const float* mix, const float*
   return ETD_OK;
 }
 
+// y_j <- keep ? y_j s : 0 (or the same on dy_j) over n elements of decoder level j at call counter `call`; s and the threshold are formed in double
+int st_dropout(const etd_septrain* h, int j, long long call, const float* x, float* out, long long n, hipStream_t st) {
+  const float s = (float)(1.0 / (1.0 - h->drop_p));
+  const double t = floor((1.0 - h->drop_p) * 4294967296.0);
+  const unsigned thr = t >= 4294967295.0 ? 0xffffffffu : (unsigned)t;
+  const long long blocks = ((n + 3) / 4 + 255) / 256;
+  if (blocks > 0x7fffffffLL) ETD_FAIL(ETD_EINVAL, "separator training: dropout needs %lld workgroups (> 2^31 - 1)", blocks);
+  const int vec = (((uintptr_t)x | (uintptr_t)out) & 15) == 0;
+  hipLaunchKernelGGL(k_st_dropout, dim3((unsigned)blocks), dim3(256), 0, st, x, out, n, (unsigned)j, (unsigned)(call & 0xffffffffLL),
+                     (unsigned)(h->drop_seed & 0xffffffffULL), (unsigned)(h->drop_seed >> 32), thr, s, vec);
+  return ETD_OK;
+}
+#define ST_DROP_LEVELS 3
+
 long long st_pos_enc(const etd_septrain* h, int l) { return (long long)(h->cfg.T >> l) * (h->cfg.F >> l); }
 long long st_pos_dec(const etd_septrain* h, int j) { return (long long)(h->cfg.T >> (6 - j)) * (h->cfg.F >> (6 - j)); }
 
@@ -933,6 +982,7 @@ extern "C" int etd_septrain_forward_backward(etd_septrain* h, const float* mix, 
   float* ws = (float*)h->ws;
   float* cpart = ws + p.cpart;
   const int U = B * h->I, L = ETD_SEP_LEVELS;
+  const bool drop = backward && h->drop_p > 0.0;      // never in the loss-only (validation) path
   if (frozen_stats) hipLaunchKernelGGL(k_st_frozen, dim3(st_grid(h->NS)), dim3(256), 0, st, h->P + h->n_train, h->P + h->n_train + h->NS, h->cfg.bn_eps, (int)h->NS, h->S, h->S + h->NS);
   // ---- forward
   for (int l = 1; l <= L; ++l) {
@@ -944,6 +994,7 @@ extern "C" int etd_septrain_forward_backward(etd_septrain* h, const float* mix, 
     ETD_TRY(st_fwd_decoder(h, j, ws + p.pre[7 - j], j > 1 ? ws + p.y[j - 1] : nullptr, ws + p.v[j], U, st));
     if (!frozen_stats) ETD_TRY(st_stats(h, L + j, ws + p.v[j], st_pos_dec(h, j), B, cpart, st));
     ETD_TRY(st_ew(h, ST_EW_DEC, L + j, ws + p.v[j], nullptr, nullptr, ws + p.y[j], h->szD[j], U, st));
+    if (drop && j <= ST_DROP_LEVELS) ETD_TRY(st_dropout(h, j, h->drop_calls, ws + p.y[j], ws + p.y[j], U * h->szD[j], st));      // after the statistics, before any reader
   }
   ETD_TRY(st_fwd_head(h, ws + p.y[L], ws + p.logits, U, st));
   if (!frozen_stats) {      // the running statistics move once per call
@@ -962,6 +1013,7 @@ extern "C" int etd_septrain_forward_backward(etd_septrain* h, const float* mix, 
   ETD_TRY(st_dx_head(h, cur, other, U, st));
   std::swap(cur, other);
   for (int j = L; j >= 1; --j) {      // cur = dy_j
+    if (drop && j <= ST_DROP_LEVELS) ETD_TRY(st_dropout(h, j, h->drop_calls, cur, cur, U * h->szD[j], st));      // the forward's mask, regenerated
     ETD_TRY(st_norm_bwd(h, L + j, ws + p.v[j], cur, nullptr, cur, st_pos_dec(h, j), B, frozen_stats, cpart, st));      // cur = dv_j
     ETD_TRY(st_bias_grad(h, cur, st_pos_dec(h, j), h->Cdout[j], B, cpart, h->G + h->dec_b[j].off, st));
     ETD_TRY(st_dw_decoder(h, j, ws + p.pre[7 - j], j > 1 ? ws + p.y[j - 1] : nullptr, cur, B, part, h->G + h->dec_w[j].off, st));
@@ -979,8 +1031,22 @@ extern "C" int etd_septrain_forward_backward(etd_septrain* h, const float* mix, 
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(st));
+  if (drop) h->drop_calls += 1;
   return ETD_OK;
 }
+
+extern "C" int etd_septrain_set_dropout(etd_septrain* h, double p, unsigned long long seed) {
+  if (!h) ETD_FAIL(ETD_EINVAL, "septrain_set_dropout: null handle");
+  if (!(p >= 0.0 && p < 1.0)) ETD_FAIL(ETD_EINVAL, "septrain_set_dropout: p = %g is outside [0, 1)", p);
+  h->drop_p = p; h->drop_seed = seed;
+  return ETD_OK;
+}
+extern "C" int etd_septrain_set_dropout_calls(etd_septrain* h, long long calls) {
+  if (!h || calls < 0) ETD_FAIL(ETD_EINVAL, "septrain_set_dropout_calls: null handle or a negative count");
+  h->drop_calls = calls;
+  return ETD_OK;
+}
+extern "C" long long etd_septrain_get_dropout_calls(const etd_septrain* h) { return h ? h->drop_calls : ETD_EINVAL; }
 
 extern "C" int etd_septrain_zero_grad(etd_septrain* h, void* stream) {
   if (!h) ETD_FAIL(ETD_EINVAL, "septrain_zero_grad: null handle");
@@ -1137,4 +1203,17 @@ extern "C" int etd_septrain_debug_loss(etd_septrain* h, const float* logits_dev,
   ETD_TRY(st_upload(h));
   ETD_TRY(st_reserve(h, p.total_bytes, st));
   return st_loss(h, logits_dev, mix_dev, target_dev, B, loss_scale, (float*)h->ws + p.lpart, p.loss_blocks, dlogits_dev, loss_out, st);
+}
+
+extern "C" int etd_septrain_debug_dropout(etd_septrain* h, int j, const float* y_dev, int B, long long numel, long long call, float* out_dev, void* stream) {
+  if (!h || !y_dev || !out_dev) ETD_FAIL(ETD_EINVAL, "septrain_debug_dropout: null argument");
+  if (j < 1 || j > ST_DROP_LEVELS) ETD_FAIL(ETD_EINVAL, "septrain_debug_dropout: level j = %d outside 1 .. %d", j, ST_DROP_LEVELS);
+  if (call < 0) ETD_FAIL(ETD_EINVAL, "septrain_debug_dropout: call = %lld is negative", call);
+  StPlan p;
+  ETD_TRY(st_check_batch(h, B, &p, "septrain_debug_dropout"));
+  const long long full = (long long)B * h->I * h->szD[j];
+  if (numel < 0 || numel > full) ETD_FAIL(ETD_EINVAL, "septrain_debug_dropout: numel = %lld outside 0 .. %lld", numel, full);
+  ETD_TRY(st_dropout(h, j, call, y_dev, out_dev, numel ? numel : full, (hipStream_t)stream));
+  HIP_TRY(hipGetLastError());
+  return ETD_OK;
 }

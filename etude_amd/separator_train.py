@@ -8,8 +8,10 @@
     tr.save("separator.pth"); sep = tr.to_separator()
 
 One call is one batch: every norm uses the batch's statistics, so the ``B`` units of a call must fit ``workspace_bytes`` together (there is no sub-batching).  The loss
-is Spleeter's L1 between the softmax estimates ``softmax_i(logits) mix`` and the true magnitudes, modelled on Spleeter and not pinned to it; its decoder dropout is
-not matched, and there is no data pipeline.  DESIGN.md 4n is the contract; tests/separator_train_np.py restates it.
+is Spleeter's L1 between the softmax estimates ``softmax_i(logits) mix`` and the true magnitudes, modelled on Spleeter and not pinned to it.  ``dropout=p`` drops
+the output of the norms of decoder levels 1 .. 3 in every ``loss_and_backward`` call (never in ``loss``) with a counter-based mask that is never stored.  Batches
+across a corpus, augmentation, the epoch loop and checkpoints are ``etude_amd.separator_data``'s.  DESIGN.md 4n is the contract; tests/separator_train_np.py and
+tests/separator_data_np.py restate it.
 """
 from __future__ import annotations
 
@@ -35,12 +37,13 @@ def _p(t: Optional[torch.Tensor]):
 class SeparatorTrainer(Engine):
     """fp32 training of the separator's U-Nets on the GPU.  ``state=None`` draws ``init_separator_state(config, seed)``; otherwise ``state`` is a separator state
     (``expected_keys``).  ``max_units`` bounds the units of one call, ``workspace_bytes`` the device workspace a call may hold (``workspace_total_bytes(B)`` tells
-    what ``B`` units need).  ``max_norm=None``: no clipping.  Constructing needs no GPU; training does: there is no CPU path."""
+    what ``B`` units need).  ``max_norm=None``: no clipping.  ``dropout`` in [0, 1) is the decoder's drop rate (Spleeter: 0.5; 0 launches nothing), ``dropout_seed`` the
+    key of its mask; the mask's call counter travels in ``optimizer_state_dict()["dropout_calls"]``.  Constructing needs no GPU; training does: there is no CPU path."""
     _destroy = "etd_septrain_destroy"
 
     def __init__(self, config: Optional[SeparatorConfig] = None, state: Optional[Dict] = None, seed: int = 0, device: Union[str, torch.device] = "cuda",
                  max_units: int = 8, workspace_bytes: int = 16 << 30, lr: float = 1e-4, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
-                 max_norm: Optional[float] = None):
+                 max_norm: Optional[float] = None, dropout: float = 0.0, dropout_seed: int = 0):
         self.config = cfg = config or SeparatorConfig()
         cfg.check()
         if workspace_bytes < 1:
@@ -52,6 +55,10 @@ class SeparatorTrainer(Engine):
             raise ValueError(f"SeparatorTrainer: lr and eps must be >= 0 and the betas in [0, 1), got {lr}, {betas}, {eps}")
         if max_norm is not None and not max_norm > 0:
             raise ValueError(f"SeparatorTrainer: max_norm must be positive or None, got {max_norm}")
+        if not (0.0 <= float(dropout) < 1.0):
+            raise ValueError(f"SeparatorTrainer: dropout must be in [0, 1), got {dropout}")
+        if not 0 <= int(dropout_seed) < 2 ** 64:
+            raise ValueError(f"SeparatorTrainer: dropout_seed must be in 0 .. 2^64 - 1, got {dropout_seed}")
         if state is None:
             state = init_separator_state(cfg, seed)
         check_separator_state(state, cfg)
@@ -64,6 +71,7 @@ class SeparatorTrainer(Engine):
         self.max_units, self.workspace_bytes = int(max_units), int(workspace_bytes)
         self.lr, self.betas, self.eps, self.max_norm = float(lr), (float(betas[0]), float(betas[1])), float(eps), max_norm
         self.global_step = 0
+        self.dropout, self.dropout_seed = float(dropout), int(dropout_seed)
         ccfg = _lib.SepCfg(n_instr=ni, n_channels=cfg.n_channels, n_fft=cfg.n_fft, hop=cfg.hop, T=cfg.T, F=cfg.F, filters=(C.c_int * LEVELS)(*cfg.conv_n_filters),
                            separation_exponent=int(cfg.separation_exponent), mask_eps=cfg.mask_eps, bn_eps=cfg.bn_eps, workspace_bytes=self.workspace_bytes)
         self._lib = _lib.lib()
@@ -73,6 +81,13 @@ class SeparatorTrainer(Engine):
         _lib.check(self._lib.etd_septrain_create(C.byref(ccfg), self.max_units, instr, names, ptrs, numels, n, C.byref(h)), "etd_septrain_create")
         del keep
         self._adopt(h)
+        if self.dropout > 0.0:      # (at 0 the handle is left as it was created)
+            _lib.check(self._lib.etd_septrain_set_dropout(self.h, self.dropout, self.dropout_seed), "etd_septrain_set_dropout")
+
+    @property
+    def dropout_calls(self) -> int:
+        """the ``loss_and_backward`` calls that dropped so far: the fourth word of the mask's counter"""
+        return nonneg(self._lib.etd_septrain_get_dropout_calls(self.h), "etd_septrain_get_dropout_calls")
 
     # ------------------------------------------------------------------ host arithmetic
     def workspace_total_bytes(self, B: int) -> int:
@@ -172,7 +187,8 @@ class SeparatorTrainer(Engine):
         return self._read(1, self._trainable())
 
     def optimizer_state_dict(self) -> Dict[str, object]:
-        return {"step": self.global_step, "exp_avg": self._read(2, self._trainable()), "exp_avg_sq": self._read(3, self._trainable())}
+        return {"step": self.global_step, "exp_avg": self._read(2, self._trainable()), "exp_avg_sq": self._read(3, self._trainable()),
+                "dropout_calls": self.dropout_calls}
 
     def load_optimizer_state_dict(self, sd: Dict[str, object]) -> None:
         dev = self._device()
@@ -184,6 +200,7 @@ class SeparatorTrainer(Engine):
                         raise ValueError(f"{key}[{k!r}] has shape {a.shape}, expected {self._shapes[k]}")
                     _lib.check(self._lib.etd_septrain_write_moment(self.h, k.encode(), second, a.ctypes.data, a.size, self._stream(dev)), "etd_septrain_write_moment")
             _lib.check(self._lib.etd_septrain_set_step(self.h, int(sd["step"])), "etd_septrain_set_step")
+        _lib.check(self._lib.etd_septrain_set_dropout_calls(self.h, int(sd.get("dropout_calls", 0))), "etd_septrain_set_dropout_calls")
         self.global_step = int(sd["step"])
 
     def save(self, path) -> None:
@@ -246,6 +263,17 @@ class SeparatorTrainer(Engine):
             _lib.check(self._lib.etd_septrain_debug_norm(self.h, int(n), _p(x), int(x.shape[0]), _p(dy), _p(y), _p(dx), _p(stats), self._stream(dev)),
                        "etd_septrain_debug_norm")
         return y, stats, dx
+
+    def debug_dropout(self, j: int, y: torch.Tensor, call: int, numel: int = 0) -> torch.Tensor:
+        """the mask of decoder level j (1 .. 3) at call counter ``call`` on y [B][I][..]: keep ? y * s : 0.  ``numel`` > 0: only that many leading elements are
+        written (a count that is no multiple of 4 ends inside a Philox block); the rest of the result keeps y."""
+        dev = self._device()
+        y = y.to(dev, torch.float32).contiguous()
+        out = y.clone()
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.etd_septrain_debug_dropout(self.h, int(j), _p(y), int(y.shape[0]), int(numel), int(call), _p(out), self._stream(dev)),
+                       "etd_septrain_debug_dropout")
+        return out
 
     def debug_loss(self, logits: torch.Tensor, mix: torch.Tensor, target: torch.Tensor, loss_scale: float = 1.0):
         """logits [B][I][T][F][C], mix [B][..], target [I][B][..] -> (loss, dlogits [B][I][..])"""

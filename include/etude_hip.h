@@ -762,6 +762,46 @@ long long etd_septrain_get_step(const etd_septrain*);
 /* One tensor by its state key, fp32 to / from the host.  which = 0: the state (running statistics included), 1: gradient, 2: exp_avg, 3: exp_avg_sq.  Synchronous. */
 int etd_septrain_read(etd_septrain*, const char* name, int which, float* out_host, long long numel, void* stream);
 int etd_septrain_write_moment(etd_septrain*, const char* name, int second, const float* in_host, long long numel, void* stream);
+/* Decoder dropout (off at p = 0, the default): in every forward_backward call with backward != 0 the output y_j of the norm of decoder level j = 1, 2, 3
+ * becomes keep ? y_j * s : 0 before anything reads it, s = 1 / (1 - p) formed in double and rounded once; dy_j is multiplied by the same mask before the norm's
+ * backward.  The batch statistics are taken before the drop; a call with backward == 0 never drops.  The mask is Philox4x32-10 and is never stored: for flat
+ * element e of y_j [B][n_instr][pos][C] the counter is (lo32(e >> 2), hi32(e >> 2), j, lo32(calls)), the key (lo32(seed), hi32(seed)), the element takes output
+ * word e & 3 and is kept iff word < min(2^32 - 1, floor((1 - p) 2^32)).  `calls` goes up by one per dropping call.  p outside [0, 1) is ETD_EINVAL.  HOST ONLY. */
+int etd_septrain_set_dropout(etd_septrain*, double p, unsigned long long seed);
+int etd_septrain_set_dropout_calls(etd_septrain*, long long calls);
+long long etd_septrain_get_dropout_calls(const etd_septrain*);
+
+/* ------------------------------------------------------------------ training data of the source separator (csrc/separator_data.hip; DESIGN.md 4o is the contract,
+ * tests/separator_data_np.py restates it).  The handle keeps the magnitudes of every track on the device, S [1 + n_instr][frames][F][n_channels] (0: the mix, then
+ * the stems; frames = Tf rounded up to a multiple of T, zeros past Tf: what etd_sep_magnitudes writes), and cuts augmented training batches from them in one launch.
+ * The device never draws a random number: the caller passes the draws. */
+typedef struct etd_sepdata etd_sepdata;
+typedef struct {
+  int struct_bytes;            /* sizeof(etd_sepdata_cfg) of the caller: a mismatch is ETD_EINVAL */
+  int n_instr, n_channels;     /* etd_sep_cfg's */
+  int T, F;                    /* frames and bins of a unit: positive, T <= 65536 */
+  long long max_bytes;         /* budget of the tracks' device memory; 0 = 16 GiB */
+} etd_sepdata_cfg;
+int etd_sepdata_create(const etd_sepdata_cfg* cfg, etd_sepdata** out);      /* needs no GPU */
+void etd_sepdata_destroy(etd_sepdata*);
+/* HOST ONLY: bytes a track of Tf frames holds; the bytes all tracks hold; the number of tracks; the frames Tf of one track (negative = ETD_EINVAL) */
+long long etd_sepdata_track_bytes(const etd_sepdata*, long long Tf);
+long long etd_sepdata_bytes(const etd_sepdata*);
+int etd_sepdata_num_tracks(const etd_sepdata*);
+long long etd_sepdata_track_frames(const etd_sepdata*, int track);
+/* A new track of Tf frames: *mag_dev = its uninitialised S on the DEVICE, for the caller to fill (1 + n_instr calls of etd_sep_magnitudes, each writing
+ * [frames][F][n_channels]); *track = its id.  A track that does not fit the budget is ETD_EINVAL with the bytes needed, and nothing is allocated. */
+int etd_sepdata_add_track(etd_sepdata*, long long Tf, float** mag_dev, int* track);
+/* mix[e] = ((stem_0[e] + stem_1[e]) + ...) in fp32, in instrument order, e < n.  stems: HOST array of n_instr DEVICE pointers. */
+int etd_sepdata_sum_stems(etd_sepdata*, const float* const* stems_dev, long long n, float* mix_dev, void* stream);
+/* One launch: unit u = (track[u], t0[u], a[u], q[u]) -> mix [B][T][F][C] and target [n_instr][B][T][F][C] (DEVICE fp32), the same draw for the mix and every stem.
+ * With W = frames t0 .. t0 + T - 1 of the track (zeros from Tf on): time stretch to T' = floor(T a) frames by align-corners linear interpolation, centre crop
+ * (T' >= T) or zero pad (T' < T) back to T; then the frequency axis to F' = floor(F q) bins likewise, bins f < min(F, F') kept and zeros above.  Positions and weights
+ * are formed in double and the weight rounded once to fp32; lerp(u, v, w) = fmaf(w, v - u, u), time first; a = q = 1 copies the frames.  A unit's output depends on
+ * its draw and its track alone.  Arrays are HOST.  ETD_EINVAL naming the unit, before the launch, for a track id outside the handle, t0 outside 0 .. Tf - 1, a
+ * non-finite factor, T' < 2 or F' < 2. */
+int etd_sepdata_gather(etd_sepdata*, int B, const int32_t* track, const int64_t* t0, const double* a, const double* q, float* mix_dev, float* target_dev,
+                       void* stream);
 
 #ifdef __cplusplus
 }

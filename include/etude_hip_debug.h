@@ -277,6 +277,9 @@ int etd_septrain_debug_dw(etd_septrain*, int kind, int layer, const float* x0_de
 int etd_septrain_debug_norm(etd_septrain*, int norm, const float* x_dev, int B, const float* dy_dev, float* y_dev, float* dx_dev, float* stats_dev, void* stream);
 int etd_septrain_debug_loss(etd_septrain*, const float* logits_dev, const float* mix_dev, const float* target_dev, int B, double loss_scale, double* loss,
                             float* dlogits_dev, void* stream);
+/* the dropout mask of decoder level j (1 .. 3) at call counter `call`, with the handle's p and seed: out = keep ? y * s : 0 over the first numel elements of
+ * y [B][n_instr][pos][C] (numel = 0: all of them; a count that is no multiple of 4 ends inside a Philox block).  out may be y.  Moves no counter. */
+int etd_septrain_debug_dropout(etd_septrain*, int j, const float* y_dev, int B, long long numel, long long call, float* out_dev, void* stream);
 
 #ifdef __cplusplus
 }
