@@ -14,6 +14,7 @@ Drop-in surfaces (same names/signatures as the reference):
     etude_amd.SeparatorTrainer / training_segments  (no counterpart: the separator's training -- batch statistics, decoder dropout, L1 loss, backward, Adam; csrc/separator_train.hip)
     etude_amd.SegmentSampler / fit_separator / validate_separator / save_separator_checkpoint / load_separator_checkpoint  (its data and loop: tracks kept on the device,
                                     augmented batches in one launch, epochs, validation, resumable checkpoints; csrc/separator_data.hip)
+    etude_amd.BSSEval / BSSEvalConfig / evaluate_separator  (its quality: BSS Eval v4 SDR / ISR / SIR / SAR per source, modelled on museval, parity unpinned; csrc/bss.hip)
     etude_amd.AlignFeatures         <- the feature extraction in front of the aligner (synctoolbox's pitch filterbank, chroma, DLNCO; csrc/alignfeat.hip)
     etude_amd.TuningEstimator / estimate_tuning  <- synctoolbox's estimate_tuning, the first call of AudioAligner._compute_alignment (csrc/tuning.hip)
     etude_amd.AudioAligner          <- etude.data.aligner.AudioAligner behind the feature extraction (exact DTW, transposition search, wp.json cache; csrc/dtw.hip)
@@ -42,7 +43,8 @@ __all__ = ["AMTAPC_Extractor", "EtudeDecoder", "EtudeDecoderConfig", "load_etude
            "evaluate_many", "BarAttributes", "EtudeDataset", "split_into_bars", "calculate_bin_edges", "save_bin_edges", "load_bin_edges", "attribute_adherence",
            "DecoderTrainer", "cosine_schedule_with_warmup", "init_decoder_state", "NoteRenderer", "PianoVoice", "default_note_renderer", "align_notes_many",
            "read_midi_notes", "save_wav", "StemSeparator", "SeparatorConfig", "init_separator_state", "load_separator_state", "structuralize_audio_many", "SeparatorTrainer", "training_segments",
-           "SegmentSampler", "fit_separator", "validate_separator", "save_separator_checkpoint", "load_separator_checkpoint"]
+           "SegmentSampler", "fit_separator", "validate_separator", "save_separator_checkpoint", "load_separator_checkpoint",
+           "BSSEval", "BSSEvalConfig", "evaluate_separator"]
 
 
 def __getattr__(name):
@@ -104,6 +106,12 @@ def __getattr__(name):
         from . import separator_data
         return getattr(separator_data, {"fit_separator": "fit", "validate_separator": "validate", "save_separator_checkpoint": "save_checkpoint",
                                         "load_separator_checkpoint": "load_checkpoint"}[name])
+    if name in ("BSSEval", "BSSEvalConfig"):
+        from . import bss
+        return getattr(bss, name)
+    if name == "evaluate_separator":
+        from .separator_eval import evaluate_separator
+        return evaluate_separator
     if name in ("StemSeparator", "SeparatorConfig", "init_separator_state", "load_separator_state"):
         from . import separator
         return getattr(separator, name)

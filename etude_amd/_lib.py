@@ -107,6 +107,10 @@ class SepDataCfg(_SizedCfg):
     _fields_ = [("struct_bytes", C.c_int)] + [(n, C.c_int) for n in ("n_instr", "n_channels", "T", "F")] + [("max_bytes", C.c_longlong)]
 
 
+class BssCfg(_SizedCfg):
+    _fields_ = [("struct_bytes", C.c_int), ("filters_len", C.c_int), ("window", C.c_int), ("hop", C.c_int), ("workspace_bytes", C.c_longlong)]
+
+
 class AttrCfg(_SizedCfg):
     _fields_ = [("struct_bytes", C.c_int), ("type_pos", C.c_int), ("type_note", C.c_int), ("type_duration", C.c_int)]
 
@@ -378,6 +382,17 @@ SIGNATURES = {
     "etd_sepdata_add_track": (C.c_int, [C.c_void_p, C.c_longlong, C.POINTER(C.c_void_p), c_int_p]),
     "etd_sepdata_sum_stems": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_longlong, C.c_void_p, C.c_void_p]),
     "etd_sepdata_gather": (C.c_int, [C.c_void_p, C.c_int, c_i32_p, c_i64_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "etd_bss_create": (C.c_int, [C.POINTER(BssCfg), C.POINTER(C.c_void_p)]),
+    "etd_bss_destroy": (None, [C.c_void_p]),
+    "etd_bss_num_windows": (C.c_longlong, [C.c_void_p, C.c_longlong]),
+    "etd_bss_workspace_bytes": (C.c_longlong, [C.c_void_p, C.c_int, C.c_int, C.c_longlong]),
+    "etd_bss_run": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), c_i32_p, c_i32_p, c_i64_p, C.POINTER(C.c_void_p),
+                              C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]),
+    "etd_bss_debug_corr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "etd_bss_debug_solve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "etd_bss_debug_filters": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "etd_bss_debug_project": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "etd_bss_debug_timing": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]),
     "etd_dtrain_workspace_bytes": (C.c_longlong, [C.POINTER(DecCfg), C.c_int]),
     "etd_dtrain_create": (C.c_int, [C.POINTER(DecCfg), C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), c_i64_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.POINTER(C.c_void_p)]),

@@ -803,6 +803,33 @@ int etd_sepdata_sum_stems(etd_sepdata*, const float* const* stems_dev, long long
 int etd_sepdata_gather(etd_sepdata*, int B, const int32_t* track, const int64_t* t0, const double* a, const double* q, float* mix_dev, float* target_dev,
                        void* stream);
 
+/* ------------------------------------------------------------------ BSS Eval v4 scores of a separation (csrc/bss.hip; DESIGN.md 4p is the contract, tests/bss_np.py
+ * restates it).  References and estimates [J][C][N] -> the eight energies per (source, window) that SDR, ISR, SIR, SAR and the plain SDR are formed from; the metrics
+ * themselves are host arithmetic (etude_amd/bss.py).  This project's own contract, modelled on museval's bss_eval (v4, images, time-invariant filters): parity with
+ * museval is unpinned, its lstsq fallback and its framewise-filter and permutation modes are not restated.  Everything is fp64 on the fp64 matrix cores, no atomics. */
+typedef struct etd_bss etd_bss;
+typedef struct {
+  int struct_bytes;            /* sizeof(etd_bss_cfg) of the caller: a mismatch is ETD_EINVAL */
+  int filters_len;             /* L = 512: a multiple of 16 in 16 .. 512 */
+  int window;                  /* 44100: samples of a window, >= filters_len */
+  int hop;                     /* 44100: 1 .. window */
+  long long workspace_bytes;   /* budget of the handle's device workspace; 0 = 4 GiB */
+} etd_bss_cfg;
+int etd_bss_create(const etd_bss_cfg* cfg, etd_bss** out);      /* needs no GPU */
+void etd_bss_destroy(etd_bss*);
+/* HOST ONLY: windows of a track of N samples: floor((N - window + hop) / hop), 1 for N < window (negative = ETD_EINVAL) */
+long long etd_bss_num_windows(const etd_bss*, long long N);
+/* HOST ONLY: bytes of workspace a track of J sources (1 .. 8), C channels (1, 2) and N samples (>= filters_len, J C filters_len <= 8192) needs at the least: the
+ * correlation partials, the matrices, the filters and one window's projections; negative = ETD_EINVAL */
+long long etd_bss_workspace_bytes(const etd_bss*, int J, int C, long long N);
+/* ref_ptrs / est_ptrs: HOST arrays of n_tracks DEVICE pointers, track b planar [J_host[b]][C_host[b]][N_host[b]] fp32 (finite: the caller checks).  E_ptrs[b]: DEVICE
+ * fp64 [J][nwin][8] (E0 .. E7 of DESIGN.md 4p; NaN in a silent window and for a singular track), silent_ptrs[b]: DEVICE int32 [nwin], status_dev: DEVICE int32
+ * [n_tracks] (1 = a Cholesky pivot was <= 0 or not finite).  A shape outside the limits, or a track that needs more than the budget (the message carries its bytes),
+ * is ETD_EINVAL before anything is launched, and the handle serves the next call.  Tracks run one after another in one workspace: a track's bits are the same alone,
+ * at any place in a batch, under any budget that admits it and from run to run.  Synchronises `stream` when the workspace grows. */
+int etd_bss_run(etd_bss*, int n_tracks, const float* const* ref_ptrs, const float* const* est_ptrs, const int32_t* J_host, const int32_t* C_host, const int64_t* N_host,
+                double* const* E_ptrs, int32_t* const* silent_ptrs, int32_t* status_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -281,6 +281,20 @@ int etd_septrain_debug_loss(etd_septrain*, const float* logits_dev, const float*
  * y [B][n_instr][pos][C] (numel = 0: all of them; a count that is no multiple of 4 ends inside a Philox block).  out may be y.  Moves no counter. */
 int etd_septrain_debug_dropout(etd_septrain*, int j, const float* y_dev, int B, long long numel, long long call, float* out_dev, void* stream);
 
+/* stage taps of BSS Eval (csrc/bss.hip), each stage on a caller's input with the launchers etd_bss_run uses.  DEVICE buffers; fp64 unless said.
+ *   corr     ref, est [J][C][N] fp32 -> r [S][S][L] (r[p][q][l] = sum_n x_p[n] x_q[n + l]) and d [S][S][L] (d[p][e][l] = sum_n x_p[n] y_e[n + l]), S = J C
+ *   solve    a caller's SPD matrix G [n][n] (n <= 8192; not changed) and right-hand sides [n][m] (m <= 16) -> x [n][m] and *status (1 = a pivot <= 0 or not finite)
+ *   filters  ref, est -> A [S L][S] and B [J][C L][C]
+ *   project  ref, window `window_index` of the track and a caller's A, B -> ps [J][C][Wout], pa [J][C][Wout], Wout = the window's length + L - 1
+ *   timing   on != 0: the following etd_bss_run calls time their stages with events; stage_ms5 (may be NULL) receives the last run's milliseconds of the
+ *            correlations, the factorisations, the substitutions, the projections and the energies */
+int etd_bss_debug_corr(etd_bss*, const float* ref_dev, const float* est_dev, int J, int C, long long N, double* r_dev, double* d_dev, void* stream);
+int etd_bss_debug_solve(etd_bss*, const double* G_dev, const double* rhs_dev, int n, int m, double* x_dev, int32_t* status_dev, void* stream);
+int etd_bss_debug_filters(etd_bss*, const float* ref_dev, const float* est_dev, int J, int C, long long N, double* A_dev, double* B_dev, int32_t* status_dev, void* stream);
+int etd_bss_debug_project(etd_bss*, const float* ref_dev, int J, int C, long long N, int window_index, const double* A_dev, const double* B_dev, double* ps_dev,
+                          double* pa_dev, void* stream);
+int etd_bss_debug_timing(etd_bss*, int on, double* stage_ms5);
+
 #ifdef __cplusplus
 }
 #endif

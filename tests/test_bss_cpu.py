@@ -1,0 +1,287 @@
+"""BSS Eval without a GPU: the numpy restatement against itself (two routes, closed forms, window arithmetic, wrong variants), the host side of
+``etude_amd.BSSEval`` (refusals, metrics, aggregation) and the symbols.
+
+AGREE_DB is the bound on |direct - fft| of a metric in dB, AGREE_E the relative one on an energy.  Reasoning: the two routes solve the same normal equations in
+fp64; their filters differ by about cond(G) 2^-52 (cond = 3.6 for the white references here, 755 for the AR(1) ones: 1.7e-13), the smallest error term (e_artif, some
+20 dB below the source, so 10 x smaller in amplitude) carries that as a relative 1e-11 of its energy at the most, and 10 log10 turns a relative 1e-11 into 4.3e-11 dB.
+Measured: 5e-14 dB and 8e-15."""
+import sys
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, str(Path(__file__).resolve().parent))
+import bss_np as B      # noqa: E402
+
+AGREE_DB = 1e-10
+AGREE_E = 1e-11
+L, W = 32, 512
+
+
+def make_track(J, C, N, colour, seed=0, noise=0.05):
+    """references white or AR(1)-coloured (pole 0.9); estimates = a mix of the references + a 3-sample delay + a channel swap + noise: all four error terms non-zero"""
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal((J, C, N))
+    if colour:
+        for n in range(1, N):
+            x[:, :, n] += 0.9 * x[:, :, n - 1]
+    mix = rng.uniform(-0.3, 0.3, (J, J)) + np.eye(J)
+    est = np.einsum("ij,jcn->icn", mix, x)
+    est[:, :, 3:] = 0.7 * est[:, :, 3:] + 0.3 * est[:, :, :-3]
+    if C == 2:
+        est = est + 0.1 * est[:, ::-1]
+    est = est + noise * x.std() * rng.standard_normal(est.shape)
+    return x.astype(np.float32), est.astype(np.float32)
+
+
+@pytest.fixture(scope="module", params=[0, 1], ids=["white", "ar1"])
+def case(request):
+    ref, est = make_track(3, 2, 4 * W + 37, request.param)
+    return ref, est, B.evaluate(ref, est, L, W, W)
+
+
+def test_direct_and_fft_routes_agree(case):
+    ref, est, a = case
+    f = B.evaluate(ref, est, L, W, W, route="fft")
+    assert not a["silent"].any() and a["status"] == 0
+    rel = np.abs(a["E"] - f["E"]) / np.abs(a["E"])
+    print("energies: largest relative difference", rel.max())
+    assert rel.max() <= AGREE_E
+    for k in B.NAMES:
+        diff = np.abs(a["metrics"][k] - f["metrics"][k]).max()
+        print(k, "range", a["metrics"][k].min(), a["metrics"][k].max(), "diff", diff)
+        assert diff <= AGREE_DB
+        assert 3 < a["metrics"][k].min() and a["metrics"][k].max() < 40
+
+
+def test_filters_satisfy_the_normal_equations(case):
+    _, _, a = case
+    r, d = a["r"], a["d"]
+    S = r.shape[0]
+    G, D = B.gram(r), d.transpose(0, 2, 1).reshape(S * L, S)
+    res = np.abs(G @ a["A"] - D).max() / np.abs(D).max()
+    assert res < 1e-12, res
+    for j in range(3):
+        sel = np.arange(2 * j, 2 * j + 2)
+        Dj = d[np.ix_(sel, sel)].transpose(0, 2, 1).reshape(2 * L, 2)
+        assert np.abs(B.gram(r, sel) @ a["B"][j] - Dj).max() / np.abs(Dj).max() < 1e-12
+    assert np.allclose(G, G.T, rtol=0, atol=0)
+
+
+def test_sdr_equals_plain_sdr_up_to_rounding(case):
+    """e_spat + e_interf + e_artif = est - ref on the window, and the tail carries nothing of either"""
+    _, _, a = case
+    assert np.abs(a["metrics"]["sdr"] - a["metrics"]["sdr_plain"]).max() < 1e-9
+
+
+def test_closed_form_identity_and_gain():
+    ref, _ = make_track(2, 2, 3 * W, 1, seed=1)
+    a = B.evaluate(ref, ref, L, W, W)
+    assert (a["E"][..., 7] == 0).all() and np.isposinf(a["metrics"]["sdr_plain"]).all()
+    g = np.float32(0.75)
+    b = B.evaluate(ref, g * ref, L, W, W)
+    assert np.abs(b["metrics"]["sdr_plain"] - (-20 * np.log10(abs(1 - 0.75)))).max() < 1e-6      # (the fp32 product g ref rounds: 2^-24 relative)
+
+
+def test_closed_form_spatial_filter_goes_to_e_spat():
+    """est_j = a 4-tap FIR mixing the channels of ref_j lies in the span B_j projects on, except where a window cuts it: the projection takes the references as zero
+    outside the window, so the first 3 samples of a window miss the taps that reach back, at most 3 / W of the estimate's energy (-22.3 dB), which is what e_artif
+    and e_interf may hold; e_spat holds the filter's whole deviation from the identity (ISR below 15 dB)"""
+    ref, _ = make_track(2, 2, 3 * W, 1, seed=2)
+    h = np.array([[[0.5, 0.2, -0.1, 0.05], [0.3, -0.2, 0.1, 0.0]], [[-0.2, 0.1, 0.0, 0.05], [0.6, 0.1, -0.05, 0.02]]])     # [out c][in c][tap]
+    est = np.zeros(ref.shape)
+    for j in range(2):
+        for c in range(2):
+            for ci in range(2):
+                est[j, c] += np.convolve(ref[j, ci].astype(np.float64), h[c, ci])[:ref.shape[2]]
+    m = B.evaluate(ref, est.astype(np.float32), L, W, W)["metrics"]
+    print("isr", m["isr"].max(), "sir", m["sir"].min(), "sar", m["sar"].min())
+    assert m["isr"].max() < 15
+    edge = 10 * np.log10(W / 3)
+    assert m["sir"].min() > edge and m["sar"].min() > edge and min(m["sir"].min(), m["sar"].min()) > m["isr"].max() + 10
+
+
+def test_closed_form_interference_leaves_nothing_in_e_artif():
+    ref, _ = make_track(2, 2, 3 * W, 0, seed=3)
+    est = ref.astype(np.float64).copy()
+    est[0] += 0.3 * ref[1]
+    est[1] += 0.3 * ref[0]
+    m = B.evaluate(ref, est.astype(np.float32), L, W, W)["metrics"]
+    print("sir", m["sir"], "sar", m["sar"].min())
+    assert m["sar"].min() > 100                   # (fp32 rounding of est alone: 2^-24 relative is 144 dB)
+    assert np.abs(m["sir"] - (-20 * np.log10(0.3))).max() < 1.0
+
+
+def test_window_arithmetic():
+    assert B.window_bounds(4 * W + 37, W, W) == [(0, W), (W, 2 * W), (2 * W, 3 * W), (3 * W, 4 * W + 37)]
+    assert B.window_bounds(W - 5, W, W) == [(0, W - 5)]
+    assert B.window_bounds(2 * W, W, W // 2) == [(0, W), (W // 2, W + W // 2), (W, 2 * W)]
+    assert B.num_windows(W, W, W) == 1 and B.num_windows(2 * W - 1, W, W) == 1
+    ref, est = make_track(2, 1, W - 5, 0, seed=4)
+    a = B.evaluate(ref, est, L, W, W)
+    assert a["E"].shape == (2, 1, 8) and np.isfinite(a["E"]).all()
+    ref, est = make_track(2, 1, 2 * W, 0, seed=4)
+    assert B.evaluate(ref, est, L, W, W // 2)["E"].shape == (2, 3, 8)
+
+
+def test_silent_rule_for_a_reference_and_for_an_estimate():
+    ref, est = make_track(2, 2, 4 * W, 0, seed=5)
+    r2, e2 = ref.copy(), est.copy()
+    r2[1, :, W:2 * W] = 0            # a reference source silent on all its channels in window 1
+    e2[0, :, 3 * W:] = 0             # an estimate source silent in window 3
+    r2[0, 0, 2 * W:3 * W] = 0        # one channel only: not silent
+    a = B.evaluate(r2, e2, L, W, W)
+    assert a["silent"].tolist() == [False, True, False, True]
+    for k in B.NAMES:
+        assert np.isnan(a["metrics"][k][:, [1, 3]]).all() and np.isfinite(a["metrics"][k][:, [0, 2]]).all()
+    assert np.isfinite(a["scores"]["sdr"]).all()
+
+
+@pytest.mark.parametrize("variant", ["lag_sign", "no_tail", "b_for_a", "per_window", "neighbours"])
+def test_wrong_variants_are_told_apart(case, variant):
+    ref, est, a = case
+    w = B.evaluate(ref, est, L, W, W, variant=variant)
+    with np.errstate(invalid="ignore"):
+        moved = max(float(np.nanmax(np.abs(a["metrics"][k] - w["metrics"][k]))) for k in B.NAMES)
+    print(variant, "moves a metric by", moved, "dB")
+    assert moved > 100 * AGREE_DB
+
+
+def test_singular_track_is_marked():
+    ref, est = make_track(2, 1, 2 * W, 0, seed=6)
+    ref[1] = ref[0]                   # two identical references: G is singular up to eps
+    a = B.evaluate(ref, est, L, W, W)
+    if a["status"]:
+        assert np.isnan(a["E"]).all()
+    G = np.eye(4)
+    G[2, 2] = -1.0
+    x, st = B.spd_solve(G, np.ones((4, 1)))
+    assert st == 1 and np.isnan(x).all()
+
+
+def test_hand_written_cholesky_runs_in_longdouble():
+    rng = np.random.default_rng(7)
+    M = rng.standard_normal((40, 40))
+    G = (M @ M.T + 40 * np.eye(40)).astype(np.longdouble)
+    D = rng.standard_normal((40, 3)).astype(np.longdouble)
+    x, st = B.spd_solve(G, D)
+    assert st == 0 and x.dtype == np.longdouble
+    assert np.abs(np.asarray(x, np.float64) - np.linalg.solve(np.asarray(G, np.float64), np.asarray(D, np.float64))).max() < 1e-13
+
+
+# ---------------------------------------------------------------------------------------------------------------- the package's host side
+def test_config_refusals():
+    from etude_amd.bss import BSSEvalConfig
+    BSSEvalConfig().check()
+    BSSEvalConfig(filters_len=48, window=48, hop=1).check()
+    for kw in (dict(filters_len=0), dict(filters_len=24), dict(filters_len=528), dict(filters_len=64, window=63), dict(hop=0), dict(window=100, hop=101, filters_len=16),
+               dict(workspace_bytes=0)):
+        with pytest.raises(ValueError):
+            BSSEvalConfig(**kw).check()
+
+
+def test_library_refuses_a_bad_config_and_sizes_a_workspace_without_a_device():
+    import ctypes as C
+    from etude_amd import _lib
+    from etude_amd.bss import BSSEval, BSSEvalConfig
+    lib = _lib.lib()
+    for kw in (dict(filters_len=24, window=100, hop=10), dict(filters_len=32, window=16, hop=1), dict(filters_len=32, window=64, hop=65)):
+        h = C.c_void_p()
+        cfg = _lib.BssCfg(workspace_bytes=0, **kw)
+        assert lib.etd_bss_create(C.byref(cfg), C.byref(h)) == -22
+        assert b"bss_create" in lib.etd_last_error()
+    eng = BSSEval(BSSEvalConfig(filters_len=L, window=W, hop=W))
+    assert eng.num_windows(4 * W + 37) == 4 and eng.num_windows(W - 5) == 1
+    assert eng.window_bounds(4 * W + 37) == B.window_bounds(4 * W + 37, W, W)
+    small, big = eng.workspace_bytes(1, 1, 4 * W), eng.workspace_bytes(3, 2, 4 * W)
+    assert 0 < small < big
+    n = 6 * L
+    assert big >= 8 * n * n                       # the matrix alone
+    for bad in ((0, 1, 4 * W), (9, 1, 4 * W), (1, 3, 4 * W), (1, 1, L - 1)):
+        with pytest.raises(_lib.EtudeHipError):
+            eng.workspace_bytes(*bad)
+    full = BSSEval()
+    need = full.workspace_bytes(5, 2, 180 * 44100)
+    assert 8 * 5120 * 5120 < need < (4 << 30)     # the issue's track fits the default budget
+    assert full.workspace_bytes(8, 2, 44100 * 10) > 8 * 8192 * 8192      # S L = 8192, the largest order the limits on J, C and L allow
+    eng.close()
+    full.close()
+
+
+def test_shape_refusals_name_the_track():
+    from etude_amd.bss import BSSEvalConfig, check_shapes
+    cfg = BSSEvalConfig(filters_len=L, window=W, hop=W)
+    ok = np.zeros((2, 2, 4 * W), np.float32)
+    assert check_shapes(cfg, [ok, ok], [ok, ok]) == [(2, 2, 4 * W)] * 2
+    cases = [(np.zeros((2, 2, 100), np.float32), np.zeros((2, 2, 101), np.float32)), (np.zeros((9, 1, 4 * W)),) * 2, (np.zeros((1, 3, 4 * W)),) * 2,
+             (np.zeros((1, 1, L - 1)),) * 2, (np.zeros((4 * W,)),) * 2]
+    for a, b in cases:
+        with pytest.raises(ValueError, match="track 1"):
+            check_shapes(cfg, [ok, a], [ok, b])
+    with pytest.raises(ValueError):
+        check_shapes(cfg, [ok], [ok, ok])
+
+
+def test_a_missing_gpu_and_a_track_over_the_budget_are_refused():
+    from etude_amd import _lib
+    from etude_amd.bss import BSSEval, BSSEvalConfig
+    eng = BSSEval(BSSEvalConfig(filters_len=L, window=W, hop=W), device="cpu")      # there is no CPU path, with or without a GPU in the machine
+    ok = np.zeros((2, 2, 4 * W), np.float32)
+    with pytest.raises(_lib.EtudeHipError, match="needs a ROCm GPU"):
+        eng.evaluate_many([ok], [ok])
+    need = eng.workspace_bytes(2, 2, 4 * W)
+    with pytest.raises(ValueError, match=f"track 0: needs {need} bytes"):             # before a device is asked for
+        BSSEval(BSSEvalConfig(filters_len=L, window=W, hop=W, workspace_bytes=4096), device="cpu").evaluate_many([ok], [ok])
+
+
+def test_host_metrics_match_the_restatement_and_aggregate():
+    from etude_amd.bss import aggregate, decibels, metrics_from_energies, nanmedian_rows
+    rng = np.random.default_rng(8)
+    E = rng.random((3, 5, 8))
+    E[1, 2] = np.nan
+    E[0, 0, 7] = 0.0
+    m, want = metrics_from_energies(E), B.metrics(E)
+    for k in B.NAMES:
+        assert np.array_equal(m[k], want[k], equal_nan=True)
+    assert np.isposinf(m["sdr_plain"][0, 0]) and np.isnan(m["sdr"][1, 2])
+    assert np.isnan(decibels(np.nan, 1.0))
+    assert np.array_equal(nanmedian_rows(m["sdr"]), B.track_scores(want)["sdr"])
+    tracks = [dict(scores={k: np.array([1.0 + t, np.nan if t == 1 else 2.0 * t]) for k in B.NAMES}) for t in range(3)]
+    tracks.append(dict(scores={k: np.array([np.nan, np.nan]) for k in B.NAMES}))
+    agg = aggregate(tracks)
+    assert agg["n_tracks"] == 4 and agg["n_skipped"] == 1
+    assert agg["sdr"].tolist() == [2.0, 2.0]      # medians of (1, 2, 3) and of (0, 4)
+    with pytest.raises(ValueError):
+        aggregate([tracks[0], dict(scores={k: np.zeros(3) for k in B.NAMES})])
+
+
+def test_evaluate_separator_refuses_a_rate_or_channel_mismatch_before_a_device():
+    from etude_amd.separator import SeparatorConfig
+    from etude_amd.separator_eval import evaluate_separator
+
+    class Sep:      # the checks read the config alone and come before anything touches a device
+        config = SeparatorConfig(instruments=("a", "b"))
+        device = "cuda"
+    x = np.zeros((2, 5000), np.float32)
+    with pytest.raises(ValueError, match="22050 Hz"):
+        evaluate_separator(Sep(), [(x, dict(a=x, b=x))], bss=object(), sample_rate=22050)
+    with pytest.raises(ValueError, match="n_channels"):
+        evaluate_separator(Sep(), [(x, dict(a=x[:1], b=x))], bss=object())
+    with pytest.raises(ValueError, match="no stem"):
+        evaluate_separator(Sep(), [(x, dict(a=x))], bss=object())
+    with pytest.raises(ValueError, match="not among"):
+        evaluate_separator(Sep(), [(x, dict(a=x, b=x))], bss=object(), instruments=["c"])
+
+
+def test_symbols():
+    import etude_amd
+    from etude_amd import _lib
+    for n in ("BSSEval", "BSSEvalConfig", "evaluate_separator"):
+        assert n in etude_amd.__all__ and getattr(etude_amd, n) is not None
+    lib = _lib.lib()
+    for n in ("etd_bss_create", "etd_bss_destroy", "etd_bss_num_windows", "etd_bss_workspace_bytes", "etd_bss_run", "etd_bss_debug_corr", "etd_bss_debug_solve",
+              "etd_bss_debug_filters", "etd_bss_debug_project", "etd_bss_debug_timing"):
+        assert n in _lib.SIGNATURES and hasattr(lib, n)
+    header = (Path(__file__).resolve().parent.parent / "include" / "etude_hip.h").read_text()
+    assert "etd_bss_run" in header and "etd_bss_debug" not in header
