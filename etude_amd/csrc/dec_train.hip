@@ -20,6 +20,7 @@
 #include "etude_hip_debug.h"
 #include "host_util.h"
 #include "prof.h"
+#include "train_optim.h"
 
 #define ETD_IGNORE_LABEL (-100)
 
@@ -494,30 +495,8 @@ __global__ __launch_bounds__(256) void k_tembed_grad(const float* __restrict__ s
 // ================================================================================================
 // optimizer
 // ================================================================================================
-#define TN_BLOCKS 256
-// fp64 partial sums of squares: block b owns elements [b * chunk, (b + 1) * chunk), thread t every 256th of them; the 256 thread sums are added in thread order
-__global__ __launch_bounds__(256) void k_tsumsq(const float* __restrict__ g, long long n, long long chunk, double* __restrict__ partial) {
-  __shared__ double ps[256];
-  const long long b0 = (long long)blockIdx.x * chunk, b1 = b0 + chunk < n ? b0 + chunk : n;
-  double a = 0.0;
-  for (long long i = b0 + threadIdx.x; i < b1; i += 256) { const double v = (double)g[i]; a += v * v; }
-  ps[threadIdx.x] = a;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double tot = 0.0;
-    for (int i = 0; i < 256; ++i) tot += ps[i];
-    partial[blockIdx.x] = tot;
-  }
-}
-
+// (the gradient norm, mul_scalar and the step's scalars: train_optim.h)
 #pragma clang fp contract(off)
-// a v_mul_f32 of its own: left to itself the SLP vectoriser pairs this kernel's independent multiplies into v_pk_mul_f32 with a crossed op_sel, the packed form
-// tests/test_isa_guard.py keeps out of the library (merge_sum in dec_kernels.hip)
-__device__ __forceinline__ float mul_scalar(float a, float b) {
-  float r;
-  asm volatile("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
 // clip_grad_norm_'s g *= coef, then torch.optim.AdamW's single-tensor step, one element per thread.  1 - beta1 and 1 - beta2 arrive as the host's double differences
 // rounded once, as torch passes them: formed here from the rounded betas, 1.f - 0.98f is 9.5e-7 (relative) short of 0.02 and every update 7e-7 too long -- a bias
 // that showed as a loss below the fp64 trajectory's at every step.
@@ -879,22 +858,9 @@ extern "C" int etd_dtrain_zero_grad(etd_dtrain* d, void* stream) {
   return ETD_OK;
 }
 
-static int grad_norm(etd_dtrain* d, hipStream_t st, double* out) {
-  const long long n = (long long)d->n_train, chunk = (n + TN_BLOCKS - 1) / TN_BLOCKS;
-  hipLaunchKernelGGL(k_tsumsq, dim3(TN_BLOCKS), dim3(256), 0, st, d->G, n, chunk, d->partial);
-  HIP_TRY(hipGetLastError());
-  double part[TN_BLOCKS];
-  HIP_TRY(hipMemcpyAsync(part, d->partial, sizeof(part), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  double tot = 0.0;
-  for (int i = 0; i < TN_BLOCKS; ++i) tot += part[i];
-  *out = sqrt(tot);
-  return ETD_OK;
-}
-
 extern "C" int etd_dtrain_grad_norm(etd_dtrain* d, double* norm, void* stream) {
   if (!d || !norm) ETD_FAIL(ETD_EINVAL, "etd_dtrain_grad_norm: null argument");
-  return grad_norm(d, (hipStream_t)stream, norm);
+  return grad_norm(d->G, (long long)d->n_train, d->partial, (hipStream_t)stream, norm);
 }
 
 extern "C" int etd_dtrain_clip_and_step(etd_dtrain* d, double max_norm, double lr, double beta1, double beta2, double eps, double weight_decay, double* norm_out,
@@ -905,15 +871,13 @@ extern "C" int etd_dtrain_clip_and_step(etd_dtrain* d, double max_norm, double l
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps("dtrain_optimizer", st);
   double norm = 0.0;
-  ETD_TRY(grad_norm(d, st, &norm));
-  if (norm_out) *norm_out = norm;
-  double coef = 1.0;                                   // max_norm <= 0: no clipping
-  if (max_norm > 0.0) coef = std::min(1.0, max_norm / (norm + 1e-6));
-  d->step += 1;
-  const double bc1 = 1.0 - pow(beta1, (double)d->step), bc2 = 1.0 - pow(beta2, (double)d->step);
   const long long n = (long long)d->n_train;
-  hipLaunchKernelGGL(k_tadamw, ew_grid(n), dim3(256), 0, st, d->P, d->G, d->M1, d->M2, n, (float)coef, (float)(1.0 - lr * weight_decay), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2),
-                     (float)(lr / bc1), (float)sqrt(bc2), (float)eps);
+  ETD_TRY(grad_norm(d->G, n, d->partial, st, &norm));
+  if (norm_out) *norm_out = norm;
+  d->step += 1;
+  const StepScalars s = step_scalars(max_norm, norm, lr, beta1, beta2, d->step);
+  hipLaunchKernelGGL(k_tadamw, ew_grid(n), dim3(256), 0, st, d->P, d->G, d->M1, d->M2, n, s.coef, (float)(1.0 - lr * weight_decay), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2),
+                     s.step_size, s.bc2_sqrt, (float)eps);
   HIP_TRY(hipGetLastError());
   return ETD_OK;
 }
@@ -932,11 +896,7 @@ static int dtrain_io(etd_dtrain* d, const char* name, int which, float* out, con
   if (it == d->index.end()) ETD_FAIL(ETD_EINVAL, "etd_dtrain: no parameter '%s'", name);
   const TParam& p = d->params[it->second];
   if ((long long)p.n != numel) ETD_FAIL(ETD_EINVAL, "etd_dtrain: '%s' has %zu elements, the buffer %lld", name, p.n, numel);
-  float* base = which == 0 ? d->P : which == 1 ? d->G : which == 2 ? d->M1 : d->M2;
-  if (out) HIP_TRY(hipMemcpyAsync(out, base + p.off, sizeof(float) * p.n, hipMemcpyDeviceToHost, st));
-  else HIP_TRY(hipMemcpyAsync(base + p.off, in, sizeof(float) * p.n, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return ETD_OK;
+  return flat_io(d->P, d->G, d->M1, d->M2, which, (long long)p.off, (long long)p.n, out, in, st);
 }
 extern "C" int etd_dtrain_read_param(etd_dtrain* d, const char* name, float* out_host, long long numel, void* stream) {
   return dtrain_io(d, name, 0, out_host, nullptr, numel, (hipStream_t)stream);

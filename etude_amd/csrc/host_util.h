@@ -109,6 +109,27 @@ struct WsCursor {
   long long take(long long bytes) { const long long o = off; off += ws_align(bytes); return o; }
 };
 
+// A handle's per-call workspace: grown when a call needs more than it holds, never shrunk, 256 bytes of slack like the pool's allocations.  A call that grows it
+// waits for its stream first (earlier calls on it may still read the old block).
+struct Workspace {
+  char* p = nullptr;
+  long long bytes = 0;
+  int reserve(long long need, hipStream_t st) {
+    if (need <= bytes) return ETD_OK;
+    HIP_TRY(hipStreamSynchronize(st));
+    if (p) { (void)hipFree(p); p = nullptr; bytes = 0; }
+    HIP_TRY(hipMalloc((void**)&p, (size_t)need + 256));
+    bytes = need;
+    return ETD_OK;
+  }
+  void release() {                         // a handle's destroy
+    if (!p) return;
+    (void)hipDeviceSynchronize();          // kernels of this handle may still be in flight
+    (void)hipFree(p);
+    p = nullptr; bytes = 0;
+  }
+};
+
 template <typename T> bool finite_all(const T* p, size_t n) {      // T: float or double
   for (size_t i = 0; i < n; ++i)
     if (!std::isfinite(p[i])) return false;

@@ -7,6 +7,8 @@
 //                    from the NHWC activations (no im2col buffer); bias, ELU and the batch-norm affine in the epilogue.  A transposed convolution is four such
 //                    launches, one per output parity, each with the 2 or 3 kernel taps per axis that reach it: no lane multiplies by a structural zero.
 //   k_sep_conv_valu  the same launch descriptor, one output element per thread: layers with K < 64 (the first convolution of mono or stereo audio), Cout = 1 and the head
+//                    Both are the trainer's convolutions too (separator_train.hip, through sep_launch with the PLAIN epilogue): separator.h holds the descriptor,
+//                    the tile step and the layers' geometry.
 //   k_sep_mask       softmax over the instruments, ratio mask, zero extension and the product with X in one pass
 //   k_sep_istft      one workgroup per (stem, channel, frame): inverse split pass -> the same Stockham stages on conjugated data -> windowed frame
 //   k_sep_ola        gather overlap-add: every output sample sums its at most four frames in ascending frame order
@@ -82,13 +84,20 @@ __device__ __forceinline__ float sep_gather(const SepLaunch& a, const float* x0,
   return ci < a.C0 ? x0[p * a.C0 + ci] : x1[p * a.C1 + (ci - a.C0)];
 }
 
-// the epilogue of one output element: v = the sum, at GEMM position (jt, jf), output channel col
-__device__ __forceinline__ void sep_store(const SepLaunch& a, int u, int inst, int jt, int jf, int col, float v) {
+// the epilogue EPI (= a.epi: the launch picks the instantiation) of one output element: v = the sum, at GEMM position (jt, jf), output channel col
+template <int EPI> __device__ __forceinline__ void sep_store(const SepLaunch& a, int u, int inst, int jt, int jf, int col, float v) {
+  if (EPI == SEP_EPI_PLAIN) {
+    if (a.bias) v += a.bias[inst * a.N + col];
+    const long long p = (long long)(a.oS * jt + a.opt) * a.Wout + (a.oS * jf + a.opf);
+    if (col < a.N0) a.pre[(long long)u * a.out_us + p * a.N0 + col] = v;
+    else a.out1[(long long)u * a.out1_us + p * (a.N - a.N0) + (col - a.N0)] = v;
+    return;
+  }
   const long long o = (long long)u * a.out_us + ((long long)(a.oS * jt + a.opt) * a.Wout + (a.oS * jf + a.opf)) * a.N + col;
   v += a.bias[inst * a.N + col];
-  if (a.epi == SEP_EPI_HEAD) { a.pre[o] = v; return; }
+  if (EPI == SEP_EPI_HEAD) { a.pre[o] = v; return; }
   const float bn_a = a.bn_a[inst * a.N + col], bn_s = a.bn_s[inst * a.N + col];
-  if (a.epi == SEP_EPI_CONV) {
+  if (EPI == SEP_EPI_CONV) {
     if (a.pre) a.pre[o] = v;
     if (a.act) a.act[o] = sep_elu(fmaf(bn_a, v, bn_s));
   } else {
@@ -96,9 +105,8 @@ __device__ __forceinline__ void sep_store(const SepLaunch& a, int u, int inst, i
   }
 }
 
-// grid (M tiles, N tiles, units).  The K sum of an output element: every step of 32 runs as two chains of 8 MFMAs (16 terms each) that are added and join one of four running totals
-// (step s -> total s % 4); the totals are added pairwise at the end.  No chain is longer than K / 128 + 16 terms, in an order the layer's shape fixes.
-__global__ __launch_bounds__(SEP_THREADS) void k_sep_conv_mfma(const SepLaunch a) {
+// grid (M tiles, N tiles, units).  The K sum of an output element runs in the order of separator.h's tile step.
+template <int EPI> __global__ __launch_bounds__(SEP_THREADS) void k_sep_conv_mfma(const SepLaunch a) {
   __shared__ float As[SEP_BK][SEP_LD], Bs[SEP_BK][SEP_LD];
   const int t = threadIdx.x, l = t & 63, w = t >> 6;
   const int m0 = blockIdx.x * SEP_BM, n0 = blockIdx.y * SEP_BN, u = blockIdx.z;
@@ -122,10 +130,7 @@ __global__ __launch_bounds__(SEP_THREADS) void k_sep_conv_mfma(const SepLaunch a
   }
   float ra[8], rb[8];
   f32x16 tot[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) tot[c][r] = 0.f;
+  sep_tile_zero(tot);
 #define SEP_LOAD(k0)                                                                                        \
   {                                                                                                         \
     const int kg = (k0) + (t & 31);                                                                         \
@@ -148,22 +153,7 @@ __global__ __launch_bounds__(SEP_THREADS) void k_sep_conv_mfma(const SepLaunch a
     }
     __syncthreads();
     if (k0 + SEP_BK < K) SEP_LOAD(k0 + SEP_BK)         // the next tile's loads fly while this one is multiplied
-    f32x16 p0, p1;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { p0[r] = 0.f; p1[r] = 0.f; }
-#pragma unroll
-    for (int kk = 0; kk < SEP_BK; kk += 4) {
-      p0 = __builtin_amdgcn_mfma_f32_32x32x2f32(As[kk + half][wr * 32 + l31], Bs[kk + half][wc * 32 + l31], p0, 0, 0, 0);
-      p1 = __builtin_amdgcn_mfma_f32_32x32x2f32(As[kk + 2 + half][wr * 32 + l31], Bs[kk + 2 + half][wc * 32 + l31], p1, 0, 0, 0);
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) p0[r] += p1[r];
-    switch (step & 3) {                                // (uniform)
-      case 0: for (int r = 0; r < 16; ++r) tot[0][r] += p0[r]; break;
-      case 1: for (int r = 0; r < 16; ++r) tot[1][r] += p0[r]; break;
-      case 2: for (int r = 0; r < 16; ++r) tot[2][r] += p0[r]; break;
-      default: for (int r = 0; r < 16; ++r) tot[3][r] += p0[r]; break;
-    }
+    sep_tile_step(As, Bs, wr * 32 + l31, wc * 32 + l31, half, step, tot);
   }
 #undef SEP_LOAD
   const int col = n0 + wc * 32 + l31;
@@ -173,12 +163,12 @@ __global__ __launch_bounds__(SEP_THREADS) void k_sep_conv_mfma(const SepLaunch a
     const int pos = m0 + wr * 32 + acc_row(r, half);
     if (pos >= Mpos) continue;
     const int jt = pos / a.Wj, jf = pos - jt * a.Wj;
-    sep_store(a, u, inst, jt, jf, col, (tot[0][r] + tot[1][r]) + (tot[2][r] + tot[3][r]));
+    sep_store<EPI>(a, u, inst, jt, jf, col, sep_tile_total(tot, r));
   }
 }
 
 // one output element per thread, channel fastest: per tap one fmaf chain over the input channels, the taps' sums added in tap order
-__global__ __launch_bounds__(SEP_THREADS) void k_sep_conv_valu(const SepLaunch a, long long total) {
+template <int EPI> __global__ __launch_bounds__(SEP_THREADS) void k_sep_conv_valu(const SepLaunch a, long long total) {
   const long long e = (long long)blockIdx.x * SEP_THREADS + threadIdx.x;
   if (e >= total) return;
   const int col = (int)(e % a.N);
@@ -205,7 +195,7 @@ __global__ __launch_bounds__(SEP_THREADS) void k_sep_conv_valu(const SepLaunch a
       sum += acc;
     }
   }
-  sep_store(a, u, inst, jt, jf, col, sum);
+  sep_store<EPI>(a, u, inst, jt, jf, col, sum);
 }
 
 // ================================================================================================ masks
@@ -303,11 +293,42 @@ __global__ __launch_bounds__(SEP_THREADS) void k_sep_ola(const float* __restrict
 
 }  // namespace
 
+template <int EPI> static int sep_launch_kernel(const SepLaunch& a, int n_units, bool valu, const char* name, hipStream_t st) {
+  const long long Mpos = (long long)a.Hj * a.Wj;
+  if (valu) {
+    const long long total = (long long)n_units * Mpos * a.N, blocks = (total + SEP_THREADS - 1) / SEP_THREADS;
+    if (blocks > 0x7fffffffLL)
+      ETD_FAIL(ETD_EINVAL, "separator: %s needs %lld workgroups (> 2^31 - 1); lower the workspace budget", name ? name : "a training convolution", blocks);
+    hipLaunchKernelGGL(k_sep_conv_valu<EPI>, dim3((unsigned)blocks), dim3(SEP_THREADS), 0, st, a, total);
+  } else {
+    const dim3 grid((unsigned)((Mpos + SEP_BM - 1) / SEP_BM), (unsigned)((a.N + SEP_BN - 1) / SEP_BN), (unsigned)n_units);
+    hipLaunchKernelGGL(k_sep_conv_mfma<EPI>, grid, dim3(SEP_THREADS), 0, st, a);
+  }
+  return ETD_OK;
+}
+
+static int sep_launch_epi(const SepLaunch& a, int n_units, bool valu, const char* name, hipStream_t st) {
+  switch (a.epi) {
+    case SEP_EPI_CONV: return sep_launch_kernel<SEP_EPI_CONV>(a, n_units, valu, name, st);
+    case SEP_EPI_DECONV: return sep_launch_kernel<SEP_EPI_DECONV>(a, n_units, valu, name, st);
+    case SEP_EPI_HEAD: return sep_launch_kernel<SEP_EPI_HEAD>(a, n_units, valu, name, st);
+    case SEP_EPI_PLAIN: return sep_launch_kernel<SEP_EPI_PLAIN>(a, n_units, valu, name, st);
+  }
+  ETD_FAIL(ETD_EINVAL, "separator: epilogue %d is not one of the four", a.epi);
+}
+
+int sep_launch(const SepLaunch& a, int n_units, bool force_valu, const char* name, hipStream_t st) {
+  const int K = a.nt * a.nf * (a.C0 + a.C1);
+  const bool valu = K < SEP_MFMA_MIN_K || a.N == 1 || a.epi == SEP_EPI_HEAD || force_valu;
+  if (!name) return sep_launch_epi(a, n_units, valu, name, st);
+  ProfScope ps(name, st, 2.0 * (double)n_units * (double)a.Hj * a.Wj * K * a.N, 0);
+  return sep_launch_epi(a, n_units, valu, name, st);
+}
+
 struct etd_sep {
   etd_sep_cfg cfg;
   int M = 0, lgM = 0, L = ETD_SEP_LEVELS;
-  int Cenc[ETD_SEP_LEVELS + 1];      // Cenc[0] = n_channels, Cenc[l] = filters[l - 1]
-  int Cdout[ETD_SEP_LEVELS + 1];     // decoder j's output channels: filters[5 - j], 1 for j = 6
+  SepNet net;
   // a unit's activations, in floats: conv_l before the norm (the skips and the decoder's first input) and the two buffers every other tensor alternates between
   long long pre_off[ETD_SEP_LEVELS + 1], a_off[2], unit_floats = 0;
   double seg_flops = 0;
@@ -320,15 +341,10 @@ struct etd_sep {
   float* d_window = nullptr; float2 *d_twM = nullptr, *d_twS = nullptr;
   float *d_w_conv[ETD_SEP_LEVELS], *d_b_conv[ETD_SEP_LEVELS], *d_w_dec[ETD_SEP_LEVELS][4], *d_b_dec[ETD_SEP_LEVELS], *d_bn_a[2 * ETD_SEP_LEVELS], *d_bn_s[2 * ETD_SEP_LEVELS];
   float *d_w_head = nullptr, *d_b_head = nullptr;
-  // per-call workspace, grown on demand
-  char* ws = nullptr; long long ws_bytes = 0;
+  Workspace ws;
 };
 
 namespace {
-
-// kernel taps of a transposed convolution that reach output parity p, in the order the packed weights hold them (a = 0, 1, (2)): p = 0: 1, 3; p = 1: 0, 2, 4
-inline int sep_dec_taps(int p) { return p ? 3 : 2; }
-inline int sep_dec_tap(int p, int a) { return p ? 2 * a : 1 + 2 * a; }
 
 int sep_upload(etd_sep* h) {
   DevPool& P = h->pool;
@@ -351,23 +367,6 @@ int sep_upload(etd_sep* h) {
   });
 }
 
-int sep_launch(const SepLaunch& a, int n_units, const char* name, hipStream_t st) {
-  const int Cin = a.C0 + a.C1, K = a.nt * a.nf * Cin;
-  const long long Mpos = (long long)a.Hj * a.Wj;
-  const double flops = 2.0 * (double)n_units * (double)Mpos * K * a.N;
-  const bool valu = K < SEP_MFMA_MIN_K || a.N == 1 || a.epi == SEP_EPI_HEAD;
-  ProfScope ps(name, st, flops, 0);
-  if (valu) {
-    const long long total = (long long)n_units * Mpos * a.N, blocks = (total + SEP_THREADS - 1) / SEP_THREADS;
-    if (blocks > 0x7fffffffLL) ETD_FAIL(ETD_EINVAL, "separator: %s needs %lld workgroups (> 2^31 - 1); lower the workspace budget", name, blocks);
-    hipLaunchKernelGGL(k_sep_conv_valu, dim3((unsigned)blocks), dim3(SEP_THREADS), 0, st, a, total);
-  } else {
-    const dim3 grid((unsigned)((Mpos + SEP_BM - 1) / SEP_BM), (unsigned)((a.N + SEP_BN - 1) / SEP_BN), (unsigned)n_units);
-    hipLaunchKernelGGL(k_sep_conv_mfma, grid, dim3(SEP_THREADS), 0, st, a);
-  }
-  return ETD_OK;
-}
-
 // the test hooks run every unit of a launch with one instrument's weights
 void sep_fix_instrument(SepLaunch& a, int fixed) {
   if (fixed < 0) return;
@@ -380,15 +379,13 @@ void sep_fix_instrument(SepLaunch& a, int fixed) {
 int sep_encoder(etd_sep* h, int l, const float* x0, long long x0_us, int x0_u0, int x0_div, float* pre, float* act, long long out_us, int u0, int n, hipStream_t st,
                 int fixed = -1) {
   SepLaunch a{};
-  a.x0 = x0; a.x0_us = x0_us; a.x0_u0 = x0_u0; a.x0_div = x0_div; a.C0 = h->Cenc[l - 1]; a.x1 = nullptr; a.x1_us = 0; a.C1 = 0;
-  a.Hin = h->cfg.T >> (l - 1); a.Win = h->cfg.F >> (l - 1); a.Hj = h->cfg.T >> l; a.Wj = h->cfg.F >> l;
-  a.S = 2; a.o0t = -1; a.o0f = -1; a.d = 1; a.nt = 5; a.nf = 5;
-  a.N = h->Cenc[l];
+  sep_geom_encoder(h->net, l, &a);
+  a.x0 = x0; a.x0_us = x0_us; a.x0_u0 = x0_u0; a.x0_div = x0_div;
   a.W = h->d_w_conv[l - 1]; a.w_is = 25LL * a.C0 * a.N; a.bias = h->d_b_conv[l - 1]; a.bn_a = h->d_bn_a[l - 1]; a.bn_s = h->d_bn_s[l - 1];
-  a.pre = pre; a.act = act; a.out_us = out_us; a.Wout = a.Wj; a.oS = 1; a.opt = 0; a.opf = 0; a.epi = SEP_EPI_CONV;
+  a.pre = pre; a.act = act; a.out_us = out_us; a.epi = SEP_EPI_CONV;
   a.u0 = u0; a.I = h->cfg.n_instr;
   sep_fix_instrument(a, fixed);
-  return sep_launch(a, n, "k_sep_conv", st);
+  return sep_launch(a, n, false, "k_sep_conv", st);
 }
 
 // decoder layer j = 1 .. 6: [skip | up] -> act, four launches by output parity
@@ -397,32 +394,27 @@ int sep_decoder(etd_sep* h, int j, const float* skip, long long skip_us, const f
   for (int par = 0; par < 4; ++par) {
     const int pt = par >> 1, pf = par & 1;
     SepLaunch a{};
-    a.x0 = skip; a.x0_us = skip_us; a.x0_u0 = 0; a.x0_div = 1; a.C0 = h->Cenc[7 - j];
-    a.x1 = up; a.x1_us = up_us; a.C1 = j > 1 ? h->Cdout[j - 1] : 0;
-    a.Hin = h->cfg.T >> (7 - j); a.Win = h->cfg.F >> (7 - j); a.Hj = a.Hin; a.Wj = a.Win;
-    a.S = 1; a.o0t = pt; a.o0f = pf; a.d = -1; a.nt = sep_dec_taps(pt); a.nf = sep_dec_taps(pf);
-    a.N = h->Cdout[j];
+    sep_geom_deconv(h->net, j, pt, pf, &a);
+    a.x0 = skip; a.x0_us = skip_us; a.x0_div = 1; a.x1 = up; a.x1_us = up_us;
     a.W = h->d_w_dec[j - 1][par]; a.w_is = (long long)a.nt * a.nf * (a.C0 + a.C1) * a.N;
     a.bias = h->d_b_dec[j - 1]; a.bn_a = h->d_bn_a[ETD_SEP_LEVELS + j - 1]; a.bn_s = h->d_bn_s[ETD_SEP_LEVELS + j - 1];
-    a.pre = nullptr; a.act = act; a.out_us = out_us; a.Wout = 2 * a.Win; a.oS = 2; a.opt = pt; a.opf = pf; a.epi = SEP_EPI_DECONV;
+    a.act = act; a.out_us = out_us; a.epi = SEP_EPI_DECONV;
     a.u0 = u0; a.I = h->cfg.n_instr;
     sep_fix_instrument(a, fixed);
-    ETD_TRY(sep_launch(a, n, "k_sep_deconv", st));
+    ETD_TRY(sep_launch(a, n, false, "k_sep_deconv", st));
   }
   return ETD_OK;
 }
 
 int sep_head(etd_sep* h, const float* x, long long x_us, float* logits, long long out_us, int u0, int n, hipStream_t st, int fixed = -1) {
   SepLaunch a{};
-  a.x0 = x; a.x0_us = x_us; a.x0_u0 = 0; a.x0_div = 1; a.C0 = 1; a.x1 = nullptr; a.x1_us = 0; a.C1 = 0;
-  a.Hin = h->cfg.T; a.Win = h->cfg.F; a.Hj = a.Hin; a.Wj = a.Win;
-  a.S = 1; a.o0t = -3; a.o0f = -3; a.d = 2; a.nt = 4; a.nf = 4;
-  a.N = h->cfg.n_channels;
-  a.W = h->d_w_head; a.w_is = 16LL * a.N; a.bias = h->d_b_head; a.bn_a = nullptr; a.bn_s = nullptr;
-  a.pre = logits; a.act = nullptr; a.out_us = out_us; a.Wout = a.Win; a.oS = 1; a.opt = 0; a.opf = 0; a.epi = SEP_EPI_HEAD;
+  sep_geom_head(h->net, &a);
+  a.x0 = x; a.x0_us = x_us; a.x0_div = 1;
+  a.W = h->d_w_head; a.w_is = 16LL * a.N; a.bias = h->d_b_head;
+  a.pre = logits; a.out_us = out_us; a.epi = SEP_EPI_HEAD;
   a.u0 = u0; a.I = h->cfg.n_instr;
   sep_fix_instrument(a, fixed);
-  return sep_launch(a, n, "k_sep_head", st);
+  return sep_launch(a, n, false, "k_sep_head", st);
 }
 
 // the U-Nets of units u0 .. u0 + n - 1 (unit = segment * I + instrument): mag [segments][T][F][C] -> logits + u0 * T F C, activations in `work`
@@ -474,15 +466,6 @@ int sep_istft(etd_sep* h, const float2* Y, long long Tf, long long N, long long 
     ProfScope ps("k_sep_ola", st, 0, (double)rows * N * 20.0);
     hipLaunchKernelGGL(k_sep_ola, dim3((unsigned)((rows * N + SEP_THREADS - 1) / SEP_THREADS)), dim3(SEP_THREADS), 0, st, frames, Tf, a.n_fft, h->cfg.hop, N, rows, out);
   }
-  return ETD_OK;
-}
-
-int sep_reserve(etd_sep* h, long long bytes, hipStream_t st) {
-  if (bytes <= h->ws_bytes) return ETD_OK;
-  HIP_TRY(hipStreamSynchronize(st));
-  if (h->ws) { (void)hipFree(h->ws); h->ws = nullptr; h->ws_bytes = 0; }
-  HIP_TRY(hipMalloc((void**)&h->ws, (size_t)bytes + 256));
-  h->ws_bytes = bytes;
   return ETD_OK;
 }
 
@@ -613,21 +596,16 @@ extern "C" int etd_sep_create(const etd_sep_cfg* cfg, const char* const* instr_n
   h->cfg = c;
   h->M = c.n_fft / 2;
   while ((1 << h->lgM) < h->M) ++h->lgM;
-  h->Cenc[0] = c.n_channels;
-  for (int l = 1; l <= ETD_SEP_LEVELS; ++l) h->Cenc[l] = c.filters[l - 1];
-  h->Cdout[0] = 0;
-  for (int j = 1; j < ETD_SEP_LEVELS; ++j) h->Cdout[j] = c.filters[ETD_SEP_LEVELS - 1 - j];
-  h->Cdout[ETD_SEP_LEVELS] = 1;
+  sep_net_init(&h->net, c);
   // the unit's layout; every tensor of a unit must be indexable by an int
   long long o = 0, amax = 0;
   const long long lim = 1LL << 30;
   for (int l = 1; l <= ETD_SEP_LEVELS; ++l) {
-    const long long sz = (long long)(c.T >> l) * (c.F >> l) * h->Cenc[l];
+    const long long sz = h->net.szE[l];
     if (sz > lim) { g_etd_err = "sep_create: an activation of one segment has more than 2^30 elements"; return fail(ETD_EINVAL); }
     h->pre_off[l] = o; o += (sz + 63) & ~63LL;
     if (l < ETD_SEP_LEVELS && sz > amax) amax = sz;
-    const int j = l;
-    const long long up = (long long)(c.T >> (ETD_SEP_LEVELS - j)) * (c.F >> (ETD_SEP_LEVELS - j)) * h->Cdout[j];
+    const long long up = h->net.szD[l];
     if (up > lim) { g_etd_err = "sep_create: an activation of one segment has more than 2^30 elements"; return fail(ETD_EINVAL); }
     if (up > amax) amax = up;
   }
@@ -649,11 +627,11 @@ extern "C" int etd_sep_create(const etd_sep_cfg* cfg, const char* const* instr_n
   };
   double flops = 0;
   for (int l = 1; l <= ETD_SEP_LEVELS; ++l) {
-    const int Ci = h->Cenc[l - 1], Co = h->Cenc[l];
+    const int Ci = h->net.Cenc[l - 1], Co = h->net.Cenc[l];
     h->w_conv[l - 1].resize((size_t)I * 25 * Ci * Co); h->b_conv[l - 1].resize((size_t)I * Co);
     flops += 2.0 * (c.T >> l) * (c.F >> l) * 25.0 * Ci * Co;
     // decoder j = l
-    const int j = l, D0 = h->Cenc[7 - j], D1 = j > 1 ? h->Cdout[j - 1] : 0, Di = D0 + D1, Do = h->Cdout[j];
+    const int j = l, D0 = h->net.Cenc[7 - j], D1 = j > 1 ? h->net.Cdout[j - 1] : 0, Di = D0 + D1, Do = h->net.Cdout[j];
     for (int par = 0; par < 4; ++par) h->w_dec[j - 1][par].resize((size_t)I * sep_dec_taps(par >> 1) * sep_dec_taps(par & 1) * Di * Do);
     h->b_dec[j - 1].resize((size_t)I * Do);
     flops += 2.0 * (c.T >> (7 - j)) * (c.F >> (7 - j)) * 25.0 * Di * Do;
@@ -666,14 +644,14 @@ extern "C" int etd_sep_create(const etd_sep_cfg* cfg, const char* const* instr_n
   for (int i = 0; i < I; ++i) {
     const std::string pre = std::string(instr_names[i]) + ".";
     for (int l = 1; l <= ETD_SEP_LEVELS; ++l) {
-      const int Ci = h->Cenc[l - 1], Co = h->Cenc[l];
+      const int Ci = h->net.Cenc[l - 1], Co = h->net.Cenc[l];
       const float* w = need(pre + "conv" + std::to_string(l) + ".weight", 25LL * Ci * Co);
       if (!w) return fail(ETD_EINVAL);
       memcpy(&h->w_conv[l - 1][(size_t)i * 25 * Ci * Co], w, (size_t)25 * Ci * Co * 4);      // [kt][kf][ci][co] is the GEMM's [K][N]
       const float* b = need(pre + "conv" + std::to_string(l) + ".bias", Co);
       if (!b) return fail(ETD_EINVAL);
       memcpy(&h->b_conv[l - 1][(size_t)i * Co], b, (size_t)Co * 4);
-      const int j = l, D0 = h->Cenc[7 - j], D1 = j > 1 ? h->Cdout[j - 1] : 0, Di = D0 + D1, Do = h->Cdout[j];
+      const int j = l, D0 = h->net.Cenc[7 - j], D1 = j > 1 ? h->net.Cdout[j - 1] : 0, Di = D0 + D1, Do = h->net.Cdout[j];
       const float* wd = need(pre + "deconv" + std::to_string(j) + ".weight", 25LL * Do * Di);
       if (!wd) return fail(ETD_EINVAL);
       for (int par = 0; par < 4; ++par) {               // [kt][kf][co][ci] -> per parity [a][b][ci][co]
@@ -691,7 +669,7 @@ extern "C" int etd_sep_create(const etd_sep_cfg* cfg, const char* const* instr_n
       memcpy(&h->b_dec[j - 1][(size_t)i * Do], bd, (size_t)Do * 4);
     }
     for (int nn = 1; nn <= 2 * ETD_SEP_LEVELS; ++nn) {   // a = gamma / sqrt(var + eps), s = beta - mean a: fp64, rounded once
-      const int Cn = nn <= ETD_SEP_LEVELS ? h->Cenc[nn] : h->Cdout[nn - ETD_SEP_LEVELS];
+      const int Cn = nn <= ETD_SEP_LEVELS ? h->net.Cenc[nn] : h->net.Cdout[nn - ETD_SEP_LEVELS];
       const std::string k = pre + "bn" + std::to_string(nn);
       const float *g = need(k + ".gamma", Cn), *be = g ? need(k + ".beta", Cn) : nullptr, *mu = be ? need(k + ".mean", Cn) : nullptr, *va = mu ? need(k + ".var", Cn) : nullptr;
       if (!va) return fail(ETD_EINVAL);
@@ -715,11 +693,8 @@ extern "C" int etd_sep_create(const etd_sep_cfg* cfg, const char* const* instr_n
 
 extern "C" void etd_sep_destroy(etd_sep* h) {
   if (!h) return;
-  if (h->pool.uploaded || h->ws) {
-    (void)hipDeviceSynchronize();   // kernels of this handle may still be in flight
-    h->pool.free_all();
-    if (h->ws) (void)hipFree(h->ws);
-  }
+  h->pool.release_uploaded();
+  h->ws.release();
   delete h;
 }
 
@@ -749,17 +724,17 @@ extern "C" int etd_sep_run(etd_sep* h, const float* const* wav_ptrs, int n_songs
   for (int s = 0; s < n_songs; ++s)
     if (!wav_ptrs[s] || !out_ptrs[s]) ETD_FAIL(ETD_EINVAL, "sep_run: song %d has a null pointer", s);
   ETD_TRY(sep_upload(h));
-  ETD_TRY(sep_reserve(h, bytes, st));
+  ETD_TRY(h->ws.reserve(bytes, st));
   const etd_sep_cfg& c = h->cfg;
   const long long plane = (long long)c.T * c.F * c.n_channels;
   for (size_t g = 0; g < plans.size(); ++g) {            // (the groups follow each other on the stream, in the same workspace)
     const SepPlan& p = plans[g];
     const int s0 = first[g], ng = first[g + 1] - s0;
-    float2* X = (float2*)(h->ws + p.off_X);
-    float* mag = (float*)(h->ws + p.off_mag);
-    float* logits = (float*)(h->ws + p.off_logits);
-    float2* Y = (float2*)(h->ws + p.off_Y);
-    float* work = (float*)(h->ws + p.off_work);
+    float2* X = (float2*)(h->ws.p + p.off_X);
+    float* mag = (float*)(h->ws.p + p.off_mag);
+    float* logits = (float*)(h->ws.p + p.off_logits);
+    float2* Y = (float2*)(h->ws.p + p.off_Y);
+    float* work = (float*)(h->ws.p + p.off_work);
     HIP_TRY(hipMemsetAsync(mag, 0, (size_t)(p.segs * plane * 4), st));          // the frames past a song's last are zeros
     for (int s = 0; s < ng; ++s)
       ETD_TRY(sep_stft(h, wav_ptrs[s0 + s], N_host[s0 + s], p.Tf[s], X + p.x_off[s], c.F, mag + p.seg0[s] * plane, st));
@@ -787,9 +762,9 @@ extern "C" int etd_sep_magnitudes(etd_sep* h, const float* wav_dev, long long N,
   const etd_sep_cfg& c = h->cfg;
   const long long Tf = 1 + (N + c.n_fft) / c.hop, segs = (Tf + c.T - 1) / c.T;
   ETD_TRY(sep_upload(h));
-  ETD_TRY(sep_reserve(h, ws_align((long long)c.n_channels * Tf * c.F * 8), st));
+  ETD_TRY(h->ws.reserve(ws_align((long long)c.n_channels * Tf * c.F * 8), st));
   HIP_TRY(hipMemsetAsync(mag_dev, 0, (size_t)(segs * c.T * c.F * c.n_channels * 4), st));      // the frames past the song's last are zeros
-  ETD_TRY(sep_stft(h, wav_dev, N, Tf, (float2*)h->ws, c.F, mag_dev, st));
+  ETD_TRY(sep_stft(h, wav_dev, N, Tf, (float2*)h->ws.p, c.F, mag_dev, st));
   HIP_TRY(hipGetLastError());
   return ETD_OK;
 }
@@ -814,14 +789,14 @@ extern "C" int etd_sep_debug_layer(etd_sep* h, int instr, int kind, int layer, c
   const int n = n_units;
   if (kind == 0) {
     const int l = layer;
-    const long long in_us = (long long)(c.T >> (l - 1)) * (c.F >> (l - 1)) * h->Cenc[l - 1], out_us = (long long)(c.T >> l) * (c.F >> l) * h->Cenc[l];
+    const long long in_us = (long long)(c.T >> (l - 1)) * (c.F >> (l - 1)) * h->net.Cenc[l - 1], out_us = (long long)(c.T >> l) * (c.F >> l) * h->net.Cenc[l];
     if (!pre_dev && !act_dev) ETD_FAIL(ETD_EINVAL, "sep_debug_layer: no output");
     ETD_TRY(sep_encoder(h, l, x0_dev, in_us, 0, 1, pre_dev, act_dev, out_us, 0, n, st, instr));
   } else if (kind == 1) {
     const int j = layer;
     const long long pix = (long long)(c.T >> (7 - j)) * (c.F >> (7 - j));
     if (!act_dev || (j > 1 && !x1_dev)) ETD_FAIL(ETD_EINVAL, "sep_debug_layer: a decoder layer needs act_dev, and x1_dev for j > 1");
-    ETD_TRY(sep_decoder(h, j, x0_dev, pix * h->Cenc[7 - j], j > 1 ? x1_dev : nullptr, j > 1 ? pix * h->Cdout[j - 1] : 0, act_dev, 4 * pix * h->Cdout[j], 0, n, st, instr));
+    ETD_TRY(sep_decoder(h, j, x0_dev, pix * h->net.Cenc[7 - j], j > 1 ? x1_dev : nullptr, j > 1 ? pix * h->net.Cdout[j - 1] : 0, act_dev, 4 * pix * h->net.Cdout[j], 0, n, st, instr));
   } else if (kind == 2) {
     const long long pix = (long long)c.T * c.F;
     if (!pre_dev) ETD_FAIL(ETD_EINVAL, "sep_debug_layer: the head needs pre_dev");
@@ -846,8 +821,8 @@ extern "C" int etd_sep_debug_istft(etd_sep* h, const float* Y_dev, long long N, 
   const etd_sep_cfg& c = h->cfg;
   const long long Tf = 1 + (N + c.n_fft) / c.hop, rows = (long long)c.n_instr * c.n_channels;
   ETD_TRY(sep_upload(h));
-  ETD_TRY(sep_reserve(h, ws_align(rows * Tf * c.n_fft * 4), st));
-  ETD_TRY(sep_istft(h, (const float2*)Y_dev, Tf, N, rows, (float*)h->ws, out_dev, st));
+  ETD_TRY(h->ws.reserve(ws_align(rows * Tf * c.n_fft * 4), st));
+  ETD_TRY(sep_istft(h, (const float2*)Y_dev, Tf, N, rows, (float*)h->ws.p, out_dev, st));
   HIP_TRY(hipGetLastError());
   return ETD_OK;
 }

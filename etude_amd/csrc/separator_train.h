@@ -9,17 +9,7 @@
 // running statistics: r <- m r + (1 - m) batch
 #define ST_BN_MOMENTUM 0.99
 
-// One launch of a gather convolution with a plain epilogue (SepLaunch's geometry): out = sum + bias (bias may be null), columns < N0 to out0, the rest to out1.
-// Unit u = b * I + instrument.
-struct StConv {
-  const float* x0; long long x0_us; int x0_div, C0;             // unit u reads x0 + (u / x0_div) * x0_us
-  const float* x1; long long x1_us; int C1;
-  int Hin, Win, Hj, Wj, S, o0t, o0f, d, nt, nf;
-  const float* W; long long w_is; const float* bias;
-  int N, N0;
-  float* out0; long long out0_us; float* out1; long long out1_us;
-  int Wout, oS, opt, opf, I;
-};
+// (The convolutions -- every forward one and every input gradient -- are launches of separator.h's SepLaunch with the PLAIN epilogue; unit u = b * I + instrument.)
 
 // One weight gradient: part[inst][slice][m][n] = sum over the slice's rows k = b * P + pos of g(pos, tap(m), cg(m)) y[pos][n]; m = tap * Cg + cg, y = [y0 | y1]
 struct StDw {

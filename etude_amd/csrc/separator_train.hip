@@ -2,16 +2,17 @@
 // training mode -- every norm on the batch's statistics --, Spleeter's L1 loss on the softmax estimates, the gradient of every kernel, bias, gamma and beta of every
 // instrument, and torch.optim.Adam's single-tensor step.  One call is one batch: mix [B][T][F][C], target [I][B][T][F][C]; unit u = b * I + instrument.
 //
-//   k_st_conv_mfma / _valu  the gather convolution of separator.hip with a plain epilogue (bias only, two output tensors): every forward convolution and every input
-//                           gradient -- conv dX = the four parity launches of the transposed geometry on channel-swapped kernels, transposed-conv dX = a stride-2
-//                           convolution of dy to [dskip | dup], head dX = the dilated correlation with the flipped kernel
-//   k_st_dw                 weight gradients as a GEMM on v_mfma_f32_32x32x2_f32: M = taps x gathered channels, N = dense channels, K = (unit, position) in slices of
-//                           ST_DW_SLICE rows; k_st_dw_reduce adds the slices' partials in slice order (fp64, rounded once) into the gradient
+//   k_sep_conv_mfma / _valu separator.hip's gather convolution, launched through sep_launch with the PLAIN epilogue (bias or none, two output tensors): every forward
+//                           convolution and every input gradient -- conv dX = the four parity launches of the transposed geometry on channel-swapped kernels,
+//                           transposed-conv dX = a stride-2 convolution of dy to [dskip | dup], head dX = the dilated correlation with the flipped kernel
+//   k_st_dw                 weight gradients as a GEMM on v_mfma_f32_32x32x2_f32 with the forward's tile step (separator.h): M = taps x gathered channels, N = dense
+//                           channels, K = (unit, position) in slices of ST_DW_SLICE rows; k_st_dw_reduce adds the slices' partials in slice order (fp64, rounded
+//                           once) into the gradient
 //   k_st_col / k_st_colfin  ordered column reductions: per-channel mean, centred variance, the norm's two backward sums, bias gradients.  fp32 partials of
 //                           ST_COL_ROWS rows per workgroup, joined in chunk order in fp64
 //   k_st_ew                 normalise + ELU (encoder), ELU + normalise (decoder) and their backward passes, xhat recomputed from the saved pre-norm tensor
 //   k_st_loss               softmax over the instruments, |s_i mix - target_i| partials and dlogits in one pass
-//   k_st_sumsq / k_st_adam  the gradient norm and Adam, after dec_train.hip
+//   k_tsumsq / k_st_adam    the gradient norm dec_train.hip uses (train_optim.h) and torch.optim.Adam's step
 //   k_st_dropout            decoder dropout (levels 1 .. 3, only when p > 0): y <- keep ? y s : 0 in place with a Philox4x32-10 mask that is a function of the element
 //                           index, the level, the seed and the call counter; the backward pass runs the same kernel on dy, so no mask is stored
 //
@@ -24,134 +25,14 @@
 #include <string>
 
 #include "etude_hip_debug.h"
+#include "train_optim.h"
 
 namespace {
 
 __device__ __forceinline__ float st_elu(float x) { return x > 0.f ? x : expm1f(x); }
 __device__ __forceinline__ float st_elu_grad(float x) { return x > 0.f ? 1.f : expf(x); }
 
-// ================================================================================================ convolutions
-__device__ __forceinline__ float st_gather(const StConv& a, const float* x0, const float* x1, int it, int jf, int ci) {
-  if (it < 0 || it >= a.Hin || jf < 0 || jf >= a.Win) return 0.f;
-  const int p = it * a.Win + jf;
-  return ci < a.C0 ? x0[p * a.C0 + ci] : x1[p * a.C1 + (ci - a.C0)];
-}
-
-__device__ __forceinline__ void st_store(const StConv& a, int u, int jt, int jf, int col, float v) {
-  if (a.bias) v += a.bias[(u % a.I) * a.N + col];
-  const long long p = (long long)(a.oS * jt + a.opt) * a.Wout + (a.oS * jf + a.opf);
-  if (col < a.N0) a.out0[(long long)u * a.out0_us + p * a.N0 + col] = v;
-  else a.out1[(long long)u * a.out1_us + p * (a.N - a.N0) + (col - a.N0)] = v;
-}
-
-// k_sep_conv_mfma's tiles, LDS images and summation order (two chains of 8 MFMAs per step of 32, four running totals added pairwise)
-__global__ __launch_bounds__(SEP_THREADS) void k_st_conv_mfma(const StConv a) {
-  __shared__ float As[SEP_BK][SEP_LD], Bs[SEP_BK][SEP_LD];
-  const int t = threadIdx.x, l = t & 63, w = t >> 6;
-  const int m0 = blockIdx.x * SEP_BM, n0 = blockIdx.y * SEP_BN, u = blockIdx.z;
-  const int wr = w >> 1, wc = w & 1, half = l >> 5, l31 = l & 31;
-  const int Cin = a.C0 + a.C1, K = a.nt * a.nf * Cin, Mpos = a.Hj * a.Wj;
-  const float* x0 = a.x0 + (long long)(u / a.x0_div) * a.x0_us;
-  const float* x1 = a.C1 ? a.x1 + (long long)u * a.x1_us : nullptr;
-  const float* W = a.W + (long long)(u % a.I) * a.w_is;
-  int rt[8], rf[8];
-#pragma unroll
-  for (int r = 0; r < 8; ++r) {
-    const int pos = m0 + (t >> 5) + 8 * r;
-    if (pos < Mpos) {
-      const int jt = pos / a.Wj, jf = pos - jt * a.Wj;
-      rt[r] = a.S * jt + a.o0t; rf[r] = a.S * jf + a.o0f;
-    } else {
-      rt[r] = -(1 << 28); rf[r] = 0;
-    }
-  }
-  float ra[8], rb[8];
-  f32x16 tot[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) tot[c][r] = 0.f;
-#define ST_LOAD(k0)                                                                                         \
-  {                                                                                                         \
-    const int kg = (k0) + (t & 31);                                                                         \
-    const int tap = kg / Cin, ci = kg - tap * Cin, ta = tap / a.nf, tb = tap - ta * a.nf;                   \
-    _Pragma("unroll") for (int r = 0; r < 8; ++r)                                                           \
-      ra[r] = kg < K ? st_gather(a, x0, x1, rt[r] + a.d * ta, rf[r] + a.d * tb, ci) : 0.f;                  \
-    _Pragma("unroll") for (int r = 0; r < 8; ++r) {                                                         \
-      const int kb = (k0) + (t >> 6) + 4 * r, nb = n0 + (t & 63);                                           \
-      rb[r] = (kb < K && nb < a.N) ? W[(long long)kb * a.N + nb] : 0.f;                                     \
-    }                                                                                                       \
-  }
-  ST_LOAD(0)
-  int step = 0;
-  for (int k0 = 0; k0 < K; k0 += SEP_BK, ++step) {
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      As[t & 31][(t >> 5) + 8 * r] = ra[r];
-      Bs[(t >> 6) + 4 * r][t & 63] = rb[r];
-    }
-    __syncthreads();
-    if (k0 + SEP_BK < K) ST_LOAD(k0 + SEP_BK)
-    f32x16 p0, p1;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { p0[r] = 0.f; p1[r] = 0.f; }
-#pragma unroll
-    for (int kk = 0; kk < SEP_BK; kk += 4) {
-      p0 = __builtin_amdgcn_mfma_f32_32x32x2f32(As[kk + half][wr * 32 + l31], Bs[kk + half][wc * 32 + l31], p0, 0, 0, 0);
-      p1 = __builtin_amdgcn_mfma_f32_32x32x2f32(As[kk + 2 + half][wr * 32 + l31], Bs[kk + 2 + half][wc * 32 + l31], p1, 0, 0, 0);
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) p0[r] += p1[r];
-    switch (step & 3) {
-      case 0: for (int r = 0; r < 16; ++r) tot[0][r] += p0[r]; break;
-      case 1: for (int r = 0; r < 16; ++r) tot[1][r] += p0[r]; break;
-      case 2: for (int r = 0; r < 16; ++r) tot[2][r] += p0[r]; break;
-      default: for (int r = 0; r < 16; ++r) tot[3][r] += p0[r]; break;
-    }
-  }
-#undef ST_LOAD
-  const int col = n0 + wc * 32 + l31;
-  if (col >= a.N) return;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int pos = m0 + wr * 32 + acc_row(r, half);
-    if (pos >= Mpos) continue;
-    const int jt = pos / a.Wj, jf = pos - jt * a.Wj;
-    st_store(a, u, jt, jf, col, (tot[0][r] + tot[1][r]) + (tot[2][r] + tot[3][r]));
-  }
-}
-
-__global__ __launch_bounds__(SEP_THREADS) void k_st_conv_valu(const StConv a, long long total) {
-  const long long e = (long long)blockIdx.x * SEP_THREADS + threadIdx.x;
-  if (e >= total) return;
-  const int col = (int)(e % a.N);
-  const long long q = e / a.N;
-  const int Mpos = a.Hj * a.Wj;
-  const int pos = (int)(q % Mpos), u = (int)(q / Mpos);
-  const int jt = pos / a.Wj, jf = pos - jt * a.Wj;
-  const int Cin = a.C0 + a.C1;
-  const float* x0 = a.x0 + (long long)(u / a.x0_div) * a.x0_us;
-  const float* x1 = a.C1 ? a.x1 + (long long)u * a.x1_us : nullptr;
-  const float* W = a.W + (long long)(u % a.I) * a.w_is + col;
-  float sum = 0.f;
-  for (int ta = 0; ta < a.nt; ++ta) {
-    const int it = a.S * jt + a.o0t + a.d * ta;
-    if (it < 0 || it >= a.Hin) continue;
-    for (int tb = 0; tb < a.nf; ++tb) {
-      const int jx = a.S * jf + a.o0f + a.d * tb;
-      if (jx < 0 || jx >= a.Win) continue;
-      const int p = it * a.Win + jx;
-      const float* wk = W + (long long)(ta * a.nf + tb) * Cin * a.N;
-      float acc = 0.f;
-      for (int ci = 0; ci < a.C0; ++ci) acc = fmaf(x0[p * a.C0 + ci], wk[(long long)ci * a.N], acc);
-      for (int ci = 0; ci < a.C1; ++ci) acc = fmaf(x1[p * a.C1 + ci], wk[(long long)(a.C0 + ci) * a.N], acc);
-      sum += acc;
-    }
-  }
-  st_store(a, u, jt, jf, col, sum);
-}
-
+// ================================================================================================ convolutions (the kernels: separator.hip, through sep_launch)
 // dst [inst][a][b][r][c] = src [inst][kt(a)][kf(b)][c][r]: the taps of one output parity with the two channel axes swapped
 __global__ void k_st_pack(const float* __restrict__ src, float* __restrict__ dst, int pt, int pf, int nt, int nf, int R, int Cc, long long src_is, long long total) {
   const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -162,13 +43,13 @@ __global__ void k_st_pack(const float* __restrict__ src, float* __restrict__ dst
   const int c = (int)(q % Cc); q /= Cc;
   const int r = (int)(q % R); q /= R;
   const int b = (int)(q % nf), a = (int)(q / nf);
-  const int kt = pt ? 2 * a : 1 + 2 * a, kf = pf ? 2 * b : 1 + 2 * b;
+  const int kt = sep_dec_tap(pt, a), kf = sep_dec_tap(pf, b);
   dst[e] = src[inst * src_is + ((long long)(kt * 5 + kf) * Cc + c) * R + r];
 }
 
 // ================================================================================================ weight gradients
 // grid (M tiles, N tiles, instruments x slices).  Thread t loads column t & 63 of both tiles (m of A, n of B) at rows k = (t >> 6) + 4 r of the step; the sum over a
-// slice runs in k_sep_conv_mfma's order: per step of 32 two chains of 8 MFMAs, added, into one of four running totals that are added pairwise at the end.
+// slice runs in the order of separator.h's tile step, as the forward's does.
 __global__ __launch_bounds__(SEP_THREADS) void k_st_dw(const StDw a) {
   __shared__ float As[SEP_BK][SEP_LD], Bs[SEP_BK][SEP_LD];
   const int t = threadIdx.x, l = t & 63, w = t >> 6;
@@ -187,10 +68,7 @@ __global__ __launch_bounds__(SEP_THREADS) void k_st_dw(const StDw a) {
   }
   float ra[8], rb[8];
   f32x16 tot[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) tot[c][r] = 0.f;
+  sep_tile_zero(tot);
 #define ST_DW_LOAD(k0)                                                                                       \
   {                                                                                                          \
     _Pragma("unroll") for (int r = 0; r < 8; ++r) {                                                          \
@@ -220,22 +98,7 @@ __global__ __launch_bounds__(SEP_THREADS) void k_st_dw(const StDw a) {
     }
     __syncthreads();
     if (k0 + SEP_BK < kend) ST_DW_LOAD(k0 + SEP_BK)
-    f32x16 p0, p1;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { p0[r] = 0.f; p1[r] = 0.f; }
-#pragma unroll
-    for (int kk = 0; kk < SEP_BK; kk += 4) {
-      p0 = __builtin_amdgcn_mfma_f32_32x32x2f32(As[kk + half][wr * 32 + l31], Bs[kk + half][wc * 32 + l31], p0, 0, 0, 0);
-      p1 = __builtin_amdgcn_mfma_f32_32x32x2f32(As[kk + 2 + half][wr * 32 + l31], Bs[kk + 2 + half][wc * 32 + l31], p1, 0, 0, 0);
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) p0[r] += p1[r];
-    switch (step & 3) {
-      case 0: for (int r = 0; r < 16; ++r) tot[0][r] += p0[r]; break;
-      case 1: for (int r = 0; r < 16; ++r) tot[1][r] += p0[r]; break;
-      case 2: for (int r = 0; r < 16; ++r) tot[2][r] += p0[r]; break;
-      default: for (int r = 0; r < 16; ++r) tot[3][r] += p0[r]; break;
-    }
+    sep_tile_step(As, Bs, wr * 32 + l31, wc * 32 + l31, half, step, tot);
   }
 #undef ST_DW_LOAD
   const int col = n0 + wc * 32 + l31;
@@ -244,7 +107,7 @@ __global__ __launch_bounds__(SEP_THREADS) void k_st_dw(const StDw a) {
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int row = m0 + wr * 32 + acc_row(r, half);
-    if (row < Mtot) out[(long long)row * N + col] = (tot[0][r] + tot[1][r]) + (tot[2][r] + tot[3][r]);
+    if (row < Mtot) out[(long long)row * N + col] = sep_tile_total(tot, r);
   }
 }
 
@@ -452,39 +315,18 @@ __global__ __launch_bounds__(256) void k_st_loss(const float* __restrict__ logit
   if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
 }
 
-// ================================================================================================ optimizer (the pattern of dec_train.hip)
-#define ST_NORM_BLOCKS 256
-__global__ __launch_bounds__(256) void k_st_sumsq(const float* __restrict__ g, long long n, long long chunk, double* __restrict__ partial) {
-  __shared__ double ps[256];
-  const long long b0 = (long long)blockIdx.x * chunk, b1 = b0 + chunk < n ? b0 + chunk : n;
-  double a = 0.0;
-  for (long long i = b0 + threadIdx.x; i < b1; i += 256) { const double v = (double)g[i]; a += v * v; }
-  ps[threadIdx.x] = a;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double tot = 0.0;
-    for (int i = 0; i < 256; ++i) tot += ps[i];
-    partial[blockIdx.x] = tot;
-  }
-}
-
+// ================================================================================================ optimizer (the norm and the scalars: train_optim.h)
 #pragma clang fp contract(off)
-// a v_mul_f32 of its own (dec_train.hip's mul_scalar: the vectoriser must not pair these multiplies into a packed form with a crossed op_sel)
-__device__ __forceinline__ float st_mul(float a, float b) {
-  float r;
-  asm volatile("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
 // g *= coef (clipping; 1 without), then torch.optim.Adam's single-tensor step.  1 - beta arrive as the host's double differences rounded once.
 __global__ void k_st_adam(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long long n, float coef, float one_minus_beta1,
                           float beta2, float one_minus_beta2, float step_size, float bc2_sqrt, float eps) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const float gi = st_mul(g[i], coef);
+  const float gi = mul_scalar(g[i], coef);
   const float mi = fmaf(one_minus_beta1, gi - m[i], m[i]);                            // exp_avg.lerp_(grad, 1 - beta1): torch's CPU kernel ends in one fma
-  const float vi = fmaf(st_mul(one_minus_beta2, gi), gi, st_mul(v[i], beta2));        // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2): likewise
+  const float vi = fmaf(mul_scalar(one_minus_beta2, gi), gi, mul_scalar(v[i], beta2));        // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2): likewise
   const float denom = sqrtf(vi) / bc2_sqrt + eps;
-  p[i] = p[i] + st_mul(-step_size, mi) / denom;                                       // p.addcdiv_(exp_avg, denom, value = -step_size): the numerator is scaled first
+  p[i] = p[i] + mul_scalar(-step_size, mi) / denom;                                       // p.addcdiv_(exp_avg, denom, value = -step_size): the numerator is scaled first
   g[i] = gi; m[i] = mi; v[i] = vi;
 }
 #pragma clang fp contract(on)
@@ -497,8 +339,8 @@ struct StPar { long long off = 0, per = 0; };      // [I][per] at P + off
 struct etd_septrain {
   etd_sep_cfg cfg;
   int I = 0, C = 0, max_units = 0;
-  int Cenc[ETD_SEP_LEVELS + 1], Cdout[ETD_SEP_LEVELS + 1];
-  long long szE[ETD_SEP_LEVELS + 1], szD[ETD_SEP_LEVELS + 1], plane = 0, szmax = 0;      // floats of one unit's conv_l / decoder j output, a segment, the largest
+  SepNet net;
+  long long plane = 0, szmax = 0;      // floats of a segment and of the largest tensor of a unit
   StPar conv_w[ETD_SEP_LEVELS + 1], conv_b[ETD_SEP_LEVELS + 1], dec_w[ETD_SEP_LEVELS + 1], dec_b[ETD_SEP_LEVELS + 1], head_w, head_b;
   long long gam0 = 0, bet0 = 0, noff[2 * ETD_SEP_LEVELS + 2], NS = 0;                   // norm n's [I][C_n] block starts at noff[n] of every [NS] array
   long long n_train = 0, n_total = 0;                                                   // P = [trainable | running mean [NS] | running var [NS]]
@@ -513,13 +355,12 @@ struct etd_septrain {
   bool pack_dirty = true;
   long long step = 0;
   double drop_p = 0.0; unsigned long long drop_seed = 0; long long drop_calls = 0;      // decoder dropout: off at p = 0; drop_calls counts the backward calls with p > 0
-  char* ws = nullptr; long long ws_bytes = 0;
-  int normC(int n) const { return n <= ETD_SEP_LEVELS ? Cenc[n] : Cdout[n - ETD_SEP_LEVELS]; }
+  Workspace ws;
+  int normC(int n) const { return n <= ETD_SEP_LEVELS ? net.Cenc[n] : net.Cdout[n - ETD_SEP_LEVELS]; }
 };
 
 namespace {
 
-inline int st_taps(int p) { return p ? 3 : 2; }
 inline unsigned st_grid(long long n, int threads = 256) { return (unsigned)((n + threads - 1) / threads); }
 
 struct StPlan {                      // offsets in floats of the workspace of a call with B units per instrument
@@ -536,16 +377,16 @@ void st_plan(const etd_septrain* h, int B, StPlan* p) {
   auto take = [&](long long floats) { const long long at = o; o += (floats + 63) & ~63LL; return at; };
   long long part = 0, cpart = 0;
   for (int l = 1; l <= ETD_SEP_LEVELS; ++l) {
-    p->pre[l] = take(U * h->szE[l]);
-    p->act[l] = l < ETD_SEP_LEVELS ? take(U * h->szE[l]) : 0;
-    p->v[l] = take(U * h->szD[l]);
-    p->y[l] = take(U * h->szD[l]);
-    p->D[l] = take(U * h->szE[l]);
+    p->pre[l] = take(U * h->net.szE[l]);
+    p->act[l] = l < ETD_SEP_LEVELS ? take(U * h->net.szE[l]) : 0;
+    p->v[l] = take(U * h->net.szD[l]);
+    p->y[l] = take(U * h->net.szD[l]);
+    p->D[l] = take(U * h->net.szE[l]);
     const long long Pe = (long long)(h->cfg.T >> l) * (h->cfg.F >> l), Pd = (long long)(h->cfg.T >> (7 - l)) * (h->cfg.F >> (7 - l));
     part = std::max(part, st_slices(B * Pe) * h->conv_w[l].per);
     part = std::max(part, st_slices(B * Pd) * h->dec_w[l].per);
-    cpart = std::max(cpart, ((B * Pe + ST_COL_ROWS - 1) / ST_COL_ROWS) * h->Cenc[l]);
-    cpart = std::max(cpart, ((B * 4 * Pd + ST_COL_ROWS - 1) / ST_COL_ROWS) * h->Cdout[l]);
+    cpart = std::max(cpart, ((B * Pe + ST_COL_ROWS - 1) / ST_COL_ROWS) * h->net.Cenc[l]);
+    cpart = std::max(cpart, ((B * 4 * Pd + ST_COL_ROWS - 1) / ST_COL_ROWS) * h->net.Cdout[l]);
   }
   const long long Ph = (long long)h->cfg.T * h->cfg.F;
   part = std::max(part, st_slices(B * Ph) * h->head_w.per);
@@ -581,10 +422,10 @@ int st_upload(etd_septrain* h) {
     ETD_TRY(Q.alloc(&h->M1, (size_t)h->n_train, true));
     ETD_TRY(Q.alloc(&h->M2, (size_t)h->n_train, true));
     ETD_TRY(Q.alloc(&h->S, (size_t)(5 * h->NS), true));
-    ETD_TRY(Q.alloc(&h->norm_part, (size_t)ST_NORM_BLOCKS));
+    ETD_TRY(Q.alloc(&h->norm_part, (size_t)TN_BLOCKS));
     for (int l = 1; l <= ETD_SEP_LEVELS; ++l)
       for (int par = 0; par < 4; ++par) {
-        const long long taps = st_taps(par >> 1) * st_taps(par & 1);
+        const long long taps = sep_dec_taps(par >> 1) * sep_dec_taps(par & 1);
         ETD_TRY(Q.alloc(&h->dec_pk[l][par], (size_t)(h->dec_w[l].per / 25 * taps * h->I)));
         if (l > 1) ETD_TRY(Q.alloc(&h->conv_pk[l][par], (size_t)(h->conv_w[l].per / 25 * taps * h->I)));
       }
@@ -593,28 +434,19 @@ int st_upload(etd_septrain* h) {
   });
 }
 
-int st_reserve(etd_septrain* h, long long bytes, hipStream_t st) {
-  if (bytes <= h->ws_bytes) return ETD_OK;
-  HIP_TRY(hipStreamSynchronize(st));
-  if (h->ws) { (void)hipFree(h->ws); h->ws = nullptr; h->ws_bytes = 0; }
-  HIP_TRY(hipMalloc((void**)&h->ws, (size_t)bytes + 256));
-  h->ws_bytes = bytes;
-  return ETD_OK;
-}
-
 // the parity-packed, channel-swapped copies of the kernels the forward's transposed convolutions and the encoder's input gradients read
 int st_pack(etd_septrain* h, hipStream_t st) {
   if (!h->pack_dirty) return ETD_OK;
   for (int l = 1; l <= ETD_SEP_LEVELS; ++l)
     for (int par = 0; par < 4; ++par) {
-      const int pt = par >> 1, pf = par & 1, nt = st_taps(pt), nf = st_taps(pf);
+      const int pt = par >> 1, pf = par & 1, nt = sep_dec_taps(pt), nf = sep_dec_taps(pf);
       {      // deconv l: [kt][kf][co][ci] -> [a][b][ci][co]
-        const int Di = h->Cenc[7 - l] + (l > 1 ? h->Cdout[l - 1] : 0), Do = h->Cdout[l];
+        const int Di = h->net.Cenc[7 - l] + (l > 1 ? h->net.Cdout[l - 1] : 0), Do = h->net.Cdout[l];
         const long long total = (long long)h->I * nt * nf * Di * Do;
         hipLaunchKernelGGL(k_st_pack, dim3(st_grid(total)), dim3(256), 0, st, h->P + h->dec_w[l].off, h->dec_pk[l][par], pt, pf, nt, nf, Di, Do, h->dec_w[l].per, total);
       }
       if (l > 1) {      // conv l: [kt][kf][ci][co] -> [a][b][co][ci]
-        const int Ci = h->Cenc[l - 1], Co = h->Cenc[l];
+        const int Ci = h->net.Cenc[l - 1], Co = h->net.Cenc[l];
         const long long total = (long long)h->I * nt * nf * Ci * Co;
         hipLaunchKernelGGL(k_st_pack, dim3(st_grid(total)), dim3(256), 0, st, h->P + h->conv_w[l].off, h->conv_pk[l][par], pt, pf, nt, nf, Co, Ci, h->conv_w[l].per, total);
       }
@@ -624,109 +456,99 @@ int st_pack(etd_septrain* h, hipStream_t st) {
   return ETD_OK;
 }
 
-int st_conv(const StConv& a, int U, bool force_valu, hipStream_t st) {
-  const int K = a.nt * a.nf * (a.C0 + a.C1);
-  const long long Mpos = (long long)a.Hj * a.Wj;
-  if (K < SEP_MFMA_MIN_K || a.N == 1 || force_valu) {
-    const long long total = (long long)U * Mpos * a.N, blocks = (total + SEP_THREADS - 1) / SEP_THREADS;
-    if (blocks > 0x7fffffffLL) ETD_FAIL(ETD_EINVAL, "separator training: a convolution needs %lld workgroups (> 2^31 - 1)", blocks);
-    hipLaunchKernelGGL(k_st_conv_valu, dim3((unsigned)blocks), dim3(SEP_THREADS), 0, st, a, total);
-  } else {
-    const dim3 grid((unsigned)((Mpos + SEP_BM - 1) / SEP_BM), (unsigned)((a.N + SEP_BN - 1) / SEP_BN), (unsigned)U);
-    hipLaunchKernelGGL(k_st_conv_mfma, grid, dim3(SEP_THREADS), 0, st, a);
-  }
-  return ETD_OK;
-}
-
-StConv st_conv_base(const etd_septrain* h) {
-  StConv a{};
-  a.x0_div = 1; a.I = h->I; a.oS = 1;
+// a launch with the PLAIN epilogue: one output tensor with all N columns unless the caller splits them; unit u = b * I + instrument
+SepLaunch st_conv_base(const etd_septrain* h) {
+  SepLaunch a{};
+  a.x0_div = 1; a.I = h->I; a.epi = SEP_EPI_PLAIN;
   return a;
+}
+int st_launch(SepLaunch& a, float* out, long long out_us, int U, bool force_valu, hipStream_t st) {
+  a.N0 = a.N; a.pre = out; a.out_us = out_us;
+  return sep_launch(a, U, force_valu, nullptr, st);
 }
 
 // ---- forward launches -------------------------------------------------------------------------------------------------------------------------------------------
 int st_fwd_encoder(etd_septrain* h, int l, const float* x, float* pre, int U, hipStream_t st) {
-  StConv a = st_conv_base(h);
-  a.x0 = x; a.C0 = h->Cenc[l - 1];
-  if (l == 1) { a.x0_us = h->plane; a.x0_div = h->I; } else { a.x0_us = h->szE[l - 1]; }
-  a.Hin = h->cfg.T >> (l - 1); a.Win = h->cfg.F >> (l - 1); a.Hj = h->cfg.T >> l; a.Wj = h->cfg.F >> l;
-  a.S = 2; a.o0t = -1; a.o0f = -1; a.d = 1; a.nt = 5; a.nf = 5;
-  a.N = a.N0 = h->Cenc[l];
+  SepLaunch a = st_conv_base(h);
+  sep_geom_encoder(h->net, l, &a);
+  a.x0 = x;
+  if (l == 1) { a.x0_us = h->plane; a.x0_div = h->I; } else { a.x0_us = h->net.szE[l - 1]; }
   a.W = h->P + h->conv_w[l].off; a.w_is = h->conv_w[l].per; a.bias = h->P + h->conv_b[l].off;
-  a.out0 = pre; a.out0_us = h->szE[l]; a.Wout = a.Wj;
-  return st_conv(a, U, false, st);
+  return st_launch(a, pre, h->net.szE[l], U, false, st);
 }
 
 int st_fwd_decoder(etd_septrain* h, int j, const float* skip, const float* up, float* v, int U, hipStream_t st) {
   for (int par = 0; par < 4; ++par) {
-    const int pt = par >> 1, pf = par & 1;
-    StConv a = st_conv_base(h);
-    a.x0 = skip; a.x0_us = h->szE[7 - j]; a.C0 = h->Cenc[7 - j];
-    a.x1 = j > 1 ? up : nullptr; a.x1_us = j > 1 ? h->szD[j - 1] : 0; a.C1 = j > 1 ? h->Cdout[j - 1] : 0;
-    a.Hin = h->cfg.T >> (7 - j); a.Win = h->cfg.F >> (7 - j); a.Hj = a.Hin; a.Wj = a.Win;
-    a.S = 1; a.o0t = pt; a.o0f = pf; a.d = -1; a.nt = st_taps(pt); a.nf = st_taps(pf);
-    a.N = a.N0 = h->Cdout[j];
+    SepLaunch a = st_conv_base(h);
+    sep_geom_deconv(h->net, j, par >> 1, par & 1, &a);
+    a.x0 = skip; a.x0_us = h->net.szE[7 - j];
+    a.x1 = j > 1 ? up : nullptr; a.x1_us = j > 1 ? h->net.szD[j - 1] : 0;
     a.W = h->dec_pk[j][par]; a.w_is = (long long)a.nt * a.nf * (a.C0 + a.C1) * a.N; a.bias = h->P + h->dec_b[j].off;
-    a.out0 = v; a.out0_us = h->szD[j]; a.Wout = 2 * a.Win; a.oS = 2; a.opt = pt; a.opf = pf;
-    ETD_TRY(st_conv(a, U, false, st));
+    ETD_TRY(st_launch(a, v, h->net.szD[j], U, false, st));
   }
   return ETD_OK;
 }
 
 int st_fwd_head(etd_septrain* h, const float* x, float* logits, int U, hipStream_t st) {
-  StConv a = st_conv_base(h);
-  a.x0 = x; a.x0_us = (long long)h->cfg.T * h->cfg.F; a.C0 = 1;
-  a.Hin = h->cfg.T; a.Win = h->cfg.F; a.Hj = a.Hin; a.Wj = a.Win;
-  a.S = 1; a.o0t = -3; a.o0f = -3; a.d = 2; a.nt = 4; a.nf = 4;
-  a.N = a.N0 = h->C;
+  SepLaunch a = st_conv_base(h);
+  sep_geom_head(h->net, &a);
+  a.x0 = x; a.x0_us = (long long)h->cfg.T * h->cfg.F;
   a.W = h->P + h->head_w.off; a.w_is = h->head_w.per; a.bias = h->P + h->head_b.off;
-  a.out0 = logits; a.out0_us = h->plane; a.Wout = a.Win;
-  return st_conv(a, U, true, st);
+  return st_launch(a, logits, h->plane, U, true, st);
 }
 
-// ---- input gradients ---------------------------------------------------------------------------------------------------------------------------------------------
-// conv l (l >= 2): dpre [T >> l][F >> l][Cenc l] -> dx [T >> (l-1)][F >> (l-1)][Cenc l-1]
+// ---- input gradients (no bias) -----------------------------------------------------------------------------------------------------------------------------------
+// conv l (l >= 2): dpre [T >> l][F >> l][Cenc l] -> dx [T >> (l-1)][F >> (l-1)][Cenc l-1]: the geometry of the transposed convolution at conv l's size (decoder
+// 7 - l, whose output channels are Cenc l-1), without a second input
 int st_dx_encoder(etd_septrain* h, int l, const float* dpre, float* dx, int U, hipStream_t st) {
   for (int par = 0; par < 4; ++par) {
-    const int pt = par >> 1, pf = par & 1;
-    StConv a = st_conv_base(h);
-    a.x0 = dpre; a.x0_us = h->szE[l]; a.C0 = h->Cenc[l];
-    a.Hin = h->cfg.T >> l; a.Win = h->cfg.F >> l; a.Hj = a.Hin; a.Wj = a.Win;
-    a.S = 1; a.o0t = pt; a.o0f = pf; a.d = -1; a.nt = st_taps(pt); a.nf = st_taps(pf);
-    a.N = a.N0 = h->Cenc[l - 1];
-    a.W = h->conv_pk[l][par]; a.w_is = (long long)a.nt * a.nf * a.C0 * a.N; a.bias = nullptr;
-    a.out0 = dx; a.out0_us = h->szE[l - 1]; a.Wout = 2 * a.Win; a.oS = 2; a.opt = pt; a.opf = pf;
-    ETD_TRY(st_conv(a, U, false, st));
+    SepLaunch a = st_conv_base(h);
+    sep_geom_deconv(h->net, 7 - l, par >> 1, par & 1, &a);
+    a.C1 = 0;
+    a.x0 = dpre; a.x0_us = h->net.szE[l];
+    a.W = h->conv_pk[l][par]; a.w_is = (long long)a.nt * a.nf * a.C0 * a.N;
+    ETD_TRY(st_launch(a, dx, h->net.szE[l - 1], U, false, st));
   }
   return ETD_OK;
 }
 
-// decoder j: dv [2H][2W][Cdout j] -> dskip [H][W][Cenc 7-j] and dup [H][W][Cdout j-1] (j > 1)
-int st_dx_decoder(etd_septrain* h, int j, const float* dv, float* dskip, float* dup, int U, hipStream_t st) {
-  StConv a = st_conv_base(h);
-  a.x0 = dv; a.x0_us = h->szD[j]; a.C0 = h->Cdout[j];
-  a.Hj = h->cfg.T >> (7 - j); a.Wj = h->cfg.F >> (7 - j); a.Hin = 2 * a.Hj; a.Win = 2 * a.Wj;
-  a.S = 2; a.o0t = -1; a.o0f = -1; a.d = 1; a.nt = 5; a.nf = 5;
-  a.N0 = h->Cenc[7 - j]; a.N = a.N0 + (j > 1 ? h->Cdout[j - 1] : 0);
-  a.W = h->P + h->dec_w[j].off; a.w_is = h->dec_w[j].per; a.bias = nullptr;      // [kt][kf][co][ci] is this GEMM's [K][N]
-  a.out0 = dskip; a.out0_us = h->szE[7 - j]; a.out1 = dup; a.out1_us = j > 1 ? h->szD[j - 1] : 0; a.Wout = a.Wj;
-  return st_conv(a, U, false, st);
+// the convolution a transposed convolution's gradients run on: decoder j gathers dv [2H][2W][Cdout j] as conv 7 - j gathers its input, at the doubled size
+SepLaunch st_geom_dv(const etd_septrain* h, int j) {
+  SepLaunch a = st_conv_base(h);
+  sep_geom_encoder(h->net, 7 - j, &a);
+  a.C0 = h->net.Cdout[j];
+  return a;
 }
 
-// head: dlogits [T][F][C] -> dx [T][F][1]
+// decoder j: dv [2H][2W][Cdout j] -> dskip [H][W][Cenc 7-j] and dup [H][W][Cdout j-1] (j > 1)
+int st_dx_decoder(etd_septrain* h, int j, const float* dv, float* dskip, float* dup, int U, hipStream_t st) {
+  SepLaunch a = st_geom_dv(h, j);
+  a.x0 = dv; a.x0_us = h->net.szD[j];
+  a.N0 = a.N; a.N = a.N0 + (j > 1 ? h->net.Cdout[j - 1] : 0);
+  a.W = h->P + h->dec_w[j].off; a.w_is = h->dec_w[j].per;      // [kt][kf][co][ci] is this GEMM's [K][N]
+  a.out1 = dup; a.out1_us = j > 1 ? h->net.szD[j - 1] : 0;
+  a.pre = dskip; a.out_us = h->net.szE[7 - j];
+  return sep_launch(a, U, false, nullptr, st);
+}
+
+// head: dlogits [T][F][C] -> dx [T][F][1]: the head's geometry with offset and dilation negated and the channels swapped
 int st_dx_head(etd_septrain* h, const float* dlogits, float* dx, int U, hipStream_t st) {
-  StConv a = st_conv_base(h);
-  a.x0 = dlogits; a.x0_us = h->plane; a.C0 = h->C;
-  a.Hin = h->cfg.T; a.Win = h->cfg.F; a.Hj = a.Hin; a.Wj = a.Win;
-  a.S = 1; a.o0t = 3; a.o0f = 3; a.d = -2; a.nt = 4; a.nf = 4;
-  a.N = a.N0 = 1;
-  a.W = h->P + h->head_w.off; a.w_is = h->head_w.per; a.bias = nullptr;          // [kt][kf][1][co] read as [K = (tap, co)][1]
-  a.out0 = dx; a.out0_us = (long long)h->cfg.T * h->cfg.F; a.Wout = a.Win;
-  return st_conv(a, U, true, st);
+  SepLaunch a = st_conv_base(h);
+  sep_geom_head(h->net, &a);
+  a.o0t = -a.o0t; a.o0f = -a.o0f; a.d = -a.d; a.C0 = h->C; a.N = 1;
+  a.x0 = dlogits; a.x0_us = h->plane;
+  a.W = h->P + h->head_w.off; a.w_is = h->head_w.per;          // [kt][kf][1][co] read as [K = (tap, co)][1]
+  return st_launch(a, dx, (long long)h->cfg.T * h->cfg.F, U, true, st);
 }
 
 // ---- weight gradients --------------------------------------------------------------------------------------------------------------------------------------------
-int st_dw(etd_septrain* h, StDw a, int B, float* part, float* grad, hipStream_t st) {
+// g: the gathered tensor, read as the convolution `c` reads its first input; y = [y0 | y1]: the dense one, at c's Hj x Wj positions
+int st_dw(etd_septrain* h, const SepLaunch& c, const float* g, long long g_us, int g_div, const float* y0, long long y0_us, int N0, const float* y1, long long y1_us,
+          int N1, int B, float* part, float* grad, hipStream_t st) {
+  StDw a{};
+  a.g = g; a.g_us = g_us; a.g_div = g_div; a.Cg = c.C0; a.Hg = c.Hin; a.Wg = c.Win;
+  a.S = c.S; a.o0t = c.o0t; a.o0f = c.o0f; a.d = c.d; a.nt = c.nt; a.nf = c.nf; a.Hj = c.Hj; a.Wj = c.Wj;
+  a.y0 = y0; a.y0_us = y0_us; a.N0 = N0; a.y1 = y1; a.y1_us = y1_us; a.N1 = N1;
   const long long rows = (long long)B * a.Hj * a.Wj;
   a.B = B; a.I = h->I; a.slices = (int)st_slices(rows); a.part = part;
   const long long M = (long long)a.nt * a.nf * a.Cg, N = a.N0 + a.N1;
@@ -739,32 +561,20 @@ int st_dw(etd_septrain* h, StDw a, int B, float* part, float* grad, hipStream_t 
 }
 
 int st_dw_encoder(etd_septrain* h, int l, const float* x, const float* dpre, int B, float* part, float* grad, hipStream_t st) {
-  StDw a{};
-  a.g = x; a.Cg = h->Cenc[l - 1]; a.Hg = h->cfg.T >> (l - 1); a.Wg = h->cfg.F >> (l - 1);
-  if (l == 1) { a.g_us = h->plane; a.g_div = h->I; } else { a.g_us = h->szE[l - 1]; a.g_div = 1; }
-  a.S = 2; a.o0t = -1; a.o0f = -1; a.d = 1; a.nt = 5; a.nf = 5;
-  a.y0 = dpre; a.y0_us = h->szE[l]; a.N0 = h->Cenc[l]; a.y1 = nullptr; a.N1 = 0;
-  a.Hj = h->cfg.T >> l; a.Wj = h->cfg.F >> l;
-  return st_dw(h, a, B, part, grad, st);
+  SepLaunch c{};
+  sep_geom_encoder(h->net, l, &c);
+  return st_dw(h, c, x, l == 1 ? h->plane : h->net.szE[l - 1], l == 1 ? h->I : 1, dpre, h->net.szE[l], c.N, nullptr, 0, 0, B, part, grad, st);
 }
 
 int st_dw_decoder(etd_septrain* h, int j, const float* skip, const float* up, const float* dv, int B, float* part, float* grad, hipStream_t st) {
-  StDw a{};
-  a.Hj = h->cfg.T >> (7 - j); a.Wj = h->cfg.F >> (7 - j);
-  a.g = dv; a.g_us = h->szD[j]; a.g_div = 1; a.Cg = h->Cdout[j]; a.Hg = 2 * a.Hj; a.Wg = 2 * a.Wj;
-  a.S = 2; a.o0t = -1; a.o0f = -1; a.d = 1; a.nt = 5; a.nf = 5;
-  a.y0 = skip; a.y0_us = h->szE[7 - j]; a.N0 = h->Cenc[7 - j];
-  a.y1 = j > 1 ? up : nullptr; a.y1_us = j > 1 ? h->szD[j - 1] : 0; a.N1 = j > 1 ? h->Cdout[j - 1] : 0;
-  return st_dw(h, a, B, part, grad, st);
+  return st_dw(h, st_geom_dv(h, j), dv, h->net.szD[j], 1, skip, h->net.szE[7 - j], h->net.Cenc[7 - j], j > 1 ? up : nullptr, j > 1 ? h->net.szD[j - 1] : 0,
+               j > 1 ? h->net.Cdout[j - 1] : 0, B, part, grad, st);
 }
 
 int st_dw_head(etd_septrain* h, const float* x, const float* dlogits, int B, float* part, float* grad, hipStream_t st) {
-  StDw a{};
-  a.Hj = h->cfg.T; a.Wj = h->cfg.F;
-  a.g = x; a.g_us = (long long)h->cfg.T * h->cfg.F; a.g_div = 1; a.Cg = 1; a.Hg = a.Hj; a.Wg = a.Wj;
-  a.S = 1; a.o0t = -3; a.o0f = -3; a.d = 2; a.nt = 4; a.nf = 4;
-  a.y0 = dlogits; a.y0_us = h->plane; a.N0 = h->C; a.y1 = nullptr; a.N1 = 0;
-  return st_dw(h, a, B, part, grad, st);
+  SepLaunch c{};
+  sep_geom_head(h->net, &c);
+  return st_dw(h, c, x, (long long)h->cfg.T * h->cfg.F, 1, dlogits, h->plane, h->C, nullptr, 0, 0, B, part, grad, st);
 }
 
 // ---- reductions and elementwise passes ---------------------------------------------------------------------------------------------------------------------------
@@ -848,22 +658,6 @@ int st_dropout(const etd_septrain* h, int j, long long call, const float* x, flo
 }
 #define ST_DROP_LEVELS 3
 
-long long st_pos_enc(const etd_septrain* h, int l) { return (long long)(h->cfg.T >> l) * (h->cfg.F >> l); }
-long long st_pos_dec(const etd_septrain* h, int j) { return (long long)(h->cfg.T >> (6 - j)) * (h->cfg.F >> (6 - j)); }
-
-int st_grad_norm(etd_septrain* h, hipStream_t st, double* out) {
-  const long long n = h->n_train, chunk = (n + ST_NORM_BLOCKS - 1) / ST_NORM_BLOCKS;
-  hipLaunchKernelGGL(k_st_sumsq, dim3(ST_NORM_BLOCKS), dim3(256), 0, st, h->G, n, chunk, h->norm_part);
-  HIP_TRY(hipGetLastError());
-  double part[ST_NORM_BLOCKS];
-  HIP_TRY(hipMemcpyAsync(part, h->norm_part, sizeof(part), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  double tot = 0.0;
-  for (int i = 0; i < ST_NORM_BLOCKS; ++i) tot += part[i];
-  *out = sqrt(tot);
-  return ETD_OK;
-}
-
 }  // namespace
 
 extern "C" int etd_septrain_create(const etd_sep_cfg* cfg, int max_units, const char* const* instr_names, const char* const* names, const float* const* host_ptrs,
@@ -878,28 +672,19 @@ extern "C" int etd_septrain_create(const etd_sep_cfg* cfg, int max_units, const 
   if (max_units < 1 || (long long)max_units * c.n_instr > 16384) ETD_FAIL(ETD_EINVAL, "septrain_create: max_units = %d must be in 1 .. 16384 / n_instr", max_units);
   etd_septrain* h = new etd_septrain();
   h->cfg = c; h->I = c.n_instr; h->C = c.n_channels; h->max_units = max_units;
-  h->Cenc[0] = c.n_channels;
-  for (int l = 1; l <= ETD_SEP_LEVELS; ++l) h->Cenc[l] = c.filters[l - 1];
-  h->Cdout[0] = 0;
-  for (int j = 1; j < ETD_SEP_LEVELS; ++j) h->Cdout[j] = c.filters[ETD_SEP_LEVELS - 1 - j];
-  h->Cdout[ETD_SEP_LEVELS] = 1;
+  sep_net_init(&h->net, c);
   h->plane = (long long)c.T * c.F * c.n_channels;
   h->szmax = h->plane;
-  h->szE[0] = h->szD[0] = 0;
-  for (int l = 1; l <= ETD_SEP_LEVELS; ++l) {
-    h->szE[l] = (long long)(c.T >> l) * (c.F >> l) * h->Cenc[l];
-    h->szD[l] = (long long)(c.T >> (6 - l)) * (c.F >> (6 - l)) * h->Cdout[l];
-    h->szmax = std::max(h->szmax, std::max(h->szE[l], h->szD[l]));
-  }
+  for (int l = 1; l <= ETD_SEP_LEVELS; ++l) h->szmax = std::max(h->szmax, std::max(h->net.szE[l], h->net.szD[l]));
   const long long I = h->I;
   long long o = 0;
   auto place = [&](StPar& p, long long per) { p.off = o; p.per = per; o += per * I; };
   for (int l = 1; l <= ETD_SEP_LEVELS; ++l) {
-    place(h->conv_w[l], 25LL * h->Cenc[l - 1] * h->Cenc[l]);
-    place(h->conv_b[l], h->Cenc[l]);
-    const long long Di = h->Cenc[7 - l] + (l > 1 ? h->Cdout[l - 1] : 0);
-    place(h->dec_w[l], 25LL * h->Cdout[l] * Di);
-    place(h->dec_b[l], h->Cdout[l]);
+    place(h->conv_w[l], 25LL * h->net.Cenc[l - 1] * h->net.Cenc[l]);
+    place(h->conv_b[l], h->net.Cenc[l]);
+    const long long Di = h->net.Cenc[7 - l] + (l > 1 ? h->net.Cdout[l - 1] : 0);
+    place(h->dec_w[l], 25LL * h->net.Cdout[l] * Di);
+    place(h->dec_b[l], h->net.Cdout[l]);
   }
   place(h->head_w, 16LL * c.n_channels);
   place(h->head_b, c.n_channels);
@@ -943,11 +728,8 @@ extern "C" int etd_septrain_create(const etd_sep_cfg* cfg, int max_units, const 
 
 extern "C" void etd_septrain_destroy(etd_septrain* h) {
   if (!h) return;
-  if (h->pool.uploaded || h->ws) {
-    (void)hipDeviceSynchronize();
-    h->pool.free_all();
-    if (h->ws) (void)hipFree(h->ws);
-  }
+  h->pool.release_uploaded();
+  h->ws.release();
   delete h;
 }
 
@@ -962,8 +744,8 @@ extern "C" double etd_septrain_step_flops(const etd_septrain* h, int B) {
   if (!h) return 0.0;
   double f = 0.0;      // one forward's multiply-adds that are not structural zeros
   for (int l = 1; l <= ETD_SEP_LEVELS; ++l) {
-    f += 2.0 * st_pos_enc(h, l) * 25.0 * h->Cenc[l - 1] * h->Cenc[l];
-    f += 2.0 * (st_pos_dec(h, l) / 4) * (double)h->dec_w[l].per;
+    f += 2.0 * h->net.posE(l) * 25.0 * h->net.Cenc[l - 1] * h->net.Cenc[l];
+    f += 2.0 * (h->net.posD(l) / 4) * (double)h->dec_w[l].per;
   }
   f += 2.0 * (double)h->cfg.T * h->cfg.F * 16.0 * h->C;
   return 3.0 * f * h->I * B;      // forward, input gradient, weight gradient
@@ -977,9 +759,9 @@ extern "C" int etd_septrain_forward_backward(etd_septrain* h, const float* mix, 
   ETD_TRY(st_check_batch(h, B, &p, "septrain_forward_backward"));
   hipStream_t st = (hipStream_t)stream;
   ETD_TRY(st_upload(h));
-  ETD_TRY(st_reserve(h, p.total_bytes, st));
+  ETD_TRY(h->ws.reserve(p.total_bytes, st));
   ETD_TRY(st_pack(h, st));
-  float* ws = (float*)h->ws;
+  float* ws = (float*)h->ws.p;
   float* cpart = ws + p.cpart;
   const int U = B * h->I, L = ETD_SEP_LEVELS;
   const bool drop = backward && h->drop_p > 0.0;      // never in the loss-only (validation) path
@@ -987,14 +769,14 @@ extern "C" int etd_septrain_forward_backward(etd_septrain* h, const float* mix, 
   // ---- forward
   for (int l = 1; l <= L; ++l) {
     ETD_TRY(st_fwd_encoder(h, l, l == 1 ? mix : ws + p.act[l - 1], ws + p.pre[l], U, st));
-    if (!frozen_stats) ETD_TRY(st_stats(h, l, ws + p.pre[l], st_pos_enc(h, l), B, cpart, st));
-    if (l < L) ETD_TRY(st_ew(h, ST_EW_ENC, l, ws + p.pre[l], nullptr, nullptr, ws + p.act[l], h->szE[l], U, st));
+    if (!frozen_stats) ETD_TRY(st_stats(h, l, ws + p.pre[l], h->net.posE(l), B, cpart, st));
+    if (l < L) ETD_TRY(st_ew(h, ST_EW_ENC, l, ws + p.pre[l], nullptr, nullptr, ws + p.act[l], h->net.szE[l], U, st));
   }
   for (int j = 1; j <= L; ++j) {
     ETD_TRY(st_fwd_decoder(h, j, ws + p.pre[7 - j], j > 1 ? ws + p.y[j - 1] : nullptr, ws + p.v[j], U, st));
-    if (!frozen_stats) ETD_TRY(st_stats(h, L + j, ws + p.v[j], st_pos_dec(h, j), B, cpart, st));
-    ETD_TRY(st_ew(h, ST_EW_DEC, L + j, ws + p.v[j], nullptr, nullptr, ws + p.y[j], h->szD[j], U, st));
-    if (drop && j <= ST_DROP_LEVELS) ETD_TRY(st_dropout(h, j, h->drop_calls, ws + p.y[j], ws + p.y[j], U * h->szD[j], st));      // after the statistics, before any reader
+    if (!frozen_stats) ETD_TRY(st_stats(h, L + j, ws + p.v[j], h->net.posD(j), B, cpart, st));
+    ETD_TRY(st_ew(h, ST_EW_DEC, L + j, ws + p.v[j], nullptr, nullptr, ws + p.y[j], h->net.szD[j], U, st));
+    if (drop && j <= ST_DROP_LEVELS) ETD_TRY(st_dropout(h, j, h->drop_calls, ws + p.y[j], ws + p.y[j], U * h->net.szD[j], st));      // after the statistics, before any reader
   }
   ETD_TRY(st_fwd_head(h, ws + p.y[L], ws + p.logits, U, st));
   if (!frozen_stats) {      // the running statistics move once per call
@@ -1013,16 +795,16 @@ extern "C" int etd_septrain_forward_backward(etd_septrain* h, const float* mix, 
   ETD_TRY(st_dx_head(h, cur, other, U, st));
   std::swap(cur, other);
   for (int j = L; j >= 1; --j) {      // cur = dy_j
-    if (drop && j <= ST_DROP_LEVELS) ETD_TRY(st_dropout(h, j, h->drop_calls, cur, cur, U * h->szD[j], st));      // the forward's mask, regenerated
-    ETD_TRY(st_norm_bwd(h, L + j, ws + p.v[j], cur, nullptr, cur, st_pos_dec(h, j), B, frozen_stats, cpart, st));      // cur = dv_j
-    ETD_TRY(st_bias_grad(h, cur, st_pos_dec(h, j), h->Cdout[j], B, cpart, h->G + h->dec_b[j].off, st));
+    if (drop && j <= ST_DROP_LEVELS) ETD_TRY(st_dropout(h, j, h->drop_calls, cur, cur, U * h->net.szD[j], st));      // the forward's mask, regenerated
+    ETD_TRY(st_norm_bwd(h, L + j, ws + p.v[j], cur, nullptr, cur, h->net.posD(j), B, frozen_stats, cpart, st));      // cur = dv_j
+    ETD_TRY(st_bias_grad(h, cur, h->net.posD(j), h->net.Cdout[j], B, cpart, h->G + h->dec_b[j].off, st));
     ETD_TRY(st_dw_decoder(h, j, ws + p.pre[7 - j], j > 1 ? ws + p.y[j - 1] : nullptr, cur, B, part, h->G + h->dec_w[j].off, st));
     ETD_TRY(st_dx_decoder(h, j, cur, ws + p.D[7 - j], other, U, st));
     std::swap(cur, other);
   }
   for (int l = L; l >= 1; --l) {      // D[l] = the skip's gradient; cur = dact_l for l < 6 (conv_6's normalised output is read by nothing)
-    if (l < L) ETD_TRY(st_norm_bwd(h, l, ws + p.pre[l], cur, ws + p.D[l], ws + p.D[l], st_pos_enc(h, l), B, frozen_stats, cpart, st));
-    ETD_TRY(st_bias_grad(h, ws + p.D[l], st_pos_enc(h, l), h->Cenc[l], B, cpart, h->G + h->conv_b[l].off, st));
+    if (l < L) ETD_TRY(st_norm_bwd(h, l, ws + p.pre[l], cur, ws + p.D[l], ws + p.D[l], h->net.posE(l), B, frozen_stats, cpart, st));
+    ETD_TRY(st_bias_grad(h, ws + p.D[l], h->net.posE(l), h->net.Cenc[l], B, cpart, h->G + h->conv_b[l].off, st));
     ETD_TRY(st_dw_encoder(h, l, l == 1 ? mix : ws + p.act[l - 1], ws + p.D[l], B, part, h->G + h->conv_w[l].off, st));
     if (l > 1) {
       ETD_TRY(st_dx_encoder(h, l, ws + p.D[l], other, U, st));
@@ -1058,7 +840,7 @@ extern "C" int etd_septrain_zero_grad(etd_septrain* h, void* stream) {
 extern "C" int etd_septrain_grad_norm(etd_septrain* h, double* norm, void* stream) {
   if (!h || !norm) ETD_FAIL(ETD_EINVAL, "septrain_grad_norm: null argument");
   ETD_TRY(st_upload(h));
-  return st_grad_norm(h, (hipStream_t)stream, norm);
+  return grad_norm(h->G, h->n_train, h->norm_part, (hipStream_t)stream, norm);
 }
 
 extern "C" int etd_septrain_step(etd_septrain* h, double max_norm, double lr, double beta1, double beta2, double eps, double* norm_out, void* stream) {
@@ -1067,17 +849,13 @@ extern "C" int etd_septrain_step(etd_septrain* h, double max_norm, double lr, do
     ETD_FAIL(ETD_EINVAL, "septrain_step: lr and eps must be >= 0 and the betas in [0, 1)");
   hipStream_t st = (hipStream_t)stream;
   ETD_TRY(st_upload(h));
-  double coef = 1.0;                                   // max_norm <= 0: no clipping, and no norm unless the caller asks
-  if (max_norm > 0.0 || norm_out) {
-    double norm = 0.0;
-    ETD_TRY(st_grad_norm(h, st, &norm));
-    if (norm_out) *norm_out = norm;
-    if (max_norm > 0.0) coef = std::min(1.0, max_norm / (norm + 1e-6));
-  }
+  double norm = 0.0;                                   // max_norm <= 0: no clipping, and no norm unless the caller asks
+  if (max_norm > 0.0 || norm_out) ETD_TRY(grad_norm(h->G, h->n_train, h->norm_part, st, &norm));
+  if (norm_out) *norm_out = norm;
   h->step += 1;
-  const double bc1 = 1.0 - pow(beta1, (double)h->step), bc2 = 1.0 - pow(beta2, (double)h->step);
-  hipLaunchKernelGGL(k_st_adam, dim3(st_grid(h->n_train)), dim3(256), 0, st, h->P, h->G, h->M1, h->M2, h->n_train, (float)coef, (float)(1.0 - beta1), (float)beta2,
-                     (float)(1.0 - beta2), (float)(lr / bc1), (float)sqrt(bc2), (float)eps);
+  const StepScalars s = step_scalars(max_norm, norm, lr, beta1, beta2, h->step);
+  hipLaunchKernelGGL(k_st_adam, dim3(st_grid(h->n_train)), dim3(256), 0, st, h->P, h->G, h->M1, h->M2, h->n_train, s.coef, (float)(1.0 - beta1), (float)beta2,
+                     (float)(1.0 - beta2), s.step_size, s.bc2_sqrt, (float)eps);
   HIP_TRY(hipGetLastError());
   h->pack_dirty = true;
   return ETD_OK;
@@ -1105,11 +883,7 @@ static int septrain_io(etd_septrain* h, const char* name, int which, float* out,
     return ETD_OK;
   }
   ETD_TRY(st_upload(h));
-  float* base = which == 0 ? h->P : which == 1 ? h->G : which == 2 ? h->M1 : h->M2;
-  if (out) HIP_TRY(hipMemcpyAsync(out, base + off, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, st));
-  else HIP_TRY(hipMemcpyAsync(base + off, in, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return ETD_OK;
+  return flat_io(h->P, h->G, h->M1, h->M2, which, off, n, out, in, st);
 }
 
 extern "C" int etd_septrain_read(etd_septrain* h, const char* name, int which, float* out_host, long long numel, void* stream) {
@@ -1153,8 +927,8 @@ extern "C" int etd_septrain_debug_dw(etd_septrain* h, int kind, int layer, const
   ETD_TRY(st_check_batch(h, B, &p, "septrain_debug_dw"));
   hipStream_t st = (hipStream_t)stream;
   ETD_TRY(st_upload(h));
-  ETD_TRY(st_reserve(h, p.total_bytes, st));
-  float* part = (float*)h->ws + p.part;
+  ETD_TRY(h->ws.reserve(p.total_bytes, st));
+  float* part = (float*)h->ws.p + p.part;
   if (kind != 2 && (layer < 1 || layer > ETD_SEP_LEVELS)) ETD_FAIL(ETD_EINVAL, "septrain_debug_dw: layer = %d outside 1 .. %d", layer, ETD_SEP_LEVELS);
   if (kind == 0) {
     ETD_TRY(st_dw_encoder(h, layer, x0_dev, dy_dev, B, part, dw_dev, st));
@@ -1178,10 +952,10 @@ extern "C" int etd_septrain_debug_norm(etd_septrain* h, int norm, const float* x
   ETD_TRY(st_check_batch(h, B, &p, "septrain_debug_norm"));
   hipStream_t st = (hipStream_t)stream;
   ETD_TRY(st_upload(h));
-  ETD_TRY(st_reserve(h, p.total_bytes, st));
-  float* cpart = (float*)h->ws + p.cpart;
+  ETD_TRY(h->ws.reserve(p.total_bytes, st));
+  float* cpart = (float*)h->ws.p + p.cpart;
   const bool dec = norm > ETD_SEP_LEVELS;
-  const long long P = dec ? st_pos_dec(h, norm - ETD_SEP_LEVELS) : st_pos_enc(h, norm);
+  const long long P = dec ? h->net.posD(norm - ETD_SEP_LEVELS) : h->net.posE(norm);
   const int C = h->normC(norm), U = B * h->I;
   ETD_TRY(st_stats(h, norm, x_dev, P, B, cpart, st));
   ETD_TRY(st_ew(h, dec ? ST_EW_DEC : ST_EW_ENC, norm, x_dev, nullptr, nullptr, y_dev, P * C, U, st));
@@ -1201,8 +975,8 @@ extern "C" int etd_septrain_debug_loss(etd_septrain* h, const float* logits_dev,
   ETD_TRY(st_check_batch(h, B, &p, "septrain_debug_loss"));
   hipStream_t st = (hipStream_t)stream;
   ETD_TRY(st_upload(h));
-  ETD_TRY(st_reserve(h, p.total_bytes, st));
-  return st_loss(h, logits_dev, mix_dev, target_dev, B, loss_scale, (float*)h->ws + p.lpart, p.loss_blocks, dlogits_dev, loss_out, st);
+  ETD_TRY(h->ws.reserve(p.total_bytes, st));
+  return st_loss(h, logits_dev, mix_dev, target_dev, B, loss_scale, (float*)h->ws.p + p.lpart, p.loss_blocks, dlogits_dev, loss_out, st);
 }
 
 extern "C" int etd_septrain_debug_dropout(etd_septrain* h, int j, const float* y_dev, int B, long long numel, long long call, float* out_dev, void* stream) {
@@ -1211,7 +985,7 @@ extern "C" int etd_septrain_debug_dropout(etd_septrain* h, int j, const float* y
   if (call < 0) ETD_FAIL(ETD_EINVAL, "septrain_debug_dropout: call = %lld is negative", call);
   StPlan p;
   ETD_TRY(st_check_batch(h, B, &p, "septrain_debug_dropout"));
-  const long long full = (long long)B * h->I * h->szD[j];
+  const long long full = (long long)B * h->I * h->net.szD[j];
   if (numel < 0 || numel > full) ETD_FAIL(ETD_EINVAL, "septrain_debug_dropout: numel = %lld outside 0 .. %lld", numel, full);
   ETD_TRY(st_dropout(h, j, call, y_dev, out_dev, numel ? numel : full, (hipStream_t)stream));
   HIP_TRY(hipGetLastError());

@@ -170,6 +170,32 @@ def test_adam_trajectory_of_five_steps():
     _verdict()
 
 
+# (filters, T, F, instruments, B): the MFMA path with K = 600 and N = 40 inside one 64-column tile and M = 2 below one tile; K = 50 < SEP_MFMA_MIN_K, the VALU path;
+# 16 x 8 = 128 output positions and N = 72: two M tiles and two N tiles, the second N tile ragged
+SHARED_CONV_CASES = [((3, 5, 8, 16, 24, 40), 128, 64, 2, 3), ((3, 5, 8, 16, 2, 40), 128, 64, 2, 3), ((3, 5, 8, 16, 24, 72), 1024, 512, 1, 1)]
+
+
+@pytest.mark.parametrize("filters,T,F,I,B", SHARED_CONV_CASES)
+def test_the_trainer_and_the_separator_convolve_alike(filters, T, F, I, B):
+    """the input gradient of transposed convolution 1 is the GEMM of encoder convolution 6 -- a 5 x 5 stride-2 convolution of dy with deconv1.weight [5][5][Cout][Cin]
+    read as [K][N]: with conv6.weight holding deconv1.weight's flat contents and no bias, the trainer's dskip and the separator's pre-norm output are the same bits"""
+    cfg = SeparatorConfig(instruments=tuple("abc"[:I]), n_fft=1024, hop=256, T=T, F=F, n_channels=2, conv_n_filters=filters)
+    state = init_separator_state(cfg, 5)
+    for n in cfg.instruments:
+        state[f"{n}.conv6.weight"] = state[f"{n}.deconv1.weight"].reshape(state[f"{n}.conv6.weight"].shape).copy()
+        state[f"{n}.conv6.bias"] = np.zeros_like(state[f"{n}.conv6.bias"])
+    tr = SeparatorTrainer(cfg, state, max_units=4)
+    sep = tr.to_separator()
+    dy = torch.randn(B, I, T >> 5, F >> 5, filters[4], generator=torch.Generator().manual_seed(37)).cuda()
+    dskip, dup = tr.debug_dx(1, 1, dy)
+    assert dup is None and tuple(dskip.shape) == (B, I, T >> 6, F >> 6, filters[5])
+    for i in range(I):
+        pre, _ = sep.debug_layer(i, 0, 6, dy[:, i])
+        assert np.array_equal(dskip[:, i].cpu().numpy(), pre.cpu().numpy()), i
+    assert bool(dskip.any())
+    tr.close()
+
+
 # ------------------------------------------------------------------ stage by stage
 def _taps(c):
     """the fp32 restatement's tensors around every layer, [B][I][..] as the device holds them"""
