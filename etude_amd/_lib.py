@@ -410,6 +410,16 @@ SIGNATURES = {
     "etd_dtrain_write_moment": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]),
     "etd_debug_dtrain_gemm": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "etd_debug_dtrain_attn": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "etd_debug_dtrain_ln": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float] + [C.c_void_p] * 11),
+    "etd_debug_dtrain_gelu": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "etd_debug_dtrain_add3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
+    "etd_debug_dtrain_rope": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "etd_debug_dtrain_embed": (C.c_int, [C.c_int] * 6 + [C.c_void_p] * 13),
+    "etd_debug_dtrain_ce": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    "etd_debug_dtrain_colred": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6),
+    "etd_debug_dtrain_embed_grad": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "etd_debug_dtrain_adamw": (C.c_int, [C.c_void_p] * 4 + [C.c_longlong] + [C.c_double] * 7 + [C.c_longlong, C.c_void_p]),
+    "etd_debug_dtrain_sumsq": (C.c_int, [C.c_void_p, C.c_longlong, C.POINTER(C.c_double), C.c_void_p]),
     "etd_debug_decoder_trace_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.POINTER(C.c_int), C.c_void_p]),
 }
 

@@ -515,6 +515,65 @@ __global__ void k_tadamw(float* __restrict__ p, float* __restrict__ g, float* __
 #pragma clang fp contract(on)
 
 // ================================================================================================
+// launchers: each kernel above with its grid and block, called by the engine and by the stage taps at the end of this file
+// ================================================================================================
+static inline dim3 ew_grid(long long n) { return dim3((unsigned)((n + 255) / 256)); }
+
+static void launch_trope(float* qkv, int nh, int M, const int* pos, const float* tab, float sign, hipStream_t st) {
+  hipLaunchKernelGGL(k_trope, ew_grid((long long)M * nh * 16), dim3(256), 0, st, qkv, nh, M, pos, tab, sign);
+}
+// mean / rstd (both or neither) and the second output may be NULL
+static void launch_tln_fwd(const float* x, int M, int H, float eps, float* mean, float* rstd, const float* g1, const float* b1, float* y1, const float* g2,
+                           const float* b2, float* y2, hipStream_t st) {
+  hipLaunchKernelGGL(k_tln_fwd, dim3(M), dim3(64), 0, st, x, M, H, eps, mean, rstd, g1, b1, y1, g2, b2, y2);
+}
+static void launch_tln_bwd(const float* dy, const float* x, const float* mean, const float* rstd, const float* g, int M, int H, float* dx, hipStream_t st) {
+  hipLaunchKernelGGL(k_tln_bwd, dim3(M), dim3(64), 0, st, dy, x, mean, rstd, g, H, dx);
+}
+static void launch_tgelu(const float* x, float* y, long long n, hipStream_t st) { hipLaunchKernelGGL(k_tgelu, ew_grid(n), dim3(256), 0, st, x, y, n); }
+static void launch_tgelu_bwd(const float* x, float* dy, long long n, hipStream_t st) { hipLaunchKernelGGL(k_tgelu_bwd, ew_grid(n), dim3(256), 0, st, x, dy, n); }
+static void launch_tadd3(const float* m, const float* a, const float* h, float* out, long long n, hipStream_t st) {
+  hipLaunchKernelGGL(k_tadd3, ew_grid(n), dim3(256), 0, st, m, a, h, out, n);
+}
+static void launch_tembed_gather(const int* attrs4, int M, int E, const float* t0, const float* t1, const float* t2, const float* t3, float* A, hipStream_t st) {
+  hipLaunchKernelGGL(k_tembed_gather, ew_grid((long long)M * 4 * E), dim3(256), 0, st, attrs4, M, E, t0, t1, t2, t3, A);
+}
+static void launch_tembed_sum(const int* ids, const int* cls, const float* word, const float* cemb, int M, int H, float* h, hipStream_t st) {
+  const long long n = (long long)M * H;
+  hipLaunchKernelGGL(k_tembed_sum, ew_grid(n), dim3(256), 0, st, ids, cls, word, cemb, H, h, n);
+}
+static void launch_tce(float* logits, int M, int V, const int* labels, float scale, float* row_loss, hipStream_t st) {
+  hipLaunchKernelGGL(k_tce, dim3(M), dim3(64), 0, st, logits, V, labels, scale, row_loss);
+}
+// mode 0: x, mean, rstd and g1 are not read (NULL)
+static void launch_tcolred(int mode, const float* dy, int ld, int M, int N, const float* x, const float* mean, const float* rstd, float* g0, float* g1,
+                           hipStream_t st) {
+  const dim3 grid((N + 31) / 32), block(256);
+  if (mode == 1) hipLaunchKernelGGL(k_tcolred<1>, grid, block, 0, st, dy, ld, M, N, x, mean, rstd, g0, g1);
+  else hipLaunchKernelGGL(k_tcolred<0>, grid, block, 0, st, dy, ld, M, N, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, g0, (float*)nullptr);
+}
+// grad [.][width] += the rows of src [.][ld] at columns [col0, col0 + width), by segment; a table none of whose rows has a segment is not launched
+static void launch_tembed_grad(const float* src, int ld, int col0, int width, const int* order, const int* seg_id, const int* seg_start, const int* seg_count,
+                               int n_seg, float* grad, hipStream_t st) {
+  if (n_seg > 0) hipLaunchKernelGGL(k_tembed_grad, dim3(n_seg, (width + 63) / 64), dim3(256), 0, st, src, ld, col0, width, order, seg_id, seg_start, seg_count, grad);
+}
+
+// the arguments of k_tadamw for optimizer step `step` (1-based): the step's scalars (train_optim.h) and the hyper-parameters, each a double rounded once
+struct AdamwArgs { float coef, decay, one_minus_beta1, beta2, one_minus_beta2, step_size, bc2_sqrt, eps; };
+static int adamw_check(const char* who, double lr, double beta1, double beta2, double eps, double weight_decay) {
+  if (!(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !(weight_decay >= 0.0))
+    ETD_FAIL(ETD_EINVAL, "%s: lr, eps, weight_decay must be >= 0 and the betas in [0, 1)", who);
+  return ETD_OK;
+}
+static AdamwArgs adamw_args(double max_norm, double norm, double lr, double beta1, double beta2, double eps, double weight_decay, long long step) {
+  const StepScalars s = step_scalars(max_norm, norm, lr, beta1, beta2, step);
+  return {s.coef, (float)(1.0 - lr * weight_decay), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), s.step_size, s.bc2_sqrt, (float)eps};
+}
+static void launch_tadamw(float* p, float* g, float* m, float* v, long long n, const AdamwArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(k_tadamw, ew_grid(n), dim3(256), 0, st, p, g, m, v, n, a.coef, a.decay, a.one_minus_beta1, a.beta2, a.one_minus_beta2, a.step_size, a.bc2_sqrt, a.eps);
+}
+
+// ================================================================================================
 // the engine
 // ================================================================================================
 struct TParam { std::string name; size_t off, n; };
@@ -677,8 +736,6 @@ extern "C" long long etd_dtrain_bytes(const etd_dtrain* d, int what) {
   return what == 0 ? (long long)d->workspace_bytes : (long long)(4 * d->n_total * sizeof(float));      // 0: activations + scratch; 1: weights, gradients, two moments
 }
 
-static inline dim3 ew_grid(long long n) { return dim3((unsigned)((n + 255) / 256)); }
-
 // stable grouping of M rows by table index: order / segments appended to `ints` at (o_order, o_seg ..); returns the number of segments (the padding row has none)
 static int group_rows(const int32_t* idx, int M, int n_rows, int pad, int* order, int* seg_id, int* seg_start, int* seg_count) {
   std::vector<int> cnt(n_rows + 1, 0);
@@ -756,30 +813,29 @@ extern "C" int etd_dtrain_forward_backward(etd_dtrain* d, int n, const int32_t* 
   // ================================================================ forward
   {
     ProfScope ps("dtrain_forward", st);
-    hipLaunchKernelGGL(k_tembed_gather, ew_grid((long long)M * 4 * E), dim3(256), 0, st, d_at, M, E, P + d->attr[0], P + d->attr[1], P + d->attr[2], P + d->attr[3], d->A4);
+    launch_tembed_gather(d_at, M, E, P + d->attr[0], P + d->attr[1], P + d->attr[2], P + d->attr[3], d->A4, st);
     ETD_TRY(launch_tgemm(ETD_TG_NT, M, H, 4 * E, d->A4, 4 * E, P + d->proj_w, 4 * E, P + d->proj_b, d->hs, H, false, st));
-    hipLaunchKernelGGL(k_tembed_sum, ew_grid(MH), dim3(256), 0, st, d_ids, d_cls, P + d->word, P + d->cemb, H, d->hs, MH);
+    launch_tembed_sum(d_ids, d_cls, P + d->word, P + d->cemb, M, H, d->hs, st);
     for (int l = 0; l < L; ++l) {
       const TLayer& y = d->layers[l];
       float* h = d->hs + (size_t)l * R * H;
       float* qkv = d->qkv + (size_t)l * R * 3 * H;
       float* att = d->att + (size_t)l * R * H;
       float* pre = d->pre + (size_t)l * R * I;
-      hipLaunchKernelGGL(k_tln_fwd, dim3(M), dim3(64), 0, st, h, M, H, eps, d->mean + (size_t)l * R, d->rstd + (size_t)l * R, P + y.ln1_w, P + y.ln1_b, d->wH1,
-                         P + y.ln2_w, P + y.ln2_b, d->wH2);
+      launch_tln_fwd(h, M, H, eps, d->mean + (size_t)l * R, d->rstd + (size_t)l * R, P + y.ln1_w, P + y.ln1_b, d->wH1, P + y.ln2_w, P + y.ln2_b, d->wH2, st);
       ETD_TRY(launch_tgemm(ETD_TG_NT, M, 3 * H, H, d->wH1, H, P + y.qkv_w, H, P + y.qkv_b, qkv, 3 * H, false, st));
-      hipLaunchKernelGGL(k_trope, ew_grid((long long)M * nh * 16), dim3(256), 0, st, qkv, nh, M, d_pos, d->rope, 1.f);
+      launch_trope(qkv, nh, M, d_pos, d->rope, 1.f, st);
       ETD_TRY(launch_tattn_fwd(qkv, nh, d_row0, d_len, n, max_len, att, d->lse + (size_t)l * R * nh, st));
       ETD_TRY(launch_tgemm(ETD_TG_NT, M, H, H, att, H, P + y.d_w, H, P + y.d_b, d->wH1, H, false, st));          // wH1: attention branch
       ETD_TRY(launch_tgemm(ETD_TG_NT, M, I, H, d->wH2, H, P + y.f1_w, H, P + y.f1_b, pre, I, false, st));
-      hipLaunchKernelGGL(k_tgelu, ew_grid(MI), dim3(256), 0, st, pre, d->wI, MI);
+      launch_tgelu(pre, d->wI, MI, st);
       ETD_TRY(launch_tgemm(ETD_TG_NT, M, H, I, d->wI, I, P + y.f2_w, I, P + y.f2_b, d->wH3, H, false, st));       // wH3: MLP branch
-      hipLaunchKernelGGL(k_tadd3, ew_grid(MH), dim3(256), 0, st, d->wH3, d->wH1, h, h + R * H, MH);
+      launch_tadd3(d->wH3, d->wH1, h, h + R * H, MH, st);
     }
-    hipLaunchKernelGGL(k_tln_fwd, dim3(M), dim3(64), 0, st, d->hs + (size_t)L * R * H, M, H, eps, d->mean + (size_t)L * R, d->rstd + (size_t)L * R,
-                       P + d->lnf_w, P + d->lnf_b, d->hf, (const float*)nullptr, (const float*)nullptr, (float*)nullptr);
+    launch_tln_fwd(d->hs + (size_t)L * R * H, M, H, eps, d->mean + (size_t)L * R, d->rstd + (size_t)L * R, P + d->lnf_w, P + d->lnf_b, d->hf, nullptr, nullptr,
+                   nullptr, st);
     ETD_TRY(launch_tgemm(ETD_TG_NT, M, V, H, d->hf, H, P + d->head, H, nullptr, d->logits, V, false, st));
-    hipLaunchKernelGGL(k_tce, dim3(M), dim3(64), 0, st, d->logits, V, d_lab, loss_scale / (float)scored, d->row_loss);
+    launch_tce(d->logits, M, V, d_lab, loss_scale / (float)scored, d->row_loss, st);
     HIP_TRY(hipGetLastError());
   }
   // ================================================================ backward
@@ -790,10 +846,9 @@ extern "C" int etd_dtrain_forward_backward(etd_dtrain* d, int n, const int32_t* 
     float* dxn = d->wH3;                               // gradient of a LayerNorm output / of the attention output
     ETD_TRY(launch_tgemm(ETD_TG_TN, V, H, M, d->logits, V, d->hf, H, nullptr, G + d->head, H, true, st));
     ETD_TRY(launch_tgemm(ETD_TG_NN, M, H, V, d->logits, V, P + d->head, H, nullptr, dxn, H, false, st));
-    hipLaunchKernelGGL(k_tcolred<1>, dim3((H + 31) / 32), dim3(256), 0, st, dxn, H, M, H, d->hs + (size_t)L * R * H, d->mean + (size_t)L * R, d->rstd + (size_t)L * R,
-                       G + d->lnf_b, G + d->lnf_w);
+    launch_tcolred(1, dxn, H, M, H, d->hs + (size_t)L * R * H, d->mean + (size_t)L * R, d->rstd + (size_t)L * R, G + d->lnf_b, G + d->lnf_w, st);
     HIP_TRY(hipMemsetAsync(dh, 0, sizeof(float) * MH, st));
-    hipLaunchKernelGGL(k_tln_bwd, dim3(M), dim3(64), 0, st, dxn, d->hs + (size_t)L * R * H, d->mean + (size_t)L * R, d->rstd + (size_t)L * R, P + d->lnf_w, H, dh);
+    launch_tln_bwd(dxn, d->hs + (size_t)L * R * H, d->mean + (size_t)L * R, d->rstd + (size_t)L * R, P + d->lnf_w, M, H, dh, st);
     for (int l = L - 1; l >= 0; --l) {
       const TLayer& y = d->layers[l];
       const float* h = d->hs + (size_t)l * R * H;
@@ -804,44 +859,39 @@ extern "C" int etd_dtrain_forward_backward(etd_dtrain* d, int n, const int32_t* 
       const float* pre = d->pre + (size_t)l * R * I;
       // dh is d loss / d (mlp + attn + h): the gradient of both branch outputs, and (kept) of h through the residual
       // ---- MLP branch
-      hipLaunchKernelGGL(k_tgelu, ew_grid(MI), dim3(256), 0, st, pre, d->wI, MI);
+      launch_tgelu(pre, d->wI, MI, st);
       ETD_TRY(launch_tgemm(ETD_TG_TN, H, I, M, dh, H, d->wI, I, nullptr, G + y.f2_w, I, true, st));
-      hipLaunchKernelGGL(k_tcolred<0>, dim3((H + 31) / 32), dim3(256), 0, st, dh, H, M, H, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, G + y.f2_b, (float*)nullptr);
+      launch_tcolred(0, dh, H, M, H, nullptr, nullptr, nullptr, G + y.f2_b, nullptr, st);
       ETD_TRY(launch_tgemm(ETD_TG_NN, M, I, H, dh, H, P + y.f2_w, I, nullptr, d->wI, I, false, st));
-      hipLaunchKernelGGL(k_tgelu_bwd, ew_grid(MI), dim3(256), 0, st, pre, d->wI, MI);
-      hipLaunchKernelGGL(k_tln_fwd, dim3(M), dim3(64), 0, st, h, M, H, eps, (float*)nullptr, (float*)nullptr, P + y.ln2_w, P + y.ln2_b, tx,
-                         (const float*)nullptr, (const float*)nullptr, (float*)nullptr);
+      launch_tgelu_bwd(pre, d->wI, MI, st);
+      launch_tln_fwd(h, M, H, eps, nullptr, nullptr, P + y.ln2_w, P + y.ln2_b, tx, nullptr, nullptr, nullptr, st);
       ETD_TRY(launch_tgemm(ETD_TG_TN, I, H, M, d->wI, I, tx, H, nullptr, G + y.f1_w, H, true, st));
-      hipLaunchKernelGGL(k_tcolred<0>, dim3((I + 31) / 32), dim3(256), 0, st, d->wI, I, M, I, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, G + y.f1_b, (float*)nullptr);
+      launch_tcolred(0, d->wI, I, M, I, nullptr, nullptr, nullptr, G + y.f1_b, nullptr, st);
       ETD_TRY(launch_tgemm(ETD_TG_NN, M, H, I, d->wI, I, P + y.f1_w, H, nullptr, dxn, H, false, st));
-      hipLaunchKernelGGL(k_tcolred<1>, dim3((H + 31) / 32), dim3(256), 0, st, dxn, H, M, H, h, mean, rstd, G + y.ln2_b, G + y.ln2_w);
+      launch_tcolred(1, dxn, H, M, H, h, mean, rstd, G + y.ln2_b, G + y.ln2_w, st);
       // ---- attention branch (before dh takes the LayerNorm terms: both branches read the incoming dh)
       ETD_TRY(launch_tgemm(ETD_TG_TN, H, H, M, dh, H, att, H, nullptr, G + y.d_w, H, true, st));
-      hipLaunchKernelGGL(k_tcolred<0>, dim3((H + 31) / 32), dim3(256), 0, st, dh, H, M, H, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, G + y.d_b, (float*)nullptr);
+      launch_tcolred(0, dh, H, M, H, nullptr, nullptr, nullptr, G + y.d_b, nullptr, st);
       ETD_TRY(launch_tgemm(ETD_TG_NN, M, H, H, dh, H, P + y.d_w, H, nullptr, tx, H, false, st));                 // tx: d loss / d attention output
-      hipLaunchKernelGGL(k_tln_bwd, dim3(M), dim3(64), 0, st, dxn, h, mean, rstd, P + y.ln2_w, H, dh);            // (the MLP branch's LayerNorm, now that dh has been read)
+      launch_tln_bwd(dxn, h, mean, rstd, P + y.ln2_w, M, H, dh, st);                                              // (the MLP branch's LayerNorm, now that dh has been read)
       ETD_TRY(launch_tattn_bwd(qkv, att, d->lse + (size_t)l * R * nh, tx, nh, d_row0, d_len, n, max_len, d->Dbuf, d->dqkv, st));
-      hipLaunchKernelGGL(k_trope, ew_grid((long long)M * nh * 16), dim3(256), 0, st, d->dqkv, nh, M, d_pos, d->rope, -1.f);
-      hipLaunchKernelGGL(k_tln_fwd, dim3(M), dim3(64), 0, st, h, M, H, eps, (float*)nullptr, (float*)nullptr, P + y.ln1_w, P + y.ln1_b, tx,
-                         (const float*)nullptr, (const float*)nullptr, (float*)nullptr);
+      launch_trope(d->dqkv, nh, M, d_pos, d->rope, -1.f, st);
+      launch_tln_fwd(h, M, H, eps, nullptr, nullptr, P + y.ln1_w, P + y.ln1_b, tx, nullptr, nullptr, nullptr, st);
       ETD_TRY(launch_tgemm(ETD_TG_TN, 3 * H, H, M, d->dqkv, 3 * H, tx, H, nullptr, G + y.qkv_w, H, true, st));
-      hipLaunchKernelGGL(k_tcolred<0>, dim3((3 * H + 31) / 32), dim3(256), 0, st, d->dqkv, 3 * H, M, 3 * H, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, G + y.qkv_b, (float*)nullptr);
+      launch_tcolred(0, d->dqkv, 3 * H, M, 3 * H, nullptr, nullptr, nullptr, G + y.qkv_b, nullptr, st);
       ETD_TRY(launch_tgemm(ETD_TG_NN, M, H, 3 * H, d->dqkv, 3 * H, P + y.qkv_w, H, nullptr, dxn, H, false, st));
-      hipLaunchKernelGGL(k_tcolred<1>, dim3((H + 31) / 32), dim3(256), 0, st, dxn, H, M, H, h, mean, rstd, G + y.ln1_b, G + y.ln1_w);
-      hipLaunchKernelGGL(k_tln_bwd, dim3(M), dim3(64), 0, st, dxn, h, mean, rstd, P + y.ln1_w, H, dh);
+      launch_tcolred(1, dxn, H, M, H, h, mean, rstd, G + y.ln1_b, G + y.ln1_w, st);
+      launch_tln_bwd(dxn, h, mean, rstd, P + y.ln1_w, M, H, dh, st);
     }
     // ---- embeddings: dh is d loss / d inputs_embeds
     ETD_TRY(launch_tgemm(ETD_TG_TN, H, 4 * E, M, dh, H, d->A4, 4 * E, nullptr, G + d->proj_w, 4 * E, true, st));
-    hipLaunchKernelGGL(k_tcolred<0>, dim3((H + 31) / 32), dim3(256), 0, st, dh, H, M, H, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, G + d->proj_b, (float*)nullptr);
+    launch_tcolred(0, dh, H, M, H, nullptr, nullptr, nullptr, G + d->proj_b, nullptr, st);
     ETD_TRY(launch_tgemm(ETD_TG_NN, M, 4 * E, H, dh, H, P + d->proj_w, 4 * E, nullptr, d->dA4, 4 * E, false, st));
-    if (seg0[1] > 0)
-      hipLaunchKernelGGL(k_tembed_grad, dim3(seg0[1], (H + 63) / 64), dim3(256), 0, st, dh, H, 0, H, d_ord, d_sid, d_sst, d_scn, G + d->word);
-    if (seg0[2] > seg0[1])
-      hipLaunchKernelGGL(k_tembed_grad, dim3(seg0[2] - seg0[1], (H + 63) / 64), dim3(256), 0, st, dh, H, 0, H, d_ord + R, d_sid + seg0[1], d_sst + seg0[1], d_scn + seg0[1], G + d->cemb);
+    launch_tembed_grad(dh, H, 0, H, d_ord, d_sid, d_sst, d_scn, seg0[1], G + d->word, st);
+    launch_tembed_grad(dh, H, 0, H, d_ord + R, d_sid + seg0[1], d_sst + seg0[1], d_scn + seg0[1], seg0[2] - seg0[1], G + d->cemb, st);
     for (int k = 0; k < 4; ++k)
-      if (seg0[3 + k] > seg0[2 + k])
-        hipLaunchKernelGGL(k_tembed_grad, dim3(seg0[3 + k] - seg0[2 + k], (E + 63) / 64), dim3(256), 0, st, d->dA4, 4 * E, k * E, E, d_ord + (2 + k) * R, d_sid + seg0[2 + k],
-                           d_sst + seg0[2 + k], d_scn + seg0[2 + k], G + d->attr[k]);
+      launch_tembed_grad(d->dA4, 4 * E, k * E, E, d_ord + (2 + k) * R, d_sid + seg0[2 + k], d_sst + seg0[2 + k], d_scn + seg0[2 + k], seg0[3 + k] - seg0[2 + k],
+                         G + d->attr[k], st);
     HIP_TRY(hipGetLastError());
   }
   HIP_TRY(hipMemcpyAsync(d->h_row_loss.data(), d->row_loss, sizeof(float) * M, hipMemcpyDeviceToHost, st));
@@ -866,8 +916,7 @@ extern "C" int etd_dtrain_grad_norm(etd_dtrain* d, double* norm, void* stream) {
 extern "C" int etd_dtrain_clip_and_step(etd_dtrain* d, double max_norm, double lr, double beta1, double beta2, double eps, double weight_decay, double* norm_out,
                                         void* stream) {
   if (!d) ETD_FAIL(ETD_EINVAL, "etd_dtrain_clip_and_step: null handle");
-  if (!(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !(weight_decay >= 0.0))
-    ETD_FAIL(ETD_EINVAL, "etd_dtrain_clip_and_step: lr, eps, weight_decay must be >= 0 and the betas in [0, 1)");
+  ETD_TRY(adamw_check("etd_dtrain_clip_and_step", lr, beta1, beta2, eps, weight_decay));
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps("dtrain_optimizer", st);
   double norm = 0.0;
@@ -875,9 +924,7 @@ extern "C" int etd_dtrain_clip_and_step(etd_dtrain* d, double max_norm, double l
   ETD_TRY(grad_norm(d->G, n, d->partial, st, &norm));
   if (norm_out) *norm_out = norm;
   d->step += 1;
-  const StepScalars s = step_scalars(max_norm, norm, lr, beta1, beta2, d->step);
-  hipLaunchKernelGGL(k_tadamw, ew_grid(n), dim3(256), 0, st, d->P, d->G, d->M1, d->M2, n, s.coef, (float)(1.0 - lr * weight_decay), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2),
-                     s.step_size, s.bc2_sqrt, (float)eps);
+  launch_tadamw(d->P, d->G, d->M1, d->M2, n, adamw_args(max_norm, norm, lr, beta1, beta2, eps, weight_decay, d->step), st);
   HIP_TRY(hipGetLastError());
   return ETD_OK;
 }
@@ -942,4 +989,161 @@ extern "C" int etd_debug_dtrain_attn(int n_seq, const int32_t* T_host, int n_hea
   ETD_TRY_OR(fail, launch_tattn_fwd(qkv_dev, n_heads, di, di + n_seq, n_seq, max_len, O_dev, lse_dev, st));
   ETD_TRY_OR(fail, launch_tattn_bwd(qkv_dev, O_dev, lse_dev, dO_dev, n_heads, di, di + n_seq, n_seq, max_len, Dbuf, dqkv_dev, st));
   return fail(ETD_HIP_RC(hipStreamSynchronize(st)));
+}
+
+// ================================================================================================
+// stage taps (include/etude_hip_debug.h): every row and elementwise kernel on a caller's input, through the launcher the engine calls
+// ================================================================================================
+#define TAP_MAX_ROWS (1 << 22)          // etd_dtrain_create's limit of max_rows
+#define TAP_MAX_ELEMS (1LL << 36)       // elementwise taps: the grid of ew_grid stays below 2^31 workgroups
+
+extern "C" int etd_debug_dtrain_ln(const float* x_dev, int M, int H, float eps, float* mean_dev, float* rstd_dev, const float* g1_dev, const float* b1_dev,
+                                   float* y1_dev, const float* g2_dev, const float* b2_dev, float* y2_dev, const float* dy_dev, float* dx_dev, void* stream) {
+  if (!x_dev || !g1_dev || !b1_dev || !y1_dev) ETD_FAIL(ETD_EINVAL, "etd_debug_dtrain_ln: x, the first gain and bias and y1 are required");
+  if (M < 1 || M > TAP_MAX_ROWS || H < 1 || !(eps >= 0.f)) ETD_FAIL(ETD_EINVAL, "etd_debug_dtrain_ln: bad shape M=%d H=%d eps=%g", M, H, (double)eps);
+  if ((mean_dev == nullptr) != (rstd_dev == nullptr)) ETD_FAIL(ETD_EINVAL, "etd_debug_dtrain_ln: mean and rstd go together");
+  if ((y2_dev != nullptr) != (g2_dev != nullptr) || (y2_dev != nullptr) != (b2_dev != nullptr)) ETD_FAIL(ETD_EINVAL, "etd_debug_dtrain_ln: y2, g2 and b2 go together");
+  if ((dy_dev != nullptr) != (dx_dev != nullptr)) ETD_FAIL(ETD_EINVAL, "etd_debug_dtrain_ln: dy and dx go together");
+  if (dy_dev && !mean_dev) ETD_FAIL(ETD_EINVAL, "etd_debug_dtrain_ln: the backward pass reads the saved mean and rstd");
+  hipStream_t st = (hipStream_t)stream;
+  launch_tln_fwd(x_dev, M, H, eps, mean_dev, rstd_dev, g1_dev, b1_dev, y1_dev, g2_dev, b2_dev, y2_dev, st);
+  if (dy_dev) launch_tln_bwd(dy_dev, x_dev, mean_dev, rstd_dev, g1_dev, M, H, dx_dev, st);
+  HIP_TRY(hipGetLastError());
+  return ETD_OK;
+}
+
+extern "C" int etd_debug_dtrain_gelu(const float* x_dev, long long n, float* y_dev, float* dy_dev, void* stream) {
+  if (!x_dev || !y_dev || n < 1 || n > TAP_MAX_ELEMS) ETD_FAIL(ETD_EINVAL, "etd_debug_dtrain_gelu: null buffer or n=%lld outside 1 .. 2^36", n);
+  launch_tgelu(x_dev, y_dev, n, (hipStream_t)stream);
+  if (dy_dev) launch_tgelu_bwd(x_dev, dy_dev, n, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return ETD_OK;
+}
+
+extern "C" int etd_debug_dtrain_add3(const float* m_dev, const float* a_dev, const float* h_dev, long long n, float* out_dev, void* stream) {
+  if (!m_dev || !a_dev || !h_dev || !out_dev || n < 1 || n > TAP_MAX_ELEMS) ETD_FAIL(ETD_EINVAL, "etd_debug_dtrain_add3: null buffer or n=%lld outside 1 .. 2^36", n);
+  launch_tadd3(m_dev, a_dev, h_dev, out_dev, n, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return ETD_OK;
+}
+
+extern "C" int etd_debug_dtrain_rope(etd_dtrain* d, float* qkv_dev, int n_heads, int M, const int32_t* pos_dev, int sign, void* stream) {
+  if (!d || !qkv_dev || !pos_dev) ETD_FAIL(ETD_EINVAL, "etd_debug_dtrain_rope: null argument");
+  if (n_heads < 1 || n_heads > 65535 || M < 1 || M > TAP_MAX_ROWS || (sign != 1 && sign != -1))
+    ETD_FAIL(ETD_EINVAL, "etd_debug_dtrain_rope: bad shape heads=%d M=%d sign=%d", n_heads, M, sign);
+  hipStream_t st = (hipStream_t)stream;
+  std::vector<int32_t> pos((size_t)M);                 // read back: a position past the handle's table must not reach the kernel
+  HIP_TRY(hipMemcpyAsync(pos.data(), pos_dev, sizeof(int32_t) * (size_t)M, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  for (int r = 0; r < M; ++r)
+    if (pos[r] < 0 || pos[r] >= d->cfg.max_position_embeddings)
+      ETD_FAIL(ETD_EINVAL, "etd_debug_dtrain_rope: position %d at row %d outside [0, %d)", pos[r], r, d->cfg.max_position_embeddings);
+  launch_trope(qkv_dev, n_heads, M, pos_dev, d->rope, (float)sign, st);
+  HIP_TRY(hipGetLastError());
+  return ETD_OK;
+}
+
+// `n` host ints on the device for the length of one tap
+static int tap_upload(DevPool& pl, const std::vector<int>& h, int** out, hipStream_t st) {
+  ETD_TRY(pl.alloc(out, h.size()));
+  HIP_TRY(hipMemcpyAsync(*out, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice, st));
+  return ETD_OK;
+}
+
+extern "C" int etd_debug_dtrain_embed(int M, int H, int E, int V, int NC, int NB, const int32_t* ids_host, const int32_t* cls_host, const int32_t* attrs4_host,
+                                      const float* word_dev, const float* cemb_dev, const float* attr0_dev, const float* attr1_dev, const float* attr2_dev,
+                                      const float* attr3_dev, const float* h_in_dev, float* A4_dev, float* h_dev, void* stream) {
+  if (!ids_host || !cls_host || !attrs4_host || !word_dev || !cemb_dev || !attr0_dev || !attr1_dev || !attr2_dev || !attr3_dev || !h_in_dev || !A4_dev || !h_dev)
+    ETD_FAIL(ETD_EINVAL, "etd_debug_dtrain_embed: null argument");
+  if (M < 1 || M > TAP_MAX_ROWS || H < 1 || E < 1 || V < 1 || NC < 1 || NB < 1 || (long long)M * 4 * E > TAP_MAX_ELEMS || (long long)M * H > TAP_MAX_ELEMS)
+    ETD_FAIL(ETD_EINVAL, "etd_debug_dtrain_embed: bad shape M=%d H=%d E=%d V=%d NC=%d NB=%d", M, H, E, V, NC, NB);
+  std::vector<int> h(6 * (size_t)M);                    // ids | cls | attrs4 [4][M]
+  for (int r = 0; r < M; ++r) {
+    if (ids_host[r] < 0 || ids_host[r] >= V || cls_host[r] < 0 || cls_host[r] >= NC) ETD_FAIL(ETD_EINVAL, "etd_debug_dtrain_embed: token or class id out of range at row %d", r);
+    h[r] = ids_host[r]; h[(size_t)M + r] = cls_host[r];
+    for (int k = 0; k < 4; ++k) {
+      const int a = attrs4_host[(size_t)k * M + r];
+      if (a < 0 || a >= NB) ETD_FAIL(ETD_EINVAL, "etd_debug_dtrain_embed: attribute bin %d out of range [0, %d) at row %d", a, NB, r);
+      h[(2 + (size_t)k) * M + r] = a;
+    }
+  }
+  hipStream_t st = (hipStream_t)stream;
+  DevPool pl;
+  int* di = nullptr;
+  auto fail = [&](int rc) { (void)hipStreamSynchronize(st); pl.free_all(); return rc; };
+  ETD_TRY_OR(fail, tap_upload(pl, h, &di, st));
+  launch_tembed_gather(di + 2 * (size_t)M, M, E, attr0_dev, attr1_dev, attr2_dev, attr3_dev, A4_dev, st);
+  if (h_dev != h_in_dev) ETD_TRY_OR(fail, ETD_HIP_RC(hipMemcpyAsync(h_dev, h_in_dev, sizeof(float) * (size_t)M * H, hipMemcpyDeviceToDevice, st)));
+  launch_tembed_sum(di, di + M, word_dev, cemb_dev, M, H, h_dev, st);
+  ETD_TRY_OR(fail, ETD_HIP_RC(hipGetLastError()));
+  return fail(ETD_HIP_RC(hipStreamSynchronize(st)));
+}
+
+extern "C" int etd_debug_dtrain_ce(float* logits_dev, int M, int V, const int32_t* labels_host, float scale, float* row_loss_dev, void* stream) {
+  if (!logits_dev || !labels_host || !row_loss_dev) ETD_FAIL(ETD_EINVAL, "etd_debug_dtrain_ce: null argument");
+  if (M < 1 || M > TAP_MAX_ROWS || V < 1) ETD_FAIL(ETD_EINVAL, "etd_debug_dtrain_ce: bad shape M=%d V=%d", M, V);
+  std::vector<int> h((size_t)M);
+  for (int r = 0; r < M; ++r) {
+    if (labels_host[r] != ETD_IGNORE_LABEL && (labels_host[r] < 0 || labels_host[r] >= V)) ETD_FAIL(ETD_EINVAL, "etd_debug_dtrain_ce: label %d out of range at row %d", labels_host[r], r);
+    h[r] = labels_host[r];
+  }
+  hipStream_t st = (hipStream_t)stream;
+  DevPool pl;
+  int* di = nullptr;
+  auto fail = [&](int rc) { (void)hipStreamSynchronize(st); pl.free_all(); return rc; };
+  ETD_TRY_OR(fail, tap_upload(pl, h, &di, st));
+  launch_tce(logits_dev, M, V, di, scale, row_loss_dev, st);
+  ETD_TRY_OR(fail, ETD_HIP_RC(hipGetLastError()));
+  return fail(ETD_HIP_RC(hipStreamSynchronize(st)));
+}
+
+extern "C" int etd_debug_dtrain_colred(int mode, const float* dy_dev, int ld, int M, int N, const float* x_dev, const float* mean_dev, const float* rstd_dev,
+                                       float* g0_dev, float* g1_dev, void* stream) {
+  if (mode != 0 && mode != 1) ETD_FAIL(ETD_EINVAL, "etd_debug_dtrain_colred: unknown mode %d", mode);
+  if (!dy_dev || !g0_dev || (mode == 1 && (!x_dev || !mean_dev || !rstd_dev || !g1_dev))) ETD_FAIL(ETD_EINVAL, "etd_debug_dtrain_colred: null argument");
+  if (M < 1 || M > TAP_MAX_ROWS || N < 1 || ld < N) ETD_FAIL(ETD_EINVAL, "etd_debug_dtrain_colred: bad shape M=%d N=%d ld=%d", M, N, ld);
+  launch_tcolred(mode, dy_dev, ld, M, N, x_dev, mean_dev, rstd_dev, g0_dev, g1_dev, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return ETD_OK;
+}
+
+extern "C" int etd_debug_dtrain_embed_grad(const float* src_dev, int ld, int col0, int width, int M, const int32_t* idx_host, int n_rows, int pad_row,
+                                           float* grad_dev, void* stream) {
+  if (!src_dev || !idx_host || !grad_dev) ETD_FAIL(ETD_EINVAL, "etd_debug_dtrain_embed_grad: null argument");
+  if (M < 1 || M > TAP_MAX_ROWS || n_rows < 1 || n_rows > TAP_MAX_ROWS || width < 1 || width > (1 << 20) || col0 < 0 || (long long)col0 + width > ld || pad_row < 0 || pad_row >= n_rows)
+    ETD_FAIL(ETD_EINVAL, "etd_debug_dtrain_embed_grad: bad shape M=%d rows=%d width=%d col0=%d ld=%d pad=%d", M, n_rows, width, col0, ld, pad_row);
+  for (int r = 0; r < M; ++r)
+    if (idx_host[r] < 0 || idx_host[r] >= n_rows) ETD_FAIL(ETD_EINVAL, "etd_debug_dtrain_embed_grad: index %d out of range [0, %d) at row %d", idx_host[r], n_rows, r);
+  std::vector<int> h((size_t)M + 3 * (size_t)n_rows, 0);      // order | segment id, start, count
+  int* h_seg = h.data() + M;
+  const int n_seg = group_rows(idx_host, M, n_rows, pad_row, h.data(), h_seg, h_seg + n_rows, h_seg + 2 * (size_t)n_rows);
+  hipStream_t st = (hipStream_t)stream;
+  DevPool pl;
+  int* di = nullptr;
+  auto fail = [&](int rc) { (void)hipStreamSynchronize(st); pl.free_all(); return rc; };
+  ETD_TRY_OR(fail, tap_upload(pl, h, &di, st));
+  const int* seg = di + M;
+  launch_tembed_grad(src_dev, ld, col0, width, di, seg, seg + n_rows, seg + 2 * (size_t)n_rows, n_seg, grad_dev, st);
+  ETD_TRY_OR(fail, ETD_HIP_RC(hipGetLastError()));
+  return fail(ETD_HIP_RC(hipStreamSynchronize(st)));
+}
+
+extern "C" int etd_debug_dtrain_adamw(float* p_dev, float* g_dev, float* m_dev, float* v_dev, long long n, double max_norm, double norm, double lr, double beta1,
+                                      double beta2, double eps, double weight_decay, long long step, void* stream) {
+  if (!p_dev || !g_dev || !m_dev || !v_dev || n < 1 || n > TAP_MAX_ELEMS) ETD_FAIL(ETD_EINVAL, "etd_debug_dtrain_adamw: null buffer or n=%lld outside 1 .. 2^36", n);
+  if (step < 1 || !(norm >= 0.0)) ETD_FAIL(ETD_EINVAL, "etd_debug_dtrain_adamw: step %lld (1-based) or norm %g", step, norm);
+  ETD_TRY(adamw_check("etd_debug_dtrain_adamw", lr, beta1, beta2, eps, weight_decay));
+  launch_tadamw(p_dev, g_dev, m_dev, v_dev, n, adamw_args(max_norm, norm, lr, beta1, beta2, eps, weight_decay, step), (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return ETD_OK;
+}
+
+extern "C" int etd_debug_dtrain_sumsq(const float* g_dev, long long n, double* norm, void* stream) {
+  if (!g_dev || !norm || n < 1 || n > TAP_MAX_ELEMS) ETD_FAIL(ETD_EINVAL, "etd_debug_dtrain_sumsq: null argument or n=%lld outside 1 .. 2^36", n);
+  hipStream_t st = (hipStream_t)stream;
+  DevPool pl;
+  double* partial = nullptr;
+  auto fail = [&](int rc) { (void)hipStreamSynchronize(st); pl.free_all(); return rc; };
+  ETD_TRY_OR(fail, pl.alloc(&partial, (size_t)TN_BLOCKS));
+  return fail(grad_norm(g_dev, n, partial, st, norm));
 }

@@ -241,6 +241,40 @@ int etd_debug_dtrain_gemm(int form, int M, int N, int K, const float* A_dev, int
  * -> O_dev [M][n_heads * 64], lse_dev [M][n_heads], dqkv_dev in qkv's layout (scale 1 / 8 on the scores).  Synchronous. */
 int etd_debug_dtrain_attn(int n_seq, const int32_t* T_host, int n_heads, const float* qkv_dev, const float* dO_dev, float* O_dev, float* lse_dev, float* dqkv_dev,
                           void* stream);
+/* Stage taps of the training engine: every row and elementwise kernel on a caller's input, through the launcher (kernel, grid, block) the engine itself calls.
+ * DEVICE fp32 buffers unless named _host.  A malformed argument is ETD_EINVAL before anything is launched.  Asynchronous unless said.
+ *   ln          x [M][H] (any H >= 1) -> y1 = xhat g1 + b1; with g2, b2, y2 (all three or none) also y2; with mean, rstd [M] (both or neither) the statistics.
+ *               With dy [M][H]: dx [M][H] += the input gradient of y1 (needs mean and rstd; dx is the caller's to initialise).
+ *   gelu        x [n] -> y = gelu(x) (erf form); with dy [n]: dy *= gelu'(x) in place
+ *   add3        out [n] = (m + a) + h
+ *   rope        qkv [M][n_heads][q | k | v][64] in place: dims 0 .. 15 of q and k rotated by the handle's table at pos [M] (DEVICE int32, read back and checked
+ *               against max_position_embeddings: synchronous up to the launch); sign +1 forward, -1 the inverse rotation
+ *   embed       ids, cls [M] and attrs4 [4][M] (HOST int32, checked against V, NC, NB) -> A4 [M][4 E] = the four attribute rows side by side and
+ *               h [M][H] = (word[ids] + cemb[cls]) + h_in (h may be h_in).  Synchronous.
+ *   ce          logits [M][V] in place -> (softmax - onehot) * scale, zero rows where labels_host [M] is -100; row_loss [M] = lse - logit[label] (0 there).  Synchronous.
+ *   colred      mode 0: g0 [N] += sum_r dy[r][c] over dy [M][N] with row stride ld >= N.  mode 1: also g1 [N] += sum_r dy[r][c] xhat[r][c], xhat from x [M][N]
+ *               (row stride N), mean, rstd [M].  Any N >= 1.
+ *   embed_grad  grad [n_rows][width] += per table row i != pad_row the sum of src[r][col0 .. col0 + width) (src [M][ld]) over the rows r with idx_host[r] == i, in
+ *               ascending r: the engine's own grouping and launch; a batch with no such row launches nothing.  Synchronous.
+ *   adamw       clip (g *= coef) and one AdamW step of p, g, m, v [n] at optimizer step `step` (1-based), the scalars formed from the doubles exactly as
+ *               etd_dtrain_clip_and_step forms them; `norm` is the gradient norm the clipping coefficient is taken from
+ *   sumsq       *norm = sqrt(sum g[i]^2) of g [n], the fp64 reduction both trainers' clip_and_step use.  Synchronous. */
+int etd_debug_dtrain_ln(const float* x_dev, int M, int H, float eps, float* mean_dev, float* rstd_dev, const float* g1_dev, const float* b1_dev, float* y1_dev,
+                        const float* g2_dev, const float* b2_dev, float* y2_dev, const float* dy_dev, float* dx_dev, void* stream);
+int etd_debug_dtrain_gelu(const float* x_dev, long long n, float* y_dev, float* dy_dev, void* stream);
+int etd_debug_dtrain_add3(const float* m_dev, const float* a_dev, const float* h_dev, long long n, float* out_dev, void* stream);
+int etd_debug_dtrain_rope(etd_dtrain*, float* qkv_dev, int n_heads, int M, const int32_t* pos_dev, int sign, void* stream);
+int etd_debug_dtrain_embed(int M, int H, int E, int V, int NC, int NB, const int32_t* ids_host, const int32_t* cls_host, const int32_t* attrs4_host,
+                           const float* word_dev, const float* cemb_dev, const float* attr0_dev, const float* attr1_dev, const float* attr2_dev,
+                           const float* attr3_dev, const float* h_in_dev, float* A4_dev, float* h_dev, void* stream);
+int etd_debug_dtrain_ce(float* logits_dev, int M, int V, const int32_t* labels_host, float scale, float* row_loss_dev, void* stream);
+int etd_debug_dtrain_colred(int mode, const float* dy_dev, int ld, int M, int N, const float* x_dev, const float* mean_dev, const float* rstd_dev, float* g0_dev,
+                            float* g1_dev, void* stream);
+int etd_debug_dtrain_embed_grad(const float* src_dev, int ld, int col0, int width, int M, const int32_t* idx_host, int n_rows, int pad_row, float* grad_dev,
+                                void* stream);
+int etd_debug_dtrain_adamw(float* p_dev, float* g_dev, float* m_dev, float* v_dev, long long n, double max_norm, double norm, double lr, double beta1, double beta2,
+                           double eps, double weight_decay, long long step, void* stream);
+int etd_debug_dtrain_sumsq(const float* g_dev, long long n, double* norm, void* stream);
 
 /* test hook, HOST ONLY: the plan etd_render_run makes of a call, without a device: first_end_host int64 [notes][2] = per note the first sample it sounds on and the
  * first it no longer does; ranges_host int32 [blocks][2] = per block of 1 024 samples (cover after cover) the candidate notes [lo, hi) of its cover.  Either may be

@@ -75,3 +75,37 @@ def split_generated(ids, bos):
     if cur is not None:
         bars.append(cur)
     return bars
+
+
+# ---- device buffers between guard floats (the stage files' rule: nothing is written outside an output, every float inside is written)
+GUARD = 64
+NAN_BITS = 0x7FC0DEAD
+
+
+class Guarded:
+    """n floats on the device between two guards.  Guards and inside hold NAN_BITS until a kernel writes them; ``fill`` (a scalar) or ``data`` (n fp32 values, for a
+    buffer a kernel updates in place) initialises the inside."""
+
+    def __init__(self, n, fill=None, data=None):
+        import ctypes as C
+        self.n = int(n)
+        self.buf = torch.full((self.n + 2 * GUARD,), NAN_BITS, dtype=torch.int32, device="cuda")
+        if fill is not None:
+            self.buf[GUARD:GUARD + self.n] = fill
+        if data is not None:
+            d = torch.as_tensor(data).detach().to(torch.float32).contiguous().reshape(-1)
+            assert d.numel() == self.n, (d.numel(), self.n)
+            self.buf[GUARD:GUARD + self.n] = d.view(torch.int32).cuda()
+        self.ptr = C.c_void_p(self.buf.data_ptr() + 4 * GUARD)
+
+    def floats(self):
+        """the inside, on the host, as fp32"""
+        torch.cuda.synchronize()
+        return self.buf[GUARD:GUARD + self.n].cpu().view(torch.float32)
+
+    def check(self, what):
+        torch.cuda.synchronize()
+        b = self.buf.cpu().numpy()
+        assert (b[:GUARD] == NAN_BITS).all(), f"{what}: written below the buffer"
+        assert (b[GUARD + self.n:] == NAN_BITS).all(), f"{what}: written beyond the buffer"
+        assert not (b[GUARD:GUARD + self.n] == NAN_BITS).any(), f"{what}: a float inside was never written"

@@ -452,26 +452,7 @@ def test_non_finite_or_negative_input_is_refused():
     tr.close()
 
 
-GUARD = 64
-NAN_BITS = 0x7FC0DEAD
-
-
-class _Guarded:
-    """n floats on the device between two guards, all holding NAN_BITS until a kernel writes them (tests/test_gpu_frontend_stages.py)"""
-
-    def __init__(self, n, fill=None):
-        self.n = int(n)
-        self.buf = torch.full((self.n + 2 * GUARD,), NAN_BITS, dtype=torch.int32, device="cuda")
-        if fill is not None:
-            self.buf[GUARD:GUARD + self.n] = fill
-        self.ptr = C.c_void_p(self.buf.data_ptr() + 4 * GUARD)
-
-    def check(self, what):
-        torch.cuda.synchronize()
-        b = self.buf.cpu().numpy()
-        assert (b[:GUARD] == NAN_BITS).all(), f"{what}: written below the buffer"
-        assert (b[GUARD + self.n:] == NAN_BITS).all(), f"{what}: written beyond the buffer"
-        assert not (b[GUARD:GUARD + self.n] == NAN_BITS).any(), f"{what}: a float inside was never written"
+from _util import Guarded as _Guarded  # noqa: E402  (n floats between guard floats, all holding a NaN pattern until a kernel writes them)
 
 
 def test_guard_floats_around_every_tap_output_are_untouched():

@@ -46,7 +46,7 @@ def report(name, rows):
 
 def trainer(cfg, state, **kw):
     from etude_amd.train import DecoderTrainer
-    return DecoderTrainer(cfg, state, max_rows=1100, clip_grad_norm=kw.pop("clip_grad_norm", 1.0), grad_accum_steps=kw.pop("grad_accum_steps", 1), **OPT, **kw)
+    return DecoderTrainer(cfg, state, max_rows=kw.pop("max_rows", 1100), clip_grad_norm=kw.pop("clip_grad_norm", 1.0), grad_accum_steps=kw.pop("grad_accum_steps", 1), **OPT, **kw)
 
 
 @pytest.fixture(scope="module")
@@ -100,6 +100,21 @@ def test_gradients_of_the_ragged_batch_second_config():
     tr = trainer(cfg, state)
     loss, _, _ = tr.loss_and_backward(batch)
     check_grads("grad_err_second", cfg, tr, tr.grads(), g64, g32, loss, l64, l32)
+    tr.close()
+
+
+def test_gradients_of_the_ragged_batch_third_config():
+    """the edges of the stage tests (tests/test_gpu_train_stages.py) composed: an attribute width that is no multiple of 64 (4 E = 96, table k at column 24 k),
+    other table sizes, and positions past 255 through RoPE and attention together, up to the last row of the default decoder's rotary table"""
+    cfg = tn.tiny_config(attribute_emb_dim=24, vocab_size=193, num_classes=4, num_attribute_bins=5, max_position_embeddings=1024)
+    state = tn.seeded_state(cfg, 7)
+    batch = tn.ragged_batch(cfg, (1, 300, 1024), seed=8, ignore_all=(1,))
+    l64, g64 = tn.loss_and_grads(state, cfg, batch, torch.float64)
+    l32, g32 = tn.loss_and_grads(state, cfg, batch, torch.float32)
+    tr = trainer(cfg, state, max_rows=1 + 300 + 1024)
+    loss, n, _ = tr.loss_and_backward(batch)
+    assert n == int((batch["labels"] != -100).sum())
+    check_grads("grad_err_third", cfg, tr, tr.grads(), g64, g32, loss, l64, l32)
     tr.close()
 
 

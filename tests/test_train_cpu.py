@@ -130,3 +130,56 @@ def test_trainer_refuses_bad_batches_and_shapes():
     assert _lib.lib().etd_dtrain_workspace_bytes(C.byref(c), 64) > 0
     assert _lib.lib().etd_dtrain_create(C.byref(c), names, ptrs, numels, n, 0, 0, 0, 64, C.byref(h)) == -22
     assert b"missing weight" in _lib.lib().etd_last_error()
+
+
+def test_stage_references_chained_reproduce_the_restatement():
+    """tests/train_stage_np.py states each kernel of the trainer on its own (the references of tests/test_gpu_train_stages.py); chained in fp64 in the engine's
+    order they are the model: the loss and every gradient of tn.loss_and_grads to 1e-12 relative."""
+    import train_stage_np as ts
+    cfg = tn.tiny_config()
+    state = tn.seeded_state(cfg, 3)
+    batch = tn.ragged_batch(cfg, (1, 2, 63, 65, 40), seed=5, ignore_all=(3,))
+    loss, grads = tn.loss_and_grads(state, cfg, batch, torch.float64)
+    loss_c, grads_c = ts.chain(state, cfg, batch, torch.float64)
+    assert abs(loss_c - loss) <= 1e-12 * abs(loss), (loss_c, loss)
+    assert list(grads_c) == list(grads)
+    for k in grads:
+        assert close(grads_c[k], grads[k], 1e-12), (k, float(np.abs(grads_c[k] - grads[k]).max()), float(np.abs(grads[k]).max()))
+    assert not grads_c[tn.FROZEN].any()
+
+
+def test_stage_taps_refuse_malformed_arguments_before_any_launch():
+    """ETD_EINVAL from every etd_debug_dtrain_* tap without a GPU: the checks run before the device is touched (`dev` stands for a device pointer that is never read)"""
+    lib, dev = _lib.lib(), C.c_void_p(4096)
+    i32 = lambda *v: np.array(v, np.int32)      # noqa: E731
+    ids, ptr = i32(0, 1, 2), lambda a: a.ctypes.data      # noqa: E731
+    calls = {
+        "ln: no input": lib.etd_debug_dtrain_ln(None, 2, 8, 1e-5, dev, dev, dev, dev, dev, None, None, None, None, None, None),
+        "ln: H = 0": lib.etd_debug_dtrain_ln(dev, 2, 0, 1e-5, dev, dev, dev, dev, dev, None, None, None, None, None, None),
+        "ln: mean without rstd": lib.etd_debug_dtrain_ln(dev, 2, 8, 1e-5, dev, None, dev, dev, dev, None, None, None, None, None, None),
+        "ln: y2 without its gain": lib.etd_debug_dtrain_ln(dev, 2, 8, 1e-5, dev, dev, dev, dev, dev, None, None, dev, None, None, None),
+        "ln: dy without dx": lib.etd_debug_dtrain_ln(dev, 2, 8, 1e-5, dev, dev, dev, dev, dev, None, None, None, dev, None, None),
+        "ln: backward without statistics": lib.etd_debug_dtrain_ln(dev, 2, 8, 1e-5, None, None, dev, dev, dev, None, None, None, dev, dev, None),
+        "gelu: n = 0": lib.etd_debug_dtrain_gelu(dev, 0, dev, None, None),
+        "gelu: no output": lib.etd_debug_dtrain_gelu(dev, 4, None, dev, None),
+        "add3: n = 0": lib.etd_debug_dtrain_add3(dev, dev, dev, 0, dev, None),
+        "rope: no handle": lib.etd_debug_dtrain_rope(None, dev, 1, 2, dev, 1, None),
+        "embed: M = 0": lib.etd_debug_dtrain_embed(0, 256, 8, 5, 3, 3, ptr(ids), ptr(ids), ptr(ids), *([dev] * 9), None),
+        "embed: token id past the table": lib.etd_debug_dtrain_embed(3, 256, 8, 2, 3, 3, ptr(ids), ptr(ids), ptr(i32(*[0] * 12)), *([dev] * 9), None),
+        "embed: no table": lib.etd_debug_dtrain_embed(3, 256, 8, 5, 3, 3, ptr(ids), ptr(ids), ptr(i32(*[0] * 12)), dev, dev, dev, None, dev, dev, dev, dev, dev, None),
+        "ce: label = V": lib.etd_debug_dtrain_ce(dev, 3, 2, ptr(ids), 1.0, dev, None),
+        "ce: V = 0": lib.etd_debug_dtrain_ce(dev, 3, 0, ptr(ids), 1.0, dev, None),
+        "colred: mode 2": lib.etd_debug_dtrain_colred(2, dev, 8, 4, 8, dev, dev, dev, dev, dev, None),
+        "colred: stride below the row": lib.etd_debug_dtrain_colred(0, dev, 7, 4, 8, None, None, None, dev, None, None),
+        "colred: mode 1 without x": lib.etd_debug_dtrain_colred(1, dev, 8, 4, 8, None, dev, dev, dev, dev, None),
+        "embed_grad: index past the table": lib.etd_debug_dtrain_embed_grad(dev, 8, 0, 8, 3, ptr(ids), 2, 0, dev, None),
+        "embed_grad: columns past the row": lib.etd_debug_dtrain_embed_grad(dev, 8, 4, 8, 3, ptr(ids), 3, 0, dev, None),
+        "embed_grad: padding row outside": lib.etd_debug_dtrain_embed_grad(dev, 8, 0, 8, 3, ptr(ids), 3, 3, dev, None),
+        "adamw: step 0": lib.etd_debug_dtrain_adamw(dev, dev, dev, dev, 4, 1.0, 1.0, 1e-3, 0.9, 0.98, 1e-8, 0.01, 0, None),
+        "adamw: beta1 = 1": lib.etd_debug_dtrain_adamw(dev, dev, dev, dev, 4, 1.0, 1.0, 1e-3, 1.0, 0.98, 1e-8, 0.01, 1, None),
+        "adamw: n = 0": lib.etd_debug_dtrain_adamw(dev, dev, dev, dev, 0, 1.0, 1.0, 1e-3, 0.9, 0.98, 1e-8, 0.01, 1, None),
+        "sumsq: n = 0": lib.etd_debug_dtrain_sumsq(dev, 0, C.byref(C.c_double()), None),
+        "sumsq: no result": lib.etd_debug_dtrain_sumsq(dev, 4, None, None),
+    }
+    assert {k: v for k, v in calls.items() if v != -22} == {}
+    assert b"etd_debug_dtrain_sumsq" in lib.etd_last_error()
