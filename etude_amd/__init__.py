@@ -22,6 +22,8 @@ Drop-in surfaces (same names/signatures as the reference):
     etude_amd.RGCCalculator / IPECalculator / RhythmMetrics  <- etude.evaluation.metrics.rgc / ipe (a ragged batch of note lists; csrc/rhythm.hip)
     etude_amd.EtudeDataset / BarAttributes / attribute_adherence  <- etude.data.dataset.EtudeDataset (bar attributes, bin edges, training samples; csrc/attributes.hip)
     etude_amd.NoteRenderer / PianoVoice / align_notes_many  (no counterpart: the reference leaves rendering a cover's .mid to an external synthesiser; csrc/render.hip)
+    etude_amd.AudioLoader / read_wav_raw / resample_filter  <- librosa.load(path, sr=22050) and torchaudio.load in front of every chain (WAV bytes -> an engine's rate and
+                                    layout: decode, mono mean and a windowed-sinc resampler of this project's own, parity unpinned; csrc/resample.hip)
     etude_amd.BeatAnalyzer          <- etude.data.beat_analyzer.BeatAnalyzer (beat_pred.json -> tempo.json; host Python)
 All arithmetic runs in libetude_hip.so (hand-written HIP, see csrc/); importing the heavy
 modules is lazy so that `import etude_amd` works on a box without a GPU.
@@ -44,7 +46,8 @@ __all__ = ["AMTAPC_Extractor", "EtudeDecoder", "EtudeDecoderConfig", "load_etude
            "DecoderTrainer", "cosine_schedule_with_warmup", "init_decoder_state", "NoteRenderer", "PianoVoice", "default_note_renderer", "align_notes_many",
            "read_midi_notes", "save_wav", "StemSeparator", "SeparatorConfig", "init_separator_state", "load_separator_state", "structuralize_audio_many", "SeparatorTrainer", "training_segments",
            "SegmentSampler", "fit_separator", "validate_separator", "save_separator_checkpoint", "load_separator_checkpoint",
-           "BSSEval", "BSSEvalConfig", "evaluate_separator"]
+           "BSSEval", "BSSEvalConfig", "evaluate_separator",
+           "AudioLoader", "resample_filter", "resampled_len", "read_wav_raw", "align_files_many", "structuralize_files_many"]
 
 
 def __getattr__(name):
@@ -84,7 +87,7 @@ def __getattr__(name):
     if name in ("BarAttributes", "EtudeDataset", "split_into_bars", "calculate_bin_edges", "save_bin_edges", "load_bin_edges", "attribute_adherence"):
         from . import attributes
         return getattr(attributes, name)
-    if name in ("AudioAligner", "align_features", "align_features_many", "align_and_filter_many", "align_audio_many", "align_and_filter_audio_many", "align_notes_many"):
+    if name in ("AudioAligner", "align_features", "align_features_many", "align_and_filter_many", "align_audio_many", "align_and_filter_audio_many", "align_notes_many", "align_files_many"):
         from . import aligner
         return getattr(aligner, name)
     if name in ("NoteRenderer", "PianoVoice", "default_note_renderer"):
@@ -106,6 +109,9 @@ def __getattr__(name):
         from . import separator_data
         return getattr(separator_data, {"fit_separator": "fit", "validate_separator": "validate", "save_separator_checkpoint": "save_checkpoint",
                                         "load_separator_checkpoint": "load_checkpoint"}[name])
+    if name in ("AudioLoader", "resample_filter", "resampled_len", "read_wav_raw"):
+        from . import audio
+        return getattr(audio, name)
     if name in ("BSSEval", "BSSEvalConfig"):
         from . import bss
         return getattr(bss, name)
@@ -115,7 +121,7 @@ def __getattr__(name):
     if name in ("StemSeparator", "SeparatorConfig", "init_separator_state", "load_separator_state"):
         from . import separator
         return getattr(separator, name)
-    if name in ("BeatAnalyzer", "structuralize_many", "structuralize_stems_many", "structuralize_audio_many"):
+    if name in ("BeatAnalyzer", "structuralize_many", "structuralize_stems_many", "structuralize_audio_many", "structuralize_files_many"):
         from . import beat_analyzer
         return getattr(beat_analyzer, name)
     if name in ("DecoderTrainer", "cosine_schedule_with_warmup", "init_decoder_state"):

@@ -87,6 +87,10 @@ class TuningCfg(_SizedCfg):
     _fields_ = [("struct_bytes", C.c_int)] + [(n, C.c_int) for n in ("sample_rate", "n_fft", "hop")]
 
 
+class ResampleCfg(_SizedCfg):
+    _fields_ = [("struct_bytes", C.c_int)] + [(n, C.c_int) for n in ("sr_in", "sr_out", "quality", "up", "down", "half", "reserved")]
+
+
 class RhythmCfg(_SizedCfg):
     _fields_ = ([("struct_bytes", C.c_int)] + [(n, C.c_int) for n in ("top_k", "precision_digits", "n_gram", "n_clusters", "n_random")]
                 + [("min_ioi", C.c_double), ("max_ioi", C.c_double), ("random_host", C.POINTER(C.c_double))])
@@ -322,6 +326,12 @@ SIGNATURES = {
     "etd_tuning_run": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, c_i64_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
     "etd_tuning_debug_layout": (C.c_int, [C.c_void_p, C.c_int, c_i64_p, C.c_int, c_i64_p, C.c_int]),
     "etd_tuning_debug_power": (C.c_int, [C.c_void_p, C.c_int, c_i32_p, C.c_int, C.c_void_p]),
+    "etd_resample_create": (C.c_int, [C.POINTER(ResampleCfg), C.c_void_p, C.POINTER(C.c_void_p)]),
+    "etd_resample_destroy": (None, [C.c_void_p]),
+    "etd_resample_out_len": (C.c_longlong, [C.c_void_p, C.c_longlong]),
+    "etd_resample_workspace_bytes": (C.c_longlong, [C.c_void_p, C.c_int, c_i64_p, c_i32_p, c_i32_p]),
+    "etd_resample_run": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, c_i64_p, c_i32_p, c_i32_p, c_i32_p, c_i64_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_longlong, C.c_void_p]),
+    "etd_resample_debug_layout": (C.c_int, [C.c_void_p, C.c_int, c_i64_p, c_i32_p, c_i32_p, c_i64_p, C.c_longlong, C.POINTER(C.c_longlong)]),
     "etd_rhythm_limits": (C.c_int, [c_int_p, c_int_p, c_int_p, c_int_p]),
     "etd_rhythm_create": (C.c_int, [C.POINTER(RhythmCfg), C.POINTER(C.c_void_p)]),
     "etd_rhythm_destroy": (None, [C.c_void_p]),

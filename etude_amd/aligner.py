@@ -207,6 +207,22 @@ def align_audio_many(pairs_of_wavs: Sequence[Tuple], tuning_offsets: Union[None,
     return align_features_many([(feats[2 * i], feats[2 * i + 1]) for i in range(len(pairs_of_wavs))], device)
 
 
+def align_files_many(pairs_of_paths: Sequence[Tuple], loader=None, tuning: Union[None, str, Sequence[Tuple[float, float]]] = "estimate", device="cuda",
+                     features=None) -> List[Dict]:
+    """From files: pairs of (cover WAV, origin WAV) of any rate and channel count -> the result dicts of ``align_audio_many``.  Every file is loaded on the device as
+    mono 22 050 Hz (``etude_amd.audio``; one launch per source rate); loader: an ``AudioLoader`` (default: one per device, made once); tuning: the
+    ``tuning_offsets`` of ``align_audio_many``, by default estimated as the reference does."""
+    from .alignfeat import FS
+    if loader is None:
+        from .audio import default_audio_loader
+        loader = default_audio_loader(device)
+    paths = [p for pair in pairs_of_paths for p in pair]
+    if len(paths) != 2 * len(pairs_of_paths):
+        raise ValueError("align_files_many: every pair is (cover path, origin path)")
+    wavs = loader.load_many(paths, FS, mono=True)
+    return align_audio_many([(wavs[2 * i], wavs[2 * i + 1]) for i in range(len(pairs_of_paths))], tuning, device, features)
+
+
 def align_notes_many(pairs: Sequence[Tuple], tuning_offsets: Optional[Sequence[Tuple[float, float]]] = None, device="cuda", renderer=None, features=None) -> List[Dict]:
     """From notes: pairs of (cover notes, origin) -> the result dicts of ``align_features_many``.  Cover notes: whatever ``NoteRenderer.render_many`` takes (a
     NOTE_DTYPE array, a list of note dicts, a ``.json`` / ``.mid`` path); origin: mono samples at 22 050 Hz, or its features (quantised chroma, DLNCO) computed

@@ -4,7 +4,7 @@ Modelled on synctoolbox's published pipeline (audio_to_pitch_features, pitch_to_
 pitch_onset_features_to_DLNCO): three rate tiers, 88 zero-phase elliptic band-passes (the hot path: csrc/alignfeat.hip splits the recurrence's time axis
 exactly into chunks), pitch energy, chroma, onset novelty, peaks, DLNCO.  DESIGN.md 4f is the contract; tests/alignfeat_np.py restates it in fp64 numpy.
 synctoolbox is not a dependency and parity with it is unpinned; ``tuning_offsets="estimate"`` takes each song's offset from ``etude_amd.tuning`` (DESIGN.md 4g);
-decoding and resampling audio files stay the caller's.
+WAV files of any rate come in through ``etude_amd.audio.AudioLoader``; decoding other formats stays the caller's.
 
 The filter design (``ellip_bandpass_sos``) is numpy fp64 of its own -- the package does not depend on scipy; tests/test_alignfeat_cpu.py holds it to
 ``scipy.signal.ellipord`` / ``ellip``.
@@ -400,8 +400,8 @@ class AlignFeatures(Engine):
         return self.features_many([wav], [tuning_offset])[0]
 
     def as_feature_fn(self, load_fn: Callable, tuning_fn: Union[None, str, Callable] = None) -> Callable:
-        """-> the ``path -> (quantised chroma, DLNCO)`` callable ``AudioAligner(feature_fn=...)`` takes.  load_fn(path) -> mono samples at 22 050 Hz (decoding and
-        resampling are the caller's); tuning_fn(path, samples) -> cents, default 0; ``tuning_fn="estimate"`` estimates it on the device."""
+        """-> the ``path -> (quantised chroma, DLNCO)`` callable ``AudioAligner(feature_fn=...)`` takes.  load_fn(path) -> mono samples at 22 050 Hz (``AudioLoader().as_load_fn()``
+        for WAV files of any rate; other formats are the caller's); tuning_fn(path, samples) -> cents, default 0; ``tuning_fn="estimate"`` estimates it on the device."""
         if isinstance(tuning_fn, str) and tuning_fn != "estimate":
             raise ValueError(f"as_feature_fn: tuning_fn is a callable, None or \"estimate\", got {tuning_fn!r}")
 

@@ -352,3 +352,9 @@ class BeatDetector(Engine):
                 raise ValueError(f"debug_stage_taps: {k} holds {v.numel()} floats, the stated sizes need {need}")
             setattr(t, k, v.data_ptr())
         _lib.check(self._lib.etd_beat_debug_stage_taps(self.h, C.byref(t)), "etd_beat_debug_stage_taps")
+
+
+def structuralize_files_many(detector: BeatDetector, separator, paths: Sequence, loader=None) -> List[List[Dict]]:
+    """WAV files of any rate -> their tempo.json rows: ``beat_analyzer.structuralize_files_many`` under the detector's module name"""
+    from .beat_analyzer import structuralize_files_many as run
+    return run(detector, separator, paths, loader)

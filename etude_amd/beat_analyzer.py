@@ -169,3 +169,13 @@ def structuralize_stems_many(detector, stems_list: Sequence, stem_features=None)
 def structuralize_audio_many(detector, separator, wavs: Sequence) -> List[List[Dict]]:
     """the same from the songs' audio [channels][N]: ``detector.detect_audio_many`` (separator, features, model and trackers on the device) then ``analyze_data``"""
     return [BeatAnalyzer().analyze_data(r) for r in detector.detect_audio_many(separator, wavs)]
+
+
+def structuralize_files_many(detector, separator, paths: Sequence, loader=None) -> List[List[Dict]]:
+    """the same from WAV files of any rate: loaded on the device at the separator's rate (``etude_amd.audio``), as the mean of their channels for a
+    1-channel separator, else with the channels they have (the separator duplicates a mono file).  loader: an ``AudioLoader`` (default: one per device, made once)"""
+    if loader is None:
+        from .audio import default_audio_loader
+        loader = default_audio_loader(separator.device)
+    wavs = loader.load_many(paths, separator.config.sample_rate, mono=separator.config.n_channels == 1)
+    return structuralize_audio_many(detector, separator, wavs)

@@ -348,9 +348,10 @@ class IPECalculator:
         return self.calculate_many([file_path])[0]
 
 
-def _align_rendered(eval_dir: Path, keys: Sequence[Tuple[str, str]], results: List[Optional[Dict]], renderer, device) -> List[Optional[Dict]]:
+def _align_rendered(eval_dir: Path, keys: Sequence[Tuple[str, str]], results: List[Optional[Dict]], renderer, device, loader=None) -> List[Optional[Dict]]:
     """``evaluate_many(renderer=...)``: the alignment results with those of the covers that exist as notes only filled in.  Every origin's features are computed
-    once, whatever the number of its versions."""
+    once, whatever the number of its versions.  loader: an ``AudioLoader``; with one the origins are loaded on the device as mono 22 050 Hz, whatever their own
+    rate and channel count."""
     from .aligner import align_notes_many
     from .alignfeat import FS, default_align_features
     from .extractor import read_wav
@@ -366,13 +367,16 @@ def _align_rendered(eval_dir: Path, keys: Sequence[Tuple[str, str]], results: Li
     if not todo:
         return results
     songs = sorted({d for _, d, _ in todo})
-    wavs = []
-    for d in songs:
-        x, sr = read_wav(eval_dir / d / "origin.wav")
-        if sr != FS or x.shape[0] != 1:
-            raise ValueError(f"{eval_dir / d / 'origin.wav'}: {x.shape[0]} channel(s) at {sr} Hz; a rendered cover is aligned to a mono origin at {FS} Hz "
-                             f"(resample it first: FrontEnd(sr_in, {FS}).resample)")
-        wavs.append(x[0])
+    if loader is not None:
+        wavs = loader.load_many([eval_dir / d / "origin.wav" for d in songs], FS, mono=True)
+    else:
+        wavs = []
+        for d in songs:
+            x, sr = read_wav(eval_dir / d / "origin.wav")
+            if sr != FS or x.shape[0] != 1:
+                raise ValueError(f"{eval_dir / d / 'origin.wav'}: {x.shape[0]} channel(s) at {sr} Hz; a rendered cover is aligned to a mono origin at {FS} Hz "
+                                 f"(resample it first: FrontEnd(sr_in, {FS}).resample)")
+            wavs.append(x[0])
     features = default_align_features(device)
     origin = dict(zip(songs, features.features_many(wavs)))
     out = list(results)
@@ -382,14 +386,15 @@ def _align_rendered(eval_dir: Path, keys: Sequence[Tuple[str, str]], results: Li
 
 
 def evaluate_many(eval_dir, metadata: Sequence[Dict], versions: Sequence[str], metrics: Sequence[str] = ("wpd", "rgc", "ipe"), aligner=None, device="cuda",
-                  wpd_subsample_step: int = 1, wpd_trim_seconds: float = 0, renderer=None, **rhythm_params) -> List[Dict]:
+                  wpd_subsample_step: int = 1, wpd_trim_seconds: float = 0, renderer=None, loader=None, **rhythm_params) -> List[Dict]:
     """``EvaluationRunner.run`` of the reference (etude/evaluation/runner.py) -> its rows as dicts: ``song``, ``version``, then ``wpd_score``, ``rgc_score``,
     ``inferred_tau``, ``ipe_score`` where the metric succeeded; a row with no metric is dropped.  metadata: the loaded metadata list (``dir_name`` per song).  WPD
     goes through ``AudioAligner.align`` and ``wpd_many`` as they stand; RGC and IPE of every (song, version) come from ONE device call.
 
     renderer: a ``NoteRenderer`` (22 050 Hz).  With one, a (song, version) that ``align`` has no result for, whose ``{version}.wav`` is missing but whose ``.mid`` or
     ``.json`` exists next to an ``origin.wav``, gets its WPD from the cover rendered on the device (``aligner.align_notes_many``; nothing is written to ``wp.json``).
-    ``origin.wav`` must already be mono at 22 050 Hz: resampling stays the caller's (``FrontEnd(sr_in, 22050).resample``)."""
+    loader: an ``etude_amd.AudioLoader``.  With one, ``origin.wav`` of any rate and channel count is loaded on the device as mono 22 050 Hz; without
+    one it must already be mono at 22 050 Hz."""
     eval_dir = Path(eval_dir)
     keys = [(s["dir_name"], v) for s in metadata if s.get("dir_name") for v in versions]
     rows = [{"song": d, "version": v} for d, v in keys]
@@ -399,7 +404,7 @@ def evaluate_many(eval_dir, metadata: Sequence[Dict], versions: Sequence[str], m
         aligner = aligner or AudioAligner(device=device)
         results = [aligner.align(eval_dir / d / "origin.wav", eval_dir / d / f"{v}.wav", eval_dir / d) for d, v in keys]
         if renderer is not None:
-            results = _align_rendered(eval_dir, keys, results, renderer, device)
+            results = _align_rendered(eval_dir, keys, results, renderer, device, loader)
         for row, res in zip(rows, wpd_many(results, wpd_subsample_step, wpd_trim_seconds)):
             if "error" not in res:
                 row.update(res)

@@ -107,6 +107,14 @@ class TuningEstimator(Engine):
         tun, sim = self.estimate_device(self.check_songs(wavs))
         return (tun, sim.cpu().numpy()) if details else tun
 
+    def estimate_files_many(self, paths: Sequence, loader=None, details: bool = False):
+        """``estimate_many`` from WAV files of any rate and channel count, loaded on the device as mono 22 050 Hz (``etude_amd.audio``).  loader: an
+        ``AudioLoader`` (default: one per device, made once)"""
+        if loader is None:
+            from .audio import default_audio_loader
+            loader = default_audio_loader(self.device)
+        return self.estimate_many(loader.load_many(paths, FS, mono=True), details)
+
     def estimate(self, wav) -> int:
         return int(self.estimate_many([wav])[0])
 
@@ -125,5 +133,5 @@ def default_tuning_estimator(device="cuda") -> TuningEstimator:
 def estimate_tuning(x, Fs: int = FS) -> int:
     """the reference's call shape: ``estimate_tuning(audio, fs)`` -> cents.  The engine is fixed to 22 050 Hz."""
     if int(Fs) != FS or Fs != int(Fs):
-        raise ValueError(f"estimate_tuning: the engine is fixed to Fs = {FS}, got {Fs} (resampling is the caller's)")
+        raise ValueError(f"estimate_tuning: the engine is fixed to Fs = {FS}, got {Fs} (resample first: AudioLoader().resample_many([x], Fs, {FS}))")
     return default_tuning_estimator().estimate(x)

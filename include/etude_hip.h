@@ -31,7 +31,9 @@
  *                         strictly monotonic path, pitch_shift
  *   etd_tuning_run        estimate_tuning(audio, fs) of                  etude/data/aligner.py:100-101
  *                         AudioAligner._compute_alignment
- *   etd_rhythm_run        RGCCalculator / IPECalculator .calculate       etude/evaluation/metrics/rgc.py, ipe.py
+ *   etd_resample_run      librosa.load(path, sr=22050) behind the walk   etude/data/aligner.py:71-72,
+ *                         over the WAV's chunks; torchaudio.load          scripts/run_separation.py:89
+ *   etd_rhythm_run       RGCCalculator / IPECalculator .calculate       etude/evaluation/metrics/rgc.py, ipe.py
  *   etd_attr_run          EtudeDataset._extract_bar_features,             etude/data/dataset.py:204-270, 335-339
  *                         _compute_musical_attributes, _get_attribute_bin_id
  *
@@ -464,7 +466,8 @@ int etd_dtw_align(etd_dtw*, const float* const* feat_ptrs, int n_pairs, const in
  * The feature extraction in front of the DTW, modelled on synctoolbox's published pipeline (audio_to_pitch_features, pitch_to_chroma, quantize_chroma,
  * audio_to_pitch_onset_features, pitch_onset_features_to_DLNCO): rate tiers 22 050 / 4 410 / 882 Hz, 88 zero-phase elliptic band-passes (pitches 21 .. 108, an fp64
  * recurrence whose time axis is split exactly into chunks), pitch energy, chroma, onset novelty, peaks, DLNCO.  DESIGN.md 4f is the contract (parity with synctoolbox
- * itself is unpinned); the tuning offset comes from etd_tuning_run or the caller, decoding and resampling audio stay the caller's. */
+ * itself is unpinned); the tuning offset comes from etd_tuning_run or the caller; WAV samples of another rate or layout come through etd_resample_run, decoding other
+ * file formats stays the caller's. */
 typedef struct etd_alignfeat etd_alignfeat;
 typedef struct {
   int struct_bytes;          /* sizeof(etd_alignfeat_cfg) of the caller: a mismatch is ETD_EINVAL */
@@ -526,6 +529,53 @@ long long etd_tuning_workspace_bytes(const etd_tuning*, int n_songs, const int64
  * a song's numbers depend on its samples alone: bit-identical alone, in any batch and in any order.  Synchronises `stream` once at the start (song table upload). */
 int etd_tuning_run(etd_tuning*, const float* const* wav_ptrs, int n_songs, const int64_t* N_host, int32_t* tuning_dev, double* sim_dev, void* workspace_dev,
                    long long workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------ audio loading (raw WAV samples of any rate, width and channel count -> fp32 at an engine's rate
+ * and layout).  librosa.load(path, sr=22050) of etude/data/aligner.py:71-72 and scripts/preprocess.py:135, torchaudio.load of scripts/run_separation.py:89, behind the
+ * walk over the file's chunks (etude_amd.audio.read_wav_raw).  The filter is this project's own windowed sinc, modelled on resampy's kaiser_best / kaiser_fast:
+ *   up / down = sr_out / sr_in in lowest terms, s = min(1, up / down), half = ceil(Z / s), K = 2 half,
+ *   h(t) = s r sinc(s r t) I0(beta sqrt(1 - (s t / Z)^2)) / I0(beta) for |s t| < Z, else 0  (t in input samples; best: Z 64, fast: Z 16),
+ *   y[n] = sum_{k < K} tab[p][k] x[i0 - half + 1 + k],  i0 = n down div up,  p = n down mod up,  tab[p][k] = h(k - half + 1 - p / up),  x = 0 outside [0, N),
+ *   N' = ceil(N up / down); the sum is one fp32 fmaf chain with k ascending.  Mono is the fp32 sum of the channels in order times 1.f / C, taken before the filter.
+ * DESIGN.md 4q is the contract (parity with soxr, resampy or librosa is unpinned).  Decoding anything but RIFF/WAVE stays the caller's. */
+typedef struct etd_resample etd_resample;
+enum {                       /* sample formats: little-endian, interleaved [N][C] as in a WAV data chunk, except the last */
+  ETD_PCM_U8 = 0,            /* (v - 128) / 128 */
+  ETD_PCM_S16 = 1,           /* float(v) 2^-15 */
+  ETD_PCM_S24 = 2,           /* float(v) 2^-23; three bytes per sample, no alignment */
+  ETD_PCM_S32 = 3,           /* float(v) 2^-31 */
+  ETD_PCM_F32 = 4,
+  ETD_PCM_F64 = 5,           /* (float)v */
+  ETD_PCM_F32_PLANAR = 6     /* fp32 [C][N]: tensors already on the device */
+};
+enum { ETD_RESAMPLE_BEST = 0, ETD_RESAMPLE_FAST = 1 };
+typedef struct {
+  int struct_bytes;          /* sizeof(etd_resample_cfg) of the caller: a mismatch is ETD_EINVAL */
+  int sr_in, sr_out;         /* Hz, 1 .. 2^30 */
+  int quality;               /* ETD_RESAMPLE_BEST (Z = 64) or ETD_RESAMPLE_FAST (Z = 16) */
+  int up, down;              /* sr_out / sr_in in lowest terms, as the caller's table was designed: anything else is ETD_EINVAL */
+  int half;                  /* ceil(Z / s) of that table */
+  int reserved;              /* 0 */
+} etd_resample_cfg;
+/* table_host: fp32 [up][2 half], the filter designed by the host layer in fp64 and rounded once (NULL when sr_in == sr_out: such a handle only decodes).  Needs no
+ * GPU: the table goes to the device with the first etd_resample_run.  ETD_EINVAL with a sentence: a cfg that does not match the rates, up x 2 half above 2^22
+ * entries (e.g. 44 100 -> 22 051 Hz), a non-finite table. */
+int etd_resample_create(const etd_resample_cfg* cfg, const float* table_host, etd_resample** out);
+void etd_resample_destroy(etd_resample*);
+/* HOST ONLY: N' = ceil(N up / down) in integers; negative = ETD_EINVAL (N < 0 or above 2^32) */
+long long etd_resample_out_len(const etd_resample*, long long N);
+/* HOST ONLY: bytes of device workspace a call with these songs needs (the song table and one 16-byte record per 256 outputs of every written channel); negative =
+ * ETD_EINVAL: n_songs outside 1 .. 4096, channels outside 1 .. 8, frames outside 1 .. 2^32 */
+long long etd_resample_workspace_bytes(const etd_resample*, int n_songs, const int64_t* frames_host, const int32_t* channels_host, const int32_t* mono_host);
+/* src_ptrs: HOST array of n_songs DEVICE pointers to the raw samples of song s: frames_host[s] frames of channels_host[s] channels in format_host[s] (ETD_PCM_*),
+ * bytes_host[s] bytes in all, aligned to the sample width (S24 and U8: any address).  out_ptrs: HOST array of DEVICE pointers, song s = fp32 [C][N'], or [N'] where
+ * mono_host[s] != 0.  workspace_dev: 256-byte aligned device memory of workspace_bytes >= etd_resample_workspace_bytes.  Refused with ETD_EINVAL and a sentence before
+ * anything is launched: channels outside 1 .. 8, a byte count other than frames x channels x width, an unknown format, a NULL or misaligned pointer, a workspace that
+ * is too small, and a rate ratio whose staged input span (about 256 down / up + 2 half floats) outgrows the LDS the device reports.  One launch whatever n_songs, no
+ * atomics: a song's samples depend on its own bytes and the table alone, bit-identical alone, in any batch and in any order.  Synchronises `stream` once at the start
+ * (table upload). */
+int etd_resample_run(etd_resample*, const void* const* src_ptrs, int n_songs, const int64_t* frames_host, const int32_t* channels_host, const int32_t* format_host,
+                     const int32_t* mono_host, const int64_t* bytes_host, float* const* out_ptrs, void* workspace_dev, long long workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ rhythm metrics (note onsets -> Rhythmic Grid Consistency and IOI Pattern Entropy).
  * RGCCalculator.calculate and IPECalculator.calculate (etude/evaluation/metrics/rgc.py, ipe.py) behind get_onsets_from_file, with the KMeans of scikit-learn the second

@@ -223,6 +223,11 @@ int etd_tuning_debug_layout(const etd_tuning*, int n_songs, const int64_t* N_hos
  * launch is added either way. */
 int etd_tuning_debug_power(etd_tuning*, int song, const int32_t* frames_host, int n_frames, float* power_dev);
 
+/* HOST ONLY test hook: the plan of an etd_resample_run with these shapes, one record per workgroup in launch order: out int64 [n_tiles][4] = song, channel (0 for a
+ * mono song), first output n0, outputs (256, fewer in a channel's last tile).  *n_tiles is always set; capacity (in records) below it, or out = NULL, is ETD_ENOMEM. */
+int etd_resample_debug_layout(const etd_resample*, int n_songs, const int64_t* frames_host, const int32_t* channels_host, const int32_t* mono_host, int64_t* out,
+                              long long capacity, long long* n_tiles);
+
 /* test hook: during the following etd_rhythm_run calls the kernel also copies out what it clustered: logioi_dev (DEVICE fp64, as long as onsets_dev): the centred,
  * clipped log-IOIs of cover b at [offsets[b] .. offsets[b + 1] - 1) -- the device's own logarithm, which may differ from numpy's by an ulp --; labels_dev (DEVICE
  * int8, same layout): the final labels; centres_dev (DEVICE fp64 [n_covers][8]): the final centres on the centred axis, NaN past k.  Entries of covers without an IPE
