@@ -363,6 +363,9 @@ SIGNATURES = {
     "etd_sep_debug_mask": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
     "etd_sep_debug_istft": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
     "etd_sep_magnitudes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
+    "etd_sep_set_mwf": (C.c_int, [C.c_void_p, C.c_int]),
+    "etd_sep_get_mwf": (C.c_int, [C.c_void_p]),
+    "etd_sep_debug_mwf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p]),
     "etd_septrain_create": (C.c_int, [C.POINTER(SepCfg), C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), c_i64_p, C.c_int, C.POINTER(C.c_void_p)]),
     "etd_septrain_destroy": (None, [C.c_void_p]),
     "etd_septrain_workspace_bytes": (C.c_longlong, [C.c_void_p, C.c_int]),

@@ -120,3 +120,12 @@ __device__ __forceinline__ void sep_tile_step(const float (&As)[SEP_BK][SEP_LD],
   }
 }
 __device__ __forceinline__ float sep_tile_total(const f32x16 (&tot)[4], int r) { return (tot[0][r] + tot[1][r]) + (tot[2][r] + tot[3][r]); }
+
+// ---- multichannel Wiener filtering of one song's masked spectra (separator_mwf.hip): `iterations` (1 .. SEP_MWF_MAX_ITER) passes in place on
+// Y [I][C][Tf][F] with the mixture X [C][Tf][F], C = 1 or 2, in `scratch` (sep_mwf_scratch_bytes of it, 256-byte aligned, the caller's: etd_sep_run lends the work
+// region, idle between the mask pass and the inverse STFT).  Reads nothing but the song's own X and Y, sums in an order Tf alone fixes.
+#define SEP_MWF_MAX_ITER 8
+#define SEP_MWF_MAX_CHANNELS 2
+#define SEP_MWF_CHUNK 64                   // frames per partial sum of the source model
+long long sep_mwf_scratch_bytes(int I, int C, int F, long long Tf);
+int sep_mwf_run(const float2* X, float2* Y, long long Tf, int I, int C, int F, int iterations, void* scratch, hipStream_t st);

@@ -10,6 +10,7 @@
 //                    Both are the trainer's convolutions too (separator_train.hip, through sep_launch with the PLAIN epilogue): separator.h holds the descriptor,
 //                    the tile step and the layers' geometry.
 //   k_sep_mask       softmax over the instruments, ratio mask, zero extension and the product with X in one pass
+//   (k_mwf_*)        with etd_sep_set_mwf: passes of multichannel Wiener filtering in place on the masked spectra (separator_mwf.hip)
 //   k_sep_istft      one workgroup per (stem, channel, frame): inverse split pass -> the same Stockham stages on conjugated data -> windowed frame
 //   k_sep_ola        gather overlap-add: every output sample sums its at most four frames in ascending frame order
 //
@@ -342,6 +343,7 @@ struct etd_sep {
   float *d_w_conv[ETD_SEP_LEVELS], *d_b_conv[ETD_SEP_LEVELS], *d_w_dec[ETD_SEP_LEVELS][4], *d_b_dec[ETD_SEP_LEVELS], *d_bn_a[2 * ETD_SEP_LEVELS], *d_bn_s[2 * ETD_SEP_LEVELS];
   float *d_w_head = nullptr, *d_b_head = nullptr;
   Workspace ws;
+  int mwf = 0;                       // Wiener iterations between the mask pass and the inverse STFT (etd_sep_set_mwf; 0 = none)
 };
 
 namespace {
@@ -543,6 +545,11 @@ int sep_plan(const etd_sep* h, int n_songs, const int64_t* N_host, SepPlan* p) {
   p->nb = nb;
   const long long uw = nb * h->unit_floats * 4;
   work = uw > work ? uw : work;
+  if (h->mwf > 0)                                      // the Wiener stage borrows the work region: its tables do not depend on the budget, so they raise the floor
+    for (int s = 0; s < n_songs; ++s) {
+      const long long mw = sep_mwf_scratch_bytes(c.n_instr, c.n_channels, c.F, p->Tf[s]);
+      work = mw > work ? mw : work;
+    }
   const long long plane = (long long)c.T * c.F * c.n_channels * 4;
   WsCursor ws;
   p->off_X = ws.take(xf * 8);
@@ -744,6 +751,7 @@ extern "C" int etd_sep_run(etd_sep* h, const float* const* wav_ptrs, int n_songs
     for (int s = 0; s < ng; ++s) {
       const long long N = N_host[s0 + s];
       ETD_TRY(sep_mask(h, logits + p.seg0[s] * c.n_instr * plane, mag + p.seg0[s] * plane, X + p.x_off[s], p.Tf[s], Y + p.y_off[s], st));
+      if (h->mwf > 0) ETD_TRY(sep_mwf_run(X + p.x_off[s], Y + p.y_off[s], p.Tf[s], c.n_instr, c.n_channels, c.F, h->mwf, work, st));
       const long long ni = sep_stems_per_pass(h, p.Tf[s], p.work_budget);
       for (long long i0 = 0; i0 < c.n_instr; i0 += ni) {
         const long long n = c.n_instr - i0 < ni ? c.n_instr - i0 : ni;
@@ -767,6 +775,20 @@ extern "C" int etd_sep_magnitudes(etd_sep* h, const float* wav_dev, long long N,
   ETD_TRY(sep_stft(h, wav_dev, N, Tf, (float2*)h->ws.p, c.F, mag_dev, st));
   HIP_TRY(hipGetLastError());
   return ETD_OK;
+}
+
+extern "C" int etd_sep_set_mwf(etd_sep* h, int iterations) {
+  if (!h) ETD_FAIL(ETD_EINVAL, "sep_set_mwf: null handle");
+  if (iterations < 0 || iterations > SEP_MWF_MAX_ITER) ETD_FAIL(ETD_EINVAL, "sep_set_mwf: iterations = %d must be in 0 .. %d", iterations, SEP_MWF_MAX_ITER);
+  if (iterations > 0 && h->cfg.n_channels > SEP_MWF_MAX_CHANNELS)
+    ETD_FAIL(ETD_EINVAL, "sep_set_mwf: Wiener filtering takes 1 or %d channels, the engine has %d", SEP_MWF_MAX_CHANNELS, h->cfg.n_channels);
+  h->mwf = iterations;
+  return ETD_OK;
+}
+
+extern "C" int etd_sep_get_mwf(const etd_sep* h) {
+  if (!h) ETD_FAIL(ETD_EINVAL, "sep_get_mwf: null handle");
+  return h->mwf;
 }
 
 // ================================================================================================ test hooks
@@ -823,6 +845,19 @@ extern "C" int etd_sep_debug_istft(etd_sep* h, const float* Y_dev, long long N, 
   ETD_TRY(sep_upload(h));
   ETD_TRY(h->ws.reserve(ws_align(rows * Tf * c.n_fft * 4), st));
   ETD_TRY(sep_istft(h, (const float2*)Y_dev, Tf, N, rows, (float*)h->ws.p, out_dev, st));
+  HIP_TRY(hipGetLastError());
+  return ETD_OK;
+}
+
+extern "C" int etd_sep_debug_mwf(etd_sep* h, const float* X_dev, float* Y_dev, long long Tf, int iterations, void* stream) {
+  if (!h || !X_dev || !Y_dev || Tf < 1) ETD_FAIL(ETD_EINVAL, "sep_debug_mwf: null argument or Tf < 1");
+  if (iterations < 0 || iterations > SEP_MWF_MAX_ITER) ETD_FAIL(ETD_EINVAL, "sep_debug_mwf: iterations = %d must be in 0 .. %d", iterations, SEP_MWF_MAX_ITER);
+  const etd_sep_cfg& c = h->cfg;
+  if (c.n_channels > SEP_MWF_MAX_CHANNELS) ETD_FAIL(ETD_EINVAL, "sep_debug_mwf: Wiener filtering takes 1 or %d channels, the engine has %d", SEP_MWF_MAX_CHANNELS, c.n_channels);
+  if (iterations == 0) return ETD_OK;
+  hipStream_t st = (hipStream_t)stream;
+  ETD_TRY(h->ws.reserve(ws_align(sep_mwf_scratch_bytes(c.n_instr, c.n_channels, c.F, Tf)), st));
+  ETD_TRY(sep_mwf_run((const float2*)X_dev, (float2*)Y_dev, Tf, c.n_instr, c.n_channels, c.F, iterations, h->ws.p, st));
   HIP_TRY(hipGetLastError());
   return ETD_OK;
 }

@@ -29,6 +29,8 @@ from ._engine import Engine, hold, i64, nonneg, ptrs
 LEVELS = 6            # ETD_SEP_LEVELS
 MAX_INSTR = 16        # ETD_SEP_MAX_INSTR
 MAX_CHANNELS = 8      # ETD_SEP_MAX_CHANNELS
+MWF_MAX_ITERATIONS = 8    # etd_sep_set_mwf's range
+MWF_MAX_CHANNELS = 2
 
 
 @dataclass
@@ -147,13 +149,16 @@ class StemSeparator(Engine):
     ``{name: [N][channels]}`` of numpy arrays.  A song's stems are bit-identical alone, in any batch, under any ``workspace_bytes`` and from run to run.
     ``workspace_bytes`` bounds the device workspace: songs are grouped and (segment, instrument) units sub-batched under it; one song with one unit is the floor
     (``workspace_total_bytes`` tells what a call holds).
+    ``mwf_iterations`` (0 .. 8, default 0 = off; 1 or 2 channels) refines the masked spectra by that many passes of multichannel Wiener filtering before the inverse
+    STFT, the ratio mask being the initial estimate (csrc/separator_mwf.hip; modelled on norbert's, parity unpinned).
     Constructing needs no GPU; separating does: there is no CPU path."""
     _destroy = "etd_sep_destroy"
 
     def __init__(self, config: Optional[SeparatorConfig] = None, state: Optional[Dict] = None, seed: int = 0, device: Union[str, torch.device] = "cuda",
-                 workspace_bytes: int = 4 << 30):
+                 workspace_bytes: int = 4 << 30, mwf_iterations: int = 0):
         self.config = cfg = config or SeparatorConfig()
         cfg.check()
+        mwf_iterations = self._check_mwf(mwf_iterations)
         if workspace_bytes < 1:
             raise ValueError(f"StemSeparator: workspace_bytes must be positive, got {workspace_bytes}")
         if state is None:
@@ -176,6 +181,7 @@ class StemSeparator(Engine):
         _lib.check(self._lib.etd_sep_create(C.byref(ccfg), instr, names, ptrs, numels, n, C.byref(h)), "etd_sep_create")
         del keep
         self._adopt(h)
+        self.mwf_iterations = mwf_iterations
 
     # ------------------------------------------------------------------ host arithmetic
     def num_frames(self, N: int) -> int:
@@ -194,6 +200,23 @@ class StemSeparator(Engine):
     def workspace_total_bytes(self, Ns: Sequence[int]) -> int:
         return nonneg(self._lib.etd_sep_workspace_bytes(self.h, len(Ns), i64(Ns)), "etd_sep_workspace_bytes")
 
+    def _check_mwf(self, n) -> int:
+        """ValueError for what etd_sep_set_mwf refuses; needs no GPU"""
+        if isinstance(n, bool) or int(n) != n or not 0 <= n <= MWF_MAX_ITERATIONS:
+            raise ValueError(f"StemSeparator: mwf_iterations must be an integer in 0 .. {MWF_MAX_ITERATIONS}, got {n!r}")
+        if n > 0 and self.config.n_channels > MWF_MAX_CHANNELS:
+            raise ValueError(f"StemSeparator: multichannel Wiener filtering takes 1 or {MWF_MAX_CHANNELS} channels, the config has {self.config.n_channels}")
+        return int(n)
+
+    @property
+    def mwf_iterations(self) -> int:
+        """Wiener passes every ``separate_many`` runs between the masks and the inverse STFT (0 = none); settable"""
+        return nonneg(self._lib.etd_sep_get_mwf(self.h), "etd_sep_get_mwf")
+
+    @mwf_iterations.setter
+    def mwf_iterations(self, n: int) -> None:
+        _lib.check(self._lib.etd_sep_set_mwf(self.h, self._check_mwf(n)), "etd_sep_set_mwf")
+
     def save(self, path) -> None:
         torch.save({k: torch.from_numpy(v) for k, v in self.state.items()}, str(path))
 
@@ -208,8 +231,17 @@ class StemSeparator(Engine):
             raise ValueError(f"song {i}: audio must have 1 or {self.config.n_channels} channels, got {shp[0]}")
         return shp
 
-    def separate_many(self, wavs: Sequence) -> List[torch.Tensor]:
-        """songs [n_channels][N_s] (or mono [N_s] / [1][N_s]) -> [instr][n_channels][N_s] device tensors, one per song"""
+    def separate_many(self, wavs: Sequence, mwf_iterations: Optional[int] = None) -> List[torch.Tensor]:
+        """songs [n_channels][N_s] (or mono [N_s] / [1][N_s]) -> [instr][n_channels][N_s] device tensors, one per song.  ``mwf_iterations``: this call's Wiener
+        passes instead of the engine's"""
+        if mwf_iterations is not None:
+            n, own = self._check_mwf(mwf_iterations), self.mwf_iterations
+            if n != own:
+                self.mwf_iterations = n
+                try:
+                    return self.separate_many(wavs)
+                finally:
+                    self.mwf_iterations = own
         if len(wavs) == 0:
             return []
         shapes = [self._song_shape(i, x) for i, x in enumerate(wavs)]
@@ -296,3 +328,19 @@ class StemSeparator(Engine):
         with torch.cuda.device(dev):
             _lib.check(self._lib.etd_sep_debug_istft(self.h, C.c_void_p(Yr.data_ptr()), int(N), C.c_void_p(out.data_ptr()), self._stream(dev)), "etd_sep_debug_istft")
         return out
+
+    def debug_mwf(self, X: torch.Tensor, Y: torch.Tensor, iterations: int) -> torch.Tensor:
+        """X [C][Tf][F] complex64, Y [instr][C][Tf][F] complex64 -> Y after ``iterations`` Wiener passes (a new tensor; the stage runs in place on a copy)"""
+        dev = self._device()
+        cfg = self.config
+        iterations = self._check_mwf(iterations)
+        if cfg.n_channels > MWF_MAX_CHANNELS:
+            raise ValueError(f"debug_mwf: multichannel Wiener filtering takes 1 or {MWF_MAX_CHANNELS} channels, the config has {cfg.n_channels}")
+        Xr = torch.view_as_real(X.to(dev, torch.complex64).contiguous()).contiguous()
+        Yr = torch.view_as_real(Y.to(dev, torch.complex64).contiguous()).clone()
+        Tf = int(X.shape[1])
+        if tuple(Xr.shape) != (cfg.n_channels, Tf, cfg.F, 2) or tuple(Yr.shape) != (len(cfg.instruments), cfg.n_channels, Tf, cfg.F, 2) or Tf < 1:
+            raise ValueError(f"debug_mwf: X has shape {tuple(X.shape)}, Y {tuple(Y.shape)}")
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.etd_sep_debug_mwf(self.h, C.c_void_p(Xr.data_ptr()), C.c_void_p(Yr.data_ptr()), Tf, iterations, self._stream(dev)), "etd_sep_debug_mwf")
+        return torch.view_as_complex(Yr)

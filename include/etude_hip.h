@@ -781,6 +781,14 @@ double etd_sep_segment_flops(const etd_sep*);
 /* audio -> the U-Net's input: wav [n_channels][N] DEVICE fp32 -> mag [ceil(Tf / T)][T][F][n_channels] DEVICE fp32, |X| below bin F of the song's Tf =
  * etd_sep_num_frames(N) frames, zeros past the last (step 2 of etd_sep_run, by the same kernel).  Synchronises `stream` when the workspace grows. */
 int etd_sep_magnitudes(etd_sep*, const float* wav_dev, long long N, float* mag_dev, void* stream);
+/* HOST ONLY: multichannel Wiener filtering of the stems (csrc/separator_mwf.hip; DESIGN.md 4r is the contract, tests/separator_mwf_np.py restates it; modelled on
+ * norbert.wiener, parity unpinned).  `iterations` in 0 .. 8 refinements of every later etd_sep_run's masked spectra between the mask pass and the inverse STFT, the
+ * ratio mask being the initial estimate: per iteration a spatial covariance per (source, bin) over all frames of the song, then the multichannel Wiener gain per
+ * (frame, bin), in fp64 on the fp32 spectra.  0 (a new handle's value) = none: etd_sep_run is then what it was.  iterations > 0 needs n_channels 1 or 2
+ * (ETD_EINVAL otherwise).  The scratch comes from the workspace's work region and may raise its floor: etd_sep_workspace_bytes tells. */
+int etd_sep_set_mwf(etd_sep*, int iterations);
+/* HOST ONLY: the value set (negative = ETD_EINVAL) */
+int etd_sep_get_mwf(const etd_sep*);
 
 /* ---- training of the source separator (csrc/separator_train.hip; DESIGN.md 4n is the contract, tests/separator_train_np.py restates it) ----------------------
  * The U-Nets of etd_sep in training mode (every norm on the batch's statistics), the L1 loss on the softmax estimates, every gradient and torch.optim.Adam, in fp32

@@ -301,6 +301,9 @@ int etd_sep_debug_stft(etd_sep*, const float* wav_dev, long long N, float* X_dev
 int etd_sep_debug_layer(etd_sep*, int instr, int kind, int layer, const float* x0_dev, const float* x1_dev, int n_units, float* pre_dev, float* act_dev, void* stream);
 int etd_sep_debug_mask(etd_sep*, const float* logits_dev, const float* mag_dev, const float* X_dev, long long Tf, float* Y_dev, void* stream);
 int etd_sep_debug_istft(etd_sep*, const float* Y_dev, long long N, float* out_dev, void* stream);
+/*   mwf     the Wiener stage of etd_sep_set_mwf on a tapped input, by the launcher etd_sep_run uses: X [n_channels][Tf][F] complex, Y [n_instr][n_channels][Tf][F]
+ *           complex, refined IN PLACE by `iterations` (0 .. 8; 0 leaves Y untouched) passes.  Synchronises `stream` when the workspace grows. */
+int etd_sep_debug_mwf(etd_sep*, const float* X_dev, float* Y_dev, long long Tf, int iterations, void* stream);
 
 /* stage taps of separator training (csrc/separator_train.hip): each backward kernel on a caller's input, with the launchers etd_septrain_forward_backward uses.
  * DEVICE fp32; every tensor holds B x n_instr units back to back, unit u = b * n_instr + instrument, each with its instrument's weights.

@@ -1,10 +1,13 @@
 """Time the source separator on one 3-minute stereo song at the default config and write profiles/separator_device.json.
 
     python tools/bench_separator.py [--seconds 180] [--runs 5] [--warmup 2] [--test-log LOG] [--out profiles/separator_device.json]
+    python tools/bench_separator.py --mwf 1 [--out profiles/separator_mwf.json]
 
 Median wall time of ``StemSeparator.separate_many`` (synchronised) over the runs, then one profiled run for the per-kernel split (the library's event profiler).
 --test-log: the output of ``pytest tests/test_gpu_separator.py -s``; its SEP_ERR lines give the largest device / yardstick error ratio of every stage.
-The weights are random (``init_separator_state``): the time does not depend on their values."""
+The weights are random (``init_separator_state``): the time does not depend on their values.
+--mwf N: the same song with N passes of multichannel Wiener filtering against the same engine with the filter off, the two timed in alternation;
+writes the added time per iteration, each k_mwf_* kernel's time and its algorithmic bytes over that time as a share of the 8 TB/s HBM peak."""
 import argparse
 import json
 import re
@@ -20,6 +23,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 
 PEAK_FP32_MFMA = 157.3e12
+PEAK_HBM = 8.0e12
 
 
 def error_ratios(log: Path) -> dict:
@@ -30,6 +34,55 @@ def error_ratios(log: Path) -> dict:
     return out
 
 
+def timed(sep, wav, mwf=None):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = sep.separate_many([wav], mwf_iterations=mwf) if mwf is not None else sep.separate_many([wav])
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, out
+
+
+def bench_mwf(a, sep, cfg, wav, N) -> dict:
+    """off and on in alternation (one process, one engine, one song), then one profiled run with the filter on"""
+    from etude_amd import _lib
+    off, on = [], []
+    for i in range(a.warmup + a.runs):
+        t_off, _ = timed(sep, wav, 0)
+        t_on, out = timed(sep, wav, a.mwf)
+        if i >= a.warmup:
+            off.append(t_off); on.append(t_on)
+    assert bool(torch.isfinite(out[0]).all())
+    _lib.prof_enable(True)
+    _lib.prof_reset()
+    timed(sep, wav, a.mwf)
+    prof = _lib.prof_report()
+    _lib.prof_enable(False)
+    Tf, I, C, F = sep.num_frames(N), len(cfg.instruments), cfg.n_channels, cfg.F
+    y_bytes, x_bytes = I * C * Tf * F * 8, C * Tf * F * 8
+    chunks = -(-Tf // 64)
+    # what each kernel must move, per launch: stats reads Y and writes the chunk partials; reduce reads them; apply reads X and Y and writes Y; scale reads X once per song
+    algo = {"k_mwf_scale": x_bytes, "k_mwf_stats": y_bytes + chunks * I * F * (C * C + 1) * 8, "k_mwf_reduce": chunks * I * F * (C * C + 1) * 8 + I * F * C * C * 8,
+            "k_mwf_apply": 2 * y_bytes + x_bytes}
+    kernels = {}
+    for k, v in sorted(prof.items()):
+        if k.startswith("k_mwf"):
+            per = v["ms"] / v["launches"]
+            kernels[k] = {"ms": v["ms"], "launches": v["launches"], "ms_per_launch": per, "algorithmic_bytes_per_launch": algo[k],
+                          "share_of_hbm_peak": algo[k] / (per * 1e-3) / PEAK_HBM}
+    med_off, med_on = statistics.median(off), statistics.median(on)
+    it_bytes = 3 * y_bytes + x_bytes
+    kern_ms_it = sum(v["ms"] for k, v in kernels.items() if k != "k_mwf_scale") / a.mwf
+    return {
+        "what": f"StemSeparator.separate_many with mwf_iterations = {a.mwf} against 0, one stereo song, default config, random weights, timed in alternation",
+        "device": torch.cuda.get_device_name(0), "arch": getattr(torch.cuda.get_device_properties(0), "gcnArchName", None), "seconds_of_audio": a.seconds, "samples": N, "frames": Tf,
+        "runs": a.runs, "warmup": a.warmup, "mwf_iterations": a.mwf, "median_off_s": med_off, "median_on_s": med_on, "all_off_s": off, "all_on_s": on,
+        "added_ms_per_iteration_over_wall": (med_on - med_off) * 1e3 / a.mwf, "kernel_ms_per_iteration": kern_ms_it,
+        "algorithmic_bytes_per_iteration": it_bytes, "iteration_share_of_hbm_peak_over_kernel_time": it_bytes / (kern_ms_it * 1e-3) / PEAK_HBM if kern_ms_it else None,
+        "kernels": kernels, "workspace_bytes_off": sep.workspace_total_bytes([N]),
+        "not_measured": ["hardware counters", "other song lengths, batches and instrument counts", "mono", "a trained checkpoint"],
+    }
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=180.0)
@@ -37,7 +90,10 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--test-log", type=Path, default=None)
     ap.add_argument("--out", type=Path, default=ROOT / "profiles" / "separator_device.json")
+    ap.add_argument("--mwf", type=int, default=0, help="time N passes of multichannel Wiener filtering against none (default --out: profiles/separator_mwf.json)")
     a = ap.parse_args()
+    if a.mwf and a.out == ROOT / "profiles" / "separator_device.json":
+        a.out = ROOT / "profiles" / "separator_mwf.json"
     from etude_amd import _lib
     from etude_amd.separator import SeparatorConfig, StemSeparator
     cfg = SeparatorConfig()
@@ -46,6 +102,12 @@ def main() -> None:
     r = np.random.default_rng(0)
     t = np.arange(N) / cfg.sample_rate
     wav = torch.from_numpy(np.stack([0.3 * np.sin(2 * np.pi * 220.0 * (c + 1) * t) + 0.1 * r.standard_normal(N) for c in range(2)]).astype(np.float32)).cuda()
+    if a.mwf:
+        res = bench_mwf(a, sep, cfg, wav, N)
+        a.out.parent.mkdir(parents=True, exist_ok=True)
+        a.out.write_text(json.dumps(res, indent=1) + "\n")
+        print(json.dumps(res))
+        return
     times = []
     for i in range(a.warmup + a.runs):
         torch.cuda.synchronize()
