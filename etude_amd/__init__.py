@@ -11,6 +11,7 @@ Drop-in surfaces (same names/signatures as the reference):
     etude_amd.DBNBeatTracker / DBNDownBeatTracker  <- madmom's DBNBeatTrackingProcessor / DBNDownBeatTrackingProcessor (csrc/dbn.hip)
     etude_amd.StemFeatures          <- process_stems_to_spectrogram of scripts/run_separation.py (stems -> mel-dB features; csrc/stemfeat.hip)
     etude_amd.StemSeparator         <- the separator in front of them (a U-Net mask separator modelled on Spleeter's 5stems; audio -> stems; csrc/separator.hip)
+    etude_amd.BeatTrainer / init_beat_state  (no counterpart: the Beat-Transformer's training -- beat / tempo loss, backward, clipping, AdamW, no dropout; csrc/beat_train.hip)
     etude_amd.SeparatorTrainer / training_segments  (no counterpart: the separator's training -- batch statistics, decoder dropout, L1 loss, backward, Adam; csrc/separator_train.hip)
     etude_amd.SegmentSampler / fit_separator / validate_separator / save_separator_checkpoint / load_separator_checkpoint  (its data and loop: tracks kept on the device,
                                     augmented batches in one launch, epochs, validation, resumable checkpoints; csrc/separator_data.hip)
@@ -47,6 +48,7 @@ __all__ = ["AMTAPC_Extractor", "EtudeDecoder", "EtudeDecoderConfig", "load_etude
            "read_midi_notes", "save_wav", "StemSeparator", "SeparatorConfig", "init_separator_state", "load_separator_state", "structuralize_audio_many", "SeparatorTrainer", "training_segments",
            "SegmentSampler", "fit_separator", "validate_separator", "save_separator_checkpoint", "load_separator_checkpoint",
            "BSSEval", "BSSEvalConfig", "evaluate_separator",
+           "BeatTrainer", "init_beat_state",
            "AudioLoader", "resample_filter", "resampled_len", "read_wav_raw", "align_files_many", "structuralize_files_many"]
 
 
@@ -124,6 +126,9 @@ def __getattr__(name):
     if name in ("BeatAnalyzer", "structuralize_many", "structuralize_stems_many", "structuralize_audio_many", "structuralize_files_many"):
         from . import beat_analyzer
         return getattr(beat_analyzer, name)
+    if name in ("BeatTrainer", "init_beat_state"):
+        from . import beat_train
+        return getattr(beat_train, name)
     if name in ("DecoderTrainer", "cosine_schedule_with_warmup", "init_decoder_state"):
         from . import train
         return getattr(train, name)

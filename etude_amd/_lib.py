@@ -57,6 +57,11 @@ class BeatCfg(_SizedCfg):
                                        "n_mels", "tempo_out", "max_rows")]
 
 
+class BeatTrainCfg(_SizedCfg):
+    _fields_ = [("struct_bytes", C.c_int)] + [(n, C.c_int) for n in ("attn_len", "instr", "ntoken", "dmodel", "nhead", "d_hid", "nlayers", "norm_first",
+                                       "n_mels", "tempo_out", "max_rows", "max_seqs")] + [("tempo_weight", C.c_float), ("dropout", C.c_float)]
+
+
 class BeatTaps(_SizedCfg):
     """etd_debug_beat_taps (include/etude_hip_debug.h): device destinations of the Beat-Transformer engine's stage taps"""
     PTRS = ("c1", "c2", "x3", "c3", "front", "ln1", "qkv", "skip", "x_attn", "tacc", "ln2", "hid", "x_ffn", "iln1", "iqkv", "iao", "ix_attn", "iln2", "ihid", "ix_ffn", "part")
@@ -433,6 +438,26 @@ SIGNATURES = {
     "etd_debug_dtrain_embed_grad": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "etd_debug_dtrain_adamw": (C.c_int, [C.c_void_p] * 4 + [C.c_longlong] + [C.c_double] * 7 + [C.c_longlong, C.c_void_p]),
     "etd_debug_dtrain_sumsq": (C.c_int, [C.c_void_p, C.c_longlong, C.POINTER(C.c_double), C.c_void_p]),
+    "etd_btrain_workspace_bytes": (C.c_longlong, [C.POINTER(BeatTrainCfg)]),
+    "etd_btrain_create": (C.c_int, [C.POINTER(BeatTrainCfg), C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), c_i64_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "etd_btrain_destroy": (None, [C.c_void_p]),
+    "etd_btrain_bytes": (C.c_longlong, [C.c_void_p, C.c_int]),
+    "etd_btrain_check_batch": (C.c_int, [C.POINTER(BeatTrainCfg), C.c_int, c_i64_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "etd_btrain_loss_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_i64_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, c_f32_p, c_i32_p, c_i32_p, C.c_void_p]),
+    "etd_btrain_zero_grad": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "etd_btrain_grad_norm": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
+    "etd_btrain_step": (C.c_int, [C.c_void_p] + [C.c_double] * 6 + [C.POINTER(C.c_double), C.c_void_p]),
+    "etd_btrain_set_step": (C.c_int, [C.c_void_p, C.c_longlong]),
+    "etd_btrain_get_step": (C.c_longlong, [C.c_void_p]),
+    "etd_btrain_read": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "etd_btrain_write": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "etd_debug_btrain_dattn": (C.c_int, [C.c_int, c_i64_p, C.c_int, C.c_int] + [C.c_void_p] * 12),
+    "etd_debug_btrain_iattn": (C.c_int, [C.c_int, c_i64_p, C.c_int] + [C.c_void_p] * 5),
+    "etd_debug_btrain_fold2": (C.c_int, [C.c_int] + [C.c_void_p] * 4),
+    "etd_debug_btrain_conv1_bwd": (C.c_int, [C.c_int, c_i64_p, C.c_int] + [C.c_void_p] * 8),
+    "etd_debug_btrain_bce": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int] + [C.c_void_p] * 3),
+    "etd_debug_btrain_tempo_ce": (C.c_int, [C.c_void_p] * 3 + [C.c_float, C.c_int] + [C.c_void_p] * 3),
+    "etd_debug_btrain_read_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]),
     "etd_debug_decoder_trace_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.POINTER(C.c_int), C.c_void_p]),
 }
 

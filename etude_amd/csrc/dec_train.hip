@@ -523,15 +523,15 @@ static void launch_trope(float* qkv, int nh, int M, const int* pos, const float*
   hipLaunchKernelGGL(k_trope, ew_grid((long long)M * nh * 16), dim3(256), 0, st, qkv, nh, M, pos, tab, sign);
 }
 // mean / rstd (both or neither) and the second output may be NULL
-static void launch_tln_fwd(const float* x, int M, int H, float eps, float* mean, float* rstd, const float* g1, const float* b1, float* y1, const float* g2,
+void launch_tln_fwd(const float* x, int M, int H, float eps, float* mean, float* rstd, const float* g1, const float* b1, float* y1, const float* g2,
                            const float* b2, float* y2, hipStream_t st) {
   hipLaunchKernelGGL(k_tln_fwd, dim3(M), dim3(64), 0, st, x, M, H, eps, mean, rstd, g1, b1, y1, g2, b2, y2);
 }
-static void launch_tln_bwd(const float* dy, const float* x, const float* mean, const float* rstd, const float* g, int M, int H, float* dx, hipStream_t st) {
+void launch_tln_bwd(const float* dy, const float* x, const float* mean, const float* rstd, const float* g, int M, int H, float* dx, hipStream_t st) {
   hipLaunchKernelGGL(k_tln_bwd, dim3(M), dim3(64), 0, st, dy, x, mean, rstd, g, H, dx);
 }
-static void launch_tgelu(const float* x, float* y, long long n, hipStream_t st) { hipLaunchKernelGGL(k_tgelu, ew_grid(n), dim3(256), 0, st, x, y, n); }
-static void launch_tgelu_bwd(const float* x, float* dy, long long n, hipStream_t st) { hipLaunchKernelGGL(k_tgelu_bwd, ew_grid(n), dim3(256), 0, st, x, dy, n); }
+void launch_tgelu(const float* x, float* y, long long n, hipStream_t st) { hipLaunchKernelGGL(k_tgelu, ew_grid(n), dim3(256), 0, st, x, y, n); }
+void launch_tgelu_bwd(const float* x, float* dy, long long n, hipStream_t st) { hipLaunchKernelGGL(k_tgelu_bwd, ew_grid(n), dim3(256), 0, st, x, dy, n); }
 static void launch_tadd3(const float* m, const float* a, const float* h, float* out, long long n, hipStream_t st) {
   hipLaunchKernelGGL(k_tadd3, ew_grid(n), dim3(256), 0, st, m, a, h, out, n);
 }
@@ -546,7 +546,7 @@ static void launch_tce(float* logits, int M, int V, const int* labels, float sca
   hipLaunchKernelGGL(k_tce, dim3(M), dim3(64), 0, st, logits, V, labels, scale, row_loss);
 }
 // mode 0: x, mean, rstd and g1 are not read (NULL)
-static void launch_tcolred(int mode, const float* dy, int ld, int M, int N, const float* x, const float* mean, const float* rstd, float* g0, float* g1,
+void launch_tcolred(int mode, const float* dy, int ld, int M, int N, const float* x, const float* mean, const float* rstd, float* g0, float* g1,
                            hipStream_t st) {
   const dim3 grid((N + 31) / 32), block(256);
   if (mode == 1) hipLaunchKernelGGL(k_tcolred<1>, grid, block, 0, st, dy, ld, M, N, x, mean, rstd, g0, g1);
@@ -559,17 +559,17 @@ static void launch_tembed_grad(const float* src, int ld, int col0, int width, co
 }
 
 // the arguments of k_tadamw for optimizer step `step` (1-based): the step's scalars (train_optim.h) and the hyper-parameters, each a double rounded once
-struct AdamwArgs { float coef, decay, one_minus_beta1, beta2, one_minus_beta2, step_size, bc2_sqrt, eps; };
-static int adamw_check(const char* who, double lr, double beta1, double beta2, double eps, double weight_decay) {
+// (struct AdamwArgs: dec_train.h)
+int adamw_check(const char* who, double lr, double beta1, double beta2, double eps, double weight_decay) {
   if (!(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !(weight_decay >= 0.0))
     ETD_FAIL(ETD_EINVAL, "%s: lr, eps, weight_decay must be >= 0 and the betas in [0, 1)", who);
   return ETD_OK;
 }
-static AdamwArgs adamw_args(double max_norm, double norm, double lr, double beta1, double beta2, double eps, double weight_decay, long long step) {
+AdamwArgs adamw_args(double max_norm, double norm, double lr, double beta1, double beta2, double eps, double weight_decay, long long step) {
   const StepScalars s = step_scalars(max_norm, norm, lr, beta1, beta2, step);
   return {s.coef, (float)(1.0 - lr * weight_decay), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), s.step_size, s.bc2_sqrt, (float)eps};
 }
-static void launch_tadamw(float* p, float* g, float* m, float* v, long long n, const AdamwArgs& a, hipStream_t st) {
+void launch_tadamw(float* p, float* g, float* m, float* v, long long n, const AdamwArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(k_tadamw, ew_grid(n), dim3(256), 0, st, p, g, m, v, n, a.coef, a.decay, a.one_minus_beta1, a.beta2, a.one_minus_beta2, a.step_size, a.bc2_sqrt, a.eps);
 }
 

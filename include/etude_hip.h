@@ -694,6 +694,49 @@ int etd_dtrain_read_grad(etd_dtrain*, const char* name, float* out_host, long lo
 int etd_dtrain_read_moment(etd_dtrain*, const char* name, int second, float* out_host, long long numel, void* stream);
 int etd_dtrain_write_moment(etd_dtrain*, const char* name, int second, const float* in_host, long long numel, void* stream);
 
+/* ------------------------------------------------------------------ Beat-Transformer training (the model of etd_beat with saved activations, this project's beat /
+ * tempo loss, the backward pass for every parameter, gradient accumulation, clip_grad_norm_ and torch.optim.AdamW), all in fp32.  DESIGN.md 4s is the contract.
+ * The trained arithmetic is the inference arithmetic: there is no dropout.  Every dense product is the fp32 GEMM family of the decoder trainer; no floating-point
+ * atomics anywhere: the same call on the same inputs gives the same bits.
+ *   loss = sum_c (1 / n_c) sum_{scored (f, c)} (1 + (pos_weight_c - 1) y) bce_with_logits(z, y)  +  tempo_weight * mean_{songs with a target} -sum_k p_k log_softmax(t)_k */
+typedef struct etd_btrain etd_btrain;
+typedef struct {
+  int struct_bytes;       /* sizeof(etd_btrain_cfg) of the caller: a mismatch is ETD_EINVAL */
+  int attn_len, instr, ntoken, dmodel, nhead, d_hid, nlayers, norm_first, n_mels, tempo_out;      /* the limits of etd_beat_create; tempo_out = 300 */
+  int max_rows;           /* rows (instr x frames) of one etd_btrain_loss_backward call: sizes the workspace, 1 .. 2^17 */
+  int max_seqs;           /* songs of one call, 1 .. 65535 */
+  float tempo_weight;     /* >= 0 */
+  float dropout;          /* must be 0: dropout is not implemented */
+} etd_btrain_cfg;
+/* HOST ONLY: bytes of saved activations and scratch a handle created with this config holds; negative = ETD_EINVAL (the limits of etd_btrain_create) */
+long long etd_btrain_workspace_bytes(const etd_btrain_cfg* cfg);
+/* The state-dict names of etd_beat_create.  Keeps fp32 master weights, gradients and AdamW's exp_avg / exp_avg_sq (zero) on the device.  pos_weight [ntoken] host
+ * (NULL = ones), each finite and > 0.  An unsupported architecture, dropout != 0, a missing weight or a wrong element count is ETD_EINVAL before the device is touched. */
+int etd_btrain_create(const etd_btrain_cfg* cfg, const char* const* names, const float* const* host_ptrs, const int64_t* numels, int n, const float* pos_weight,
+                      etd_btrain** out);
+void etd_btrain_destroy(etd_btrain*);
+/* what = 0: bytes of saved activations and scratch; 1: bytes of weights + gradients + the two moments */
+long long etd_btrain_bytes(const etd_btrain*, int what);
+/* HOST ONLY: the argument checks of etd_btrain_loss_backward (more songs than max_seqs or rows than max_rows, T < 1, a beat target that is neither in [0, 1] nor -1,
+ * a tempo row that is negative, not finite or does not sum to 1 within 1e-5).  n_scored [ntoken] and n_tempo may be NULL. */
+int etd_btrain_check_batch(const etd_btrain_cfg* cfg, int n_seq, const int64_t* T_host, const float* beat_targets, const float* tempo_targets,
+                           const int32_t* has_tempo, int32_t* n_scored, int32_t* n_tempo);
+/* feat_dev: the songs' [instr][T_s][128] fp32 blocks back to back on the device (PRECONDITION as etd_beat_forward: finite, |x| <= 80; the Python mirror checks it).
+ * beat_targets: host [sum T_s][ntoken] in [0, 1], -1 = that (frame, class) cell is not scored.  tempo_targets: host [n_seq][300] distributions, read where
+ * has_tempo[s] != 0 (both may be NULL: no tempo term).  *loss = loss_scale * loss and loss_scale * d loss / d p is ADDED to every parameter's gradient.
+ * *n_scored = scored beat cells.  A call with no scored cell and no tempo target returns *loss = nan and *skipped = 1 and launches nothing.  Synchronous. */
+int etd_btrain_loss_backward(etd_btrain*, const float* feat_dev, int n_seq, const int64_t* T_host, const float* beat_targets, const float* tempo_targets,
+                             const int32_t* has_tempo, float loss_scale, float* loss, int32_t* n_scored, int32_t* skipped, void* stream);
+int etd_btrain_zero_grad(etd_btrain*, void* stream);
+int etd_btrain_grad_norm(etd_btrain*, double* norm, void* stream);
+/* clip_grad_norm_ then one AdamW step, exactly as etd_dtrain_clip_and_step (the same scalars and update kernel).  *norm (may be NULL) = the norm before clipping. */
+int etd_btrain_step(etd_btrain*, double max_norm, double lr, double beta1, double beta2, double eps, double weight_decay, double* norm, void* stream);
+int etd_btrain_set_step(etd_btrain*, long long step);
+long long etd_btrain_get_step(const etd_btrain*);
+/* One tensor by its state-dict name, fp32 to / from the host, in the state dict's own layout.  which: 0 parameter, 1 gradient, 2 exp_avg, 3 exp_avg_sq.  Synchronous. */
+int etd_btrain_read(etd_btrain*, const char* name, int which, float* out_host, long long numel, void* stream);
+int etd_btrain_write(etd_btrain*, const char* name, int which, const float* in_host, long long numel, void* stream);
+
 /* ------------------------------------------------------------------ note renderer (note lists -> mono fp32 waveforms of this project's own piano voice, the audio
  * the alignment features of a generated cover are computed from).  The voice is a contract of this project (restated in fp64 in tests/render_np.py):
  * parity with pretty_midi.synthesize or a SoundFont player is not claimed.  No atomics anywhere: a cover's samples depend on its notes, tuning and rate alone. */

@@ -337,6 +337,30 @@ int etd_bss_debug_project(etd_bss*, const float* ref_dev, int J, int C, long lon
                           double* pa_dev, void* stream);
 int etd_bss_debug_timing(etd_bss*, int on, double* stage_ms5);
 
+/* stage taps of the Beat-Transformer trainer (csrc/beat_train.hip): each kernel with a tap, slice or mask edge on a caller's DEVICE inputs, through the launchers
+ * etd_btrain_loss_backward uses.  Songs are given as for etd_beat_forward (T_host [n_seq], rows = instr x frames, at most 2^17).  Malformed arguments are ETD_EINVAL
+ * before the device is touched.
+ *   dattn      dilated attention of time layer `layer`: qkv [rows][768], Er [8][32][5], xin [rows][256] -> prob [rows][8][5], skip [rows][256], xout = xin + skip; with
+ *              dO [rows][256] also dl [rows][8][5], dqkv [rows][768] (every column written; head 7's key columns zeros), and dEr [8][32][5] += the two-level row sum
+ *              (part: scratch of ceil(rows / 64) x 1280 floats)
+ *   iattn      instrument attention: qkv [rows][768] -> ao [rows][256]; with dao also dqkv [rows][768]
+ *   fold2      conv2's input gradient: dpatch [rows 24][384], c1 [rows][42][32] -> dc1 [rows][42][32]
+ *   conv1_bwd  conv1's dw [32][15] += and db [32] += from feat [rows][128] and dc1 [rows][42][32] (part: scratch of ceil(rows / 16) x 512 floats)
+ *   bce        z, y [frames][ntoken], pos_weight, coef [ntoken] -> cell, dz [frames][ntoken]
+ *   tempo_ce   t, p [n][300], has [n] int32 -> row [n], dt [n][300]
+ *   read_rows  per-row results of the handle's last etd_btrain_loss_backward, to the HOST: what 0 = the gradient of the front end's tokens [rows][256], 1 = the logits
+ *              [frames][ntoken], 2 = the gradient of conv1's pooled output [rows][42][32].  Synchronous. */
+int etd_debug_btrain_dattn(int n_seq, const int64_t* T_host, int instr, int layer, const float* qkv_dev, const float* Er_dev, const float* xin_dev, const float* dO_dev,
+                           float* prob_dev, float* skip_dev, float* xout_dev, float* dl_dev, float* dqkv_dev, float* part_dev, float* dEr_dev, void* stream);
+int etd_debug_btrain_iattn(int n_seq, const int64_t* T_host, int instr, const float* qkv_dev, const float* dao_dev, float* ao_dev, float* dqkv_dev, void* stream);
+int etd_debug_btrain_fold2(int rows, const float* dpatch_dev, const float* c1_dev, float* dc1_dev, void* stream);
+int etd_debug_btrain_conv1_bwd(int n_seq, const int64_t* T_host, int instr, const float* feat_dev, const float* dc1_dev, const float* w_dev, const float* b_dev,
+                               float* part_dev, float* dw_dev, float* db_dev, void* stream);
+int etd_debug_btrain_bce(const float* z_dev, const float* y_dev, const float* pos_weight_dev, const float* coef_dev, int frames, int ntoken, float* cell_dev, float* dz_dev,
+                         void* stream);
+int etd_debug_btrain_tempo_ce(const float* t_dev, const float* p_dev, const int32_t* has_dev, float coef, int n, float* row_dev, float* dt_dev, void* stream);
+int etd_debug_btrain_read_rows(etd_btrain*, int what, float* out_host, long long numel, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
