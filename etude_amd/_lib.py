@@ -458,6 +458,16 @@ SIGNATURES = {
     "etd_debug_btrain_bce": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int] + [C.c_void_p] * 3),
     "etd_debug_btrain_tempo_ce": (C.c_int, [C.c_void_p] * 3 + [C.c_float, C.c_int] + [C.c_void_p] * 3),
     "etd_debug_btrain_read_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "etd_debug_btrain_front_fwd": (C.c_int, [C.c_int, C.c_int, c_i64_p, C.c_int] + [C.c_void_p] * 5),
+    "etd_debug_btrain_front_bwd": (C.c_int, [C.c_int, C.c_int, c_i64_p, C.c_int] + [C.c_void_p] * 4),
+    "etd_debug_btrain_repack": (C.c_int, [C.c_int] * 4 + [C.c_void_p] * 3),
+    "etd_debug_btrain_colsum": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 3),
+    "etd_debug_btrain_slice_sum": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "etd_debug_btrain_means": (C.c_int, [C.c_int, C.c_int, c_i64_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "etd_debug_btrain_relu": (C.c_int, [C.c_void_p, C.c_longlong] + [C.c_void_p] * 3),
+    "etd_debug_btrain_conv_wgrad": (C.c_int, [C.c_int] * 3 + [C.c_void_p] * 5),
+    "etd_debug_btrain_ffn_bwd": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 8),
+    "etd_debug_btrain_proj_bwd": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 8),
     "etd_debug_decoder_trace_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.POINTER(C.c_int), C.c_void_p]),
 }
 

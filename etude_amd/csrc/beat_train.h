@@ -1,7 +1,8 @@
 // Training engine of the Beat-Transformer (etd_btrain_*): the model of beat.hip with saved activations, this project's beat / tempo loss, the backward pass for
 // every parameter, global-norm clipping and AdamW, all in fp32.  Dense products are launch_tgemm of dec_train.h; LayerNorm, GELU, the column
-// reductions, the gradient norm and the AdamW update are the decoder trainer's kernels.  These are the launchers of the kernels that are new here; the ones with a
-// slice or tap edge are also reachable on their own through include/etude_hip_debug.h.
+// reductions, the gradient norm and the AdamW update are the decoder trainer's kernels.  These are the launchers of the kernels that are new here; every one is
+// also reachable on its own through include/etude_hip_debug.h (etd_debug_btrain_*: dattn, iattn, fold2, conv1_bwd, bce, tempo_ce, front_fwd, front_bwd, repack, colsum,
+// slice_sum, means, relu, conv_wgrad, and the two host pipelines ffn_bwd and proj_bwd on a handle's scratch).
 // Nothing here uses a floating-point atomic: every sum runs in an order fixed by the shapes alone.
 #pragma once
 #include "beat.h"
@@ -36,3 +37,28 @@ int launch_bt_bce(const float* z, const float* y, const float* pos_weight, const
 int launch_bt_tempo_ce(const float* t, const float* p, const int* has, float coef, int n, int n_out, float* row, float* dt, hipStream_t st);
 // out[c] += sum over the M rows of dy[r][c] (row stride ld), c < N: slices of BT_CS_ROWS rows, then an ordered sum (part: [ceil(M / BT_CS_ROWS)][N] scratch)
 int launch_bt_colsum(const float* dy, int ld, int M, int N, float* part, float* out, hipStream_t st);
+// ---- the conv front end.  conv1 + pool + ReLU: feat [rows][128], w [32][15], b [32] -> c1 [rows][42][32]; conv2's patches x2 [rows 24][384]; conv3's patches through
+// pool2 + ReLU: c2 [rows][24][64] -> x3 [rows 3][1152] (0 outside the song); pool3 + ReLU: c3 [rows][3][256] -> x [rows][256]
+int launch_bt_conv1(const float* feat, const BtSongs& S, const float* w, const float* b, float* c1, hipStream_t st);
+int launch_bt_patch2(const float* c1, int rows, float* x2, hipStream_t st);
+int launch_bt_patch3(const float* c2, const BtSongs& S, float* x3, hipStream_t st);
+int launch_bt_pool3(const float* c3, int rows, float* x, hipStream_t st);
+// a conv weight between the state dict's [co][ci][kk] and the GEMM's [co][kk][ci].  dir 0: packed = native; dir 1: native += packed
+int launch_bt_repack(float* native, float* packed, int co_n, int ci_n, int kk_n, int dir, hipStream_t st);
+// through pool + ReLU: the gradient goes to the first maximal entry of a triple, nowhere when the maximum is not positive.  patch3_bwd first gathers dx3 [rows 3][1152]
+// per pooled cell (kt ascending, then c ascending)
+int launch_bt_pool3_bwd(const float* c3, const float* dx, int rows, float* dc3, hipStream_t st);
+int launch_bt_patch3_bwd(const float* c2, const float* dx3, const BtSongs& S, float* dc2, hipStream_t st);
+// out[e] += sum over the slices, 16 at a time in order, then the groups in order, of part[slice][e], e < width
+int launch_bt_slice_sum(const float* part, int n_slices, int width, float* out, hipStream_t st);
+// dw [M][N] = dY^T X over K rows (dY [K][M], X [K][N]) in segments of BT_SEG_ROWS rows (seg: [ceil(K / BT_SEG_ROWS)][M][N] scratch), then the ordered sum; dw is overwritten
+int launch_bt_conv_wgrad(int M, int N, int K, const float* dY, const float* X, float* seg, float* dw, hipStream_t st);
+// the instrument means and the tempo mean with their backward passes (frames are (song, t); see the kernels)
+int launch_bt_skipacc(const float* skip, const BtSongs& S, int first_layer, float* tacc, hipStream_t st);
+int launch_bt_dskip(const float* dx, const float* dtf, const BtSongs& S, float* dsk, hipStream_t st);
+int launch_bt_hmean(const float* x, const BtSongs& S, float* hm, hipStream_t st);
+int launch_bt_hmean_bwd(const float* x, const float* dhm, const BtSongs& S, float* dx, hipStream_t st);
+int launch_bt_tmean(const float* tacc, const BtSongs& S, float* tm, hipStream_t st);
+int launch_bt_tmean_bwd(const float* tacc, const float* dtm, const BtSongs& S, float* dtf, hipStream_t st);
+int launch_bt_relu(const float* x, float* y, long long n, hipStream_t st);
+int launch_bt_relu_bwd(const float* x, float* dy, long long n, hipStream_t st);      // dy = x > 0 ? dy : 0

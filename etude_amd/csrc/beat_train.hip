@@ -595,13 +595,78 @@ __global__ __launch_bounds__(64) void k_bt_tempo_ce(const float* __restrict__ t,
 // ================================================================================================ launchers
 static inline dim3 bt_grid(long long n, int block = 256) { return dim3((unsigned)((n + block - 1) / block)); }
 
+#define BT_LAUNCHED() do { HIP_TRY(hipGetLastError()); return ETD_OK; } while (0)
+// ---- the front end, the means and the element kernels: one launcher per kernel, which the engine and the taps of include/etude_hip_debug.h both call
+int launch_bt_conv1(const float* feat, const BtSongs& S, const float* w, const float* b, float* c1, hipStream_t st) {
+  hipLaunchKernelGGL(k_bt_conv1, bt_grid((long long)S.rows * BEAT_W1 * BEAT_C1), dim3(256), 0, st, feat, S, w, b, c1);
+  BT_LAUNCHED();
+}
+int launch_bt_patch2(const float* c1, int rows, float* x2, hipStream_t st) {
+  hipLaunchKernelGGL(k_bt_patch2, bt_grid((long long)rows * BT_C2_COLS * BEAT_K2), dim3(256), 0, st, c1, rows, x2);
+  BT_LAUNCHED();
+}
+int launch_bt_patch3(const float* c2, const BtSongs& S, float* x3, hipStream_t st) {
+  hipLaunchKernelGGL(k_bt_patch3, bt_grid((long long)S.rows * 3 * BEAT_K3), dim3(256), 0, st, c2, S, x3);
+  BT_LAUNCHED();
+}
+int launch_bt_pool3(const float* c3, int rows, float* x, hipStream_t st) {
+  hipLaunchKernelGGL(k_bt_pool3, bt_grid((long long)rows * BEAT_DMODEL), dim3(256), 0, st, c3, rows, x);
+  BT_LAUNCHED();
+}
+int launch_bt_repack(float* native, float* packed, int co_n, int ci_n, int kk_n, int dir, hipStream_t st) {
+  hipLaunchKernelGGL(k_bt_repack, bt_grid((long long)co_n * ci_n * kk_n), dim3(256), 0, st, native, packed, co_n, ci_n, kk_n, dir);
+  BT_LAUNCHED();
+}
+int launch_bt_pool3_bwd(const float* c3, const float* dx, int rows, float* dc3, hipStream_t st) {
+  hipLaunchKernelGGL(k_bt_pool3_bwd, bt_grid((long long)rows * BEAT_DMODEL), dim3(256), 0, st, c3, dx, rows, dc3);
+  BT_LAUNCHED();
+}
+int launch_bt_patch3_bwd(const float* c2, const float* dx3, const BtSongs& S, float* dc2, hipStream_t st) {
+  hipLaunchKernelGGL(k_bt_patch3_bwd, bt_grid((long long)S.rows * 8 * BEAT_C2), dim3(256), 0, st, c2, dx3, S, dc2);
+  BT_LAUNCHED();
+}
+int launch_bt_slice_sum(const float* part, int n_slices, int width, float* out, hipStream_t st) {
+  hipLaunchKernelGGL(k_bt_slice_sum, bt_grid(width), dim3(256), 0, st, part, n_slices, width, width, out, (float*)nullptr, 0);
+  BT_LAUNCHED();
+}
+int launch_bt_skipacc(const float* skip, const BtSongs& S, int first_layer, float* tacc, hipStream_t st) {
+  hipLaunchKernelGGL(k_bt_skipacc, bt_grid((long long)S.frames * 256), dim3(256), 0, st, skip, S, first_layer, tacc);
+  BT_LAUNCHED();
+}
+int launch_bt_dskip(const float* dx, const float* dtf, const BtSongs& S, float* dsk, hipStream_t st) {
+  hipLaunchKernelGGL(k_bt_dskip, bt_grid((long long)S.rows * 256), dim3(256), 0, st, dx, dtf, S, dsk);
+  BT_LAUNCHED();
+}
+int launch_bt_hmean(const float* x, const BtSongs& S, float* hm, hipStream_t st) {
+  hipLaunchKernelGGL(k_bt_hmean, bt_grid((long long)S.frames * 256), dim3(256), 0, st, x, S, hm);
+  BT_LAUNCHED();
+}
+int launch_bt_hmean_bwd(const float* x, const float* dhm, const BtSongs& S, float* dx, hipStream_t st) {
+  hipLaunchKernelGGL(k_bt_hmean_bwd, bt_grid((long long)S.rows * 256), dim3(256), 0, st, x, dhm, S, dx);
+  BT_LAUNCHED();
+}
+int launch_bt_tmean(const float* tacc, const BtSongs& S, float* tm, hipStream_t st) {
+  hipLaunchKernelGGL(k_bt_tmean, dim3(S.n), dim3(256), 0, st, tacc, S, tm);
+  BT_LAUNCHED();
+}
+int launch_bt_tmean_bwd(const float* tacc, const float* dtm, const BtSongs& S, float* dtf, hipStream_t st) {
+  hipLaunchKernelGGL(k_bt_tmean_bwd, bt_grid((long long)S.frames * 256), dim3(256), 0, st, tacc, dtm, S, dtf);
+  BT_LAUNCHED();
+}
+int launch_bt_relu(const float* x, float* y, long long n, hipStream_t st) {
+  hipLaunchKernelGGL(k_bt_relu, bt_grid(n), dim3(256), 0, st, x, y, n);
+  BT_LAUNCHED();
+}
+int launch_bt_relu_bwd(const float* x, float* dy, long long n, hipStream_t st) {
+  hipLaunchKernelGGL(k_bt_relu_bwd, bt_grid(n), dim3(256), 0, st, x, dy, n);
+  BT_LAUNCHED();
+}
+
 // out[c] += sum over the M rows of dy[r][c] (row stride ld), c < N; part: [ceil(M / BT_CS_ROWS)][N] scratch
 int launch_bt_colsum(const float* dy, int ld, int M, int N, float* part, float* out, hipStream_t st) {
   const int ns = (M + BT_CS_ROWS - 1) / BT_CS_ROWS;
   hipLaunchKernelGGL(k_bt_colsum_part, dim3((N + 31) / 32, ns), dim3(256), 0, st, dy, ld, M, N, part);
-  hipLaunchKernelGGL(k_bt_slice_sum, bt_grid(N), dim3(256), 0, st, part, ns, N, N, out, (float*)nullptr, 0);
-  HIP_TRY(hipGetLastError());
-  return ETD_OK;
+  return launch_bt_slice_sum(part, ns, N, out, st);
 }
 int launch_bt_dattn_fwd(const float* qkv, const BtSongs& S, const float* Er, int dil, const float* xin, float* prob, float* skip, float* xout, hipStream_t st) {
   hipLaunchKernelGGL(k_bt_dattn, bt_grid((long long)S.rows * 8), dim3(256), 0, st, qkv, S, Er, dil, xin, prob, skip, xout);
@@ -614,9 +679,7 @@ int launch_bt_dattn_bwd(const float* qkv, const float* prob, const float* dO, co
   hipLaunchKernelGGL(k_bt_dattn_dkv, bt_grid((long long)S.rows * 8), dim3(256), 0, st, qkv, prob, dl, dO, S, dil, dqkv);
   const int ns = (S.rows + BT_ER_ROWS - 1) / BT_ER_ROWS;
   hipLaunchKernelGGL(k_bt_der_part, dim3(ns), dim3(256), 0, st, qkv, dl, S.rows, part);
-  hipLaunchKernelGGL(k_bt_slice_sum, bt_grid(1280), dim3(256), 0, st, part, ns, 1280, 1280, dEr, (float*)nullptr, 0);
-  HIP_TRY(hipGetLastError());
-  return ETD_OK;
+  return launch_bt_slice_sum(part, ns, 1280, dEr, st);
 }
 int launch_bt_iattn_fwd(const float* qkv, const BtSongs& S, float* ao, hipStream_t st) {
   hipLaunchKernelGGL(k_bt_iattn, bt_grid((long long)S.frames * 8, 64), dim3(64), 0, st, qkv, S, ao);
@@ -894,18 +957,18 @@ extern "C" int etd_btrain_check_batch(const etd_btrain_cfg* cfg, int n_seq, cons
 #define BT_GEMM(...) ETD_TRY(launch_tgemm(__VA_ARGS__))
 
 // one feed-forward sublayer's backward (act 0: GELU, 1: ReLU): dx is the gradient of the sublayer's output x + W2 act(W1 LN(x) + b1) + b2 on entry, of x on exit
-static int ffn_backward(etd_btrain* d, int R, int act, const float* x, const float* mean, const float* rstd, const float* pre, size_t nw, size_t nb, size_t l1w, size_t l1b,
-                        size_t l2w, size_t l2b, hipStream_t st) {
+// P / G: the buffers the six offsets (LayerNorm gain, bias, linear1, linear2) index -- the engine's flat parameters and accumulated gradients, or a tap's own
+static int ffn_backward(etd_btrain* d, int R, int act, const float* x, const float* mean, const float* rstd, const float* pre, const float* P, float* G, float* dx, size_t nw,
+                        size_t nb, size_t l1w, size_t l1b, size_t l2w, size_t l2b, hipStream_t st) {
   const int H = d->cfg.d_hid;
   const long long RH = (long long)R * H;
-  float *P = d->P, *G = d->G, *dx = d->dx;
   if (act == 0) launch_tgelu(pre, d->wI, RH, st);
-  else hipLaunchKernelGGL(k_bt_relu, bt_grid(RH), dim3(256), 0, st, pre, d->wI, RH);
+  else ETD_TRY(launch_bt_relu(pre, d->wI, RH, st));
   BT_GEMM(ETD_TG_TN, 256, H, R, dx, 256, d->wI, H, nullptr, G + l2w, H, true, st);
   ETD_TRY(launch_bt_colsum(dx, 256, R, 256, d->cpart, G + l2b, st));
   BT_GEMM(ETD_TG_NN, R, H, 256, dx, 256, P + l2w, H, nullptr, d->wI, H, false, st);
   if (act == 0) launch_tgelu_bwd(pre, d->wI, RH, st);
-  else hipLaunchKernelGGL(k_bt_relu_bwd, bt_grid(RH), dim3(256), 0, st, pre, d->wI, RH);
+  else ETD_TRY(launch_bt_relu_bwd(pre, d->wI, RH, st));
   launch_tln_fwd(x, R, 256, 1e-5f, nullptr, nullptr, P + nw, P + nb, d->tx, nullptr, nullptr, nullptr, st);
   BT_GEMM(ETD_TG_TN, H, 256, R, d->wI, H, d->tx, 256, nullptr, G + l1w, 256, true, st);
   ETD_TRY(launch_bt_colsum(d->wI, H, R, H, d->cpart, G + l1b, st));
@@ -916,18 +979,18 @@ static int ffn_backward(etd_btrain* d, int R, int act, const float* x, const flo
   return ETD_OK;
 }
 // a fused q | k | v projection's backward from dqkv: its weight and bias, the LayerNorm in front of it, and dx += the LayerNorm's input gradient
-static int proj_backward(etd_btrain* d, int R, const float* x, const float* mean, const float* rstd, size_t nw, size_t nb, size_t w, size_t b, hipStream_t st) {
-  float *P = d->P, *G = d->G;
+static int proj_backward(etd_btrain* d, int R, const float* x, const float* mean, const float* rstd, const float* dqkv, const float* P, float* G, float* dx, size_t nw,
+                         size_t nb, size_t w, size_t b, hipStream_t st) {
   launch_tln_fwd(x, R, 256, 1e-5f, nullptr, nullptr, P + nw, P + nb, d->tx, nullptr, nullptr, nullptr, st);
-  BT_GEMM(ETD_TG_TN, 768, 256, R, d->dqkv, 768, d->tx, 256, nullptr, G + w, 256, true, st);
+  BT_GEMM(ETD_TG_TN, 768, 256, R, dqkv, 768, d->tx, 256, nullptr, G + w, 256, true, st);
   // The query and value biases only.  A key bias (a time layer's or an instrument layer's) adds the same q . b to every logit of a query, which the softmax cancels: its
   // gradient is identically zero, and summing dk over the rows would only leave rounding residue there (which AdamW's normalisation would turn into steps of the size of
   // lr).  It is left at exactly zero (tests/test_gpu_beat_train.py::test_key_bias_gradients_are_exactly_zero).
-  ETD_TRY(launch_bt_colsum(d->dqkv, 768, R, 256, d->cpart, G + b, st));
-  ETD_TRY(launch_bt_colsum(d->dqkv + 512, 768, R, 256, d->cpart, G + b + 512, st));
-  BT_GEMM(ETD_TG_NN, R, 256, 768, d->dqkv, 768, P + w, 256, nullptr, d->dxn, 256, false, st);
+  ETD_TRY(launch_bt_colsum(dqkv, 768, R, 256, d->cpart, G + b, st));
+  ETD_TRY(launch_bt_colsum(dqkv + 512, 768, R, 256, d->cpart, G + b + 512, st));
+  BT_GEMM(ETD_TG_NN, R, 256, 768, dqkv, 768, P + w, 256, nullptr, d->dxn, 256, false, st);
   launch_tcolred(1, d->dxn, 256, R, 256, x, mean, rstd, G + nb, G + nw, st);
-  launch_tln_bwd(d->dxn, x, mean, rstd, P + nw, R, 256, d->dx, st);
+  launch_tln_bwd(d->dxn, x, mean, rstd, P + nw, R, 256, dx, st);
   HIP_TRY(hipGetLastError());
   return ETD_OK;
 }
@@ -935,7 +998,7 @@ static int proj_backward(etd_btrain* d, int R, const float* x, const float* mean
 // A conv layer's weight gradient: the reduction runs over 3 (conv3) or 24 (conv2) rows per token, too long for one fp32 chain per element at the bound of
 // DESIGN.md 4s.  It runs in segments of BT_SEG_ROWS rows: each segment's dY^T X goes to a slice of `seg` of their own, k_bt_slice_sum adds the slices
 // in order.  dw [M][N] is overwritten (the packed weight's gradient of this call).
-static int conv_wgrad(int M, int N, int K, const float* dY, const float* X, float* seg, float* dw, hipStream_t st) {
+int launch_bt_conv_wgrad(int M, int N, int K, const float* dY, const float* X, float* seg, float* dw, hipStream_t st) {
   const int ns = (K + BT_SEG_ROWS - 1) / BT_SEG_ROWS;
   const long long width = (long long)M * N;
   for (int q = 0; q < ns; ++q) {
@@ -943,9 +1006,7 @@ static int conv_wgrad(int M, int N, int K, const float* dY, const float* X, floa
     BT_GEMM(ETD_TG_TN, M, N, kn, dY + (long long)k0 * M, M, X + (long long)k0 * N, N, nullptr, seg + q * width, N, false, st);
   }
   HIP_TRY(hipMemsetAsync(dw, 0, (size_t)width * 4, st));
-  hipLaunchKernelGGL(k_bt_slice_sum, bt_grid(width), dim3(256), 0, st, seg, ns, (int)width, (int)width, dw, (float*)nullptr, 0);
-  HIP_TRY(hipGetLastError());
-  return ETD_OK;
+  return launch_bt_slice_sum(seg, ns, (int)width, dw, st);
 }
 
 extern "C" int etd_btrain_loss_backward(etd_btrain* d, const float* feat_dev, int n_seq, const int64_t* T_host, const float* beat_targets, const float* tempo_targets,
@@ -996,15 +1057,15 @@ extern "C" int etd_btrain_loss_backward(etd_btrain* d, const float* feat_dev, in
   // ================================================================ forward
   {
     ProfScope ps("btrain_forward", st);
-    hipLaunchKernelGGL(k_bt_repack, bt_grid(64 * BEAT_K2), dim3(256), 0, st, P + d->c2w, d->w2p, 64, 32, 12, 0);
-    hipLaunchKernelGGL(k_bt_repack, bt_grid(256 * BEAT_K3), dim3(256), 0, st, P + d->c3w, d->w3p, 256, 64, 18, 0);
-    hipLaunchKernelGGL(k_bt_conv1, bt_grid((long long)R * BEAT_W1 * BEAT_C1), dim3(256), 0, st, feat_dev, S, P + d->c1w, P + d->c1b, d->c1);
-    hipLaunchKernelGGL(k_bt_patch2, bt_grid((long long)R * BT_C2_COLS * BEAT_K2), dim3(256), 0, st, d->c1, R, d->x2);
+    ETD_TRY(launch_bt_repack(P + d->c2w, d->w2p, 64, 32, 12, 0, st));
+    ETD_TRY(launch_bt_repack(P + d->c3w, d->w3p, 256, 64, 18, 0, st));
+    ETD_TRY(launch_bt_conv1(feat_dev, S, P + d->c1w, P + d->c1b, d->c1, st));
+    ETD_TRY(launch_bt_patch2(d->c1, R, d->x2, st));
     BT_GEMM(ETD_TG_NT, R * BT_C2_COLS, 64, BEAT_K2, d->x2, BEAT_K2, d->w2p, BEAT_K2, P + d->c2b, d->c2o, 64, false, st);
-    hipLaunchKernelGGL(k_bt_patch3, bt_grid((long long)R * 3 * BEAT_K3), dim3(256), 0, st, d->c2o, S, d->x3);
+    ETD_TRY(launch_bt_patch3(d->c2o, S, d->x3, st));
     BT_GEMM(ETD_TG_NT, R * 3, 256, BEAT_K3, d->x3, BEAT_K3, d->w3p, BEAT_K3, P + d->c3b, d->c3o, 256, false, st);
     float* x0 = d->st[0].xin;
-    hipLaunchKernelGGL(k_bt_pool3, bt_grid(RD), dim3(256), 0, st, d->c3o, R, x0);
+    ETD_TRY(launch_bt_pool3(d->c3o, R, x0, st));
     HIP_TRY(hipGetLastError());
     int il = 0;
     for (int l = 0; l < L; ++l) {
@@ -1015,7 +1076,7 @@ extern "C" int etd_btrain_loss_backward(etd_btrain* d, const float* feat_dev, in
       launch_tln_fwd(a.xin, R, 256, 1e-5f, a.m1, a.r1, P + y.n1w, P + y.n1b, d->tx, nullptr, nullptr, nullptr, st);
       BT_GEMM(ETD_TG_NT, R, 768, 256, d->tx, 256, P + y.qkv_w, 256, P + y.qkv_b, a.qkv, 768, false, st);
       ETD_TRY(launch_bt_dattn_fwd(a.qkv, S, P + y.Er, 1 << l, a.xin, a.prob, d->dsk, a.xat, st));
-      hipLaunchKernelGGL(k_bt_skipacc, bt_grid((long long)F * 256), dim3(256), 0, st, d->dsk, S, l == 0 ? 1 : 0, d->tacc);
+      ETD_TRY(launch_bt_skipacc(d->dsk, S, l == 0 ? 1 : 0, d->tacc, st));
       launch_tln_fwd(a.xat, R, 256, 1e-5f, a.m2, a.r2, P + y.n2w, P + y.n2b, d->tx, nullptr, nullptr, nullptr, st);
       BT_GEMM(ETD_TG_NT, R, H, 256, d->tx, 256, P + y.l1w, 256, P + y.l1b, a.pre, H, false, st);
       launch_tgelu(a.pre, d->wI, RH, st);
@@ -1032,15 +1093,15 @@ extern "C" int etd_btrain_loss_backward(etd_btrain* d, const float* feat_dev, in
         BT_GEMM(ETD_TG_NT, R, 256, 256, b.ao, 256, P + z.out_w, 256, P + z.out_b, b.xat, 256, true, st);
         launch_tln_fwd(b.xat, R, 256, 1e-5f, b.m2, b.r2, P + z.n2w, P + z.n2b, d->tx, nullptr, nullptr, nullptr, st);
         BT_GEMM(ETD_TG_NT, R, H, 256, d->tx, 256, P + z.l1w, 256, P + z.l1b, b.pre, H, false, st);
-        hipLaunchKernelGGL(k_bt_relu, bt_grid(RH), dim3(256), 0, st, b.pre, d->wI, RH);
+        ETD_TRY(launch_bt_relu(b.pre, d->wI, RH, st));
         ETD_TRY(copy(xn2, b.xat, RD));
         BT_GEMM(ETD_TG_NT, R, 256, H, d->wI, H, P + z.l2w, H, P + z.l2b, xn2, 256, true, st);
         ++il;
       }
     }
-    hipLaunchKernelGGL(k_bt_hmean, bt_grid((long long)F * 256), dim3(256), 0, st, d->xL, S, d->hm);
+    ETD_TRY(launch_bt_hmean(d->xL, S, d->hm, st));
     BT_GEMM(ETD_TG_NT, F, nt, 256, d->hm, 256, P + d->ow, 256, P + d->ob, d->logits, nt, false, st);
-    hipLaunchKernelGGL(k_bt_tmean, dim3(n_seq), dim3(256), 0, st, d->tacc, S, d->tm);
+    ETD_TRY(launch_bt_tmean(d->tacc, S, d->tm, st));
     BT_GEMM(ETD_TG_NT, n_seq, BT_TEMPO, 256, d->tm, 256, P + d->tw, 256, P + d->tb, d->tlog, BT_TEMPO, false, st);
     ETD_TRY(launch_bt_bce(d->logits, d->ytgt, d->fl, d->fl + nt, F, nt, d->cell, d->dz, st));
     if (ntempo) ETD_TRY(launch_bt_tempo_ce(d->tlog, d->ttgt, d_has, tcoef, n_seq, BT_TEMPO, d->trow, d->dt, st));
@@ -1054,7 +1115,7 @@ extern "C" int etd_btrain_loss_backward(etd_btrain* d, const float* feat_dev, in
       BT_GEMM(ETD_TG_TN, BT_TEMPO, 256, n_seq, d->dt, BT_TEMPO, d->tm, 256, nullptr, G + d->tw, 256, true, st);
       ETD_TRY(launch_bt_colsum(d->dt, BT_TEMPO, n_seq, BT_TEMPO, d->cpart, G + d->tb, st));
       BT_GEMM(ETD_TG_NN, n_seq, 256, BT_TEMPO, d->dt, BT_TEMPO, P + d->tw, 256, nullptr, d->dtm, 256, false, st);
-      hipLaunchKernelGGL(k_bt_tmean_bwd, bt_grid((long long)F * 256), dim3(256), 0, st, d->tacc, d->dtm, S, d->dtf);
+      ETD_TRY(launch_bt_tmean_bwd(d->tacc, d->dtm, S, d->dtf, st));
     } else {
       HIP_TRY(hipMemsetAsync(d->dtf, 0, (size_t)F * 256 * 4, st));
     }
@@ -1062,7 +1123,7 @@ extern "C" int etd_btrain_loss_backward(etd_btrain* d, const float* feat_dev, in
     BT_GEMM(ETD_TG_TN, nt, 256, F, d->dz, nt, d->hm, 256, nullptr, G + d->ow, 256, true, st);
     ETD_TRY(launch_bt_colsum(d->dz, nt, F, nt, d->cpart, G + d->ob, st));
     BT_GEMM(ETD_TG_NN, F, 256, nt, d->dz, nt, P + d->ow, 256, nullptr, d->dhm, 256, false, st);
-    hipLaunchKernelGGL(k_bt_hmean_bwd, bt_grid(RD), dim3(256), 0, st, d->xL, d->dhm, S, d->dx);
+    ETD_TRY(launch_bt_hmean_bwd(d->xL, d->dhm, S, d->dx, st));
     HIP_TRY(hipGetLastError());
     int il = (int)d->il.size();
     for (int l = L - 1; l >= 0; --l) {
@@ -1070,33 +1131,33 @@ extern "C" int etd_btrain_loss_backward(etd_btrain* d, const float* feat_dev, in
         --il;
         const BInstr& z = d->il[il];
         const BSavedI& b = d->si[il];
-        ETD_TRY(ffn_backward(d, R, 1, b.xat, b.m2, b.r2, b.pre, z.n2w, z.n2b, z.l1w, z.l1b, z.l2w, z.l2b, st));
+        ETD_TRY(ffn_backward(d, R, 1, b.xat, b.m2, b.r2, b.pre, P, G, d->dx, z.n2w, z.n2b, z.l1w, z.l1b, z.l2w, z.l2b, st));
         BT_GEMM(ETD_TG_TN, 256, 256, R, d->dx, 256, b.ao, 256, nullptr, G + z.out_w, 256, true, st);
         ETD_TRY(launch_bt_colsum(d->dx, 256, R, 256, d->cpart, G + z.out_b, st));
         BT_GEMM(ETD_TG_NN, R, 256, 256, d->dx, 256, P + z.out_w, 256, nullptr, d->dsk, 256, false, st);
         ETD_TRY(launch_bt_iattn_bwd(b.qkv, d->dsk, S, d->dqkv, st));
-        ETD_TRY(proj_backward(d, R, b.xin, b.m1, b.r1, z.n1w, z.n1b, z.in_w, z.in_b, st));
+        ETD_TRY(proj_backward(d, R, b.xin, b.m1, b.r1, d->dqkv, P, G, d->dx, z.n1w, z.n1b, z.in_w, z.in_b, st));
       }
       const BTime& y = d->tl[l];
       const BSavedT& a = d->st[l];
-      ETD_TRY(ffn_backward(d, R, 0, a.xat, a.m2, a.r2, a.pre, y.n2w, y.n2b, y.l1w, y.l1b, y.l2w, y.l2b, st));
-      hipLaunchKernelGGL(k_bt_dskip, bt_grid(RD), dim3(256), 0, st, d->dx, d->dtf, S, d->dsk);
+      ETD_TRY(ffn_backward(d, R, 0, a.xat, a.m2, a.r2, a.pre, P, G, d->dx, y.n2w, y.n2b, y.l1w, y.l1b, y.l2w, y.l2b, st));
+      ETD_TRY(launch_bt_dskip(d->dx, d->dtf, S, d->dsk, st));
       ETD_TRY(launch_bt_dattn_bwd(a.qkv, a.prob, d->dsk, S, P + y.Er, 1 << l, d->dl, d->dqkv, d->part, G + y.Er, st));
-      ETD_TRY(proj_backward(d, R, a.xin, a.m1, a.r1, y.n1w, y.n1b, y.qkv_w, y.qkv_b, st));
+      ETD_TRY(proj_backward(d, R, a.xin, a.m1, a.r1, d->dqkv, P, G, d->dx, y.n1w, y.n1b, y.qkv_w, y.qkv_b, st));
     }
     // ---- conv front end: dx is the gradient of the tokens
     float* dc3 = d->dqkv;                              // [3 R][256] = [R][768]
-    hipLaunchKernelGGL(k_bt_pool3_bwd, bt_grid(RD), dim3(256), 0, st, d->c3o, d->dx, R, dc3);
-    ETD_TRY(conv_wgrad(256, BEAT_K3, 3 * R, dc3, d->x3, d->seg, d->dw3p, st));
+    ETD_TRY(launch_bt_pool3_bwd(d->c3o, d->dx, R, dc3, st));
+    ETD_TRY(launch_bt_conv_wgrad(256, BEAT_K3, 3 * R, dc3, d->x3, d->seg, d->dw3p, st));
     ETD_TRY(launch_bt_colsum(dc3, 256, 3 * R, 256, d->cpart, G + d->c3b, st));
     BT_GEMM(ETD_TG_NN, 3 * R, BEAT_K3, 256, dc3, 256, d->w3p, BEAT_K3, nullptr, d->big, BEAT_K3, false, st);
-    hipLaunchKernelGGL(k_bt_repack, bt_grid(256 * BEAT_K3), dim3(256), 0, st, G + d->c3w, d->dw3p, 256, 64, 18, 1);
+    ETD_TRY(launch_bt_repack(G + d->c3w, d->dw3p, 256, 64, 18, 1, st));
     float* dc2 = d->x3;                                // [24 R][64]: x3 [3 R][1152] has been read for the last time
-    hipLaunchKernelGGL(k_bt_patch3_bwd, bt_grid((long long)R * 8 * BEAT_C2), dim3(256), 0, st, d->c2o, d->big, S, dc2);
-    ETD_TRY(conv_wgrad(64, BEAT_K2, BT_C2_COLS * R, dc2, d->x2, d->seg, d->dw2p, st));
+    ETD_TRY(launch_bt_patch3_bwd(d->c2o, d->big, S, dc2, st));
+    ETD_TRY(launch_bt_conv_wgrad(64, BEAT_K2, BT_C2_COLS * R, dc2, d->x2, d->seg, d->dw2p, st));
     ETD_TRY(launch_bt_colsum(dc2, 64, BT_C2_COLS * R, 64, d->cpart, G + d->c2b, st));
     BT_GEMM(ETD_TG_NN, BT_C2_COLS * R, BEAT_K2, 64, dc2, 64, d->w2p, BEAT_K2, nullptr, d->big, BEAT_K2, false, st);
-    hipLaunchKernelGGL(k_bt_repack, bt_grid(64 * BEAT_K2), dim3(256), 0, st, G + d->c2w, d->dw2p, 64, 32, 12, 1);
+    ETD_TRY(launch_bt_repack(G + d->c2w, d->dw2p, 64, 32, 12, 1, st));
     float* dc1 = d->x2;                                // [R][42][32]: the patches have been read for the last time
     ETD_TRY(launch_bt_fold2(d->big, d->c1, R, dc1, st));
     ETD_TRY(launch_bt_conv1_bwd(feat_dev, dc1, S, P + d->c1w, P + d->c1b, d->part, G + d->c1w, G + d->c1b, st));
@@ -1173,7 +1234,7 @@ extern "C" int etd_btrain_write(etd_btrain* d, const char* name, int which, cons
 }
 
 // ================================================================================================
-// debug entries (include/etude_hip_debug.h): the kernels with a tap, slice or mask edge on a caller's inputs, through the engine's own launchers
+// debug entries (include/etude_hip_debug.h): every kernel and the two host pipelines on a caller's inputs, through the engine's own launchers
 // ================================================================================================
 namespace {
 // the song tables of a tap: checked on the host, then uploaded to a block of its own (freed by the tap after its stream has drained)
@@ -1266,4 +1327,97 @@ extern "C" int etd_debug_btrain_read_rows(etd_btrain* d, int what, float* out_ho
   HIP_TRY(hipMemcpyAsync(out_host, src, (size_t)n * 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return ETD_OK;
+}
+
+// which 0: conv1 (in = feat, w, b); 1: conv2's patches (in = c1); 2: conv3's patches (in = c2); 3: pool3 (in = c3)
+extern "C" int etd_debug_btrain_front_fwd(int which, int n_seq, const int64_t* T_host, int instr, const float* in_dev, const float* w_dev, const float* b_dev, float* out_dev,
+                                          void* stream) {
+  if (which < 0 || which > 3 || !in_dev || !out_dev || (which == 0 && (!w_dev || !b_dev))) ETD_FAIL(ETD_EINVAL, "etd_debug_btrain_front_fwd: which = %d (0 .. 3) or a null argument", which);
+  hipStream_t st = (hipStream_t)stream;
+  TapSongs t;
+  ETD_TRY(t.make("etd_debug_btrain_front_fwd", n_seq, T_host, instr, st));
+  const int rc = which == 0 ? launch_bt_conv1(in_dev, t.S, w_dev, b_dev, out_dev, st) : which == 1 ? launch_bt_patch2(in_dev, t.S.rows, out_dev, st)
+               : which == 2 ? launch_bt_patch3(in_dev, t.S, out_dev, st) : launch_bt_pool3(in_dev, t.S.rows, out_dev, st);
+  return t.done(rc, st);
+}
+
+// which 0: pool3 backward (c = c3, g = dx -> dc3); 1: patch3 backward (c = c2, g = dx3 -> dc2)
+extern "C" int etd_debug_btrain_front_bwd(int which, int n_seq, const int64_t* T_host, int instr, const float* c_dev, const float* g_dev, float* out_dev, void* stream) {
+  if (which < 0 || which > 1 || !c_dev || !g_dev || !out_dev) ETD_FAIL(ETD_EINVAL, "etd_debug_btrain_front_bwd: which = %d (0 .. 1) or a null argument", which);
+  hipStream_t st = (hipStream_t)stream;
+  TapSongs t;
+  ETD_TRY(t.make("etd_debug_btrain_front_bwd", n_seq, T_host, instr, st));
+  return t.done(which == 0 ? launch_bt_pool3_bwd(c_dev, g_dev, t.S.rows, out_dev, st) : launch_bt_patch3_bwd(c_dev, g_dev, t.S, out_dev, st), st);
+}
+
+extern "C" int etd_debug_btrain_repack(int dir, int co, int ci, int kk, float* native_dev, float* packed_dev, void* stream) {
+  if (dir < 0 || dir > 1 || co < 1 || ci < 1 || kk < 1 || (long long)co * ci * kk > (1 << 24) || !native_dev || !packed_dev)
+    ETD_FAIL(ETD_EINVAL, "etd_debug_btrain_repack: dir = %d (0, 1), co x ci x kk = %d x %d x %d (each >= 1, at most 2^24 elements) or a null argument", dir, co, ci, kk);
+  return launch_bt_repack(native_dev, packed_dev, co, ci, kk, dir, (hipStream_t)stream);
+}
+
+extern "C" int etd_debug_btrain_colsum(const float* dy_dev, int ld, int M, int N, float* part_dev, float* out_dev, void* stream) {
+  if (M < 1 || M > BT_C2_COLS * (1 << 17) || N < 1 || N > 8192 || ld < N || !dy_dev || !part_dev || !out_dev)
+    ETD_FAIL(ETD_EINVAL, "etd_debug_btrain_colsum: M = %d (1 .. 24 x 2^17), N = %d (1 .. 8192), ld = %d (>= N) or a null argument", M, N, ld);
+  return launch_bt_colsum(dy_dev, ld, M, N, part_dev, out_dev, (hipStream_t)stream);
+}
+
+extern "C" int etd_debug_btrain_slice_sum(const float* part_dev, int n_slices, int width, float* out_dev, void* stream) {
+  if (n_slices < 1 || n_slices > (1 << 17) || width < 1 || width > (1 << 24) || !part_dev || !out_dev)
+    ETD_FAIL(ETD_EINVAL, "etd_debug_btrain_slice_sum: n_slices = %d (1 .. 2^17), width = %d (1 .. 2^24) or a null argument", n_slices, width);
+  return launch_bt_slice_sum(part_dev, n_slices, width, out_dev, (hipStream_t)stream);
+}
+
+// which 0: skipacc (a = skip -> tacc, first_layer 0 / 1); 1: dskip (a = dx, b = dtf -> dsk); 2: hmean (a = x -> hm); 3: hmean_bwd (a = x, b = dhm -> dx);
+// 4: tmean (a = tacc -> tm); 5: tmean_bwd (a = tacc, b = dtm -> dtf)
+extern "C" int etd_debug_btrain_means(int which, int n_seq, const int64_t* T_host, int instr, const float* a_dev, const float* b_dev, int first_layer, float* out_dev,
+                                      void* stream) {
+  const bool two = which == 1 || which == 3 || which == 5;
+  if (which < 0 || which > 5 || !a_dev || !out_dev || (two && !b_dev) || first_layer < 0 || first_layer > 1)
+    ETD_FAIL(ETD_EINVAL, "etd_debug_btrain_means: which = %d (0 .. 5), first_layer = %d (0, 1) or a null argument", which, first_layer);
+  hipStream_t st = (hipStream_t)stream;
+  TapSongs t;
+  ETD_TRY(t.make("etd_debug_btrain_means", n_seq, T_host, instr, st));
+  int rc;
+  switch (which) {
+    case 0: rc = launch_bt_skipacc(a_dev, t.S, first_layer, out_dev, st); break;
+    case 1: rc = launch_bt_dskip(a_dev, b_dev, t.S, out_dev, st); break;
+    case 2: rc = launch_bt_hmean(a_dev, t.S, out_dev, st); break;
+    case 3: rc = launch_bt_hmean_bwd(a_dev, b_dev, t.S, out_dev, st); break;
+    case 4: rc = launch_bt_tmean(a_dev, t.S, out_dev, st); break;
+    default: rc = launch_bt_tmean_bwd(a_dev, b_dev, t.S, out_dev, st); break;
+  }
+  return t.done(rc, st);
+}
+
+// y = relu(x) (y may be NULL); then dy = x > 0 ? dy : 0 in place (dy may be NULL); at least one of them
+extern "C" int etd_debug_btrain_relu(const float* x_dev, long long n, float* y_dev, float* dy_dev, void* stream) {
+  if (n < 1 || n > (1LL << 31) || !x_dev || (!y_dev && !dy_dev)) ETD_FAIL(ETD_EINVAL, "etd_debug_btrain_relu: n = %lld (1 .. 2^31) or a null argument", n);
+  hipStream_t st = (hipStream_t)stream;
+  if (y_dev) ETD_TRY(launch_bt_relu(x_dev, y_dev, n, st));
+  if (dy_dev) ETD_TRY(launch_bt_relu_bwd(x_dev, dy_dev, n, st));
+  return ETD_OK;
+}
+
+extern "C" int etd_debug_btrain_conv_wgrad(int M, int N, int K, const float* dY_dev, const float* X_dev, float* seg_dev, float* dw_dev, void* stream) {
+  if (M < 1 || N < 1 || K < 1 || K > BT_C2_COLS * (1 << 17) || (long long)M * N > (1 << 24) || !dY_dev || !X_dev || !seg_dev || !dw_dev)
+    ETD_FAIL(ETD_EINVAL, "etd_debug_btrain_conv_wgrad: M x N = %d x %d (each >= 1, at most 2^24 elements), K = %d (1 .. 24 x 2^17) or a null argument", M, N, K);
+  return launch_bt_conv_wgrad(M, N, K, dY_dev, X_dev, seg_dev, dw_dev, (hipStream_t)stream);
+}
+
+// P_dev / G_dev: gain [256] | bias [256] | linear1.weight [H][256] | linear1.bias [H] | linear2.weight [256][H] | linear2.bias [256], H = the handle's d_hid
+extern "C" int etd_debug_btrain_ffn_bwd(etd_btrain* d, int R, int act, const float* x_dev, const float* mean_dev, const float* rstd_dev, const float* pre_dev, const float* P_dev,
+                                        float* G_dev, float* dx_dev, void* stream) {
+  if (!d || !x_dev || !mean_dev || !rstd_dev || !pre_dev || !P_dev || !G_dev || !dx_dev) ETD_FAIL(ETD_EINVAL, "etd_debug_btrain_ffn_bwd: null argument");
+  if (R < 1 || R > d->cfg.max_rows || act < 0 || act > 1) ETD_FAIL(ETD_EINVAL, "etd_debug_btrain_ffn_bwd: R = %d (1 .. max_rows = %d) or act = %d (0, 1)", R, d->cfg.max_rows, act);
+  const size_t H = (size_t)d->cfg.d_hid, l1w = 512, l1b = l1w + H * 256, l2w = l1b + H, l2b = l2w + 256 * H;
+  return ffn_backward(d, R, act, x_dev, mean_dev, rstd_dev, pre_dev, P_dev, G_dev, dx_dev, 0, 256, l1w, l1b, l2w, l2b, (hipStream_t)stream);
+}
+
+// P_dev / G_dev: gain [256] | bias [256] | weight [768][256] | bias [768]
+extern "C" int etd_debug_btrain_proj_bwd(etd_btrain* d, int R, const float* x_dev, const float* mean_dev, const float* rstd_dev, const float* dqkv_dev, const float* P_dev,
+                                         float* G_dev, float* dx_dev, void* stream) {
+  if (!d || !x_dev || !mean_dev || !rstd_dev || !dqkv_dev || !P_dev || !G_dev || !dx_dev) ETD_FAIL(ETD_EINVAL, "etd_debug_btrain_proj_bwd: null argument");
+  if (R < 1 || R > d->cfg.max_rows) ETD_FAIL(ETD_EINVAL, "etd_debug_btrain_proj_bwd: R = %d (1 .. max_rows = %d)", R, d->cfg.max_rows);
+  return proj_backward(d, R, x_dev, mean_dev, rstd_dev, dqkv_dev, P_dev, G_dev, dx_dev, 0, 256, 512, 512 + 768 * 256, (hipStream_t)stream);
 }

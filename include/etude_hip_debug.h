@@ -337,7 +337,7 @@ int etd_bss_debug_project(etd_bss*, const float* ref_dev, int J, int C, long lon
                           double* pa_dev, void* stream);
 int etd_bss_debug_timing(etd_bss*, int on, double* stage_ms5);
 
-/* stage taps of the Beat-Transformer trainer (csrc/beat_train.hip): each kernel with a tap, slice or mask edge on a caller's DEVICE inputs, through the launchers
+/* stage taps of the Beat-Transformer trainer (csrc/beat_train.hip): every kernel and host pipeline on a caller's DEVICE inputs, through the launchers
  * etd_btrain_loss_backward uses.  Songs are given as for etd_beat_forward (T_host [n_seq], rows = instr x frames, at most 2^17).  Malformed arguments are ETD_EINVAL
  * before the device is touched.
  *   dattn      dilated attention of time layer `layer`: qkv [rows][768], Er [8][32][5], xin [rows][256] -> prob [rows][8][5], skip [rows][256], xout = xin + skip; with
@@ -348,6 +348,25 @@ int etd_bss_debug_timing(etd_bss*, int on, double* stage_ms5);
  *   conv1_bwd  conv1's dw [32][15] += and db [32] += from feat [rows][128] and dc1 [rows][42][32] (part: scratch of ceil(rows / 16) x 512 floats)
  *   bce        z, y [frames][ntoken], pos_weight, coef [ntoken] -> cell, dz [frames][ntoken]
  *   tempo_ce   t, p [n][300], has [n] int32 -> row [n], dt [n][300]
+ *   front_fwd  which 0: conv1 + pool + ReLU, in = feat [rows][128], w [32][15], b [32] -> out = c1 [rows][42][32]; 1: conv2's patches, in = c1 -> x2 [rows 24][384];
+ *              2: conv3's patches through pool2 + ReLU, in = c2 [rows][24][64] -> x3 [rows 3][1152]; 3: pool3 + ReLU, in = c3 [rows][3][256] -> x [rows][256]
+ *              (w, b are read by which 0 only)
+ *   front_bwd  which 0: c = c3, g = dx [rows][256] -> dc3 [rows][3][256]; 1: c = c2, g = dx3 [rows 3][1152] -> dc2 [rows][24][64] (every float written)
+ *   repack     k_bt_repack on native [co][ci][kk] and packed [co][kk][ci]: dir 0 packed = native, dir 1 native += packed
+ *   colsum     out [N] += the column sums of dy [M][N] (row stride ld >= N): slices of 256 rows, then slice_sum (part: scratch of ceil(M / 256) x N floats)
+ *   slice_sum  out [width] += the sum of part [n_slices][width] over the slices: 16 at a time in order, then the groups in order
+ *   means      which 0: skipacc, a = skip [rows][256] -> out = tacc [frames][256] (first_layer 1: overwritten, 0: added to); 1: dskip, a = dx [rows][256],
+ *              b = dtf [frames][256] -> dsk [rows][256]; 2: hmean, a = x [rows][256] -> hm [frames][256]; 3: hmean_bwd, a = x, b = dhm [frames][256] -> dx [rows][256];
+ *              4: tmean, a = tacc [frames][256] -> tm [n_seq][256]; 5: tmean_bwd, a = tacc, b = dtm [n_seq][256] -> dtf [frames][256]
+ *   relu       x [n] -> y = max(x, 0) (y may be NULL); then dy = x > 0 ? dy : 0 in place (dy may be NULL)
+ *   conv_wgrad dw [M][N] = dY^T X over K rows (dY [K][M], X [K][N]) in segments of 4 096 rows, then slice_sum; dw is overwritten (seg: scratch of
+ *              ceil(K / 4096) x M x N floats)
+ *   ffn_bwd    one feed-forward sublayer's backward (act 0 GELU, 1 ReLU) over R <= max_rows rows on the handle's scratch, with the handle's d_hid = H: x [R][256], its
+ *              LayerNorm statistics mean, rstd [R], pre = W1 LN(x) + b1 [R][H], P = gain [256] | bias [256] | linear1.weight [H][256] | linear1.bias [H] |
+ *              linear2.weight [256][H] | linear2.bias [256]; dx [R][256] holds the gradient of the sublayer's output on entry and of x on exit; the six parameter
+ *              gradients are ADDED to G (P's layout).  The handle's parameters, accumulated gradients and moments are neither read nor written.
+ *   proj_bwd   a fused q | k | v projection's backward from dqkv [R][768]: P = gain [256] | bias [256] | weight [768][256] | bias [768]; dx [R][256] += the gradient of
+ *              x, G (P's layout) += the parameter gradients; the key third of the bias gradient is not touched.  The handle as for ffn_bwd.
  *   read_rows  per-row results of the handle's last etd_btrain_loss_backward, to the HOST: what 0 = the gradient of the front end's tokens [rows][256], 1 = the logits
  *              [frames][ntoken], 2 = the gradient of conv1's pooled output [rows][42][32].  Synchronous. */
 int etd_debug_btrain_dattn(int n_seq, const int64_t* T_host, int instr, int layer, const float* qkv_dev, const float* Er_dev, const float* xin_dev, const float* dO_dev,
@@ -360,6 +379,19 @@ int etd_debug_btrain_bce(const float* z_dev, const float* y_dev, const float* po
                          void* stream);
 int etd_debug_btrain_tempo_ce(const float* t_dev, const float* p_dev, const int32_t* has_dev, float coef, int n, float* row_dev, float* dt_dev, void* stream);
 int etd_debug_btrain_read_rows(etd_btrain*, int what, float* out_host, long long numel, void* stream);
+int etd_debug_btrain_front_fwd(int which, int n_seq, const int64_t* T_host, int instr, const float* in_dev, const float* w_dev, const float* b_dev, float* out_dev,
+                               void* stream);
+int etd_debug_btrain_front_bwd(int which, int n_seq, const int64_t* T_host, int instr, const float* c_dev, const float* g_dev, float* out_dev, void* stream);
+int etd_debug_btrain_repack(int dir, int co, int ci, int kk, float* native_dev, float* packed_dev, void* stream);
+int etd_debug_btrain_colsum(const float* dy_dev, int ld, int M, int N, float* part_dev, float* out_dev, void* stream);
+int etd_debug_btrain_slice_sum(const float* part_dev, int n_slices, int width, float* out_dev, void* stream);
+int etd_debug_btrain_means(int which, int n_seq, const int64_t* T_host, int instr, const float* a_dev, const float* b_dev, int first_layer, float* out_dev, void* stream);
+int etd_debug_btrain_relu(const float* x_dev, long long n, float* y_dev, float* dy_dev, void* stream);
+int etd_debug_btrain_conv_wgrad(int M, int N, int K, const float* dY_dev, const float* X_dev, float* seg_dev, float* dw_dev, void* stream);
+int etd_debug_btrain_ffn_bwd(etd_btrain*, int R, int act, const float* x_dev, const float* mean_dev, const float* rstd_dev, const float* pre_dev, const float* P_dev,
+                             float* G_dev, float* dx_dev, void* stream);
+int etd_debug_btrain_proj_bwd(etd_btrain*, int R, const float* x_dev, const float* mean_dev, const float* rstd_dev, const float* dqkv_dev, const float* P_dev, float* G_dev,
+                              float* dx_dev, void* stream);
 
 #ifdef __cplusplus
 }
