@@ -66,12 +66,12 @@ def iteration(X: torch.Tensor, Y: torch.Tensor, s: torch.Tensor, dtype, parts=No
     return v[:, None] * torch.einsum("jcdk,dtk->jctk", R, z) * s
 
 
-def wiener(X: torch.Tensor, Y: torch.Tensor, iterations: int, dtype) -> torch.Tensor:
-    """``iterations`` passes (0 .. 8; 0 returns Y untouched) -> Y [I][C][Tf][F]"""
+def wiener(X: torch.Tensor, Y: torch.Tensor, iterations: int, dtype, scale=None) -> torch.Tensor:
+    """``iterations`` passes (0 .. 8; 0 returns Y untouched) -> Y [I][C][Tf][F].  ``scale`` forces s, for a test to show what a wrong s would give"""
     if int(iterations) != iterations or not 0 <= iterations <= 8:
         raise ValueError(f"mwf_iterations must be an integer in 0 .. 8, got {iterations}")
     Y = Y.to(_cdtype(dtype))
-    s = song_scale(X, dtype)
+    s = song_scale(X, dtype) if scale is None else torch.tensor(float(scale), dtype=dtype)
     for _ in range(int(iterations)):
         Y = iteration(X, Y, s, dtype)
     return Y

@@ -35,6 +35,45 @@ def make_track(J, C, N, colour, seed=0, noise=0.05):
     return x.astype(np.float32), est.astype(np.float32)
 
 
+# The cases of tests/test_gpu_bss.py, (J, C, L, window, hop, N, coloured), kept here so that test_the_gpu_cases_are_regular_in_fp64 below and the GPU file read one
+# list.  With WG = 256: L = 48 is a multiple of 16 that is no power of two; N = 4 WG + 37 extends the last window, WG - 5 is one short window, 32768 + 300 lies just
+# above one correlation slice (BSS_SLICE), so that the slice join is exercised.  From (5, 2, ...) on, the tile edges of csrc/bss.hip the product's shape (five stereo
+# stems, L = 512) lies beyond: S = 10 takes the 32-column layout with a ragged second tile (20 of 32) under overlapping windows; S = 16 fills every column and
+# right-hand side (2 S = NC); L = 80 wakes the correlation kernel's wave 1 with a ragged lag tile (lags 64 .. 79); L = 272 its second lag block with one ragged wave
+# (order 1088); L = 512, the default, two full lag blocks of four waves (order 1024).  Track i is make_track(..., seed=10 + i): append, never insert.
+WG = 256
+GPU_CASES = [(1, 1, 16, WG, 256, WG - 5, 0), (2, 2, 32, WG, 128, 4 * WG + 37, 1), (3, 2, 48, WG, 256, 4 * WG + 37, 1), (3, 1, 32, WG, 256, 4 * WG + 37, 0),
+             (1, 2, 16, WG, 256, 32768 + 300, 0), (2, 1, 16, WG, 128, 4 * WG + 37, 1),
+             (5, 2, 16, 256, 128, 4 * 256 + 37, 1), (8, 2, 16, 256, 256, 4 * 256 + 37, 0), (1, 2, 80, 256, 256, 4 * 256 + 37, 1), (2, 2, 272, 512, 512, 2 * 512 + 37, 1),
+             (2, 1, 512, 1024, 1024, 2 * 1024 + 37, 1)]
+GPU_IDS = [f"J{c[0]}C{c[1]}L{c[2]}{'' if c[3] == WG else f'W{c[3]}'}h{c[4]}N{c[5]}{'ar1' if c[6] else 'white'}" for c in GPU_CASES]
+
+
+def gpu_track(case):
+    """the references and estimates of a case of GPU_CASES"""
+    J, C, _, _, _, N, colour = case
+    return make_track(J, C, N, colour, seed=10 + GPU_CASES.index(case))
+
+
+@pytest.mark.parametrize("gpu_case", GPU_CASES, ids=GPU_IDS)
+def test_the_gpu_cases_are_regular_in_fp64(gpu_case):
+    """the GPU tests hold NaN to NaN and skip nothing else on a silent window or a singular track: a case that went either way would pass them without comparing a
+    number.  So every case must give, in the fp64 restatement, status 0, no silent window and finite positive energies (e_interf of a single source alone is zero)"""
+    J, C, Lc, window, hop, N, _ = gpu_case
+    ref, est = gpu_track(gpu_case)
+    a = B.evaluate(ref, est, Lc, window, hop)
+    assert a["status"] == 0 and not a["silent"].any()
+    assert a["E"].shape == (J, B.num_windows(N, window, hop), 8) and np.isfinite(a["E"]).all()
+    assert np.isfinite(a["A"]).all() and np.isfinite(a["B"]).all()
+    nonzero = [i for i in range(8) if not (J == 1 and i == 4)]
+    assert (a["E"][..., nonzero] > 0).all()
+    if J == 1:
+        assert (a["E"][..., 4] == 0).all() and np.isposinf(a["metrics"]["sir"]).all()
+    for k in B.NAMES:
+        if not (J == 1 and k == "sir"):
+            assert np.isfinite(a["metrics"][k]).all(), k
+
+
 @pytest.fixture(scope="module", params=[0, 1], ids=["white", "ar1"])
 def case(request):
     ref, est = make_track(3, 2, 4 * W + 37, request.param)

@@ -7,7 +7,10 @@ under the same rule: the floor is 4 x 2^-53 of the largest |dB| of the tensor, N
 4.4e-16 dB would lie below the half-ulp any rounding of the host's 10 log10(num / den) can move a correct result by.  Every test prints
 ``ratio = device error / max(yardstick error, 2^-53)``; the largest per stage are in profiles/bss_device.json and DESIGN.md 4p.
 
-Measured on an MI355X, largest ratios: correlations 0.61, solve 0.14, filters 0.78, projection 1.07, energies 1.25, metrics 1.89."""
+Measured on an MI355X, largest ratios and the case each came from: correlations 0.61 (J1C1L16 N251, r), solve 0.58 (n = 1; 0.14 at n = 16 was the largest before
+n < 16 was tried), filters 0.78 (J1C1L16 N251, A), projection 1.10 (J2C2L272 W512, ps of window 0; 1.07 for J2C1L16 h128 before), energies 1.25 (J2C1L16 h128, E0),
+metrics 1.89 (J1C1L16 N251, isr).  The five cases beyond the first tile edges (J5C2L16, J8C2L16, J1C2L80, J2C2L272, J2C1L512) reach 0.34, 0.17, 1.10, 1.20 and 1.31 in
+correlations, filters, projection, energies and metrics."""
 import sys
 from pathlib import Path
 
@@ -17,33 +20,31 @@ import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 import bss_np as B      # noqa: E402
-from test_bss_cpu import make_track      # noqa: E402
+from test_bss_cpu import GPU_CASES as CASES, GPU_IDS as IDS, gpu_track, make_track      # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-W = 256
+W = 256                 # the window of every test below that names no case
 FLOOR = 2.0 ** -53
 LD = np.longdouble
-# (J, C, L, hop, N, coloured): L = 48 is a multiple of 16 that is no power of two; N = 4 W + 37 extends the last window, W - 5 is one short window, 32768 + 300 lies
-# just above one correlation slice (BSS_SLICE), so that the slice join is exercised
-CASES = [(1, 1, 16, 256, W - 5, 0), (2, 2, 32, 128, 4 * W + 37, 1), (3, 2, 48, 256, 4 * W + 37, 1), (3, 1, 32, 256, 4 * W + 37, 0), (1, 2, 16, 256, 32768 + 300, 0),
-         (2, 1, 16, 128, 4 * W + 37, 1)]
-IDS = [f"J{c[0]}C{c[1]}L{c[2]}h{c[3]}N{c[4]}{'ar1' if c[5] else 'white'}" for c in CASES]
+# CASES, (J, C, L, window, hop, N, coloured), live in tests/test_bss_cpu.py, which also shows without a GPU that none of them is silent or singular
+PRODUCT = CASES[6]      # five stereo stems: the 32-column layout
+assert PRODUCT[:2] == (5, 2)
 _cache = {}
 
 
 def reference(case):
     """the track, its truth and its yardstick, computed once"""
     if case not in _cache:
-        J, C, L, hop, N, colour = case
-        ref, est = make_track(J, C, N, colour, seed=10 + CASES.index(case))
-        _cache[case] = (ref, est, B.evaluate(ref, est, L, W, hop, dtype=LD), B.evaluate(ref, est, L, W, hop, dtype=np.float64))
+        _, _, L, window, hop, _, _ = case
+        ref, est = gpu_track(case)
+        _cache[case] = (ref, est, B.evaluate(ref, est, L, window, hop, dtype=LD), B.evaluate(ref, est, L, window, hop, dtype=np.float64))
     return _cache[case]
 
 
 def engine(case, **kw):
     from etude_amd.bss import BSSEval, BSSEvalConfig
-    eng = BSSEval(BSSEvalConfig(filters_len=case[2], window=W, hop=case[3], **kw))
+    eng = BSSEval(BSSEvalConfig(filters_len=case[2], window=case[3], hop=case[4], **kw))
     eng.guard = 64
     return eng
 
@@ -79,19 +80,21 @@ def test_correlations(case):
     held("corr d", d, yard["d"], truth["d"])
 
 
-@pytest.mark.parametrize("n", [16, 48, 80, 200])
-def test_solve_on_a_callers_matrix(n):
-    """order 16: one panel; 48, 80: several panels and trailing updates; 200: a partial last panel"""
-    rng = np.random.default_rng(n)
+@pytest.mark.parametrize("n,m", [(16, 5), (48, 5), (80, 5), (200, 5), (1, 5), (15, 5), (17, 5), (48, 16)], ids=["16", "48", "80", "200", "1", "15", "17", "48-m16"])
+def test_solve_on_a_callers_matrix(n, m):
+    """order 16: one panel; 48, 80: several panels and trailing updates; 200: a partial last panel; 1, 15: below one panel, the rest of it the identity's; 17: one row
+    past a panel; m = 16: every right-hand side of the block is the caller's"""
+    rng = np.random.default_rng(n if m == 5 else 1000 * m + n)
     M = rng.standard_normal((n, 2 * n))
     G = M @ M.T / (2 * n) + 0.05 * np.eye(n)
-    D = rng.standard_normal((n, 5))
+    D = rng.standard_normal((n, m))
     truth, st = B.spd_solve(G.astype(LD), D.astype(LD))
     yard, _ = B.spd_solve(G, D)
     eng = engine(CASES[0])
     x, status = eng.debug_solve(G, D)
     assert eng.guards_intact() and status == 0 and st == 0
-    held(f"solve n={n}", x, yard, truth)
+    assert x.shape == (n, m)
+    held(f"solve n={n} m={m}", x, yard, truth)
 
 
 def test_indefinite_matrix_sets_the_status_and_the_next_call_works():
@@ -121,13 +124,14 @@ def test_filters(case):
 
 @pytest.mark.parametrize("case", CASES, ids=IDS)
 def test_projection_with_a_callers_filters(case):
-    """the first window and the last (the extended one where N = 4 W + 37), with the yardstick's fp64 filters as the caller's"""
-    J, C, L, hop, N, _ = case
+    """the first window and the last (the extended one where N = 4 W + 37), with the yardstick's fp64 filters as the caller's; at the 32-column layout of five stereo
+    stems a middle window too (w = 2: the hop is half a window there, so its samples start inside window 1)"""
+    J, C, L, window, hop, N, _ = case
     ref, est, _, yard = reference(case)
     eng = engine(case)
     A, Bf = yard["A"], yard["B"]
-    bounds = B.window_bounds(N, W, hop)
-    for w in sorted({0, len(bounds) - 1}):
+    bounds = B.window_bounds(N, window, hop)
+    for w in sorted({0, len(bounds) - 1} | ({2} if case == PRODUCT else set())):
         a, b = bounds[w]
         ps, pa = eng.debug_project(ref, w, A, Bf)
         assert ps.shape == (J, C, b - a + L - 1)
@@ -157,8 +161,8 @@ def test_energies_and_metrics(case):
 
 
 def test_silent_windows_are_nan_and_their_neighbours_are_not():
-    case = (2, 2, 32, 256, 4 * W + 37, 1)
-    J, C, L, hop, N, colour = case
+    case = (2, 2, 32, W, 256, 4 * W + 37, 1)
+    J, C, L, _, hop, N, colour = case
     ref, est = make_track(J, C, N, colour, seed=40)
     ref[1, :, W:2 * W] = 0           # a silent reference source in window 1
     est[0, :, 3 * W:] = 0            # a silent estimate source in window 3 (the extended one)
@@ -177,16 +181,16 @@ def test_silent_windows_are_nan_and_their_neighbours_are_not():
 def test_a_track_is_bit_identical_alone_in_a_batch_under_a_tight_budget_and_across_runs():
     from etude_amd.bss import BSSEval, BSSEvalConfig
     L, hop = 32, 128
-    shapes = [(2, 2, 4 * W + 37), (3, 1, W - 5), (1, 2, 7 * W + 11)]
+    shapes = [(2, 2, 4 * W + 37), (3, 1, W - 5), (1, 2, 7 * W + 11), (5, 2, 4 * W + 37)]      # (the last: NC = 32, the layout of five stereo stems)
     tracks = [make_track(J, C, N, i % 2, seed=50 + i) for i, (J, C, N) in enumerate(shapes)]
     eng = BSSEval(BSSEvalConfig(filters_len=L, window=W, hop=hop))
     alone = [eng.energies_many([r], [e])[0] for r, e in tracks]
-    for order in ([0, 1, 2], [2, 0, 1], [1, 2, 0]):
+    for order in ([0, 1, 2, 3], [2, 3, 0, 1], [3, 1, 2, 0]):
         batch = eng.energies_many([tracks[i][0] for i in order], [tracks[i][1] for i in order])
         for pos, i in enumerate(order):
             assert np.array_equal(batch[pos]["E"], alone[i]["E"], equal_nan=True) and np.array_equal(batch[pos]["silent"], alone[i]["silent"])
     again = eng.energies_many([t[0] for t in tracks], [t[1] for t in tracks])
-    for i in range(3):
+    for i in range(len(shapes)):
         assert np.array_equal(again[i]["E"], alone[i]["E"], equal_nan=True)
         assert np.isfinite(alone[i]["E"]).all()
     for i, (J, C, N) in enumerate(shapes):      # a budget that just admits the track: one window's projections at a time
