@@ -26,7 +26,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._engine import Engine, i64
+from ._engine import i64
+from ._trainer import Trainer
 from .beat import BeatDetector, _check_range, expected_keys
 from .config import BeatDetectorConfig, BeatDetectorModelConfig
 
@@ -102,10 +103,11 @@ def pack_targets(cfg: BeatDetectorModelConfig, Ts: Sequence[int], beat_targets: 
     return np.ascontiguousarray(np.concatenate(ys)), tempo, has
 
 
-class BeatTrainer(Engine):
+class BeatTrainer(Trainer):
     """fp32 training of the Beat-Transformer on the GPU.  ``state=None`` draws ``init_beat_state(config, seed)``; otherwise ``state`` maps the checkpoint's keys to
     arrays or tensors.  ``max_rows`` bounds instr x frames of one ``loss_and_backward`` call and sizes the activation workspace (a call above it is refused)."""
     _destroy = "etd_btrain_destroy"
+    _abi = "etd_btrain"
 
     def __init__(self, config: Optional[BeatDetectorModelConfig] = None, state: Optional[Dict] = None, seed: int = 0, device: Union[str, torch.device] = "cuda",
                  max_rows: int = 5 * 1024, max_seqs: int = 64, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
@@ -171,25 +173,12 @@ class BeatTrainer(Engine):
             self._last = (self.config.instr * sum(Ts), sum(Ts))
         return float(loss.value), int(n_scored.value), bool(skipped.value)
 
-    def zero_grad(self) -> None:
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().etd_btrain_zero_grad(self.h, self._stream(self.device)), "etd_btrain_zero_grad")
-
-    def grad_norm(self) -> float:
-        v = C.c_double()
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().etd_btrain_grad_norm(self.h, C.byref(v), self._stream(self.device)), "etd_btrain_grad_norm")
-        return float(v.value)
+    def _step_call(self, norm_ref, stream) -> None:
+        self._call("step", self.max_norm, self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, norm_ref, stream)
 
     def step(self) -> float:
         """``clip_grad_norm_`` + ``AdamW.step`` + ``zero_grad``, as ``DecoderTrainer.step``.  Returns the gradient norm before clipping."""
-        v = C.c_double()
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().etd_btrain_step(self.h, self.max_norm, self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, C.byref(v),
-                                                  self._stream(self.device)), "etd_btrain_step")
-        self.global_step += 1
-        self.zero_grad()
-        return float(v.value)
+        return super().step()
 
     def train_step(self, batches: Sequence[Tuple]) -> Tuple[List[float], float]:
         """Each batch is ``(feats, beat_targets)`` or ``(feats, beat_targets, tempo_targets)``; their gradients are accumulated with ``loss_scale = 1 / len(batches)``,
@@ -200,35 +189,9 @@ class BeatTrainer(Engine):
         losses = [self.loss_and_backward(*b, loss_scale=1.0 / k)[0] * k for b in batches]
         return losses, self.step()
 
-    # ------------------------------------------------------------------ state
-    def _read(self, which: int) -> "OrderedDict[str, np.ndarray]":
-        out = OrderedDict()
-        with torch.cuda.device(self.device):
-            for k, shape in self._shapes.items():
-                a = np.empty(shape, np.float32)
-                _lib.check(_lib.lib().etd_btrain_read(self.h, k.encode(), which, a.ctypes.data, a.size, self._stream(self.device)), "etd_btrain_read")
-                out[k] = a
-        return out
-
-    def state_dict(self) -> "OrderedDict[str, np.ndarray]":
-        return self._read(0)
-
-    def grads(self) -> "OrderedDict[str, np.ndarray]":
-        return self._read(1)
-
-    def optimizer_state_dict(self) -> Dict[str, object]:
-        return {"step": self.global_step, "exp_avg": self._read(2), "exp_avg_sq": self._read(3)}
-
-    def load_optimizer_state_dict(self, sd: Dict[str, object]) -> None:
-        with torch.cuda.device(self.device):
-            for which, key in ((2, "exp_avg"), (3, "exp_avg_sq")):
-                for k, shape in self._shapes.items():
-                    a = np.ascontiguousarray(sd[key][k], np.float32)
-                    if a.shape != tuple(shape):
-                        raise ValueError(f"{key}['{k}'] has shape {a.shape}, expected {tuple(shape)}")
-                    _lib.check(_lib.lib().etd_btrain_write(self.h, k.encode(), which, a.ctypes.data, a.size, self._stream(self.device)), "etd_btrain_write")
-            _lib.check(_lib.lib().etd_btrain_set_step(self.h, int(sd["step"])), "etd_btrain_set_step")
-        self.global_step = int(sd["step"])
+    # ------------------------------------------------------------------ state (state_dict, grads and the optimizer's state: Trainer)
+    def _write_entry(self, second: int):
+        return "write", (2 + second,)
 
     def debug_read_rows(self, what: int) -> np.ndarray:
         """test hook (etd_debug_btrain_read_rows): per-row results of the last ``loss_and_backward`` that ran -- 0: the gradient of the front end's tokens

@@ -1,12 +1,12 @@
 // Training engine of the Beat-Transformer (etd_btrain_*): the model of beat.hip with saved activations, this project's beat / tempo loss, the backward pass for
-// every parameter, global-norm clipping and AdamW, all in fp32.  Dense products are launch_tgemm of dec_train.h; LayerNorm, GELU, the column
-// reductions, the gradient norm and the AdamW update are the decoder trainer's kernels.  These are the launchers of the kernels that are new here; every one is
+// every parameter, global-norm clipping and AdamW, all in fp32.  Dense products, LayerNorm, GELU, the column reductions, the gradient norm
+// and the AdamW update are the trainers' shared kernels (train_kernels.h).  These are the launchers of the kernels that are new here; every one is
 // also reachable on its own through include/etude_hip_debug.h (etd_debug_btrain_*: dattn, iattn, fold2, conv1_bwd, bce, tempo_ce, front_fwd, front_bwd, repack, colsum,
 // slice_sum, means, relu, conv_wgrad, and the two host pipelines ffn_bwd and proj_bwd on a handle's scratch).
 // Nothing here uses a floating-point atomic: every sum runs in an order fixed by the shapes alone.
 #pragma once
 #include "beat.h"
-#include "dec_train.h"
+#include "train_kernels.h"
 
 #define BT_C2_COLS 24         // conv2 columns the model reads (8 pooled columns x 3); the patches and conv2's output are [row][24][.]
 #define BT_C1_ROWS 16         // rows per slice of the conv1 weight reduction

@@ -4,7 +4,7 @@
 // Rows are (song, instr, t) as in beat.hip: song s owns rows [row0_s, row0_s + instr T_s) laid out [instr][T_s]; frames are (song, t).  One call is one chunk: its rows
 // must fit the workspace sized at create.
 // Arithmetic: fp32 operands and accumulation.  Every dense product (the linear layers, conv2 and conv3 on explicit patches, the two heads) is launch_tgemm of
-// dec_train.h in its forward, input-gradient and weight-gradient form.  No floating-point atomics: a kernel either owns its output element and adds its terms in an
+// train_kernels.h in its forward, input-gradient and weight-gradient form.  No floating-point atomics: a kernel either owns its output element and adds its terms in an
 // order fixed by the shapes (taps ascending, kw ascending, instruments ascending), or reduces over rows in fixed slices followed by an ordered sum.  Every gradient
 // is formed for the call and then added once to the accumulated one.
 #include "beat_train.h"
@@ -12,15 +12,12 @@
 #include <math.h>
 
 #include <algorithm>
-#include <map>
 #include <string>
 #include <vector>
 
 #include "etude_hip.h"
 #include "etude_hip_debug.h"
-#include "host_util.h"
-#include "prof.h"
-#include "train_optim.h"
+#include "train_store.h"
 
 #define BT_SCALE 5.656854249492380195f      // sqrt(head_dim)
 
@@ -243,7 +240,7 @@ __global__ __launch_bounds__(256) void k_bt_slice_sum(const float* __restrict__ 
 }
 
 // Column sums over the batch rows (a bias gradient), level 1: workgroup = 32 columns x one slice of BT_CS_ROWS rows; thread = (column, one of 8 sub-slices taking every
-// 8th row in ascending order); the 8 partial sums are added in order.  Level 2 is k_bt_slice_sum.  (dec_train.hip's k_tcolred runs 8 chains over ALL rows: at 5 150 rows
+// 8th row in ascending order); the 8 partial sums are added in order.  Level 2 is k_bt_slice_sum.  (train_kernels.hip's k_tcolred runs 8 chains over ALL rows: at 5 150 rows
 // its chains of 644 terms missed the bound of DESIGN.md 4s on four biases by ratios of 4.1 .. 5.2.)
 __global__ __launch_bounds__(256) void k_bt_colsum_part(const float* __restrict__ dy, int ld, int M, int N, float* __restrict__ part) {
   __shared__ float ps[8][32];
@@ -555,7 +552,7 @@ __global__ __launch_bounds__(256) void k_bt_bce(const float* __restrict__ z, con
   const float yi = y[i], zi = z[i];
   if (yi < 0.f) { cell[i] = 0.f; dz[i] = 0.f; return; }      // -1: not scored
   // (scalar adds and multiplies of their own: left to itself the SLP vectoriser pairs this kernel's independent ones into crossed v_pk_add_f32, the packed form
-  // tests/test_isa_guard.py keeps out of the library; see mul_scalar in train_optim.h)
+  // tests/test_isa_guard.py keeps out of the library; see mul_scalar in train_kernels.h)
   const float w = add_scalar(1.f, mul_scalar(add_scalar(pos_weight[c], -1.f), yi));
   const float e = expf(-fabsf(zi));
   const float den = add_scalar(1.f, e);
@@ -717,7 +714,6 @@ int launch_bt_tempo_ce(const float* t, const float* p, const int* has, float coe
 
 // ================================================================================================ the engine
 namespace {
-struct BParam { std::string name; size_t off, n; };
 struct BTime { size_t qkv_w, qkv_b, Er, n1w, n1b, n2w, n2b, l1w, l1b, l2w, l2b; };
 struct BInstr { size_t in_w, in_b, out_w, out_b, n1w, n1b, n2w, n2b, l1w, l1b, l2w, l2b; };
 // what one time layer (and the instrument layer behind it) keeps from forward to backward, per row: x 256, qkv 768, prob 40, x after attention 256, pre d_hid, 4 statistics
@@ -728,13 +724,10 @@ struct BSavedI { float *xin, *qkv, *ao, *xat, *pre, *m1, *r1, *m2, *r2; };
 struct etd_btrain {
   etd_btrain_cfg cfg;
   std::vector<float> pos_weight;
-  std::vector<BParam> params;
-  std::map<std::string, int> index;
-  size_t n_total = 0;
+  TrainStore ps;                           // every tensor is trained: the norm and the step run over n_total
   size_t c1w = 0, c1b = 0, c2w = 0, c2b = 0, c3w = 0, c3b = 0, ow = 0, ob = 0, tw = 0, tb = 0;
   std::vector<BTime> tl;
   std::vector<BInstr> il;                  // for time layers 3 .. 5 (those below nlayers)
-  float *P = nullptr, *G = nullptr, *M1 = nullptr, *M2 = nullptr;
   // packed conv weights and their gradients ([co][kk][ci])
   float *w2p = nullptr, *w3p = nullptr, *dw2p = nullptr, *dw3p = nullptr;
   // saved activations
@@ -744,22 +737,12 @@ struct etd_btrain {
   // scratch
   float *wI = nullptr, *tx = nullptr, *dxn = nullptr, *dx = nullptr, *dsk = nullptr, *dqkv = nullptr, *dl = nullptr, *big = nullptr, *part = nullptr, *dtf = nullptr, *dhm = nullptr,
         *dtm = nullptr, *seg = nullptr, *cpart = nullptr, *dz = nullptr, *dt = nullptr, *cell = nullptr, *trow = nullptr, *ytgt = nullptr, *ttgt = nullptr, *fl = nullptr;
-  double* partial = nullptr;
   int* ints = nullptr;
   std::vector<float> h_cell, h_trow;
-  long long step = 0;
   int last_rows = 0, last_frames = 0;      // of the last call that ran (etd_debug_btrain_read_rows)
   size_t workspace_bytes = 0;
   DevPool pool;
 };
-
-static size_t bp_add(etd_btrain* d, const std::string& name, size_t n) {
-  const size_t off = d->n_total;
-  d->index[name] = (int)d->params.size();
-  d->params.push_back({name, off, n});
-  d->n_total += (n + 63) / 64 * 64;                    // 256-byte alignment of every tensor; the gaps stay 0 in all four buffers
-  return off;
-}
 
 static int btrain_check_cfg(const etd_btrain_cfg* cfg) {
   if (!cfg) ETD_FAIL(ETD_EINVAL, "etd_btrain: null config");
@@ -826,51 +809,46 @@ extern "C" int etd_btrain_create(const etd_btrain_cfg* cfg, const char* const* n
   d->pos_weight.assign(c.ntoken, 1.f);
   if (pos_weight) d->pos_weight.assign(pos_weight, pos_weight + c.ntoken);
   const size_t D = 256, H = c.d_hid;
-  d->c1w = bp_add(d, "conv1.weight", 32 * 15); d->c1b = bp_add(d, "conv1.bias", 32);
-  d->c2w = bp_add(d, "conv2.weight", 64 * BEAT_K2); d->c2b = bp_add(d, "conv2.bias", 64);
-  d->c3w = bp_add(d, "conv3.weight", D * BEAT_K3); d->c3b = bp_add(d, "conv3.bias", D);
+  TrainStore& ps = d->ps;
+  d->c1w = ps.add("conv1.weight", 32 * 15); d->c1b = ps.add("conv1.bias", 32);
+  d->c2w = ps.add("conv2.weight", 64 * BEAT_K2); d->c2b = ps.add("conv2.bias", 64);
+  d->c3w = ps.add("conv3.weight", D * BEAT_K3); d->c3b = ps.add("conv3.bias", D);
   for (int l = 0; l < c.nlayers; ++l) {
     const std::string p = "Transformer_layers.time_attention_" + std::to_string(l) + ".";
     BTime t;
     // query | key | value back to back: one [768][256] weight and one [768] bias for the fused projection (every tensor is a multiple of 64 floats: no gaps)
-    t.qkv_w = bp_add(d, p + "self_attn.query.weight", D * D); bp_add(d, p + "self_attn.key.weight", D * D); bp_add(d, p + "self_attn.value.weight", D * D);
-    t.qkv_b = bp_add(d, p + "self_attn.query.bias", D); bp_add(d, p + "self_attn.key.bias", D); bp_add(d, p + "self_attn.value.bias", D);
-    t.Er = bp_add(d, p + "self_attn.Er", 8 * 32 * 5);
-    t.n1w = bp_add(d, p + "norm1.weight", D); t.n1b = bp_add(d, p + "norm1.bias", D); t.n2w = bp_add(d, p + "norm2.weight", D); t.n2b = bp_add(d, p + "norm2.bias", D);
-    t.l1w = bp_add(d, p + "linear1.weight", H * D); t.l1b = bp_add(d, p + "linear1.bias", H);
-    t.l2w = bp_add(d, p + "linear2.weight", D * H); t.l2b = bp_add(d, p + "linear2.bias", D);
+    t.qkv_w = ps.add(p + "self_attn.query.weight", D * D); ps.add(p + "self_attn.key.weight", D * D); ps.add(p + "self_attn.value.weight", D * D);
+    t.qkv_b = ps.add(p + "self_attn.query.bias", D); ps.add(p + "self_attn.key.bias", D); ps.add(p + "self_attn.value.bias", D);
+    t.Er = ps.add(p + "self_attn.Er", 8 * 32 * 5);
+    t.n1w = ps.add(p + "norm1.weight", D); t.n1b = ps.add(p + "norm1.bias", D); t.n2w = ps.add(p + "norm2.weight", D); t.n2b = ps.add(p + "norm2.bias", D);
+    t.l1w = ps.add(p + "linear1.weight", H * D); t.l1b = ps.add(p + "linear1.bias", H);
+    t.l2w = ps.add(p + "linear2.weight", D * H); t.l2b = ps.add(p + "linear2.bias", D);
     d->tl.push_back(t);
     if (l >= 3 && l <= 5) {
       const std::string q = "Transformer_layers.instr_attention_" + std::to_string(l) + ".";
       BInstr i;
-      i.in_w = bp_add(d, q + "self_attn.in_proj_weight", 3 * D * D); i.in_b = bp_add(d, q + "self_attn.in_proj_bias", 3 * D);
-      i.out_w = bp_add(d, q + "self_attn.out_proj.weight", D * D); i.out_b = bp_add(d, q + "self_attn.out_proj.bias", D);
-      i.n1w = bp_add(d, q + "norm1.weight", D); i.n1b = bp_add(d, q + "norm1.bias", D); i.n2w = bp_add(d, q + "norm2.weight", D); i.n2b = bp_add(d, q + "norm2.bias", D);
-      i.l1w = bp_add(d, q + "linear1.weight", H * D); i.l1b = bp_add(d, q + "linear1.bias", H);
-      i.l2w = bp_add(d, q + "linear2.weight", D * H); i.l2b = bp_add(d, q + "linear2.bias", D);
+      i.in_w = ps.add(q + "self_attn.in_proj_weight", 3 * D * D); i.in_b = ps.add(q + "self_attn.in_proj_bias", 3 * D);
+      i.out_w = ps.add(q + "self_attn.out_proj.weight", D * D); i.out_b = ps.add(q + "self_attn.out_proj.bias", D);
+      i.n1w = ps.add(q + "norm1.weight", D); i.n1b = ps.add(q + "norm1.bias", D); i.n2w = ps.add(q + "norm2.weight", D); i.n2b = ps.add(q + "norm2.bias", D);
+      i.l1w = ps.add(q + "linear1.weight", H * D); i.l1b = ps.add(q + "linear1.bias", H);
+      i.l2w = ps.add(q + "linear2.weight", D * H); i.l2b = ps.add(q + "linear2.bias", D);
       d->il.push_back(i);
     }
   }
-  d->ow = bp_add(d, "out_linear.weight", (size_t)c.ntoken * D); d->ob = bp_add(d, "out_linear.bias", c.ntoken);
-  d->tw = bp_add(d, "out_linear_t.weight", (size_t)BT_TEMPO * D); d->tb = bp_add(d, "out_linear_t.bias", BT_TEMPO);
+  d->ow = ps.add("out_linear.weight", (size_t)c.ntoken * D); d->ob = ps.add("out_linear.bias", c.ntoken);
+  d->tw = ps.add("out_linear_t.weight", (size_t)BT_TEMPO * D); d->tb = ps.add("out_linear_t.bias", BT_TEMPO);
   // host image of the parameters, checked before the device is touched
   WeightTable wt(names, host_ptrs, numels, n);
   if (wt.null_name >= 0) { g_etd_err = "etd_btrain_create: null name " + std::to_string(wt.null_name); return fail(ETD_EINVAL); }
-  std::vector<float> host(d->n_total, 0.f);
-  for (const BParam& p : d->params) {
-    const float* src = wt.get(p.name, (int64_t)p.n);
-    if (!src) { g_etd_err = "etd_btrain_create: " + g_etd_err; return fail(ETD_EINVAL); }
-    memcpy(host.data() + p.off, src, p.n * sizeof(float));
-  }
+  ps.n_train = ps.n_total;
+  std::vector<float> host(ps.n_total, 0.f);
+  if (ps.fill(wt, host.data()) != ETD_OK) { g_etd_err = "etd_btrain_create: " + g_etd_err; return fail(ETD_EINVAL); }
   // ---- device
   DevPool& pl = d->pool;
-  ETD_TRY_OR(fail, (pl.upload<float, float>(&d->P, host.data(), d->n_total)));
-  ETD_TRY_OR(fail, pl.alloc(&d->G, d->n_total, true));
-  ETD_TRY_OR(fail, pl.alloc(&d->M1, d->n_total, true));
-  ETD_TRY_OR(fail, pl.alloc(&d->M2, d->n_total, true));
+  ETD_TRY_OR(fail, ps.upload(pl, host.data(), ps.n_total));
   ETD_TRY_OR(fail, pl.alloc(&d->w2p, (size_t)64 * BEAT_K2)); ETD_TRY_OR(fail, pl.alloc(&d->dw2p, (size_t)64 * BEAT_K2));
   ETD_TRY_OR(fail, pl.alloc(&d->w3p, D * BEAT_K3)); ETD_TRY_OR(fail, pl.alloc(&d->dw3p, D * BEAT_K3));
-  ETD_TRY_OR(fail, pl.alloc(&d->partial, (size_t)TN_BLOCKS));
+  ETD_TRY_OR(fail, pl.alloc(&ps.partial, (size_t)TN_BLOCKS));
   const size_t R = (size_t)c.max_rows, ns = (size_t)c.max_seqs, nt = (size_t)c.ntoken;
   const size_t before = pl.mark();
   ETD_TRY_OR(fail, pl.alloc(&d->c1, R * BEAT_W1 * BEAT_C1)); ETD_TRY_OR(fail, pl.alloc(&d->x2, R * BT_C2_COLS * BEAT_K2)); ETD_TRY_OR(fail, pl.alloc(&d->c2o, R * BT_C2_COLS * BEAT_C2));
@@ -913,7 +891,7 @@ extern "C" void etd_btrain_destroy(etd_btrain* d) {
 
 extern "C" long long etd_btrain_bytes(const etd_btrain* d, int what) {
   if (!d) return ETD_EINVAL;
-  return what == 0 ? (long long)d->workspace_bytes : (long long)(4 * d->n_total * sizeof(float));
+  return what == 0 ? (long long)d->workspace_bytes : (long long)(4 * d->ps.n_total * sizeof(float));
 }
 
 // HOST ONLY: the argument checks of etd_btrain_loss_backward.  n_scored [ntoken] (may be NULL): scored cells per class; *n_tempo: songs with a tempo target
@@ -1048,7 +1026,7 @@ extern "C" int etd_btrain_loss_backward(etd_btrain* d, const float* feat_dev, in
   BtSongs S;
   S.row0 = d->ints; S.frame0 = d->ints + n_seq + 1; S.n = n_seq; S.rows = R; S.frames = F; S.instr = ni;
   const int* d_has = d->ints + 2 * (n_seq + 1);
-  float *P = d->P, *G = d->G;
+  float *P = d->ps.P, *G = d->ps.G;
   const long long RD = (long long)R * 256, RH = (long long)R * H;
   auto copy = [&](float* dst, const float* src, long long nfl) -> int {
     HIP_TRY(hipMemcpyAsync(dst, src, (size_t)nfl * 4, hipMemcpyDeviceToDevice, st));
@@ -1186,51 +1164,34 @@ extern "C" int etd_btrain_loss_backward(etd_btrain* d, const float* feat_dev, in
 
 extern "C" int etd_btrain_zero_grad(etd_btrain* d, void* stream) {
   if (!d) ETD_FAIL(ETD_EINVAL, "etd_btrain_zero_grad: null handle");
-  HIP_TRY(hipMemsetAsync(d->G, 0, sizeof(float) * d->n_total, (hipStream_t)stream));
-  return ETD_OK;
+  return d->ps.zero_grad(d->ps.n_total, (hipStream_t)stream);
 }
 
 extern "C" int etd_btrain_grad_norm(etd_btrain* d, double* norm, void* stream) {
   if (!d || !norm) ETD_FAIL(ETD_EINVAL, "etd_btrain_grad_norm: null argument");
-  return grad_norm(d->G, (long long)d->n_total, d->partial, (hipStream_t)stream, norm);
+  return d->ps.grad_norm(d->ps.n_total, (hipStream_t)stream, norm);
 }
 
 extern "C" int etd_btrain_step(etd_btrain* d, double max_norm, double lr, double beta1, double beta2, double eps, double weight_decay, double* norm_out, void* stream) {
   if (!d) ETD_FAIL(ETD_EINVAL, "etd_btrain_step: null handle");
-  ETD_TRY(adamw_check("etd_btrain_step", lr, beta1, beta2, eps, weight_decay));
-  hipStream_t st = (hipStream_t)stream;
-  ProfScope ps("btrain_optimizer", st);
-  double norm = 0.0;
-  const long long n = (long long)d->n_total;
-  ETD_TRY(grad_norm(d->G, n, d->partial, st, &norm));
-  if (norm_out) *norm_out = norm;
-  d->step += 1;
-  launch_tadamw(d->P, d->G, d->M1, d->M2, n, adamw_args(max_norm, norm, lr, beta1, beta2, eps, weight_decay, d->step), st);
-  HIP_TRY(hipGetLastError());
-  return ETD_OK;
+  return adamw_step(d->ps, d->ps.n_total, "etd_btrain_step", "btrain_optimizer", max_norm, lr, beta1, beta2, eps, weight_decay, norm_out, (hipStream_t)stream);
 }
 
 extern "C" int etd_btrain_set_step(etd_btrain* d, long long step) {
   if (!d || step < 0) ETD_FAIL(ETD_EINVAL, "etd_btrain_set_step: null handle or negative step");
-  d->step = step;
+  d->ps.step = step;
   return ETD_OK;
 }
-extern "C" long long etd_btrain_get_step(const etd_btrain* d) { return d ? d->step : ETD_EINVAL; }
+extern "C" long long etd_btrain_get_step(const etd_btrain* d) { return d ? d->ps.step : ETD_EINVAL; }
 
 // which: 0 parameter, 1 gradient, 2 exp_avg, 3 exp_avg_sq
-static int btrain_io(etd_btrain* d, const char* name, int which, float* out, const float* in, long long numel, hipStream_t st) {
-  if (!d || !name || (!out && !in) || which < 0 || which > 3) ETD_FAIL(ETD_EINVAL, "etd_btrain: null argument or unknown buffer");
-  auto it = d->index.find(name);
-  if (it == d->index.end()) ETD_FAIL(ETD_EINVAL, "etd_btrain: no parameter '%s'", name);
-  const BParam& p = d->params[it->second];
-  if ((long long)p.n != numel) ETD_FAIL(ETD_EINVAL, "etd_btrain: '%s' has %zu elements, the buffer %lld", name, p.n, numel);
-  return flat_io(d->P, d->G, d->M1, d->M2, which, (long long)p.off, (long long)p.n, out, in, st);
-}
 extern "C" int etd_btrain_read(etd_btrain* d, const char* name, int which, float* out_host, long long numel, void* stream) {
-  return btrain_io(d, name, which, out_host, nullptr, numel, (hipStream_t)stream);
+  if (!d || !name || !out_host || which < 0 || which > 3) ETD_FAIL(ETD_EINVAL, "etd_btrain: null argument or unknown buffer");
+  return train_io(&d->ps, "etd_btrain", name, which, out_host, nullptr, numel, (hipStream_t)stream);
 }
 extern "C" int etd_btrain_write(etd_btrain* d, const char* name, int which, const float* in_host, long long numel, void* stream) {
-  return btrain_io(d, name, which, nullptr, in_host, numel, (hipStream_t)stream);
+  if (!d || !name || !in_host || which < 0 || which > 3) ETD_FAIL(ETD_EINVAL, "etd_btrain: null argument or unknown buffer");
+  return train_io(&d->ps, "etd_btrain", name, which, nullptr, in_host, numel, (hipStream_t)stream);
 }
 
 // ================================================================================================

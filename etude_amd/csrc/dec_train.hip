@@ -2,125 +2,24 @@
 // clipping and AdamW (dec_train.h).  The model is the reference's (etude/models/etude_decoder.py:148-206 over HF GPT-NeoX) in its fp32 arithmetic;
 // dropout is 0 in the reference's configuration, so train mode computes what eval mode computes.
 //
-// Arithmetic: fp32 operands and fp32 accumulation everywhere.  The linear layers' products (forward, input gradient, weight gradient) run on
-// v_mfma_f32_32x32x2_f32; the attention kernels keep one query (or key) row per lane and use fmaf chains.  The f16-split planes of gemm3.h are not used: they
-// need a proven bound of their operands, which gradients do not have.
-// Order: no floating-point atomics.  Every sum -- a GEMM's K chain, a column reduction over the batch rows, an embedding row's gradient, the norm -- runs in an
-// order fixed by the shapes of the call, so the same call on the same inputs gives the same bits.
+// This file holds what is the decoder's own: attention, rotary embedding, the parallel residual, the embedding kernels, the cross-entropy and the engine.  The
+// linear layers' products, LayerNorm, GELU, the column reductions, the norm and AdamW are train_kernels.hip's; the parameter store is train_store.h.
+// Arithmetic: fp32 operands and fp32 accumulation everywhere.  The attention kernels keep one query (or key) row per lane and use fmaf chains.
+// Order: no floating-point atomics.  Every sum -- an attention row, an embedding row's gradient -- runs in an order fixed by the shapes of the call, so the
+// same call on the same inputs gives the same bits.
 #include "dec_train.h"
 
 #include <math.h>
 
 #include <algorithm>
-#include <map>
 #include <string>
 #include <vector>
 
 #include "etude_hip.h"
 #include "etude_hip_debug.h"
-#include "host_util.h"
-#include "prof.h"
-#include "train_optim.h"
+#include "train_store.h"
 
 #define ETD_IGNORE_LABEL (-100)
-
-// ================================================================================================
-// the GEMM family
-// ================================================================================================
-#define TG_BK 32
-#define TG_CH 8      // accumulator chains per output element
-#define TG_LD 65     // 64 + 1: a wave that stores 32 consecutive k of two rows hits 64 distinct (bank, half) pairs
-
-// AKC / BKC: k is the contiguous index of the operand in memory (decides which way the 256 threads sweep the tile, so that global loads coalesce)
-template <bool KC>
-__device__ __forceinline__ void tg_coords(int t, int r, int& i, int& k) {
-  if (KC) { k = t & 31; i = (t >> 5) + 8 * r; }
-  else { i = t & 63; k = (t >> 6) + 4 * r; }
-}
-
-template <bool AKC, bool BKC>
-__global__ __launch_bounds__(256) void k_tgemm(int M, int N, int K, const float* __restrict__ A, long long sai, long long sak, const float* __restrict__ B,
-                                               long long sbk, long long sbj, const float* __restrict__ bias, float* __restrict__ C, int ldc, int accumulate) {
-  __shared__ float As[TG_BK][TG_LD], Bs[TG_BK][TG_LD];
-  const int t = threadIdx.x, l = t & 63, w = t >> 6;
-  const int i0 = blockIdx.y * 64, j0 = blockIdx.x * 64;
-  const int wr = w >> 1, wc = w & 1, half = l >> 5, l31 = l & 31;
-  float ra[8], rb[8];
-  // TG_CH accumulator chains: MFMA j of every K tile adds into chain j % TG_CH, and the chains are added pairwise at the end.  Each output element's sum is then
-  // TG_CH interleaved chains of K / TG_CH terms instead of one of K terms -- the rounding error of a long batch-row reduction (dW over thousands of rows) grows
-  // with the chain's length -- in an order that the shape alone fixes.
-  f32x16 acc[TG_CH];
-#pragma unroll
-  for (int c = 0; c < TG_CH; ++c)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[c][r] = 0.f;
-#define TG_LOAD(k0)                                                                                         \
-  _Pragma("unroll") for (int r = 0; r < 8; ++r) {                                                           \
-    int i, k;                                                                                               \
-    tg_coords<AKC>(t, r, i, k);                                                                             \
-    const long long gi = i0 + i, gk = (k0) + k;                                                             \
-    ra[r] = (gi < M && gk < K) ? A[gi * sai + gk * sak] : 0.f;                                              \
-    tg_coords<BKC>(t, r, i, k);                                                                             \
-    const long long gj = j0 + i, gk2 = (k0) + k;                                                            \
-    rb[r] = (gj < N && gk2 < K) ? B[gk2 * sbk + gj * sbj] : 0.f;                                            \
-  }
-  TG_LOAD(0)
-  for (int k0 = 0; k0 < K; k0 += TG_BK) {
-    __syncthreads();                                   // the previous tile has been read
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      int i, k;
-      tg_coords<AKC>(t, r, i, k);
-      As[k][i] = ra[r];
-      tg_coords<BKC>(t, r, i, k);
-      Bs[k][i] = rb[r];
-    }
-    __syncthreads();
-    if (k0 + TG_BK < K) { TG_LOAD(k0 + TG_BK) }        // the next tile's loads fly while this one is multiplied
-#pragma unroll
-    for (int kk = 0; kk < TG_BK; kk += 2)
-      acc[(kk >> 1) % TG_CH] = __builtin_amdgcn_mfma_f32_32x32x2f32(As[kk + half][wr * 32 + l31], Bs[kk + half][wc * 32 + l31], acc[(kk >> 1) % TG_CH], 0, 0, 0);
-  }
-#undef TG_LOAD
-#pragma unroll
-  for (int w2 = 1; w2 < TG_CH; w2 *= 2)
-#pragma unroll
-    for (int c = 0; c + w2 < TG_CH; c += 2 * w2)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[c][r] += acc[c + w2][r];
-  const int col = j0 + wc * 32 + l31;
-  if (col < N) {
-    const float bv = bias ? bias[col] : 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = i0 + wr * 32 + acc_row(r, half);
-      if (row < M) {
-        float* p = C + (long long)row * ldc + col;
-        float v = acc[0][r] + bv;
-        if (accumulate) v = *p + v;
-        *p = v;
-      }
-    }
-  }
-}
-
-int launch_tgemm(int form, int M, int N, int K, const float* A, int lda, const float* B, int ldb, const float* bias, float* C, int ldc, bool accumulate,
-                 hipStream_t st) {
-  if (M < 1 || N < 1 || K < 1 || !A || !B || !C) ETD_FAIL(ETD_EINVAL, "tgemm: bad shape M=%d N=%d K=%d", M, N, K);
-  const int a_row = form == ETD_TG_TN ? M : K, b_row = form == ETD_TG_NT ? K : N;
-  if (lda < a_row || ldb < b_row || ldc < N) ETD_FAIL(ETD_EINVAL, "tgemm: a row stride is shorter than its row (lda=%d ldb=%d ldc=%d)", lda, ldb, ldc);
-  const dim3 grid((N + 63) / 64, (M + 63) / 64), block(256);
-  if (grid.y > 65535u) ETD_FAIL(ETD_EINVAL, "tgemm: M=%d is above 65535 row tiles", M);
-  const int acc = accumulate ? 1 : 0;
-  switch (form) {
-    case ETD_TG_NT: hipLaunchKernelGGL((k_tgemm<true, true>), grid, block, 0, st, M, N, K, A, (long long)lda, 1LL, B, 1LL, (long long)ldb, bias, C, ldc, acc); break;
-    case ETD_TG_NN: hipLaunchKernelGGL((k_tgemm<true, false>), grid, block, 0, st, M, N, K, A, (long long)lda, 1LL, B, (long long)ldb, 1LL, bias, C, ldc, acc); break;
-    case ETD_TG_TN: hipLaunchKernelGGL((k_tgemm<false, false>), grid, block, 0, st, M, N, K, A, 1LL, (long long)lda, B, (long long)ldb, 1LL, bias, C, ldc, acc); break;
-    default: ETD_FAIL(ETD_EINVAL, "tgemm: unknown form %d", form);
-  }
-  HIP_TRY(hipGetLastError());
-  return ETD_OK;
-}
 
 // ================================================================================================
 // attention: one row per lane, the other side's tile in LDS (every lane reads the same LDS address: a broadcast)
@@ -349,60 +248,6 @@ __global__ void k_trope(float* __restrict__ qkv, int nh, int M, const int* __res
   p[i + 8] = x2 * c + x1 * sn;
 }
 
-// LayerNorm statistics of each row + up to two normalised outputs (the two LayerNorms of a GPT-NeoX layer read the same input).  One wave per row.
-__global__ __launch_bounds__(64) void k_tln_fwd(const float* __restrict__ x, int M, int H, float eps, float* __restrict__ mean, float* __restrict__ rstd,
-                                                const float* __restrict__ g1, const float* __restrict__ b1, float* __restrict__ y1,
-                                                const float* __restrict__ g2, const float* __restrict__ b2, float* __restrict__ y2) {
-  const int r = blockIdx.x, lane = threadIdx.x;
-  const float* xr = x + (long long)r * H;
-  float s = 0.f;
-  for (int c = lane; c < H; c += 64) s += xr[c];
-  const float mu = wave_sum(s) / (float)H;
-  float q = 0.f;
-  for (int c = lane; c < H; c += 64) { const float d = xr[c] - mu; q = fmaf(d, d, q); }
-  const float rs = 1.f / sqrtf(wave_sum(q) / (float)H + eps);
-  if (lane == 0 && mean) { mean[r] = mu; rstd[r] = rs; }
-  for (int c = lane; c < H; c += 64) {
-    const float xh = (xr[c] - mu) * rs;
-    if (y1) y1[(long long)r * H + c] = xh * g1[c] + b1[c];
-    if (y2) y2[(long long)r * H + c] = xh * g2[c] + b2[c];
-  }
-}
-// dx += rstd * (dy g - mean(dy g) - xhat mean(dy g xhat)); one wave per row
-__global__ __launch_bounds__(64) void k_tln_bwd(const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ mean,
-                                                const float* __restrict__ rstd, const float* __restrict__ g, int H, float* __restrict__ dx) {
-  const int r = blockIdx.x, lane = threadIdx.x;
-  const float* xr = x + (long long)r * H;
-  const float* dr = dy + (long long)r * H;
-  const float mu = mean[r], rs = rstd[r];
-  float a = 0.f, b = 0.f;
-  for (int c = lane; c < H; c += 64) {
-    const float dg = dr[c] * g[c];
-    a += dg;
-    b = fmaf(dg, (xr[c] - mu) * rs, b);
-  }
-  a = wave_sum(a) / (float)H;
-  b = wave_sum(b) / (float)H;
-  for (int c = lane; c < H; c += 64) {
-    const float xh = (xr[c] - mu) * rs;
-    dx[(long long)r * H + c] += rs * (dr[c] * g[c] - a - xh * b);
-  }
-}
-
-__device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
-__global__ void k_tgelu(const float* __restrict__ x, float* __restrict__ y, long long n) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) y[i] = gelu_f(x[i]);
-}
-// dy *= gelu'(x) = Phi(x) + x phi(x)
-__global__ void k_tgelu_bwd(const float* __restrict__ x, float* __restrict__ dy, long long n) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float v = x[i];
-  const float cdf = 0.5f * (1.f + erff(v * 0.70710678118654752440f));
-  const float pdf = 0.39894228040143267794f * expf(-0.5f * v * v);
-  dy[i] *= cdf + v * pdf;
-}
 // h_next = (mlp + attn) + h: the order of HF's parallel residual
 __global__ void k_tadd3(const float* __restrict__ m, const float* __restrict__ a, const float* __restrict__ h, float* __restrict__ out, long long n) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -452,30 +297,6 @@ __global__ __launch_bounds__(64) void k_tce(float* __restrict__ logits, int V, c
   if (lane == 0) row_loss[r] = (mx + logf(s)) - at;
 }
 
-// Column reductions over the batch rows: 32 columns x 8 row slices per workgroup; slice s adds rows s, s + 8, .. in ascending order and the 8 partial sums are
-// added in slice order.  MODE 0: g0[c] += sum_r dy[r][c] (a bias gradient).  MODE 1: also g1[c] += sum_r dy[r][c] xhat[r][c] (LayerNorm: g0 = bias, g1 = gain).
-template <int MODE>
-__global__ __launch_bounds__(256) void k_tcolred(const float* __restrict__ dy, int ld, int M, int N, const float* __restrict__ x, const float* __restrict__ mean,
-                                                 const float* __restrict__ rstd, float* __restrict__ g0, float* __restrict__ g1) {
-  __shared__ float p0[8][32], p1[8][32];
-  const int t = threadIdx.x, c = blockIdx.x * 32 + (t & 31), s = t >> 5;
-  float a0 = 0.f, a1 = 0.f;
-  if (c < N)
-    for (int r = s; r < M; r += 8) {
-      const float v = dy[(long long)r * ld + c];
-      a0 += v;
-      if (MODE == 1) a1 = fmaf(v, (x[(long long)r * N + c] - mean[r]) * rstd[r], a1);
-    }
-  p0[s][t & 31] = a0; p1[s][t & 31] = a1;
-  __syncthreads();
-  if (s == 0 && c < N) {
-    float t0 = p0[0][t], t1 = p1[0][t];
-    for (int k = 1; k < 8; ++k) { t0 += p0[k][t]; t1 += p1[k][t]; }
-    g0[c] += t0;
-    if (MODE == 1) g1[c] += t1;
-  }
-}
-
 // Embedding gradients.  The batch rows are grouped by table row on the host (a stable counting sort): segment g = rows order[start[g] .. start[g] + count[g]) ascending,
 // all with index seg_id[g]; the padding row has no segment.  grid (segments, column blocks of 64), 4 row slices, summed as in k_tcolred.
 __global__ __launch_bounds__(256) void k_tembed_grad(const float* __restrict__ src, int ld, int col0, int width, const int* __restrict__ order,
@@ -493,45 +314,11 @@ __global__ __launch_bounds__(256) void k_tembed_grad(const float* __restrict__ s
 }
 
 // ================================================================================================
-// optimizer
-// ================================================================================================
-// (the gradient norm, mul_scalar and the step's scalars: train_optim.h)
-#pragma clang fp contract(off)
-// clip_grad_norm_'s g *= coef, then torch.optim.AdamW's single-tensor step, one element per thread.  1 - beta1 and 1 - beta2 arrive as the host's double differences
-// rounded once, as torch passes them: formed here from the rounded betas, 1.f - 0.98f is 9.5e-7 (relative) short of 0.02 and every update 7e-7 too long -- a bias
-// that showed as a loss below the fp64 trajectory's at every step.
-__global__ void k_tadamw(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long long n, float coef, float decay,
-                         float one_minus_beta1, float beta2, float one_minus_beta2, float step_size, float bc2_sqrt, float eps) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float gi = mul_scalar(g[i], coef);
-  float pi = mul_scalar(p[i], decay);                                  // p.mul_(1 - lr * weight_decay)
-  const float mi = m[i] + mul_scalar(gi - m[i], one_minus_beta1);       // exp_avg.lerp_(grad, 1 - beta1)
-  const float vi = mul_scalar(v[i], beta2) + mul_scalar(one_minus_beta2, gi) * gi;   // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
-  const float denom = sqrtf(vi) / bc2_sqrt + eps;
-  pi = pi - step_size * (mi / denom);                        // p.addcdiv_(exp_avg, denom, value = -step_size)
-  p[i] = pi; g[i] = gi; m[i] = mi; v[i] = vi;
-}
-#pragma clang fp contract(on)
-
-// ================================================================================================
 // launchers: each kernel above with its grid and block, called by the engine and by the stage taps at the end of this file
 // ================================================================================================
-static inline dim3 ew_grid(long long n) { return dim3((unsigned)((n + 255) / 256)); }
-
 static void launch_trope(float* qkv, int nh, int M, const int* pos, const float* tab, float sign, hipStream_t st) {
   hipLaunchKernelGGL(k_trope, ew_grid((long long)M * nh * 16), dim3(256), 0, st, qkv, nh, M, pos, tab, sign);
 }
-// mean / rstd (both or neither) and the second output may be NULL
-void launch_tln_fwd(const float* x, int M, int H, float eps, float* mean, float* rstd, const float* g1, const float* b1, float* y1, const float* g2,
-                           const float* b2, float* y2, hipStream_t st) {
-  hipLaunchKernelGGL(k_tln_fwd, dim3(M), dim3(64), 0, st, x, M, H, eps, mean, rstd, g1, b1, y1, g2, b2, y2);
-}
-void launch_tln_bwd(const float* dy, const float* x, const float* mean, const float* rstd, const float* g, int M, int H, float* dx, hipStream_t st) {
-  hipLaunchKernelGGL(k_tln_bwd, dim3(M), dim3(64), 0, st, dy, x, mean, rstd, g, H, dx);
-}
-void launch_tgelu(const float* x, float* y, long long n, hipStream_t st) { hipLaunchKernelGGL(k_tgelu, ew_grid(n), dim3(256), 0, st, x, y, n); }
-void launch_tgelu_bwd(const float* x, float* dy, long long n, hipStream_t st) { hipLaunchKernelGGL(k_tgelu_bwd, ew_grid(n), dim3(256), 0, st, x, dy, n); }
 static void launch_tadd3(const float* m, const float* a, const float* h, float* out, long long n, hipStream_t st) {
   hipLaunchKernelGGL(k_tadd3, ew_grid(n), dim3(256), 0, st, m, a, h, out, n);
 }
@@ -545,71 +332,35 @@ static void launch_tembed_sum(const int* ids, const int* cls, const float* word,
 static void launch_tce(float* logits, int M, int V, const int* labels, float scale, float* row_loss, hipStream_t st) {
   hipLaunchKernelGGL(k_tce, dim3(M), dim3(64), 0, st, logits, V, labels, scale, row_loss);
 }
-// mode 0: x, mean, rstd and g1 are not read (NULL)
-void launch_tcolred(int mode, const float* dy, int ld, int M, int N, const float* x, const float* mean, const float* rstd, float* g0, float* g1,
-                           hipStream_t st) {
-  const dim3 grid((N + 31) / 32), block(256);
-  if (mode == 1) hipLaunchKernelGGL(k_tcolred<1>, grid, block, 0, st, dy, ld, M, N, x, mean, rstd, g0, g1);
-  else hipLaunchKernelGGL(k_tcolred<0>, grid, block, 0, st, dy, ld, M, N, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, g0, (float*)nullptr);
-}
 // grad [.][width] += the rows of src [.][ld] at columns [col0, col0 + width), by segment; a table none of whose rows has a segment is not launched
 static void launch_tembed_grad(const float* src, int ld, int col0, int width, const int* order, const int* seg_id, const int* seg_start, const int* seg_count,
                                int n_seg, float* grad, hipStream_t st) {
   if (n_seg > 0) hipLaunchKernelGGL(k_tembed_grad, dim3(n_seg, (width + 63) / 64), dim3(256), 0, st, src, ld, col0, width, order, seg_id, seg_start, seg_count, grad);
 }
 
-// the arguments of k_tadamw for optimizer step `step` (1-based): the step's scalars (train_optim.h) and the hyper-parameters, each a double rounded once
-// (struct AdamwArgs: dec_train.h)
-int adamw_check(const char* who, double lr, double beta1, double beta2, double eps, double weight_decay) {
-  if (!(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !(weight_decay >= 0.0))
-    ETD_FAIL(ETD_EINVAL, "%s: lr, eps, weight_decay must be >= 0 and the betas in [0, 1)", who);
-  return ETD_OK;
-}
-AdamwArgs adamw_args(double max_norm, double norm, double lr, double beta1, double beta2, double eps, double weight_decay, long long step) {
-  const StepScalars s = step_scalars(max_norm, norm, lr, beta1, beta2, step);
-  return {s.coef, (float)(1.0 - lr * weight_decay), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), s.step_size, s.bc2_sqrt, (float)eps};
-}
-void launch_tadamw(float* p, float* g, float* m, float* v, long long n, const AdamwArgs& a, hipStream_t st) {
-  hipLaunchKernelGGL(k_tadamw, ew_grid(n), dim3(256), 0, st, p, g, m, v, n, a.coef, a.decay, a.one_minus_beta1, a.beta2, a.one_minus_beta2, a.step_size, a.bc2_sqrt, a.eps);
-}
-
 // ================================================================================================
 // the engine
 // ================================================================================================
-struct TParam { std::string name; size_t off, n; };
 struct TLayer { size_t ln1_w, ln1_b, ln2_w, ln2_b, qkv_w, qkv_b, d_w, d_b, f1_w, f1_b, f2_w, f2_b; };
 
 struct etd_dtrain {
   etd_dec_cfg cfg;
   int pad_token = 0, pad_class = 0, pad_attr = 0, max_rows = 0;
   int V = 0, H = 0, I = 0, L = 0, nh = 0, E = 0, NB = 0, NC = 0;
-  std::vector<TParam> params;
-  std::map<std::string, int> index;
-  size_t n_total = 0, n_train = 0;                    // floats in the flat buffers; the first n_train are trained (transformer.embed_in.weight sits behind them)
+  TrainStore ps;                                      // the first n_train floats are trained; transformer.embed_in.weight sits behind them
   size_t word = 0, cemb = 0, attr[4] = {0, 0, 0, 0}, proj_w = 0, proj_b = 0, lnf_w = 0, lnf_b = 0, head = 0;
   std::vector<TLayer> layers;
-  float *P = nullptr, *G = nullptr, *M1 = nullptr, *M2 = nullptr;
   // saved activations
   float *A4 = nullptr, *dA4 = nullptr, *hs = nullptr, *mean = nullptr, *rstd = nullptr, *qkv = nullptr, *lse = nullptr, *att = nullptr, *pre = nullptr, *hf = nullptr;
   // workspace
   float *logits = nullptr, *wI = nullptr, *wH1 = nullptr, *wH2 = nullptr, *wH3 = nullptr, *dqkv = nullptr, *Dbuf = nullptr, *row_loss = nullptr, *rope = nullptr;
-  double* partial = nullptr;
   int* ints = nullptr;
   size_t n_ints = 0;
   std::vector<float> h_row_loss;
   std::vector<int> h_ints;
-  long long step = 0;
   size_t workspace_bytes = 0;
   DevPool pool;
 };
-
-static size_t tp_add(etd_dtrain* d, const std::string& name, size_t n) {
-  const size_t off = d->n_total;
-  d->index[name] = (int)d->params.size();
-  d->params.push_back({name, off, n});
-  d->n_total += (n + 63) / 64 * 64;                    // 256-byte alignment of every tensor; the gaps stay 0 in all four buffers
-  return off;
-}
 
 static int dtrain_check_cfg(const etd_dec_cfg* c, int max_rows) {
   if (!c) ETD_FAIL(ETD_EINVAL, "etd_dtrain_create: null config");
@@ -648,38 +399,35 @@ extern "C" int etd_dtrain_create(const etd_dec_cfg* cfg, const char* const* name
   d->V = c.vocab_size; d->H = c.hidden_size; d->I = c.intermediate_size; d->L = c.num_hidden_layers; d->nh = c.num_attention_heads;
   d->E = c.attribute_emb_dim; d->NB = c.num_attribute_bins; d->NC = c.num_classes;
   const size_t V = d->V, H = d->H, I = d->I, E = d->E;
-  d->word = tp_add(d, "word_embeddings.weight", V * H);
-  d->cemb = tp_add(d, "class_embeddings.weight", (size_t)d->NC * H);
+  TrainStore& ps = d->ps;
+  d->word = ps.add("word_embeddings.weight", V * H);
+  d->cemb = ps.add("class_embeddings.weight", (size_t)d->NC * H);
   static const char* attr_names[4] = {"pitch_overlap", "polyphony", "note_sustain", "rhythm_intensity"};      // the concat order of etude_decoder.py:171-176
-  for (int k = 0; k < 4; ++k) d->attr[k] = tp_add(d, std::string(attr_names[k]) + "_embeddings.weight", (size_t)d->NB * E);
-  d->proj_w = tp_add(d, "attribute_projection.weight", H * 4 * E);
-  d->proj_b = tp_add(d, "attribute_projection.bias", H);
+  for (int k = 0; k < 4; ++k) d->attr[k] = ps.add(std::string(attr_names[k]) + "_embeddings.weight", (size_t)d->NB * E);
+  d->proj_w = ps.add("attribute_projection.weight", H * 4 * E);
+  d->proj_b = ps.add("attribute_projection.bias", H);
   for (int i = 0; i < d->L; ++i) {
     const std::string p = "transformer.layers." + std::to_string(i) + ".";
     TLayer y;
-    y.ln1_w = tp_add(d, p + "input_layernorm.weight", H); y.ln1_b = tp_add(d, p + "input_layernorm.bias", H);
-    y.ln2_w = tp_add(d, p + "post_attention_layernorm.weight", H); y.ln2_b = tp_add(d, p + "post_attention_layernorm.bias", H);
-    y.qkv_w = tp_add(d, p + "attention.query_key_value.weight", 3 * H * H); y.qkv_b = tp_add(d, p + "attention.query_key_value.bias", 3 * H);
-    y.d_w = tp_add(d, p + "attention.dense.weight", H * H); y.d_b = tp_add(d, p + "attention.dense.bias", H);
-    y.f1_w = tp_add(d, p + "mlp.dense_h_to_4h.weight", I * H); y.f1_b = tp_add(d, p + "mlp.dense_h_to_4h.bias", I);
-    y.f2_w = tp_add(d, p + "mlp.dense_4h_to_h.weight", H * I); y.f2_b = tp_add(d, p + "mlp.dense_4h_to_h.bias", H);
+    y.ln1_w = ps.add(p + "input_layernorm.weight", H); y.ln1_b = ps.add(p + "input_layernorm.bias", H);
+    y.ln2_w = ps.add(p + "post_attention_layernorm.weight", H); y.ln2_b = ps.add(p + "post_attention_layernorm.bias", H);
+    y.qkv_w = ps.add(p + "attention.query_key_value.weight", 3 * H * H); y.qkv_b = ps.add(p + "attention.query_key_value.bias", 3 * H);
+    y.d_w = ps.add(p + "attention.dense.weight", H * H); y.d_b = ps.add(p + "attention.dense.bias", H);
+    y.f1_w = ps.add(p + "mlp.dense_h_to_4h.weight", I * H); y.f1_b = ps.add(p + "mlp.dense_h_to_4h.bias", I);
+    y.f2_w = ps.add(p + "mlp.dense_4h_to_h.weight", H * I); y.f2_b = ps.add(p + "mlp.dense_4h_to_h.bias", H);
     d->layers.push_back(y);
   }
-  d->lnf_w = tp_add(d, "transformer.final_layer_norm.weight", H);
-  d->lnf_b = tp_add(d, "transformer.final_layer_norm.bias", H);
-  d->head = tp_add(d, "lm_head.weight", V * H);
-  d->n_train = d->n_total;
+  d->lnf_w = ps.add("transformer.final_layer_norm.weight", H);
+  d->lnf_b = ps.add("transformer.final_layer_norm.bias", H);
+  d->head = ps.add("lm_head.weight", V * H);
+  ps.n_train = ps.n_total;
   // GPTNeoXModel's own token table: part of the state dict, never read (the model is fed inputs_embeds), so autograd gives it no gradient and
   // torch.optim.AdamW leaves it alone, weight decay included.  It is kept, saved and never changed.
-  tp_add(d, "transformer.embed_in.weight", V * H);
+  ps.add("transformer.embed_in.weight", V * H);
   // host image of the parameters, checked before the device is touched
   WeightTable wt(names, host_ptrs, numels, n);
-  std::vector<float> host(d->n_total, 0.f);
-  for (const TParam& p : d->params) {
-    const float* src = wt.get(p.name, (int64_t)p.n);
-    if (!src) return fail(ETD_EINVAL);
-    memcpy(host.data() + p.off, src, p.n * sizeof(float));
-  }
+  std::vector<float> host(ps.n_total, 0.f);
+  ETD_TRY_OR(fail, ps.fill(wt, host.data()));
   std::vector<float> rope((size_t)c.max_position_embeddings * 16);
   for (int pos = 0; pos < c.max_position_embeddings; ++pos)
     for (int i = 0; i < 8; ++i) {                      // modeling_gpt_neox.py:72-109 in fp32: inv_freq, pos * inv_freq, then cos / sin of that fp32 angle
@@ -690,10 +438,7 @@ extern "C" int etd_dtrain_create(const etd_dec_cfg* cfg, const char* const* name
     }
   // ---- device
   DevPool& pl = d->pool;
-  ETD_TRY_OR(fail, (pl.upload<float, float>(&d->P, host.data(), d->n_total)));
-  ETD_TRY_OR(fail, pl.alloc(&d->G, d->n_total, true));
-  ETD_TRY_OR(fail, pl.alloc(&d->M1, d->n_total, true));
-  ETD_TRY_OR(fail, pl.alloc(&d->M2, d->n_total, true));
+  ETD_TRY_OR(fail, ps.upload(pl, host.data(), ps.n_total));
   ETD_TRY_OR(fail, (pl.upload<float, float>(&d->rope, rope.data(), rope.size())));
   const size_t R = (size_t)max_rows, Lz = (size_t)d->L, nh = (size_t)d->nh;
   const size_t before = pl.mark();
@@ -715,7 +460,7 @@ extern "C" int etd_dtrain_create(const etd_dec_cfg* cfg, const char* const* name
   ETD_TRY_OR(fail, pl.alloc(&d->dqkv, R * 3 * H));
   ETD_TRY_OR(fail, pl.alloc(&d->Dbuf, R * nh));
   ETD_TRY_OR(fail, pl.alloc(&d->row_loss, R));
-  ETD_TRY_OR(fail, pl.alloc(&d->partial, (size_t)TN_BLOCKS));
+  ETD_TRY_OR(fail, pl.alloc(&ps.partial, (size_t)TN_BLOCKS));
   // ints: ids, cls, attrs4 [4], labels, pos (8 R) | row0, len (2 R) | six sort orders (6 R) | segments: id, start, count of at most V + NC + 4 NB table rows
   d->n_ints = 16 * R + 3 * (V + (size_t)d->NC + 4 * (size_t)d->NB);
   ETD_TRY_OR(fail, pl.alloc(&d->ints, d->n_ints));
@@ -733,7 +478,7 @@ extern "C" void etd_dtrain_destroy(etd_dtrain* d) {
 
 extern "C" long long etd_dtrain_bytes(const etd_dtrain* d, int what) {
   if (!d) return ETD_EINVAL;
-  return what == 0 ? (long long)d->workspace_bytes : (long long)(4 * d->n_total * sizeof(float));      // 0: activations + scratch; 1: weights, gradients, two moments
+  return what == 0 ? (long long)d->workspace_bytes : (long long)(4 * d->ps.n_total * sizeof(float));      // 0: activations + scratch; 1: weights, gradients, two moments
 }
 
 // stable grouping of M rows by table index: order / segments appended to `ints` at (o_order, o_seg ..); returns the number of segments (the padding row has none)
@@ -806,8 +551,8 @@ extern "C" int etd_dtrain_forward_backward(etd_dtrain* d, int n, const int32_t* 
   const int* ii = d->ints;
   const int *d_ids = ii, *d_cls = ii + R, *d_at = ii + 2 * R, *d_lab = ii + 6 * R, *d_pos = ii + 7 * R, *d_row0 = ii + 8 * R, *d_len = ii + 9 * R, *d_ord = ii + 10 * R;
   const int *d_sid = ii + 16 * R, *d_sst = d_sid + seg_cap, *d_scn = d_sid + 2 * seg_cap;
-  float* P = d->P;
-  float* G = d->G;
+  float* P = d->ps.P;
+  float* G = d->ps.G;
   const long long MH = (long long)M * H, MI = (long long)M * I;
   const float eps = d->cfg.layer_norm_eps;
   // ================================================================ forward
@@ -904,59 +649,41 @@ extern "C" int etd_dtrain_forward_backward(etd_dtrain* d, int n, const int32_t* 
 
 extern "C" int etd_dtrain_zero_grad(etd_dtrain* d, void* stream) {
   if (!d) ETD_FAIL(ETD_EINVAL, "etd_dtrain_zero_grad: null handle");
-  HIP_TRY(hipMemsetAsync(d->G, 0, sizeof(float) * d->n_total, (hipStream_t)stream));
-  return ETD_OK;
+  return d->ps.zero_grad(d->ps.n_total, (hipStream_t)stream);
 }
 
 extern "C" int etd_dtrain_grad_norm(etd_dtrain* d, double* norm, void* stream) {
   if (!d || !norm) ETD_FAIL(ETD_EINVAL, "etd_dtrain_grad_norm: null argument");
-  return grad_norm(d->G, (long long)d->n_train, d->partial, (hipStream_t)stream, norm);
+  return d->ps.grad_norm(d->ps.n_train, (hipStream_t)stream, norm);
 }
 
 extern "C" int etd_dtrain_clip_and_step(etd_dtrain* d, double max_norm, double lr, double beta1, double beta2, double eps, double weight_decay, double* norm_out,
                                         void* stream) {
   if (!d) ETD_FAIL(ETD_EINVAL, "etd_dtrain_clip_and_step: null handle");
-  ETD_TRY(adamw_check("etd_dtrain_clip_and_step", lr, beta1, beta2, eps, weight_decay));
-  hipStream_t st = (hipStream_t)stream;
-  ProfScope ps("dtrain_optimizer", st);
-  double norm = 0.0;
-  const long long n = (long long)d->n_train;
-  ETD_TRY(grad_norm(d->G, n, d->partial, st, &norm));
-  if (norm_out) *norm_out = norm;
-  d->step += 1;
-  launch_tadamw(d->P, d->G, d->M1, d->M2, n, adamw_args(max_norm, norm, lr, beta1, beta2, eps, weight_decay, d->step), st);
-  HIP_TRY(hipGetLastError());
-  return ETD_OK;
+  return adamw_step(d->ps, d->ps.n_train, "etd_dtrain_clip_and_step", "dtrain_optimizer", max_norm, lr, beta1, beta2, eps, weight_decay, norm_out, (hipStream_t)stream);
 }
 
 extern "C" int etd_dtrain_set_step(etd_dtrain* d, long long step) {
   if (!d || step < 0) ETD_FAIL(ETD_EINVAL, "etd_dtrain_set_step: null handle or negative step");
-  d->step = step;
+  d->ps.step = step;
   return ETD_OK;
 }
-extern "C" long long etd_dtrain_get_step(const etd_dtrain* d) { return d ? d->step : ETD_EINVAL; }
+extern "C" long long etd_dtrain_get_step(const etd_dtrain* d) { return d ? d->ps.step : ETD_EINVAL; }
 
-// which: 0 parameter, 1 gradient, 2 exp_avg, 3 exp_avg_sq
-static int dtrain_io(etd_dtrain* d, const char* name, int which, float* out, const float* in, long long numel, hipStream_t st) {
-  if (!d || !name || (!out && !in)) ETD_FAIL(ETD_EINVAL, "etd_dtrain: null argument");
-  auto it = d->index.find(name);
-  if (it == d->index.end()) ETD_FAIL(ETD_EINVAL, "etd_dtrain: no parameter '%s'", name);
-  const TParam& p = d->params[it->second];
-  if ((long long)p.n != numel) ETD_FAIL(ETD_EINVAL, "etd_dtrain: '%s' has %zu elements, the buffer %lld", name, p.n, numel);
-  return flat_io(d->P, d->G, d->M1, d->M2, which, (long long)p.off, (long long)p.n, out, in, st);
-}
+static TrainStore* dstore(etd_dtrain* d) { return d ? &d->ps : nullptr; }      // (train_io refuses a null handle with its other null arguments)
 extern "C" int etd_dtrain_read_param(etd_dtrain* d, const char* name, float* out_host, long long numel, void* stream) {
-  return dtrain_io(d, name, 0, out_host, nullptr, numel, (hipStream_t)stream);
+  return train_io(dstore(d), "etd_dtrain", name, 0, out_host, nullptr, numel, (hipStream_t)stream);
 }
 extern "C" int etd_dtrain_read_grad(etd_dtrain* d, const char* name, float* out_host, long long numel, void* stream) {
-  return dtrain_io(d, name, 1, out_host, nullptr, numel, (hipStream_t)stream);
+  return train_io(dstore(d), "etd_dtrain", name, 1, out_host, nullptr, numel, (hipStream_t)stream);
 }
 extern "C" int etd_dtrain_read_moment(etd_dtrain* d, const char* name, int second, float* out_host, long long numel, void* stream) {
-  return dtrain_io(d, name, second ? 3 : 2, out_host, nullptr, numel, (hipStream_t)stream);
+  return train_io(dstore(d), "etd_dtrain", name, second ? 3 : 2, out_host, nullptr, numel, (hipStream_t)stream);
 }
 extern "C" int etd_dtrain_write_moment(etd_dtrain* d, const char* name, int second, const float* in_host, long long numel, void* stream) {
-  return dtrain_io(d, name, second ? 3 : 2, nullptr, in_host, numel, (hipStream_t)stream);
+  return train_io(dstore(d), "etd_dtrain", name, second ? 3 : 2, nullptr, in_host, numel, (hipStream_t)stream);
 }
+
 // ================================================================================================
 // debug entries (include/etude_hip_debug.h): the two kernels with tile edges, on their own inputs
 // ================================================================================================

@@ -12,7 +12,7 @@
 //                           ST_COL_ROWS rows per workgroup, joined in chunk order in fp64
 //   k_st_ew                 normalise + ELU (encoder), ELU + normalise (decoder) and their backward passes, xhat recomputed from the saved pre-norm tensor
 //   k_st_loss               softmax over the instruments, |s_i mix - target_i| partials and dlogits in one pass
-//   k_tsumsq / k_st_adam    the gradient norm dec_train.hip uses (train_optim.h) and torch.optim.Adam's step
+//   k_tsumsq / k_st_adam    the trainers' gradient norm (train_kernels.h) and torch.optim.Adam's step
 //   k_st_dropout            decoder dropout (levels 1 .. 3, only when p > 0): y <- keep ? y s : 0 in place with a Philox4x32-10 mask that is a function of the element
 //                           index, the level, the seed and the call counter; the backward pass runs the same kernel on dy, so no mask is stored
 //
@@ -21,11 +21,10 @@
 
 #include <algorithm>
 #include <cmath>
-#include <map>
 #include <string>
 
 #include "etude_hip_debug.h"
-#include "train_optim.h"
+#include "train_store.h"
 
 namespace {
 
@@ -315,7 +314,7 @@ __global__ __launch_bounds__(256) void k_st_loss(const float* __restrict__ logit
   if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
 }
 
-// ================================================================================================ optimizer (the norm and the scalars: train_optim.h)
+// ================================================================================================ optimizer (the norm and the scalars: train_kernels.h)
 #pragma clang fp contract(off)
 // g *= coef (clipping; 1 without), then torch.optim.Adam's single-tensor step.  1 - beta arrive as the host's double differences rounded once.
 __global__ void k_st_adam(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long long n, float coef, float one_minus_beta1,
@@ -343,17 +342,13 @@ struct etd_septrain {
   long long plane = 0, szmax = 0;      // floats of a segment and of the largest tensor of a unit
   StPar conv_w[ETD_SEP_LEVELS + 1], conv_b[ETD_SEP_LEVELS + 1], dec_w[ETD_SEP_LEVELS + 1], dec_b[ETD_SEP_LEVELS + 1], head_w, head_b;
   long long gam0 = 0, bet0 = 0, noff[2 * ETD_SEP_LEVELS + 2], NS = 0;                   // norm n's [I][C_n] block starts at noff[n] of every [NS] array
-  long long n_train = 0, n_total = 0;                                                   // P = [trainable | running mean [NS] | running var [NS]]
-  std::map<std::string, std::pair<long long, long long>> index;                        // state key -> (offset in P, elements)
-  std::vector<float> hP;
+  TrainStore ps;                       // P = [trainable (n_train) | running mean [NS] | running var [NS]]; G, M1 and M2 hold the trainable part only
+  std::vector<float> hP;               // the state until the first device call uploads it
   std::vector<float> h_loss;
   DevPool pool;
-  float *P = nullptr, *G = nullptr, *M1 = nullptr, *M2 = nullptr;
   double* S = nullptr;                                                                  // the norms' statistics in fp64: [mean | rstd | m1 | m2 | var], [NS] each
   float *dec_pk[ETD_SEP_LEVELS + 1][4], *conv_pk[ETD_SEP_LEVELS + 1][4];
-  double* norm_part = nullptr;
   bool pack_dirty = true;
-  long long step = 0;
   double drop_p = 0.0; unsigned long long drop_seed = 0; long long drop_calls = 0;      // decoder dropout: off at p = 0; drop_calls counts the backward calls with p > 0
   Workspace ws;
   int normC(int n) const { return n <= ETD_SEP_LEVELS ? net.Cenc[n] : net.Cdout[n - ETD_SEP_LEVELS]; }
@@ -417,12 +412,9 @@ int st_check_batch(const etd_septrain* h, int B, StPlan* p, const char* who) {
 int st_upload(etd_septrain* h) {
   DevPool& Q = h->pool;
   return Q.upload_once([&]() -> int {
-    ETD_TRY(Q.upload(&h->P, h->hP.data(), h->hP.size()));
-    ETD_TRY(Q.alloc(&h->G, (size_t)h->n_train, true));
-    ETD_TRY(Q.alloc(&h->M1, (size_t)h->n_train, true));
-    ETD_TRY(Q.alloc(&h->M2, (size_t)h->n_train, true));
+    ETD_TRY(h->ps.upload(Q, h->hP.data(), h->ps.n_train));
     ETD_TRY(Q.alloc(&h->S, (size_t)(5 * h->NS), true));
-    ETD_TRY(Q.alloc(&h->norm_part, (size_t)TN_BLOCKS));
+    ETD_TRY(Q.alloc(&h->ps.partial, (size_t)TN_BLOCKS));
     for (int l = 1; l <= ETD_SEP_LEVELS; ++l)
       for (int par = 0; par < 4; ++par) {
         const long long taps = sep_dec_taps(par >> 1) * sep_dec_taps(par & 1);
@@ -443,12 +435,12 @@ int st_pack(etd_septrain* h, hipStream_t st) {
       {      // deconv l: [kt][kf][co][ci] -> [a][b][ci][co]
         const int Di = h->net.Cenc[7 - l] + (l > 1 ? h->net.Cdout[l - 1] : 0), Do = h->net.Cdout[l];
         const long long total = (long long)h->I * nt * nf * Di * Do;
-        hipLaunchKernelGGL(k_st_pack, dim3(st_grid(total)), dim3(256), 0, st, h->P + h->dec_w[l].off, h->dec_pk[l][par], pt, pf, nt, nf, Di, Do, h->dec_w[l].per, total);
+        hipLaunchKernelGGL(k_st_pack, dim3(st_grid(total)), dim3(256), 0, st, h->ps.P + h->dec_w[l].off, h->dec_pk[l][par], pt, pf, nt, nf, Di, Do, h->dec_w[l].per, total);
       }
       if (l > 1) {      // conv l: [kt][kf][ci][co] -> [a][b][co][ci]
         const int Ci = h->net.Cenc[l - 1], Co = h->net.Cenc[l];
         const long long total = (long long)h->I * nt * nf * Ci * Co;
-        hipLaunchKernelGGL(k_st_pack, dim3(st_grid(total)), dim3(256), 0, st, h->P + h->conv_w[l].off, h->conv_pk[l][par], pt, pf, nt, nf, Co, Ci, h->conv_w[l].per, total);
+        hipLaunchKernelGGL(k_st_pack, dim3(st_grid(total)), dim3(256), 0, st, h->ps.P + h->conv_w[l].off, h->conv_pk[l][par], pt, pf, nt, nf, Co, Ci, h->conv_w[l].per, total);
       }
     }
   HIP_TRY(hipGetLastError());
@@ -473,7 +465,7 @@ int st_fwd_encoder(etd_septrain* h, int l, const float* x, float* pre, int U, hi
   sep_geom_encoder(h->net, l, &a);
   a.x0 = x;
   if (l == 1) { a.x0_us = h->plane; a.x0_div = h->I; } else { a.x0_us = h->net.szE[l - 1]; }
-  a.W = h->P + h->conv_w[l].off; a.w_is = h->conv_w[l].per; a.bias = h->P + h->conv_b[l].off;
+  a.W = h->ps.P + h->conv_w[l].off; a.w_is = h->conv_w[l].per; a.bias = h->ps.P + h->conv_b[l].off;
   return st_launch(a, pre, h->net.szE[l], U, false, st);
 }
 
@@ -483,7 +475,7 @@ int st_fwd_decoder(etd_septrain* h, int j, const float* skip, const float* up, f
     sep_geom_deconv(h->net, j, par >> 1, par & 1, &a);
     a.x0 = skip; a.x0_us = h->net.szE[7 - j];
     a.x1 = j > 1 ? up : nullptr; a.x1_us = j > 1 ? h->net.szD[j - 1] : 0;
-    a.W = h->dec_pk[j][par]; a.w_is = (long long)a.nt * a.nf * (a.C0 + a.C1) * a.N; a.bias = h->P + h->dec_b[j].off;
+    a.W = h->dec_pk[j][par]; a.w_is = (long long)a.nt * a.nf * (a.C0 + a.C1) * a.N; a.bias = h->ps.P + h->dec_b[j].off;
     ETD_TRY(st_launch(a, v, h->net.szD[j], U, false, st));
   }
   return ETD_OK;
@@ -493,7 +485,7 @@ int st_fwd_head(etd_septrain* h, const float* x, float* logits, int U, hipStream
   SepLaunch a = st_conv_base(h);
   sep_geom_head(h->net, &a);
   a.x0 = x; a.x0_us = (long long)h->cfg.T * h->cfg.F;
-  a.W = h->P + h->head_w.off; a.w_is = h->head_w.per; a.bias = h->P + h->head_b.off;
+  a.W = h->ps.P + h->head_w.off; a.w_is = h->head_w.per; a.bias = h->ps.P + h->head_b.off;
   return st_launch(a, logits, h->plane, U, true, st);
 }
 
@@ -525,7 +517,7 @@ int st_dx_decoder(etd_septrain* h, int j, const float* dv, float* dskip, float* 
   SepLaunch a = st_geom_dv(h, j);
   a.x0 = dv; a.x0_us = h->net.szD[j];
   a.N0 = a.N; a.N = a.N0 + (j > 1 ? h->net.Cdout[j - 1] : 0);
-  a.W = h->P + h->dec_w[j].off; a.w_is = h->dec_w[j].per;      // [kt][kf][co][ci] is this GEMM's [K][N]
+  a.W = h->ps.P + h->dec_w[j].off; a.w_is = h->dec_w[j].per;      // [kt][kf][co][ci] is this GEMM's [K][N]
   a.out1 = dup; a.out1_us = j > 1 ? h->net.szD[j - 1] : 0;
   a.pre = dskip; a.out_us = h->net.szE[7 - j];
   return sep_launch(a, U, false, nullptr, st);
@@ -537,7 +529,7 @@ int st_dx_head(etd_septrain* h, const float* dlogits, float* dx, int U, hipStrea
   sep_geom_head(h->net, &a);
   a.o0t = -a.o0t; a.o0f = -a.o0f; a.d = -a.d; a.C0 = h->C; a.N = 1;
   a.x0 = dlogits; a.x0_us = h->plane;
-  a.W = h->P + h->head_w.off; a.w_is = h->head_w.per;          // [kt][kf][1][co] read as [K = (tap, co)][1]
+  a.W = h->ps.P + h->head_w.off; a.w_is = h->head_w.per;          // [kt][kf][1][co] read as [K = (tap, co)][1]
   return st_launch(a, dx, (long long)h->cfg.T * h->cfg.F, U, true, st);
 }
 
@@ -590,7 +582,7 @@ int st_col(etd_septrain* h, int mode, int n, const float* x, const float* x2, lo
   int CT = 1;
   while (CT < C && CT < 64) CT <<= 1;
   a.CT = CT;
-  if (n > 0) { a.mean = st_S(h, 0, n); a.rstd = st_S(h, 1, n); a.gamma = h->P + h->gam0 + h->noff[n]; a.beta = h->P + h->bet0 + h->noff[n]; }
+  if (n > 0) { a.mean = st_S(h, 0, n); a.rstd = st_S(h, 1, n); a.gamma = h->ps.P + h->gam0 + h->noff[n]; a.beta = h->ps.P + h->bet0 + h->noff[n]; }
   a.part = cpart;
   hipLaunchKernelGGL(k_st_col, dim3((unsigned)a.chunks, (unsigned)((C + CT - 1) / CT), (unsigned)h->I), dim3(256), 0, st, a);
   hipLaunchKernelGGL(k_st_colfin, dim3(st_grid((long long)h->I * C, 64)), dim3(64), 0, st, cpart, a.chunks, C, h->I, R, fin, h->cfg.bn_eps, frozen, o1, o2, o3, o4);
@@ -609,7 +601,7 @@ int st_ew(etd_septrain* h, int mode, int n, const float* x, const float* dy, con
   StEw a{};
   a.x = x; a.dy = dy; a.add = add; a.out = out; a.unit = unit; a.total = unit * U; a.C = h->normC(n); a.I = h->I; a.mode = mode;
   a.mean = st_S(h, 0, n); a.rstd = st_S(h, 1, n); a.m1 = st_S(h, 2, n); a.m2 = st_S(h, 3, n);
-  a.gamma = h->P + h->gam0 + h->noff[n]; a.beta = h->P + h->bet0 + h->noff[n];
+  a.gamma = h->ps.P + h->gam0 + h->noff[n]; a.beta = h->ps.P + h->bet0 + h->noff[n];
   const long long blocks = (a.total + 255) / 256;
   if (blocks > 0x7fffffffLL) ETD_FAIL(ETD_EINVAL, "separator training: an elementwise pass needs %lld workgroups (> 2^31 - 1)", blocks);
   hipLaunchKernelGGL(k_st_ew, dim3((unsigned)blocks), dim3(256), 0, st, a);
@@ -621,8 +613,8 @@ int st_ew(etd_septrain* h, int mode, int n, const float* x, const float* dy, con
 int st_norm_bwd(etd_septrain* h, int n, const float* x, const float* dy, const float* add, float* out, long long P, int B, int frozen, float* cpart, hipStream_t st) {
   const bool dec = n > ETD_SEP_LEVELS;
   const int C = h->normC(n);
-  ETD_TRY(st_col(h, dec ? ST_COL_BWD_DEC : ST_COL_BWD_ENC, n, x, dy, P, C, B, cpart, ST_FIN_BWD, frozen, st_S(h, 2, n), st_S(h, 3, n), h->G + h->bet0 + h->noff[n],
-                 h->G + h->gam0 + h->noff[n], st));
+  ETD_TRY(st_col(h, dec ? ST_COL_BWD_DEC : ST_COL_BWD_ENC, n, x, dy, P, C, B, cpart, ST_FIN_BWD, frozen, st_S(h, 2, n), st_S(h, 3, n), h->ps.G + h->bet0 + h->noff[n],
+                 h->ps.G + h->gam0 + h->noff[n], st));
   return st_ew(h, dec ? ST_EW_DEC_BWD : ST_EW_ENC_BWD, n, x, dy, add, out, P * C, B * h->I, st);
 }
 
@@ -693,15 +685,10 @@ extern "C" int etd_septrain_create(const etd_sep_cfg* cfg, int max_units, const 
   h->NS = ns;
   h->gam0 = o; o += ns;
   h->bet0 = o; o += ns;
-  h->n_train = o;
-  h->n_total = o + 2 * ns;
-  h->hP.assign((size_t)h->n_total, 0.f);
-  const WeightTable wt(names, host_ptrs, numels, n);
-  auto put = [&](const std::string& key, long long off, long long numel) {
-    const float* p = wt.get(key, numel);      // (present and of this size: etd_sep_create has checked)
-    if (p) memcpy(&h->hP[(size_t)off], p, (size_t)numel * 4);
-    h->index[key] = {off, numel};
-  };
+  const long long n_train = o;
+  h->ps.n_train = (size_t)o;
+  h->ps.n_total = (size_t)(o + 2 * ns);
+  auto put = [&](const std::string& key, long long off, long long numel) { h->ps.add_at(key, (size_t)off, (size_t)numel); };
   for (int i = 0; i < I; ++i) {
     const std::string pre = std::string(instr_names[i]) + ".";
     for (int l = 1; l <= ETD_SEP_LEVELS; ++l) {
@@ -716,12 +703,14 @@ extern "C" int etd_septrain_create(const etd_sep_cfg* cfg, int max_units, const 
       const std::string k = pre + "bn" + std::to_string(nn);
       put(k + ".gamma", h->gam0 + at, Cn);
       put(k + ".beta", h->bet0 + at, Cn);
-      put(k + ".mean", h->n_train + at, Cn);
-      put(k + ".var", h->n_train + ns + at, Cn);
+      put(k + ".mean", n_train + at, Cn);
+      put(k + ".var", n_train + ns + at, Cn);
     }
     put(pre + "head.weight", h->head_w.off + i * h->head_w.per, h->head_w.per);
     put(pre + "head.bias", h->head_b.off + i * h->head_b.per, h->head_b.per);
   }
+  h->hP.assign(h->ps.n_total, 0.f);
+  (void)h->ps.fill(WeightTable(names, host_ptrs, numels, n), h->hP.data());      // (every key is present and of this size: etd_sep_create has checked)
   *out = h;
   return ETD_OK;
 }
@@ -765,7 +754,7 @@ extern "C" int etd_septrain_forward_backward(etd_septrain* h, const float* mix, 
   float* cpart = ws + p.cpart;
   const int U = B * h->I, L = ETD_SEP_LEVELS;
   const bool drop = backward && h->drop_p > 0.0;      // never in the loss-only (validation) path
-  if (frozen_stats) hipLaunchKernelGGL(k_st_frozen, dim3(st_grid(h->NS)), dim3(256), 0, st, h->P + h->n_train, h->P + h->n_train + h->NS, h->cfg.bn_eps, (int)h->NS, h->S, h->S + h->NS);
+  if (frozen_stats) hipLaunchKernelGGL(k_st_frozen, dim3(st_grid(h->NS)), dim3(256), 0, st, h->ps.P + h->ps.n_train, h->ps.P + h->ps.n_train + h->NS, h->cfg.bn_eps, (int)h->NS, h->S, h->S + h->NS);
   // ---- forward
   for (int l = 1; l <= L; ++l) {
     ETD_TRY(st_fwd_encoder(h, l, l == 1 ? mix : ws + p.act[l - 1], ws + p.pre[l], U, st));
@@ -781,8 +770,8 @@ extern "C" int etd_septrain_forward_backward(etd_septrain* h, const float* mix, 
   ETD_TRY(st_fwd_head(h, ws + p.y[L], ws + p.logits, U, st));
   if (!frozen_stats) {      // the running statistics move once per call
     const float m = (float)ST_BN_MOMENTUM, om = (float)(1.0 - ST_BN_MOMENTUM);
-    hipLaunchKernelGGL(k_st_running, dim3(st_grid(h->NS)), dim3(256), 0, st, h->P + h->n_train, h->S, (int)h->NS, m, om);
-    hipLaunchKernelGGL(k_st_running, dim3(st_grid(h->NS)), dim3(256), 0, st, h->P + h->n_train + h->NS, h->S + 4 * h->NS, (int)h->NS, m, om);
+    hipLaunchKernelGGL(k_st_running, dim3(st_grid(h->NS)), dim3(256), 0, st, h->ps.P + h->ps.n_train, h->S, (int)h->NS, m, om);
+    hipLaunchKernelGGL(k_st_running, dim3(st_grid(h->NS)), dim3(256), 0, st, h->ps.P + h->ps.n_train + h->NS, h->S + 4 * h->NS, (int)h->NS, m, om);
   }
   HIP_TRY(hipGetLastError());
   float *cur = ws + p.E[0], *other = ws + p.E[1];
@@ -790,22 +779,22 @@ extern "C" int etd_septrain_forward_backward(etd_septrain* h, const float* mix, 
   // ---- backward
   ETD_TRY(st_loss(h, ws + p.logits, mix, target, B, loss_scale, ws + p.lpart, p.loss_blocks, cur, loss_out, st));
   float* part = ws + p.part;
-  ETD_TRY(st_bias_grad(h, cur, (long long)h->cfg.T * h->cfg.F, h->C, B, cpart, h->G + h->head_b.off, st));
-  ETD_TRY(st_dw_head(h, ws + p.y[L], cur, B, part, h->G + h->head_w.off, st));
+  ETD_TRY(st_bias_grad(h, cur, (long long)h->cfg.T * h->cfg.F, h->C, B, cpart, h->ps.G + h->head_b.off, st));
+  ETD_TRY(st_dw_head(h, ws + p.y[L], cur, B, part, h->ps.G + h->head_w.off, st));
   ETD_TRY(st_dx_head(h, cur, other, U, st));
   std::swap(cur, other);
   for (int j = L; j >= 1; --j) {      // cur = dy_j
     if (drop && j <= ST_DROP_LEVELS) ETD_TRY(st_dropout(h, j, h->drop_calls, cur, cur, U * h->net.szD[j], st));      // the forward's mask, regenerated
     ETD_TRY(st_norm_bwd(h, L + j, ws + p.v[j], cur, nullptr, cur, h->net.posD(j), B, frozen_stats, cpart, st));      // cur = dv_j
-    ETD_TRY(st_bias_grad(h, cur, h->net.posD(j), h->net.Cdout[j], B, cpart, h->G + h->dec_b[j].off, st));
-    ETD_TRY(st_dw_decoder(h, j, ws + p.pre[7 - j], j > 1 ? ws + p.y[j - 1] : nullptr, cur, B, part, h->G + h->dec_w[j].off, st));
+    ETD_TRY(st_bias_grad(h, cur, h->net.posD(j), h->net.Cdout[j], B, cpart, h->ps.G + h->dec_b[j].off, st));
+    ETD_TRY(st_dw_decoder(h, j, ws + p.pre[7 - j], j > 1 ? ws + p.y[j - 1] : nullptr, cur, B, part, h->ps.G + h->dec_w[j].off, st));
     ETD_TRY(st_dx_decoder(h, j, cur, ws + p.D[7 - j], other, U, st));
     std::swap(cur, other);
   }
   for (int l = L; l >= 1; --l) {      // D[l] = the skip's gradient; cur = dact_l for l < 6 (conv_6's normalised output is read by nothing)
     if (l < L) ETD_TRY(st_norm_bwd(h, l, ws + p.pre[l], cur, ws + p.D[l], ws + p.D[l], h->net.posE(l), B, frozen_stats, cpart, st));
-    ETD_TRY(st_bias_grad(h, ws + p.D[l], h->net.posE(l), h->net.Cenc[l], B, cpart, h->G + h->conv_b[l].off, st));
-    ETD_TRY(st_dw_encoder(h, l, l == 1 ? mix : ws + p.act[l - 1], ws + p.D[l], B, part, h->G + h->conv_w[l].off, st));
+    ETD_TRY(st_bias_grad(h, ws + p.D[l], h->net.posE(l), h->net.Cenc[l], B, cpart, h->ps.G + h->conv_b[l].off, st));
+    ETD_TRY(st_dw_encoder(h, l, l == 1 ? mix : ws + p.act[l - 1], ws + p.D[l], B, part, h->ps.G + h->conv_w[l].off, st));
     if (l > 1) {
       ETD_TRY(st_dx_encoder(h, l, ws + p.D[l], other, U, st));
       std::swap(cur, other);
@@ -833,14 +822,13 @@ extern "C" long long etd_septrain_get_dropout_calls(const etd_septrain* h) { ret
 extern "C" int etd_septrain_zero_grad(etd_septrain* h, void* stream) {
   if (!h) ETD_FAIL(ETD_EINVAL, "septrain_zero_grad: null handle");
   ETD_TRY(st_upload(h));
-  HIP_TRY(hipMemsetAsync(h->G, 0, sizeof(float) * (size_t)h->n_train, (hipStream_t)stream));
-  return ETD_OK;
+  return h->ps.zero_grad(h->ps.n_train, (hipStream_t)stream);
 }
 
 extern "C" int etd_septrain_grad_norm(etd_septrain* h, double* norm, void* stream) {
   if (!h || !norm) ETD_FAIL(ETD_EINVAL, "septrain_grad_norm: null argument");
   ETD_TRY(st_upload(h));
-  return grad_norm(h->G, h->n_train, h->norm_part, (hipStream_t)stream, norm);
+  return h->ps.grad_norm(h->ps.n_train, (hipStream_t)stream, norm);
 }
 
 extern "C" int etd_septrain_step(etd_septrain* h, double max_norm, double lr, double beta1, double beta2, double eps, double* norm_out, void* stream) {
@@ -849,13 +837,14 @@ extern "C" int etd_septrain_step(etd_septrain* h, double max_norm, double lr, do
     ETD_FAIL(ETD_EINVAL, "septrain_step: lr and eps must be >= 0 and the betas in [0, 1)");
   hipStream_t st = (hipStream_t)stream;
   ETD_TRY(st_upload(h));
+  TrainStore& ps = h->ps;
   double norm = 0.0;                                   // max_norm <= 0: no clipping, and no norm unless the caller asks
-  if (max_norm > 0.0 || norm_out) ETD_TRY(grad_norm(h->G, h->n_train, h->norm_part, st, &norm));
+  if (max_norm > 0.0 || norm_out) ETD_TRY(ps.grad_norm(ps.n_train, st, &norm));
   if (norm_out) *norm_out = norm;
-  h->step += 1;
-  const StepScalars s = step_scalars(max_norm, norm, lr, beta1, beta2, h->step);
-  hipLaunchKernelGGL(k_st_adam, dim3(st_grid(h->n_train)), dim3(256), 0, st, h->P, h->G, h->M1, h->M2, h->n_train, s.coef, (float)(1.0 - beta1), (float)beta2,
-                     (float)(1.0 - beta2), s.step_size, s.bc2_sqrt, (float)eps);
+  ps.step += 1;
+  const StepScalars s = step_scalars(max_norm, norm, lr, beta1, beta2, ps.step);
+  hipLaunchKernelGGL(k_st_adam, dim3(st_grid((long long)ps.n_train)), dim3(256), 0, st, ps.P, ps.G, ps.M1, ps.M2, (long long)ps.n_train, s.coef, (float)(1.0 - beta1),
+                     (float)beta2, (float)(1.0 - beta2), s.step_size, s.bc2_sqrt, (float)eps);
   HIP_TRY(hipGetLastError());
   h->pack_dirty = true;
   return ETD_OK;
@@ -863,27 +852,25 @@ extern "C" int etd_septrain_step(etd_septrain* h, double max_norm, double lr, do
 
 extern "C" int etd_septrain_set_step(etd_septrain* h, long long step) {
   if (!h || step < 0) ETD_FAIL(ETD_EINVAL, "septrain_set_step: null handle or negative step");
-  h->step = step;
+  h->ps.step = step;
   return ETD_OK;
 }
-extern "C" long long etd_septrain_get_step(const etd_septrain* h) { return h ? h->step : ETD_EINVAL; }
+extern "C" long long etd_septrain_get_step(const etd_septrain* h) { return h ? h->ps.step : ETD_EINVAL; }
 
-// which: 0 state (parameters and running statistics), 1 gradient, 2 exp_avg, 3 exp_avg_sq
+// which: 0 state (parameters and running statistics), 1 gradient, 2 exp_avg, 3 exp_avg_sq.  The store's checks, and around them what is the separator's own
 static int septrain_io(etd_septrain* h, const char* name, int which, float* out, const float* in, long long numel, hipStream_t st) {
   if (!h || !name || (!out && !in)) ETD_FAIL(ETD_EINVAL, "etd_septrain: null argument");
   if (which < 0 || which > 3) ETD_FAIL(ETD_EINVAL, "etd_septrain: which = %d is not 0 .. 3", which);
-  auto it = h->index.find(name);
-  if (it == h->index.end()) ETD_FAIL(ETD_EINVAL, "etd_septrain: no tensor '%s'", name);
-  const long long off = it->second.first, n = it->second.second;
-  if (n != numel) ETD_FAIL(ETD_EINVAL, "etd_septrain: '%s' has %lld elements, the buffer %lld", name, n, numel);
-  if (which > 0 && off >= h->n_train) ETD_FAIL(ETD_EINVAL, "etd_septrain: '%s' is a running statistic: it has no gradient and no moments", name);
-  if (!h->pool.uploaded && out) {      // before the first device call the state is the host's copy, and the gradients and moments are zeros
-    if (which == 0) memcpy(out, &h->hP[(size_t)off], sizeof(float) * (size_t)n);
-    else memset(out, 0, sizeof(float) * (size_t)n);
+  const TrainStore::Tensor* t = nullptr;
+  ETD_TRY(h->ps.find("etd_septrain", "tensor", name, numel, &t));
+  if (which > 0 && t->off >= h->ps.n_train) ETD_FAIL(ETD_EINVAL, "etd_septrain: '%s' is a running statistic: it has no gradient and no moments", name);
+  if (!h->pool.uploaded && out) {      // the state is the host's copy, and the gradients and moments are zeros
+    if (which == 0) memcpy(out, &h->hP[t->off], sizeof(float) * t->n);
+    else memset(out, 0, sizeof(float) * t->n);
     return ETD_OK;
   }
   ETD_TRY(st_upload(h));
-  return flat_io(h->P, h->G, h->M1, h->M2, which, off, n, out, in, st);
+  return h->ps.copy(*t, which, out, in, st);
 }
 
 extern "C" int etd_septrain_read(etd_septrain* h, const char* name, int which, float* out_host, long long numel, void* stream) {

@@ -15,7 +15,6 @@ tests/separator_data_np.py restate it.
 """
 from __future__ import annotations
 
-import contextlib
 import ctypes as C
 from collections import OrderedDict
 from typing import Dict, Optional, Sequence, Tuple, Union
@@ -24,7 +23,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._engine import Engine, nonneg
+from ._engine import nonneg
+from ._trainer import Trainer
 from .separator import LEVELS, SeparatorConfig, StemSeparator, check_separator_state, expected_keys, init_separator_state
 
 TRAINABLE = (".weight", ".bias", ".gamma", ".beta")
@@ -34,12 +34,13 @@ def _p(t: Optional[torch.Tensor]):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
-class SeparatorTrainer(Engine):
+class SeparatorTrainer(Trainer):
     """fp32 training of the separator's U-Nets on the GPU.  ``state=None`` draws ``init_separator_state(config, seed)``; otherwise ``state`` is a separator state
     (``expected_keys``).  ``max_units`` bounds the units of one call, ``workspace_bytes`` the device workspace a call may hold (``workspace_total_bytes(B)`` tells
     what ``B`` units need).  ``max_norm=None``: no clipping.  ``dropout`` in [0, 1) is the decoder's drop rate (Spleeter: 0.5; 0 launches nothing), ``dropout_seed`` the
     key of its mask; the mask's call counter travels in ``optimizer_state_dict()["dropout_calls"]``.  Constructing needs no GPU; training does: there is no CPU path."""
     _destroy = "etd_septrain_destroy"
+    _abi = "etd_septrain"
 
     def __init__(self, config: Optional[SeparatorConfig] = None, state: Optional[Dict] = None, seed: int = 0, device: Union[str, torch.device] = "cuda",
                  max_units: int = 8, workspace_bytes: int = 16 << 30, lr: float = 1e-4, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
@@ -134,28 +135,13 @@ class SeparatorTrainer(Engine):
         """the loss alone (by default on the running statistics, as ``StemSeparator`` will use the state); no gradient is touched"""
         return self._run(mix, target, 1.0, frozen_stats, False)
 
-    def zero_grad(self) -> None:
-        dev = self._device()
-        with torch.cuda.device(dev):
-            _lib.check(self._lib.etd_septrain_zero_grad(self.h, self._stream(dev)), "etd_septrain_zero_grad")
-
-    def grad_norm(self) -> float:
-        dev = self._device()
-        v = C.c_double()
-        with torch.cuda.device(dev):
-            _lib.check(self._lib.etd_septrain_grad_norm(self.h, C.byref(v), self._stream(dev)), "etd_septrain_grad_norm")
-        return float(v.value)
+    def _step_call(self, norm_ref, stream) -> None:
+        self._call("step", float(self.max_norm or 0.0), self.lr, self.betas[0], self.betas[1], self.eps, norm_ref if self.max_norm else None, stream)
 
     def step(self) -> Optional[float]:
         """``clip_grad_norm_`` (with ``max_norm``) + ``torch.optim.Adam.step`` + ``zero_grad``.  Returns the gradient norm before clipping, None without clipping."""
-        dev = self._device()
-        v = C.c_double()
-        with torch.cuda.device(dev):
-            _lib.check(self._lib.etd_septrain_step(self.h, float(self.max_norm or 0.0), self.lr, self.betas[0], self.betas[1], self.eps,
-                                                   C.byref(v) if self.max_norm else None, self._stream(dev)), "etd_septrain_step")
-        self.global_step += 1
-        self.zero_grad()
-        return float(v.value) if self.max_norm else None
+        norm = super().step()
+        return norm if self.max_norm else None
 
     def train_step(self, mix, target) -> float:
         """one batch, one optimizer step: the batch's loss before the step"""
@@ -163,45 +149,24 @@ class SeparatorTrainer(Engine):
         self.step()
         return loss
 
-    # ------------------------------------------------------------------ state
-    def _read(self, which: int, keys) -> "OrderedDict[str, np.ndarray]":
-        out = OrderedDict()
-        on_gpu = self.device.type == "cuda" and torch.cuda.is_available()      # (before the first device call the library answers from the host's copy)
-        dev = self._device() if on_gpu else None
-        with torch.cuda.device(dev) if on_gpu else contextlib.nullcontext():
-            for k in keys:
-                a = np.empty(self._shapes[k], np.float32)
-                _lib.check(self._lib.etd_septrain_read(self.h, k.encode(), which, a.ctypes.data, a.size, self._stream(dev) if on_gpu else None), "etd_septrain_read")
-                out[k] = a
-        return out
-
-    def _trainable(self):
+    # ------------------------------------------------------------------ state (the reads and the moments: Trainer; they need no GPU before the first device call)
+    def _moment_keys(self):
         return [k for k in self._shapes if k.endswith(TRAINABLE)]
 
     def state_dict(self) -> "OrderedDict[str, np.ndarray]":
         """the separator state (``expected_keys``), running statistics included"""
-        return self._read(0, self._shapes)
+        return super().state_dict()
 
     def grads(self) -> "OrderedDict[str, np.ndarray]":
         """the accumulated gradient of every trainable tensor by its state key"""
-        return self._read(1, self._trainable())
+        return super().grads()
 
     def optimizer_state_dict(self) -> Dict[str, object]:
-        return {"step": self.global_step, "exp_avg": self._read(2, self._trainable()), "exp_avg_sq": self._read(3, self._trainable()),
-                "dropout_calls": self.dropout_calls}
+        return dict(super().optimizer_state_dict(), dropout_calls=self.dropout_calls)
 
     def load_optimizer_state_dict(self, sd: Dict[str, object]) -> None:
-        dev = self._device()
-        with torch.cuda.device(dev):
-            for second, key in ((0, "exp_avg"), (1, "exp_avg_sq")):
-                for k in self._trainable():
-                    a = np.ascontiguousarray(sd[key][k], np.float32)
-                    if a.shape != self._shapes[k]:
-                        raise ValueError(f"{key}[{k!r}] has shape {a.shape}, expected {self._shapes[k]}")
-                    _lib.check(self._lib.etd_septrain_write_moment(self.h, k.encode(), second, a.ctypes.data, a.size, self._stream(dev)), "etd_septrain_write_moment")
-            _lib.check(self._lib.etd_septrain_set_step(self.h, int(sd["step"])), "etd_septrain_set_step")
+        super().load_optimizer_state_dict(sd)
         _lib.check(self._lib.etd_septrain_set_dropout_calls(self.h, int(sd.get("dropout_calls", 0))), "etd_septrain_set_dropout_calls")
-        self.global_step = int(sd["step"])
 
     def save(self, path) -> None:
         """what ``load_separator_state`` reads"""

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._trainer import Trainer
 from .decoder import IGNORE_INDEX, EtudeDecoder, EtudeDecoderConfig, _int_array, expected_state_keys, right_padded_lengths
 
 # the keys train.py:156-165 reads from a batch, with the C-ABI attribute order (the concat order of etude_decoder.py:171-176) for the four bin arrays
@@ -131,10 +132,12 @@ def pack_batch(cfg: EtudeDecoderConfig, batch: Dict[str, object]) -> Tuple[np.nd
     return i32(lens[lens > 0]), i32(pid), i32(cols[0]), i32(np.stack(cols[1:])), i32(pl)
 
 
-class DecoderTrainer:
+class DecoderTrainer(Trainer):
     """fp32 training of the EtudeDecoder on the GPU.  ``state=None`` initialises as the reference does (``init_decoder_state(config, seed)``); otherwise ``state`` maps
     the reference's state-dict keys to arrays.  ``lr_fn(step)`` is the factor on ``lr`` at optimizer step ``step`` (None = 1; ``cosine_schedule_with_warmup``).
     ``max_rows`` bounds the valid positions of one batch and sizes the activation workspace (default: 8 full-length sequences)."""
+    _destroy = "etd_dtrain_destroy"
+    _abi = "etd_dtrain"
 
     def __init__(self, config: EtudeDecoderConfig, state: Optional[Dict[str, np.ndarray]] = None, seed: int = 0, device: Union[str, torch.device] = "cuda",
                  lr: float = 2e-4, betas: Tuple[float, float] = (0.9, 0.98), eps: float = 1e-8, weight_decay: float = 0.01, clip_grad_norm: float = 1.0,
@@ -158,10 +161,7 @@ class DecoderTrainer:
         if device == "auto":
             device = "cuda"
         self.device = torch.device(device)
-        if self.device.type != "cuda" or not torch.cuda.is_available():
-            raise _lib.EtudeHipError("etude_amd.DecoderTrainer needs a ROCm GPU (device='cuda'); there is no CPU path")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._device()
         cfg = _lib.DecCfg(vocab_size=config.vocab_size, hidden_size=config.hidden_size, num_hidden_layers=config.num_hidden_layers,
                           num_attention_heads=config.num_attention_heads, intermediate_size=config.intermediate_size,
                           max_position_embeddings=config.max_position_embeddings, num_classes=config.num_classes,
@@ -173,23 +173,19 @@ class DecoderTrainer:
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().etd_dtrain_create(C.byref(cfg), names, ptrs, numels, n, int(config.pad_token_id), int(config.pad_class_id),
                                                     int(config.attribute_pad_id), self.max_rows, C.byref(h)), "etd_dtrain_create")
-        self._h = h
+        del keep
+        self._adopt(h)
         self._ts = torch.cuda.Stream(device=self.device)
         self.global_step = 0          # optimizer steps taken: the schedule's argument
         self._micro = 0               # batches since the last step (skipped ones included, as train.py counts batch_idx)
 
     # ------------------------------------------------------------------ plumbing
-    def _stream(self):
+    def _stream(self, dev=None):
+        """the trainer's own stream, not the current one"""
         return C.c_void_p(self._ts.cuda_stream)
 
-    def _read(self, fn, *mid) -> "OrderedDict[str, np.ndarray]":
-        out = OrderedDict()
-        with torch.cuda.device(self.device):
-            for k, shape in self._shapes.items():
-                a = np.empty(shape, np.float32)
-                _lib.check(fn(self._h, k.encode(), *mid, a.ctypes.data, a.size, self._stream()), fn.__name__)
-                out[k] = a
-        return out
+    def _read_entry(self, which: int):
+        return (("read_param", ()), ("read_grad", ()), ("read_moment", (0,)), ("read_moment", (1,)))[which]
 
     # ------------------------------------------------------------------ one batch
     def loss_and_backward(self, batch: Dict[str, object]) -> Tuple[float, int, bool]:
@@ -203,34 +199,22 @@ class DecoderTrainer:
             return float("nan"), 0, True
         loss, n_scored = C.c_float(), C.c_int32()
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().etd_dtrain_forward_backward(self._h, int(T.size), T.ctypes.data, ids.ctypes.data, cls.ctypes.data, attrs4.ctypes.data,
+            _lib.check(_lib.lib().etd_dtrain_forward_backward(self.h, int(T.size), T.ctypes.data, ids.ctypes.data, cls.ctypes.data, attrs4.ctypes.data,
                                                               labels.ctypes.data, 1.0 / self.grad_accum_steps, C.byref(loss), C.byref(n_scored), self._stream()),
                        "etd_dtrain_forward_backward")
         return float(loss.value), int(n_scored.value), n_scored.value == 0
 
-    def zero_grad(self) -> None:
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().etd_dtrain_zero_grad(self._h, self._stream()), "etd_dtrain_zero_grad")
-
-    def grad_norm(self) -> float:
-        v = C.c_double()
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().etd_dtrain_grad_norm(self._h, C.byref(v), self._stream()), "etd_dtrain_grad_norm")
-        return float(v.value)
-
     def current_lr(self) -> float:
         return self.lr * (float(self.lr_fn(self.global_step)) if self.lr_fn is not None else 1.0)
 
+    def _step_call(self, norm_ref, stream) -> None:
+        self._call("clip_and_step", self.clip_grad_norm, self.current_lr(), self.betas[0], self.betas[1], self.eps, self.weight_decay, norm_ref, stream)
+
     def step(self) -> float:
         """``clip_grad_norm_`` + ``AdamW.step`` + ``scheduler.step`` + ``zero_grad`` (train.py:175-181).  Returns the gradient norm before clipping."""
-        v = C.c_double()
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().etd_dtrain_clip_and_step(self._h, self.clip_grad_norm, self.current_lr(), self.betas[0], self.betas[1], self.eps, self.weight_decay,
-                                                           C.byref(v), self._stream()), "etd_dtrain_clip_and_step")
-        self.global_step += 1
+        norm = super().step()
         self._micro = 0
-        self.zero_grad()
-        return float(v.value)
+        return norm
 
     def train_step(self, batches: Sequence[Dict[str, object]]) -> Tuple[List[float], float]:
         """``grad_accum_steps`` batches, then one optimizer step: ``(the batches' losses, gradient norm before clipping)``."""
@@ -239,30 +223,9 @@ class DecoderTrainer:
         losses = [self.loss_and_backward(b)[0] for b in batches]
         return losses, self.step()
 
-    # ------------------------------------------------------------------ state
-    def state_dict(self) -> "OrderedDict[str, np.ndarray]":
-        return self._read(_lib.lib().etd_dtrain_read_param)
-
-    def grads(self) -> "OrderedDict[str, np.ndarray]":
-        return self._read(_lib.lib().etd_dtrain_read_grad)
-
-    def optimizer_state_dict(self) -> Dict[str, object]:
-        return {"step": self.global_step, "exp_avg": self._read(_lib.lib().etd_dtrain_read_moment, 0), "exp_avg_sq": self._read(_lib.lib().etd_dtrain_read_moment, 1)}
-
-    def load_optimizer_state_dict(self, sd: Dict[str, object]) -> None:
-        l = _lib.lib()
-        with torch.cuda.device(self.device):
-            for second, key in ((0, "exp_avg"), (1, "exp_avg_sq")):
-                for k, shape in self._shapes.items():
-                    a = np.ascontiguousarray(sd[key][k], np.float32)
-                    if a.shape != shape:
-                        raise ValueError(f"{key}['{k}'] has shape {a.shape}, expected {shape}")
-                    _lib.check(l.etd_dtrain_write_moment(self._h, k.encode(), second, a.ctypes.data, a.size, self._stream()), "etd_dtrain_write_moment")
-            _lib.check(l.etd_dtrain_set_step(self._h, int(sd["step"])), "etd_dtrain_set_step")
-        self.global_step = int(sd["step"])
-
+    # ------------------------------------------------------------------ state (state_dict, grads and the optimizer's state: Trainer)
     def workspace_bytes(self) -> int:
-        return int(_lib.lib().etd_dtrain_bytes(self._h, 0))
+        return int(_lib.lib().etd_dtrain_bytes(self.h, 0))
 
     def save(self, path: Union[str, Path]) -> None:
         """The training payload ``{"model_state_dict": ...}`` that ``load_decoder_state`` / ``load_etude_decoder`` read back."""
@@ -271,14 +234,3 @@ class DecoderTrainer:
     def to_decoder(self, precision: Optional[str] = None, **kwargs) -> EtudeDecoder:
         """An inference ``EtudeDecoder`` over a copy of the current weights."""
         return EtudeDecoder(self.config, self.state_dict(), device=self.device, precision=precision, **kwargs)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.lib().etd_dtrain_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:      # noqa: BLE001
-            pass

@@ -283,3 +283,77 @@ def test_a_song_alone_and_batched_has_the_same_rows():
         a, b = out["alone"][w], out["batch"][w][lo:lo + n]
         assert a.shape == b.shape and np.abs(a).max() > 0
         assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), ("rows", w)
+
+
+# ------------------------------------------------------------------ the parameter store: refusals of the read / write entries, checkpoint round trip
+@pytest.fixture(scope="module")
+def mini():
+    """four layers, so that one instrument layer and its parameters exist; songs of 2 and 7 frames, the second with a tempo target"""
+    cfg, dims = model_config(dict(instr=2, nlayers=4, d_hid=256))
+    return dict(cfg=cfg, state=synth.beat_state_dict(15, dims), batch=bt.make_batch(43, (2, 7), instr=2, ntoken=cfg.ntoken, no_tempo=(0,)))
+
+
+def test_read_and_write_refuse_unknown_names_wrong_sizes_and_unknown_buffers(mini):
+    from etude_amd import _lib
+    tr = trainer(mini["cfg"], mini["state"], 18)
+    l, key = _lib.lib(), b"Transformer_layers.instr_attention_3.norm1.bias"
+    n = mini["state"][key.decode()].size
+    buf = np.zeros(n + 1, np.float32)
+    try:
+        with torch.cuda.device(tr.device):
+            st = tr._stream(tr.device)
+            for name in ("etd_btrain_read", "etd_btrain_write"):
+                fn = getattr(l, name)
+                for which in range(4):
+                    with pytest.raises(_lib.EtudeHipError, match=r"etd_btrain: no parameter 'no\.such\.weight'"):
+                        _lib.check(fn(tr.h, b"no.such.weight", which, buf.ctypes.data, n, st), name)
+                    with pytest.raises(_lib.EtudeHipError, match=rf"etd_btrain: '{key.decode()}' has {n} elements, the buffer {n + 1}".replace(".", r"\.")):
+                        _lib.check(fn(tr.h, key, which, buf.ctypes.data, n + 1, st), name)
+                for which in (-1, 4):
+                    with pytest.raises(_lib.EtudeHipError, match="etd_btrain: null argument or unknown buffer"):
+                        _lib.check(fn(tr.h, key, which, buf.ctypes.data, n, st), name)
+                with pytest.raises(_lib.EtudeHipError, match="etd_btrain: null argument or unknown buffer"):
+                    _lib.check(fn(tr.h, key, 0, None, n, st), name)
+                with pytest.raises(_lib.EtudeHipError, match="etd_btrain: null argument or unknown buffer"):
+                    _lib.check(fn(None, key, 0, buf.ctypes.data, n, st), name)
+        assert np.array_equal(tr.state_dict()[key.decode()], mini["state"][key.decode()])      # a refused write changed nothing
+        assert all(not v.any() for v in tr.grads().values())
+    finally:
+        tr.close()
+
+
+def test_checkpoint_round_trip_continues_bit_for_bit(mini):
+    """two optimizer steps, then a second trainer from state_dict() and optimizer_state_dict(): one more step on the same batch gives the same bits in both"""
+    from etude_amd import _lib
+    cfg, batch = mini["cfg"], args_of(mini["batch"])
+    a = trainer(cfg, mini["state"], 18)
+    b = None
+    try:
+        for _ in range(2):
+            a.loss_and_backward(*batch)
+            a.step()
+        sd, osd = a.state_dict(), a.optimizer_state_dict()
+        assert osd["step"] == 2 and list(osd["exp_avg"]) == list(sd) and osd["exp_avg_sq"]["Transformer_layers.instr_attention_3.linear1.weight"].any()
+        b = trainer(cfg, sd, 18)
+        b.load_optimizer_state_dict(osd)
+        assert b.global_step == 2 and _lib.lib().etd_btrain_get_step(b.h) == 2
+        out = []
+        for tr in (a, b):
+            loss = tr.loss_and_backward(*batch)[0]
+            g = tr.grads()
+            norm = tr.step()
+            out.append(dict(loss=np.float32(loss).tobytes(), norm=np.float64(norm).tobytes(), step=tr.global_step, g=g, p=tr.state_dict(), zg=tr.grads(),
+                            o=tr.optimizer_state_dict()))
+        x, y = out
+        assert x["loss"] == y["loss"] and x["norm"] == y["norm"] and x["step"] == y["step"] == 3 and x["o"]["step"] == y["o"]["step"] == 3
+        for k in sd:
+            assert x["g"][k].tobytes() == y["g"][k].tobytes(), k
+            assert x["p"][k].tobytes() == y["p"][k].tobytes(), k
+            assert x["zg"][k].tobytes() == y["zg"][k].tobytes() and not x["zg"][k].any(), k
+            for m in ("exp_avg", "exp_avg_sq"):
+                assert x["o"][m][k].tobytes() == y["o"][m][k].tobytes(), (m, k)
+        assert any(x["p"][k].tobytes() != sd[k].tobytes() for k in sd)      # the third step moved the parameters
+    finally:
+        a.close()
+        if b is not None:
+            b.close()

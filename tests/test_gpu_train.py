@@ -334,3 +334,72 @@ def test_hand_over_to_the_inference_decoder(tiny, run10, tmp_path):
     for k in now:
         assert back[k].tobytes() == now[k].tobytes(), k
     load_etude_decoder(tmp_path / "cfg.json", tmp_path / "latest.pth", device="cuda", precision="fp32").close()
+
+
+# ------------------------------------------------------------------ the parameter store: refusals of the read / write entries, checkpoint round trip
+@pytest.fixture(scope="module")
+def mini():
+    """the smallest decoder the engine accepts: hidden 256, 4 heads, 1 layer, intermediate 128; two sequences of 3 and 5 positions"""
+    cfg = tn.tiny_config(num_hidden_layers=1, intermediate_size=128)
+    return dict(cfg=cfg, state=tn.seeded_state(cfg, 4), batch=tn.ragged_batch(cfg, (3, 5), seed=6))
+
+
+def test_read_and_write_entries_refuse_unknown_names_and_wrong_sizes(mini):
+    tr = trainer(mini["cfg"], mini["state"], max_rows=8)
+    l, key = _lib.lib(), b"attribute_projection.bias"
+    n = mini["state"][key.decode()].size
+    buf = np.zeros(n + 1, np.float32)
+    entries = (("etd_dtrain_read_param", ()), ("etd_dtrain_read_grad", ()), ("etd_dtrain_read_moment", (0,)), ("etd_dtrain_read_moment", (1,)),
+               ("etd_dtrain_write_moment", (0,)), ("etd_dtrain_write_moment", (1,)))
+    try:
+        with torch.cuda.device(tr.device):
+            for name, mid in entries:
+                fn = getattr(l, name)
+                with pytest.raises(_lib.EtudeHipError, match=r"etd_dtrain: no parameter 'no\.such\.weight'"):
+                    _lib.check(fn(tr._h, b"no.such.weight", *mid, buf.ctypes.data, n, tr._stream()), name)
+                with pytest.raises(_lib.EtudeHipError, match=rf"etd_dtrain: 'attribute_projection\.bias' has {n} elements, the buffer {n + 1}"):
+                    _lib.check(fn(tr._h, key, *mid, buf.ctypes.data, n + 1, tr._stream()), name)
+                with pytest.raises(_lib.EtudeHipError, match="etd_dtrain: null argument"):
+                    _lib.check(fn(tr._h, key, *mid, None, n, tr._stream()), name)
+                with pytest.raises(_lib.EtudeHipError, match="etd_dtrain: null argument"):
+                    _lib.check(fn(None, key, *mid, buf.ctypes.data, n, tr._stream()), name)
+        assert tr.state_dict()[key.decode()].tobytes() == mini["state"][key.decode()].tobytes()      # a refused write changed nothing
+        assert all(not v.any() for d in (tr.optimizer_state_dict()["exp_avg"], tr.optimizer_state_dict()["exp_avg_sq"]) for v in d.values())
+    finally:
+        tr.close()
+
+
+def test_checkpoint_round_trip_continues_bit_for_bit(mini):
+    """two optimizer steps, then a second trainer from state_dict() and optimizer_state_dict(): one more step on the same batch gives the same bits in both"""
+    cfg, batch = mini["cfg"], mini["batch"]
+    a = trainer(cfg, mini["state"], max_rows=8)
+    b = None
+    try:
+        for _ in range(2):
+            a.loss_and_backward(batch)
+            a.step()
+        sd, osd = a.state_dict(), a.optimizer_state_dict()
+        assert osd["step"] == 2 and list(osd["exp_avg"]) == list(sd) and any(v.any() for v in osd["exp_avg_sq"].values())
+        b = trainer(cfg, sd, max_rows=8)
+        b.load_optimizer_state_dict(osd)
+        assert b.global_step == 2 and _lib.lib().etd_dtrain_get_step(b._h) == 2
+        out = []
+        for tr in (a, b):
+            loss = tr.loss_and_backward(batch)[0]
+            g = tr.grads()
+            norm = tr.step()
+            out.append(dict(loss=np.float32(loss).tobytes(), norm=np.float64(norm).tobytes(), step=tr.global_step, g=g, p=tr.state_dict(), zg=tr.grads(),
+                            o=tr.optimizer_state_dict()))
+        x, y = out
+        assert x["loss"] == y["loss"] and x["norm"] == y["norm"] and x["step"] == y["step"] == 3 and x["o"]["step"] == y["o"]["step"] == 3
+        for k in sd:
+            assert x["g"][k].tobytes() == y["g"][k].tobytes(), k
+            assert x["p"][k].tobytes() == y["p"][k].tobytes(), k
+            assert x["zg"][k].tobytes() == y["zg"][k].tobytes() and not x["zg"][k].any(), k
+            for m in ("exp_avg", "exp_avg_sq"):
+                assert x["o"][m][k].tobytes() == y["o"][m][k].tobytes(), (m, k)
+        assert any(x["p"][k].tobytes() != sd[k].tobytes() for k in sd)      # the third step moved the parameters
+    finally:
+        a.close()
+        if b is not None:
+            b.close()

@@ -11,6 +11,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parent))
 import separator_np as sp  # noqa: E402
 import separator_train_np as st  # noqa: E402
 
+from etude_amd import _lib  # noqa: E402
 from etude_amd.separator import SeparatorConfig, expected_keys, init_separator_state  # noqa: E402
 from etude_amd.separator_train import SeparatorTrainer  # noqa: E402
 
@@ -174,4 +175,60 @@ def test_config_state_and_input_refusals():
         tr.loss_and_backward(mix, target[:1])
     with pytest.raises(ValueError, match="max_units is 2"):
         tr.loss_and_backward(torch.cat([mix, mix]), torch.cat([target, target], 1))
+    tr.close()
+
+
+# ------------------------------------------------------------------ the parameter store, before any device call (reads are answered from the host's copy)
+def _store_call(tr, entry, *args):
+    _lib.check(getattr(_lib.lib(), entry)(tr.h, *args), entry)
+
+
+def _store_refusal(tr, match, entry, *args):
+    with pytest.raises(_lib.EtudeHipError, match=match):
+        _store_call(tr, entry, *args)
+
+
+def test_store_reads_return_the_state_and_zeros_without_a_device():
+    cfg, state, _, _ = _tiny()
+    tr = SeparatorTrainer(cfg, state, max_units=2)
+    sd = tr._read(0, tr._shapes)
+    assert list(sd) == list(expected_keys(cfg)) and all(np.array_equal(sd[k], state[k]) for k in sd)
+    trainable = [k for k in expected_keys(cfg) if not k.endswith((".mean", ".var"))]
+    for which in (1, 2, 3):
+        got = tr._read(which, trainable)
+        assert list(got) == trainable and all(v.shape == state[k].shape and not v.any() for k, v in got.items()), which
+    tr.close()
+
+
+def test_store_refusals_name_the_key_the_counts_and_the_buffer():
+    cfg, state, _, _ = _tiny()
+    tr = SeparatorTrainer(cfg, state, max_units=2)
+    n = state["a.conv1.weight"].size
+    buf = np.zeros(n + 1, np.float32)
+    _store_refusal(tr, r"etd_septrain: no tensor 'a\.conv9\.weight'", "etd_septrain_read", b"a.conv9.weight", 0, buf.ctypes.data, n, None)
+    _store_refusal(tr, rf"etd_septrain: 'a\.conv1\.weight' has {n} elements, the buffer {n + 1}", "etd_septrain_read", b"a.conv1.weight", 0, buf.ctypes.data, n + 1, None)
+    for which in (-1, 4):
+        _store_refusal(tr, rf"etd_septrain: which = {which} is not 0 \.\. 3", "etd_septrain_read", b"a.conv1.weight", which, buf.ctypes.data, n, None)
+    for key in ("b.bn7.mean", "a.bn1.var"):
+        m = state[key].size
+        for which in (1, 2, 3):
+            _store_refusal(tr, rf"etd_septrain: '{key}' is a running statistic", "etd_septrain_read", key.encode(), which, buf.ctypes.data, m, None)
+        got = np.empty(m, np.float32)
+        _store_call(tr, "etd_septrain_read", key.encode(), 0, got.ctypes.data, m, None)
+        assert np.array_equal(got, state[key].reshape(-1))
+    _store_refusal(tr, "septrain_read: null buffer", "etd_septrain_read", b"a.conv1.weight", 0, None, n, None)
+    tr.close()
+
+
+def test_step_counter_follows_set_step_and_refuses_a_negative_one():
+    cfg, state, _, _ = _tiny()
+    tr = SeparatorTrainer(cfg, state, max_units=2)
+    lib = _lib.lib()
+    assert lib.etd_septrain_get_step(tr.h) == 0
+    for s in (7, 0, 2 ** 40):
+        _store_call(tr, "etd_septrain_set_step", s)
+        assert lib.etd_septrain_get_step(tr.h) == s
+    _store_refusal(tr, "septrain_set_step: null handle or negative step", "etd_septrain_set_step", -1)
+    assert lib.etd_septrain_get_step(tr.h) == 2 ** 40
+    assert lib.etd_septrain_set_step(None, 1) == -22 and lib.etd_septrain_get_step(None) == -22
     tr.close()
