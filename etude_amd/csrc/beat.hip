@@ -13,28 +13,12 @@
 #include "etude_hip_debug.h"
 #include "prof.h"
 
-// ================================================================================================ device: song tables
-// The chunk's songs: global row / frame offsets of every song of the call (one table, uploaded once per call) and the chunk's slice of it.
-struct BeatChunk {
-  const int* row0;      // [n_seq + 1] global row offset of song s (row0[n_seq] = total rows)
-  const int* frame0;    // [n_seq + 1] global frame offset
-  const int* seg0;      // [n_seq + 1] global offset of song s's first tempo partial sum (ceil(T / 128) per song)
-  int first, count;     // songs [first, first + count) form this chunk
-  int row_base, frame_base;     // row0[first], frame0[first]: chunk-local row r = global row - row_base
-  int rows, frames;
-  int instr;
-};
-
-__device__ __forceinline__ int beat_song_of(const int* off, int first, int count, int g) {       // largest s in the chunk with off[s] <= g
-  int lo = first, hi = first + count - 1;
-  while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (off[mid] <= g) lo = mid; else hi = mid - 1; }
-  return lo;
-}
-
 // ================================================================================================ conv1 + maxpool(1,3) + ReLU
 // c1[r][p][co] = relu(max_{u<3} (b[co] + sum_{kt<5,kw<3} w[co][kt][kw] x[t+kt-2][3p+u+kw])), x = 0 outside the song (padding (2, 0)).  Channel-last, so that the
 // conv2 patch of pooled column c is the 384 contiguous floats at (r 42 + c) 32.  One thread per (row, p, co).
 // (feat points at the chunk's first row)
+// The chain is written out here and once more as beat_conv1_at (beat.h), which the trainer's k_bt_conv1_bwd calls to find the maximum this kernel took: the same
+// fmaf order, bias first, kt then kw ascending.  Calling the helper from here folds the row offsets differently (3 more instructions), so this body stays as written.
 __global__ __launch_bounds__(256) void k_beat_conv1(const float* __restrict__ feat, BeatChunk c, const float* __restrict__ w, const float* __restrict__ b, float* __restrict__ c1) {
   const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
   if (gid >= (long long)c.rows * BEAT_W1 * BEAT_C1) return;
@@ -62,19 +46,22 @@ __global__ __launch_bounds__(256) void k_beat_conv1(const float* __restrict__ fe
 }
 
 // ================================================================================================ conv2 maxpool + ReLU -> conv3 patches
-// c2 = conv2 + bias over the 42 columns of every row ([r 42 + col][64]); X3[r 3 + c][kt 384 + kw 64 + ci] = relu(max_{u<3} c2[(r+kt-1) 42 + 3 (c+kw) + u][ci]),
-// 0 where the row r+kt-1 is outside the song (conv3 padding (1, 0)).  One thread per X3 element.
+// c2 = conv2 + bias over COLS columns of every row ([r COLS + col][64]: the engine's GEMM forms all 42, the trainer's the 24 that are read);
+// X3[r 3 + c][kt 384 + kw 64 + ci] = relu(max_{u<3} c2[(r+kt-1) COLS + 3 (c+kw) + u][ci]), 0 where the row r+kt-1 is outside the song (conv3 padding (1, 0)).
+// One thread per X3 element.
+template <int COLS>
 __global__ __launch_bounds__(256) void k_beat_patch3(const float* __restrict__ c2, BeatChunk c, float* __restrict__ x3) {
   const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
   if (gid >= (long long)c.rows * 3 * BEAT_K3) return;
   const int rc = (int)(gid / BEAT_K3), k = (int)(gid - (long long)rc * BEAT_K3);
   const int r = rc / 3, col = rc - r * 3, kt = k / 384, kw = (k - kt * 384) / 64, ci = k & 63;
-  const int g = r + c.row_base, s = beat_song_of(c.row0, c.first, c.count, g);
-  const int T = (c.frame0[s + 1] - c.frame0[s]), t = (g - c.row0[s]) % T, tt = t + kt - 1;
+  int s, T, t;
+  beat_row_at(c, r, s, T, t);
+  const int tt = t + kt - 1;
   float v = 0.f;
   if (tt >= 0 && tt < T) {
-    const float* p = c2 + ((long long)(r + kt - 1) * BEAT_W1 + 3 * (col + kw)) * BEAT_C2 + ci;
-    v = fmaxf(fmaxf(fmaxf(p[0], p[BEAT_C2]), p[2 * BEAT_C2]), 0.f);
+    const float* p = c2 + ((long long)(r + kt - 1) * COLS + 3 * (col + kw)) * BEAT_C2 + ci;
+    v = beat_pool3_relu(p[0], p[BEAT_C2], p[2 * BEAT_C2]);
   }
   x3[gid] = v;
 }
@@ -85,16 +72,21 @@ __global__ __launch_bounds__(256) void k_beat_pool3(const float* __restrict__ c3
   if (gid >= (long long)rows * BEAT_DMODEL) return;
   const int r = (int)(gid >> 8), co = (int)(gid & 255);
   const float* p = c3 + (long long)r * 3 * BEAT_DMODEL + co;
-  x[gid] = fmaxf(fmaxf(fmaxf(p[0], p[BEAT_DMODEL]), p[2 * BEAT_DMODEL]), 0.f);
+  x[gid] = beat_pool3_relu(p[0], p[BEAT_DMODEL], p[2 * BEAT_DMODEL]);
 }
 
 // ================================================================================================ dilated 5-tap attention (dilated_transformer_layer.py:37-95)
 // One thread per (row, head).  Tap j of head h reads the row at time t + o_h(j) 2^layer of the same (song, instr): o = j-2 (heads 0-3), j-4 (4), j-3 (5), j-1 (6), j (7);
 // head 7 takes its KEYS from head 6's projection (:51) and its values from its own.  logit = (q.k_j + q.Er[h][:, j]) / sqrt(32); a tap outside the song is masked
 // (the reference masks qk == 0 of its zero-padded keys).  out = sum_j p_j v_j is the layer's skip; x += out.
-__device__ __forceinline__ int beat_tap_off(int h, int j) { return h < 4 ? j - 2 : h == 4 ? j - 4 : h == 5 ? j - 3 : h == 6 ? j - 1 : j; }
-
-__global__ __launch_bounds__(256) void k_beat_dattn(const float* __restrict__ qkv, BeatChunk c, const float* __restrict__ Er, int dil, float* __restrict__ skip, float* __restrict__ x) {
+// One body, two instances.  The engine's (TRAIN = false) updates x in place through the one restrict pointer x.  The trainer's reads the layer's input from keep.xin,
+// writes x = xin + out out of place and keeps the probabilities in keep.prob [rows][8][5] (0 for a masked tap).  What only the trainer passes travels in `keep`, which
+// is empty for the engine, so that the engine's arguments and code are what they were before the trainer shared the kernel.
+template <bool TRAIN> struct BeatDattnKeep {};
+template <> struct BeatDattnKeep<true> { const float* xin; float* prob; };
+template <bool TRAIN>
+__global__ __launch_bounds__(256) void k_beat_dattn(const float* __restrict__ qkv, BeatChunk c, const float* __restrict__ Er, int dil, float* __restrict__ skip, float* __restrict__ x,
+                                                    BeatDattnKeep<TRAIN> keep) {
   const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
   if (gid >= (long long)c.rows * BEAT_HEADS) return;
   const int r = (int)(gid >> 3), h = (int)(gid & 7), kh = h == 7 ? 6 : h;
@@ -134,6 +126,7 @@ __global__ __launch_bounds__(256) void k_beat_dattn(const float* __restrict__ qk
   for (int d = 0; d < BEAT_HEAD_DIM; ++d) o[d] = 0.f;
 #pragma unroll
   for (int j = 0; j < BEAT_TAPS; ++j) {
+    if constexpr (TRAIN) keep.prob[gid * BEAT_TAPS + j] = ok[j] ? lg[j] / den : 0.f;
     if (!ok[j]) continue;
     const float p = lg[j] / den;
     const float* vp = qkv + (long long)(r + beat_tap_off(h, j) * dil) * 768 + 512 + h * BEAT_HEAD_DIM;
@@ -145,23 +138,24 @@ __global__ __launch_bounds__(256) void k_beat_dattn(const float* __restrict__ qk
   }
   float* sp = skip + (long long)r * BEAT_DMODEL + h * BEAT_HEAD_DIM;
   float* xp = x + (long long)r * BEAT_DMODEL + h * BEAT_HEAD_DIM;
+  const float* xi = xp;
+  if constexpr (TRAIN) xi = keep.xin + (long long)r * BEAT_DMODEL + h * BEAT_HEAD_DIM;
 #pragma unroll
   for (int d = 0; d < BEAT_HEAD_DIM; d += 4) {
     const f32x4 ov = {o[d], o[d + 1], o[d + 2], o[d + 3]};
     *reinterpret_cast<f32x4*>(sp + d) = ov;
-    f32x4 xv = *reinterpret_cast<const f32x4*>(xp + d);
+    f32x4 xv = *reinterpret_cast<const f32x4*>(xi + d);
     xv[0] = xv[0] + ov[0]; xv[1] = xv[1] + ov[1]; xv[2] = xv[2] + ov[2]; xv[3] = xv[3] + ov[3];
     *reinterpret_cast<f32x4*>(xp + d) = xv;
   }
 }
-
 // per-layer skip into the tempo accumulator: tacc[f][d] (+)= (sum_i skip[row(i, f)][d]) / instr   (beat_transformer.py:82-84, 101), layers added in order
 __global__ __launch_bounds__(256) void k_beat_skipacc(const float* __restrict__ skip, BeatChunk c, int first_layer, float* __restrict__ tacc) {
   const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
   if (gid >= (long long)c.frames * BEAT_DMODEL) return;
   const int fl = (int)(gid >> 8), d = (int)(gid & 255);
-  const int gf = fl + c.frame_base, s = beat_song_of(c.frame0, c.first, c.count, gf);
-  const int T = c.frame0[s + 1] - c.frame0[s], t = gf - c.frame0[s], rb = c.row0[s] - c.row_base + t;
+  int s, T, rb;
+  beat_frame_at(c, fl, s, T, rb);
   float sum = 0.f;
   for (int i = 0; i < c.instr; ++i) sum += skip[(long long)(rb + i * T) * BEAT_DMODEL + d];
   const float m = sum / (float)c.instr;
@@ -170,6 +164,8 @@ __global__ __launch_bounds__(256) void k_beat_skipacc(const float* __restrict__ 
 
 // ================================================================================================ instrument attention (torch TransformerEncoderLayer self-attention)
 // 8-head attention over the instr rows of one frame, no mask; one thread per (frame, head, query instr); qkv = in_proj output [row][q|k|v].
+// (Loads, dots and axpys are written out, as in k_beat_dattn: on beat.h's helpers the compiler schedules both kernels differently.  The order of operations per
+// query is that of beat_dot32 / beat_axpy32, which the trainer's k_bt_iattn_bwd uses to recompute this softmax.)
 __global__ __launch_bounds__(256) void k_beat_iattn(const float* __restrict__ qkv, BeatChunk c, float* __restrict__ ao) {
   const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
   const int ni = c.instr;
@@ -267,6 +263,56 @@ __global__ __launch_bounds__(256) void k_beat_tempo(const float* __restrict__ pa
   }
 }
 
+// ================================================================================================ launchers of the stages shared with the trainer (beat.h)
+static inline unsigned nblk(long long threads) { return (unsigned)((threads + 255) / 256); }
+
+int launch_beat_conv1(const float* feat, const BeatChunk& c, const float* w, const float* b, float* c1, hipStream_t st) {
+  ProfScope ps("k_beat_conv1", st, (double)c.rows * BEAT_W1 * BEAT_C1 * 3 * 15 * 2, (double)c.rows * (BEAT_MELS * 4 + BEAT_W1 * BEAT_C1 * 4));
+  hipLaunchKernelGGL(k_beat_conv1, dim3(nblk((long long)c.rows * BEAT_W1 * BEAT_C1)), dim3(256), 0, st, feat, c, w, b, c1);
+  HIP_TRY(hipGetLastError());
+  return ETD_OK;
+}
+int launch_beat_patch3(const float* c2, int c2_cols, const BeatChunk& c, float* x3, hipStream_t st) {
+  if (c2_cols != BEAT_W1 && c2_cols != BEAT_C2_COLS) ETD_FAIL(ETD_EINVAL, "launch_beat_patch3: c2 of %d columns (%d or %d)", c2_cols, BEAT_W1, BEAT_C2_COLS);
+  ProfScope ps("k_beat_patch3", st, 0.0, (double)c.rows * 3 * BEAT_K3 * 4 * 2);
+  const dim3 grid(nblk((long long)c.rows * 3 * BEAT_K3));
+  if (c2_cols == BEAT_W1) hipLaunchKernelGGL(k_beat_patch3<BEAT_W1>, grid, dim3(256), 0, st, c2, c, x3);
+  else hipLaunchKernelGGL(k_beat_patch3<BEAT_C2_COLS>, grid, dim3(256), 0, st, c2, c, x3);
+  HIP_TRY(hipGetLastError());
+  return ETD_OK;
+}
+int launch_beat_pool3(const float* c3, int rows, float* x, hipStream_t st) {
+  ProfScope ps("k_beat_pool3", st, 0.0, (double)rows * 4 * 256 * 4);
+  hipLaunchKernelGGL(k_beat_pool3, dim3(nblk((long long)rows * 256)), dim3(256), 0, st, c3, rows, x);
+  HIP_TRY(hipGetLastError());
+  return ETD_OK;
+}
+#define BEAT_DATTN_SCOPE ProfScope ps("k_beat_dattn", st, (double)c.rows * BEAT_HEADS * BEAT_TAPS * BEAT_HEAD_DIM * 6, (double)c.rows * (768 * 4 * 3 + 256 * 4 * 3))
+int launch_beat_dattn(const float* qkv, const BeatChunk& c, const float* Er, int dil, float* skip, float* x, hipStream_t st) {
+  BEAT_DATTN_SCOPE;
+  hipLaunchKernelGGL(k_beat_dattn<false>, dim3(nblk((long long)c.rows * BEAT_HEADS)), dim3(256), 0, st, qkv, c, Er, dil, skip, x, BeatDattnKeep<false>{});
+  HIP_TRY(hipGetLastError());
+  return ETD_OK;
+}
+int launch_beat_dattn_train(const float* qkv, const BeatChunk& c, const float* Er, int dil, const float* xin, float* prob, float* skip, float* xout, hipStream_t st) {
+  BEAT_DATTN_SCOPE;
+  hipLaunchKernelGGL(k_beat_dattn<true>, dim3(nblk((long long)c.rows * BEAT_HEADS)), dim3(256), 0, st, qkv, c, Er, dil, skip, xout, BeatDattnKeep<true>{xin, prob});
+  HIP_TRY(hipGetLastError());
+  return ETD_OK;
+}
+int launch_beat_skipacc(const float* skip, const BeatChunk& c, int first_layer, float* tacc, hipStream_t st) {
+  ProfScope ps("k_beat_skipacc", st, (double)c.rows * 256, (double)c.rows * 256 * 4 + (double)c.frames * 256 * 8);
+  hipLaunchKernelGGL(k_beat_skipacc, dim3(nblk((long long)c.frames * 256)), dim3(256), 0, st, skip, c, first_layer, tacc);
+  HIP_TRY(hipGetLastError());
+  return ETD_OK;
+}
+int launch_beat_iattn(const float* qkv, const BeatChunk& c, float* ao, hipStream_t st) {
+  ProfScope ps("k_beat_iattn", st, (double)c.rows * BEAT_HEADS * c.instr * BEAT_HEAD_DIM * 4, (double)c.rows * (768 * 4 * (1 + 2 * c.instr) / 1.0 + 256 * 4));
+  hipLaunchKernelGGL(k_beat_iattn, dim3(nblk((long long)c.frames * BEAT_HEADS * c.instr)), dim3(256), 0, st, qkv, c, ao);
+  HIP_TRY(hipGetLastError());
+  return ETD_OK;
+}
+
 // ================================================================================================ host: the engine
 namespace {
 
@@ -304,8 +350,6 @@ int gemm(const G3Lin& L, const float* X, int M, int epi, float* Y, float* resid,
   if (epi == DEPI_RESID) { a.hin = resid; a.hout = resid; a.add = nullptr; }
   return launch_gemm3(a, epi, st);
 }
-
-inline unsigned nblk(long long threads) { return (unsigned)((threads + 255) / 256); }
 
 // per-row floats of the workspace: x, xa, skip (256 each), qkv 768, hid d_hid, conv1 42 x 32, conv2 42 x 64, conv3 patches 3 x 1152, conv3 out 3 x 256
 size_t ws_row_floats(int d_hid) { return 3 * 256 + 768 + (size_t)d_hid + BEAT_W1 * BEAT_C1 + BEAT_W1 * BEAT_C2 + 3 * BEAT_K3 + 3 * 256; }
@@ -354,27 +398,15 @@ int run_chunk(etd_beat* e, const float* feat_dev, const BeatChunk& c, int max_se
     return ETD_OK;
   };
   auto rtap = [&](float* dst, int sl, const float* src, long long width) { return tap(dst, sl, tp.rows, c.row_base, src, R, width); };
-  {  // conv front end
-    ProfScope ps("k_beat_conv1", st, fR * BEAT_W1 * BEAT_C1 * 3 * 15 * 2, fR * (BEAT_MELS * 4 + BEAT_W1 * BEAT_C1 * 4));
-    hipLaunchKernelGGL(k_beat_conv1, dim3(nblk((long long)R * BEAT_W1 * BEAT_C1)), dim3(256), 0, st, feat_dev + (long long)c.row_base * BEAT_MELS, c, e->c1w, e->c1b, e->c1);
-    HIP_TRY(hipGetLastError());
-  }
+  ETD_TRY(launch_beat_conv1(feat_dev + (long long)c.row_base * BEAT_MELS, c, e->c1w, e->c1b, e->c1, st));      // conv front end
   if (ton) ETD_TRY(rtap(tp.c1, 0, e->c1, BEAT_W1 * BEAT_C1));
   ETD_TRY(gemm(e->c2, e->c1, R * BEAT_W1, DEPI_BIAS, e->c2o, nullptr, st, BEAT_C1));      // row r 42 + col = the patch at (r 42 + col) 32
   if (ton) ETD_TRY(rtap(tp.c2, 0, e->c2o, BEAT_W1 * BEAT_C2));
-  {
-    ProfScope ps("k_beat_patch3", st, 0.0, fR * 3 * BEAT_K3 * 4 * 2);
-    hipLaunchKernelGGL(k_beat_patch3, dim3(nblk((long long)R * 3 * BEAT_K3)), dim3(256), 0, st, e->c2o, c, e->x3);
-    HIP_TRY(hipGetLastError());
-  }
+  ETD_TRY(launch_beat_patch3(e->c2o, BEAT_W1, c, e->x3, st));
   if (ton) ETD_TRY(rtap(tp.x3, 0, e->x3, 3 * BEAT_K3));
   ETD_TRY(gemm(e->c3, e->x3, R * 3, DEPI_BIAS, e->c3o, nullptr, st));
   if (ton) ETD_TRY(rtap(tp.c3, 0, e->c3o, 3 * 256));
-  {
-    ProfScope ps("k_beat_pool3", st, 0.0, fR * 4 * 256 * 4);
-    hipLaunchKernelGGL(k_beat_pool3, dim3(nblk((long long)R * 256)), dim3(256), 0, st, e->c3o, R, e->x);
-    HIP_TRY(hipGetLastError());
-  }
+  ETD_TRY(launch_beat_pool3(e->c3o, R, e->x, st));
   if (e->tap_front) HIP_TRY(hipMemcpyAsync(e->tap_front + (long long)c.row_base * 256, e->x, (size_t)R * 256 * 4, hipMemcpyDeviceToDevice, st));
   if (ton) ETD_TRY(rtap(tp.front, 0, e->x, 256));
   for (int l = 0; l < k.nlayers; ++l) {
@@ -385,17 +417,9 @@ int run_chunk(etd_beat* e, const float* feat_dev, const BeatChunk& c, int max_se
     if (tl) ETD_TRY(rtap(tp.ln1, sl, e->xa, 256));
     ETD_TRY(gemm(L.qkv, e->xa, R, DEPI_BIAS, e->qkv, nullptr, st));
     if (tl) ETD_TRY(rtap(tp.qkv, sl, e->qkv, 768));
-    {
-      ProfScope ps("k_beat_dattn", st, fR * BEAT_HEADS * BEAT_TAPS * BEAT_HEAD_DIM * 6, fR * (768 * 4 * 3 + 256 * 4 * 3));
-      hipLaunchKernelGGL(k_beat_dattn, dim3(nblk((long long)R * BEAT_HEADS)), dim3(256), 0, st, e->qkv, c, L.Er, 1 << l, e->skip, e->x);
-      HIP_TRY(hipGetLastError());
-    }
+    ETD_TRY(launch_beat_dattn(e->qkv, c, L.Er, 1 << l, e->skip, e->x, st));
     if (tl) { ETD_TRY(rtap(tp.skip, sl, e->skip, 256)); ETD_TRY(rtap(tp.x_attn, sl, e->x, 256)); }
-    {
-      ProfScope ps("k_beat_skipacc", st, fR * 256, fR * 256 * 4 + (double)F * 256 * 8);
-      hipLaunchKernelGGL(k_beat_skipacc, dim3(nblk((long long)F * 256)), dim3(256), 0, st, e->skip, c, l == 0 ? 1 : 0, e->tacc);
-      HIP_TRY(hipGetLastError());
-    }
+    ETD_TRY(launch_beat_skipacc(e->skip, c, l == 0 ? 1 : 0, e->tacc, st));
     if (tl) ETD_TRY(tap(tp.tacc, sl, tp.frames, c.frame_base, e->tacc, F, 256));
     ETD_TRY(launch_ln_rows_f32(e->x, R, 256, L.ln2g, L.ln2b, nullptr, nullptr, 1e-5f, e->xa, nullptr, st));
     if (tl) ETD_TRY(rtap(tp.ln2, sl, e->xa, 256));
@@ -410,11 +434,7 @@ int run_chunk(etd_beat* e, const float* feat_dev, const BeatChunk& c, int max_se
       if (tl) ETD_TRY(rtap(tp.iln1, isl, e->xa, 256));
       ETD_TRY(gemm(I.inp, e->xa, R, DEPI_BIAS, e->qkv, nullptr, st));
       if (tl) ETD_TRY(rtap(tp.iqkv, isl, e->qkv, 768));
-      {
-        ProfScope ps("k_beat_iattn", st, fR * BEAT_HEADS * k.instr * BEAT_HEAD_DIM * 4, fR * (768 * 4 * (1 + 2 * k.instr) / 1.0 + 256 * 4));
-        hipLaunchKernelGGL(k_beat_iattn, dim3(nblk((long long)F * BEAT_HEADS * k.instr)), dim3(256), 0, st, e->qkv, c, e->skip);
-        HIP_TRY(hipGetLastError());
-      }
+      ETD_TRY(launch_beat_iattn(e->qkv, c, e->skip, st));
       if (tl) ETD_TRY(rtap(tp.iao, isl, e->skip, 256));
       ETD_TRY(gemm(I.outp, e->skip, R, DEPI_RESID, nullptr, e->x, st));
       if (tl) ETD_TRY(rtap(tp.ix_attn, isl, e->x, 256));

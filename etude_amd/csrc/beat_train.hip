@@ -1,8 +1,12 @@
-// Training engine of the Beat-Transformer (beat_train.h): the model csrc/beat.hip runs (Demixed_DilatedTransformerModel in eval arithmetic: no
-// dropout), with saved activations, this project's beat / tempo loss, the backward pass for every parameter, gradient accumulation, clip_grad_norm_ and AdamW.
+// Training engine of the Beat-Transformer (beat_train.h): Demixed_DilatedTransformerModel in eval arithmetic (no dropout) with saved activations, this
+// project's beat / tempo loss, the backward pass for every parameter, gradient accumulation, clip_grad_norm_ and AdamW.
 //
-// Rows are (song, instr, t) as in beat.hip: song s owns rows [row0_s, row0_s + instr T_s) laid out [instr][T_s]; frames are (song, t).  One call is one chunk: its rows
-// must fit the workspace sized at create.
+// The non-GEMM forward stages are the inference engine's kernels, launched through beat.h: k_beat_conv1, k_beat_patch3 (its 24-column instance), k_beat_pool3,
+// k_beat_dattn (its instance that keeps the probabilities and writes out of place), k_beat_skipacc and k_beat_iattn.  Forward kernels of this file: k_bt_patch2
+// (conv2's explicit patches; the engine's GEMM reads overlapping rows instead), k_bt_hmean and k_bt_tmean (the heads' means, which feed launch_tgemm; the engine fuses
+// them with its GEMVs) and k_bt_relu.  Everything else here is loss and backward.  The song table is the engine's BeatChunk, one chunk for the whole call
+// (beat_whole_call: its rows must fit the workspace sized at create), and the backward kernels locate rows, load, dot and recompute conv1 with beat.h's helpers.
+// Rows are (song, instr, t) as in beat.hip: song s owns rows [row0_s, row0_s + instr T_s) laid out [instr][T_s]; frames are (song, t).
 // Arithmetic: fp32 operands and accumulation.  Every dense product (the linear layers, conv2 and conv3 on explicit patches, the two heads) is launch_tgemm of
 // train_kernels.h in its forward, input-gradient and weight-gradient form.  No floating-point atomics: a kernel either owns its output element and adds its terms in an
 // order fixed by the shapes (taps ascending, kw ascending, instruments ascending), or reduces over rows in fixed slices followed by an ordered sum.  Every gradient
@@ -19,99 +23,16 @@
 #include "etude_hip_debug.h"
 #include "train_store.h"
 
-#define BT_SCALE 5.656854249492380195f      // sqrt(head_dim)
-
-__device__ __forceinline__ int bt_song_of(const int* off, int n, int g) {       // largest s with off[s] <= g
-  int lo = 0, hi = n - 1;
-  while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (off[mid] <= g) lo = mid; else hi = mid - 1; }
-  return lo;
-}
-__device__ __forceinline__ int bt_tap_off(int h, int j) { return h < 4 ? j - 2 : h == 4 ? j - 4 : h == 5 ? j - 3 : h == 6 ? j - 1 : j; }
-__device__ __forceinline__ void bt_load32(float (&a)[32], const float* __restrict__ p) {
-#pragma unroll
-  for (int d = 0; d < 32; d += 4) { const f32x4 v = *reinterpret_cast<const f32x4*>(p + d); a[d] = v[0]; a[d + 1] = v[1]; a[d + 2] = v[2]; a[d + 3] = v[3]; }
-}
-__device__ __forceinline__ void bt_store32(float* __restrict__ p, const float (&a)[32]) {
-#pragma unroll
-  for (int d = 0; d < 32; d += 4) { const f32x4 v = {a[d], a[d + 1], a[d + 2], a[d + 3]}; *reinterpret_cast<f32x4*>(p + d) = v; }
-}
-__device__ __forceinline__ float bt_dot32(const float (&a)[32], const float* __restrict__ p) {
-  float s = 0.f;
-#pragma unroll
-  for (int d = 0; d < 32; d += 4) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(p + d);
-    s = fmaf(a[d], v[0], s); s = fmaf(a[d + 1], v[1], s); s = fmaf(a[d + 2], v[2], s); s = fmaf(a[d + 3], v[3], s);
-  }
-  return s;
-}
-__device__ __forceinline__ void bt_axpy32(float (&acc)[32], float s, const float* __restrict__ p) {
-#pragma unroll
-  for (int d = 0; d < 32; d += 4) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(p + d);
-    acc[d] = fmaf(s, v[0], acc[d]); acc[d + 1] = fmaf(s, v[1], acc[d + 1]); acc[d + 2] = fmaf(s, v[2], acc[d + 2]); acc[d + 3] = fmaf(s, v[3], acc[d + 3]);
-  }
-}
-
 // ================================================================================================ conv front end, forward
-// one conv1 output before pooling: b + sum_{kt<5,kw<3} w[kt][kw] x[t + kt - 2][col + kw], x = 0 outside the song; forward and backward share this chain, so the
-// backward finds the maximum the forward took
-__device__ __forceinline__ float bt_conv1_at(const float* __restrict__ feat, long long r, int t, int T, int col, const float (&wr)[15], float b) {
-  float acc = b;
-#pragma unroll
-  for (int kt = 0; kt < 5; ++kt) {
-    const int tt = t + kt - 2;
-    if (tt < 0 || tt >= T) continue;
-    const float* xr = feat + (r + kt - 2) * BEAT_MELS + col;
-#pragma unroll
-    for (int kw = 0; kw < 3; ++kw) acc = fmaf(wr[kt * 3 + kw], xr[kw], acc);
-  }
-  return acc;
-}
-// c1[r][p][co] = relu(max_{u<3} conv1(r, 3 p + u, co)); one thread per (row, p, co)
-__global__ __launch_bounds__(256) void k_bt_conv1(const float* __restrict__ feat, BtSongs S, const float* __restrict__ w, const float* __restrict__ b, float* __restrict__ c1) {
-  const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (gid >= (long long)S.rows * BEAT_W1 * BEAT_C1) return;
-  const int r = (int)(gid / (BEAT_W1 * BEAT_C1)), rem = (int)(gid - (long long)r * (BEAT_W1 * BEAT_C1)), p = rem / BEAT_C1, co = rem - p * BEAT_C1;
-  const int s = bt_song_of(S.row0, S.n, r), T = S.frame0[s + 1] - S.frame0[s], t = (r - S.row0[s]) % T;
-  float wr[15];
-#pragma unroll
-  for (int k = 0; k < 15; ++k) wr[k] = w[co * 15 + k];
-  float m = -INFINITY;
-#pragma unroll 1
-  for (int u = 0; u < 3; ++u) m = fmaxf(m, bt_conv1_at(feat, r, t, T, 3 * p + u, wr, b[co]));
-  c1[gid] = fmaxf(m, 0.f);
-}
 // conv2's patches: x2[r 24 + col][kw 32 + ci] = c1[r][col + kw][ci], the 384 floats from (r 42 + col) 32 on
 __global__ __launch_bounds__(256) void k_bt_patch2(const float* __restrict__ c1, int rows, float* __restrict__ x2) {
   const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (gid >= (long long)rows * BT_C2_COLS * BEAT_K2) return;
+  if (gid >= (long long)rows * BEAT_C2_COLS * BEAT_K2) return;
   const long long rc = gid / BEAT_K2;
   const int k = (int)(gid - rc * BEAT_K2);
-  const long long r = rc / BT_C2_COLS;
-  const int col = (int)(rc - r * BT_C2_COLS);
+  const long long r = rc / BEAT_C2_COLS;
+  const int col = (int)(rc - r * BEAT_C2_COLS);
   x2[gid] = c1[(r * BEAT_W1 + col) * BEAT_C1 + k];
-}
-// conv3's patches through pool2 + ReLU: x3[r 3 + c][kt 384 + kw 64 + ci] = relu(max_{u<3} c2[r + kt - 1][3 (c + kw) + u][ci]), 0 outside the song; c2 is [rows][24][64]
-__global__ __launch_bounds__(256) void k_bt_patch3(const float* __restrict__ c2, BtSongs S, float* __restrict__ x3) {
-  const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (gid >= (long long)S.rows * 3 * BEAT_K3) return;
-  const int rc = (int)(gid / BEAT_K3), k = (int)(gid - (long long)rc * BEAT_K3);
-  const int r = rc / 3, col = rc - r * 3, kt = k / 384, kw = (k - kt * 384) / 64, ci = k & 63;
-  const int s = bt_song_of(S.row0, S.n, r), T = S.frame0[s + 1] - S.frame0[s], t = (r - S.row0[s]) % T, tt = t + kt - 1;
-  float v = 0.f;
-  if (tt >= 0 && tt < T) {
-    const float* p = c2 + ((long long)(r + kt - 1) * BT_C2_COLS + 3 * (col + kw)) * BEAT_C2 + ci;
-    v = fmaxf(fmaxf(fmaxf(p[0], p[BEAT_C2]), p[2 * BEAT_C2]), 0.f);
-  }
-  x3[gid] = v;
-}
-__global__ __launch_bounds__(256) void k_bt_pool3(const float* __restrict__ c3, int rows, float* __restrict__ x) {
-  const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (gid >= (long long)rows * BEAT_DMODEL) return;
-  const long long r = gid >> 8;
-  const int co = (int)(gid & 255);
-  const float* p = c3 + r * 3 * BEAT_DMODEL + co;
-  x[gid] = fmaxf(fmaxf(fmaxf(p[0], p[BEAT_DMODEL]), p[2 * BEAT_DMODEL]), 0.f);
 }
 // a conv weight between the state dict's [co][ci][kk] and the GEMM's [co][kk][ci].  dir 0: packed = native; dir 1: native += packed (a gradient)
 __global__ __launch_bounds__(256) void k_bt_repack(float* __restrict__ native, float* __restrict__ packed, int co_n, int ci_n, int kk_n, int dir) {
@@ -143,11 +64,12 @@ __global__ __launch_bounds__(256) void k_bt_pool3_bwd(const float* __restrict__ 
 }
 // conv3's patch gradient gathered back through pool2 + ReLU into conv2's output gradient: the pooled cell (r, pc, ci) is read by the patches (r - kt + 1, c, kw = pc - c);
 // its terms are added kt ascending, then c ascending.  One thread per (row, pooled column < 8, ci), writing the cell's three conv2 columns.
-__global__ __launch_bounds__(256) void k_bt_patch3_bwd(const float* __restrict__ c2, const float* __restrict__ dx3, BtSongs S, float* __restrict__ dc2) {
+__global__ __launch_bounds__(256) void k_bt_patch3_bwd(const float* __restrict__ c2, const float* __restrict__ dx3, BeatChunk S, float* __restrict__ dc2) {
   const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
   if (gid >= (long long)S.rows * 8 * BEAT_C2) return;
   const int r = (int)(gid / (8 * BEAT_C2)), rem = (int)(gid - (long long)r * 8 * BEAT_C2), pc = rem / BEAT_C2, ci = rem - pc * BEAT_C2;
-  const int s = bt_song_of(S.row0, S.n, r), T = S.frame0[s + 1] - S.frame0[s], t = (r - S.row0[s]) % T;
+  int s, T, t;
+  beat_row_at(S, r, s, T, t);
   float g = 0.f;
   for (int kt = 0; kt < 3; ++kt) {
     const int tq = t - kt + 1;
@@ -158,7 +80,7 @@ __global__ __launch_bounds__(256) void k_bt_patch3_bwd(const float* __restrict__
       g += dx3[((long long)(r - kt + 1) * 3 + c) * BEAT_K3 + kt * 384 + kw * 64 + ci];
     }
   }
-  const long long o = ((long long)r * BT_C2_COLS + 3 * pc) * BEAT_C2 + ci;
+  const long long o = ((long long)r * BEAT_C2_COLS + 3 * pc) * BEAT_C2 + ci;
   float g0, g1, g2;
   bt_pool_route(c2[o], c2[o + BEAT_C2], c2[o + 2 * BEAT_C2], g, g0, g1, g2);
   dc2[o] = g0; dc2[o + BEAT_C2] = g1; dc2[o + 2 * BEAT_C2] = g2;
@@ -171,14 +93,14 @@ __global__ __launch_bounds__(256) void k_bt_fold2(const float* __restrict__ dpat
   float g = 0.f;
   for (int kw = 0; kw < 12; ++kw) {
     const int col = p - kw;
-    if (col < 0 || col >= BT_C2_COLS) continue;
-    g += dpatch[(r * BT_C2_COLS + col) * BEAT_K2 + kw * BEAT_C1 + ci];
+    if (col < 0 || col >= BEAT_C2_COLS) continue;
+    g += dpatch[(r * BEAT_C2_COLS + col) * BEAT_K2 + kw * BEAT_C1 + ci];
   }
   dc1[gid] = c1[gid] > 0.f ? g : 0.f;
 }
 // conv1 dW / db, level 1: workgroup = one slice of BT_C1_ROWS rows; thread = (co, one of 8 sub-slices of the slice's (row, p) cells, taken every 8th in ascending order);
 // the 8 sub-slices are added in order.  part[slice][co][16]: 15 weights + the bias.
-__global__ __launch_bounds__(256) void k_bt_conv1_bwd(const float* __restrict__ feat, const float* __restrict__ dc1, BtSongs S, const float* __restrict__ w,
+__global__ __launch_bounds__(256) void k_bt_conv1_bwd(const float* __restrict__ feat, const float* __restrict__ dc1, BeatChunk S, const float* __restrict__ w,
                                                       const float* __restrict__ b, float* __restrict__ part) {
   __shared__ float ps[8][32][17];
   const int tid = threadIdx.x, co = tid & 31, sub = tid >> 5;
@@ -194,12 +116,13 @@ __global__ __launch_bounds__(256) void k_bt_conv1_bwd(const float* __restrict__ 
     const int r = (int)r0 + idx / BEAT_W1, p = idx % BEAT_W1;
     const float dm = dc1[((long long)r * BEAT_W1 + p) * BEAT_C1 + co];
     if (dm == 0.f) continue;                           // (adds exact zeros)
-    const int s = bt_song_of(S.row0, S.n, r), T = S.frame0[s + 1] - S.frame0[s], t = (r - S.row0[s]) % T;
+    int s, T, t;
+  beat_row_at(S, r, s, T, t);
     float m = -INFINITY;
     int um = 0;
 #pragma unroll 1
     for (int u = 0; u < 3; ++u) {
-      const float v = bt_conv1_at(feat, r, t, T, 3 * p + u, wr, bc);
+      const float v = beat_conv1_at(feat, r, t, T, p, u, wr, bc);      // the chain k_beat_conv1 runs: the maximum the forward took
       if (v > m) { m = v; um = u; }                    // strict: the first maximal column
     }
 #pragma unroll
@@ -259,68 +182,25 @@ __global__ __launch_bounds__(256) void k_bt_colsum_part(const float* __restrict_
 }
 
 // ================================================================================================ dilated 5-tap attention
-// forward of k_beat_dattn with the probabilities kept: one thread per (row, head); a tap outside the song is masked by index
-__global__ __launch_bounds__(256) void k_bt_dattn(const float* __restrict__ qkv, BtSongs S, const float* __restrict__ Er, int dil, const float* __restrict__ xin,
-                                                  float* __restrict__ prob, float* __restrict__ skip, float* __restrict__ xout) {
-  const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (gid >= (long long)S.rows * BEAT_HEADS) return;
-  const int r = (int)(gid >> 3), h = (int)(gid & 7), kh = h == 7 ? 6 : h;
-  const int s = bt_song_of(S.row0, S.n, r), T = S.frame0[s + 1] - S.frame0[s], t = (r - S.row0[s]) % T;
-  float q[32];
-  bt_load32(q, qkv + (long long)r * 768 + h * 32);
-  const float* er = Er + h * 32 * BEAT_TAPS;
-  float lg[BEAT_TAPS];
-  bool ok[BEAT_TAPS];
-  float mx = -INFINITY;
-#pragma unroll
-  for (int j = 0; j < BEAT_TAPS; ++j) {
-    const long long o = (long long)bt_tap_off(h, j) * dil, tt = t + o;
-    ok[j] = tt >= 0 && tt < T;
-    float qk = 0.f, qe = 0.f;
-#pragma unroll
-    for (int d = 0; d < 32; ++d) qe = fmaf(q[d], er[d * BEAT_TAPS + j], qe);
-    if (ok[j]) qk = bt_dot32(q, qkv + (r + o) * 768 + 256 + kh * 32);
-    lg[j] = (qk + qe) / BT_SCALE;
-    if (ok[j]) mx = fmaxf(mx, lg[j]);
-  }
-  float den = 0.f;
-#pragma unroll
-  for (int j = 0; j < BEAT_TAPS; ++j) { lg[j] = ok[j] ? expf(lg[j] - mx) : 0.f; den += lg[j]; }
-  float o32[32];
-#pragma unroll
-  for (int d = 0; d < 32; ++d) o32[d] = 0.f;
-#pragma unroll
-  for (int j = 0; j < BEAT_TAPS; ++j) {
-    const float p = ok[j] ? lg[j] / den : 0.f;
-    prob[gid * BEAT_TAPS + j] = p;
-    if (ok[j]) bt_axpy32(o32, p, qkv + (r + (long long)bt_tap_off(h, j) * dil) * 768 + 512 + h * 32);
-  }
-  const long long xo = (long long)r * BEAT_DMODEL + h * 32;
-  bt_store32(skip + xo, o32);
-  float xi[32];
-  bt_load32(xi, xin + xo);
-#pragma unroll
-  for (int d = 0; d < 32; ++d) xi[d] = xi[d] + o32[d];
-  bt_store32(xout + xo, xi);
-}
 // backward, query side: dl[r][h][j] = p_j (dO . v_j - sum_i p_i dO . v_i) / sqrt(32), dq = sum_j dl_j (k_j + Er[h][:, j]), taps ascending
-__global__ __launch_bounds__(256) void k_bt_dattn_dq(const float* __restrict__ qkv, const float* __restrict__ prob, const float* __restrict__ dO, BtSongs S,
+__global__ __launch_bounds__(256) void k_bt_dattn_dq(const float* __restrict__ qkv, const float* __restrict__ prob, const float* __restrict__ dO, BeatChunk S,
                                                      const float* __restrict__ Er, int dil, float* __restrict__ dl, float* __restrict__ dqkv) {
   const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
   if (gid >= (long long)S.rows * BEAT_HEADS) return;
   const int r = (int)(gid >> 3), h = (int)(gid & 7), kh = h == 7 ? 6 : h;
-  const int s = bt_song_of(S.row0, S.n, r), T = S.frame0[s + 1] - S.frame0[s], t = (r - S.row0[s]) % T;
+  int s, T, t;
+  beat_row_at(S, r, s, T, t);
   float go[32];
-  bt_load32(go, dO + (long long)r * BEAT_DMODEL + h * 32);
+  beat_load32(go, dO + (long long)r * BEAT_DMODEL + h * 32);
   float p[BEAT_TAPS], dp[BEAT_TAPS];
   bool ok[BEAT_TAPS];
   float sum = 0.f;
 #pragma unroll
   for (int j = 0; j < BEAT_TAPS; ++j) {
-    const long long o = (long long)bt_tap_off(h, j) * dil, tt = t + o;
+    const long long o = (long long)beat_tap_off(h, j) * dil, tt = t + o;
     ok[j] = tt >= 0 && tt < T;
     p[j] = prob[gid * BEAT_TAPS + j];
-    dp[j] = ok[j] ? bt_dot32(go, qkv + (r + o) * 768 + 512 + h * 32) : 0.f;
+    dp[j] = ok[j] ? beat_dot32(go, qkv + (r + o) * 768 + 512 + h * 32) : 0.f;
     sum = fmaf(p[j], dp[j], sum);
   }
   float dq[32];
@@ -329,46 +209,47 @@ __global__ __launch_bounds__(256) void k_bt_dattn_dq(const float* __restrict__ q
   const float* er = Er + h * 32 * BEAT_TAPS;
 #pragma unroll
   for (int j = 0; j < BEAT_TAPS; ++j) {
-    const float g = ok[j] ? p[j] * (dp[j] - sum) / BT_SCALE : 0.f;
+    const float g = ok[j] ? p[j] * (dp[j] - sum) / BEAT_SCALE : 0.f;
     dl[gid * BEAT_TAPS + j] = g;
     if (!ok[j]) continue;
-    const float* kp = qkv + (r + (long long)bt_tap_off(h, j) * dil) * 768 + 256 + kh * 32;
+    const float* kp = qkv + (r + (long long)beat_tap_off(h, j) * dil) * 768 + 256 + kh * 32;
 #pragma unroll
     for (int d = 0; d < 32; ++d) dq[d] = fmaf(g, kp[d] + er[d * BEAT_TAPS + j], dq[d]);
   }
-  bt_store32(dqkv + (long long)r * 768 + h * 32, dq);
+  beat_store32(dqkv + (long long)r * 768 + h * 32, dq);
 }
 // backward, key side: one thread per (key row, head).  dv = sum over the taps j (ascending) whose query row r - o_h(j) dil lies in the song of p_j dO; dk likewise of dl_j q,
 // key head 6 first from query head 6 and then from query head 7 (which reads head 6's keys); key head 7 is read by no query: exact zeros
 __global__ __launch_bounds__(256) void k_bt_dattn_dkv(const float* __restrict__ qkv, const float* __restrict__ prob, const float* __restrict__ dl,
-                                                      const float* __restrict__ dO, BtSongs S, int dil, float* __restrict__ dqkv) {
+                                                      const float* __restrict__ dO, BeatChunk S, int dil, float* __restrict__ dqkv) {
   const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
   if (gid >= (long long)S.rows * BEAT_HEADS) return;
   const int r = (int)(gid >> 3), h = (int)(gid & 7);
-  const int s = bt_song_of(S.row0, S.n, r), T = S.frame0[s + 1] - S.frame0[s], t = (r - S.row0[s]) % T;
+  int s, T, t;
+  beat_row_at(S, r, s, T, t);
   float dk[32], dv[32];
 #pragma unroll
   for (int d = 0; d < 32; ++d) { dk[d] = 0.f; dv[d] = 0.f; }
 #pragma unroll
   for (int j = 0; j < BEAT_TAPS; ++j) {
-    const long long o = (long long)bt_tap_off(h, j) * dil, tq = t - o;
+    const long long o = (long long)beat_tap_off(h, j) * dil, tq = t - o;
     if (tq < 0 || tq >= T) continue;
     const long long rq = r - o;
-    bt_axpy32(dv, prob[(rq * 8 + h) * BEAT_TAPS + j], dO + rq * BEAT_DMODEL + h * 32);
+    beat_axpy32(dv, prob[(rq * 8 + h) * BEAT_TAPS + j], dO + rq * BEAT_DMODEL + h * 32);
   }
   if (h != 7) {
     for (int qh = h; qh < (h == 6 ? 8 : h + 1); ++qh) {
 #pragma unroll
       for (int j = 0; j < BEAT_TAPS; ++j) {
-        const long long o = (long long)bt_tap_off(qh, j) * dil, tq = t - o;
+        const long long o = (long long)beat_tap_off(qh, j) * dil, tq = t - o;
         if (tq < 0 || tq >= T) continue;
         const long long rq = r - o;
-        bt_axpy32(dk, dl[(rq * 8 + qh) * BEAT_TAPS + j], qkv + rq * 768 + qh * 32);
+        beat_axpy32(dk, dl[(rq * 8 + qh) * BEAT_TAPS + j], qkv + rq * 768 + qh * 32);
       }
     }
   }
-  bt_store32(dqkv + (long long)r * 768 + 256 + h * 32, dk);
-  bt_store32(dqkv + (long long)r * 768 + 512 + h * 32, dv);
+  beat_store32(dqkv + (long long)r * 768 + 256 + h * 32, dk);
+  beat_store32(dqkv + (long long)r * 768 + 512 + h * 32, dv);
 }
 // dEr, level 1: part[slice][h][d][j] = sum over the slice's rows, ascending, of dl[r][h][j] q[r][h][d]; 1280 outputs, 5 per thread
 __global__ __launch_bounds__(256) void k_bt_der_part(const float* __restrict__ qkv, const float* __restrict__ dl, int rows, float* __restrict__ part) {
@@ -382,40 +263,13 @@ __global__ __launch_bounds__(256) void k_bt_der_part(const float* __restrict__ q
 }
 
 // ================================================================================================ instrument attention: one thread per (frame, head)
-__global__ __launch_bounds__(64) void k_bt_iattn(const float* __restrict__ qkv, BtSongs S, float* __restrict__ ao) {
-  const long long gid = (long long)blockIdx.x * 64 + threadIdx.x;
-  if (gid >= (long long)S.frames * BEAT_HEADS) return;
-  const int f = (int)(gid >> 3), h = (int)(gid & 7), ni = S.instr;
-  const int s = bt_song_of(S.frame0, S.n, f), T = S.frame0[s + 1] - S.frame0[s];
-  const long long rb = S.row0[s] + (f - S.frame0[s]);
-  for (int i = 0; i < ni; ++i) {
-    float q[32], lg[8];
-    bt_load32(q, qkv + (rb + (long long)i * T) * 768 + h * 32);
-    float mx = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      lg[j] = -INFINITY;
-      if (j < ni) { lg[j] = bt_dot32(q, qkv + (rb + (long long)j * T) * 768 + 256 + h * 32) / BT_SCALE; mx = fmaxf(mx, lg[j]); }
-    }
-    float den = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { lg[j] = j < ni ? expf(lg[j] - mx) : 0.f; den += lg[j]; }
-    float o[32];
-#pragma unroll
-    for (int d = 0; d < 32; ++d) o[d] = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      if (j < ni) bt_axpy32(o, lg[j] / den, qkv + (rb + (long long)j * T) * 768 + 512 + h * 32);
-    bt_store32(ao + (rb + (long long)i * T) * BEAT_DMODEL + h * 32, o);
-  }
-}
 // backward: the softmax is recomputed as the forward computes it; dq of query i adds its keys in ascending order, dk and dv of key j their queries in ascending order
-__global__ __launch_bounds__(64) void k_bt_iattn_bwd(const float* __restrict__ qkv, const float* __restrict__ dao, BtSongs S, float* __restrict__ dqkv) {
+__global__ __launch_bounds__(64) void k_bt_iattn_bwd(const float* __restrict__ qkv, const float* __restrict__ dao, BeatChunk S, float* __restrict__ dqkv) {
   const long long gid = (long long)blockIdx.x * 64 + threadIdx.x;
   if (gid >= (long long)S.frames * BEAT_HEADS) return;
   const int f = (int)(gid >> 3), h = (int)(gid & 7), ni = S.instr;
-  const int s = bt_song_of(S.frame0, S.n, f), T = S.frame0[s + 1] - S.frame0[s];
-  const long long rb = S.row0[s] + (f - S.frame0[s]);
+  int s, T, rb;
+  beat_frame_at(S, f, s, T, rb);
   float p[8][8], ds[8][8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
@@ -423,16 +277,16 @@ __global__ __launch_bounds__(64) void k_bt_iattn_bwd(const float* __restrict__ q
     for (int j = 0; j < 8; ++j) { p[i][j] = 0.f; ds[i][j] = 0.f; }
     if (i >= ni) continue;
     float q[32], go[32], lg[8], dp[8];
-    bt_load32(q, qkv + (rb + (long long)i * T) * 768 + h * 32);
-    bt_load32(go, dao + (rb + (long long)i * T) * BEAT_DMODEL + h * 32);
+    beat_load32(q, qkv + (rb + (long long)i * T) * 768 + h * 32);
+    beat_load32(go, dao + (rb + (long long)i * T) * BEAT_DMODEL + h * 32);
     float mx = -INFINITY;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       lg[j] = -INFINITY; dp[j] = 0.f;
       if (j < ni) {
-        lg[j] = bt_dot32(q, qkv + (rb + (long long)j * T) * 768 + 256 + h * 32) / BT_SCALE;
+        lg[j] = beat_dot32(q, qkv + (rb + (long long)j * T) * 768 + 256 + h * 32) / BEAT_SCALE;
         mx = fmaxf(mx, lg[j]);
-        dp[j] = bt_dot32(go, qkv + (rb + (long long)j * T) * 768 + 512 + h * 32);
+        dp[j] = beat_dot32(go, qkv + (rb + (long long)j * T) * 768 + 512 + h * 32);
       }
     }
     float den = 0.f;
@@ -447,10 +301,10 @@ __global__ __launch_bounds__(64) void k_bt_iattn_bwd(const float* __restrict__ q
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       if (j >= ni) continue;
-      ds[i][j] = p[i][j] * (dp[j] - sum) / BT_SCALE;
-      bt_axpy32(dq, ds[i][j], qkv + (rb + (long long)j * T) * 768 + 256 + h * 32);
+      ds[i][j] = p[i][j] * (dp[j] - sum) / BEAT_SCALE;
+      beat_axpy32(dq, ds[i][j], qkv + (rb + (long long)j * T) * 768 + 256 + h * 32);
     }
-    bt_store32(dqkv + (rb + (long long)i * T) * 768 + h * 32, dq);
+    beat_store32(dqkv + (rb + (long long)i * T) * 768 + h * 32, dq);
   }
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
@@ -461,57 +315,47 @@ __global__ __launch_bounds__(64) void k_bt_iattn_bwd(const float* __restrict__ q
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       if (i >= ni) continue;
-      bt_axpy32(dk, ds[i][j], qkv + (rb + (long long)i * T) * 768 + h * 32);
-      bt_axpy32(dv, p[i][j], dao + (rb + (long long)i * T) * BEAT_DMODEL + h * 32);
+      beat_axpy32(dk, ds[i][j], qkv + (rb + (long long)i * T) * 768 + h * 32);
+      beat_axpy32(dv, p[i][j], dao + (rb + (long long)i * T) * BEAT_DMODEL + h * 32);
     }
-    bt_store32(dqkv + (rb + (long long)j * T) * 768 + 256 + h * 32, dk);
-    bt_store32(dqkv + (rb + (long long)j * T) * 768 + 512 + h * 32, dv);
+    beat_store32(dqkv + (rb + (long long)j * T) * 768 + 256 + h * 32, dk);
+    beat_store32(dqkv + (rb + (long long)j * T) * 768 + 512 + h * 32, dv);
   }
 }
 
 // ================================================================================================ skip sum, heads and their backward passes
-// tacc[f][d] (+)= (sum_i skip[row(i, f)][d]) / instr, layers added in order
-__global__ __launch_bounds__(256) void k_bt_skipacc(const float* __restrict__ skip, BtSongs S, int first_layer, float* __restrict__ tacc) {
-  const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (gid >= (long long)S.frames * BEAT_DMODEL) return;
-  const int f = (int)(gid >> 8), d = (int)(gid & 255);
-  const int s = bt_song_of(S.frame0, S.n, f), T = S.frame0[s + 1] - S.frame0[s];
-  const long long rb = S.row0[s] + (f - S.frame0[s]);
-  float sum = 0.f;
-  for (int i = 0; i < S.instr; ++i) sum += skip[(rb + (long long)i * T) * BEAT_DMODEL + d];
-  const float m = sum / (float)S.instr;
-  tacc[gid] = first_layer ? m : tacc[gid] + m;
-}
 // every time layer's skip gets the same gradient from the tempo head, dtf[f] (already divided by instr): dsk[r] = dx[r] + dtf[frame of r]
-__global__ __launch_bounds__(256) void k_bt_dskip(const float* __restrict__ dx, const float* __restrict__ dtf, BtSongs S, float* __restrict__ dsk) {
+__global__ __launch_bounds__(256) void k_bt_dskip(const float* __restrict__ dx, const float* __restrict__ dtf, BeatChunk S, float* __restrict__ dsk) {
   const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
   if (gid >= (long long)S.rows * BEAT_DMODEL) return;
   const int r = (int)(gid >> 8), d = (int)(gid & 255);
-  const int s = bt_song_of(S.row0, S.n, r), T = S.frame0[s + 1] - S.frame0[s], t = (r - S.row0[s]) % T;
-  dsk[gid] = dx[gid] + dtf[((long long)S.frame0[s] + t) * BEAT_DMODEL + d];
+  int s, T, t;
+  beat_row_at(S, r, s, T, t);
+  dsk[gid] = dx[gid] + dtf[((long long)S.frame0[s] - S.frame_base + t) * BEAT_DMODEL + d];
 }
 // hm[f][d] = (sum_i relu(x[row(i, f)][d])) / instr: the beat head's input
-__global__ __launch_bounds__(256) void k_bt_hmean(const float* __restrict__ x, BtSongs S, float* __restrict__ hm) {
+__global__ __launch_bounds__(256) void k_bt_hmean(const float* __restrict__ x, BeatChunk S, float* __restrict__ hm) {
   const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
   if (gid >= (long long)S.frames * BEAT_DMODEL) return;
   const int f = (int)(gid >> 8), d = (int)(gid & 255);
-  const int s = bt_song_of(S.frame0, S.n, f), T = S.frame0[s + 1] - S.frame0[s];
-  const long long rb = S.row0[s] + (f - S.frame0[s]);
+  int s, T, rb;
+  beat_frame_at(S, f, s, T, rb);
   float sum = 0.f;
   for (int i = 0; i < S.instr; ++i) sum += fmaxf(x[(rb + (long long)i * T) * BEAT_DMODEL + d], 0.f);
   hm[gid] = sum / (float)S.instr;
 }
-__global__ __launch_bounds__(256) void k_bt_hmean_bwd(const float* __restrict__ x, const float* __restrict__ dhm, BtSongs S, float* __restrict__ dx) {
+__global__ __launch_bounds__(256) void k_bt_hmean_bwd(const float* __restrict__ x, const float* __restrict__ dhm, BeatChunk S, float* __restrict__ dx) {
   const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
   if (gid >= (long long)S.rows * BEAT_DMODEL) return;
   const int r = (int)(gid >> 8), d = (int)(gid & 255);
-  const int s = bt_song_of(S.row0, S.n, r), T = S.frame0[s + 1] - S.frame0[s], t = (r - S.row0[s]) % T;
-  dx[gid] = x[gid] > 0.f ? dhm[((long long)S.frame0[s] + t) * BEAT_DMODEL + d] / (float)S.instr : 0.f;
+  int s, T, t;
+  beat_row_at(S, r, s, T, t);
+  dx[gid] = x[gid] > 0.f ? dhm[((long long)S.frame0[s] - S.frame_base + t) * BEAT_DMODEL + d] / (float)S.instr : 0.f;
 }
 // tm[s][d] = (sum over segments of BEAT_SEG frames, in order, of the segment's sum of relu(tacc[f][d]) in frame order) / T: the tempo head's input.  One workgroup per song.
-__global__ __launch_bounds__(256) void k_bt_tmean(const float* __restrict__ tacc, BtSongs S, float* __restrict__ tm) {
-  const int s = blockIdx.x, d = threadIdx.x, T = S.frame0[s + 1] - S.frame0[s];
-  const float* p = tacc + (long long)S.frame0[s] * BEAT_DMODEL + d;
+__global__ __launch_bounds__(256) void k_bt_tmean(const float* __restrict__ tacc, BeatChunk S, float* __restrict__ tm) {
+  const int s = S.first + blockIdx.x, d = threadIdx.x, T = S.frame0[s + 1] - S.frame0[s];
+  const float* p = tacc + (long long)(S.frame0[s] - S.frame_base) * BEAT_DMODEL + d;
   float tot = 0.f;
   for (int f0 = 0; f0 < T; f0 += BEAT_SEG) {
     const int f1 = f0 + BEAT_SEG < T ? f0 + BEAT_SEG : T;
@@ -519,15 +363,16 @@ __global__ __launch_bounds__(256) void k_bt_tmean(const float* __restrict__ tacc
     for (int f = f0; f < f1; ++f) sum += fmaxf(p[(long long)f * BEAT_DMODEL], 0.f);
     tot += sum;
   }
-  tm[(long long)s * BEAT_DMODEL + d] = tot / (float)T;
+  tm[(long long)blockIdx.x * BEAT_DMODEL + d] = tot / (float)T;
 }
 // dtf[f][d] = (tacc > 0) dtm[s][d] / T / instr
-__global__ __launch_bounds__(256) void k_bt_tmean_bwd(const float* __restrict__ tacc, const float* __restrict__ dtm, BtSongs S, float* __restrict__ dtf) {
+__global__ __launch_bounds__(256) void k_bt_tmean_bwd(const float* __restrict__ tacc, const float* __restrict__ dtm, BeatChunk S, float* __restrict__ dtf) {
   const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
   if (gid >= (long long)S.frames * BEAT_DMODEL) return;
   const int f = (int)(gid >> 8), d = (int)(gid & 255);
-  const int s = bt_song_of(S.frame0, S.n, f), T = S.frame0[s + 1] - S.frame0[s];
-  dtf[gid] = tacc[gid] > 0.f ? dtm[(long long)s * BEAT_DMODEL + d] / (float)T / (float)S.instr : 0.f;
+  int s, T, rb;
+  beat_frame_at(S, f, s, T, rb);
+  dtf[gid] = tacc[gid] > 0.f ? dtm[(long long)(s - S.first) * BEAT_DMODEL + d] / (float)T / (float)S.instr : 0.f;
 }
 __global__ void k_bt_relu(const float* __restrict__ x, float* __restrict__ y, long long n) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -593,21 +438,9 @@ __global__ __launch_bounds__(64) void k_bt_tempo_ce(const float* __restrict__ t,
 static inline dim3 bt_grid(long long n, int block = 256) { return dim3((unsigned)((n + block - 1) / block)); }
 
 #define BT_LAUNCHED() do { HIP_TRY(hipGetLastError()); return ETD_OK; } while (0)
-// ---- the front end, the means and the element kernels: one launcher per kernel, which the engine and the taps of include/etude_hip_debug.h both call
-int launch_bt_conv1(const float* feat, const BtSongs& S, const float* w, const float* b, float* c1, hipStream_t st) {
-  hipLaunchKernelGGL(k_bt_conv1, bt_grid((long long)S.rows * BEAT_W1 * BEAT_C1), dim3(256), 0, st, feat, S, w, b, c1);
-  BT_LAUNCHED();
-}
+// ---- this file's kernels: one launcher per kernel, which the engine and the taps of include/etude_hip_debug.h both call (the shared forward stages: beat.h)
 int launch_bt_patch2(const float* c1, int rows, float* x2, hipStream_t st) {
-  hipLaunchKernelGGL(k_bt_patch2, bt_grid((long long)rows * BT_C2_COLS * BEAT_K2), dim3(256), 0, st, c1, rows, x2);
-  BT_LAUNCHED();
-}
-int launch_bt_patch3(const float* c2, const BtSongs& S, float* x3, hipStream_t st) {
-  hipLaunchKernelGGL(k_bt_patch3, bt_grid((long long)S.rows * 3 * BEAT_K3), dim3(256), 0, st, c2, S, x3);
-  BT_LAUNCHED();
-}
-int launch_bt_pool3(const float* c3, int rows, float* x, hipStream_t st) {
-  hipLaunchKernelGGL(k_bt_pool3, bt_grid((long long)rows * BEAT_DMODEL), dim3(256), 0, st, c3, rows, x);
+  hipLaunchKernelGGL(k_bt_patch2, bt_grid((long long)rows * BEAT_C2_COLS * BEAT_K2), dim3(256), 0, st, c1, rows, x2);
   BT_LAUNCHED();
 }
 int launch_bt_repack(float* native, float* packed, int co_n, int ci_n, int kk_n, int dir, hipStream_t st) {
@@ -618,7 +451,7 @@ int launch_bt_pool3_bwd(const float* c3, const float* dx, int rows, float* dc3, 
   hipLaunchKernelGGL(k_bt_pool3_bwd, bt_grid((long long)rows * BEAT_DMODEL), dim3(256), 0, st, c3, dx, rows, dc3);
   BT_LAUNCHED();
 }
-int launch_bt_patch3_bwd(const float* c2, const float* dx3, const BtSongs& S, float* dc2, hipStream_t st) {
+int launch_bt_patch3_bwd(const float* c2, const float* dx3, const BeatChunk& S, float* dc2, hipStream_t st) {
   hipLaunchKernelGGL(k_bt_patch3_bwd, bt_grid((long long)S.rows * 8 * BEAT_C2), dim3(256), 0, st, c2, dx3, S, dc2);
   BT_LAUNCHED();
 }
@@ -626,27 +459,23 @@ int launch_bt_slice_sum(const float* part, int n_slices, int width, float* out, 
   hipLaunchKernelGGL(k_bt_slice_sum, bt_grid(width), dim3(256), 0, st, part, n_slices, width, width, out, (float*)nullptr, 0);
   BT_LAUNCHED();
 }
-int launch_bt_skipacc(const float* skip, const BtSongs& S, int first_layer, float* tacc, hipStream_t st) {
-  hipLaunchKernelGGL(k_bt_skipacc, bt_grid((long long)S.frames * 256), dim3(256), 0, st, skip, S, first_layer, tacc);
-  BT_LAUNCHED();
-}
-int launch_bt_dskip(const float* dx, const float* dtf, const BtSongs& S, float* dsk, hipStream_t st) {
+int launch_bt_dskip(const float* dx, const float* dtf, const BeatChunk& S, float* dsk, hipStream_t st) {
   hipLaunchKernelGGL(k_bt_dskip, bt_grid((long long)S.rows * 256), dim3(256), 0, st, dx, dtf, S, dsk);
   BT_LAUNCHED();
 }
-int launch_bt_hmean(const float* x, const BtSongs& S, float* hm, hipStream_t st) {
+int launch_bt_hmean(const float* x, const BeatChunk& S, float* hm, hipStream_t st) {
   hipLaunchKernelGGL(k_bt_hmean, bt_grid((long long)S.frames * 256), dim3(256), 0, st, x, S, hm);
   BT_LAUNCHED();
 }
-int launch_bt_hmean_bwd(const float* x, const float* dhm, const BtSongs& S, float* dx, hipStream_t st) {
+int launch_bt_hmean_bwd(const float* x, const float* dhm, const BeatChunk& S, float* dx, hipStream_t st) {
   hipLaunchKernelGGL(k_bt_hmean_bwd, bt_grid((long long)S.rows * 256), dim3(256), 0, st, x, dhm, S, dx);
   BT_LAUNCHED();
 }
-int launch_bt_tmean(const float* tacc, const BtSongs& S, float* tm, hipStream_t st) {
-  hipLaunchKernelGGL(k_bt_tmean, dim3(S.n), dim3(256), 0, st, tacc, S, tm);
+int launch_bt_tmean(const float* tacc, const BeatChunk& S, float* tm, hipStream_t st) {
+  hipLaunchKernelGGL(k_bt_tmean, dim3(S.count), dim3(256), 0, st, tacc, S, tm);
   BT_LAUNCHED();
 }
-int launch_bt_tmean_bwd(const float* tacc, const float* dtm, const BtSongs& S, float* dtf, hipStream_t st) {
+int launch_bt_tmean_bwd(const float* tacc, const float* dtm, const BeatChunk& S, float* dtf, hipStream_t st) {
   hipLaunchKernelGGL(k_bt_tmean_bwd, bt_grid((long long)S.frames * 256), dim3(256), 0, st, tacc, dtm, S, dtf);
   BT_LAUNCHED();
 }
@@ -665,12 +494,7 @@ int launch_bt_colsum(const float* dy, int ld, int M, int N, float* part, float* 
   hipLaunchKernelGGL(k_bt_colsum_part, dim3((N + 31) / 32, ns), dim3(256), 0, st, dy, ld, M, N, part);
   return launch_bt_slice_sum(part, ns, N, out, st);
 }
-int launch_bt_dattn_fwd(const float* qkv, const BtSongs& S, const float* Er, int dil, const float* xin, float* prob, float* skip, float* xout, hipStream_t st) {
-  hipLaunchKernelGGL(k_bt_dattn, bt_grid((long long)S.rows * 8), dim3(256), 0, st, qkv, S, Er, dil, xin, prob, skip, xout);
-  HIP_TRY(hipGetLastError());
-  return ETD_OK;
-}
-int launch_bt_dattn_bwd(const float* qkv, const float* prob, const float* dO, const BtSongs& S, const float* Er, int dil, float* dl, float* dqkv, float* part,
+int launch_bt_dattn_bwd(const float* qkv, const float* prob, const float* dO, const BeatChunk& S, const float* Er, int dil, float* dl, float* dqkv, float* part,
                         float* dEr, hipStream_t st) {
   hipLaunchKernelGGL(k_bt_dattn_dq, bt_grid((long long)S.rows * 8), dim3(256), 0, st, qkv, prob, dO, S, Er, dil, dl, dqkv);
   hipLaunchKernelGGL(k_bt_dattn_dkv, bt_grid((long long)S.rows * 8), dim3(256), 0, st, qkv, prob, dl, dO, S, dil, dqkv);
@@ -678,12 +502,7 @@ int launch_bt_dattn_bwd(const float* qkv, const float* prob, const float* dO, co
   hipLaunchKernelGGL(k_bt_der_part, dim3(ns), dim3(256), 0, st, qkv, dl, S.rows, part);
   return launch_bt_slice_sum(part, ns, 1280, dEr, st);
 }
-int launch_bt_iattn_fwd(const float* qkv, const BtSongs& S, float* ao, hipStream_t st) {
-  hipLaunchKernelGGL(k_bt_iattn, bt_grid((long long)S.frames * 8, 64), dim3(64), 0, st, qkv, S, ao);
-  HIP_TRY(hipGetLastError());
-  return ETD_OK;
-}
-int launch_bt_iattn_bwd(const float* qkv, const float* dao, const BtSongs& S, float* dqkv, hipStream_t st) {
+int launch_bt_iattn_bwd(const float* qkv, const float* dao, const BeatChunk& S, float* dqkv, hipStream_t st) {
   hipLaunchKernelGGL(k_bt_iattn_bwd, bt_grid((long long)S.frames * 8, 64), dim3(64), 0, st, qkv, dao, S, dqkv);
   HIP_TRY(hipGetLastError());
   return ETD_OK;
@@ -693,7 +512,7 @@ int launch_bt_fold2(const float* dpatch, const float* c1, int rows, float* dc1, 
   HIP_TRY(hipGetLastError());
   return ETD_OK;
 }
-int launch_bt_conv1_bwd(const float* feat, const float* dc1, const BtSongs& S, const float* w, const float* b, float* part, float* dw, float* db, hipStream_t st) {
+int launch_bt_conv1_bwd(const float* feat, const float* dc1, const BeatChunk& S, const float* w, const float* b, float* part, float* dw, float* db, hipStream_t st) {
   const int ns = (S.rows + BT_C1_ROWS - 1) / BT_C1_ROWS;
   hipLaunchKernelGGL(k_bt_conv1_bwd, dim3(ns), dim3(256), 0, st, feat, dc1, S, w, b, part);
   hipLaunchKernelGGL(k_bt_slice_sum, bt_grid(512), dim3(256), 0, st, part, ns, 512, 512, dw, db, 1);
@@ -770,19 +589,19 @@ static int n_instr_layers(int nlayers) { return nlayers > 6 ? 3 : nlayers > 3 ? 
 // scratch of launch_bt_colsum: the widest of its uses (d_hid or 768 columns over R rows, 64 over 24 R, 256 over 3 R, 300 over the songs)
 static long long btrain_cpart_floats(const etd_btrain_cfg& c) {
   const long long R = c.max_rows, W = c.d_hid > 768 ? c.d_hid : 768, S = BT_CS_ROWS;
-  return std::max(std::max((R + S - 1) / S * W, (BT_C2_COLS * R + S - 1) / S * 64), std::max((3 * R + S - 1) / S * 256, ((long long)c.max_seqs + S - 1) / S * BT_TEMPO));
+  return std::max(std::max((R + S - 1) / S * W, (BEAT_C2_COLS * R + S - 1) / S * 64), std::max((3 * R + S - 1) / S * 256, ((long long)c.max_seqs + S - 1) / S * BT_TEMPO));
 }
 
 // floats of saved activations and scratch for these arguments (the allocations of create, in its order)
 static long long btrain_ws_floats(const etd_btrain_cfg& c) {
   const long long R = c.max_rows, H = c.d_hid, n = c.max_seqs, nt = c.ntoken;
-  long long f = R * (BEAT_W1 * BEAT_C1 + BT_C2_COLS * BEAT_K2 + BT_C2_COLS * BEAT_C2 + 3 * BEAT_K3 + 3 * 256 + 256 + 256 + 256);      // c1 x2 c2o x3 c3o xL tacc hm
+  long long f = R * (BEAT_W1 * BEAT_C1 + BEAT_C2_COLS * BEAT_K2 + BEAT_C2_COLS * BEAT_C2 + 3 * BEAT_K3 + 3 * 256 + 256 + 256 + 256);      // c1 x2 c2o x3 c3o xL tacc hm
   f += n * 256 + R * nt + n * BT_TEMPO;                                                                                             // tm logits tlog
   f += (long long)c.nlayers * R * (256 + 768 + 40 + 256 + H + 4);
   f += (long long)n_instr_layers(c.nlayers) * R * (256 + 768 + 256 + 256 + H + 4);
-  f += R * (H + 256 * 4 + 768 + 40 + (long long)BT_C2_COLS * BEAT_K2 + 256 + 256);                                                     // wI tx dxn dx dsk dqkv dl big dtf dhm
+  f += R * (H + 256 * 4 + 768 + 40 + (long long)BEAT_C2_COLS * BEAT_K2 + 256 + 256);                                                     // wI tx dxn dx dsk dqkv dl big dtf dhm
   f += ((R + BT_C1_ROWS - 1) / BT_C1_ROWS) * 512 + ((R + BT_ER_ROWS - 1) / BT_ER_ROWS) * 1280;                                      // part (the larger is used; both counted)
-  f += std::max((3 * R + BT_SEG_ROWS - 1) / BT_SEG_ROWS * (256LL * BEAT_K3 + 256), (BT_C2_COLS * R + BT_SEG_ROWS - 1) / BT_SEG_ROWS * (64LL * BEAT_K2 + 64));      // seg
+  f += std::max((3 * R + BT_SEG_ROWS - 1) / BT_SEG_ROWS * (256LL * BEAT_K3 + 256), (BEAT_C2_COLS * R + BT_SEG_ROWS - 1) / BT_SEG_ROWS * (64LL * BEAT_K2 + 64));      // seg
   f += btrain_cpart_floats(c);
   f += n * 256 + R * nt * 3 + n * BT_TEMPO * 2 + n + 2 * nt;                                                                        // dtm dz cell ytgt dt ttgt trow fl
   return f;
@@ -851,7 +670,7 @@ extern "C" int etd_btrain_create(const etd_btrain_cfg* cfg, const char* const* n
   ETD_TRY_OR(fail, pl.alloc(&ps.partial, (size_t)TN_BLOCKS));
   const size_t R = (size_t)c.max_rows, ns = (size_t)c.max_seqs, nt = (size_t)c.ntoken;
   const size_t before = pl.mark();
-  ETD_TRY_OR(fail, pl.alloc(&d->c1, R * BEAT_W1 * BEAT_C1)); ETD_TRY_OR(fail, pl.alloc(&d->x2, R * BT_C2_COLS * BEAT_K2)); ETD_TRY_OR(fail, pl.alloc(&d->c2o, R * BT_C2_COLS * BEAT_C2));
+  ETD_TRY_OR(fail, pl.alloc(&d->c1, R * BEAT_W1 * BEAT_C1)); ETD_TRY_OR(fail, pl.alloc(&d->x2, R * BEAT_C2_COLS * BEAT_K2)); ETD_TRY_OR(fail, pl.alloc(&d->c2o, R * BEAT_C2_COLS * BEAT_C2));
   ETD_TRY_OR(fail, pl.alloc(&d->x3, R * 3 * BEAT_K3)); ETD_TRY_OR(fail, pl.alloc(&d->c3o, R * 3 * D)); ETD_TRY_OR(fail, pl.alloc(&d->xL, R * D));
   ETD_TRY_OR(fail, pl.alloc(&d->tacc, R * D)); ETD_TRY_OR(fail, pl.alloc(&d->hm, R * D)); ETD_TRY_OR(fail, pl.alloc(&d->tm, ns * D));
   ETD_TRY_OR(fail, pl.alloc(&d->logits, R * nt)); ETD_TRY_OR(fail, pl.alloc(&d->tlog, ns * BT_TEMPO));
@@ -869,9 +688,9 @@ extern "C" int etd_btrain_create(const etd_btrain_cfg* cfg, const char* const* n
   }
   ETD_TRY_OR(fail, pl.alloc(&d->wI, R * H)); ETD_TRY_OR(fail, pl.alloc(&d->tx, R * D)); ETD_TRY_OR(fail, pl.alloc(&d->dxn, R * D)); ETD_TRY_OR(fail, pl.alloc(&d->dx, R * D));
   ETD_TRY_OR(fail, pl.alloc(&d->dsk, R * D)); ETD_TRY_OR(fail, pl.alloc(&d->dqkv, R * 768)); ETD_TRY_OR(fail, pl.alloc(&d->dl, R * 40));
-  ETD_TRY_OR(fail, pl.alloc(&d->big, R * BT_C2_COLS * BEAT_K2));      // dx3 [3 R][1152], then conv2's dpatch [24 R][384], then dc1 [R][42][32]: each is dead when the next is written
+  ETD_TRY_OR(fail, pl.alloc(&d->big, R * BEAT_C2_COLS * BEAT_K2));      // dx3 [3 R][1152], then conv2's dpatch [24 R][384], then dc1 [R][42][32]: each is dead when the next is written
   ETD_TRY_OR(fail, pl.alloc(&d->part, std::max((R + BT_C1_ROWS - 1) / BT_C1_ROWS * 512, (R + BT_ER_ROWS - 1) / BT_ER_ROWS * 1280)));
-  ETD_TRY_OR(fail, pl.alloc(&d->seg, std::max((3 * R + BT_SEG_ROWS - 1) / BT_SEG_ROWS * (D * BEAT_K3 + D), (BT_C2_COLS * R + BT_SEG_ROWS - 1) / BT_SEG_ROWS * (size_t)(64 * BEAT_K2 + 64))));
+  ETD_TRY_OR(fail, pl.alloc(&d->seg, std::max((3 * R + BT_SEG_ROWS - 1) / BT_SEG_ROWS * (D * BEAT_K3 + D), (BEAT_C2_COLS * R + BT_SEG_ROWS - 1) / BT_SEG_ROWS * (size_t)(64 * BEAT_K2 + 64))));
   ETD_TRY_OR(fail, pl.alloc(&d->cpart, (size_t)btrain_cpart_floats(c)));
   ETD_TRY_OR(fail, pl.alloc(&d->dtf, R * D)); ETD_TRY_OR(fail, pl.alloc(&d->dhm, R * D)); ETD_TRY_OR(fail, pl.alloc(&d->dtm, ns * D));
   ETD_TRY_OR(fail, pl.alloc(&d->dz, R * nt)); ETD_TRY_OR(fail, pl.alloc(&d->cell, R * nt)); ETD_TRY_OR(fail, pl.alloc(&d->ytgt, R * nt));
@@ -1023,8 +842,7 @@ extern "C" int etd_btrain_loss_backward(etd_btrain* d, const float* feat_dev, in
   HIP_TRY(hipMemcpyAsync(d->ytgt, beat_targets, (size_t)F * nt * 4, hipMemcpyHostToDevice, st));
   if (ntempo) HIP_TRY(hipMemcpyAsync(d->ttgt, tempo_targets, (size_t)n_seq * BT_TEMPO * 4, hipMemcpyHostToDevice, st));
   HIP_TRY(hipStreamSynchronize(st));                    // (the host tables are this call's memory)
-  BtSongs S;
-  S.row0 = d->ints; S.frame0 = d->ints + n_seq + 1; S.n = n_seq; S.rows = R; S.frames = F; S.instr = ni;
+  const BeatChunk S = beat_whole_call(d->ints, d->ints + n_seq + 1, n_seq, R, F, ni);
   const int* d_has = d->ints + 2 * (n_seq + 1);
   float *P = d->ps.P, *G = d->ps.G;
   const long long RD = (long long)R * 256, RH = (long long)R * H;
@@ -1037,13 +855,13 @@ extern "C" int etd_btrain_loss_backward(etd_btrain* d, const float* feat_dev, in
     ProfScope ps("btrain_forward", st);
     ETD_TRY(launch_bt_repack(P + d->c2w, d->w2p, 64, 32, 12, 0, st));
     ETD_TRY(launch_bt_repack(P + d->c3w, d->w3p, 256, 64, 18, 0, st));
-    ETD_TRY(launch_bt_conv1(feat_dev, S, P + d->c1w, P + d->c1b, d->c1, st));
+    ETD_TRY(launch_beat_conv1(feat_dev, S, P + d->c1w, P + d->c1b, d->c1, st));
     ETD_TRY(launch_bt_patch2(d->c1, R, d->x2, st));
-    BT_GEMM(ETD_TG_NT, R * BT_C2_COLS, 64, BEAT_K2, d->x2, BEAT_K2, d->w2p, BEAT_K2, P + d->c2b, d->c2o, 64, false, st);
-    ETD_TRY(launch_bt_patch3(d->c2o, S, d->x3, st));
+    BT_GEMM(ETD_TG_NT, R * BEAT_C2_COLS, 64, BEAT_K2, d->x2, BEAT_K2, d->w2p, BEAT_K2, P + d->c2b, d->c2o, 64, false, st);
+    ETD_TRY(launch_beat_patch3(d->c2o, BEAT_C2_COLS, S, d->x3, st));
     BT_GEMM(ETD_TG_NT, R * 3, 256, BEAT_K3, d->x3, BEAT_K3, d->w3p, BEAT_K3, P + d->c3b, d->c3o, 256, false, st);
     float* x0 = d->st[0].xin;
-    ETD_TRY(launch_bt_pool3(d->c3o, R, x0, st));
+    ETD_TRY(launch_beat_pool3(d->c3o, R, x0, st));
     HIP_TRY(hipGetLastError());
     int il = 0;
     for (int l = 0; l < L; ++l) {
@@ -1053,8 +871,8 @@ extern "C" int etd_btrain_loss_backward(etd_btrain* d, const float* feat_dev, in
       float* xnext = has_i ? d->si[il].xin : l + 1 < L ? d->st[l + 1].xin : d->xL;
       launch_tln_fwd(a.xin, R, 256, 1e-5f, a.m1, a.r1, P + y.n1w, P + y.n1b, d->tx, nullptr, nullptr, nullptr, st);
       BT_GEMM(ETD_TG_NT, R, 768, 256, d->tx, 256, P + y.qkv_w, 256, P + y.qkv_b, a.qkv, 768, false, st);
-      ETD_TRY(launch_bt_dattn_fwd(a.qkv, S, P + y.Er, 1 << l, a.xin, a.prob, d->dsk, a.xat, st));
-      ETD_TRY(launch_bt_skipacc(d->dsk, S, l == 0 ? 1 : 0, d->tacc, st));
+      ETD_TRY(launch_beat_dattn_train(a.qkv, S, P + y.Er, 1 << l, a.xin, a.prob, d->dsk, a.xat, st));
+      ETD_TRY(launch_beat_skipacc(d->dsk, S, l == 0 ? 1 : 0, d->tacc, st));
       launch_tln_fwd(a.xat, R, 256, 1e-5f, a.m2, a.r2, P + y.n2w, P + y.n2b, d->tx, nullptr, nullptr, nullptr, st);
       BT_GEMM(ETD_TG_NT, R, H, 256, d->tx, 256, P + y.l1w, 256, P + y.l1b, a.pre, H, false, st);
       launch_tgelu(a.pre, d->wI, RH, st);
@@ -1066,7 +884,7 @@ extern "C" int etd_btrain_loss_backward(etd_btrain* d, const float* feat_dev, in
         float* xn2 = l + 1 < L ? d->st[l + 1].xin : d->xL;
         launch_tln_fwd(b.xin, R, 256, 1e-5f, b.m1, b.r1, P + z.n1w, P + z.n1b, d->tx, nullptr, nullptr, nullptr, st);
         BT_GEMM(ETD_TG_NT, R, 768, 256, d->tx, 256, P + z.in_w, 256, P + z.in_b, b.qkv, 768, false, st);
-        ETD_TRY(launch_bt_iattn_fwd(b.qkv, S, b.ao, st));
+        ETD_TRY(launch_beat_iattn(b.qkv, S, b.ao, st));
         ETD_TRY(copy(b.xat, b.xin, RD));
         BT_GEMM(ETD_TG_NT, R, 256, 256, b.ao, 256, P + z.out_w, 256, P + z.out_b, b.xat, 256, true, st);
         launch_tln_fwd(b.xat, R, 256, 1e-5f, b.m2, b.r2, P + z.n2w, P + z.n2b, d->tx, nullptr, nullptr, nullptr, st);
@@ -1132,9 +950,9 @@ extern "C" int etd_btrain_loss_backward(etd_btrain* d, const float* feat_dev, in
     ETD_TRY(launch_bt_repack(G + d->c3w, d->dw3p, 256, 64, 18, 1, st));
     float* dc2 = d->x3;                                // [24 R][64]: x3 [3 R][1152] has been read for the last time
     ETD_TRY(launch_bt_patch3_bwd(d->c2o, d->big, S, dc2, st));
-    ETD_TRY(launch_bt_conv_wgrad(64, BEAT_K2, BT_C2_COLS * R, dc2, d->x2, d->seg, d->dw2p, st));
-    ETD_TRY(launch_bt_colsum(dc2, 64, BT_C2_COLS * R, 64, d->cpart, G + d->c2b, st));
-    BT_GEMM(ETD_TG_NN, BT_C2_COLS * R, BEAT_K2, 64, dc2, 64, d->w2p, BEAT_K2, nullptr, d->big, BEAT_K2, false, st);
+    ETD_TRY(launch_bt_conv_wgrad(64, BEAT_K2, BEAT_C2_COLS * R, dc2, d->x2, d->seg, d->dw2p, st));
+    ETD_TRY(launch_bt_colsum(dc2, 64, BEAT_C2_COLS * R, 64, d->cpart, G + d->c2b, st));
+    BT_GEMM(ETD_TG_NN, BEAT_C2_COLS * R, BEAT_K2, 64, dc2, 64, d->w2p, BEAT_K2, nullptr, d->big, BEAT_K2, false, st);
     ETD_TRY(launch_bt_repack(G + d->c2w, d->dw2p, 64, 32, 12, 1, st));
     float* dc1 = d->x2;                                // [R][42][32]: the patches have been read for the last time
     ETD_TRY(launch_bt_fold2(d->big, d->c1, R, dc1, st));
@@ -1200,7 +1018,7 @@ extern "C" int etd_btrain_write(etd_btrain* d, const char* name, int which, cons
 namespace {
 // the song tables of a tap: checked on the host, then uploaded to a block of its own (freed by the tap after its stream has drained)
 struct TapSongs {
-  BtSongs S;
+  BeatChunk S;
   int* dev = nullptr;
   int make(const char* who, int n_seq, const int64_t* T_host, int instr, hipStream_t st) {
     if (n_seq < 1 || n_seq > 65535 || !T_host) ETD_FAIL(ETD_EINVAL, "%s: n_seq = %d or no lengths", who, n_seq);
@@ -1217,7 +1035,7 @@ struct TapSongs {
     HIP_TRY(hipMalloc((void**)&dev, tab.size() * 4));
     HIP_TRY(hipMemcpyAsync(dev, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));
-    S.row0 = dev; S.frame0 = dev + n_seq + 1; S.n = n_seq; S.rows = (int)rows; S.frames = (int)frames; S.instr = instr;
+    S = beat_whole_call(dev, dev + n_seq + 1, n_seq, (int)rows, (int)frames, instr);
     return ETD_OK;
   }
   int done(int rc, hipStream_t st) {
@@ -1236,7 +1054,7 @@ extern "C" int etd_debug_btrain_dattn(int n_seq, const int64_t* T_host, int inst
   hipStream_t st = (hipStream_t)stream;
   TapSongs t;
   ETD_TRY(t.make("etd_debug_btrain_dattn", n_seq, T_host, instr, st));
-  int rc = launch_bt_dattn_fwd(qkv_dev, t.S, Er_dev, 1 << layer, xin_dev, prob_dev, skip_dev, xout_dev, st);
+  int rc = launch_beat_dattn_train(qkv_dev, t.S, Er_dev, 1 << layer, xin_dev, prob_dev, skip_dev, xout_dev, st);
   if (rc == ETD_OK && dO_dev) rc = launch_bt_dattn_bwd(qkv_dev, prob_dev, dO_dev, t.S, Er_dev, 1 << layer, dl_dev, dqkv_dev, part_dev, dEr_dev, st);
   return t.done(rc, st);
 }
@@ -1246,7 +1064,7 @@ extern "C" int etd_debug_btrain_iattn(int n_seq, const int64_t* T_host, int inst
   hipStream_t st = (hipStream_t)stream;
   TapSongs t;
   ETD_TRY(t.make("etd_debug_btrain_iattn", n_seq, T_host, instr, st));
-  int rc = launch_bt_iattn_fwd(qkv_dev, t.S, ao_dev, st);
+  int rc = launch_beat_iattn(qkv_dev, t.S, ao_dev, st);
   if (rc == ETD_OK && dao_dev) rc = launch_bt_iattn_bwd(qkv_dev, dao_dev, t.S, dqkv_dev, st);
   return t.done(rc, st);
 }
@@ -1297,8 +1115,8 @@ extern "C" int etd_debug_btrain_front_fwd(int which, int n_seq, const int64_t* T
   hipStream_t st = (hipStream_t)stream;
   TapSongs t;
   ETD_TRY(t.make("etd_debug_btrain_front_fwd", n_seq, T_host, instr, st));
-  const int rc = which == 0 ? launch_bt_conv1(in_dev, t.S, w_dev, b_dev, out_dev, st) : which == 1 ? launch_bt_patch2(in_dev, t.S.rows, out_dev, st)
-               : which == 2 ? launch_bt_patch3(in_dev, t.S, out_dev, st) : launch_bt_pool3(in_dev, t.S.rows, out_dev, st);
+  const int rc = which == 0 ? launch_beat_conv1(in_dev, t.S, w_dev, b_dev, out_dev, st) : which == 1 ? launch_bt_patch2(in_dev, t.S.rows, out_dev, st)
+               : which == 2 ? launch_beat_patch3(in_dev, BEAT_C2_COLS, t.S, out_dev, st) : launch_beat_pool3(in_dev, t.S.rows, out_dev, st);
   return t.done(rc, st);
 }
 
@@ -1318,7 +1136,7 @@ extern "C" int etd_debug_btrain_repack(int dir, int co, int ci, int kk, float* n
 }
 
 extern "C" int etd_debug_btrain_colsum(const float* dy_dev, int ld, int M, int N, float* part_dev, float* out_dev, void* stream) {
-  if (M < 1 || M > BT_C2_COLS * (1 << 17) || N < 1 || N > 8192 || ld < N || !dy_dev || !part_dev || !out_dev)
+  if (M < 1 || M > BEAT_C2_COLS * (1 << 17) || N < 1 || N > 8192 || ld < N || !dy_dev || !part_dev || !out_dev)
     ETD_FAIL(ETD_EINVAL, "etd_debug_btrain_colsum: M = %d (1 .. 24 x 2^17), N = %d (1 .. 8192), ld = %d (>= N) or a null argument", M, N, ld);
   return launch_bt_colsum(dy_dev, ld, M, N, part_dev, out_dev, (hipStream_t)stream);
 }
@@ -1341,7 +1159,7 @@ extern "C" int etd_debug_btrain_means(int which, int n_seq, const int64_t* T_hos
   ETD_TRY(t.make("etd_debug_btrain_means", n_seq, T_host, instr, st));
   int rc;
   switch (which) {
-    case 0: rc = launch_bt_skipacc(a_dev, t.S, first_layer, out_dev, st); break;
+    case 0: rc = launch_beat_skipacc(a_dev, t.S, first_layer, out_dev, st); break;
     case 1: rc = launch_bt_dskip(a_dev, b_dev, t.S, out_dev, st); break;
     case 2: rc = launch_bt_hmean(a_dev, t.S, out_dev, st); break;
     case 3: rc = launch_bt_hmean_bwd(a_dev, b_dev, t.S, out_dev, st); break;
@@ -1361,7 +1179,7 @@ extern "C" int etd_debug_btrain_relu(const float* x_dev, long long n, float* y_d
 }
 
 extern "C" int etd_debug_btrain_conv_wgrad(int M, int N, int K, const float* dY_dev, const float* X_dev, float* seg_dev, float* dw_dev, void* stream) {
-  if (M < 1 || N < 1 || K < 1 || K > BT_C2_COLS * (1 << 17) || (long long)M * N > (1 << 24) || !dY_dev || !X_dev || !seg_dev || !dw_dev)
+  if (M < 1 || N < 1 || K < 1 || K > BEAT_C2_COLS * (1 << 17) || (long long)M * N > (1 << 24) || !dY_dev || !X_dev || !seg_dev || !dw_dev)
     ETD_FAIL(ETD_EINVAL, "etd_debug_btrain_conv_wgrad: M x N = %d x %d (each >= 1, at most 2^24 elements), K = %d (1 .. 24 x 2^17) or a null argument", M, N, K);
   return launch_bt_conv_wgrad(M, N, K, dY_dev, X_dev, seg_dev, dw_dev, (hipStream_t)stream);
 }
